@@ -1114,6 +1114,25 @@ def run_ops_multi(args, torch, bsk, _lib, lib, check, dev, local, rank, world, b
     return ops
 
 
+def dump_stats_outputs(out_dir, vec, m, info, text):
+    """--dump-outputs: what the caller of the timed `stats` step receives, as float64 .npy files (every count is far below
+    2**53, so the values are exact) -- the stats vector the kernels wrote (include/bsk.h; after the all-reduce on N ranks),
+    the merged map[int64]int64 sorted by key, the StatInfo fields and the bytes of the text row.  Well under 1 MB in all."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    ks = sorted(m)
+    fields = [f for f, _ in info._fields_ if f != "type"]
+    arrays = {
+        "stats_vector": vec.double().cpu().numpy(),
+        "stats_map_keys": np.array(ks, dtype=np.float64),
+        "stats_map_values": np.array([m[k] for k in ks], dtype=np.float64),
+        "stats_info": np.array([getattr(info, f) for f in fields], dtype=np.float64),  # in the order of StatInfo._fields_
+        "stats_text": np.frombuffer(text.encode(), dtype=np.uint8).astype(np.float32),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1132,7 +1151,11 @@ def main():
     ap.add_argument("--launch-check", action="store_true",
                     help="only prove that --gpus N ranks start and reduce together (backend from BSK_BENCH_BACKEND, "
                          "default nccl; the CPU test suite runs it with gloo), print one JSON line and exit")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step of the "
+                    "headline `stats` returned (stats vector, merged map, StatInfo, text row) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     want_world = max(1, args.gpus)
 
     # ---- self-launch: `python bench.py --gpus N` starts N ranks itself (one process per GPU); under torchrun
@@ -1247,6 +1270,7 @@ def main():
         return op, vec
 
     reduce_ev = [] if dist_on else None  # (start, stop) HIP events around the all-reduce of every timed step
+    last = {}  # the StatInfo of the latest step (--dump-outputs)
 
     def one_step(op, vec, nb=None):
         nb = nbytes if nb is None else nb
@@ -1275,6 +1299,7 @@ def main():
         info = bsk.api._finalize(op, m)
         buf = C.create_string_buffer(4096)
         check(lib.bsk_stats_string(op.ctx, b"input0", b"N/A", C.byref(info), buf, len(buf)), op.ctx)
+        last["info"] = info
         return m, buf.value.decode()
 
     def timed(op, vec, steps, warmup, nb=None):
@@ -1317,6 +1342,8 @@ def main():
     dt, m, text, k_ms, p_ms, reduce_ms, per_rank = timed(op, vec, args.steps, args.warmup)
     want_row = "input0\tN/A\tDNA\t%d\t%d\t150\t150.0\t150" % (total_rec, total_rec * 150)
     verified = (m.get(150) == total_rec) and text.splitlines()[1] == want_row
+    if args.dump_outputs and rank == 0:
+        dump_stats_outputs(args.dump_outputs, vec, m, last["info"], text)
     op.close()
 
     # secondary line: stats -a (Q20/Q30/gap counters on top), same timing recipe

@@ -34,6 +34,29 @@ def test_bench_single_gpu_line_small():
     assert d["unit"] == "M records/s" and d["higher_is_better"] is True
 
 
+def test_bench_dump_outputs_repeat(tmp_path):
+    """--dump-outputs: the last timed step's result as .npy files, the same from run to run with the same arguments"""
+    import numpy as np
+    names = ["stats_info", "stats_map_keys", "stats_map_values", "stats_text", "stats_vector"]
+    runs = []
+    for k in range(2):
+        out = tmp_path / ("run%d" % k)
+        d = run_bench(["--gb", "1", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-scaling-model",
+                       "--dump-outputs", str(out)])
+        assert d["steps"] == 4 and d["ms_per_step"] > 0 and d["bit_exact_vs_expected_row"] is True
+        assert sorted(p.name for p in out.iterdir()) == [n + ".npy" for n in names]
+        runs.append({n: np.load(out / (n + ".npy")) for n in names})
+    a, b = runs
+    for n in names:
+        assert a[n].dtype in (np.float32, np.float64) and np.array_equal(a[n], b[n]), n
+    records = d["config"]["records"]
+    v = a["stats_vector"]   # include/bsk.h: [3] records, [6] sum of lengths, [8 + L] records of length L
+    assert v[3] == records and v[6] == 150 * records and v[8 + 150] == records
+    assert dict(zip(a["stats_map_keys"], a["stats_map_values"]))[150] == records
+    assert a["stats_info"][0] == records and a["stats_info"][1] == 150 * records   # num, len_sum
+    assert bytes(a["stats_text"].astype(np.uint8)).decode().splitlines()[1].startswith("input0\tN/A\tDNA\t%d\t" % records)
+
+
 @pytest.mark.parametrize("n", [2, 3])
 def test_bench_n_ranks_sharing_one_gpu(n):
     d = run_bench(["--gpus", str(n), "--gb", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--ops-scale", "0.02",

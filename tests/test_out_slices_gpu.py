@@ -116,7 +116,7 @@ def test_pieces_of_a_large_result(name, opts, nrec, tmp_path):
     op.close()
 
 
-def test_a_result_dies_with_the_next_run_and_exceptions_keep_one_block():
+def test_a_result_dies_with_the_next_run_and_exceptions_keep_one_block(tmp_path):
     import torch
     data = fastq(5, 3000)
     t = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda()
@@ -131,7 +131,7 @@ def test_a_result_dies_with_the_next_run_and_exceptions_keep_one_block():
     op.close()
     # -d / -D read the scratch arrays again, '+' lines that repeat the name are re-formatted: one block, whatever the switch says
     plus = data.replace(b"\n+\n", b"\n+read\n", 1)
-    for d, o in ((data, {"BySeq": True, "DupNumFile": "/tmp/bsk_slices_dupnum"}), (plus, {"BySeq": True})):
+    for d, o in ((data, {"BySeq": True, "DupNumFile": str(tmp_path / "dupnum")}), (plus, {"BySeq": True})):
         tt = torch.frombuffer(bytearray(d), dtype=torch.uint8).cuda()
         op, out = run("RmDup", o, tt, "slices")
         assert out.n_segments == 0 and host(op, out) == oracle.rmdup(d, True, json.dumps({"BySeq": True}))
