@@ -123,6 +123,7 @@ SIGNATURES = {
     "bsk_rmdup_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, _vp, _p(Out)]),
     "bsk_fq2fa_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, _vp, _p(Out)]),
     "bsk_rename_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, _vp, _p(Out)]),
+    "bsk_replace_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, _vp, _p(Out)]),
     "bsk_sort_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, _vp, _p(Out)]),
     "bsk_pair_run": (_i, [_vp, _vp, _sz, _sz, _i, _i, _vp, _p(Out)]),
     "bsk_concat_run": (_i, [_vp, _vp, _sz, _sz, _i, _i, _vp, _p(Out)]),
@@ -141,6 +142,7 @@ SIGNATURES = {
     "bsk_host_alloc": (_vp, [_sz]),
     "bsk_host_free": (None, [_vp]),
     "bsk_regex_match": (_i, [C.c_char_p, _vp, _sz, _p(C.c_int)]),
+    "bsk_regex_replace": (_i, [C.c_char_p, C.c_char_p, _vp, _sz, _vp, _sz, _p(_sz)]),
     "bsk_rmdup_finish": (_i, [_vp]),
     "bsk_rmdup_dist_keys": (_i, [_vp, _vp, _sz, _i, _vp, _p(C.c_uint64)]),
     "bsk_rmdup_dist_pack": (_i, [_vp, C.c_uint64, _i, _vp, _p(C.c_uint64), _vp]),

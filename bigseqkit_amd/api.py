@@ -10,7 +10,7 @@ import os
 
 from . import _lib
 from ._lib import lib, check, BskError, FORMAT_FASTA, FORMAT_FASTQ
-from .options import SeqKitStatsOptions, SeqKitSeqOptions, SeqKitGrepOptions, SeqKitSubseqOptions, SeqKitTranslateOptions, SeqKitRmDupOptions, SeqKitLocateOptions, SeqKitFq2FaOptions, SeqKitHeadOptions, SeqKitDuplicateOptions, SeqKitRenameOptions, SeqKitSortOptions, SeqKitFaidxOptions, SeqKitPairOptions, SeqKitCommonOptions, SeqKitConcatOptions
+from .options import SeqKitStatsOptions, SeqKitSeqOptions, SeqKitGrepOptions, SeqKitSubseqOptions, SeqKitTranslateOptions, SeqKitRmDupOptions, SeqKitLocateOptions, SeqKitFq2FaOptions, SeqKitHeadOptions, SeqKitDuplicateOptions, SeqKitRenameOptions, SeqKitSortOptions, SeqKitFaidxOptions, SeqKitPairOptions, SeqKitCommonOptions, SeqKitConcatOptions, SeqKitReplaceOptions
 
 
 class SeqFrame:
@@ -263,6 +263,11 @@ def Duplicate(input, o=None, device=0):
 def Rename(input, o=None, device=0):
     """bigseqkit/rename.go:34-60 (ordinals count over the whole dataframe: several shards are joined, like RmDup)"""
     return _run_records("Rename", lib.bsk_rename_run, _one_shard(input), o or SeqKitRenameOptions(), device)[0]
+
+
+def Replace(input, o, device=0):
+    """bigseqkit/replace.go:39-60 (MapPartitions: {nr} counts the records of each shard from 1)"""
+    return _run_records("Replace", lib.bsk_replace_run, input, o or SeqKitReplaceOptions(), device)[0]
 
 
 def Sort(input, o=None, device=0):

@@ -193,6 +193,7 @@ int bsk_create(const char* op_name_, const char* opts_json, int device, bsk_ctx*
             case Op::Sort: validate_sort_opts(c); break;
             case Op::Faidx: validate_faidx_opts(c); break;
             case Op::Common: validate_common_opts(c); break;
+            case Op::Replace: validate_replace_opts(c); break;
             default: break;  // validated by the op's own module once it is built
         }
     } catch (const std::exception& e) {
@@ -260,6 +261,7 @@ void bsk_destroy(bsk_ctx* c) {
         if (c->d_seg_first) hipFree(c->d_seg_first);
         if (c->d_names_aux) hipFree(c->d_names_aux);
         if (c->d_id_prog) hipFree(c->d_id_prog);
+        bsk::replace_free(c);
         if (c->d_vm_progs) hipFree(c->d_vm_progs);
         if (c->d_id_off) hipFree(c->d_id_off);
         if (c->d_id_len) hipFree(c->d_id_len);
@@ -1137,6 +1139,14 @@ int bsk_rename_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int f
     if (out) { out->d_seg_src = nullptr; out->d_seg_off = nullptr; out->n_segments = 0; }
     (void)pid;
     return run_record_op(c, Op::Rename, "Rename", rename_run_device, shard, n, on_device, format, stream, out);
+}
+
+int bsk_replace_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,
+                    bsk_out* out) {
+    if (out) { out->d_seg_src = nullptr; out->d_seg_off = nullptr; out->n_segments = 0; }
+    (void)pid;
+    if (c) c->nr_base = 0;  // {nr} counts the records of this call from 1
+    return run_record_op(c, Op::Replace, "Replace", replace_run_device, shard, n, on_device, format, stream, out);
 }
 
 int bsk_fq2fa_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,

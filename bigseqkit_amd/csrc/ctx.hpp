@@ -28,7 +28,7 @@
 struct bsk_tuning {
     static const char* const* names() {
         static const char* const N[] = {"filter", "grep_shiftand", "index", "locate_nopre", "long_bytes", "min_range_bytes", "names",
-                                        "names_scale", "out", "pin_alphabet", "ranges_per_wave", "rmdup", "rmdup_buckets", "rmdup_hash", "rmdup_k1_bits", "rmdup_k2_bits", "rmdup_keys", "rmdup_place", "rmdup_xcheck", "rmdup_xlocal", "scan", "segcopy",
+                                        "names_scale", "out", "pin_alphabet", "ranges_per_wave", "replace", "rmdup", "rmdup_buckets", "rmdup_hash", "rmdup_k1_bits", "rmdup_k2_bits", "rmdup_keys", "rmdup_place", "rmdup_xcheck", "rmdup_xlocal", "scan", "segcopy",
                                         "sort", "stage_bytes", "stats_a", "stats_fasta", "subseq", "subseq_scale", "text", "translate", "translate_index", "translate_probe", "translate_stream", "tr_lanes", nullptr};
         return N;
     }
@@ -131,6 +131,11 @@ struct bsk_ctx {
     uint32_t* d_id_off = nullptr;
     uint32_t* d_id_len = nullptr;
     uint64_t id_cap = 0;
+    // replace (ops_host_replace.cpp): program, template, key-value table and their device copies; {nr} of the next
+    // record is nr_base + 1 (reset by bsk_replace_run and by bsk_run_to_store unless pin_alphabet is set, advanced by every
+    // shard or chunk that replace_run_device completes)
+    struct ReplaceState* repl = nullptr;
+    uint64_t nr_base = 0;
     uint64_t avg_record_bytes = 0;   // bytes per record in the head of the last indexed shard (0: unknown)
     bsk::RecordTable sparse;         // one-pass index: per-range slices, compacted into `table`
     uint64_t* d_range_count = nullptr;  // [cap_ranges]

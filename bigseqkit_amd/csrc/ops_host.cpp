@@ -675,7 +675,7 @@ int finish_sizes(bsk_ctx* c, hipStream_t st, uint64_t* total, uint64_t* kept) {
 // records that leave exactly as they stand in the shard (4-line FASTQ, everything printed, nothing rewritten)
 static bool records_verbatim(const SeqParams& P) {
     return P.fastq && !P.fasta_out && P.print_name && P.print_seq && P.print_qual && !P.qual_only && !P.only_id && !P.reverse && !P.use_lut &&
-           !P.region_on && !P.feat_on && !P.remove_gaps;  // (rename: per record, k_seg_build)
+           !P.region_on && !P.feat_on && !P.remove_gaps && !P.rep_len;  // (rename: per record, k_seg_build)
 }
 
 // Round 6 (results as ordered slices, include/bsk.h bsk_out.d_seg_*): the records an operator KEEPS, verbatim, are segments of

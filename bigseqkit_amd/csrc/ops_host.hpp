@@ -55,6 +55,9 @@ int rmdup_dist_flagged_settle(bsk_ctx* c, const void* all, size_t n, hipStream_t
 int rmdup_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, bsk_out* out);
 void validate_locate_opts(bsk_ctx* c);
 int locate_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, bsk_out* out);
+void validate_replace_opts(bsk_ctx* c);
+int replace_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, bsk_out* out);
+void replace_free(bsk_ctx* c);
 void validate_records_opts(bsk_ctx* c);
 int range_resolve(bsk_ctx* c, int64_t n_records);
 int fq2fa_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, bsk_out* out);

@@ -250,6 +250,7 @@ __global__ __launch_bounds__(256) void k_seq_size(const uint8_t* __restrict__ bu
             if (P.only_id) hl = id_span_rec(t, i, r.head, r.head_len, P.id_mode, &off, P.buf_end);
             HeadSrc H;
             if (rename_head(t, P, i, r.head, r.head_len, &H)) hl = H.len;
+            if (P.rep_len && P.rep_len[i]) hl = P.rep_len[i] - 1u;
             n += (P.print_seq ? 1u : 0u) + hl + 1u;
         }
         if (P.print_seq) n += wrapped_len(kept, P.line_width) + 1u;
@@ -313,6 +314,11 @@ __global__ __launch_bounds__(256) void k_seq_emit(const uint8_t* __restrict__ bu
     HeadSrc HS;
     HS.head = r.head; HS.suffix = suffix; HS.hoff = hoff; HS.id_len = id_len; HS.ord = 0; HS.ndig = 0; HS.desc_off = 0;
     if (rename_head(t, P, g, r.head, r.head_len, &HS)) hl = HS.len;
+    const bool staged = P.rep_len && P.rep_len[g];
+    if (staged) {  // replace: the new head, whole
+        HS.head = P.rep_stage + P.rep_off[g]; HS.hoff = 0; HS.suffix = nullptr;
+        hl = HS.id_len = P.rep_len[g] - 1u;
+    }
     HS.len = hl;
     const uint32_t a = P.print_name ? (P.print_seq ? 1u : 0u) + hl + 1u : 0u;
     // random access to the bases: contiguous text, or a wrapped FASTA record through the text view
@@ -336,7 +342,7 @@ __global__ __launch_bounds__(256) void k_seq_emit(const uint8_t* __restrict__ bu
     // Whole FASTQ record printed unchanged (grep / rmdup / plain seq): Format() reproduces the
     // record text byte for byte when the '+' line is bare, so copy it 16 bytes per lane.
     if (fast && P.fastq && P.print_name && P.print_seq && P.print_qual && !P.qual_only && !P.only_id && !reverse &&
-        !use_lut && !P.region_on && !P.feat_on && t.aux[g] == 1 && HS.ord == 0) {
+        !use_lut && !P.region_on && !P.feat_on && t.aux[g] == 1 && HS.ord == 0 && !staged) {
         const uint8_t* src = buf + t.start[g];
         const uint32_t body = n - 1;  // everything but the final newline, which the shard may lack
         const uint32_t hi = last_byte(0, body);

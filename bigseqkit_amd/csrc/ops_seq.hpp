@@ -58,6 +58,10 @@ struct SeqParams {  // SeqTransform options after Before() (bigseqkit-lib/seq.go
     const uint32_t* long_list;              // their indices (launch_find_long), or null
     uint64_t long_count, long_max;          // how many, and the largest output size
     uint32_t long_thresh;                   // output bytes from which a record is 'long' (0: none are)
+    // replace (ops_replace.hip): rep_len[i] = new head bytes + 1 (0: the head stays), the head at rep_stage + rep_off[i]
+    const uint32_t* rep_len;
+    const uint64_t* rep_off;
+    const uint8_t* rep_stage;
     // records whose output is written by the segmented copy (ops_segcopy.hip): seg_src[i] != 0; null = none
     const uint64_t* seg_src;
 };

@@ -70,6 +70,10 @@ Options Options::defaults(Op op) {
         case Op::Rename: o.fields = {fb("ByName", false)}; break;   // bigseqkit/rename.go:17-22
         case Op::Pair: o.fields = {fb("SaveUnpaired", false)}; break;   // bigseqkit/pair.go:17-22
         case Op::Concat: o.fields = {fb("Full", false), fs("Separator", "|")}; break;   // bigseqkit/concat.go:18-24
+        case Op::Replace:  // bigseqkit/replace.go:23-37
+            o.fields = {fs("Pattern", ""), fs("Replacement", ""), fi("NrWidth", 1), fb("BySeq", false), fb("IgnoreCase", false),
+                        fs("KvFile", ""), fb("KeepUntouch", false), fb("KeepKey", false), fi("KeyCaptIdx", 1), fs("KeyMissRepl", "")};
+            break;
         case Op::Common:  // bigseqkit/common.go:21-29
             o.fields = {fb("ByName", false), fb("BySeq", false), fb("IgnoreCase", false), fb("OnlyPositiveStrand", false)};
             break;
@@ -224,7 +228,7 @@ bool op_from_name(const std::string& name, Op* out) {
         {"Duplicate", Op::Duplicate}, {"Rename", Op::Rename}, {"RenamePrepare", Op::Rename},
         {"Sort", Op::Sort}, {"Faidx", Op::Faidx}, {"Pair", Op::Pair},
         {"PairPrepare", Op::Pair}, {"Common", Op::Common}, {"CommonPrepare", Op::Common},
-        {"Concat", Op::Concat}, {"ConcatPrepare", Op::Concat}};
+        {"Concat", Op::Concat}, {"ConcatPrepare", Op::Concat}, {"Replace", Op::Replace}};
     for (auto& t : tbl)
         if (name == t.n) { *out = t.op; return true; }
     return false;
@@ -249,6 +253,7 @@ const char* op_name(Op op) {
         case Op::Pair: return "Pair";
         case Op::Common: return "Common";
         case Op::Concat: return "Concat";
+        case Op::Replace: return "Replace";
     }
     return "";
 }

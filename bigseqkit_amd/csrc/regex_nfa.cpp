@@ -42,6 +42,7 @@ struct Parser {
     size_t i = 0;
     bool icase = false, dotall = false, ungreedy = false;
     int ngroups = 0;
+    std::vector<std::string> names{""};  // names[g]: name of capture group g ("" unnamed; [0] the whole match)
     explicit Parser(const std::string& s) : e(s) {}
     bool more() const { return i < e.size(); }
     char peek() const { return e[i]; }
@@ -176,15 +177,18 @@ struct Parser {
         switch (c) {
             case '(': {
                 bool capture = true;
+                std::string name;
                 if (more() && peek() == '?') {
                     if (e.compare(i, 2, "?:") == 0) { i += 2; capture = false; }
                     else if (e.compare(i, 3, "?P<") == 0) {
                         const size_t j = e.find('>', i);
                         if (j == std::string::npos) bad("invalid named capture", e);
+                        name = e.substr(i + 3, j - i - 3);
                         i = j + 1;
                     } else unsupported("flags / look-around inside the expression", e);
                 }
                 const int idx = capture ? ++ngroups : 0;  // groups are numbered by their opening parenthesis
+                if (capture) names.push_back(name);
                 NodeP n = alt();
                 if (!more() || peek() != ')') bad("missing closing )", e);
                 ++i;
@@ -410,6 +414,7 @@ struct VmBuilder {
     const std::string& expr;
     VmProgram P;
     uint32_t nsets = 0;
+    int max_group = 1;  // groups whose bounds are recorded
     explicit VmBuilder(const std::string& e) : expr(e) {}
     uint32_t emit(uint8_t op, uint8_t arg = 0, uint8_t x = 0, uint8_t y = 0) {
         if (P.n >= (uint32_t)VM_MAX_INST) unsupported("expression too large for the position-reporting matcher", expr);
@@ -491,9 +496,9 @@ struct VmBuilder {
                 return;
             }
             case NT::Group:
-                if (n.group == 1) emit(VM_SAVE, 2);
+                if (n.group <= max_group) emit(VM_SAVE, (uint8_t)(2 * n.group));
                 gen(*n.kids[0]);
-                if (n.group == 1) emit(VM_SAVE, 3);
+                if (n.group <= max_group) emit(VM_SAVE, (uint8_t)(2 * n.group + 1));
                 return;
         }
     }
@@ -501,10 +506,12 @@ struct VmBuilder {
 
 }  // namespace
 
-VmProgram compile_vm(const std::string& expr) {
+VmProgram compile_vm(const std::string& expr, int max_group, std::vector<std::string>* names) {
     Parser ps(expr);
     NodeP root = ps.parse();
+    if (names) *names = ps.names;
     VmBuilder b(expr);
+    b.max_group = max_group;
     memset(&b.P, 0, sizeof b.P);
     b.emit(VM_SAVE, 0);
     b.gen(*root);

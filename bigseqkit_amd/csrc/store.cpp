@@ -147,6 +147,7 @@ dev_fn fn_of(const bsk_ctx* c, bool* chunkable) {
         case Op::Rename: return rename_run_device;
         case Op::Sort: return sort_run_device;
         case Op::Duplicate: *chunkable = true; return records_run_device;
+        case Op::Replace: *chunkable = true; return replace_run_device;  // {nr}: the chunks of one call are one partition
         default: return nullptr;
     }
 }
@@ -396,6 +397,9 @@ int bsk_run_to_store(bsk_ctx* c, const void* host_shard, size_t n, int format, i
     if (out_records) *out_records = 0;
     bsk_call_scope scope(c);
     if (!scope.owns) { c->set_error(BSK_BUSY_TEXT); return BSK_ERR_INVALID_ARG; }
+    // replace: {nr} counts the records of this call from 1, across its chunks; with pin_alphabet set the caller says that
+    // several calls carry ONE partition (the CLI's pieces of a worker's shard), and the count goes on from the last call
+    if (!c->tune.is("pin_alphabet", "1")) c->nr_base = 0;
     // (the chunks' outputs are drained from the two output buffers while the next chunk computes: one block each, whatever
     // the switch "out" says)
     struct Contig { bsk_ctx* c; bool was; ~Contig() { c->force_contiguous = was; } } contig{c, c->force_contiguous};

@@ -31,6 +31,8 @@ _FIELDS = {
     "Rename": ["ByName"],     # bigseqkit/rename.go:12-15
     "Pair": ["SaveUnpaired"], # bigseqkit/pair.go:12-15
     "Concat": ["Full", "Separator"],   # bigseqkit/concat.go:12-16
+    "Replace": ["Pattern", "Replacement", "NrWidth", "BySeq", "IgnoreCase", "KvFile", "KeepUntouch", "KeepKey",
+                "KeyCaptIdx", "KeyMissRepl"],   # bigseqkit/replace.go:9-21
     "Common": ["ByName", "BySeq", "IgnoreCase", "OnlyPositiveStrand"],   # bigseqkit/common.go:13-19
     "Faidx": ["UseRegexp", "IgnoreCase", "FullHead", "RegionFile", "Regions"],   # bigseqkit/faidx.go:11-18
     "Sort": ["InNaturalOrder", "BySeq", "ByName", "ByLength", "ByBases", "GapLetters", "Reverse", "IgnoreCase",
@@ -113,3 +115,4 @@ SeqKitFaidxOptions = _make("Faidx")
 SeqKitPairOptions = _make("Pair")
 SeqKitCommonOptions = _make("Common")
 SeqKitConcatOptions = _make("Concat")
+SeqKitReplaceOptions = _make("Replace")

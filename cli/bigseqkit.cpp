@@ -132,6 +132,12 @@ const Command kCommands[] = {
      {{"read1", '1', STR, "", ""}, {"read2", '2', STR, "", ""}, {"out-dir", 'O', STR, "", ""}, {"force", 'f', BOOL, "", "false"},
       {"save-unpaired", 'u', BOOL, "SaveUnpaired", "false"}}},
     {"rename", "Rename", {{"by-name", 'n', BOOL, "ByName", "false"}}},                  // cli/rename.go
+    {"replace", "Replace",                                                             // cli/replace.go:70-83
+     {{"pattern", 'p', STR, "Pattern", ""}, {"replacement", 'r', STR, "Replacement", ""},
+      {"nr-width", 0, INT, "NrWidth", "1"}, {"by-seq", 's', BOOL, "BySeq", "false"},
+      {"ignore-case", 'i', BOOL, "IgnoreCase", "false"}, {"kv-file", 'k', STR, "KvFile", ""},
+      {"keep-untouch", 'U', BOOL, "KeepUntouch", "false"}, {"keep-key", 'K', BOOL, "KeepKey", "false"},
+      {"key-capt-idx", 'I', INT, "KeyCaptIdx", "1"}, {"key-miss-repl", 'm', STR, "KeyMissRepl", ""}}},
     {"faidx", "Faidx",                                                                 // cli/faidx.go:68-72
      {{"use-regexp", 'r', BOOL, "UseRegexp", "false"}, {"ignore-case", 'i', BOOL, "IgnoreCase", "false"},
       {"full-head", 'f', BOOL, "FullHead", "false"}, {"region-file", 'l', STR, "RegionFile", ""},
@@ -478,6 +484,7 @@ int run_op(const std::string& use, bsk_ctx* ctx, const Part& in, int64_t pid, ui
     if (use == "translate") return bsk_translate_run(ctx, p, n, dev, in.fmt, pid, nullptr, out);
     if (use == "fq2fa") return bsk_fq2fa_run(ctx, p, n, dev, in.fmt, pid, nullptr, out);
     if (use == "rename") return bsk_rename_run(ctx, p, n, dev, in.fmt, pid, nullptr, out);
+    if (use == "replace") return bsk_replace_run(ctx, p, n, dev, in.fmt, pid, nullptr, out);
     if (use == "sort") return bsk_sort_run(ctx, p, n, dev, in.fmt, pid, nullptr, out);
     if (use == "faidx" && g_faidx_query) return bsk_faidx_query_run(ctx, p, n, dev, in.fmt, pid, nullptr, out);
     if (use == "faidx") return bsk_faidx_run(ctx, p, n, dev, in.fmt, pid, first_record /* = byte offset here */, nullptr, out);
@@ -860,11 +867,11 @@ static bool parallel_pread(int fd, uint8_t* buf, size_t len, size_t off, int thr
 
 int run_devices(const Invocation& inv) {
     const std::string use = inv.cmd->use;
-    static const char* const kStreamed[] = {"seq", "grep", "locate", "subseq", "translate", "fq2fa"};
+    static const char* const kStreamed[] = {"seq", "grep", "locate", "subseq", "translate", "fq2fa", "replace"};
     bool streamed = false;
     for (const char* u : kStreamed) streamed = streamed || use == u;
     if (!streamed && use != "stats" && use != "rmdup")
-        die("'" + use + "' runs on one device (bigseqkit " + use + " ... --device N); several GPUs: fq2fa, grep, locate, rmdup, seq, stats, subseq, translate");
+        die("'" + use + "' runs on one device (bigseqkit " + use + " ... --device N); several GPUs: fq2fa, grep, locate, replace, rmdup, seq, stats, subseq, translate");
     if (inv.files.size() != 1) die("--devices: exactly one input file (it is cut into one shard per GPU)");
     const std::vector<int> devices = parse_devices(inv.pget("devices"));
     const int world = (int)devices.size();

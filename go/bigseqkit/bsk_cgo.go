@@ -40,6 +40,7 @@ static bsk_run_fn bsk_fn_locate(void)    { return bsk_locate_run; }
 static bsk_run_fn bsk_fn_subseq(void)    { return bsk_subseq_run; }
 static bsk_run_fn bsk_fn_translate(void) { return bsk_translate_run; }
 static bsk_run_fn bsk_fn_rmdup(void)     { return bsk_rmdup_run; }
+static bsk_run_fn bsk_fn_replace(void)   { return bsk_replace_run; }
 */
 import "C"
 
@@ -369,6 +370,12 @@ func Subseq(input *SeqFrame, o *SeqKitSubseqOptions) (*Result, error) {
 func Translate(input *SeqFrame, o *SeqKitTranslateOptions) (*Result, error) {
 	o.setDefaults()
 	return mapPartitions("Translate", C.bsk_fn_translate(), OptionsToString(o), input, nil, workersFor(input))
+}
+
+// Replace: bigseqkit/replace.go:39-60 ({nr} counts the records of each partition from 1)
+func Replace(input *SeqFrame, o *SeqKitReplaceOptions) (*Result, error) {
+	o.setDefaults()
+	return mapPartitions("Replace", C.bsk_fn_replace(), OptionsToString(o), input, nil, workersFor(input))
 }
 
 // RmDup: bigseqkit/rmdup.go:70-108.  Duplicates are global (GroupByKey): the partitions of this process are joined and

@@ -326,6 +326,19 @@ int bsk_sort_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int f
 int bsk_rename_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,
                    bsk_out* out);
 
+/* ---- Replace (bigseqkit-lib/replace.go:127-179, options bigseqkit/replace.go:9-37): the name (or, with BySeq, the
+ * FASTA sequence) of every record through Go's Regexp.ReplaceAll with template expansion; {nr} / {kv} as the reference.
+ * Every record is written with record.Format(LineWidth) (FASTQ: width 0).  {nr} counts the records of one call from 1:
+ * bsk_replace_run and bsk_run_to_store start it again (the chunks of one bsk_run_to_store continue it), except that
+ * with the switch pin_alphabet = 1 bsk_run_to_store continues from the context's previous call (one partition fed
+ * through several calls).  A record whose output would reach 2^32 bytes is BSK_ERR_UNSUPPORTED.  A target holding a byte >= 0x80 is BSK_ERR_UNSUPPORTED
+ * (Go matches UTF-8 runes, this engine bytes). */
+int bsk_replace_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,
+                    bsk_out* out);
+/* replace on the HOST, through the routines the device runs (regex_vm.hpp): out = Regexp.ReplaceAll(text, repl) for
+ * the expression `expr`; *len = bytes of the result (BSK_ERR_CAPACITY when it exceeds `cap`).  Needs no device. */
+int bsk_regex_replace(const char* expr, const char* repl, const uint8_t* text, size_t n, uint8_t* out, size_t cap, size_t* len);
+
 /* ---- Fq2Fa (bigseqkit-lib/fq2fa.go:16-59): every record as FASTA, the sequence on one line (Format(0)). */
 int bsk_fq2fa_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,
                   bsk_out* out);

@@ -1,0 +1,269 @@
+"""Restatement of `replace` (/root/reference/bigseqkit-lib/replace.go) in Python, the checker of the replace tests.
+
+Go's regexp.ReplaceAll loop and Regexp.Expand are written out (Python's re.sub differs on empty matches: `x*` -> `-`
+on `abxd` is `-a-b-d-` in Go, `-a-b--d-` in re.sub); the matching itself is Python `re` on bytes, with the expression
+translated where RE2 and Python differ for the syntax the tests draw from ($ / \\z -> \\Z, \\s without \\v).
+Inputs stay ASCII."""
+import re
+
+_WORD = re.compile(rb"[A-Za-z0-9_]")
+
+
+def translate(expr):
+    """RE2 expression -> Python expression of the same matches (outside classes: $ \\z \\s)."""
+    out, i, in_cls = [], 0, False
+    while i < len(expr):
+        c = expr[i]
+        if c == "\\" and i + 1 < len(expr):
+            d = expr[i + 1]
+            if not in_cls and d == "z":
+                out.append(r"\Z")
+            elif d == "s":
+                out.append(r"\t\n\f\r " if in_cls else r"[\t\n\f\r ]")
+            else:
+                out.append(expr[i:i + 2])
+            i += 2
+            continue
+        if in_cls:
+            if expr.startswith("[:", i):
+                j = expr.index(":]", i + 2)
+                name = expr[i + 2:j]
+                neg = name.startswith("^")
+                sets = {"alpha": "a-zA-Z", "digit": "0-9", "alnum": "a-zA-Z0-9", "upper": "A-Z", "lower": "a-z",
+                        "space": r"\t\n\v\f\r ", "xdigit": "0-9a-fA-F", "word": "a-zA-Z0-9_", "blank": r" \t",
+                        "punct": r"!-/:-@\[-`{-~"}
+                if neg:
+                    raise ValueError("negated POSIX class")
+                out.append(sets[name.lstrip("^")])
+                i = j + 2
+                cls_first = False
+                continue
+            if c == "]" and not cls_first:
+                in_cls = False
+            cls_first = False
+            out.append(c)
+            i += 1
+            continue
+        if c == "[":
+            in_cls, cls_first = True, True
+            out.append(c)
+            i += 1
+            if i < len(expr) and expr[i] == "^":
+                out.append("^")
+                i += 1
+            continue
+        out.append(r"\Z" if c == "$" else c)
+        i += 1
+    return "".join(out)
+
+
+def compile_go(expr):
+    return re.compile(translate(expr).encode())
+
+
+def _extract(t):
+    """Go regexp.extract: (name, num, rest) or None."""
+    if not t:
+        return None
+    brace = t[:1] == b"{"
+    s = t[1:] if brace else t
+    i = 0
+    while i < len(s) and _WORD.match(s[i:i + 1]):
+        i += 1
+    if i == 0:
+        return None
+    name = s[:i]
+    if brace:
+        if i >= len(s) or s[i:i + 1] != b"}":
+            return None
+        i += 1
+    num = 0
+    for ch in name:
+        if ch < 0x30 or ch > 0x39 or num >= 100000000:
+            num = -1
+            break
+        num = num * 10 + ch - 0x30
+    if name[:1] == b"0" and len(name) > 1:
+        num = -1
+    return name, num, s[i:]
+
+
+def expand(template, src, spans, names):
+    """Go Regexp.Expand: spans[g] = (a, b) or (-1, -1); names[g] = name of group g ('' unnamed)."""
+    dst = bytearray()
+    t = bytes(template)
+    while t:
+        k = t.find(b"$")
+        if k < 0:
+            break
+        dst += t[:k]
+        t = t[k + 1:]
+        if t[:1] == b"$":
+            dst += b"$"
+            t = t[1:]
+            continue
+        e = _extract(t)
+        if e is None:
+            dst += b"$"
+            continue
+        name, num, t = e
+        if num >= 0:
+            if num < len(spans) and spans[num][0] >= 0:
+                dst += src[spans[num][0]:spans[num][1]]
+        else:
+            for g, nm in enumerate(names):
+                if nm.encode() == name and spans[g][0] >= 0:
+                    dst += src[spans[g][0]:spans[g][1]]
+                    break
+    dst += t
+    return bytes(dst)
+
+
+def _spans(m):
+    return [m.span(g) for g in range(m.re.groups + 1)]
+
+
+def _names(rx):
+    names = [""] * (rx.groups + 1)
+    for nm, g in rx.groupindex.items():
+        names[g] = nm
+    return names
+
+
+def replace_all(rx, src, template):
+    """Go regexp.ReplaceAll (regexp.go replaceAll): byte semantics (ASCII inputs)."""
+    src = bytes(src)
+    names = _names(rx)
+    buf, last, pos = bytearray(), 0, 0
+    while pos <= len(src):
+        m = rx.search(src, pos)
+        if not m:
+            break
+        a0, a1 = m.span()
+        buf += src[last:a0]
+        if a1 > last or a0 == 0:
+            buf += expand(template, src, _spans(m), names)
+        last = a1
+        pos = pos + 1 if pos + 1 > a1 else a1
+    buf += src[last:]
+    return bytes(buf)
+
+
+def find_all(rx, src):
+    """Go regexp.FindAllSubmatchIndex(src, -1) (allMatches): spans of every match."""
+    out, pos, prev_end = [], 0, -1
+    while pos <= len(src):
+        m = rx.search(src, pos)
+        if not m:
+            break
+        accept = True
+        if m.end() == pos:
+            if m.start() == prev_end:
+                accept = False
+            pos += 1
+        else:
+            pos = m.end()
+        prev_end = m.end()
+        if accept:
+            out.append(_spans(m))
+    return out
+
+
+_NR = re.compile(rb"\{(NR|nr)\}")
+_KV = re.compile(rb"\{(KV|kv)\}")
+
+
+def read_kvs(text, ignore_case):
+    """readKVs (replace.go:183-218) over the file's bytes."""
+    kvs = {}
+    for line in text.split(b"\n"):
+        if not line:
+            continue
+        items = line.rstrip(b"\r\n").split(b"\t")
+        if len(items) < 2:
+            continue
+        k = items[0].lower() if ignore_case else items[0]
+        kvs[k] = items[1]
+    return kvs
+
+
+class ReplaceError(Exception):
+    pass
+
+
+def parse(data, fastq):
+    """(name, seq, qual) of every record: the header without the marker, the sequence without line breaks.  Lines end
+    at '\n' only: a '\r' before it is data (SeqParser, PARITY Q18)."""
+    recs = []
+    text = bytes(data)
+    if fastq:
+        lines = text.split(b"\n")
+        if lines and lines[-1] == b"":
+            lines.pop()
+        for i in range(0, len(lines), 4):
+            recs.append((lines[i][1:], lines[i + 1], lines[i + 3]))
+        return recs
+    for chunk in text.split(b"\n>"):
+        if not chunk:
+            continue
+        if chunk.startswith(b">"):
+            chunk = chunk[1:]
+        head, _, body = chunk.partition(b"\n")
+        recs.append((head, body.replace(b"\n", b""), None))
+    return recs
+
+
+def fmt(name, seq, qual, width, fastq):
+    """record.Format(width): FASTQ with width 0 and a bare '+'."""
+    if fastq:
+        return b"@" + name + b"\n" + seq + b"\n+\n" + qual + b"\n"
+    if width > 0:
+        seq = b"\n".join(seq[i:i + width] for i in range(0, len(seq), width))
+    return b">" + name + b"\n" + seq + b"\n"
+
+
+def replace_records(data, fastq, opts, kvs=None, width=60, nr_base=0):
+    """Replace.Call (replace.go:106-179) over one partition.  opts: the ReplaceOptions fields (defaults as Go)."""
+    pattern = opts.get("Pattern", "")
+    repl = opts.get("Replacement", "").encode()
+    icase = opts.get("IgnoreCase", False)
+    rx = compile_go(("(?i)" if icase else "") + pattern)
+    nr_width = opts.get("NrWidth", 1)
+    idx = opts.get("KeyCaptIdx", 1)
+    with_kv = _KV.search(repl) is not None
+    out = []
+    for nr, (name, seq, qual) in enumerate(parse(data, fastq), start=nr_base + 1):
+        if opts.get("BySeq"):
+            if fastq:
+                raise ReplaceError("editing FASTQ is not supported")
+            seq = replace_all(rx, seq, repl)
+        else:
+            change = True
+            r = repl
+            if _NR.search(r):
+                r = replace_all(_NR, r, b"%0*d" % (nr_width, nr) if nr_width >= 0 else b"%-*d" % (-nr_width, nr))
+            if with_kv:
+                founds = find_all(rx, name)
+                if len(founds) > 1:
+                    raise ReplaceError('pattern "%s" matches multiple targets in "%s", this will cause chaos' % (pattern, name.decode()))
+                if founds:
+                    found = founds[0]
+                    if idx > len(found) - 1:
+                        raise ReplaceError("value of flag -I (--key-capt-idx) overflows")
+                    a, b = found[idx]
+                    key = name[a:b] if a >= 0 else b""
+                    k = key.lower() if icase else key
+                    if k in kvs:
+                        r = replace_all(_KV, r, kvs[k])
+                    elif opts.get("KeepUntouch"):
+                        change = False
+                    elif opts.get("KeepKey"):
+                        r = replace_all(_KV, r, key)
+                    else:
+                        r = replace_all(_KV, r, opts.get("KeyMissRepl", "").encode())
+                else:
+                    change = False
+            if change:
+                name = replace_all(rx, name, r)
+        out.append(fmt(name, seq, qual, 0 if fastq else width, fastq))
+    return b"".join(out)
