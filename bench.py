@@ -8,6 +8,11 @@ One step == one complete Stats over the whole file:
     -> bsk_stats_collect (map[int64]int64) -> Stats()/StatsString() on the host.
 The file is cut into N record-aligned shards (strong scaling: total work is fixed).
 Prints ONE JSON line (rank 0).  See DESIGN.md section 6 for how each number is defined.
+
+A plain run does only what the headline needs: set up, warm up, time the steps, --dump-outputs, print the line (with the
+roofline figures of those same timed steps).  --full runs everything else as well, after the headline: the `stats -a` line,
+the scaling model, the CPU baselines, the 'ops' object (N = 1: the other BASELINE configs and the end-to-end legs; N > 1:
+the configs defined on several GPUs), the vendor yardsticks and the PMC traffic of the committed profiles.
 """
 import argparse
 import ctypes as C
@@ -1139,6 +1144,9 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--gb", type=float, default=FILE_BYTES / 1e9, help="size of the synthetic file (GB)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run everything else the bench measures or "
+                    "checks (stats -a, scaling model, CPU baselines, 'ops', end-to-end legs, vendor yardsticks, PMC traffic); "
+                    "the --no-* options below take parts of it away again")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--no-ops", action="store_true", help="skip the 'ops' object (seq -n / grep / translate / rmdup at the "
@@ -1346,61 +1354,62 @@ def main():
         dump_stats_outputs(args.dump_outputs, vec, m, last["info"], text)
     op.close()
 
-    # secondary line: stats -a (Q20/Q30/gap counters on top), same timing recipe
-    op, vec = make_op(True)
-    dta, ma, texta, ka_ms, _, _, _ = timed(op, vec, max(3, args.steps // 2), 1)
-    stepsa = max(3, args.steps // 2)
-    op.close()
-    # exact expectation for -a, computed WITHOUT the parser: FASTQ-150 records are 317 bytes with the quality string at
-    # columns [166, 316), so Q20 / Q30 are plain column counts over the fixed layout (torch, chunked; untimed)
-    q20 = q30 = 0
-    view = shard.view(nrec, REC)
-    step_rows = 4_000_000
-    for r0 in range(0, nrec, step_rows):
-        q = view[r0:r0 + step_rows, 166:316]
-        q20 += int((q >= 33 + 20).sum().item())
-        q30 += int((q >= 33 + 30).sum().item())
-        del q
-    if dist_on:
-        q20, q30 = bdist.all_reduce_count(q20, dev), bdist.all_reduce_count(q30, dev)
-    verified_a = (ma.get(150) == total_rec and ma.get(-3) == 0 and ma.get(-1) == q20 and ma.get(-2) == q30
-                  and sum(v for k, v in ma.items() if k >= 0) == total_rec)
-
-    # ---- what one GPU does with the shard of an N-GPU job (N = 1 line only): the same step on the first 1/2, 1/4, 1/8 of the
-    # file -- the term of the 1 / 2 / 4 / 8 curve that this box CAN measure.  An ESTIMATE of the curve, not the curve: the
-    # 512 KB all-reduce per step and the other GPUs are not in it.
-    scaling_model = None
-    if not dist_on and not args.no_scaling_model:
-        op, vec = make_op(False)
-        rows = {}
-        for g in (1, 2, 4, 8):
-            nb_g = (nrec // g) * REC
-            if nb_g <= 0:
-                continue
-            dtg, mg, _, kg, pg, _, _ = timed(op, vec, max(5, args.steps // 2), 2, nb_g)
-            step = dtg / max(5, args.steps // 2) * 1e3
-            rows[str(g)] = {"shard_GB": round(nb_g / 1e9, 3), "ms_per_step": round(step, 4), "k_stats_ms": round(kg, 4), "k_prep_ms": round(pg, 4),
-                            "outside_k_stats_ms": round(step - kg, 4), "k_stats_frac": round(nb_g / (kg * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if kg > 0 else None,
-                            "exact": mg.get(150) == nrec // g}
+    # ---- --full only, after the headline and its outputs: none of what follows feeds them
+    scaling_model = ops_multi = None
+    if args.full:
+        # secondary line: stats -a (Q20/Q30/gap counters on top), same timing recipe
+        op, vec = make_op(True)
+        dta, ma, texta, ka_ms, _, _, _ = timed(op, vec, max(3, args.steps // 2), 1)
+        stepsa = max(3, args.steps // 2)
         op.close()
-        if "1" in rows:
-            scaling_model = {"what": "ESTIMATE: one GPU running the stats step on the shard an N-GPU job would give it (the first 1/N of the same "
-                                     "file); no collective, no second GPU -- not a measured scaling curve",
-                             "per_n_gpus": rows,
-                             "speedup_if_ranks_do_not_disturb_each_other": {g: round(rows["1"]["ms_per_step"] / r["ms_per_step"], 3) for g, r in rows.items()}}
+        # exact expectation for -a, computed WITHOUT the parser: FASTQ-150 records are 317 bytes with the quality string at
+        # columns [166, 316), so Q20 / Q30 are plain column counts over the fixed layout (torch, chunked; untimed)
+        q20 = q30 = 0
+        view = shard.view(nrec, REC)
+        step_rows = 4_000_000
+        for r0 in range(0, nrec, step_rows):
+            q = view[r0:r0 + step_rows, 166:316]
+            q20 += int((q >= 33 + 20).sum().item())
+            q30 += int((q >= 33 + 30).sum().item())
+            del q
+        if dist_on:
+            q20, q30 = bdist.all_reduce_count(q20, dev), bdist.all_reduce_count(q30, dev)
+        verified_a = (ma.get(150) == total_rec and ma.get(-3) == 0 and ma.get(-1) == q20 and ma.get(-2) == q30
+                      and sum(v for k, v in ma.items() if k >= 0) == total_rec)
 
-    # ---- the BASELINE configs that are defined on several GPUs (C3, C5) -- every rank takes part
-    ops_multi = None
-    if dist_on and not args.no_ops:
-        del view
-        shard = None
-        torch.cuda.empty_cache()
-        try:
-            ops_multi = run_ops_multi(args, torch, bsk, _lib, lib, check, dev, local, rank, world, bdist, dist.get_backend())
-        except Exception as e:  # reported, not hidden; the collectives of the other ranks may then time out -- say which rank
-            ops_multi = {"error": "rank %d: %s: %s" % (rank, type(e).__name__, str(e)[:400])}
-            if rank != 0:
-                print("bench.py rank %d: ops leg failed: %s" % (rank, ops_multi["error"]), file=sys.stderr, flush=True)
+        # ---- what one GPU does with the shard of an N-GPU job (N = 1 line only): the same step on the first 1/2, 1/4, 1/8 of the
+        # file -- the term of the 1 / 2 / 4 / 8 curve that this box CAN measure.  An ESTIMATE of the curve, not the curve: the
+        # 512 KB all-reduce per step and the other GPUs are not in it.
+        if not dist_on and not args.no_scaling_model:
+            op, vec = make_op(False)
+            rows = {}
+            for g in (1, 2, 4, 8):
+                nb_g = (nrec // g) * REC
+                if nb_g <= 0:
+                    continue
+                dtg, mg, _, kg, pg, _, _ = timed(op, vec, max(5, args.steps // 2), 2, nb_g)
+                step = dtg / max(5, args.steps // 2) * 1e3
+                rows[str(g)] = {"shard_GB": round(nb_g / 1e9, 3), "ms_per_step": round(step, 4), "k_stats_ms": round(kg, 4), "k_prep_ms": round(pg, 4),
+                                "outside_k_stats_ms": round(step - kg, 4), "k_stats_frac": round(nb_g / (kg * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if kg > 0 else None,
+                                "exact": mg.get(150) == nrec // g}
+            op.close()
+            if "1" in rows:
+                scaling_model = {"what": "ESTIMATE: one GPU running the stats step on the shard an N-GPU job would give it (the first 1/N of the same "
+                                         "file); no collective, no second GPU -- not a measured scaling curve",
+                                 "per_n_gpus": rows,
+                                 "speedup_if_ranks_do_not_disturb_each_other": {g: round(rows["1"]["ms_per_step"] / r["ms_per_step"], 3) for g, r in rows.items()}}
+
+        # ---- the BASELINE configs that are defined on several GPUs (C3, C5) -- every rank takes part
+        if dist_on and not args.no_ops:
+            del view
+            shard = None
+            torch.cuda.empty_cache()
+            try:
+                ops_multi = run_ops_multi(args, torch, bsk, _lib, lib, check, dev, local, rank, world, bdist, dist.get_backend())
+            except Exception as e:  # reported, not hidden; the collectives of the other ranks may then time out -- say which rank
+                ops_multi = {"error": "rank %d: %s: %s" % (rank, type(e).__name__, str(e)[:400])}
+                if rank != 0:
+                    print("bench.py rank %d: ops leg failed: %s" % (rank, ops_multi["error"]), file=sys.stderr, flush=True)
 
     if rank != 0:
         if dist_on:
@@ -1411,9 +1420,9 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     # HBM bytes per k_stats launch from the PMC passes (rocprofv3 cannot wrap itself: the counters come from the
     # committed profile of this same command, scripts/gpu_round.sh + scripts/pmc_traffic.py); only valid for the
-    # full single-GPU workload it was collected on.
+    # full single-GPU workload it was collected on.  Read with --full only: a plain run reads nothing but its own results.
     traffic, traffic_src = None, None
-    pmc = sorted(__import__("glob").glob(os.path.join(ROOT, "profiles", "*_pmc_traffic.json")))
+    pmc = sorted(__import__("glob").glob(os.path.join(ROOT, "profiles", "*_pmc_traffic.json"))) if args.full else []
     if pmc and not dist_on and total_bytes > 99e9:
         try:
             pj = json.load(open(pmc[-1]))
@@ -1466,18 +1475,19 @@ def main():
             "avg_launch_ms": round(k_ms, 4),
             "k_prep_avg_launch_ms": round(p_ms, 4),
         },
-        "stats_all": {
+    }
+    if args.full:
+        out["stats_all"] = {
             "value": round(total_rec * stepsa / dta / 1e6, 3), "unit": "M records/s",
             "gb_per_s": round(total_bytes * stepsa / dta / 1e9, 2), "ms_per_step": round(dta / stepsa * 1e3, 4),
             "k_stats_avg_launch_ms": round(ka_ms, 4),
             "roofline_frac": round(nbytes / (ka_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if ka_ms > 0 else None,
             "verified": bool(verified_a),
             "expected": {"q20": q20, "q30": q30, "gap": 0, "how": "column counts over the fixed 317-byte layout (torch), exact equality"},
-        },
-    }
+        }
 
     # ---- CPU baseline: the oracle (port of the reference algorithm), 1 thread, bounded sample
-    if not dist_on and not args.no_cpu_baseline:
+    if args.full and not dist_on and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle
         pilot = shard[:REC * 200_000].cpu()
@@ -1528,7 +1538,7 @@ def main():
         except Exception as e:  # never let the extra baseline break the bench line
             out["cpu_baseline_all_cores"] = {"error": str(e)[:200]}
     # ---- the other BASELINE configs (N = 1): seq -n @ C2, grep @ C3 shard, translate @ C4, rmdup @ C5 shard
-    if not dist_on and not args.no_ops:
+    if args.full and not dist_on and not args.no_ops:
         if total_bytes > 99e9 or args.ops_scale != 1.0:
             try:
                 out["ops"] = run_ops(args, torch, bsk, _lib, lib, check, dev, local, shard, total_rec)

@@ -12,7 +12,7 @@ import sys
 
 tag = sys.argv[1]
 out = {"source": f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, scripts/gpu_round.sh {tag}) of "
-                 "`python bench.py --steps 3 --warmup 1 --no-cpu-baseline`; bytes = FETCH_SIZE x 1024 x 2 "
+                 "`python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline`; bytes = FETCH_SIZE x 1024 x 2 "
                  "(gfx950 half-count of 16 B/lane coalesced reads, profiles/r01_calibration_stream_read.json) + WRITE_SIZE x 1024",
        "raw": {}, "per_launch": {}}
 names = {"k_stats<true, false, true": "stats", "k_stats<true, true, true": "stats -a"}  # (<FASTQ, ALL, DPP[, ROLES]>)

@@ -2,7 +2,7 @@
 # quick GPU visit: gpu tests + bench line
 R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=$(pwd); O=$R/gpurun_out; mkdir -p $O; cd $R
 (timeout 1200 python -m pytest tests -m gpu -q -x 2>&1 | tail -${2:-6}) > $O/quick_tests.log 2>&1
-(timeout 600 python bench.py --no-cpu-baseline ${1:-} 2>&1 | tail -1) > $O/quick_bench.json 2>$O/quick_bench.err
+(timeout 600 python bench.py --full --no-cpu-baseline ${1:-} 2>&1 | tail -1) > $O/quick_bench.json 2>$O/quick_bench.err
 cat $O/quick_tests.log; python - <<PY
 import json
 try:

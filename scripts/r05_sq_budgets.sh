@@ -5,8 +5,8 @@
 R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=$(pwd); O=$R/gpurun_out; mkdir -p $O; cd $R
 bash scripts/pmc_sq_ops.sh seq,subseq,grep,rmdup,translate 1.0 r05sq > $O/r05sq.log 2>&1
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_BUSY_CYCLES --output-format csv -d $O/pmc_r05sqstats_a -o pmc -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-ops > $O/pmc_r05sqstats_a.log 2>&1
-rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VMEM --output-format csv -d $O/pmc_r05sqstats_b -o pmc -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-ops > $O/pmc_r05sqstats_b.log 2>&1
+rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_BUSY_CYCLES --output-format csv -d $O/pmc_r05sqstats_a -o pmc -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-ops > $O/pmc_r05sqstats_a.log 2>&1
+rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VMEM --output-format csv -d $O/pmc_r05sqstats_b -o pmc -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-ops > $O/pmc_r05sqstats_b.log 2>&1
 cd $R
 python - <<PY
 import csv, collections, glob, json

@@ -26,8 +26,20 @@ def run_bench(args, env_extra=None):
     return json.loads(lines[0])
 
 
+def test_bench_plain_line_is_the_headline_alone():
+    """a plain run (no --full) times the steps and prints the line: none of the legs that --full adds"""
+    d = run_bench(["--gb", "2", "--steps", "3", "--warmup", "1"])
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["bit_exact_vs_expected_row"] is True
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "M records/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "u8" and d["roofline"]["bound"] == "hbm" and d["roofline"]["avg_launch_ms"] > 0
+    assert d["roofline"]["traffic"] is None
+    full_only = {"stats_all", "scaling_model", "cpu_baseline", "cpu_baseline_all_cores", "ops", "end_to_end",
+                 "end_to_end_config_size", "vendor_yardsticks"}
+    assert not full_only & set(d), sorted(full_only & set(d))
+
+
 def test_bench_single_gpu_line_small():
-    d = run_bench(["--gb", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"])
+    d = run_bench(["--full", "--gb", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"])
     assert d["n_gpus"] == 1 and d["bit_exact_vs_expected_row"] is True
     assert d["stats_all"]["verified"] is True
     assert d["roofline"]["bound"] == "hbm" and d["roofline"]["avg_launch_ms"] > 0
@@ -59,7 +71,7 @@ def test_bench_dump_outputs_repeat(tmp_path):
 
 @pytest.mark.parametrize("n", [2, 3])
 def test_bench_n_ranks_sharing_one_gpu(n):
-    d = run_bench(["--gpus", str(n), "--gb", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--ops-scale", "0.02",
+    d = run_bench(["--full", "--gpus", str(n), "--gb", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--ops-scale", "0.02",
                    "--ops-calls", "2"], {"BSK_BENCH_SHARE_GPU": "1"})
     assert d["n_gpus"] == n
     assert d["bit_exact_vs_expected_row"] is True and d["stats_all"]["verified"] is True
@@ -88,7 +100,7 @@ def test_bench_one_rank_over_rccl():
     """BSK_BENCH_DIST_SINGLE=1: the N-rank path with ONE rank -- process group "nccl", the all-reduce of every step, the
     grep count all-reduce, the rmdup tuple exchange (all_gather + three all_to_all_single) -- so that the RCCL calls of
     that path run on a one-GPU box at all.  A small message limit forces the exchange into rounds."""
-    d = run_bench(["--gpus", "1", "--gb", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--ops-scale", "0.02",
+    d = run_bench(["--full", "--gpus", "1", "--gb", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--ops-scale", "0.02",
                    "--ops-calls", "2"], {"BSK_BENCH_DIST_SINGLE": "1", "BSK_A2A_MAX_BYTES": str(8 << 20)})
     assert d["single_rank_dist_check"] is True and d["backend"] == "nccl" and d["n_gpus"] == 1
     assert d["bit_exact_vs_expected_row"] is True and d["allreduce_ms_per_step"] is not None
@@ -103,7 +115,7 @@ def test_bench_one_rank_over_rccl():
 def test_bench_ops_object_small():
     """the 'ops' object of the driver-run line (seq -n @ C2, grep @ C3 shard, translate @ C4, rmdup @ C5 shard) at 1 / 50
     of the BASELINE sizes: every entry must carry its timing, its algorithmic bytes and an exact full-output check"""
-    d = run_bench(["--gb", "2", "--steps", "2", "--warmup", "1", "--cpu-seconds", "1", "--ops-scale", "0.02", "--ops-calls", "2"])
+    d = run_bench(["--full", "--gb", "2", "--steps", "2", "--warmup", "1", "--cpu-seconds", "1", "--ops-scale", "0.02", "--ops-calls", "2"])
     ops = d["ops"]
     assert "error" not in ops, ops
     stats_legs = {"stats @ FASTA-1k (C1 layout, 20 GB)", "stats -a @ FASTA-1k (C1 layout, 20 GB)", "stats @ C4 input (50 GB FASTA-5k)"}
