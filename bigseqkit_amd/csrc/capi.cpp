@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <optional>
 
 #include "../../include/bsk.h"
 #include "anchor.hpp"
@@ -121,30 +122,131 @@ int init_device(bsk_ctx* c) {
     return BSK_OK;
 }
 
-// sequence bytes of the first record in `b` (up to `limit` bytes)
-std::vector<uint8_t> first_record_seq(const std::vector<uint8_t>& b, int format, size_t limit) {
-    std::vector<uint8_t> s;
-    const size_t n = b.size();
-    size_t p = 0;
-    while (p < n && b[p] != '\n') ++p;  // header
-    ++p;
-    if (format == BSK_FORMAT_FASTQ) {
-        while (p < n && b[p] != '\n' && s.size() < limit) s.push_back(b[p++]);
-        return s;
-    }
-    while (p < n && s.size() < limit) {
-        if (b[p] == '>' && b[p - 1] == '\n') break;
-        if (b[p] != '\n') s.push_back(b[p]);
-        ++p;
-    }
-    return s;
-}
-
 }  // namespace
 
 namespace bsk {
 int global_error_set(int code, const std::string& m) { return fail_global(code, m); }
+
+// ---------------------------------------------------------------------------
+// what the entry points of this file and of store.cpp share (ops_host.hpp)
+// ---------------------------------------------------------------------------
+RecordOp record_op(const bsk_ctx* c) {
+    const Options& o = c->opts;
+    switch (c->op) {
+        case Op::Seq: return {seq_run_device, RecordOp::Chunks};
+        case Op::Grep:
+            return {grep_run_device, !o.b("Count") && !(o.b("DeleteMatched") && !o.b("InvertMatch")) ? RecordOp::Chunks : RecordOp::Whole};
+        case Op::Locate: return {locate_run_device, RecordOp::Chunks};
+        case Op::Subseq: return {subseq_run_device, RecordOp::Chunks};
+        case Op::Translate: return {translate_run_device, RecordOp::Chunks};
+        case Op::Fq2Fa: return {fq2fa_run_device, RecordOp::Chunks};
+        case Op::RmDup: return {rmdup_run_device, RecordOp::Whole};
+        case Op::Rename: return {rename_run_device, RecordOp::Whole};
+        case Op::Sort: return {sort_run_device, RecordOp::Whole};
+        case Op::Duplicate: return {records_run_device, RecordOp::Chunks};
+        case Op::Replace: return {replace_run_device, RecordOp::Chunks};  // {nr}: the chunks of one call are one partition
+        case Op::Range: case Op::Head: return {records_run_device, RecordOp::NoStore};
+        case Op::Faidx: return {faidx_run_device, RecordOp::NoStore};
+        default: return {};  // stats; pair / common / concat read several texts
+    }
 }
+
+int stage_reserve(bsk_ctx* c, int b, size_t need, size_t spare, size_t slack, bool drain, hipStream_t st) {
+    if (need + slack <= c->stage_size[b]) return BSK_OK;
+    if (drain) HIP_TRY(c, hipStreamSynchronize(st));  // nothing may still read the buffer that is replaced
+    if (c->d_stage[b]) HIP_TRY(c, hipFree(c->d_stage[b]));
+    c->d_stage[b] = nullptr;
+    c->stage_size[b] = 0;
+    HIP_TRY(c, hipMalloc((void**)&c->d_stage[b], need + spare + slack));
+    c->stage_size[b] = need + spare + slack;
+    return BSK_OK;
+}
+
+std::vector<size_t> record_cuts(const uint8_t* h, size_t n, int format, size_t chunk) {
+    std::vector<size_t> cuts{0};
+    while (cuts.back() < n) {
+        const size_t lo = cuts.back();
+        size_t hi = n;
+        if (n - lo > chunk) {  // the first record start at or after lo + chunk
+            hi = format == BSK_FORMAT_FASTQ ? (size_t)find_fastq_cut(h, n, lo + chunk) : (size_t)find_fasta_start(h, n, lo + chunk);
+            if (hi <= lo || hi > n) hi = n;
+        }
+        cuts.push_back(hi);
+    }
+    return cuts;
+}
+
+// several FASTQ texts in one buffer (ends[k] = one past text k): every text is rewritten as 4-line FASTQ by itself and the
+// rewritten texts, back to back, take the place of the buffer: *d2 / ends2.  The combined text lives in c->d_norm2.
+static int normalize_pieces(bsk_ctx* c, const uint8_t* d, const std::vector<uint64_t>& ends, hipStream_t st, const uint8_t** d2,
+                            std::vector<uint64_t>* ends2) {
+    ends2->clear();
+    uint64_t total = 0, from = 0;
+    for (size_t k = 0; k < ends.size(); ++k) {
+        const uint8_t* dk = nullptr;
+        size_t nk = 0;
+        if (k) HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), st));  // (run_multiline clears it before the first)
+        int rc = normalize_multiline_fastq(c, d + from, ends[k] - from, st, &dk, &nk);
+        if (rc != BSK_OK) return rc;
+        // (a text that does not end with a newline must not run into the next one)
+        uint8_t last = '\n';
+        if (nk) HIP_TRY(c, hipMemcpy(&last, dk + nk - 1, 1, hipMemcpyDeviceToHost));
+        const uint64_t need = total + nk + 1;
+        if (need > c->norm2_cap) {
+            uint8_t* g = nullptr;
+            const uint64_t cap = need + need / 4 + (ends.back() - from) + 256;
+            HIP_TRY(c, hipMalloc((void**)&g, cap));
+            if (total) HIP_TRY(c, hipMemcpy(g, c->d_norm2, total, hipMemcpyDeviceToDevice));
+            if (c->d_norm2) HIP_TRY(c, hipFree(c->d_norm2));
+            c->d_norm2 = g;
+            c->norm2_cap = cap;
+        }
+        if (nk) HIP_TRY(c, hipMemcpyAsync(c->d_norm2 + total, dk, nk, hipMemcpyDeviceToDevice, st));
+        total += nk;
+        if (nk && last != '\n' && k + 1 < ends.size()) {
+            const uint8_t nl = '\n';
+            HIP_TRY(c, hipMemcpyAsync(c->d_norm2 + total, &nl, 1, hipMemcpyHostToDevice, st));
+            total += 1;
+        }
+        HIP_TRY(c, hipStreamSynchronize(st));  // (c->d_norm is written again by the next text)
+        ends2->push_back(total);
+        from = ends[k];
+    }
+    *d2 = c->d_norm2;
+    return BSK_OK;
+}
+
+int run_multiline(bsk_ctx* c, const TextsOp& op, const uint8_t* d, const std::vector<uint64_t>& ends, int format, hipStream_t st,
+                  bool head_only) {
+    c->last_kernel_flags = 0;
+    const int rc0 = op(d, ends.data());
+    // (range / head / duplicate print the record text as it stands and deal with wrapped records themselves: records_run_device)
+    const bool wrapped_head = rc0 == BSK_ERR_MULTILINE_FASTQ;
+    // the head of the text was 4-line FASTQ and the strict reader gave up further down: wrapped records there?
+    const bool wrapped_later = !head_only && rc0 != BSK_OK && !wrapped_head && format == BSK_FORMAT_FASTQ && !c->norm_active &&
+                               (c->last_kernel_flags & STRICT_FASTQ_FLAGS) != 0;
+    if (!wrapped_head && !wrapped_later) return rc0;
+    const std::string msg = c->last_error;
+    // (head_only: bsk_run_to_store cleared the status word right before the operator gave up on its head sample)
+    if (!head_only) HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), st));
+    const uint8_t* d2 = nullptr;
+    std::vector<uint64_t> ends2(1);
+    size_t n2 = 0;
+    const int rc = ends.size() == 1 ? normalize_multiline_fastq(c, d, ends[0], st, &d2, &n2) : normalize_pieces(c, d, ends, st, &d2, &ends2);
+    if (rc != BSK_OK) {
+        if (wrapped_later) { c->set_error(msg); return rc0; }  // (not FASTQ under either reader: the first complaint stands)
+        return rc;
+    }
+    if (ends.size() == 1) ends2[0] = n2;
+    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), st));
+    struct NormActive {  // the operator runs on the rewrite
+        bsk_ctx* c;
+        explicit NormActive(bsk_ctx* c_) : c(c_) { c->norm_active = true; }
+        ~NormActive() { c->norm_active = false; }
+    } norm(c);
+    return op(d2, ends2.data());
+}
+}  // namespace bsk
 
 extern "C" {
 
@@ -504,30 +606,19 @@ int bsk_stats_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int fo
         if (!c->stage_done[b]) HIP_TRY(c, hipEventCreateWithFlags(&c->stage_done[b], hipEventDisableTiming));
         if (!c->stage_free[b]) HIP_TRY(c, hipEventCreateWithFlags(&c->stage_free[b], hipEventDisableTiming));
     }
-    size_t lo = 0;
-    for (int i = 0; lo < n; ++i) {
-        size_t hi = n;
-        if (n - lo > chunk) {  // cut on the first record start at or after lo + chunk (a chunk holds whole records)
-            hi = format == BSK_FORMAT_FASTQ ? (size_t)find_fastq_cut(h, n, lo + chunk) : (size_t)find_fasta_start(h, n, lo + chunk);
-            if (hi <= lo || hi > n) hi = n;
-        }
-        const int b = i & 1;
-        const size_t len = hi - lo;
-        if (len > c->stage_cap_b[b]) {
-            HIP_TRY(c, hipStreamSynchronize(st));  // nothing may still read the buffer that is replaced
-            if (c->d_stage[b]) HIP_TRY(c, hipFree(c->d_stage[b]));
-            c->d_stage[b] = nullptr;
-            HIP_TRY(c, hipMalloc((void**)&c->d_stage[b], len + len / 16 + 4096));
-            c->stage_cap_b[b] = len + len / 16;
-        }
+    const std::vector<size_t> cuts = record_cuts(h, n, format, chunk);
+    for (size_t i = 0; i + 1 < cuts.size(); ++i) {
+        const int b = (int)(i & 1);
+        const size_t len = cuts[i + 1] - cuts[i];
+        int rc = stage_reserve(c, b, len, len / 16, 4096, /*drain=*/true, st);
+        if (rc != BSK_OK) return rc;
         if (i >= 2) HIP_TRY(c, hipStreamWaitEvent(c->copy_stream[0], c->stage_free[b], 0));
-        HIP_TRY(c, hipMemcpyAsync(c->d_stage[b], h + lo, len, hipMemcpyHostToDevice, c->copy_stream[0]));
+        HIP_TRY(c, hipMemcpyAsync(c->d_stage[b], h + cuts[i], len, hipMemcpyHostToDevice, c->copy_stream[0]));
         HIP_TRY(c, hipEventRecord(c->stage_done[b], c->copy_stream[0]));
         HIP_TRY(c, hipStreamWaitEvent(st, c->stage_done[b], 0));
-        int rc = stats_run_device(c, c->d_stage[b], len, format, (uint64_t*)d_vec, st);
+        rc = stats_run_device(c, c->d_stage[b], len, format, (uint64_t*)d_vec, st);
         if (rc != BSK_OK) return rc;
         HIP_TRY(c, hipEventRecord(c->stage_free[b], st));
-        lo = hi;
     }
     HIP_TRY(c, hipStreamSynchronize(st));  // the staging buffers are reused by the next call
     return BSK_OK;
@@ -610,7 +701,7 @@ static int stats_vector_to_map(bsk_ctx* c, const std::vector<uint64_t>& v, const
     std::vector<uint8_t> seq;
     if (nrec > 0 && !c->first_bytes.empty()) {
         const int64_t thr = c->opts.ci("AlphabetGuessSeqLength");
-        seq = first_record_seq(c->first_bytes, c->first_format, (size_t)std::max<int64_t>(thr, 10000));
+        seq = head_first_seq(c->first_bytes, c->first_format, (size_t)std::max<int64_t>(thr, 10000));
         if (ab == AB_NONE) ab = guess_alphabet_less_conservatively(seq.data(), seq.size(), thr);
     }
     if (ab == AB_NONE) ab = AB_UNLIMIT;  // SeqParser.Alphabet() with t == nil
@@ -774,12 +865,8 @@ int bsk_stats_string(const bsk_ctx* c, const char* name, const char* format, con
 // ---------------------------------------------------------------------------
 static int stage_shard(bsk_ctx* c, const void* shard, size_t n, int on_device, hipStream_t st, const uint8_t** d) {
     if (on_device) { *d = (const uint8_t*)shard; return BSK_OK; }
-    if (n > c->stage_cap || !c->d_stage[0]) {
-        if (c->d_stage[0]) HIP_TRY(c, hipFree(c->d_stage[0]));
-        c->d_stage[0] = nullptr;
-        HIP_TRY(c, hipMalloc((void**)&c->d_stage[0], n + 16));
-        c->stage_cap = n;
-    }
+    const int rc = stage_reserve(c, 0, n, 0, 16, false, st);
+    if (rc != BSK_OK) return rc;
     HIP_TRY(c, hipMemcpyAsync(c->d_stage[0], shard, n, hipMemcpyHostToDevice, st));
     *d = c->d_stage[0];
     return BSK_OK;
@@ -834,127 +921,69 @@ int bsk_out_materialize(bsk_ctx* c, bsk_out* out, void* stream) {
     return materialize_out(c, out, (hipStream_t)stream);
 }
 
-typedef int (*run_fn)(bsk_ctx*, const uint8_t*, size_t, int, hipStream_t, bsk_out*);
+}  // extern "C"
 
-// runs fn; when the head of a FASTQ shard shows records wrapped over several lines (helper.go:252-269), on the shard
-// rewritten as strict 4-line FASTQ
-static int run_maybe_multiline(bsk_ctx* c, run_fn fn, const uint8_t* d, size_t n, int format, hipStream_t st, bsk_out* out) {
-    c->last_kernel_flags = 0;
-    int rc = fn(c, d, n, format, st, out);
-    // (range / head / duplicate print the record text as it stands and deal with wrapped records themselves: records_run_device)
-    const bool wrapped_head = rc == BSK_ERR_MULTILINE_FASTQ;
-    // the head of the shard was 4-line FASTQ and the strict reader gave up further down: wrapped records there?
-    const bool wrapped_later = rc != BSK_OK && !wrapped_head && format == BSK_FORMAT_FASTQ && !c->norm_active &&
-                               (c->last_kernel_flags & STRICT_FASTQ_FLAGS) != 0;
-    if (!wrapped_head && !wrapped_later) return rc;
-    const std::string msg = c->last_error;
-    const int rc0 = rc;
-    const uint8_t* d2 = nullptr;
-    size_t n2 = 0;
-    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), st));
-    rc = normalize_multiline_fastq(c, d, n, st, &d2, &n2);
-    if (rc != BSK_OK) {
-        if (wrapped_later) { c->set_error(msg); return rc0; }  // (not FASTQ under either reader: the first complaint stands)
-        return rc;
-    }
-    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), st));
-    c->norm_active = true;
-    rc = fn(c, d2, n2, format, st, out);
-    c->norm_active = false;
-    return rc;
-}
+// per-call values of the context (partition id, index of the first record, file offset of the shard): written AFTER the
+// call owns the context -- a call that is refused as busy must not change the state of the one that is running (ADVICE r04)
+struct CallValues {
+    const int64_t* pid = nullptr;
+    const int64_t* first_record = nullptr;
+    const uint64_t* base_offset = nullptr;
+};
 
-// pair / common / concat: several FASTQ texts in one buffer (ends[k] = one past text k).  When the strict reader gives up
-// on one of them, every text is rewritten as 4-line FASTQ by itself and the rewritten texts, back to back, take the
-// place of the buffer: *d2 / ends2.  The combined text lives in c->d_norm2.
-static int normalize_pieces(bsk_ctx* c, const uint8_t* d, const std::vector<uint64_t>& ends, hipStream_t st, const uint8_t** d2,
-                            std::vector<uint64_t>* ends2) {
-    ends2->clear();
-    uint64_t total = 0, from = 0;
-    for (size_t k = 0; k < ends.size(); ++k) {
-        const uint8_t* dk = nullptr;
-        size_t nk = 0;
-        HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), st));
-        int rc = normalize_multiline_fastq(c, d + from, ends[k] - from, st, &dk, &nk);
-        if (rc != BSK_OK) return rc;
-        // (a text that does not end with a newline must not run into the next one)
-        uint8_t last = '\n';
-        if (nk) HIP_TRY(c, hipMemcpy(&last, dk + nk - 1, 1, hipMemcpyDeviceToHost));
-        const uint64_t need = total + nk + 1;
-        if (need > c->norm2_cap) {
-            uint8_t* g = nullptr;
-            const uint64_t cap = need + need / 4 + (ends.back() - from) + 256;
-            HIP_TRY(c, hipMalloc((void**)&g, cap));
-            if (total) HIP_TRY(c, hipMemcpy(g, c->d_norm2, total, hipMemcpyDeviceToDevice));
-            if (c->d_norm2) HIP_TRY(c, hipFree(c->d_norm2));
-            c->d_norm2 = g;
-            c->norm2_cap = cap;
-        }
-        if (nk) HIP_TRY(c, hipMemcpyAsync(c->d_norm2 + total, dk, nk, hipMemcpyDeviceToDevice, st));
-        total += nk;
-        if (nk && last != '\n' && k + 1 < ends.size()) {
-            const uint8_t nl = '\n';
-            HIP_TRY(c, hipMemcpyAsync(c->d_norm2 + total, &nl, 1, hipMemcpyHostToDevice, st));
-            total += 1;
-        }
-        HIP_TRY(c, hipStreamSynchronize(st));  // (c->d_norm is written again by the next text)
-        ends2->push_back(total);
-        from = ends[k];
-    }
-    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), st));
-    *d2 = c->d_norm2;
-    return BSK_OK;
-}
-
-// does rc of a multi-text operator call for the multi-line reader?  (the head of a text is wrapped, or the strict reader gave up)
-static bool wants_multiline(bsk_ctx* c, int rc, int format) {
-    if (rc == BSK_ERR_MULTILINE_FASTQ) return true;
-    return rc != BSK_OK && format == BSK_FORMAT_FASTQ && !c->norm_active && (c->last_kernel_flags & STRICT_FASTQ_FLAGS) != 0;
-}
-
-int bsk_index_build(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, void* stream,
-                    uint64_t* n_records) {
+// The prologue of every record entry point, in this order: the caller's output loses its slices; check_run_args; the
+// context's operator must be `want` (none: any operator) and args_ok hold, else "libbsk: not a <want> context<extra>"; the
+// call takes the context and the per-call values land; the status word is cleared and a host shard is staged.  body(d, st)
+// is the rest of the call.
+template <class Body>
+static int record_call(bsk_ctx* c, bsk_out* out, std::optional<Op> want, bool args_ok, const char* extra, const void* shard,
+                       size_t n, int on_device, int format, void* stream, const CallValues& cv, Body body) {
+    if (out) { out->d_seg_src = nullptr; out->d_seg_off = nullptr; out->n_segments = 0; }
     int rc = check_run_args(c, shard, n, format);
     if (rc != BSK_OK) return rc;
+    if (want && (c->op != *want || !args_ok))
+        return fail(c, BSK_ERR_INVALID_ARG, std::string("libbsk: not a ") + op_name(*want) + " context" + extra);
     BSK_ENTER(c);
+    if (cv.pid) c->cur_pid = *cv.pid;
+    if (cv.first_record) c->cur_first_record = *cv.first_record;
+    if (cv.base_offset) c->cur_base_offset = *cv.base_offset;
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), st));
     const uint8_t* d = nullptr;
     rc = stage_shard(c, shard, n, on_device, st, &d);
     if (rc != BSK_OK) return rc;
-    c->last_kernel_flags = 0;
-    rc = build_index(c, d, n, format, st);
-    uint64_t status = 0;
-    if (rc == BSK_OK) {
-        HIP_TRY(c, hipStreamSynchronize(st));
-        HIP_TRY(c, hipMemcpy(&status, c->d_status, sizeof status, hipMemcpyDeviceToHost));
-        rc = kernel_error_to_status(c, status);
-    }
-    // records wrapped over several lines at the head of the shard, or -- the strict reader complained -- further down:
-    // the table then describes the rewritten text (c->d_norm), not the caller's
-    if (rc == BSK_ERR_MULTILINE_FASTQ || (rc != BSK_OK && format == BSK_FORMAT_FASTQ && (c->last_kernel_flags & STRICT_FASTQ_FLAGS))) {
-        const std::string msg = c->last_error;
-        const int rc0 = rc;
-        const uint8_t* d2 = nullptr;
-        size_t n2 = 0;
-        HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), st));
-        rc = normalize_multiline_fastq(c, d, n, st, &d2, &n2);
-        if (rc != BSK_OK) {
-            if (rc0 != BSK_ERR_MULTILINE_FASTQ) { c->set_error(msg); return rc0; }
-            return rc;
-        }
-        HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), st));
-        c->norm_active = true;
-        rc = build_index(c, d2, n2, format, st);
-        c->norm_active = false;
+    return body(d, st);
+}
+
+// bsk_<op>_run of a single-text operator: record_op's function for `want` (fn: another entry point of the operator)
+static int run_record_op(bsk_ctx* c, Op want, const void* shard, size_t n, int on_device, int format, void* stream, bsk_out* out,
+                         const CallValues& cv = CallValues(), run_fn fn = nullptr) {
+    return record_call(c, out, want, out != nullptr, "", shard, n, on_device, format, stream, cv, [&](const uint8_t* d, hipStream_t st) {
+        const run_fn f = fn ? fn : record_op(c).fn;
+        return run_multiline(c, [&](const uint8_t* t, const uint64_t* e) { return f(c, t, e[0], format, st, out); }, d, {n}, format, st);
+    });
+}
+
+extern "C" {
+
+int bsk_index_build(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, void* stream,
+                    uint64_t* n_records) {
+    return record_call(c, nullptr, std::nullopt, true, "", shard, n, on_device, format, stream, CallValues(),
+                       [&](const uint8_t* d, hipStream_t st) {
+        // records wrapped over several lines at the head of the shard, or -- the strict reader complained -- further down:
+        // the table then describes the rewritten text (c->d_norm), not the caller's
+        const int rc = run_multiline(c, [&](const uint8_t* t, const uint64_t* e) {
+            const int rci = build_index(c, t, e[0], format, st);
+            if (rci != BSK_OK) return rci;
+            uint64_t status = 0;
+            HIP_TRY(c, hipStreamSynchronize(st));
+            HIP_TRY(c, hipMemcpy(&status, c->d_status, sizeof status, hipMemcpyDeviceToHost));
+            return kernel_error_to_status(c, status);
+        }, d, {n}, format, st);
         if (rc != BSK_OK) return rc;
-        HIP_TRY(c, hipStreamSynchronize(st));
-        HIP_TRY(c, hipMemcpy(&status, c->d_status, sizeof status, hipMemcpyDeviceToHost));
-        rc = kernel_error_to_status(c, status);
-    }
-    if (rc != BSK_OK) return rc;
-    if (n_records) *n_records = c->table.n;
-    return BSK_OK;
+        if (n_records) *n_records = c->table.n;
+        return BSK_OK;
+    });
 }
 
 int bsk_index_copy(bsk_ctx* c, uint64_t* starts, uint32_t* head_len, uint32_t* seq_len, uint32_t* aux, size_t cap) {
@@ -973,49 +1002,12 @@ int bsk_index_copy(bsk_ctx* c, uint64_t* starts, uint32_t* head_len, uint32_t* s
 
 int bsk_seq_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,
                 bsk_out* out) {
-    if (out) { out->d_seg_src = nullptr; out->d_seg_off = nullptr; out->n_segments = 0; }
-    (void)pid;
-    int rc = check_run_args(c, shard, n, format);
-    if (rc != BSK_OK) return rc;
-    if (c->op != Op::Seq || !out) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: not a SeqTransform context");
-    BSK_ENTER(c);
-    hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), st));
-    const uint8_t* d = nullptr;
-    rc = stage_shard(c, shard, n, on_device, st, &d);
-    if (rc != BSK_OK) return rc;
-    return run_maybe_multiline(c, seq_run_device, d, n, format, st, out);
-}
-
-// per-call values of the context (partition id, index of the first record, file offset of the shard): written AFTER the
-// call owns the context -- a call that is refused as busy must not change the state of the one that is running (ADVICE r04)
-struct CallValues {
-    const int64_t* pid = nullptr;
-    const int64_t* first_record = nullptr;
-    const uint64_t* base_offset = nullptr;
-};
-static int run_record_op(bsk_ctx* c, Op want, const char* what, run_fn fn, const void* shard, size_t n, int on_device,
-                         int format, void* stream, bsk_out* out, const CallValues& cv = CallValues()) {
-    int rc = check_run_args(c, shard, n, format);
-    if (rc != BSK_OK) return rc;
-    if (c->op != want || !out) return fail(c, BSK_ERR_INVALID_ARG, std::string("libbsk: not a ") + what + " context");
-    BSK_ENTER(c);
-    if (cv.pid) c->cur_pid = *cv.pid;
-    if (cv.first_record) c->cur_first_record = *cv.first_record;
-    if (cv.base_offset) c->cur_base_offset = *cv.base_offset;
-    hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), st));
-    const uint8_t* d = nullptr;
-    rc = stage_shard(c, shard, n, on_device, st, &d);
-    if (rc != BSK_OK) return rc;
-    return run_maybe_multiline(c, fn, d, n, format, st, out);
+    return run_record_op(c, Op::Seq, shard, n, on_device, format, stream, out);
 }
 
 int bsk_grep_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,
                  bsk_out* out) {
-    if (out) { out->d_seg_src = nullptr; out->d_seg_off = nullptr; out->n_segments = 0; }
-    (void)pid;
-    return run_record_op(c, Op::Grep, "Grep", grep_run_device, shard, n, on_device, format, stream, out);
+    return run_record_op(c, Op::Grep, shard, n, on_device, format, stream, out);
 }
 
 int bsk_grep_last_count(const bsk_ctx* c, uint64_t* count) {
@@ -1026,134 +1018,71 @@ int bsk_grep_last_count(const bsk_ctx* c, uint64_t* count) {
 
 int bsk_subseq_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,
                    bsk_out* out) {
-    if (out) { out->d_seg_src = nullptr; out->d_seg_off = nullptr; out->n_segments = 0; }
-    (void)pid;
-    return run_record_op(c, Op::Subseq, "SubseqTransform", subseq_run_device, shard, n, on_device, format, stream, out);
+    return run_record_op(c, Op::Subseq, shard, n, on_device, format, stream, out);
 }
 
 int bsk_faidx_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t base_offset,
                   void* stream, bsk_out* out) {
-    if (out) { out->d_seg_src = nullptr; out->d_seg_off = nullptr; out->n_segments = 0; }
-    (void)pid;
-    if (!c) return BSK_ERR_INVALID_ARG;
     CallValues cv;
     cv.base_offset = &base_offset;
-    return run_record_op(c, Op::Faidx, "Faidx", faidx_run_device, shard, n, on_device, format, stream, out, cv);
+    return run_record_op(c, Op::Faidx, shard, n, on_device, format, stream, out, cv);
 }
 
+// pair / common / concat: several texts in one buffer; when the strict reader gives up on one of them, every text is
+// rewritten (run_multiline)
 int bsk_concat_run(bsk_ctx* c, const void* shard, size_t n, size_t n_first, int on_device, int format, void* stream,
                    bsk_out* out) {
-    if (out) { out->d_seg_src = nullptr; out->d_seg_off = nullptr; out->n_segments = 0; }
-    int rc = check_run_args(c, shard, n, format);
-    if (rc != BSK_OK) return rc;
-    if (c->op != Op::Concat || !out || n_first > n) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: not a Concat context / bad argument");
-    BSK_ENTER(c);
-    hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), st));
-    const uint8_t* d = nullptr;
-    rc = stage_shard(c, shard, n, on_device, st, &d);
-    if (rc != BSK_OK) return rc;
-    c->last_kernel_flags = 0;
-    const int rcm = concat_run_device(c, d, n, n_first, format, st, out);
-    if (!wants_multiline(c, rcm, format)) return rcm;
-    const std::string msg = c->last_error;
-    const uint8_t* d2 = nullptr;
-    std::vector<uint64_t> e2;
-    rc = normalize_pieces(c, d, {(uint64_t)n_first, (uint64_t)n}, st, &d2, &e2);
-    if (rc != BSK_OK) { if (rcm != BSK_ERR_MULTILINE_FASTQ) { c->set_error(msg); return rcm; } return rc; }
-    c->norm_active = true;
-    rc = concat_run_device(c, d2, e2[1], e2[0], format, st, out);
-    c->norm_active = false;
-    return rc;
+    return record_call(c, out, Op::Concat, out && n_first <= n, " / bad argument", shard, n, on_device, format, stream, CallValues(),
+                       [&](const uint8_t* d, hipStream_t st) {
+        return run_multiline(c, [&](const uint8_t* t, const uint64_t* e) { return concat_run_device(c, t, e[1], e[0], format, st, out); },
+                             d, {n_first, n}, format, st);
+    });
 }
 
 int bsk_common_run(bsk_ctx* c, const void* shard, size_t n, const uint64_t* file_ends, uint32_t n_files, int on_device,
                    int format, void* stream, bsk_out* out) {
-    if (out) { out->d_seg_src = nullptr; out->d_seg_off = nullptr; out->n_segments = 0; }
-    int rc = check_run_args(c, shard, n, format);
-    if (rc != BSK_OK) return rc;
-    if (c->op != Op::Common || !out || !file_ends || n_files < 2 || n_files > 64 || file_ends[n_files - 1] != n)
-        return fail(c, BSK_ERR_INVALID_ARG, "libbsk: not a Common context / bad argument (2..64 files, file_ends[last] == n)");
-    BSK_ENTER(c);
-    hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), st));
-    const uint8_t* d = nullptr;
-    rc = stage_shard(c, shard, n, on_device, st, &d);
-    if (rc != BSK_OK) return rc;
-    c->last_kernel_flags = 0;
-    const int rcm = common_run_device(c, d, n, file_ends, n_files, format, st, out);
-    if (!wants_multiline(c, rcm, format)) return rcm;
-    const std::string msg = c->last_error;
-    const uint8_t* d2 = nullptr;
-    std::vector<uint64_t> e2;
-    rc = normalize_pieces(c, d, std::vector<uint64_t>(file_ends, file_ends + n_files), st, &d2, &e2);
-    if (rc != BSK_OK) { if (rcm != BSK_ERR_MULTILINE_FASTQ) { c->set_error(msg); return rcm; } return rc; }
-    c->norm_active = true;
-    rc = common_run_device(c, d2, e2.back(), e2.data(), n_files, format, st, out);
-    c->norm_active = false;
-    return rc;
+    const bool args_ok = out && file_ends && n_files >= 2 && n_files <= 64 && file_ends[n_files - 1] == n;
+    return record_call(c, out, Op::Common, args_ok, " / bad argument (2..64 files, file_ends[last] == n)", shard, n, on_device, format,
+                       stream, CallValues(), [&](const uint8_t* d, hipStream_t st) {
+        return run_multiline(c, [&](const uint8_t* t, const uint64_t* e) { return common_run_device(c, t, e[n_files - 1], e, n_files, format, st, out); },
+                             d, std::vector<uint64_t>(file_ends, file_ends + n_files), format, st);
+    });
 }
 
 int bsk_pair_run(bsk_ctx* c, const void* shard, size_t n, size_t n_first, int on_device, int format, void* stream,
                  bsk_out* outs) {
     if (outs) for (int k__ = 0; k__ < 4; ++k__) { outs[k__].d_seg_src = nullptr; outs[k__].d_seg_off = nullptr; outs[k__].n_segments = 0; }
-    int rc = check_run_args(c, shard, n, format);
-    if (rc != BSK_OK) return rc;
-    if (c->op != Op::Pair || !outs || n_first > n) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: not a Pair context / bad argument");
-    BSK_ENTER(c);
-    hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), st));
-    const uint8_t* d = nullptr;
-    rc = stage_shard(c, shard, n, on_device, st, &d);
-    if (rc != BSK_OK) return rc;
-    c->last_kernel_flags = 0;
-    const int rcm = pair_run_device(c, d, n, n_first, format, st, outs);
-    if (!wants_multiline(c, rcm, format)) return rcm;
-    const std::string msg = c->last_error;
-    const uint8_t* d2 = nullptr;
-    std::vector<uint64_t> e2;
-    rc = normalize_pieces(c, d, {(uint64_t)n_first, (uint64_t)n}, st, &d2, &e2);
-    if (rc != BSK_OK) { if (rcm != BSK_ERR_MULTILINE_FASTQ) { c->set_error(msg); return rcm; } return rc; }
-    c->norm_active = true;
-    rc = pair_run_device(c, d2, e2[1], e2[0], format, st, outs);
-    c->norm_active = false;
-    return rc;
+    return record_call(c, nullptr, Op::Pair, outs && n_first <= n, " / bad argument", shard, n, on_device, format, stream, CallValues(),
+                       [&](const uint8_t* d, hipStream_t st) {
+        return run_multiline(c, [&](const uint8_t* t, const uint64_t* e) { return pair_run_device(c, t, e[1], e[0], format, st, outs); },
+                             d, {n_first, n}, format, st);
+    });
 }
 
 int bsk_faidx_query_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,
                         bsk_out* out) {
-    if (out) { out->d_seg_src = nullptr; out->d_seg_off = nullptr; out->n_segments = 0; }
-    (void)pid;
-    return run_record_op(c, Op::Faidx, "Faidx", faidx_query_run_device, shard, n, on_device, format, stream, out);
+    return run_record_op(c, Op::Faidx, shard, n, on_device, format, stream, out, CallValues(), faidx_query_run_device);
 }
 
 int bsk_sort_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,
                  bsk_out* out) {
-    if (out) { out->d_seg_src = nullptr; out->d_seg_off = nullptr; out->n_segments = 0; }
-    (void)pid;
-    return run_record_op(c, Op::Sort, "Sort", sort_run_device, shard, n, on_device, format, stream, out);
+    return run_record_op(c, Op::Sort, shard, n, on_device, format, stream, out);
 }
 
 int bsk_rename_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,
                    bsk_out* out) {
-    if (out) { out->d_seg_src = nullptr; out->d_seg_off = nullptr; out->n_segments = 0; }
-    (void)pid;
-    return run_record_op(c, Op::Rename, "Rename", rename_run_device, shard, n, on_device, format, stream, out);
+    return run_record_op(c, Op::Rename, shard, n, on_device, format, stream, out);
 }
 
 int bsk_replace_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,
                     bsk_out* out) {
-    if (out) { out->d_seg_src = nullptr; out->d_seg_off = nullptr; out->n_segments = 0; }
-    (void)pid;
     if (c) c->nr_base = 0;  // {nr} counts the records of this call from 1
-    return run_record_op(c, Op::Replace, "Replace", replace_run_device, shard, n, on_device, format, stream, out);
+    return run_record_op(c, Op::Replace, shard, n, on_device, format, stream, out);
 }
 
 int bsk_fq2fa_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,
                   bsk_out* out) {
-    if (out) { out->d_seg_src = nullptr; out->d_seg_off = nullptr; out->n_segments = 0; }
-    (void)pid;
-    return run_record_op(c, Op::Fq2Fa, "Fq2Fa", fq2fa_run_device, shard, n, on_device, format, stream, out);
+    return run_record_op(c, Op::Fq2Fa, shard, n, on_device, format, stream, out);
 }
 
 int bsk_range_needs_count(const bsk_ctx* c, int* needs) {
@@ -1176,43 +1105,32 @@ int bsk_range_bounds(const bsk_ctx* c, int64_t* start, int64_t* end) {
 
 int bsk_range_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                   void* stream, bsk_out* out) {
-    if (out) { out->d_seg_src = nullptr; out->d_seg_off = nullptr; out->n_segments = 0; }
-    (void)pid;
-    if (!c) return BSK_ERR_INVALID_ARG;
     const int64_t fr = (int64_t)first_record;
     CallValues cv;
     cv.first_record = &fr;
-    return run_record_op(c, c->op == Op::Head ? Op::Head : Op::Range, "Range", records_run_device, shard, n, on_device,
-                         format, stream, out, cv);
+    return run_record_op(c, c && c->op == Op::Head ? Op::Head : Op::Range, shard, n, on_device, format, stream, out, cv);
 }
 
 int bsk_duplicate_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,
                       bsk_out* out) {
-    if (out) { out->d_seg_src = nullptr; out->d_seg_off = nullptr; out->n_segments = 0; }
-    (void)pid;
-    return run_record_op(c, Op::Duplicate, "Duplicate", records_run_device, shard, n, on_device, format, stream, out);
+    return run_record_op(c, Op::Duplicate, shard, n, on_device, format, stream, out);
 }
 
 int bsk_locate_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,
                    bsk_out* out) {
-    if (out) { out->d_seg_src = nullptr; out->d_seg_off = nullptr; out->n_segments = 0; }
     CallValues cv;
     cv.pid = &pid;
-    return run_record_op(c, Op::Locate, "Locate", locate_run_device, shard, n, on_device, format, stream, out, cv);
+    return run_record_op(c, Op::Locate, shard, n, on_device, format, stream, out, cv);
 }
 
 int bsk_translate_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,
                       bsk_out* out) {
-    if (out) { out->d_seg_src = nullptr; out->d_seg_off = nullptr; out->n_segments = 0; }
-    (void)pid;
-    return run_record_op(c, Op::Translate, "Translate", translate_run_device, shard, n, on_device, format, stream, out);
+    return run_record_op(c, Op::Translate, shard, n, on_device, format, stream, out);
 }
 
 int bsk_rmdup_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,
                   bsk_out* out) {
-    if (out) { out->d_seg_src = nullptr; out->d_seg_off = nullptr; out->n_segments = 0; }
-    (void)pid;
-    return run_record_op(c, Op::RmDup, "RmDup", rmdup_run_device, shard, n, on_device, format, stream, out);
+    return run_record_op(c, Op::RmDup, shard, n, on_device, format, stream, out);
 }
 
 // ---- rmdup across ranks: the phases between which the caller runs the all-to-all exchanges (include/bsk.h)
@@ -1230,27 +1148,13 @@ int bsk_rmdup_dist_keys(bsk_ctx* c, const void* d_shard, size_t n, int format, v
     rc = check_run_args(c, d_shard, n, format);
     if (rc != BSK_OK) return rc;
     if (!n_records) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: null n_records");
-    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), (hipStream_t)stream));
     hipStream_t st = (hipStream_t)stream;
-    c->last_kernel_flags = 0;
-    int rcm = rmdup_dist_keys(c, (const uint8_t*)d_shard, n, format, st, n_records);
+    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), st));
     // records wrapped over several lines (at the head of the shard, or further down where the strict reader gave up): the
     // phases run on the shard rewritten as 4-line FASTQ -- it lives in the context until the next rewrite, and the emit
     // phase reads it from there (c->dist_buf); round 4 (before: refused, VERDICT r03 missing 5)
-    if (wants_multiline(c, rcm, format)) {
-        const std::string msg = c->last_error;
-        const int rc0 = rcm;
-        const uint8_t* d2 = nullptr;
-        size_t n2 = 0;
-        HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), st));
-        rcm = normalize_multiline_fastq(c, (const uint8_t*)d_shard, n, st, &d2, &n2);
-        if (rcm != BSK_OK) { if (rc0 != BSK_ERR_MULTILINE_FASTQ) { c->set_error(msg); return rc0; } return rcm; }
-        HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), st));
-        c->norm_active = true;
-        rcm = rmdup_dist_keys(c, d2, n2, format, st, n_records);
-        c->norm_active = false;
-    }
-    return rcm;
+    return run_multiline(c, [&](const uint8_t* t, const uint64_t* e) { return rmdup_dist_keys(c, t, e[0], format, st, n_records); },
+                         (const uint8_t*)d_shard, {n}, format, st);
 }
 
 // tests: the two keys of every record of the shard of the last bsk_rmdup_dist_keys, in record order (k2 == NULL: k1 alone --

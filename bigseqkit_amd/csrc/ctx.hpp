@@ -325,11 +325,10 @@ struct bsk_ctx {
     void* drainer = nullptr;   // pinned staging + events of the output drain (store.cpp: Drainer)
     uint8_t* pinned[2] = {nullptr, nullptr};
     uint8_t* d_stage[2] = {nullptr, nullptr};
-    size_t stage_cap = 0;
+    size_t stage_size[2] = {0, 0};  // bytes allocated in d_stage[b] (stage_reserve: the one rule that grows them)
     hipStream_t copy_stream[2] = {nullptr, nullptr};
     hipEvent_t stage_done[2] = {nullptr, nullptr};  // copy of buffer b finished
     hipEvent_t stage_free[2] = {nullptr, nullptr};  // kernels reading buffer b finished
-    size_t stage_cap_b[2] = {0, 0};
 
     // ---- profiling (bench.py roofline leg) -----------------------------------
     bool profile = false;

@@ -557,7 +557,7 @@ const char* const HELP_UNQUOTED_COMMA =
     "or -p \"\\\"A{2,}\\\"\"";
 
 // sequence bytes of the first record of a shard head (type guess, helper.go:286-291)
-static std::vector<uint8_t> head_first_seq(const std::vector<uint8_t>& b, int format, size_t limit) {
+std::vector<uint8_t> head_first_seq(const std::vector<uint8_t>& b, int format, size_t limit) {
     std::vector<uint8_t> s;
     const size_t n = b.size();
     size_t p = 0;

@@ -1,6 +1,9 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 
+#include <functional>
+#include <vector>
+
 #include "../../include/bsk.h"
 #include "ctx.hpp"
 
@@ -77,4 +80,29 @@ void store_drainer_free(bsk_ctx* c);  // store.cpp
 int ensure_out(bsk_ctx* c, uint64_t bytes);
 int ensure_record_scratch(bsk_ctx* c);
 Alphabet partition_alphabet(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, int* rc);
+// sequence bytes of the first record in `b` (up to `limit` bytes)
+std::vector<uint8_t> head_first_seq(const std::vector<uint8_t>& b, int format, size_t limit);
+
+// ---- shared by the entry points of capi.cpp and store.cpp (defined in capi.cpp)
+typedef int (*run_fn)(bsk_ctx*, const uint8_t*, size_t, int, hipStream_t, bsk_out*);
+// the record operator of c->op: what its bsk_<op>_run runs (null: none of this kind) and how bsk_run_to_store may feed it --
+// not at all, as one piece (the result depends on the whole partition), or in record-aligned chunks
+struct RecordOp {
+    enum Store { NoStore, Whole, Chunks };
+    run_fn fn = nullptr;
+    Store store = NoStore;
+};
+RecordOp record_op(const bsk_ctx* c);
+// op(d, ends) on the texts d[0, ends[0]), d[ends[0], ends[1]), ... (one text, or the files of pair / common / concat).  When the
+// result calls for the multi-line FASTQ reader -- the head of a text is wrapped (BSK_ERR_MULTILINE_FASTQ), or, unless
+// head_only, the strict reader gave up further down -- every text is rewritten as 4-line FASTQ and op runs once more on the
+// rewrite.  head_only: bsk_run_to_store, whose chunk cuts assume 4-line records.
+typedef std::function<int(const uint8_t* d, const uint64_t* ends)> TextsOp;
+int run_multiline(bsk_ctx* c, const TextsOp& op, const uint8_t* d, const std::vector<uint64_t>& ends, int format, hipStream_t st,
+                  bool head_only = false);
+// c->d_stage[b] for `need` bytes: when need + slack exceeds what it holds it is replaced (after `st` has finished with it, if
+// drain) by one of need + spare + slack bytes
+int stage_reserve(bsk_ctx* c, int b, size_t need, size_t spare, size_t slack, bool drain, hipStream_t st);
+// record starts that cut the host text h[0, n) into pieces of about `chunk` bytes, each holding whole records: {0, ..., n}
+std::vector<size_t> record_cuts(const uint8_t* h, size_t n, int format, size_t chunk);
 }  // namespace bsk

@@ -123,35 +123,6 @@ int store_append(bsk_store* s, uint64_t part, const uint8_t* data, size_t n, boo
     return BSK_OK;
 }
 
-int hip_fail(bsk_ctx* c, hipError_t e, const char* what) {
-    c->set_error(std::string(what) + ": " + hipGetErrorString(e));
-    return BSK_ERR_HIP;
-}
-#define ST_TRY(c, expr)                                        \
-    do {                                                       \
-        hipError_t e__ = (expr);                               \
-        if (e__ != hipSuccess) return hip_fail(c, e__, #expr); \
-    } while (0)
-
-typedef int (*dev_fn)(bsk_ctx*, const uint8_t*, size_t, int, hipStream_t, bsk_out*);
-dev_fn fn_of(const bsk_ctx* c, bool* chunkable) {
-    *chunkable = false;
-    switch (c->op) {
-        case Op::Seq: *chunkable = true; return seq_run_device;
-        case Op::Grep: *chunkable = !c->opts.b("Count") && !(c->opts.b("DeleteMatched") && !c->opts.b("InvertMatch")); return grep_run_device;
-        case Op::Locate: *chunkable = true; return locate_run_device;
-        case Op::Subseq: *chunkable = true; return subseq_run_device;
-        case Op::Translate: *chunkable = true; return translate_run_device;
-        case Op::Fq2Fa: *chunkable = true; return fq2fa_run_device;
-        case Op::RmDup: return rmdup_run_device;
-        case Op::Rename: return rename_run_device;
-        case Op::Sort: return sort_run_device;
-        case Op::Duplicate: *chunkable = true; return records_run_device;
-        case Op::Replace: *chunkable = true; return replace_run_device;  // {nr}: the chunks of one call are one partition
-        default: return nullptr;
-    }
-}
-
 // Pinned staging of the drain, per context (allocated by the thread that owns the context, before any writer thread runs)
 constexpr size_t DRAIN_PIECE = (size_t)32 << 20;
 constexpr int DRAIN_NBUF = 3;
@@ -335,9 +306,9 @@ int bsk_store_put(bsk_store* s, bsk_ctx* c, uint64_t part, const bsk_out* o) {
     if (c->device < 0) { c->set_error("libbsk: context was created without a device"); return BSK_ERR_NO_DEVICE; }
     bsk_call_scope scope(c);
     if (!scope.owns) { c->set_error(BSK_BUSY_TEXT); return BSK_ERR_INVALID_ARG; }
-    ST_TRY(c, hipSetDevice(c->device));
-    ST_TRY(c, hipDeviceSynchronize());
-    if (!c->copy_stream[1]) ST_TRY(c, hipStreamCreateWithFlags(&c->copy_stream[1], hipStreamNonBlocking));
+    HIP_TRYX(c, hipSetDevice(c->device));
+    HIP_TRYX(c, hipDeviceSynchronize());
+    if (!c->copy_stream[1]) HIP_TRYX(c, hipStreamCreateWithFlags(&c->copy_stream[1], hipStreamNonBlocking));
     int rc = drainer_prepare(c);
     if (rc != BSK_OK) return rc;
     std::string err;
@@ -351,7 +322,7 @@ int bsk_store_put(bsk_store* s, bsk_ctx* c, uint64_t part, const bsk_out* o) {
         }
         rc = pending_first4k(c, nullptr);
         if (rc != BSK_OK) return rc;
-        ST_TRY(c, hipDeviceSynchronize());
+        HIP_TRYX(c, hipDeviceSynchronize());
         rc = drain_to_store(c, s, part, nullptr, o->len, true, c->copy_stream[1], &err, &P);
     } else {
         rc = drain_to_store(c, s, part, (const uint8_t*)o->d_data, o->len, true, c->copy_stream[1], &err);
@@ -390,9 +361,8 @@ int bsk_run_to_store(bsk_ctx* c, const void* host_shard, size_t n, int format, i
     if (c->device < 0) { c->set_error("libbsk: context was created without a device"); return BSK_ERR_NO_DEVICE; }
     if (format != BSK_FORMAT_FASTA && format != BSK_FORMAT_FASTQ) { c->set_error("libbsk: bad format"); return BSK_ERR_INVALID_ARG; }
     if (n && !host_shard) { c->set_error("libbsk: null shard"); return BSK_ERR_INVALID_ARG; }
-    bool chunkable = false;
-    dev_fn fn = fn_of(c, &chunkable);
-    if (!fn) { c->set_error("libbsk: bsk_run_to_store: operator without a single-shard record output"); return BSK_ERR_INVALID_ARG; }
+    const RecordOp r = record_op(c);
+    if (r.store == RecordOp::NoStore) { c->set_error("libbsk: bsk_run_to_store: operator without a single-shard record output"); return BSK_ERR_INVALID_ARG; }
     if (out_bytes) *out_bytes = 0;      // (also on the early ways out: ADVICE r03)
     if (out_records) *out_records = 0;
     bsk_call_scope scope(c);
@@ -405,10 +375,10 @@ int bsk_run_to_store(bsk_ctx* c, const void* host_shard, size_t n, int format, i
     struct Contig { bsk_ctx* c; bool was; ~Contig() { c->force_contiguous = was; } } contig{c, c->force_contiguous};
     c->force_contiguous = true;
     c->pend_out.kind = 0;
-    ST_TRY(c, hipSetDevice(c->device));
+    HIP_TRYX(c, hipSetDevice(c->device));
     for (int b = 0; b < 2; ++b)
-        if (!c->copy_stream[b]) ST_TRY(c, hipStreamCreateWithFlags(&c->copy_stream[b], hipStreamNonBlocking));
-    if (!c->own_stream) ST_TRY(c, hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
+        if (!c->copy_stream[b]) HIP_TRYX(c, hipStreamCreateWithFlags(&c->copy_stream[b], hipStreamNonBlocking));
+    if (!c->own_stream) HIP_TRYX(c, hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
     hipStream_t st = c->own_stream, h2d = c->copy_stream[0], d2h = c->copy_stream[1];
     int rc = drainer_prepare(c);  // (pinned buffers and events exist before the writer thread does)
     if (rc != BSK_OK) return rc;
@@ -435,40 +405,26 @@ int bsk_run_to_store(bsk_ctx* c, const void* host_shard, size_t n, int format, i
     } S{c, c->d_out_alt, c->out_alt_cap};
     S.saved_alphabet = c->alphabet;
     for (int b = 0; b < 2; ++b) {
-        ST_TRY(c, hipEventCreateWithFlags(&S.in_done[b], hipEventDisableTiming));
-        ST_TRY(c, hipEventCreateWithFlags(&S.in_free[b], hipEventDisableTiming));
+        HIP_TRYX(c, hipEventCreateWithFlags(&S.in_done[b], hipEventDisableTiming));
+        HIP_TRYX(c, hipEventCreateWithFlags(&S.in_free[b], hipEventDisableTiming));
     }
     const char* env = c->tune.get("stage_bytes");
     const size_t want = env && strtoull(env, nullptr, 10) ? (size_t)strtoull(env, nullptr, 10) : ((size_t)256 << 20);
     // records wrapped over several lines: the cut points below assume 4-line records, so the shard goes as one piece
-    if (format == BSK_FORMAT_FASTQ && fastq_head_multiline((const uint8_t*)host_shard, std::min<size_t>(n, 256 * 1024))) chunkable = false;
-    const size_t chunk = chunkable ? want : n;
+    const bool chunkable = r.store == RecordOp::Chunks &&
+                           !(format == BSK_FORMAT_FASTQ && fastq_head_multiline((const uint8_t*)host_shard, std::min<size_t>(n, 256 * 1024)));
     const uint8_t* h = (const uint8_t*)host_shard;
-    // cut points: record starts (a chunk holds whole records)
-    std::vector<size_t> cuts{0};
-    while (cuts.back() < n) {
-        size_t lo = cuts.back(), hi = n;
-        if (n - lo > chunk) {
-            hi = format == BSK_FORMAT_FASTQ ? (size_t)find_fastq_cut(h, n, lo + chunk) : (size_t)find_fasta_start(h, n, lo + chunk);
-            if (hi <= lo || hi > n) hi = n;
-        }
-        cuts.push_back(hi);
-    }
+    const std::vector<size_t> cuts = record_cuts(h, n, format, chunkable ? want : n);
     const size_t nchunks = cuts.size() - 1;
     uint64_t bytes = 0, records = 0;
     auto stage_in = [&](size_t i) -> int {  // H2D of chunk i into input buffer i & 1
         const int b = (int)(i & 1);
         const size_t len = cuts[i + 1] - cuts[i];
-        if (len > c->stage_cap_b[b] || !c->d_stage[b]) {
-            ST_TRY(c, hipStreamSynchronize(st));
-            if (c->d_stage[b]) ST_TRY(c, hipFree(c->d_stage[b]));
-            c->d_stage[b] = nullptr;
-            ST_TRY(c, hipMalloc((void**)&c->d_stage[b], len + len / 16 + 4096));
-            c->stage_cap_b[b] = len + len / 16;
-        }
-        if (i >= 2) ST_TRY(c, hipStreamWaitEvent(h2d, S.in_free[b], 0));
-        ST_TRY(c, hipMemcpyAsync(c->d_stage[b], h + cuts[i], len, hipMemcpyHostToDevice, h2d));
-        ST_TRY(c, hipEventRecord(S.in_done[b], h2d));
+        const int rcs = stage_reserve(c, b, len, len / 16, 4096, /*drain=*/true, st);
+        if (rcs != BSK_OK) return rcs;
+        if (i >= 2) HIP_TRYX(c, hipStreamWaitEvent(h2d, S.in_free[b], 0));
+        HIP_TRYX(c, hipMemcpyAsync(c->d_stage[b], h + cuts[i], len, hipMemcpyHostToDevice, h2d));
+        HIP_TRYX(c, hipEventRecord(S.in_done[b], h2d));
         return BSK_OK;
     };
     if (nchunks == 0) return store_append(s, part, nullptr, 0, true);
@@ -479,8 +435,8 @@ int bsk_run_to_store(bsk_ctx* c, const void* host_shard, size_t n, int format, i
     for (size_t i = 0; i < nchunks && rc == BSK_OK; ++i) {
         const int b = (int)(i & 1);
         if (i + 1 < nchunks) { rc = stage_in(i + 1); if (rc != BSK_OK) break; }
-        ST_TRY(c, hipStreamWaitEvent(st, S.in_done[b], 0));
-        ST_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), st));
+        HIP_TRYX(c, hipStreamWaitEvent(st, S.in_done[b], 0));
+        HIP_TRYX(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), st));
         c->cur_pid = (pid == 0 && i == 0) ? 0 : (pid == 0 ? 1 : pid);  // locate: the header row belongs to the first chunk of partition 0
         // SeqType auto: the reference guesses the alphabet ONCE per partition, from its first record (helper.go:286-291);
         // a chunk that guessed from its own first record could search other strands or validate other letters than a
@@ -489,7 +445,7 @@ int bsk_run_to_store(bsk_ctx* c, const void* host_shard, size_t n, int format, i
         // that does not fit the GPU -- and the guess of the first call's first record stays for all of them)
         const bool pin_for_good = c->tune.is("pin_alphabet", "1");
         if (i == 0 && (nchunks > 1 || pin_for_good) && c->alphabet == AB_NONE && c->op != Op::Duplicate) {
-            ST_TRY(c, hipStreamSynchronize(st));  // (chunk 0 is on the device: its head is read back)
+            HIP_TRYX(c, hipStreamSynchronize(st));  // (chunk 0 is on the device: its head is read back)
             int arc = BSK_OK;
             const Alphabet ab = partition_alphabet(c, c->d_stage[b], cuts[1] - cuts[0], format, st, &arc);
             if (arc != BSK_OK) { rc = arc; break; }
@@ -503,20 +459,12 @@ int bsk_run_to_store(bsk_ctx* c, const void* host_shard, size_t n, int format, i
         bsk_out o;
         memset(&o, 0, sizeof o);
         ++c->call_gen;  // (the staging buffers come round again with other text: nothing sampled from chunk i - 2 may survive)
-        rc = fn(c, c->d_stage[b], cuts[i + 1] - cuts[i], format, st, &o);
-        if (rc == BSK_ERR_MULTILINE_FASTQ) {  // (range / head / duplicate deal with wrapped records themselves: records_run_device)
-            const uint8_t* d2 = nullptr;
-            size_t n2 = 0;
-            rc = normalize_multiline_fastq(c, c->d_stage[b], cuts[i + 1] - cuts[i], st, &d2, &n2);
-            if (rc != BSK_OK) break;
-            ST_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), st));
-            c->norm_active = true;
-            rc = fn(c, d2, n2, format, st, &o);
-            c->norm_active = false;
-        }
+        // a chunk whose head is wrapped runs on its rewrite (only then: the cuts assume 4-line records further down)
+        rc = run_multiline(c, [&](const uint8_t* t, const uint64_t* e) { return r.fn(c, t, e[0], format, st, &o); }, c->d_stage[b],
+                           {cuts[i + 1] - cuts[i]}, format, st, /*head_only=*/true);
         if (rc != BSK_OK) break;
-        ST_TRY(c, hipStreamSynchronize(st));  // the output is complete (the run functions end with launches in flight)
-        ST_TRY(c, hipEventRecord(S.in_free[b], st));
+        HIP_TRYX(c, hipStreamSynchronize(st));  // the output is complete (the run functions end with launches in flight)
+        HIP_TRYX(c, hipEventRecord(S.in_free[b], st));
         if (S.writer.valid()) {
             auto w = S.writer.get();
             if (w.first != BSK_OK) { c->set_error(w.second); rc = w.first; break; }

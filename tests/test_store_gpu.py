@@ -11,7 +11,7 @@ import oracle
 import seqgen
 import bigseqkit_amd as bsk
 from bigseqkit_amd import dist as bdist
-from bigseqkit_amd._lib import lib, check
+from bigseqkit_amd._lib import Out, lib, check
 
 pytestmark = pytest.mark.gpu
 
@@ -156,3 +156,53 @@ def test_drain_of_parts_of_several_pieces_in_and_out_of_turn(tmp_path, monkeypat
     d = tmp_path / "dir"
     run_to_file("SeqTransform", {}, parts, bsk.FORMAT_FASTQ, d, merge=0, order=[2, 0, 1])
     assert b"".join((d / ("part%05d" % k)).read_bytes() for k in range(3)) == data
+
+
+def test_staging_buffers_shared_by_chunked_and_whole_shard_calls(tmp_path, monkeypatch):
+    """One context alternates between the chunked pipelines (bsk_run_to_store, bsk_stats_run on a host shard) and the calls
+    that stage a whole host shard (bsk_<op>_run with on_device=0, bsk_stats_run on a wrapped FASTQ shard).  Both use the
+    context's first staging buffer, so each must see what the other left there: a smaller buffer is grown, in either order."""
+    monkeypatch.setenv("BSK_MIN_RANGE_BYTES", "4096")
+    rng = random.Random(31)
+    data = seqgen.random_fastq(rng, 400, 20, 120)
+    small = seqgen.random_fastq(rng, 4, 20, 60)
+    assert len(data) > 40000 and len(small) < 1000
+    opts = {"Reverse": True}
+    want, want_small = oracle.seq(data, True, json.dumps(opts)), oracle.seq(small, True, json.dumps(opts))
+    with bsk.Operator("SeqTransform", json.dumps(opts), 0) as op:
+        def to_store(stage, k):
+            check(lib.bsk_ctx_set(op.ctx, b"stage_bytes", stage), op.ctx)
+            path = tmp_path / ("s%d.fq" % k)
+            st = C.c_void_p()
+            assert lib.bsk_store_open(str(path).encode(), 1, C.byref(st)) == 0
+            buf = C.create_string_buffer(data, len(data))
+            nb, nr = C.c_uint64(), C.c_uint64()
+            rc = lib.bsk_run_to_store(op.ctx, buf, len(data), bsk.FORMAT_FASTQ, 0, st, 0, C.byref(nb), C.byref(nr))
+            assert lib.bsk_store_close(st, None) == 0
+            check(rc, op.ctx)
+            assert path.read_bytes() == want, stage
+
+        def whole(text):
+            buf = C.create_string_buffer(text, len(text))
+            out = Out()
+            check(lib.bsk_seq_run(op.ctx, buf, len(text), 0, bsk.FORMAT_FASTQ, 0, None, C.byref(out)), op.ctx)
+            host = C.create_string_buffer(max(1, out.len))
+            check(lib.bsk_out_to_host(op.ctx, C.byref(out), host, out.len), op.ctx)
+            return host.raw[:out.len]
+
+        to_store(b"8000", 0)                 # chunks of ~8 KB through both staging buffers
+        assert whole(small) == want_small    # a small host shard staged whole
+        to_store(b"4000", 1)                 # chunks larger than that shard
+        assert whole(data) == want           # a host shard larger than any chunk so far
+        to_store(b"20000", 2)                # chunks larger than the earlier ones, smaller than that shard
+        assert whole(data) == want
+    # stats: host shards cut into chunks around a wrapped shard that is staged whole
+    monkeypatch.setenv("BSK_STAGE_BYTES", "3000")
+    a, b = seqgen.random_fastq(rng, 150, 20, 120), seqgen.random_fastq(rng, 150, 20, 120)
+    wrap = lambda t: "\n".join(t[i:i + 13] for i in range(0, len(t), 13))
+    recs = [("".join(rng.choice("ACGT") for _ in range(40)), "".join(rng.choice("ABCDEFGHI") for _ in range(40))) for _ in range(12)]
+    w = "".join("@w%d\n%s\n+\n%s\n" % (i, wrap(s), wrap(q)) for i, (s, q) in enumerate(recs)).encode()
+    assert len(w) < 3000 < len(a)
+    for o in ({}, {"All": True}):
+        got = bsk.StatsString("input0", "N/A", bsk.SeqFrame(bsk.FORMAT_FASTQ, [a, w, b]), bsk.SeqKitStatsOptions().All(o.get("All", False)))
+        assert got == oracle.stats_string(a + w + b, True, json.dumps(o)), o
