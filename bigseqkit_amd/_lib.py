@@ -124,6 +124,7 @@ SIGNATURES = {
     "bsk_fq2fa_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, _vp, _p(Out)]),
     "bsk_rename_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, _vp, _p(Out)]),
     "bsk_replace_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, _vp, _p(Out)]),
+    "bsk_fa2fq_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, _vp, _p(Out)]),
     "bsk_sort_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, _vp, _p(Out)]),
     "bsk_pair_run": (_i, [_vp, _vp, _sz, _sz, _i, _i, _vp, _p(Out)]),
     "bsk_concat_run": (_i, [_vp, _vp, _sz, _sz, _i, _i, _vp, _p(Out)]),

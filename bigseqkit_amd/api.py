@@ -10,7 +10,7 @@ import os
 
 from . import _lib
 from ._lib import lib, check, BskError, FORMAT_FASTA, FORMAT_FASTQ
-from .options import SeqKitStatsOptions, SeqKitSeqOptions, SeqKitGrepOptions, SeqKitSubseqOptions, SeqKitTranslateOptions, SeqKitRmDupOptions, SeqKitLocateOptions, SeqKitFq2FaOptions, SeqKitHeadOptions, SeqKitDuplicateOptions, SeqKitRenameOptions, SeqKitSortOptions, SeqKitFaidxOptions, SeqKitPairOptions, SeqKitCommonOptions, SeqKitConcatOptions, SeqKitReplaceOptions
+from .options import SeqKitStatsOptions, SeqKitSeqOptions, SeqKitGrepOptions, SeqKitSubseqOptions, SeqKitTranslateOptions, SeqKitRmDupOptions, SeqKitLocateOptions, SeqKitFq2FaOptions, SeqKitHeadOptions, SeqKitDuplicateOptions, SeqKitRenameOptions, SeqKitSortOptions, SeqKitFaidxOptions, SeqKitPairOptions, SeqKitCommonOptions, SeqKitConcatOptions, SeqKitReplaceOptions, SeqKitFa2FqOptions
 
 
 class SeqFrame:
@@ -268,6 +268,11 @@ def Rename(input, o=None, device=0):
 def Replace(input, o, device=0):
     """bigseqkit/replace.go:39-60 (MapPartitions: {nr} counts the records of each shard from 1)"""
     return _run_records("Replace", lib.bsk_replace_run, input, o or SeqKitReplaceOptions(), device)[0]
+
+
+def Fa2Fq(input, o, device=0):
+    """bigseqkit/fa2fq.go:42-56 (MapPartitions; every shard is joined against the same FASTA table)"""
+    return _run_records("Fa2Fq", lib.bsk_fa2fq_run, input, o or SeqKitFa2FqOptions(), device)[0]
 
 
 def Sort(input, o=None, device=0):

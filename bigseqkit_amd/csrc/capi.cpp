@@ -145,6 +145,7 @@ RecordOp record_op(const bsk_ctx* c) {
         case Op::Sort: return {sort_run_device, RecordOp::Whole};
         case Op::Duplicate: return {records_run_device, RecordOp::Chunks};
         case Op::Replace: return {replace_run_device, RecordOp::Chunks};  // {nr}: the chunks of one call are one partition
+        case Op::Fa2Fq: return {fa2fq_run_device, RecordOp::Chunks};  // a join against a table the context holds whole
         case Op::Range: case Op::Head: return {records_run_device, RecordOp::NoStore};
         case Op::Faidx: return {faidx_run_device, RecordOp::NoStore};
         default: return {};  // stats; pair / common / concat read several texts
@@ -296,6 +297,7 @@ int bsk_create(const char* op_name_, const char* opts_json, int device, bsk_ctx*
             case Op::Faidx: validate_faidx_opts(c); break;
             case Op::Common: validate_common_opts(c); break;
             case Op::Replace: validate_replace_opts(c); break;
+            case Op::Fa2Fq: validate_fa2fq_opts(c); break;
             default: break;  // validated by the op's own module once it is built
         }
     } catch (const std::exception& e) {
@@ -364,6 +366,7 @@ void bsk_destroy(bsk_ctx* c) {
         if (c->d_names_aux) hipFree(c->d_names_aux);
         if (c->d_id_prog) hipFree(c->d_id_prog);
         bsk::replace_free(c);
+        bsk::fa2fq_free(c);
         if (c->d_vm_progs) hipFree(c->d_vm_progs);
         if (c->d_id_off) hipFree(c->d_id_off);
         if (c->d_id_len) hipFree(c->d_id_len);
@@ -1078,6 +1081,11 @@ int bsk_replace_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int 
                     bsk_out* out) {
     if (c) c->nr_base = 0;  // {nr} counts the records of this call from 1
     return run_record_op(c, Op::Replace, shard, n, on_device, format, stream, out);
+}
+
+int bsk_fa2fq_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,
+                  bsk_out* out) {
+    return run_record_op(c, Op::Fa2Fq, shard, n, on_device, format, stream, out);
 }
 
 int bsk_fq2fa_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,

@@ -135,6 +135,7 @@ struct bsk_ctx {
     // record is nr_base + 1 (reset by bsk_replace_run and by bsk_run_to_store unless pin_alphabet is set, advanced by every
     // shard or chunk that replace_run_device completes)
     struct ReplaceState* repl = nullptr;
+    struct Fa2FqState* fa2fq = nullptr;  // fa2fq (ops_host_fa2fq.cpp): the FASTA table and its device copy
     uint64_t nr_base = 0;
     uint64_t avg_record_bytes = 0;   // bytes per record in the head of the last indexed shard (0: unknown)
     bsk::RecordTable sparse;         // one-pass index: per-range slices, compacted into `table`

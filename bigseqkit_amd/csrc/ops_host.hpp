@@ -61,6 +61,9 @@ int locate_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hi
 void validate_replace_opts(bsk_ctx* c);
 int replace_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, bsk_out* out);
 void replace_free(bsk_ctx* c);
+void validate_fa2fq_opts(bsk_ctx* c);
+int fa2fq_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, bsk_out* out);
+void fa2fq_free(bsk_ctx* c);
 void validate_records_opts(bsk_ctx* c);
 int range_resolve(bsk_ctx* c, int64_t n_records);
 int fq2fa_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, bsk_out* out);

@@ -74,6 +74,7 @@ Options Options::defaults(Op op) {
             o.fields = {fs("Pattern", ""), fs("Replacement", ""), fi("NrWidth", 1), fb("BySeq", false), fb("IgnoreCase", false),
                         fs("KvFile", ""), fb("KeepUntouch", false), fb("KeepKey", false), fi("KeyCaptIdx", 1), fs("KeyMissRepl", "")};
             break;
+        case Op::Fa2Fq: o.fields = {fs("FastaFile", ""), fb("OnlyPositiveStrand", false)}; break;   // bigseqkit/fa2fq.go:17-23
         case Op::Common:  // bigseqkit/common.go:21-29
             o.fields = {fb("ByName", false), fb("BySeq", false), fb("IgnoreCase", false), fb("OnlyPositiveStrand", false)};
             break;
@@ -228,7 +229,8 @@ bool op_from_name(const std::string& name, Op* out) {
         {"Duplicate", Op::Duplicate}, {"Rename", Op::Rename}, {"RenamePrepare", Op::Rename},
         {"Sort", Op::Sort}, {"Faidx", Op::Faidx}, {"Pair", Op::Pair},
         {"PairPrepare", Op::Pair}, {"Common", Op::Common}, {"CommonPrepare", Op::Common},
-        {"Concat", Op::Concat}, {"ConcatPrepare", Op::Concat}, {"Replace", Op::Replace}};
+        {"Concat", Op::Concat}, {"ConcatPrepare", Op::Concat}, {"Replace", Op::Replace},
+        {"Fa2Fq", Op::Fa2Fq}};
     for (auto& t : tbl)
         if (name == t.n) { *out = t.op; return true; }
     return false;
@@ -254,6 +256,7 @@ const char* op_name(Op op) {
         case Op::Common: return "Common";
         case Op::Concat: return "Concat";
         case Op::Replace: return "Replace";
+        case Op::Fa2Fq: return "Fa2Fq";
     }
     return "";
 }

@@ -33,6 +33,7 @@ _FIELDS = {
     "Concat": ["Full", "Separator"],   # bigseqkit/concat.go:12-16
     "Replace": ["Pattern", "Replacement", "NrWidth", "BySeq", "IgnoreCase", "KvFile", "KeepUntouch", "KeepKey",
                 "KeyCaptIdx", "KeyMissRepl"],   # bigseqkit/replace.go:9-21
+    "Fa2Fq": ["FastaFile", "OnlyPositiveStrand"],   # bigseqkit/fa2fq.go:11-15
     "Common": ["ByName", "BySeq", "IgnoreCase", "OnlyPositiveStrand"],   # bigseqkit/common.go:13-19
     "Faidx": ["UseRegexp", "IgnoreCase", "FullHead", "RegionFile", "Regions"],   # bigseqkit/faidx.go:11-18
     "Sort": ["InNaturalOrder", "BySeq", "ByName", "ByLength", "ByBases", "GapLetters", "Reverse", "IgnoreCase",
@@ -116,3 +117,4 @@ SeqKitPairOptions = _make("Pair")
 SeqKitCommonOptions = _make("Common")
 SeqKitConcatOptions = _make("Concat")
 SeqKitReplaceOptions = _make("Replace")
+SeqKitFa2FqOptions = _make("Fa2Fq")

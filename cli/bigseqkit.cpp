@@ -73,6 +73,7 @@ struct Command {
     const char* use;
     const char* op;  // operator name for bsk_create
     std::vector<Flag> flags;
+    const char* help = nullptr;  // the reference's Long text and flag lines, printed by -h / --help (commands that carry one)
 };
 
 const Command kCommands[] = {
@@ -138,6 +139,21 @@ const Command kCommands[] = {
       {"ignore-case", 'i', BOOL, "IgnoreCase", "false"}, {"kv-file", 'k', STR, "KvFile", ""},
       {"keep-untouch", 'U', BOOL, "KeepUntouch", "false"}, {"keep-key", 'K', BOOL, "KeepKey", "false"},
       {"key-capt-idx", 'I', INT, "KeyCaptIdx", "1"}, {"key-miss-repl", 'm', STR, "KeyMissRepl", ""}}},
+    {"fa2fq", "Fa2Fq",                                                                 // cli/fa2fq.go:28-49
+     {{"fasta-file", 'f', STR, "FastaFile", ""}, {"only-positive-strand", 'P', BOOL, "OnlyPositiveStrand", "false"}},
+     "retrieve corresponding FASTQ records by a FASTA file\n"
+     "Attention:\n"
+     "  1. We assume the FASTA file comes from the FASTQ file,\n"
+     "     so they share sequence IDs, and sequences in FASTA\n"
+     "     should be subseq of sequences in FASTQ file.\n"
+     "\n"
+     "Usage:\n"
+     "  bigseqkit fa2fq [flags]\n"
+     "\n"
+     "Flags:\n"
+     "  -f, --fasta-file string      FASTA file)\n"
+     "  -h, --help                   help for fa2fq\n"
+     "  -P, --only-positive-strand   only search on positive strand\n"},
     {"faidx", "Faidx",                                                                 // cli/faidx.go:68-72
      {{"use-regexp", 'r', BOOL, "UseRegexp", "false"}, {"ignore-case", 'i', BOOL, "IgnoreCase", "false"},
       {"full-head", 'f', BOOL, "FullHead", "false"}, {"region-file", 'l', STR, "RegionFile", ""},
@@ -303,6 +319,7 @@ Invocation parse_invocation(const std::vector<std::string>& args) {
         std::string a = argv(i);
         if (a == "--") { for (int k = i + 1; k < argc; ++k) files.push_back(argv(k)); break; }
         if (a.size() < 2 || a[0] != '-' || a == "-") { files.push_back(a); continue; }
+        if (cmd->help && (a == "-h" || a == "--help")) { std::cout << cmd->help; exit(0); }
         std::vector<std::pair<const Flag*, std::string>> parsed;  // flag, inline value ("\x01" = none)
         if (a[1] == '-') {
             std::string name = a.substr(2), v = "\x01";
@@ -485,6 +502,7 @@ int run_op(const std::string& use, bsk_ctx* ctx, const Part& in, int64_t pid, ui
     if (use == "fq2fa") return bsk_fq2fa_run(ctx, p, n, dev, in.fmt, pid, nullptr, out);
     if (use == "rename") return bsk_rename_run(ctx, p, n, dev, in.fmt, pid, nullptr, out);
     if (use == "replace") return bsk_replace_run(ctx, p, n, dev, in.fmt, pid, nullptr, out);
+    if (use == "fa2fq") return bsk_fa2fq_run(ctx, p, n, dev, in.fmt, pid, nullptr, out);
     if (use == "sort") return bsk_sort_run(ctx, p, n, dev, in.fmt, pid, nullptr, out);
     if (use == "faidx" && g_faidx_query) return bsk_faidx_query_run(ctx, p, n, dev, in.fmt, pid, nullptr, out);
     if (use == "faidx") return bsk_faidx_run(ctx, p, n, dev, in.fmt, pid, first_record /* = byte offset here */, nullptr, out);
@@ -867,11 +885,11 @@ static bool parallel_pread(int fd, uint8_t* buf, size_t len, size_t off, int thr
 
 int run_devices(const Invocation& inv) {
     const std::string use = inv.cmd->use;
-    static const char* const kStreamed[] = {"seq", "grep", "locate", "subseq", "translate", "fq2fa", "replace"};
+    static const char* const kStreamed[] = {"seq", "grep", "locate", "subseq", "translate", "fq2fa", "replace", "fa2fq"};
     bool streamed = false;
     for (const char* u : kStreamed) streamed = streamed || use == u;
     if (!streamed && use != "stats" && use != "rmdup")
-        die("'" + use + "' runs on one device (bigseqkit " + use + " ... --device N); several GPUs: fq2fa, grep, locate, replace, rmdup, seq, stats, subseq, translate");
+        die("'" + use + "' runs on one device (bigseqkit " + use + " ... --device N); several GPUs: fa2fq, fq2fa, grep, locate, replace, rmdup, seq, stats, subseq, translate");
     if (inv.files.size() != 1) die("--devices: exactly one input file (it is cut into one shard per GPU)");
     const std::vector<int> devices = parse_devices(inv.pget("devices"));
     const int world = (int)devices.size();

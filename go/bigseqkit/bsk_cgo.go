@@ -13,6 +13,7 @@
 //   Locate                bigseqkit/locate.go:122-134   MapPartitionsWithIndex(Locate)
 //   Subseq                bigseqkit/subseq.go:86-100    MapPartitions(SubseqTransform)
 //   Translate             bigseqkit/translate.go:87-100 MapPartitions(Translate)
+//   Fa2Fq                 bigseqkit/fa2fq.go:42-56      MapPartitions(Fa2Fq)
 //   RmDup                 bigseqkit/rmdup.go:70-108     MapPartitions(RmDupPrepare) + GroupByKey + Flatmap(RmDupCheck)
 //   ReadFASTA/Q[N]        bigseqkit/helper.go:148-178   PlainFile(path, delim) + ReadFixer
 //   StoreFASTX[N]         bigseqkit/helper.go:180-195   SaveAsTextFile / FileStore
@@ -41,6 +42,7 @@ static bsk_run_fn bsk_fn_subseq(void)    { return bsk_subseq_run; }
 static bsk_run_fn bsk_fn_translate(void) { return bsk_translate_run; }
 static bsk_run_fn bsk_fn_rmdup(void)     { return bsk_rmdup_run; }
 static bsk_run_fn bsk_fn_replace(void)   { return bsk_replace_run; }
+static bsk_run_fn bsk_fn_fa2fq(void)     { return bsk_fa2fq_run; }
 */
 import "C"
 
@@ -376,6 +378,15 @@ func Translate(input *SeqFrame, o *SeqKitTranslateOptions) (*Result, error) {
 func Replace(input *SeqFrame, o *SeqKitReplaceOptions) (*Result, error) {
 	o.setDefaults()
 	return mapPartitions("Replace", C.bsk_fn_replace(), OptionsToString(o), input, nil, workersFor(input))
+}
+
+// Fa2Fq: bigseqkit/fa2fq.go:42-56 (every partition is joined against the FASTA table its context read)
+func Fa2Fq(input *SeqFrame, o *SeqKitFa2FqOptions) (*Result, error) {
+	if o == nil {
+		o = &SeqKitFa2FqOptions{}
+	}
+	o.setDefaults()
+	return mapPartitions("Fa2Fq", C.bsk_fn_fa2fq(), OptionsToString(o), input, nil, workersFor(input))
 }
 
 // RmDup: bigseqkit/rmdup.go:70-108.  Duplicates are global (GroupByKey): the partitions of this process are joined and

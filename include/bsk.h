@@ -339,6 +339,17 @@ int bsk_replace_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, in
  * the expression `expr`; *len = bytes of the result (BSK_ERR_CAPACITY when it exceeds `cap`).  Needs no device. */
 int bsk_regex_replace(const char* expr, const char* repl, const uint8_t* text, size_t n, uint8_t* out, size_t cap, size_t* len);
 
+/* ---- Fa2Fq (bigseqkit-lib/fa2fq.go:29-120, options bigseqkit/fa2fq.go:11-23; what is computed: PARITY.md FA2FQ): the
+ * FASTQ records whose ID names a record of the FASTA file `FastaFile` (read by bsk_create; keyed by full name) and whose
+ * sequence holds that record's sequence -- on the read as given, else, unless OnlyPositiveStrand, on its reverse
+ * complement (qualities reversed).  Each is written as "@ID\n" + the matched slice + "\n+\n" + its qualities + "\n", in
+ * input order; the others leave nothing.  The table is uploaded by the context's first run and stays until bsk_destroy.
+ * A FASTA shard is BSK_ERR_FORMAT ("this command only works for FASTQ format"); a table that does not fit into device
+ * memory beside the shard, or an output record of 2^32 bytes or more, is BSK_ERR_UNSUPPORTED.  The result is always one
+ * block (out->d_data), also with the switch out = slices. */
+int bsk_fa2fq_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,
+                  bsk_out* out);
+
 /* ---- Fq2Fa (bigseqkit-lib/fq2fa.go:16-59): every record as FASTA, the sequence on one line (Format(0)). */
 int bsk_fq2fa_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,
                   bsk_out* out);
