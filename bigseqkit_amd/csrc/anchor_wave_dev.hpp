@@ -143,5 +143,36 @@ __device__ __forceinline__ uint64_t find_fastq_start(const uint8_t* buf, uint64_
     return n;
 }
 
+// Where the FASTQ range that begins at the nominal boundary `from` (> 0) really begins: the first record start at or after
+// it.  ONE rule for k_prep (which stores it in anchors[]) and for k_stats (whose waves compute the start and the end of the
+// range they pulled themselves: two neighbours then agree on their common boundary by construction).
+// No record start within reach (text that is not FASTQ): the range begins at the raw boundary.  The streaming pass
+// validates every line it reads, so it reports the malformed text itself -- a check of the anchors inside its range loop
+// cost k_stats two spilled registers and 1 ms at 100 GB.
+__device__ __forceinline__ uint64_t fastq_range_start(const uint8_t* buf, uint64_t n, uint64_t from) {
+    const uint64_t a = find_fastq_start(buf, n, from, from + ANCHOR_SEARCH_BYTES);
+    return a == ANCHOR_NONE ? from : a;
+}
+
+// bsk::effective_end (anchor.hpp: the shard without its trailing blank lines -- of k trailing line feeds one stays; a
+// shard of line feeds alone is empty) with the whole wave looking at 64 bytes per step.  Every wave of a k_stats that
+// runs without k_prep needs it; byte by byte a shard that ends in a long run of blank lines would cost each of them
+// that walk.
+__device__ __forceinline__ uint64_t effective_end(const uint8_t* __restrict__ buf, uint64_t n) {
+    const uint32_t lane = threadIdx.x & 63u;
+    uint64_t k = 0;  // trailing line feeds
+    while (k < n) {
+        const uint64_t left = n - k;
+        const bool nl = lane < left && buf[left - 1u - lane] == '\n';
+        const uint64_t other = ~__ballot(nl);  // lanes that saw another byte, or none
+        const uint32_t run = other ? (uint32_t)__ffsll((long long)other) - 1u : 64u;
+        k += run;
+        if (run < 64u) break;
+    }
+    if (k > n) k = n;  // (the last step looked past the start of the buffer: lanes without a byte end the run)
+    if (k == n) return 0;
+    return k >= 2u ? n - (k - 1u) : n;
+}
+
 }  // namespace wave_anchor
 }  // namespace bsk

@@ -108,7 +108,7 @@ int init_device(bsk_ctx* c) {
     apply_tuning(c);
     HIP_TRY(c, hipMalloc((void**)&c->d_ctl, bsk_ctx::CTL_WORDS * sizeof(uint64_t)));
     HIP_TRY(c, hipMemset(c->d_ctl, 0, bsk_ctx::CTL_WORDS * sizeof(uint64_t)));
-    c->d_status = c->d_ctl;        // [2]: scratch of bsk_stats_collect
+    c->d_status = c->d_ctl;
     c->d_counter = c->d_ctl + 8;
     c->d_fin = c->d_ctl + 16;
     HIP_TRY(c, hipHostMalloc((void**)&c->h_ctl, bsk_ctx::CTL_WORDS * sizeof(uint64_t), hipHostMallocDefault));
@@ -344,6 +344,8 @@ void bsk_destroy(bsk_ctx* c) {
         if (c->d_rng) hipFree(c->d_rng);
         if (c->d_parts) hipFree(c->d_parts);
         if (c->d_vec) hipFree(c->d_vec);
+        if (c->d_pack) hipFree(c->d_pack);
+        if (c->h_pack) hipHostFree(c->h_pack);
         if (c->d_ctl) hipFree(c->d_ctl);
         if (c->h_ctl) hipHostFree(c->h_ctl);
         if (c->h_head) hipHostFree(c->h_head);
@@ -436,8 +438,12 @@ int bsk_stats_reset(bsk_ctx* c, void* stream) {
     if (c->device < 0) return fail(c, BSK_ERR_NO_DEVICE, "libbsk: context was created without a device");
     BSK_ENTER(c);
     hipStream_t st = (hipStream_t)stream;
+    // (the context's own vector is cleared whether the last run used it or a caller's: 2.5 us of device time -- it is also
+    // written by the in-place all-reduce of bsk_stats_collect_reduced on a rank that ran nothing)
     HIP_TRY(c, hipMemsetAsync(c->d_vec, 0, ((size_t)STATS_HDR + c->hist_cap) * sizeof(uint64_t), st));
-    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), st));
+    // the whole control block in one clear: the status words and, behind the FIN_* words, the range queue of k_stats (zero
+    // between two kernels anyway -- unless one was cut short: a reset is what brings the queue back then)
+    HIP_TRY(c, hipMemsetAsync(c->d_ctl, 0, bsk_ctx::CTL_WORDS * sizeof(uint64_t), st));
     c->vec_reduced = false;
     return BSK_OK;
 }
@@ -456,8 +462,27 @@ static int stats_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int form
     // 16-byte aligned nominal chunk so that most range starts keep tile alignment cheap
     uint64_t chunk = (n + nranges - 1) / nranges;
     chunk = (chunk + 15) & ~(uint64_t)15;
-    int rc = ensure_ranges(c, nranges);
-    if (rc != BSK_OK) return rc;
+    // FASTQ: no k_prep in front of k_stats -- its waves find the range behind a queue ticket themselves (stream_stats.hpp);
+    // stats_prep=pass keeps the pass and its anchors[] (the tests hold the two against each other)
+    // (the default row on the DPP scan: the kernels of `-a` and of scan=shfl have no registers for the search, stream_stats.hip)
+    const bool self_anchor = fastq && !all && c->use_dpp && !c->tune.is("stats_prep", "pass");
+    uint32_t tickets = nranges, nsplit = nranges;
+    if (self_anchor) {
+        chunk = (chunk + 63) & ~(uint64_t)63;  // (a quarter of it stays 16-byte aligned)
+        // the last sixteenth of the shard goes out in quarter chunks: the waves then run dry within a quarter of a range's
+        // time of each other.  Never below min_range_bytes, and not below 192 KiB (stats_tail=<bytes> moves that floor,
+        // stats_tail=uniform keeps one size): a range pays its start-up -- two anchor searches, the LDS window, the edge
+        // tiles -- and quarters of 128 KiB made the 12.5 GB step slower, not faster (profiles/stats_step_fixed_costs.md)
+        const uint64_t tail = nranges / 16, small = chunk / 4;
+        const uint64_t floor_bytes = std::max<uint64_t>(c->min_range_bytes, (uint64_t)c->tune.num("stats_tail", 192 << 10));
+        if (tail && small >= floor_bytes && !c->tune.is("stats_tail", "uniform") && (uint64_t)(nranges - tail) * chunk < n) {
+            nsplit = (uint32_t)(nranges - tail);
+            tickets = nsplit + (uint32_t)((n - (uint64_t)nsplit * chunk + small - 1) / small);
+        }
+    } else {
+        int rc = ensure_ranges(c, nranges);
+        if (rc != BSK_OK) return rc;
+    }
     // overflow list for lengths >= hist_cap
     const uint64_t need = n / c->hist_cap + 1024;
     if (need > c->overflow_cap) {
@@ -496,8 +521,10 @@ static int stats_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int form
         for (char ch : uniq) top = std::max(top, (uint32_t)(uint8_t)ch);
         D.pred.kgap = top >= 127u ? 0xFFFFFFFFu : (0x80u - (top + 1u)) * 0x01010101u;
     }
-    uint64_t* anchors = c->d_anchors;
-    uint32_t* queue = reinterpret_cast<uint32_t*>(c->d_anchors + (size_t)nranges + 1);
+    // (without k_prep: the queue is two words of the control block, zero whenever no k_stats runs)
+    uint64_t* anchors = self_anchor ? nullptr : c->d_anchors;
+    uint32_t* queue = self_anchor ? reinterpret_cast<uint32_t*>(c->d_ctl + bsk_ctx::CTL_STATS_QUEUE)
+                                  : reinterpret_cast<uint32_t*>(c->d_anchors + (size_t)nranges + 1);
     D.r_head = D.r_tail = nullptr;
     D.r_flags = nullptr;
     if (!fastq) {
@@ -513,7 +540,7 @@ static int stats_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int form
         D.r_flags = reinterpret_cast<uint32_t*>(c->d_rng + 2 * (size_t)nranges);
         HIP_TRY(c, hipMemsetAsync(c->d_rng, 0, (size_t)nranges * 20, st));
     }
-    {
+    if (!self_anchor) {
         Timed t(c, "k_prep", st);
         HIP_TRY(c, launch_prep(fastq, d_buf, n, chunk, nranges, anchors, queue, st, /*line_mode=*/!fastq,
                                /*raw=*/fastq ? nullptr : c->d_anchors + (size_t)nranges + 2));
@@ -522,8 +549,8 @@ static int stats_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int form
         Timed t(c, "k_stats", st);
         // FASTA: a line longer than a chunk is not read between its own chunk and its last tile; with `-a` the gap letters
         // of the chunks it covers are counted by those chunks' (otherwise empty) ranges
-        HIP_TRY(c, launch_stats(fastq, all, c->use_dpp, blocks, d_buf, n, anchors, nranges, queue, D, st, variant,
-                                !fastq ? chunk : 0));
+        HIP_TRY(c, launch_stats(fastq, all, c->use_dpp, blocks, d_buf, n, anchors, tickets, queue, D, st, variant,
+                                !fastq ? chunk : 0, self_anchor ? chunk : 0, nsplit));
     }
     if (!fastq) HIP_TRY(c, launch_stats_stitch(nranges, D, st));
     if (all && (int)gap_letters.size() > MAX_GAP_LETTERS) {
@@ -735,20 +762,34 @@ int bsk_stats_collect(bsk_ctx* c, const void* d_vec, int64_t* keys, int64_t* val
     if (c->device < 0) return fail(c, BSK_ERR_NO_DEVICE, "libbsk: context was created without a device");
     if (!n_out) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: null n_out");
     BSK_ENTER(c);
+    // (device-wide, as ever: the vector may have been written on any stream -- the caller's all-reduce runs on torch's)
     HIP_TRY(c, hipDeviceSynchronize());
-    // only the used part of the 512 KiB histogram crosses PCIe (short reads: a few hundred bins)
     const uint64_t* dv = d_vec ? (const uint64_t*)d_vec : c->d_vec;
-    HIP_TRY(c, launch_hist_extent(dv + STATS_HDR, c->hist_cap, c->d_status + 2, nullptr));
-    uint64_t status[3];
-    HIP_TRY(c, hipMemcpy(status, c->d_status, sizeof status, hipMemcpyDeviceToHost));
+    // ONE kernel and ONE copy into pinned memory bring everything a collect of reads needs: the status words, the extent
+    // of the histogram (one past its highest non-empty bin), the header slots and the first PACK_BINS bins.  Only a
+    // histogram that reaches beyond them (long reads) costs a second copy; of the 512 KiB vector the used part alone
+    // crosses PCIe either way.  (Until round 7: extent kernel, blocking copy of the status into pageable memory, blocking
+    // copy of the prefix whose length came out of the first -- three round trips one after the other.)
+    const uint32_t kbins = std::min<uint32_t>(bsk_ctx::PACK_BINS, c->hist_cap);
+    const size_t pack_words = 8 + (size_t)STATS_HDR + kbins;
+    if (!c->d_pack) HIP_TRY(c, hipMalloc((void**)&c->d_pack, pack_words * sizeof(uint64_t)));
+    if (!c->h_pack) HIP_TRY(c, hipHostMalloc((void**)&c->h_pack, pack_words * sizeof(uint64_t), hipHostMallocDefault));
+    HIP_TRY(c, launch_stats_pack(dv, c->hist_cap, c->d_status, c->d_pack, kbins, nullptr));
+    HIP_TRY(c, hipMemcpyAsync(c->h_pack, c->d_pack, pack_words * sizeof(uint64_t), hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(c, hipStreamSynchronize(nullptr));
+    const uint64_t* status = c->h_pack;  // [0] error flags [1] overflow count [2] extent
     if (status[0]) {
         int code;
         std::string m = describe_kernel_errors(status[0], &code);
         return fail(c, code, m);
     }
-    const size_t len = (size_t)STATS_HDR + (size_t)std::min<uint64_t>(status[2], c->hist_cap);
-    std::vector<uint64_t> v(len);
-    HIP_TRY(c, hipMemcpy(v.data(), dv, len * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    const size_t ext = (size_t)std::min<uint64_t>(status[2], c->hist_cap);
+    const size_t len = (size_t)STATS_HDR + ext;
+    std::vector<uint64_t> v(c->h_pack + 8, c->h_pack + 8 + std::min<size_t>(len, (size_t)STATS_HDR + kbins));
+    if (ext > kbins) {
+        v.resize(len);
+        HIP_TRY(c, hipMemcpy(v.data() + STATS_HDR + kbins, dv + STATS_HDR + kbins, (ext - kbins) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    }
     std::vector<uint64_t> ov;
     if (status[1]) {
         if (status[1] > c->overflow_cap) return fail(c, BSK_ERR_CAPACITY, "libbsk: overflow length list exhausted");

@@ -29,7 +29,7 @@ struct bsk_tuning {
     static const char* const* names() {
         static const char* const N[] = {"filter", "grep_shiftand", "index", "locate_nopre", "long_bytes", "min_range_bytes", "names",
                                         "names_scale", "out", "pin_alphabet", "ranges_per_wave", "replace", "rmdup", "rmdup_buckets", "rmdup_hash", "rmdup_k1_bits", "rmdup_k2_bits", "rmdup_keys", "rmdup_place", "rmdup_xcheck", "rmdup_xlocal", "scan", "segcopy",
-                                        "sort", "stage_bytes", "stats_a", "stats_fasta", "subseq", "subseq_scale", "text", "translate", "translate_index", "translate_probe", "translate_stream", "tr_lanes", nullptr};
+                                        "sort", "stage_bytes", "stats_a", "stats_fasta", "stats_prep", "stats_tail", "subseq", "subseq_scale", "text", "translate", "translate_index", "translate_probe", "translate_stream", "tr_lanes", nullptr};
         return N;
     }
     std::map<std::string, std::string> v;
@@ -90,16 +90,24 @@ struct bsk_ctx {
     uint32_t hist_cap = 1u << 16;
     uint64_t* d_vec = nullptr;       // ctx-owned stats vector
     uint64_t* d_status = nullptr;    // [0] err flags [1] overflow count            (= d_ctl)
+    // bsk_stats_collect's packet: status words [8], header slots and the first PACK_BINS bins -- packed by one kernel
+    // (d_pack), brought to pinned memory (h_pack) by one copy
+    static constexpr uint32_t PACK_BINS = 4096;
+    uint64_t* d_pack = nullptr;
+    uint64_t* h_pack = nullptr;
     // ---- the control block: every scalar a call reads back lives in ONE allocation and comes to the host with ONE copy
     // into pinned memory (ctl_readback).  Round 3 fetched total / kept / long count / status with a copy each: ~17 us of
     // stream time per copy, twenty of them in a `grep` call -- 0.6 ms of a 4.4 ms call.
-    //   d_ctl[0..7]  = d_status ([0] flags [1] stats overflow count [2] collect scratch [3] rmdup overflow-list count;
+    //   d_ctl[0..7]  = d_status ([0] flags [1] stats overflow count [2] free (collect scratch until round 6) [3] rmdup overflow-list count;
     //                  zeroed at the entry of every run)    d_ctl[8..15] = d_counter    d_ctl[16..31] = d_fin (FIN_* below)
+    //   d_fin[FIN_STATS_QUEUE] = the range queue of a k_stats that runs without k_prep (two 32-bit words: next ticket,
+    //                  waves that left; the last wave to leave zeroes both).  Never copied into, never read back.
     uint64_t* d_ctl = nullptr;
     uint64_t* h_ctl = nullptr;       // pinned mirror [CTL_WORDS]
     uint64_t* d_fin = nullptr;
     static constexpr int CTL_WORDS = 32;
-    enum { FIN_TOTAL = 0, FIN_KEPT = 1, FIN_LONG_COUNT = 2, FIN_LONG_MAX = 3, FIN_OTHER = 4, FIN_TABLE_N = 5, FIN_AUX0 = 6, FIN_AUX1 = 7 };
+    enum { FIN_TOTAL = 0, FIN_KEPT = 1, FIN_LONG_COUNT = 2, FIN_LONG_MAX = 3, FIN_OTHER = 4, FIN_TABLE_N = 5, FIN_AUX0 = 6, FIN_AUX1 = 7, FIN_STATS_QUEUE = 8 };
+    static constexpr int CTL_STATS_QUEUE = 16 + FIN_STATS_QUEUE;
     uint64_t fin(int k) const { return h_ctl[16 + k]; }
     uint64_t status_word() const { return h_ctl[0]; }
     // ---- head (and tail) of the shard of the running call, in pinned memory: ONE copy per call serves the alphabet

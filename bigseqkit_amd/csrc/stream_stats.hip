@@ -389,7 +389,7 @@ template <bool FASTQ, bool ALL, bool DPP, bool ROLES_T = true>
 __global__ __launch_bounds__(WAVES_PER_BLOCK * WAVE) BSK_STATS_ATTR void k_stats(const uint8_t* __restrict__ buf, uint64_t n,
                                                                    const uint64_t* __restrict__ anchors,
                                                                    uint32_t nranges, uint32_t* __restrict__ queue,
-                                                                   StatsDev D, uint64_t chunk) {
+                                                                   StatsDev D, uint64_t chunk, uint32_t nsplit) {
     __shared__ uint32_t s_hist[LDS_HIST + 2 * BIG_SLOTS];  // dense bins, then the (length, count) cache of add_big
     constexpr bool ROLES = FASTQ && ALL && ROLES_T;
     constexpr bool SALL = ALL && !ROLES;  // what the skeleton and the events see
@@ -412,14 +412,47 @@ __global__ __launch_bounds__(WAVES_PER_BLOCK * WAVE) BSK_STATS_ATTR void k_stats
     StatsSinkT<ROLES> sink;
     sink.s_hist = s_hist;
     sink.D = D;
-    const uint64_t n_eff = anchors[nranges];
+    // FASTQ without k_prep (anchors == nullptr): no pass in front of this one.  A wave derives the start and the end of the
+    // range it pulled from the ticket alone: the nominal boundaries are a pure function of (ticket, chunk, nsplit) -- whole
+    // chunks up to ticket nsplit, quarter chunks behind it, so that the waves run dry within a quarter of a range's time of
+    // each other -- and the record start behind a boundary is k_prep's rule (wave_anchor::fastq_range_start).  The searches
+    // run before the tile loop: their registers are dead when the streaming starts.
+    // Only the default row on the DPP scan is built this way: the search is hungry for scalar registers, and in the `-a`
+    // kernels (and with scan=shfl) the lanes its spilled ones take cost vector registers that the tile loop needs -- those
+    // keep k_prep (capi.cpp: stats_run_device).
+    constexpr bool SELF = FASTQ && !ALL && DPP;
+    const bool self_anchor = SELF && anchors == nullptr;
+    const uint64_t n_eff = self_anchor ? wave_anchor::effective_end(buf, n) : anchors[nranges];
     uint64_t w20 = 0, w30 = 0, wgap = 0;  // ROLES: wave totals
     for (;;) {
         uint32_t r = 0;
         if (lane == 0) r = atomicAdd(queue, 1u);
         r = wave_first(r);
         if (r >= nranges) break;
-        uint64_t rs = anchors[r], re = anchors[r + 1];
+        uint64_t rs = 0, re = n_eff;
+        if (self_anchor) {
+            if constexpr (SELF) {
+#pragma nounroll
+                for (uint32_t k = 0; k < 2u; ++k) {  // (a loop: one copy of the search in the kernel's text)
+                    const uint32_t t = r + k;
+                    if (t == 0u || t >= nranges) continue;  // the first range begins at 0, the last one ends at n_eff
+                    const uint64_t from = t <= nsplit ? (uint64_t)t * chunk : (uint64_t)nsplit * chunk + (uint64_t)(t - nsplit) * (chunk >> 2);
+                    // The boundary goes through VECTOR registers (the empty asm hides from the compiler that it is
+                    // uniform), and with it every position the search derives from it: kept in scalar registers, of which
+                    // the kernel has none to spare, they were spilled to lanes of vector registers that the tile loop
+                    // then lacked -- 4 spilled VGPRs in the default row (resource report; tests/test_stats_inkernel_resources_cpu.py)
+                    uint32_t flo = (uint32_t)from, fhi = (uint32_t)(from >> 32);
+                    asm volatile("" : "+v"(flo), "+v"(fhi));
+                    const uint64_t av = wave_anchor::fastq_range_start(buf, n, ((uint64_t)fhi << 32) | flo);
+                    const uint64_t a = ((uint64_t)wave_first((uint32_t)(av >> 32)) << 32) | wave_first((uint32_t)av);
+                    if (k == 0u) rs = a;
+                    else re = a;
+                }
+            }
+        } else {
+            rs = anchors[r];
+            re = anchors[r + 1];
+        }
         rs = rs < n_eff ? rs : n_eff;
         re = re < n_eff ? re : n_eff;
         if (rs >= re) {
@@ -478,6 +511,14 @@ __global__ __launch_bounds__(WAVES_PER_BLOCK * WAVE) BSK_STATS_ATTR void k_stats
             sink.rq20 = sink.rq30 = sink.rgap = 0;
         }
     }
+    // without k_prep nobody resets the queue in front of the kernel: the wave that leaves last does it behind itself (every
+    // other wave has drawn its last ticket by then), and the context's control block starts out zeroed
+    if (self_anchor && lane == 0) {
+        if (atomicAdd(queue + 1, 1u) == gridDim.x * (uint32_t)WAVES_PER_BLOCK - 1u) {
+            atomicExch(queue + 1, 0u);
+            atomicExch(queue, 0u);
+        }
+    }
     // flush ---------------------------------------------------------------
     const uint64_t q20 = ROLES ? w20 : wave_sum_u64(sink.q20), q30 = ROLES ? w30 : wave_sum_u64(sink.q30),
                    gap = ROLES ? wgap : wave_sum_u64(sink.gap);
@@ -529,11 +570,9 @@ __global__ __launch_bounds__(256) void k_prep(const uint8_t* __restrict__ buf, u
         if (lane0) anchors[r] = a;  // (ANCHOR_NONE stays until k_prep_fill)
         return;
     }
-    const uint64_t a = FASTQ ? wave_anchor::find_fastq_start(buf, n, from, from + ANCHOR_SEARCH_BYTES)
+    // (FASTQ: the rule k_stats applies itself when it runs without this pass, anchor_wave_dev.hpp)
+    const uint64_t a = FASTQ ? wave_anchor::fastq_range_start(buf, n, from)
                              : (line_mode ? wave_anchor::find_line_start(buf, n, from) : wave_anchor::find_fasta_start(buf, n, from));
-    // No record start within reach (text that is not FASTQ): the range begins at the raw boundary.  The streaming pass
-    // validates every line it reads, so it reports the malformed text itself -- a check of the anchors inside its range loop
-    // cost k_stats two spilled registers and 1 ms at 100 GB.
     if (lane0) anchors[r] = a == ANCHOR_NONE ? from : a;
 }
 
@@ -652,21 +691,38 @@ hipError_t launch_prep(bool fastq, const uint8_t* buf, uint64_t n, uint64_t chun
     return hipGetLastError();
 }
 
-// one past the highest non-empty bin of the length histogram (bsk_stats_collect copies only that much to the host)
-__global__ __launch_bounds__(1024) void k_hist_extent(const uint64_t* __restrict__ hist, uint32_t cap, uint64_t* __restrict__ out) {
+// bsk_stats_collect's packet, from the stats vector `vec` (the context's or the caller's) and the context's status words:
+//   pack[0..7] = status[0..7], but pack[2] = one past the highest non-empty bin of the length histogram
+//   pack[8 ..] = vec[0 .. STATS_HDR + kbins): the header slots and the first kbins bins
+// One block: 64 K bins are 512 KiB, eight independent loads per thread and step.
+__global__ __launch_bounds__(1024) void k_stats_pack(const uint64_t* __restrict__ vec, uint32_t cap, const uint64_t* __restrict__ status,
+                                                     uint64_t* __restrict__ pack, uint32_t kbins) {
     __shared__ uint32_t s_hi;
     if (threadIdx.x == 0) s_hi = 0;
     __syncthreads();
+    const uint64_t* hist = vec + STATS_HDR;
     uint32_t hi = 0;
-    for (uint32_t i = threadIdx.x; i < cap; i += 1024u)
-        if (hist[i]) hi = i + 1;
+    for (uint32_t base = threadIdx.x; base < cap; base += 8u * 1024u) {
+        uint64_t h[8];
+#pragma unroll
+        for (uint32_t k = 0; k < 8u; ++k) {
+            const uint32_t i = base + k * 1024u;
+            h[k] = i < cap ? hist[i] : 0ull;
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < 8u; ++k)
+            if (h[k]) hi = base + k * 1024u + 1u;
+    }
     if (hi) atomicMax(&s_hi, hi);
+    for (uint32_t i = threadIdx.x; i < (uint32_t)STATS_HDR + kbins; i += 1024u) pack[8u + i] = vec[i];
+    if (threadIdx.x < 8u && threadIdx.x != 2u) pack[threadIdx.x] = status[threadIdx.x];
     __syncthreads();
-    if (threadIdx.x == 0) *out = s_hi;
+    if (threadIdx.x == 0) pack[2] = s_hi;
 }
 
-hipError_t launch_hist_extent(const uint64_t* hist, uint32_t cap, uint64_t* out, hipStream_t st) {
-    hipLaunchKernelGGL(k_hist_extent, dim3(1), dim3(1024), 0, st, hist, cap, out);
+hipError_t launch_stats_pack(const uint64_t* vec, uint32_t cap, const uint64_t* status, uint64_t* pack, uint32_t kbins, hipStream_t st) {
+    if (kbins > cap) kbins = cap;
+    hipLaunchKernelGGL(k_stats_pack, dim3(1), dim3(1024), 0, st, vec, cap, status, pack, kbins);
     return hipGetLastError();
 }
 
@@ -708,19 +764,20 @@ hipError_t launch_stats_stitch(uint32_t nranges, const StatsDev& D, hipStream_t 
 
 template <bool FASTQ, bool ALL, bool ROLES_T = true>
 static hipError_t launch_stats_t(bool dpp, int blocks, const uint8_t* buf, uint64_t n, const uint64_t* anchors,
-                                 uint32_t nranges, uint32_t* queue, const StatsDev& D, hipStream_t st, uint64_t chunk) {
+                                 uint32_t nranges, uint32_t* queue, const StatsDev& D, hipStream_t st, uint64_t chunk, uint32_t nsplit = 0) {
     const dim3 b(WAVES_PER_BLOCK * WAVE);
-    if (dpp) hipLaunchKernelGGL((k_stats<FASTQ, ALL, true, ROLES_T>), dim3(blocks), b, 0, st, buf, n, anchors, nranges, queue, D, chunk);
-    else hipLaunchKernelGGL((k_stats<FASTQ, ALL, false, ROLES_T>), dim3(blocks), b, 0, st, buf, n, anchors, nranges, queue, D, chunk);
+    if (dpp) hipLaunchKernelGGL((k_stats<FASTQ, ALL, true, ROLES_T>), dim3(blocks), b, 0, st, buf, n, anchors, nranges, queue, D, chunk, nsplit);
+    else hipLaunchKernelGGL((k_stats<FASTQ, ALL, false, ROLES_T>), dim3(blocks), b, 0, st, buf, n, anchors, nranges, queue, D, chunk, nsplit);
     return hipGetLastError();
 }
 
 hipError_t launch_stats(bool fastq, bool all, bool dpp, int blocks, const uint8_t* buf, uint64_t n,
                         const uint64_t* anchors, uint32_t nranges, uint32_t* queue, const StatsDev& D,
-                        hipStream_t st, bool a_dense, uint64_t skip_chunk) {
-    if (fastq && all && a_dense) return launch_stats_t<true, true, false>(dpp, blocks, buf, n, anchors, nranges, queue, D, st, 0);
-    if (fastq) return all ? launch_stats_t<true, true>(dpp, blocks, buf, n, anchors, nranges, queue, D, st, 0)
-                          : launch_stats_t<true, false>(dpp, blocks, buf, n, anchors, nranges, queue, D, st, 0);
+                        hipStream_t st, bool a_dense, uint64_t skip_chunk, uint64_t fq_chunk, uint32_t fq_nsplit) {
+    // (FASTQ: anchors == nullptr -- the waves find their ranges themselves, fq_chunk / fq_nsplit say where; else fq_chunk = 0)
+    if (fastq && all && a_dense) return launch_stats_t<true, true, false>(dpp, blocks, buf, n, anchors, nranges, queue, D, st, fq_chunk, fq_nsplit);
+    if (fastq) return all ? launch_stats_t<true, true>(dpp, blocks, buf, n, anchors, nranges, queue, D, st, fq_chunk, fq_nsplit)
+                          : launch_stats_t<true, false>(dpp, blocks, buf, n, anchors, nranges, queue, D, st, fq_chunk, fq_nsplit);
     // (FASTA: a_dense = the pass that publishes every newline -- with `-a` the dense path with running counters --, stats_fasta=events)
     if (all) return a_dense ? launch_stats_t<false, true, false>(dpp, blocks, buf, n, anchors, nranges, queue, D, st, skip_chunk)
                             : launch_stats_t<false, true>(dpp, blocks, buf, n, anchors, nranges, queue, D, st, skip_chunk);

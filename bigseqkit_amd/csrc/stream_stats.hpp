@@ -61,12 +61,18 @@ hipError_t launch_stats_stitch(uint32_t nranges, const StatsDev& D, hipStream_t 
 struct RecordTable;
 hipError_t launch_gap_set_count(const uint8_t* buf, const RecordTable& t, const uint32_t (&set)[8], bool fastq, uint64_t* gap_slot,
                                 hipStream_t st);
-// *out := one past the highest non-zero entry of hist[0, cap)
-hipError_t launch_hist_extent(const uint64_t* hist, uint32_t cap, uint64_t* out, hipStream_t st);
+// bsk_stats_collect's packet: pack[0..7] = status[0..7] with pack[2] := one past the highest non-zero bin of the histogram
+// vec[STATS_HDR, STATS_HDR + cap); pack[8 ..] = vec[0, STATS_HDR + kbins)
+hipError_t launch_stats_pack(const uint64_t* vec, uint32_t cap, const uint64_t* status, uint64_t* pack, uint32_t kbins, hipStream_t st);
 // skip_chunk (FASTA default row, anchors from launch_prep with `raw`): the nominal chunk size; 0: read every byte
 hipError_t launch_stats(bool fastq, bool all, bool dpp, int blocks, const uint8_t* buf, uint64_t n,
                         const uint64_t* anchors, uint32_t nranges, uint32_t* queue, const StatsDev& D,
-                        hipStream_t st, bool a_dense = false, uint64_t skip_chunk = 0);  // a_dense: FASTQ -a on the dense path (BSK_STATS_A=dense)
+                        hipStream_t st, bool a_dense = false, uint64_t skip_chunk = 0,  // a_dense: FASTQ -a on the dense path (BSK_STATS_A=dense)
+                        uint64_t fq_chunk = 0, uint32_t fq_nsplit = 0);
+// FASTQ with anchors == nullptr: no launch_prep in front.  Every wave computes the start and the end of the range it pulls
+// from `queue` itself: ticket t begins at the first record start at or after t * fq_chunk (t <= fq_nsplit) or
+// fq_nsplit * fq_chunk + (t - fq_nsplit) * (fq_chunk / 4) (behind it); `queue` is two words that are zero when the kernel
+// starts and zero again when it ends.
 int stats_max_blocks_per_cu(bool fastq, bool all, bool dpp, bool a_dense = false);
 hipError_t launch_stream_read(int blocks, const uint8_t* buf, uint64_t n, uint64_t chunk, uint32_t nranges,
                               uint32_t* queue, uint32_t* sink, hipStream_t st);
