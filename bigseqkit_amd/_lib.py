@@ -133,6 +133,11 @@ SIGNATURES = {
     "bsk_faidx_query_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, _vp, _p(Out)]),
     "bsk_duplicate_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, _vp, _p(Out)]),
     "bsk_range_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp, _p(Out)]),
+    "bsk_sample_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp, _p(Out)]),
+    "bsk_sample_needs_count": (_i, [_vp, _p(C.c_int)]),
+    "bsk_sample_set_count": (_i, [_vp, C.c_uint64]),
+    "bsk_sample_set_first_record": (_i, [_vp, C.c_uint64]),
+    "bsk_shuffle_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, _vp, _p(Out)]),
     "bsk_range_needs_count": (_i, [_vp, _p(C.c_int)]),
     "bsk_range_set_count": (_i, [_vp, C.c_uint64]),
     "bsk_range_bounds": (_i, [_vp, _p(_i64), _p(_i64)]),

@@ -10,7 +10,7 @@ import os
 
 from . import _lib
 from ._lib import lib, check, BskError, FORMAT_FASTA, FORMAT_FASTQ
-from .options import SeqKitStatsOptions, SeqKitSeqOptions, SeqKitGrepOptions, SeqKitSubseqOptions, SeqKitTranslateOptions, SeqKitRmDupOptions, SeqKitLocateOptions, SeqKitFq2FaOptions, SeqKitHeadOptions, SeqKitDuplicateOptions, SeqKitRenameOptions, SeqKitSortOptions, SeqKitFaidxOptions, SeqKitPairOptions, SeqKitCommonOptions, SeqKitConcatOptions, SeqKitReplaceOptions, SeqKitFa2FqOptions
+from .options import SeqKitStatsOptions, SeqKitSeqOptions, SeqKitGrepOptions, SeqKitSubseqOptions, SeqKitTranslateOptions, SeqKitRmDupOptions, SeqKitLocateOptions, SeqKitFq2FaOptions, SeqKitHeadOptions, SeqKitDuplicateOptions, SeqKitRenameOptions, SeqKitSortOptions, SeqKitFaidxOptions, SeqKitPairOptions, SeqKitCommonOptions, SeqKitConcatOptions, SeqKitReplaceOptions, SeqKitFa2FqOptions, SeqKitSampleOptions, SeqKitShuffleOptions
 
 
 class SeqFrame:
@@ -406,6 +406,34 @@ def Range(input, o, device=0):
 def Head(input, o=None, device=0):
     """bigseqkit/head.go:34-44: Range("1:N")"""
     return _range("Head", input, o or SeqKitHeadOptions(), device)
+
+
+def Sample(input, o, device=0):
+    """bigseqkit/sample.go:48-76: the verdict on a record depends on (Seed, its index in the whole input) alone, so every
+    shard is told where it starts, as in Range; Count() only for Number > 0 or several shards."""
+    chunks = []
+    with Operator("Sample", o.to_json(), device) as op:
+        counts = Count(input, device) if len(input.shards) > 1 else [0]
+        needs = C.c_int()
+        check(lib.bsk_sample_needs_count(op.ctx, C.byref(needs)), op.ctx)
+        if needs.value:
+            if len(input.shards) == 1:
+                counts = Count(input, device)
+            check(lib.bsk_sample_set_count(op.ctx, sum(counts)), op.ctx)
+        first = 0
+        for (pid, ptr, n, on_dev, keep), cnt in zip(input.partitions(), counts):
+            out = _lib.Out()
+            check(lib.bsk_sample_run(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None, C.byref(out)), op.ctx)
+            buf = C.create_string_buffer(max(1, out.len))
+            check(lib.bsk_out_to_host(op.ctx, C.byref(out), buf, out.len), op.ctx)
+            chunks.append(buf.raw[:out.len])
+            first += cnt
+    return b"".join(chunks)
+
+
+def Shuffle(input, o=None, device=0):
+    """bigseqkit/shuffle.go:33-46 (PARITY SHUF): the records in ascending order of their draws; global, several shards are joined"""
+    return _run_records("Shuffle", lib.bsk_shuffle_run, _one_shard(input), o or SeqKitShuffleOptions(), device)[0]
 
 
 def build_index(input, device=0):

@@ -147,6 +147,8 @@ RecordOp record_op(const bsk_ctx* c) {
         case Op::Replace: return {replace_run_device, RecordOp::Chunks};  // {nr}: the chunks of one call are one partition
         case Op::Fa2Fq: return {fa2fq_run_device, RecordOp::Chunks};  // a join against a table the context holds whole
         case Op::Range: case Op::Head: return {records_run_device, RecordOp::NoStore};
+        case Op::Sample: return {records_run_device, RecordOp::Chunks};  // the context carries the running record index
+        case Op::Shuffle: return {records_run_device, RecordOp::Whole};
         case Op::Faidx: return {faidx_run_device, RecordOp::NoStore};
         default: return {};  // stats; pair / common / concat read several texts
     }
@@ -298,6 +300,7 @@ int bsk_create(const char* op_name_, const char* opts_json, int device, bsk_ctx*
             case Op::Common: validate_common_opts(c); break;
             case Op::Replace: validate_replace_opts(c); break;
             case Op::Fa2Fq: validate_fa2fq_opts(c); break;
+            case Op::Sample: case Op::Shuffle: validate_sample_opts(c); break;
             default: break;  // validated by the op's own module once it is built
         }
     } catch (const std::exception& e) {
@@ -990,6 +993,7 @@ static int record_call(bsk_ctx* c, bsk_out* out, std::optional<Op> want, bool ar
     BSK_ENTER(c);
     if (cv.pid) c->cur_pid = *cv.pid;
     if (cv.first_record) c->cur_first_record = *cv.first_record;
+    if (cv.first_record && c->op == Op::Sample) c->sample_next = (uint64_t)*cv.first_record;  // (the chunks of a call count on from it)
     if (cv.base_offset) c->cur_base_offset = *cv.base_offset;
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), st));
@@ -1158,6 +1162,38 @@ int bsk_range_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int fo
     CallValues cv;
     cv.first_record = &fr;
     return run_record_op(c, c && c->op == Op::Head ? Op::Head : Op::Range, shard, n, on_device, format, stream, out, cv);
+}
+
+int bsk_sample_needs_count(const bsk_ctx* c, int* needs) {
+    if (!c || !needs || c->op != Op::Sample) return BSK_ERR_INVALID_ARG;
+    *needs = c->sample_needs_count && !c->sample_resolved ? 1 : 0;
+    return BSK_OK;
+}
+
+int bsk_sample_set_count(bsk_ctx* c, uint64_t n_records) {
+    if (!c || c->op != Op::Sample) return BSK_ERR_INVALID_ARG;
+    return sample_resolve(c, n_records);
+}
+
+int bsk_sample_set_first_record(bsk_ctx* c, uint64_t first_record) {
+    if (!c || c->op != Op::Sample) return BSK_ERR_INVALID_ARG;
+    bsk_call_scope scope__(c);  // (no device needed: a context made for its options alone takes it too)
+    if (!scope__.owns) return fail_busy();
+    c->sample_first = c->sample_next = first_record;
+    return BSK_OK;
+}
+
+int bsk_sample_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                   void* stream, bsk_out* out) {
+    const int64_t fr = (int64_t)first_record;
+    CallValues cv;
+    cv.first_record = &fr;  // (lands once the call owns the context: a call refused as busy moves nothing)
+    return run_record_op(c, Op::Sample, shard, n, on_device, format, stream, out, cv);
+}
+
+int bsk_shuffle_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,
+                    bsk_out* out) {
+    return run_record_op(c, Op::Shuffle, shard, n, on_device, format, stream, out);
 }
 
 int bsk_duplicate_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,

@@ -145,6 +145,12 @@ struct bsk_ctx {
     struct ReplaceState* repl = nullptr;
     struct Fa2FqState* fa2fq = nullptr;  // fa2fq (ops_host_fa2fq.cpp): the FASTA table and its device copy
     uint64_t nr_base = 0;
+    // sample (ops_host_next.cpp): the index, in the whole input, of the first record of the next shard or chunk -- set by
+    // bsk_sample_run (first_record) and bsk_sample_set_first_record, advanced by every shard or chunk that completes, put back
+    // to sample_first by bsk_run_to_store unless pin_alphabet says that several calls carry one partition
+    uint64_t sample_next = 0, sample_first = 0;
+    uint64_t sample_threshold = 0;     // ceil(fraction * 2^53) (after bsk_sample_set_count when -n asks for it)
+    bool sample_needs_count = false, sample_resolved = false;
     uint64_t avg_record_bytes = 0;   // bytes per record in the head of the last indexed shard (0: unknown)
     bsk::RecordTable sparse;         // one-pass index: per-range slices, compacted into `table`
     uint64_t* d_range_count = nullptr;  // [cap_ranges]

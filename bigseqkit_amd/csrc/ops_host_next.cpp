@@ -5,7 +5,9 @@
 
 #include <algorithm>
 #include <climits>
+#include <cmath>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -23,6 +25,7 @@
 #include "ops_records.hpp"
 #include "ops_segcopy.hpp"
 #include "ops_rmdup.hpp"
+#include "ops_sample.hpp"
 #include "ops_seq.hpp"
 #include "ops_sort.hpp"
 #include "stream_stats.hpp"
@@ -111,6 +114,39 @@ int range_resolve(bsk_ctx* c, int64_t n_records) {
     return BSK_OK;
 }
 
+// The driver side of Sample and Shuffle (bigseqkit/sample.go:55-73, shuffle.go:33-46): messages and their order as written.
+// Proportion is a float32 there; with Number > 0 the fraction is Number / Count() -- "result may not exactly match".
+static uint64_t sample_threshold_of(double fraction) {
+    if (!(fraction < 1.0)) return 1ull << 53;  // (also +Inf: -n on an empty input)
+    if (fraction <= 0.0) return 0;
+    return (uint64_t)std::ceil(std::ldexp(fraction, 53));  // exact: a scaling by a power of two
+}
+
+void validate_sample_opts(bsk_ctx* c) {
+    const Options& o = c->opts;
+    c->alphabet = alphabet_from_seqtype(o.cs("SeqType"));
+    if (c->op == Op::Shuffle) return;
+    const int64_t number = o.i("Number");
+    const float proportion = (float)o.f("Proportion");
+    if (number == 0 && proportion == 0) throw OptError("one of flags -n (--number) and -p (--proportion) needed");
+    if (number < 0) throw OptError("value of -n (--number) and should be greater than 0");
+    if (proportion < 0 || proportion > 1) {
+        char b[128];
+        snprintf(b, sizeof b, "value of -p (--proportion) (%f) should be in range of (0, 1]", (double)proportion);
+        throw OptError(b);
+    }
+    c->sample_needs_count = number > 0;  // (Number wins over Proportion: sample.go:67)
+    c->sample_resolved = !c->sample_needs_count;
+    if (c->sample_resolved) c->sample_threshold = sample_threshold_of((double)proportion);
+}
+
+int sample_resolve(bsk_ctx* c, uint64_t n_records) {
+    if (!c->sample_needs_count) return BSK_OK;
+    c->sample_threshold = sample_threshold_of((double)c->opts.i("Number") / (double)n_records);
+    c->sample_resolved = true;
+    return BSK_OK;
+}
+
 // Fq2Fa.Call (bigseqkit-lib/fq2fa.go:35-59): record.Seq.Qual = []; record.Format(0) -- '>' + name, the sequence on one line
 int fq2fa_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, bsk_out* out) {
     const bool fastq = format == BSK_FORMAT_FASTQ;
@@ -142,7 +178,64 @@ int fq2fa_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hip
     return BSK_OK;
 }
 
-// RangePrepare + RangeFilter (bigseqkit-lib/range.go:26-43), Duplicate.Call (duplicate.go:24-30)
+// shuffle: the records in ascending order of their draws -- keys, one radix sort, the segments of the copy in that order
+static int shuffle_emit(bsk_ctx* c, const uint8_t* d_buf, size_t n, uint64_t total, hipStream_t st, bsk_out* out) {
+    const RecordTable& t = c->table;
+    const uint64_t N = t.n;
+    size_t tmp_bytes = 0;
+    if (sort_pairs_bits_iota_temp_bytes(N, 0, 64, &tmp_bytes) != hipSuccess) { c->set_error("libbsk: rocPRIM sort size query failed"); return BSK_ERR_HIP; }
+    Arena A;
+    const uint64_t o_keys = A.take(2 * N * 8), o_perm = A.take(N * 4), o_len = A.take(N * 4), o_off = A.take((N + 1) * 8),
+                   o_tmp = A.take(tmp_bytes ? tmp_bytes : 16);
+    int rc = arena_reserve(c, &A);
+    if (rc != BSK_OK) return rc;
+    uint64_t* keys = A.at<uint64_t>(o_keys);
+    uint32_t* perm = A.at<uint32_t>(o_perm);
+    uint32_t* len_perm = A.at<uint32_t>(o_len);
+    uint64_t* seg_off = A.at<uint64_t>(o_off);
+    rc = grow(c, &c->d_seg_src, &c->seg_src_cap, N + 1, N / 8 + 16);
+    if (rc != BSK_OK) return rc;
+    rc = grow(c, &c->d_seg_first, &c->seg_first_cap, seg_tiles(total) + 1, 64);
+    if (rc != BSK_OK) return rc;
+    rc = ensure_out(c, total);
+    if (rc != BSK_OK) return rc;
+    uint64_t* d_other = c->d_seg_src + N;
+    const bool plain = c->tune.is("segcopy", "off");
+    HIP_TRYX(c, hipMemsetAsync(d_other, 0, sizeof(uint64_t), st));
+    {
+        Timed tm(c, "k_shuffle_keys", st);
+        HIP_TRYX(c, launch_shuffle_keys(N, c->opts.i("Seed"), keys, st));
+    }
+    {
+        Timed tm(c, "radix_sort", st);  // (the values are 0 .. N - 1: no iota array is written or read)
+        HIP_TRYX(c, launch_sort_pairs_bits_iota(A.at<uint8_t>(o_tmp), tmp_bytes, keys, keys + N, perm, N, 0, 64, st));
+    }
+    {
+        Timed tm(c, "k_shuffle_segments", st);
+        HIP_TRYX(c, launch_shuffle_segments(d_buf, n, t, c->d_out_len, perm, c->d_seg_src, len_perm, d_other, st));
+    }
+    HIP_TRYX(c, launch_scan_u32(len_perm, seg_off, N, c->d_scan_tmp, st));
+    if (plain) {
+        HIP_TRYX(c, launch_shuffle_fix(d_buf, t, perm, len_perm, seg_off, c->d_seg_src, c->d_out, true, st));
+    } else {
+        {
+            Timed tm(c, "k_seg_copy", st);
+            HIP_TRYX(c, launch_seg_first(seg_off, N, c->d_seg_first, st));
+            HIP_TRYX(c, launch_seg_copy(c->d_seg_src, seg_off, N, c->d_seg_first, c->d_out, total, d_buf, d_buf + n, st));
+        }
+        uint64_t other = 0;
+        HIP_TRYX(c, hipMemcpyAsync(&other, d_other, sizeof other, hipMemcpyDeviceToHost, st));
+        HIP_TRYX(c, hipStreamSynchronize(st));
+        if (other) HIP_TRYX(c, launch_shuffle_fix(d_buf, t, perm, len_perm, seg_off, c->d_seg_src, c->d_out, false, st));
+    }
+    out->d_data = c->d_out;
+    out->len = total;
+    out->records = N;
+    return BSK_OK;
+}
+
+// RangePrepare + RangeFilter (bigseqkit-lib/range.go:26-43), Duplicate.Call (duplicate.go:24-30); sample and shuffle
+// (PARITY.md SAMPLE, SHUF) take the same way: a size per record, the scan, the verbatim copy
 int records_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, bsk_out* out) {
     RecordsParams P;
     memset(&P, 0, sizeof P);
@@ -153,6 +246,14 @@ int records_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, h
         P.hi = INT64_MAX;
         P.times = (uint32_t)c->opts.i("Times");
         if (P.times == 0) return empty_result(c, out);
+    } else if (c->op == Op::Sample || c->op == Op::Shuffle) {
+        if (c->op == Op::Sample && !c->sample_resolved) {
+            c->set_error("libbsk: sample by number needs the record count first (bsk_sample_set_count)");
+            return BSK_ERR_INVALID_ARG;
+        }
+        P.lo = INT64_MIN;  // (shuffle: every record has output; sample: launch_sample_size decides)
+        P.hi = INT64_MAX;
+        P.times = 1;
     } else {
         if (!c->range_resolved) {
             c->set_error("libbsk: a range with negative positions needs the record count first (bsk_range_set_count)");
@@ -187,7 +288,14 @@ int records_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, h
         if (c->table.n == 0) return empty_result(c, out);
         rc = ensure_record_scratch(c);
         if (rc != BSK_OK) return rc;
-        HIP_TRYX(c, launch_records_size(d_buf, n, c->table, P, c->d_out_len, c->d_status, st));
+        if (c->op == Op::Sample) {
+            Timed tm(c, "k_sample_size", st);
+            const SampleParams S{P.fastq, c->sample_next, c->opts.i("Seed"), c->sample_threshold};
+            HIP_TRYX(c, launch_sample_size(d_buf, n, c->table, S, c->d_out_len, c->d_status, st));
+        } else {
+            Timed tm(c, "k_records_size", st);
+            HIP_TRYX(c, launch_records_size(d_buf, n, c->table, P, c->d_out_len, c->d_status, st));
+        }
         HIP_TRYX(c, launch_scan_u32(c->d_out_len, c->d_out_off, c->table.n, c->d_scan_tmp, st));
         HIP_TRYX(c, hipMemsetAsync(c->d_counter, 0, 4 * sizeof(uint64_t), st));
         HIP_TRYX(c, launch_count_nonzero(c->d_out_len, c->table.n, c->d_counter, st));
@@ -204,25 +312,59 @@ int records_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, h
     out->d_data = nullptr;
     out->len = 0;
     out->records = 0;
+    if (c->op == Op::Sample) c->sample_next += c->table.n;  // the next chunk of this partition goes on from here
     if (total == 0) return BSK_OK;
-    rc = ensure_out(c, total);
-    if (rc != BSK_OK) return rc;
+    if (c->op == Op::Shuffle) {
+        rc = check_u32_records(c, "shuffle");  // 32-bit permutation
+        return rc != BSK_OK ? rc : shuffle_emit(c, d_buf, n, total, st, out);
+    }
     const char* sg = c->tune.get("segcopy");
-    if (P.times == 1 && !(sg && strcmp(sg, "off") == 0)) {
-        // range / head: the kept records are verbatim segments of the shard (ops_segcopy.hip)
+    const bool segments = P.times == 1 && !(sg && strcmp(sg, "off") == 0);
+    // sample with out=slices: the kept records are verbatim pieces of the shard, in file order -- the segment list IS the result
+    // (a record that was dropped is a segment of no bytes) and the block is neither allocated nor written
+    const bool as_slices = segments && c->op == Op::Sample && slices_wanted(c);
+    if (!as_slices) {
+        rc = ensure_out(c, total);
+        if (rc != BSK_OK) return rc;
+    }
+    if (segments) {
+        // range / head / sample: the kept records are verbatim segments of the shard (ops_segcopy.hip)
         const RecordTable& t = c->table;
         rc = grow(c, &c->d_seg_src, &c->seg_src_cap, t.n + 1, t.n / 8 + 16);
         if (rc != BSK_OK) return rc;
         rc = grow(c, &c->d_seg_first, &c->seg_first_cap, seg_tiles(total) + 1, 64);
         if (rc != BSK_OK) return rc;
         uint64_t* d_other = c->d_seg_src + t.n;
-        HIP_TRYX(c, hipMemsetAsync(d_other, 0, sizeof(uint64_t), st));
-        HIP_TRYX(c, launch_seg_build_text(d_buf, n, t, c->d_out_len, c->d_seg_src, d_other, st));
-        HIP_TRYX(c, launch_seg_first(c->d_out_off, t.n, c->d_seg_first, st));
-        HIP_TRYX(c, launch_seg_copy(c->d_seg_src, c->d_out_off, t.n, c->d_seg_first, c->d_out, total, d_buf, d_buf + n, st));
         uint64_t other = 0;
-        HIP_TRYX(c, hipMemcpyAsync(&other, d_other, sizeof other, hipMemcpyDeviceToHost, st));
-        HIP_TRYX(c, hipStreamSynchronize(st));
+        auto read_other = [&]() -> int {  // (the one synchronisation of this step, before or after the copy)
+            HIP_TRYX(c, hipMemcpyAsync(&other, d_other, sizeof other, hipMemcpyDeviceToHost, st));
+            HIP_TRYX(c, hipStreamSynchronize(st));
+            return BSK_OK;
+        };
+        HIP_TRYX(c, hipMemsetAsync(d_other, 0, sizeof(uint64_t), st));
+        {
+            Timed tm(c, "k_seg_prep", st);
+            HIP_TRYX(c, launch_seg_build_text(d_buf, n, t, c->d_out_len, c->d_seg_src, d_other, st));
+            HIP_TRYX(c, launch_seg_first(c->d_out_off, t.n, c->d_seg_first, st));
+        }
+        if (as_slices) {
+            rc = read_other();
+            if (rc != BSK_OK) return rc;
+            if (other == 0) {
+                out_as_segments(c, out, c->d_seg_src, c->d_out_off, t.n, c->d_seg_first, d_buf, d_buf + n, total, kept);
+                return BSK_OK;
+            }
+            rc = ensure_out(c, total);  // (a kept last record without its newline: one block after all)
+            if (rc != BSK_OK) return rc;
+        }
+        {
+            Timed tm(c, "k_seg_copy", st);
+            HIP_TRYX(c, launch_seg_copy(c->d_seg_src, c->d_out_off, t.n, c->d_seg_first, c->d_out, total, d_buf, d_buf + n, st));
+        }
+        if (!as_slices) {
+            rc = read_other();
+            if (rc != BSK_OK) return rc;
+        }
         if (other) HIP_TRYX(c, launch_seg_fix_text(d_buf, t, c->d_out_len, c->d_out_off, c->d_seg_src, c->d_out, st));
     } else if (P.times <= 4 && !(sg && strcmp(sg, "off") == 0)) {
         // duplicate -n 2..4: `times` segments per record (more copies: the tile copy below, whose tables do not grow with n)

@@ -10,7 +10,7 @@
 //   RmDupOptions      bigseqkit/rmdup.go:13-21,    defaults :23-33
 //   Fq2FaOptions      bigseqkit/fq2fa.go:11-18;  RangeOptions bigseqkit/range.go:14-24;  HeadOptions bigseqkit/head.go:12-22;
 //   DuplicateOptions  bigseqkit/duplicate.go:9-19;  ReplaceOptions bigseqkit/replace.go:9-37;
-//   Fa2FqOptions      bigseqkit/fa2fq.go:11-23
+//   Fa2FqOptions      bigseqkit/fa2fq.go:11-23;  SampleOptions bigseqkit/sample.go:12-26;  ShuffleOptions bigseqkit/shuffle.go:11-21
 #pragma once
 #include <cstdint>
 #include <stdexcept>
@@ -36,7 +36,7 @@ struct Field {
     std::vector<std::string> sl;
 };
 
-enum class Op { Stats, Seq, Grep, Locate, Subseq, Translate, RmDup, Fq2Fa, Range, Head, Duplicate, Rename, Sort, Faidx, Pair, Common, Concat, Replace, Fa2Fq };
+enum class Op { Stats, Seq, Grep, Locate, Subseq, Translate, RmDup, Fq2Fa, Range, Head, Duplicate, Rename, Sort, Faidx, Pair, Common, Concat, Replace, Fa2Fq, Sample, Shuffle };
 
 class Options {
    public:

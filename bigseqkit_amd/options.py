@@ -34,6 +34,8 @@ _FIELDS = {
     "Replace": ["Pattern", "Replacement", "NrWidth", "BySeq", "IgnoreCase", "KvFile", "KeepUntouch", "KeepKey",
                 "KeyCaptIdx", "KeyMissRepl"],   # bigseqkit/replace.go:9-21
     "Fa2Fq": ["FastaFile", "OnlyPositiveStrand"],   # bigseqkit/fa2fq.go:11-15
+    "Sample": ["Seed", "Number", "Proportion"],   # bigseqkit/sample.go:12-17
+    "Shuffle": ["Seed"],                           # bigseqkit/shuffle.go:11-14
     "Common": ["ByName", "BySeq", "IgnoreCase", "OnlyPositiveStrand"],   # bigseqkit/common.go:13-19
     "Faidx": ["UseRegexp", "IgnoreCase", "FullHead", "RegionFile", "Regions"],   # bigseqkit/faidx.go:11-18
     "Sort": ["InNaturalOrder", "BySeq", "ByName", "ByLength", "ByBases", "GapLetters", "Reverse", "IgnoreCase",
@@ -118,3 +120,5 @@ SeqKitCommonOptions = _make("Common")
 SeqKitConcatOptions = _make("Concat")
 SeqKitReplaceOptions = _make("Replace")
 SeqKitFa2FqOptions = _make("Fa2Fq")
+SeqKitSampleOptions = _make("Sample")
+SeqKitShuffleOptions = _make("Shuffle")

@@ -165,6 +165,11 @@ const Command kCommands[] = {
       {"reverse", 'r', BOOL, "Reverse", "false"}, {"ignore-case", 'i', BOOL, "IgnoreCase", "false"},
       {"two-pass", '2', BOOL, "", "false"}, {"keep-temp", 'k', BOOL, "", "false"},
       {"seq-prefix-length", 'L', INT, "SeqPrefixLength", "10000"}}},
+    {"sample", "Sample",                                                               // cli/sample.go:43-46
+     {{"rand-seed", 's', INT, "Seed", "11"}, {"number", 'n', INT, "Number", "0"}, {"proportion", 'p', FLOAT, "Proportion", "0"},
+      {"two-pass", '2', BOOL, "", "false"}}},
+    {"shuffle", "Shuffle",                                                             // cli/shuffle.go:44-46
+     {{"rand-seed", 's', INT, "Seed", "23"}, {"two-pass", '2', BOOL, "", "false"}, {"keep-temp", 'k', BOOL, "", "false"}}},
     {"rmdup", "RmDup",
      {{"by-name", 'n', BOOL, "ByName", "false"}, {"by-seq", 's', BOOL, "BySeq", "false"},
       {"ignore-case", 'i', BOOL, "IgnoreCase", "false"}, {"dup-seqs-file", 'd', STR, "DupSeqsFile", ""},
@@ -508,6 +513,8 @@ int run_op(const std::string& use, bsk_ctx* ctx, const Part& in, int64_t pid, ui
     if (use == "faidx") return bsk_faidx_run(ctx, p, n, dev, in.fmt, pid, first_record /* = byte offset here */, nullptr, out);
     if (use == "duplicate") return bsk_duplicate_run(ctx, p, n, dev, in.fmt, pid, nullptr, out);
     if (use == "range" || use == "head") return bsk_range_run(ctx, p, n, dev, in.fmt, pid, first_record, nullptr, out);
+    if (use == "sample") return bsk_sample_run(ctx, p, n, dev, in.fmt, pid, first_record, nullptr, out);
+    if (use == "shuffle") return bsk_shuffle_run(ctx, p, n, dev, in.fmt, pid, nullptr, out);
     return bsk_rmdup_run(ctx, p, n, dev, in.fmt, pid, nullptr, out);
 }
 
@@ -518,7 +525,8 @@ Output execute(const Invocation& inv, std::vector<Part>& inputs, bool keep_on_de
     const int device = (int)strtol(inv.pget("device").c_str(), nullptr, 10);
     Output res;
     // rmdup is global over the union of its inputs (bigseqkit/rmdup.go:97 groups the whole dataframe): one shard
-    if ((use == "rmdup" || use == "rename" || use == "sort") && inputs.size() > 1) {
+    // (shuffle: the files of the command line are unioned, cli/shuffle.go:11-15, and the order is over all of them)
+    if ((use == "rmdup" || use == "rename" || use == "sort" || use == "shuffle") && inputs.size() > 1) {
         size_t total = 0;
         for (auto& p : inputs) {
             if (p.fmt != inputs[0].fmt) die(use + ": inputs of different formats");
@@ -610,11 +618,30 @@ Output execute(const Invocation& inv, std::vector<Part>& inputs, bool keep_on_de
         bsk_destroy(probe);
         if (ctx && range_needs && bsk_range_set_count(ctx, n_records) != BSK_OK) die(bsk_last_error(ctx));
     }
+    // sample: exactly one input dataframe, the parts a `pipe` job hands over included (cli/sample.go:11-13) -- the verdict on a
+    // record hangs on its index in that one input, which starts at 0; -n: fraction = Number / Count() (bigseqkit/sample.go:67-73)
+    bool sample_needs = false;
+    if (use == "sample" && inputs.size() != 1) die("only 1 file needed");
+    if (use == "sample") {
+        bsk_ctx* probe = fresh();
+        int needs = 0;
+        bsk_sample_needs_count(probe, &needs);
+        sample_needs = needs != 0;
+        if (sample_needs)
+            for (auto& in : inputs) {
+                uint64_t k = 0;
+                if (bsk_index_build(probe, in.ptr(), in.size(), in.on_device(), in.fmt, nullptr, &k) != BSK_OK) die(bsk_last_error(probe));
+                n_records += k;
+            }
+        bsk_destroy(probe);
+        if (ctx && sample_needs && bsk_sample_set_count(ctx, n_records) != BSK_OK) die(bsk_last_error(ctx));
+    }
     for (size_t fi = 0; fi < inputs.size(); ++fi) {
         const Part& in = inputs[fi];
         bsk_out out;
         bsk_ctx* c = ctx ? ctx : fresh();
         if (!ctx && range_needs && bsk_range_set_count(c, n_records) != BSK_OK) die(bsk_last_error(c));
+        if (!ctx && sample_needs && bsk_sample_set_count(c, n_records) != BSK_OK) die(bsk_last_error(c));
         if (run_op(use, c, in, (int64_t)fi, first[fi], &out) != BSK_OK) die(bsk_last_error(c));
         if (use == "rmdup" && bsk_rmdup_finish(c) != BSK_OK) die(bsk_last_error(c));
         if (grep_count) {
@@ -681,8 +708,9 @@ std::vector<Part> read_parts(const std::vector<std::string>& files, int device =
                 p.dptr = nullptr;
                 if (use != "stats") {
                     close(fd);
-                    die(std::string(bsk_global_error()) + " -- '" + use + "': " + f + " (" + std::to_string(p.n) + " bytes) must fit one GPU next to its "
-                        "result; cut it over several GPUs (--devices 0-7: fq2fa, grep, locate, rmdup, seq, stats, subseq, translate)");
+                    const std::string what = std::string(bsk_global_error()) + " -- '" + use + "': " + f + " (" + std::to_string(p.n) + " bytes) must fit one GPU next to its result; ";
+                    if (use == "shuffle") die(what + "shuffle orders all records of its input in one pass and runs on one device");
+                    die(what + "cut it over several GPUs (--devices 0-7: fq2fa, grep, locate, rmdup, sample, seq, stats, subseq, translate)");
                 }
                 // stats: the file stays on the host, its mapping is streamed in record-aligned chunks
                 p.map = mmap(nullptr, p.n, PROT_READ, MAP_SHARED, fd, 0);
@@ -885,11 +913,11 @@ static bool parallel_pread(int fd, uint8_t* buf, size_t len, size_t off, int thr
 
 int run_devices(const Invocation& inv) {
     const std::string use = inv.cmd->use;
-    static const char* const kStreamed[] = {"seq", "grep", "locate", "subseq", "translate", "fq2fa", "replace", "fa2fq"};
+    static const char* const kStreamed[] = {"seq", "grep", "locate", "subseq", "translate", "fq2fa", "replace", "fa2fq", "sample"};
     bool streamed = false;
     for (const char* u : kStreamed) streamed = streamed || use == u;
     if (!streamed && use != "stats" && use != "rmdup")
-        die("'" + use + "' runs on one device (bigseqkit " + use + " ... --device N); several GPUs: fa2fq, fq2fa, grep, locate, replace, rmdup, seq, stats, subseq, translate");
+        die("'" + use + "' runs on one device (bigseqkit " + use + " ... --device N); several GPUs: fa2fq, fq2fa, grep, locate, replace, rmdup, sample, seq, stats, subseq, translate");
     if (inv.files.size() != 1) die("--devices: exactly one input file (it is cut into one shard per GPU)");
     const std::vector<int> devices = parse_devices(inv.pget("devices"));
     const int world = (int)devices.size();
@@ -1054,6 +1082,29 @@ int run_devices(const Invocation& inv) {
                 else if (rank == 0) me.text = std::to_string(cnt);  // fmt.Print: no newline (bigseqkit-cli/grep.go:14)
             }
         } else {
+            // sample: the verdict on a record hangs on its index in the WHOLE file -- every worker counts its shard, the counts
+            // are gathered, the prefix is this worker's first record and the sum serves -n (bigseqkit/sample.go:67-73)
+            uint64_t first_record = 0;
+            if (use == "sample") {
+                int needs = 0;
+                if (ctx) bsk_sample_needs_count(ctx, &needs);
+                if (needs || world > 1) {  // (the same on every worker: all of them enter the collective, or none)
+                    uint64_t k = 0;
+                    if (me.error.empty() && via_host)
+                        give_up(needs ? "sample -n (--number) needs the record count of the whole input before the first record is judged, and this "
+                                        "input is streamed from the file in pieces: use -p (--proportion), as the command's own help advises "
+                                        "for large files"
+                                      : "sample: a shard that is streamed from the file in pieces is not counted first; run it on one worker "
+                                        "(--devices N) or on more devices, so that every shard fits its GPU");
+                    else if (me.error.empty() && n && bsk_index_build(ctx, d_shard, n, 1, fmt, nullptr, &k) != BSK_OK) give_up(bsk_last_error(ctx));
+                    std::vector<uint64_t> all((size_t)world, 0);
+                    if (bsk_comm_allgather_u64(comm, k, all.data(), nullptr) != BSK_OK) give_up(bsk_comm_error(comm));
+                    uint64_t total = 0;
+                    for (int r = 0; r < world; ++r) { if (r < rank) first_record += all[(size_t)r]; total += all[(size_t)r]; }
+                    if (me.error.empty() && needs && bsk_sample_set_count(ctx, total) != BSK_OK) give_up(bsk_last_error(ctx));
+                }
+                if (me.error.empty()) bsk_sample_set_first_record(ctx, first_record);  // (where bsk_run_to_store starts counting)
+            }
             bsk_store* st = dir_store;
             uint64_t part = (uint64_t)rank;
             if (ok0 && !dir_store) {  // --merge / -o -: this worker's part goes to a spool file of its own first
@@ -1130,7 +1181,7 @@ int run_devices(const Invocation& inv) {
                 Part in;
                 in.fmt = fmt; in.dptr = d_shard; in.n = n;
                 bsk_out o{nullptr, 0, 0};
-                if (n && run_op(use, ctx, in, rank, 0, &o) != BSK_OK) give_up(bsk_last_error(ctx));
+                if (n && run_op(use, ctx, in, rank, first_record, &o) != BSK_OK) give_up(bsk_last_error(ctx));
                 else if (bsk_store_put(st, ctx, part, &o) != BSK_OK) give_up(bsk_store_error(st));
                 me.out_bytes = o.len; me.out_records = o.records;
             }
@@ -1256,6 +1307,7 @@ static int run_main(int argc, char** argv) {
                   << ",\"partitions\":" << strtol(inv.pget("partitions").c_str(), nullptr, 10) << "}\n";
         return 0;
     }
+    if (std::string(inv.cmd->use) == "sample" && inv.files.size() > 1) die("only 1 file needed");  // cli/sample.go:11-13
     if (!inv.pget("devices").empty()) return run_devices(inv);  // several GPUs: worker threads + librccl, in this process
     if (inv.files.empty()) die("no input files (stdin is not supported by the IgnisHPC CLI either)");
     g_faidx_query = faidx_query;

@@ -14,6 +14,8 @@
 //   Subseq                bigseqkit/subseq.go:86-100    MapPartitions(SubseqTransform)
 //   Translate             bigseqkit/translate.go:87-100 MapPartitions(Translate)
 //   Fa2Fq                 bigseqkit/fa2fq.go:42-56      MapPartitions(Fa2Fq)
+//   Sample                bigseqkit/sample.go:48-76     Count() for -n + Sample(false, fraction, seed): bsk_sample_run per partition
+//   Shuffle               bigseqkit/shuffle.go:33-46    PartitionByRandom: bsk_shuffle_run over the joined partitions
 //   RmDup                 bigseqkit/rmdup.go:70-108     MapPartitions(RmDupPrepare) + GroupByKey + Flatmap(RmDupCheck)
 //   ReadFASTA/Q[N]        bigseqkit/helper.go:148-178   PlainFile(path, delim) + ReadFixer
 //   StoreFASTX[N]         bigseqkit/helper.go:180-195   SaveAsTextFile / FileStore
@@ -43,6 +45,7 @@ static bsk_run_fn bsk_fn_translate(void) { return bsk_translate_run; }
 static bsk_run_fn bsk_fn_rmdup(void)     { return bsk_rmdup_run; }
 static bsk_run_fn bsk_fn_replace(void)   { return bsk_replace_run; }
 static bsk_run_fn bsk_fn_fa2fq(void)     { return bsk_fa2fq_run; }
+static bsk_run_fn bsk_fn_shuffle(void)   { return bsk_shuffle_run; }
 */
 import "C"
 
@@ -398,6 +401,74 @@ func RmDup(input *SeqFrame, o *SeqKitRmDupOptions) (*Result, error) {
 		return nil, errors.New("only one/none of the flags -s (--by-seq) and -n (--by-name) is allowed")
 	}
 	return mapPartitions("RmDup", C.bsk_fn_rmdup(), OptionsToString(o), joined(input), nil, 1)
+}
+
+// Shuffle: bigseqkit/shuffle.go:33-46.  The records in ascending order of draw(seed, index) (PARITY.md SHUF); global like
+// RmDup: the partitions are joined and seen by ONE context.
+func Shuffle(input *SeqFrame, o *SeqKitShuffleOptions) (*Result, error) {
+	if o == nil {
+		o = &SeqKitShuffleOptions{}
+	}
+	o.inner.setDefaults()
+	return mapPartitions("Shuffle", C.bsk_fn_shuffle(), OptionsToString(o.inner), joined(input), nil, 1)
+}
+
+// Sample: bigseqkit/sample.go:48-76.  The verdict on a record depends on (seed, its index in the whole input) alone
+// (PARITY.md SAMPLE), so every partition is told where it starts: one context counts the partitions (bsk_index_build, what
+// input.Count() costs the reference too -- only with -n or several partitions), then runs them in order.
+func Sample(input *SeqFrame, o *SeqKitSampleOptions) (*Result, error) {
+	if o == nil {
+		o = &SeqKitSampleOptions{}
+	}
+	o.inner.setDefaults()
+	op, err := newBskOp("Sample", OptionsToString(o.inner), input.Device) // the messages of sample.go:55-64 come from here
+	if err != nil {
+		return nil, err
+	}
+	defer op.Close()
+	ptrOf := func(d []byte) unsafe.Pointer {
+		if len(d) == 0 {
+			return nil
+		}
+		return unsafe.Pointer(&d[0])
+	}
+	var needs C.int
+	C.bsk_sample_needs_count(op.ctx, &needs)
+	counts := make([]uint64, len(input.Shards))
+	var total uint64
+	if needs != 0 || len(input.Shards) > 1 {
+		for i, s := range input.Shards {
+			var k C.uint64_t
+			if rc := C.bsk_index_build(op.ctx, ptrOf(s.Data), C.size_t(len(s.Data)), 0, C.int(input.Format), nil, &k); rc != C.BSK_OK {
+				return nil, op.err()
+			}
+			counts[i] = uint64(k)
+			total += uint64(k)
+		}
+	}
+	if needs != 0 {
+		C.bsk_sample_set_count(op.ctx, C.uint64_t(total))
+	}
+	res := &Result{Parts: make([][]byte, len(input.Shards))}
+	var first uint64
+	for pid, s := range input.Shards {
+		var out C.bsk_out
+		if rc := C.bsk_sample_run(op.ctx, ptrOf(s.Data), C.size_t(len(s.Data)), 0, C.int(input.Format), C.int64_t(pid),
+			C.uint64_t(first), nil, &out); rc != C.BSK_OK {
+			return nil, op.err()
+		}
+		buf := make([]byte, int(out.len))
+		if out.len > 0 {
+			if rc := C.bsk_out_to_host(op.ctx, &out, unsafe.Pointer(&buf[0]), out.len); rc != C.BSK_OK {
+				return nil, op.err()
+			}
+		}
+		res.Parts[pid] = buf
+		res.Bytes += uint64(out.len)
+		res.Records += uint64(out.records)
+		first += counts[pid]
+	}
+	return res, nil
 }
 
 // joined: all partitions as one shard (Union + Repartition(1)); a missing final newline between partitions is added

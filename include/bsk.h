@@ -366,6 +366,27 @@ int bsk_range_bounds(const bsk_ctx* ctx, int64_t* start, int64_t* end);
 int bsk_range_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                   void* stream, bsk_out* out);
 
+/* ---- Sample (driver: bigseqkit/sample.go:48-76; options {"Seed": 11, "Number": 0, "Proportion": 0}; PARITY.md SAMPLE).
+ * draw(seed, g) = splitmix64(splitmix64((uint64)(int64)seed) ^ g), g = index of the record in the WHOLE input; record g is
+ * kept iff (draw >> 11) < ceil(fraction * 2^53), fraction = float64(float32(Proportion)) or, with Number > 0,
+ * Number / Count() -- not an exact count.  The verdict depends on (seed, g) alone, so the result is the same however the
+ * input is cut into shards.  Kept records come back unchanged, in file order; with the switch out = slices as ordered
+ * slices of the shard.  first_record = index of the shard's first record.  With Number > 0 bsk_sample_needs_count says that
+ * the record count is wanted and bsk_sample_set_count supplies it before the first run.  Through bsk_run_to_store the context
+ * carries the running record index over the chunks of a call (and, with the switch pin_alphabet, over the calls that feed
+ * one partition); it starts from bsk_sample_set_first_record's value (default 0). */
+int bsk_sample_needs_count(const bsk_ctx* ctx, int* needs);
+int bsk_sample_set_count(bsk_ctx* ctx, uint64_t n_records);
+int bsk_sample_set_first_record(bsk_ctx* ctx, uint64_t first_record);
+int bsk_sample_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                   void* stream, bsk_out* out);
+
+/* ---- Shuffle (bigseqkit/shuffle.go:33-46; options {"Seed": 23}; PARITY.md SHUF): the records of the shard, unchanged, in
+ * ascending order of draw(seed, g) (see Sample; the draws of one seed are distinct).  Global like Sort: ONE call sees the
+ * whole input; 2^32 or more records are BSK_ERR_UNSUPPORTED.  The result is always one block. */
+int bsk_shuffle_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,
+                    bsk_out* out);
+
 /* ---- Duplicate (bigseqkit/duplicate.go:31-43, bigseqkit-lib/duplicate.go:13-30): every record Times times, copies
  * adjacent. */
 int bsk_duplicate_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,
