@@ -115,6 +115,52 @@ int group_resolve(bsk_ctx* c, const uint8_t* d_buf, const TextTableH& tt, const 
     return BSK_OK;
 }
 
+// The grouping / sorting operators pack (group << 32) | record index and use 32-bit permutations: a shard of 2^32 or more
+// records (> 4 x 10^9: more than 1 TB of 317-byte reads) is refused instead of being grouped wrongly.
+int check_u32_records(bsk_ctx* c, const char* op) {
+    if (c->table.n < (1ull << 32)) return BSK_OK;
+    c->set_error(std::string("libbsk: ") + op + ": 2^32 or more records in one shard are not supported (cut the input into more shards)");
+    return BSK_ERR_UNSUPPORTED;
+}
+
+// ---- the prologue of the key-grouping operators (ops_host_internal.hpp)
+const char* const MSG_HASH_COLLISION = "libbsk: two distinct subjects share one 64-bit XXH64 key; refusing to guess (rerun on the CPU path)";
+
+int group_index(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, const char* op, hipStream_t st, TextTableH* tt, RmDupParams* P) {
+    int rc = build_index(c, d_buf, n, format, st);
+    if (rc == BSK_OK) rc = check_u32_records(c, op);  // (group << 32 | index) keys, u32 permutations
+    if (rc != BSK_OK || c->table.n == 0) return rc;
+    rc = prepare_text(c, d_buf, format, st, tt);
+    if (rc != BSK_OK) return rc;
+    memset(P, 0, sizeof *P);
+    P->fastq = format == BSK_FORMAT_FASTQ;
+    P->id_mode = id_mode_of(c);
+    P->line_width = P->fastq ? 0 : (int)c->opts.ci("LineWidth");
+    P->buf_end = d_buf + n;
+    rc = grow(c, &c->d_keys, &c->keys_cap, c->table.n, c->table.n / 8 + 16);
+    if (rc != BSK_OK) return rc;
+    return ensure_record_scratch(c);
+}
+
+// groups: the rmdup machinery (XXH64 of the ID / name / sequence, first occurrence wins, exact verification of every other one)
+int group_by_key(bsk_ctx* c, const uint8_t* d_buf, size_t n, const TextTableH& tt, const RmDupParams& P, uint8_t* d_has, hipStream_t st) {
+    HIP_TRYX(c, launch_rmdup_hash(d_buf, n, c->table, tt, P, c->d_keys, nullptr, st));
+    HIP_TRYX(c, hipMemsetAsync(d_has, 0, c->table.n, st));
+    return group_resolve(c, d_buf, tt, P, d_has, st);
+}
+
+int group_status(bsk_ctx* c, hipStream_t st, const uint64_t* d_extra, uint64_t* extra) {
+    uint64_t status = 0;
+    if (d_extra) HIP_TRYX(c, hipMemcpyAsync(extra, d_extra, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRYX(c, hipMemcpyAsync(&status, c->d_status, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRYX(c, hipStreamSynchronize(st));
+    if (status & ERR_HASH_COLLISION) {
+        c->set_error(MSG_HASH_COLLISION);
+        return BSK_ERR_UNSUPPORTED;
+    }
+    return kernel_error_to_status(c, status);
+}
+
 
 
 int kernel_error_to_status(bsk_ctx* c, uint64_t f) {
@@ -143,7 +189,7 @@ int kernel_error_to_status(bsk_ctx* c, uint64_t f) {
     else if (f & ERR_CAPACITY) { code = BSK_ERR_CAPACITY; m = "libbsk: internal table capacity exceeded"; }
     else if (f & ERR_HASH_COLLISION) {
         code = BSK_ERR_UNSUPPORTED;
-        m = "libbsk: two distinct subjects share one 64-bit XXH64 key; refusing to guess (rerun on the CPU path)";
+        m = MSG_HASH_COLLISION;
     } else {
         char hex[32];
         snprintf(hex, sizeof hex, "0x%llx", (unsigned long long)f);
@@ -686,23 +732,58 @@ static bool records_verbatim(const SeqParams& P) {
 int try_records_as_slices(bsk_ctx* c, const uint8_t* d_buf, size_t n, const SeqParams& P, uint64_t total, uint64_t kept, hipStream_t st,
                           bsk_out* out) {
     const RecordTable& t = c->table;
-    if (!slices_wanted(c) || !records_verbatim(P) || t.n == 0 || total == 0 || c->tune.is("segcopy", "off")) return 0;
-    int rc = grow(c, &c->d_seg_src, &c->seg_src_cap, t.n + 1, t.n / 8 + 16);
-    if (rc != BSK_OK) return rc > 0 ? -rc : rc;
-    rc = grow(c, &c->d_seg_first, &c->seg_first_cap, seg_tiles(total) + 1, 64);
-    if (rc != BSK_OK) return rc > 0 ? -rc : rc;
-    uint64_t* d_other = c->d_fin + bsk_ctx::FIN_OTHER;
-    if (hipMemsetAsync(d_other, 0, sizeof(uint64_t), st) != hipSuccess) { c->set_error("hipMemsetAsync failed"); return -BSK_ERR_HIP; }
+    if (!slices_wanted(c) || !records_verbatim(P) || t.n == 0 || total == 0 || !segcopy_on(c)) return 0;
+    int rc = seg_begin(c, t.n, total, st);
+    if (rc != BSK_OK) return -rc;
     {
         Timed tm(c, "k_seg_prep", st);
-        if (launch_seg_build_fastq(d_buf, n, t, c->d_out_len, c->d_seg_src, d_other, st, P.ren_ord) != hipSuccess ||
-            launch_seg_first(c->d_out_off, t.n, c->d_seg_first, st) != hipSuccess) { c->set_error("k_seg_prep launch failed"); return -BSK_ERR_HIP; }
+        if (launch_seg_build_fastq(d_buf, n, t, c->d_out_len, c->d_seg_src, seg_other(c), st, P.ren_ord) != hipSuccess) {
+            c->set_error("k_seg_prep launch failed");
+            return -BSK_ERR_HIP;
+        }
     }
-    rc = ctl_readback(c, st);
-    if (rc != BSK_OK) return rc > 0 ? -rc : rc;
-    if (c->fin(bsk_ctx::FIN_OTHER) != 0) return 0;  // (records that are not four plain lines: the emit kernel writes those)
+    uint64_t other = 0;
+    rc = seg_first(c, SegList{c->d_seg_src, c->d_out_off, t.n, total}, st, &other);
+    if (rc != BSK_OK) return -rc;
+    if (other != 0) return 0;  // (records that are not four plain lines: the emit kernel writes those)
     out_as_segments(c, out, c->d_seg_src, c->d_out_off, t.n, c->d_seg_first, d_buf, d_buf + n, total, kept);
     return 1;
+}
+
+// ---- the segmented copy as a step (ops_host_internal.hpp)
+int seg_begin(bsk_ctx* c, uint64_t seg_words, uint64_t total, hipStream_t st) {
+    int rc = grow(c, &c->d_seg_src, &c->seg_src_cap, seg_words, seg_words / 8 + 16);
+    if (rc != BSK_OK) return rc;
+    rc = grow(c, &c->d_seg_first, &c->seg_first_cap, seg_tiles(total) + 1, 64);
+    if (rc != BSK_OK) return rc;
+    HIP_TRYX(c, hipMemsetAsync(seg_other(c), 0, sizeof(uint64_t), st));  // (in the control block: comes back with ctl_readback)
+    return BSK_OK;
+}
+
+static int seg_read_other(bsk_ctx* c, hipStream_t st, uint64_t* other) {
+    const int rc = ctl_readback(c, st);
+    *other = c->fin(bsk_ctx::FIN_OTHER);
+    return rc;
+}
+
+int seg_first(bsk_ctx* c, const SegList& L, hipStream_t st, uint64_t* other) {
+    HIP_TRYX(c, launch_seg_first(L.off, L.nseg, c->d_seg_first, st));
+    return seg_read_other(c, st, other);
+}
+
+int seg_copy(bsk_ctx* c, const SegList& L, uint8_t* d_out, const uint8_t* d_buf, size_t n, hipStream_t st) {
+    Timed tm(c, "k_seg_copy", st);
+    HIP_TRYX(c, launch_seg_copy(L.src, L.off, L.nseg, c->d_seg_first, d_out, L.total, d_buf, d_buf + n, st));
+    return BSK_OK;
+}
+
+int seg_run(bsk_ctx* c, const SegList& L, uint8_t* d_out, const uint8_t* d_buf, size_t n, hipStream_t st, uint64_t* other) {
+    {
+        Timed tm(c, "k_seg_copy", st);
+        HIP_TRYX(c, launch_seg_first(L.off, L.nseg, c->d_seg_first, st));
+        HIP_TRYX(c, launch_seg_copy(L.src, L.off, L.nseg, c->d_seg_first, d_out, L.total, d_buf, d_buf + n, st));
+    }
+    return seg_read_other(c, st, other);
 }
 
 // tell the emit kernel which records it must leave to the block-per-chunk launch
@@ -711,32 +792,20 @@ int emit_records_at(bsk_ctx* c, const uint8_t* d_buf, size_t n, const SeqParams&
     SeqParams P = Pin;
     P.seg_src = nullptr;
     const RecordTable& t = c->table;
-    const char* env = c->tune.get("segcopy");  // off: never; force: whenever the records qualify (tests)
-    const bool verbatim = records_verbatim(P);
-    bool seg = verbatim && t.n > 0 && total > 0 && ((uintptr_t)d_out & 15u) == 0 && !(env && strcmp(env, "off") == 0);
-    if (seg && !(env && strcmp(env, "force") == 0)) seg = kept * 2 >= t.n && total >= (4u << 20);
-    if (seg) {
-        int rc = grow(c, &c->d_seg_src, &c->seg_src_cap, t.n + 1, t.n / 8 + 16);
+    if (records_verbatim(P) && t.n > 0 && total > 0 && ((uintptr_t)d_out & 15u) == 0 && segcopy_on(c, total, kept, t.n)) {
+        int rc = seg_begin(c, t.n, total, st);
         if (rc != BSK_OK) return rc;
-        rc = grow(c, &c->d_seg_first, &c->seg_first_cap, seg_tiles(total) + 1, 64);
-        if (rc != BSK_OK) return rc;
-        uint64_t* d_other = c->d_fin + bsk_ctx::FIN_OTHER;  // (in the control block: comes back with the final read-back)
-        HIP_TRYX(c, hipMemsetAsync(d_other, 0, sizeof(uint64_t), st));
         {
             // (round 4 tried to derive the sources inside k_seg_copy from the table instead of building seg_src: the build
             // pass went away, 0.37 ms per 79 M records, and the copy grew by 0.7 ms -- two dependent loads more at the head
             // of every tile; profiles/r04d_*.  The source array stays.)
             Timed tm(c, "k_seg_prep", st);
-            HIP_TRYX(c, launch_seg_build_fastq(d_buf, n, t, d_len, c->d_seg_src, d_other, st, P.ren_ord));
-            HIP_TRYX(c, launch_seg_first(d_off, t.n, c->d_seg_first, st));
+            HIP_TRYX(c, launch_seg_build_fastq(d_buf, n, t, d_len, c->d_seg_src, seg_other(c), st, P.ren_ord));
         }
-        {
-            Timed tm(c, "k_seg_copy", st);
-            HIP_TRYX(c, launch_seg_copy(c->d_seg_src, d_off, t.n, c->d_seg_first, d_out, total, d_buf, d_buf + n, st));
-        }
-        rc = ctl_readback(c, st);
+        uint64_t other = 0;
+        rc = seg_run(c, SegList{c->d_seg_src, d_off, t.n, total}, d_out, d_buf, n, st, &other);
         if (rc != BSK_OK) return rc;
-        if (c->fin(bsk_ctx::FIN_OTHER) == 0) return BSK_OK;
+        if (other == 0) return BSK_OK;
         P.seg_src = c->d_seg_src;  // the few records the copy left out
     }
     HIP_TRYX(c, launch_seq_emit(d_buf, t, P, d_len, d_off, d_out, st, total, kept));
@@ -745,6 +814,30 @@ int emit_records_at(bsk_ctx* c, const uint8_t* d_buf, size_t n, const SeqParams&
 
 int emit_records(bsk_ctx* c, const uint8_t* d_buf, size_t n, const SeqParams& P, uint64_t total, uint64_t kept, hipStream_t st) {
     return emit_records_at(c, d_buf, n, P, c->d_out_len, c->d_out_off, c->d_out, total, kept, st);
+}
+
+int emit_result(bsk_ctx* c, const uint8_t* d_buf, size_t n, const SeqParams& Pin, uint64_t total, uint64_t kept, hipStream_t st,
+                bsk_out* out, bool allow_slices) {
+    if (allow_slices) {
+        const int rs = try_records_as_slices(c, d_buf, n, Pin, total, kept, st, out);
+        if (rs != 0) return rs < 0 ? -rs : BSK_OK;
+    }
+    int rc = ensure_out(c, total);
+    if (rc != BSK_OK) return rc;
+    SeqParams P = Pin;
+    apply_long(c, &P);
+    rc = emit_records(c, d_buf, n, P, total, kept, st);
+    if (rc != BSK_OK) return rc;
+    out->d_data = c->d_out;
+    out->len = total;
+    out->records = kept;
+    return BSK_OK;
+}
+
+int emit_sized(bsk_ctx* c, const uint8_t* d_buf, size_t n, const SeqParams& P, hipStream_t st, bsk_out* out, bool allow_slices) {
+    uint64_t total = 0, kept = 0;
+    const int rc = finish_sizes(c, st, &total, &kept);
+    return rc != BSK_OK ? rc : emit_result(c, d_buf, n, P, total, kept, st, out, allow_slices);
 }
 
 void apply_long(const bsk_ctx* c, SeqParams* P) {

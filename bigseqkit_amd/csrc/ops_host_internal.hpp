@@ -50,6 +50,22 @@ inline int arena_reserve(bsk_ctx* c, Arena* a) {
     a->base = c->d_arena;
     return rc;
 }
+// ... for an arena whose first `keep` bytes already hold values of this call (more was taken since the last reservation):
+// they are carried over when the arena has to move, so the pointers are derived again afterwards and read the same
+inline int arena_reserve_keep(bsk_ctx* c, Arena* a, uint64_t keep, hipStream_t st) {
+    if (a->used > c->arena_cap) {
+        uint8_t* nb = nullptr;
+        const uint64_t cap = a->used + a->used / 8 + 256;
+        HIP_TRYX(c, hipMalloc((void**)&nb, cap));
+        HIP_TRYX(c, hipMemcpyAsync(nb, c->d_arena, keep, hipMemcpyDeviceToDevice, st));
+        HIP_TRYX(c, hipStreamSynchronize(st));
+        HIP_TRYX(c, hipFree(c->d_arena));
+        c->d_arena = nb;
+        c->arena_cap = cap;
+    }
+    a->base = c->d_arena;
+    return BSK_OK;
+}
 
 // Open-addressing table of the key-grouping operators (rmdup, rename, pair, common, concat, grep --delete-matched):
 // d_keys for N records and `cap` zeroed slots (a power of two >= 2 N) of 16 bytes {key, ~first record index}.
@@ -57,6 +73,22 @@ int key_table(bsk_ctx* c, uint64_t N, uint64_t* cap_out, uint64_t** table, hipSt
 struct RmDupParams;
 // c->d_keys: XXH64 keys -> first record of every record's group (+ d_has, c->d_out_len); see ops_host.cpp
 int group_resolve(bsk_ctx* c, const uint8_t* d_buf, const TextTableH& tt, const RmDupParams& P, uint8_t* d_has, hipStream_t st);
+// The prologue of an operator that groups the records of a shard by a key (rename, pair, common, concat), three steps:
+//   group_index   before: the shard.  After: c->table and the text view `tt` of the shard, `P` zeroed but for fastq, id_mode,
+//                 line_width and buf_end, c->d_keys and the record scratch grown for c->table.n records.  A shard of 2^32
+//                 records or more is refused in the name of `op`.  The caller looks at c->table.n (0: nothing to group),
+//                 sets the fields of P that are its own (by_name, by_seq, ignore_case) and carves its arena, d_has (one
+//                 byte per record) included.
+//   group_by_key  after: c->d_keys[i] = first record of record i's group, c->d_out_len[i] != 0 exactly for those firsts,
+//                 d_has as group_resolve leaves it.  Launches only; the status is not read yet, so the caller queues the
+//                 kernels whose result it wants in the same synchronisation (the count of file-1 records, ...)
+//   group_status  the one synchronisation: the status word -- two subjects under one key refuse the call, MSG_HASH_COLLISION --
+//                 and, if asked for, one more device word (d_extra -> *extra)
+extern const char* const MSG_HASH_COLLISION;
+int check_u32_records(bsk_ctx* c, const char* op);  // 32-bit permutations: 2^32 records or more in one shard are refused
+int group_index(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, const char* op, hipStream_t st, TextTableH* tt, RmDupParams* P);
+int group_by_key(bsk_ctx* c, const uint8_t* d_buf, size_t n, const TextTableH& tt, const RmDupParams& P, uint8_t* d_has, hipStream_t st);
+int group_status(bsk_ctx* c, hipStream_t st, const uint64_t* d_extra = nullptr, uint64_t* extra = nullptr);
 // FASTA text view of the shard's records (text_dev.hpp); null pointers for FASTQ
 int prepare_text(bsk_ctx* c, const uint8_t* d_buf, int format, hipStream_t st, TextTableH* tt, bool flatten = false,
                  bool keep_out_len = false, uint64_t buf_n = 0);  // buf_n: bytes in the shard (flatten: bounds its wide loads)
@@ -79,6 +111,14 @@ inline void for_lines(const uint8_t* h, size_t hb, F f) {
 // size array -> scan -> total / kept / kernel status (also lists the records with a very large output)
 int finish_sizes(bsk_ctx* c, hipStream_t st, uint64_t* total, uint64_t* kept);
 void apply_long(const bsk_ctx* c, SeqParams* P);
+// The tail of size -> scan -> emit.  Before: the size kernel of the operator has filled c->d_out_len.  After: the text in
+// c->d_out and `out` filled (with allow_slices and out=slices: `out` may name segments of the shard instead, see
+// try_records_as_slices).  emit_sized = finish_sizes + emit_result; an operator that looks at total / kept first (an empty
+// result, a count) calls finish_sizes itself and then emit_result.  Steps in between, or another emit kernel: compose the
+// pieces below instead (fa2fq, grep -c, rmdup, rename).
+int emit_sized(bsk_ctx* c, const uint8_t* d_buf, size_t n, const SeqParams& P, hipStream_t st, bsk_out* out, bool allow_slices = false);
+int emit_result(bsk_ctx* c, const uint8_t* d_buf, size_t n, const SeqParams& P, uint64_t total, uint64_t kept, hipStream_t st,
+                bsk_out* out, bool allow_slices = false);
 // the emit step of size -> scan -> emit into c->d_out (sizes in c->d_out_len / c->d_out_off): FASTQ records that leave
 // unchanged go through the segmented copy when most records have output, everything else through k_seq_emit
 int emit_records(bsk_ctx* c, const uint8_t* d_buf, size_t n, const SeqParams& P, uint64_t total, uint64_t kept, hipStream_t st);
@@ -90,6 +130,30 @@ int emit_records_at(bsk_ctx* c, const uint8_t* d_buf, size_t n, const SeqParams&
 int try_records_as_slices(bsk_ctx* c, const uint8_t* d_buf, size_t n, const SeqParams& P, uint64_t total, uint64_t kept, hipStream_t st,
                           bsk_out* out);
 int empty_result(bsk_ctx* c, bsk_out* out);
+// Is the segmented copy (ops_segcopy.hpp) on for this call?  Switch segcopy: "off" never, "force" always (tests); else
+// when the output has SEGCOPY_MIN_BYTES and at least half of the n records are kept.  A site without thresholds passes the
+// context alone (everything but "off" is yes), one with the byte threshold alone passes `total`.
+constexpr uint64_t SEGCOPY_MIN_BYTES = 4u << 20;
+inline bool segcopy_on(const bsk_ctx* c, uint64_t total = ~0ull, uint64_t kept = 0, uint64_t n = 0) {
+    if (c->tune.is("segcopy", "off")) return false;
+    if (c->tune.is("segcopy", "force")) return true;
+    return total >= SEGCOPY_MIN_BYTES && kept * 2 >= n;
+}
+// The segmented verbatim copy as a step: output = segments k < nseg, off[k + 1] - off[k] bytes from address src[k] (0: not
+// copied).  The word "other" counts what the list leaves out; it is FIN_OTHER of the control block.
+//   seg_begin   c->d_seg_src grown to seg_words words (the caller carves its lists out of it), c->d_seg_first to the tiles
+//               of `total` bytes, "other" zeroed.  Then the caller launches the kernel that fills its list and counts
+//               into seg_other(c), and after it ONE of
+//   seg_run     launch_seg_first + launch_seg_copy into d_out (stage "k_seg_copy"), then the read-back: *other.  Non-zero:
+//               the caller's fix-up kernel writes the rest, or launch_seq_emit with SeqParams::seg_src = the list
+//   seg_first / seg_copy   the two halves for a result that may leave as slices: seg_first reads "other" BEFORE any copy
+//               (0: out_as_segments(..., c->d_seg_first, ...) and no block at all), seg_copy is the copy alone
+struct SegList { const uint64_t* src; const uint64_t* off; uint64_t nseg; uint64_t total; };
+inline uint64_t* seg_other(bsk_ctx* c) { return c->d_fin + bsk_ctx::FIN_OTHER; }
+int seg_begin(bsk_ctx* c, uint64_t seg_words, uint64_t total, hipStream_t st);
+int seg_first(bsk_ctx* c, const SegList& L, hipStream_t st, uint64_t* other);
+int seg_copy(bsk_ctx* c, const SegList& L, uint8_t* d_out, const uint8_t* d_buf, size_t n, hipStream_t st);
+int seg_run(bsk_ctx* c, const SegList& L, uint8_t* d_out, const uint8_t* d_buf, size_t n, hipStream_t st, uint64_t* other);
 // Round 6, results as ordered slices (include/bsk.h bsk_out.d_seg_*): does the running call leave its text where it is?
 inline bool slices_wanted(const bsk_ctx* c) { return c->out_slices && !c->force_contiguous; }
 // ... the text as segments of the shard (kind 1: what launch_seg_copy would move) / as the per-range slices of a streaming

@@ -32,12 +32,11 @@
 
 namespace bsk {
 
-// The grouping / sorting operators pack (group << 32) | record index and use 32-bit permutations: a shard of 2^32 or more
-// records (> 4 x 10^9: more than 1 TB of 317-byte reads) is refused instead of being grouped wrongly.
-static int check_u32_records(bsk_ctx* c, const char* op) {
-    if (c->table.n < (1ull << 32)) return BSK_OK;
-    c->set_error(std::string("libbsk: ") + op + ": 2^32 or more records in one shard are not supported (cut the input into more shards)");
-    return BSK_ERR_UNSUPPORTED;
+// the temporary-storage query of a rocPRIM sort (the *_temp_bytes functions of ops_sort / ops_group / ops_sample)
+static int sort_query(bsk_ctx* c, hipError_t e) {
+    if (e == hipSuccess) return BSK_OK;
+    c->set_error("libbsk: rocPRIM sort size query failed");
+    return BSK_ERR_HIP;
 }
 
 // ---------------------------------------------------------------------------
@@ -165,17 +164,7 @@ int fq2fa_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hip
     rc = ensure_record_scratch(c);
     if (rc != BSK_OK) return rc;
     HIP_TRYX(c, launch_seq_size(d_buf, c->table, P, c->d_out_len, c->d_status, st));
-    uint64_t total = 0, kept = 0;
-    rc = finish_sizes(c, st, &total, &kept);
-    if (rc != BSK_OK) return rc;
-    rc = ensure_out(c, total);
-    if (rc != BSK_OK) return rc;
-    apply_long(c, &P);
-    { const int rce = emit_records(c, d_buf, n, P, total, kept, st); if (rce != BSK_OK) return rce; }
-    out->d_data = c->d_out;
-    out->len = total;
-    out->records = kept;
-    return BSK_OK;
+    return emit_sized(c, d_buf, n, P, st, out);
 }
 
 // shuffle: the records in ascending order of their draws -- keys, one radix sort, the segments of the copy in that order
@@ -183,25 +172,21 @@ static int shuffle_emit(bsk_ctx* c, const uint8_t* d_buf, size_t n, uint64_t tot
     const RecordTable& t = c->table;
     const uint64_t N = t.n;
     size_t tmp_bytes = 0;
-    if (sort_pairs_bits_iota_temp_bytes(N, 0, 64, &tmp_bytes) != hipSuccess) { c->set_error("libbsk: rocPRIM sort size query failed"); return BSK_ERR_HIP; }
+    int rc = sort_query(c, sort_pairs_bits_iota_temp_bytes(N, 0, 64, &tmp_bytes));
+    if (rc != BSK_OK) return rc;
     Arena A;
     const uint64_t o_keys = A.take(2 * N * 8), o_perm = A.take(N * 4), o_len = A.take(N * 4), o_off = A.take((N + 1) * 8),
                    o_tmp = A.take(tmp_bytes ? tmp_bytes : 16);
-    int rc = arena_reserve(c, &A);
+    rc = arena_reserve(c, &A);
     if (rc != BSK_OK) return rc;
     uint64_t* keys = A.at<uint64_t>(o_keys);
     uint32_t* perm = A.at<uint32_t>(o_perm);
     uint32_t* len_perm = A.at<uint32_t>(o_len);
     uint64_t* seg_off = A.at<uint64_t>(o_off);
-    rc = grow(c, &c->d_seg_src, &c->seg_src_cap, N + 1, N / 8 + 16);
-    if (rc != BSK_OK) return rc;
-    rc = grow(c, &c->d_seg_first, &c->seg_first_cap, seg_tiles(total) + 1, 64);
+    rc = seg_begin(c, N, total, st);
     if (rc != BSK_OK) return rc;
     rc = ensure_out(c, total);
     if (rc != BSK_OK) return rc;
-    uint64_t* d_other = c->d_seg_src + N;
-    const bool plain = c->tune.is("segcopy", "off");
-    HIP_TRYX(c, hipMemsetAsync(d_other, 0, sizeof(uint64_t), st));
     {
         Timed tm(c, "k_shuffle_keys", st);
         HIP_TRYX(c, launch_shuffle_keys(N, c->opts.i("Seed"), keys, st));
@@ -212,20 +197,15 @@ static int shuffle_emit(bsk_ctx* c, const uint8_t* d_buf, size_t n, uint64_t tot
     }
     {
         Timed tm(c, "k_shuffle_segments", st);
-        HIP_TRYX(c, launch_shuffle_segments(d_buf, n, t, c->d_out_len, perm, c->d_seg_src, len_perm, d_other, st));
+        HIP_TRYX(c, launch_shuffle_segments(d_buf, n, t, c->d_out_len, perm, c->d_seg_src, len_perm, seg_other(c), st));
     }
     HIP_TRYX(c, launch_scan_u32(len_perm, seg_off, N, c->d_scan_tmp, st));
-    if (plain) {
+    if (!segcopy_on(c)) {
         HIP_TRYX(c, launch_shuffle_fix(d_buf, t, perm, len_perm, seg_off, c->d_seg_src, c->d_out, true, st));
     } else {
-        {
-            Timed tm(c, "k_seg_copy", st);
-            HIP_TRYX(c, launch_seg_first(seg_off, N, c->d_seg_first, st));
-            HIP_TRYX(c, launch_seg_copy(c->d_seg_src, seg_off, N, c->d_seg_first, c->d_out, total, d_buf, d_buf + n, st));
-        }
         uint64_t other = 0;
-        HIP_TRYX(c, hipMemcpyAsync(&other, d_other, sizeof other, hipMemcpyDeviceToHost, st));
-        HIP_TRYX(c, hipStreamSynchronize(st));
+        rc = seg_run(c, SegList{c->d_seg_src, seg_off, N, total}, c->d_out, d_buf, n, st, &other);
+        if (rc != BSK_OK) return rc;
         if (other) HIP_TRYX(c, launch_shuffle_fix(d_buf, t, perm, len_perm, seg_off, c->d_seg_src, c->d_out, false, st));
     }
     out->d_data = c->d_out;
@@ -318,8 +298,7 @@ int records_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, h
         rc = check_u32_records(c, "shuffle");  // 32-bit permutation
         return rc != BSK_OK ? rc : shuffle_emit(c, d_buf, n, total, st, out);
     }
-    const char* sg = c->tune.get("segcopy");
-    const bool segments = P.times == 1 && !(sg && strcmp(sg, "off") == 0);
+    const bool segments = P.times == 1 && segcopy_on(c);
     // sample with out=slices: the kept records are verbatim pieces of the shard, in file order -- the segment list IS the result
     // (a record that was dropped is a segment of no bytes) and the block is neither allocated nor written
     const bool as_slices = segments && c->op == Op::Sample && slices_wanted(c);
@@ -330,60 +309,40 @@ int records_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, h
     if (segments) {
         // range / head / sample: the kept records are verbatim segments of the shard (ops_segcopy.hip)
         const RecordTable& t = c->table;
-        rc = grow(c, &c->d_seg_src, &c->seg_src_cap, t.n + 1, t.n / 8 + 16);
+        rc = seg_begin(c, t.n, total, st);
         if (rc != BSK_OK) return rc;
-        rc = grow(c, &c->d_seg_first, &c->seg_first_cap, seg_tiles(total) + 1, 64);
-        if (rc != BSK_OK) return rc;
-        uint64_t* d_other = c->d_seg_src + t.n;
-        uint64_t other = 0;
-        auto read_other = [&]() -> int {  // (the one synchronisation of this step, before or after the copy)
-            HIP_TRYX(c, hipMemcpyAsync(&other, d_other, sizeof other, hipMemcpyDeviceToHost, st));
-            HIP_TRYX(c, hipStreamSynchronize(st));
-            return BSK_OK;
-        };
-        HIP_TRYX(c, hipMemsetAsync(d_other, 0, sizeof(uint64_t), st));
+        const SegList L{c->d_seg_src, c->d_out_off, t.n, total};
         {
             Timed tm(c, "k_seg_prep", st);
-            HIP_TRYX(c, launch_seg_build_text(d_buf, n, t, c->d_out_len, c->d_seg_src, d_other, st));
-            HIP_TRYX(c, launch_seg_first(c->d_out_off, t.n, c->d_seg_first, st));
+            HIP_TRYX(c, launch_seg_build_text(d_buf, n, t, c->d_out_len, c->d_seg_src, seg_other(c), st));
         }
+        uint64_t other = 0;
         if (as_slices) {
-            rc = read_other();
+            rc = seg_first(c, L, st, &other);  // (the one synchronisation of this step: here before the copy)
             if (rc != BSK_OK) return rc;
             if (other == 0) {
-                out_as_segments(c, out, c->d_seg_src, c->d_out_off, t.n, c->d_seg_first, d_buf, d_buf + n, total, kept);
+                out_as_segments(c, out, L.src, L.off, L.nseg, c->d_seg_first, d_buf, d_buf + n, total, kept);
                 return BSK_OK;
             }
             rc = ensure_out(c, total);  // (a kept last record without its newline: one block after all)
-            if (rc != BSK_OK) return rc;
+            if (rc == BSK_OK) rc = seg_copy(c, L, c->d_out, d_buf, n, st);
+        } else {
+            rc = seg_run(c, L, c->d_out, d_buf, n, st, &other);
         }
-        {
-            Timed tm(c, "k_seg_copy", st);
-            HIP_TRYX(c, launch_seg_copy(c->d_seg_src, c->d_out_off, t.n, c->d_seg_first, c->d_out, total, d_buf, d_buf + n, st));
-        }
-        if (!as_slices) {
-            rc = read_other();
-            if (rc != BSK_OK) return rc;
-        }
+        if (rc != BSK_OK) return rc;
         if (other) HIP_TRYX(c, launch_seg_fix_text(d_buf, t, c->d_out_len, c->d_out_off, c->d_seg_src, c->d_out, st));
-    } else if (P.times <= 4 && !(sg && strcmp(sg, "off") == 0)) {
+    } else if (P.times <= 4 && segcopy_on(c)) {
         // duplicate -n 2..4: `times` segments per record (more copies: the tile copy below, whose tables do not grow with n)
         const RecordTable& t = c->table;
         const uint64_t ns = t.n * P.times;
-        rc = grow(c, &c->d_seg_src, &c->seg_src_cap, 2 * ns + 2, ns / 4 + 16);
-        if (rc != BSK_OK) return rc;
-        rc = grow(c, &c->d_seg_first, &c->seg_first_cap, seg_tiles(total) + 1, 64);
+        rc = seg_begin(c, 2 * ns + 1, total, st);
         if (rc != BSK_OK) return rc;
         uint64_t* seg_src = c->d_seg_src;
         uint64_t* seg_off2 = c->d_seg_src + ns;       // [ns + 1]
-        uint64_t* d_other = c->d_seg_src + 2 * ns + 1;
-        HIP_TRYX(c, hipMemsetAsync(d_other, 0, sizeof(uint64_t), st));
-        HIP_TRYX(c, launch_seg_build_text_times(d_buf, n, t, c->d_out_len, c->d_out_off, P.times, seg_src, seg_off2, d_other, st));
-        HIP_TRYX(c, launch_seg_first(seg_off2, ns, c->d_seg_first, st));
-        HIP_TRYX(c, launch_seg_copy(seg_src, seg_off2, ns, c->d_seg_first, c->d_out, total, d_buf, d_buf + n, st));
+        HIP_TRYX(c, launch_seg_build_text_times(d_buf, n, t, c->d_out_len, c->d_out_off, P.times, seg_src, seg_off2, seg_other(c), st));
         uint64_t other = 0;
-        HIP_TRYX(c, hipMemcpyAsync(&other, d_other, sizeof other, hipMemcpyDeviceToHost, st));
-        HIP_TRYX(c, hipStreamSynchronize(st));
+        rc = seg_run(c, SegList{seg_src, seg_off2, ns, total}, c->d_out, d_buf, n, st, &other);
+        if (rc != BSK_OK) return rc;
         if (other) HIP_TRYX(c, launch_seg_fix_text_times(d_buf, t, c->d_out_len, c->d_out_off, P.times, seg_src, c->d_out, st));
     } else {
         rc = grow(c, &c->d_tile_first, &c->tile_first_cap, records_copy_tiles(total), 64);
@@ -403,109 +362,64 @@ int records_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, h
 // input.  Output in file order (the reference's group order is whatever GroupByKey yields); PARITY.md REN.
 // ---------------------------------------------------------------------------
 int rename_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, bsk_out* out) {
-    const Options& o = c->opts;
     const bool fastq = format == BSK_FORMAT_FASTQ;
-    int rc = build_index(c, d_buf, n, format, st);
-    if (rc == BSK_OK) rc = check_u32_records(c, "rename");  // (group << 32 | index) keys, u32 permutations
+    TextTableH tt;
+    RmDupParams P;
+    int rc = group_index(c, d_buf, n, format, "rename", st, &tt, &P);
     if (rc != BSK_OK) return rc;
     if (c->table.n == 0) return empty_result(c, out);
-    TextTableH tt;
-    rc = prepare_text(c, d_buf, format, st, &tt);
-    if (rc != BSK_OK) return rc;
-    RmDupParams P;
-    memset(&P, 0, sizeof P);
-    P.fastq = fastq;
-    P.by_name = o.b("ByName");
-    P.id_mode = id_mode_of(c);
-    P.line_width = fastq ? 0 : (int)o.ci("LineWidth");
-    P.buf_end = d_buf + n;
+    P.by_name = c->opts.b("ByName");
     const uint64_t N = c->table.n;
-    rc = grow(c, &c->d_keys, &c->keys_cap, N, N / 8 + 16);
-    if (rc != BSK_OK) return rc;
-    rc = ensure_record_scratch(c);
-    if (rc != BSK_OK) return rc;
-    // groups: the rmdup machinery (XXH64 of the ID / name, first occurrence wins, exact verification of every other one)
-    HIP_TRYX(c, launch_rmdup_hash(d_buf, n, c->table, tt, P, c->d_keys, nullptr, st));
     Arena A;
     const uint64_t o_has = A.take(N), o_ord = A.take(N * 4);
     rc = arena_reserve(c, &A);
     if (rc != BSK_OK) return rc;
-    uint8_t* d_has = A.at<uint8_t>(o_has);   // (launch_rmdup_group also marks the groups of two or more; not needed here)
-    uint32_t* d_ord = A.at<uint32_t>(o_ord);
-    uint64_t* d_list = nullptr;
-    void* d_tmp = nullptr;
-    auto cleanup = [&]() {};
-    auto fail = [&](int code) { return code; };
-    HIP_TRYX(c, hipMemsetAsync(d_has, 0, N, st));
-    HIP_TRYX(c, hipMemsetAsync(d_ord, 0, N * 4, st));
-    // collisions checked, and d_keys[i] := first record of i's group
-    rc = group_resolve(c, d_buf, tt, P, d_has, st);
+    HIP_TRYX(c, hipMemsetAsync(A.at<uint32_t>(o_ord), 0, N * 4, st));
+    rc = group_by_key(c, d_buf, n, tt, P, A.at<uint8_t>(o_has), st);  // (d_has: the groups of two or more; not needed here)
     if (rc != BSK_OK) return rc;
+    // how many records are not the first of their group (the list is allocated to size): out_len of the grouping is 0
+    // exactly for those
+    uint64_t firsts = 0;
     HIP_TRYX(c, hipMemsetAsync(c->d_counter, 0, 4 * sizeof(uint64_t), st));
-    // how many records are not the first of their group
-    uint64_t status = 0, m = 0;
-    {
-        // count first (the list is allocated to size): out_len of resolve is 0 exactly for the dropped records
-        HIP_TRYX(c, launch_count_nonzero(c->d_out_len, N, c->d_counter, st));
-        uint64_t firsts = 0;
-        HIP_TRYX(c, hipMemcpyAsync(&firsts, c->d_counter, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRYX(c, hipMemcpyAsync(&status, c->d_status, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRYX(c, hipStreamSynchronize(st));
-        if (status & ERR_HASH_COLLISION) {
-            c->set_error("libbsk: two distinct subjects share one 64-bit XXH64 key; refusing to guess (rerun on the CPU path)");
-            return fail(BSK_ERR_UNSUPPORTED);
-        }
-        rc = kernel_error_to_status(c, status);
-        if (rc != BSK_OK) return fail(rc);
-        m = N - firsts;
-    }
+    HIP_TRYX(c, launch_count_nonzero(c->d_out_len, N, c->d_counter, st));
+    rc = group_status(c, st, c->d_counter, &firsts);
+    if (rc != BSK_OK) return rc;
+    const uint64_t m = N - firsts;
     if (m) {
         size_t tmp_bytes = 0;
-        if (group_sort_temp_bytes(m, &tmp_bytes) != hipSuccess) { c->set_error("libbsk: rocPRIM sort size query failed"); return BSK_ERR_HIP; }
-        // the arena may move when it grows: d_ord has to survive, so it is re-derived after the reservation
+        rc = sort_query(c, group_sort_temp_bytes(m, &tmp_bytes));
+        if (rc != BSK_OK) return rc;
+        // the arena may move when it grows: the ordinals (zeroed above) have to survive
+        const uint64_t keep = A.used;
         const uint64_t o_list = A.take(2 * m * 8), o_tmp = A.take(tmp_bytes ? tmp_bytes : 16);
-        if (A.used > c->arena_cap) {
-            // grow by hand, keeping the first part (has / ord)
-            uint8_t* nb = nullptr;
-            const uint64_t cap = A.used + A.used / 8 + 256;
-            if (hipMalloc((void**)&nb, cap) != hipSuccess) { c->set_error("libbsk: out of device memory (rename)"); return BSK_ERR_HIP; }
-            HIP_TRYX(c, hipMemcpyAsync(nb, c->d_arena, o_list, hipMemcpyDeviceToDevice, st));
-            HIP_TRYX(c, hipStreamSynchronize(st));
-            hipFree(c->d_arena);
-            c->d_arena = nb;
-            c->arena_cap = cap;
-        }
-        A.base = c->d_arena;
-        d_has = A.at<uint8_t>(o_has);
-        d_ord = A.at<uint32_t>(o_ord);
-        d_list = A.at<uint64_t>(o_list);
-        d_tmp = A.at<uint8_t>(o_tmp);
+        rc = arena_reserve_keep(c, &A, keep, st);
+        if (rc != BSK_OK) return rc;
+        uint64_t* d_list = A.at<uint64_t>(o_list);
         HIP_TRYX(c, hipMemsetAsync(c->d_counter, 0, 8, st));
         HIP_TRYX(c, launch_group_compact(c->d_keys, N, d_list, c->d_counter, st));
-        HIP_TRYX(c, launch_group_sort(d_tmp, tmp_bytes, d_list, d_list + m, m, st, N));
-        HIP_TRYX(c, launch_group_ordinals(d_list + m, m, d_ord, st));
+        HIP_TRYX(c, launch_group_sort(A.at<uint8_t>(o_tmp), tmp_bytes, d_list, d_list + m, m, st, N));
+        HIP_TRYX(c, launch_group_ordinals(d_list + m, m, A.at<uint32_t>(o_ord), st));
     }
     SeqParams F = format_params(c, fastq);
     F.text_w = tt.text_w; F.lin_off = tt.lin_off; F.lin = tt.lin;
     F.buf_end = d_buf + n;
-    F.ren_ord = d_ord;
+    F.ren_ord = A.at<uint32_t>(o_ord);
     HIP_TRYX(c, hipMemsetAsync(c->d_status, 0, 2 * sizeof(uint64_t), st));
     HIP_TRYX(c, launch_seq_size(d_buf, c->table, F, c->d_out_len, c->d_status, st));
     uint64_t total = 0, kept = 0;
     rc = finish_sizes(c, st, &total, &kept);
-    if (rc != BSK_OK) return fail(rc);
+    if (rc != BSK_OK) return rc;
     rc = ensure_out(c, total);
-    if (rc != BSK_OK) return fail(rc);
+    if (rc != BSK_OK) return rc;
     apply_long(c, &F);
     if (m * 4 > N) {
         // many renamed records: their heads are rewritten record by record anyway, and one kernel over all records beats
         // the segmented copy of the rest plus that kernel (every ID twice: 59 vs 63 ms)
         HIP_TRYX(c, launch_seq_emit(d_buf, c->table, F, c->d_out_len, c->d_out_off, c->d_out, st, total, kept));
     } else {
-        const int rce = emit_records(c, d_buf, n, F, total, kept, st);
-        if (rce != BSK_OK) return rce;
+        rc = emit_records(c, d_buf, n, F, total, kept, st);
+        if (rc != BSK_OK) return rc;
     }
-    cleanup();
     out->d_data = c->d_out;
     out->len = total;
     out->records = kept;
@@ -550,7 +464,8 @@ int sort_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipS
     const bool desc = o.b("Reverse");  // SortByKey(!reverse, ...)
     // scratch: keys x2, perm x2, key lengths, rocPRIM temporary storage
     size_t tmp_bytes = 0;
-    if (sort_pairs_temp_bytes(N, &tmp_bytes) != hipSuccess) { c->set_error("libbsk: rocPRIM sort size query failed"); return BSK_ERR_HIP; }
+    rc = sort_query(c, sort_pairs_temp_bytes(N, &tmp_bytes));
+    if (rc != BSK_OK) return rc;
     Arena A;
     const uint64_t o_keys = A.take(2 * N * 8), o_perm = A.take(2 * N * 4), o_klen = A.take((N + 1) * 4),
                    o_tmp = A.take(tmp_bytes ? tmp_bytes : 16);
@@ -565,53 +480,50 @@ int sort_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipS
     uint32_t* d_perm2 = A.at<uint32_t>(o_perm);   // [2 N]
     uint32_t* d_klen = A.at<uint32_t>(o_klen);    // [N + 1]   (last: max)
     void* d_tmp = A.at<uint8_t>(o_tmp);
-    auto cleanup = [&]() {};
-    auto fail = [&](int code) { return code; };
     uint64_t* kin = d_keys2;
     uint64_t* kout = d_keys2 + N;
     uint32_t* pin = d_perm2;
     uint32_t* pout = d_perm2 + N;
-    if (launch_sort_iota(pin, N, st) != hipSuccess) return fail(BSK_ERR_HIP);
+    HIP_TRYX(c, launch_sort_iota(pin, N, st));
     if (P.mode >= 3) {
-        if (launch_sort_intkeys(d_buf, c->table, tt, P, kin, st) != hipSuccess ||
-            launch_sort_pairs(d_tmp, tmp_bytes, kin, kout, pin, pout, N, desc, 32, st) != hipSuccess) return fail(BSK_ERR_HIP);
+        HIP_TRYX(c, launch_sort_intkeys(d_buf, c->table, tt, P, kin, st));
+        HIP_TRYX(c, launch_sort_pairs(d_tmp, tmp_bytes, kin, kout, pin, pout, N, desc, 32, st));
         std::swap(pin, pout);
     } else {
-        uint8_t* d_nat = nullptr;
+        struct FreeNat { uint8_t* p = nullptr; ~FreeNat() { if (p) hipFree(p); } } nat;  // (sort -N: keys in an allocation of their own)
         if (o.b("InNaturalOrder") && P.mode <= 1) {
             // natural order (sort.go:130-133: IDs / names only): keys rewritten so that byte order is natural order
             uint32_t* d_nlen = c->d_out_len;     // scratch of N entries, free until the size pass
             uint64_t* d_noff = c->d_out_off;     // [N + 1]
             rc = ensure_record_scratch(c);
-            if (rc != BSK_OK) return fail(rc);
+            if (rc != BSK_OK) return rc;
             d_nlen = c->d_out_len; d_noff = c->d_out_off;
             uint64_t nat_bytes = 0;
-            if (launch_sort_natlen(d_buf, c->table, P, d_nlen, st) != hipSuccess ||
-                launch_scan_u32(d_nlen, d_noff, N, c->d_scan_tmp, st) != hipSuccess ||
-                hipMemcpyAsync(&nat_bytes, d_noff + N, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipStreamSynchronize(st) != hipSuccess) return fail(BSK_ERR_HIP);
+            HIP_TRYX(c, launch_sort_natlen(d_buf, c->table, P, d_nlen, st));
+            HIP_TRYX(c, launch_scan_u32(d_nlen, d_noff, N, c->d_scan_tmp, st));
+            HIP_TRYX(c, hipMemcpyAsync(&nat_bytes, d_noff + N, 8, hipMemcpyDeviceToHost, st));
+            HIP_TRYX(c, hipStreamSynchronize(st));
             // the offsets must survive the size pass below: keep them (and the keys) in their own allocation
-            if (hipMalloc((void**)&d_nat, nat_bytes + 16 + (N + 1) * 8) != hipSuccess) { c->set_error("libbsk: out of device memory (sort -N)"); return fail(BSK_ERR_HIP); }
-            uint64_t* d_noff2 = reinterpret_cast<uint64_t*>(d_nat);
-            uint8_t* d_keys_nat = d_nat + (N + 1) * 8;
-            if (hipMemcpyAsync(d_noff2, d_noff, (N + 1) * 8, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-                launch_sort_natkeys(d_buf, c->table, P, d_noff2, d_keys_nat, st) != hipSuccess) { hipFree(d_nat); return fail(BSK_ERR_HIP); }
+            HIP_TRYX(c, hipMalloc((void**)&nat.p, nat_bytes + 16 + (N + 1) * 8));
+            uint64_t* d_noff2 = reinterpret_cast<uint64_t*>(nat.p);
+            uint8_t* d_keys_nat = nat.p + (N + 1) * 8;
+            HIP_TRYX(c, hipMemcpyAsync(d_noff2, d_noff, (N + 1) * 8, hipMemcpyDeviceToDevice, st));
+            HIP_TRYX(c, launch_sort_natkeys(d_buf, c->table, P, d_noff2, d_keys_nat, st));
             P.nat = d_keys_nat;
             P.nat_off = d_noff2;
         }
-        struct FreeNat { uint8_t* p; ~FreeNat() { if (p) hipFree(p); } } free_nat{d_nat};
         uint32_t maxlen = 0;
-        if (hipMemsetAsync(d_klen + N, 0, 4, st) != hipSuccess ||
-            launch_sort_keylen(d_buf, c->table, P, d_klen, d_klen + N, st) != hipSuccess ||
-            hipMemcpyAsync(&maxlen, d_klen + N, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess) return fail(BSK_ERR_HIP);
+        HIP_TRYX(c, hipMemsetAsync(d_klen + N, 0, 4, st));
+        HIP_TRYX(c, launch_sort_keylen(d_buf, c->table, P, d_klen, d_klen + N, st));
+        HIP_TRYX(c, hipMemcpyAsync(&maxlen, d_klen + N, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRYX(c, hipStreamSynchronize(st));
         const uint32_t nchunks = (maxlen + 7) / 8;
         const char* se = c->tune.get("sort");  // lsd: every chunk for every record (the round-1 path)
         if (nchunks <= 3 || (se && strcmp(se, "lsd") == 0)) {
             // LSD over the 8-byte chunks of the keys, last chunk first; every pass is stable
             for (uint32_t ch = nchunks; ch-- > 0;) {
-                if (launch_sort_chunk(d_buf, c->table, tt, P, d_klen, pin, ch, kin, st) != hipSuccess ||
-                    launch_sort_pairs(d_tmp, tmp_bytes, kin, kout, pin, pout, N, desc, 64, st) != hipSuccess) return fail(BSK_ERR_HIP);
+                HIP_TRYX(c, launch_sort_chunk(d_buf, c->table, tt, P, d_klen, pin, ch, kin, st));
+                HIP_TRYX(c, launch_sort_pairs(d_tmp, tmp_bytes, kin, kout, pin, pout, N, desc, 64, st));
                 std::swap(pin, pout);
             }
         } else {
@@ -620,14 +532,14 @@ int sort_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipS
             // rest of the key (LSD over chunks n-1 .. 2 on that subset, then a stable pass by run number puts every run
             // back in its place).  Same result as the full LSD sweep, ties in file order included.
             rc = ensure_record_scratch(c);  // (the scan scratch)
-            if (rc != BSK_OK) return fail(rc);
+            if (rc != BSK_OK) return rc;
             for (uint32_t ch = 2; ch-- > 0;) {
-                if (launch_sort_chunk(d_buf, c->table, tt, P, d_klen, pin, ch, kin, st) != hipSuccess ||
-                    launch_sort_pairs(d_tmp, tmp_bytes, kin, kout, pin, pout, N, desc, 64, st) != hipSuccess) return fail(BSK_ERR_HIP);
+                HIP_TRYX(c, launch_sort_chunk(d_buf, c->table, tt, P, d_klen, pin, ch, kin, st));
+                HIP_TRYX(c, launch_sort_pairs(d_tmp, tmp_bytes, kin, kout, pin, pout, N, desc, 64, st));
                 std::swap(pin, pout);
             }
             // kout = chunk 0 in the new order; chunk 1 in that order once more
-            if (launch_sort_chunk(d_buf, c->table, tt, P, d_klen, pin, 1, kin, st) != hipSuccess) return fail(BSK_ERR_HIP);
+            HIP_TRYX(c, launch_sort_chunk(d_buf, c->table, tt, P, d_klen, pin, 1, kin, st));
             uint32_t* d_tied = A.at<uint32_t>(o_tied);
             uint32_t* d_start = A.at<uint32_t>(o_start);
             uint64_t* d_rank = A.at<uint64_t>(o_rank);
@@ -637,24 +549,23 @@ int sort_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipS
             uint32_t* sp_in = A.at<uint32_t>(o_subperm);
             uint32_t* sp_out = sp_in + N;
             uint64_t m = 0;
-            if (launch_sort_tie_flags(kout, kin, N, d_tied, d_start, st) != hipSuccess ||
-                launch_scan_u32(d_tied, d_rank, N, c->d_scan_tmp, st) != hipSuccess ||
-                launch_scan_u32(d_start, d_run, N, c->d_scan_tmp, st) != hipSuccess ||
-                hipMemcpyAsync(&m, d_rank + N, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipStreamSynchronize(st) != hipSuccess) return fail(BSK_ERR_HIP);
+            HIP_TRYX(c, launch_sort_tie_flags(kout, kin, N, d_tied, d_start, st));
+            HIP_TRYX(c, launch_scan_u32(d_tied, d_rank, N, c->d_scan_tmp, st));
+            HIP_TRYX(c, launch_scan_u32(d_start, d_run, N, c->d_scan_tmp, st));
+            HIP_TRYX(c, hipMemcpyAsync(&m, d_rank + N, 8, hipMemcpyDeviceToHost, st));
+            HIP_TRYX(c, hipStreamSynchronize(st));
             if (m) {
-                if (launch_sort_tie_gather(d_tied, d_rank, d_run, d_start, pin, N, d_sub_pos, sp_in, d_run_of, st) != hipSuccess)
-                    return fail(BSK_ERR_HIP);
+                HIP_TRYX(c, launch_sort_tie_gather(d_tied, d_rank, d_run, d_start, pin, N, d_sub_pos, sp_in, d_run_of, st));
                 uint64_t* sk_in = kin;   // the key buffers are free again
                 uint64_t* sk_out = kout;
                 for (uint32_t ch = nchunks; ch-- > 2;) {
-                    if (launch_sort_chunk(d_buf, c->table, tt, P, d_klen, sp_in, ch, sk_in, st, m) != hipSuccess ||
-                        launch_sort_pairs(d_tmp, tmp_bytes, sk_in, sk_out, sp_in, sp_out, m, desc, 64, st) != hipSuccess) return fail(BSK_ERR_HIP);
+                    HIP_TRYX(c, launch_sort_chunk(d_buf, c->table, tt, P, d_klen, sp_in, ch, sk_in, st, m));
+                    HIP_TRYX(c, launch_sort_pairs(d_tmp, tmp_bytes, sk_in, sk_out, sp_in, sp_out, m, desc, 64, st));
                     std::swap(sp_in, sp_out);
                 }
-                if (launch_sort_gather_keys(d_run_of, sp_in, m, sk_in, st) != hipSuccess ||
-                    launch_sort_pairs(d_tmp, tmp_bytes, sk_in, sk_out, sp_in, sp_out, m, false, 64, st) != hipSuccess ||
-                    launch_sort_tie_scatter(d_sub_pos, sp_out, m, pin, st) != hipSuccess) return fail(BSK_ERR_HIP);
+                HIP_TRYX(c, launch_sort_gather_keys(d_run_of, sp_in, m, sk_in, st));
+                HIP_TRYX(c, launch_sort_pairs(d_tmp, tmp_bytes, sk_in, sk_out, sp_in, sp_out, m, false, 64, st));
+                HIP_TRYX(c, launch_sort_tie_scatter(d_sub_pos, sp_out, m, pin, st));
             }
         }
     }
@@ -663,42 +574,36 @@ int sort_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipS
     F.text_w = tt.text_w; F.lin_off = tt.lin_off; F.lin = tt.lin;
     F.buf_end = d_buf + n;
     rc = ensure_record_scratch(c);
-    if (rc != BSK_OK) return fail(rc);
-    if (launch_seq_size(d_buf, c->table, F, c->d_out_len, c->d_status, st) != hipSuccess) return fail(BSK_ERR_HIP);
+    if (rc != BSK_OK) return rc;
+    HIP_TRYX(c, launch_seq_size(d_buf, c->table, F, c->d_out_len, c->d_status, st));
     uint64_t total = 0, kept = 0;
     rc = finish_sizes(c, st, &total, &kept);
-    if (rc != BSK_OK) return fail(rc);
+    if (rc != BSK_OK) return rc;
     uint32_t* len_perm = pout;  // the other permutation buffer is free now
     uint64_t* off_perm = kin;   // [N + 1] fits: kin and kout are adjacent (2 N entries)
     if (kin != d_keys2) off_perm = d_keys2;
-    if (launch_sort_gather(c->d_out_len, pin, N, len_perm, st) != hipSuccess ||
-        launch_scan_u32(len_perm, off_perm, N, c->d_scan_tmp, st) != hipSuccess ||
-        launch_sort_scatter(off_perm, pin, N, c->d_out_off, st) != hipSuccess) return fail(BSK_ERR_HIP);
+    HIP_TRYX(c, launch_sort_gather(c->d_out_len, pin, N, len_perm, st));
+    HIP_TRYX(c, launch_scan_u32(len_perm, off_perm, N, c->d_scan_tmp, st));
+    HIP_TRYX(c, launch_sort_scatter(off_perm, pin, N, c->d_out_off, st));
     rc = ensure_out(c, total);
-    if (rc != BSK_OK) return fail(rc);
+    if (rc != BSK_OK) return rc;
     apply_long(c, &F);
     // the offsets follow the SORTED order: the segments of the copy are the records in that order (FASTQ records that leave
     // unchanged; ops_segcopy.hip), the record-wise emit writes what is left
-    const char* sg = c->tune.get("segcopy");
     bool seg_done = false;
-    if (fastq && !F.ren_ord && !(sg && strcmp(sg, "off") == 0) && ((sg && strcmp(sg, "force") == 0) || total >= (4u << 20))) {
-        if (grow(c, &c->d_seg_src, &c->seg_src_cap, 2 * N + 1, N / 4 + 16) != BSK_OK ||
-            grow(c, &c->d_seg_first, &c->seg_first_cap, seg_tiles(total) + 1, 64) != BSK_OK) return fail(BSK_ERR_HIP);
+    if (fastq && !F.ren_ord && segcopy_on(c, total)) {
+        rc = seg_begin(c, 2 * N, total, st);
+        if (rc != BSK_OK) return rc;
         uint64_t* seg_sorted = c->d_seg_src;
         uint64_t* seg_rec = c->d_seg_src + N;
-        uint64_t* d_other = c->d_seg_src + 2 * N;
         uint64_t other = 0;
-        if (hipMemsetAsync(d_other, 0, sizeof(uint64_t), st) != hipSuccess ||
-            launch_seg_build_fastq_perm(d_buf, n, c->table, c->d_out_len, pin, seg_sorted, seg_rec, d_other, st) != hipSuccess ||
-            launch_seg_first(off_perm, N, c->d_seg_first, st) != hipSuccess ||
-            launch_seg_copy(seg_sorted, off_perm, N, c->d_seg_first, c->d_out, total, d_buf, d_buf + n, st) != hipSuccess ||
-            hipMemcpyAsync(&other, d_other, sizeof other, hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess) return fail(BSK_ERR_HIP);
+        HIP_TRYX(c, launch_seg_build_fastq_perm(d_buf, n, c->table, c->d_out_len, pin, seg_sorted, seg_rec, seg_other(c), st));
+        rc = seg_run(c, SegList{seg_sorted, off_perm, N, total}, c->d_out, d_buf, n, st, &other);
+        if (rc != BSK_OK) return rc;
         if (other == 0) seg_done = true;
         else F.seg_src = seg_rec;
     }
-    if (!seg_done && launch_seq_emit(d_buf, c->table, F, c->d_out_len, c->d_out_off, c->d_out, st, total, kept) != hipSuccess) return fail(BSK_ERR_HIP);
-    cleanup();
+    if (!seg_done) HIP_TRYX(c, launch_seq_emit(d_buf, c->table, F, c->d_out_len, c->d_out_off, c->d_out, st, total, kept));
     out->d_data = c->d_out;
     out->len = total;
     out->records = kept;
@@ -803,14 +708,13 @@ int faidx_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hip
     rc = arena_reserve(c, &A);
     if (rc != BSK_OK) return rc;
     uint32_t* d_lb = A.at<uint32_t>(o_lb);
-    auto fail = [&](int code) { return code; };
-    if (hipMemsetAsync(c->d_status + 1, 0xFF, 8, st) != hipSuccess ||
-        launch_faidx_size(d_buf, c->table, P, c->d_out_len, d_lb, c->d_status, st) != hipSuccess ||
-        launch_scan_u32(c->d_out_len, c->d_out_off, N, c->d_scan_tmp, st) != hipSuccess) return fail(BSK_ERR_HIP);
+    HIP_TRYX(c, hipMemsetAsync(c->d_status + 1, 0xFF, 8, st));
+    HIP_TRYX(c, launch_faidx_size(d_buf, c->table, P, c->d_out_len, d_lb, c->d_status, st));
+    HIP_TRYX(c, launch_scan_u32(c->d_out_len, c->d_out_off, N, c->d_scan_tmp, st));
     uint64_t total = 0, status[2] = {0, 0};
-    if (hipMemcpyAsync(&total, c->d_out_off + N, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(status, c->d_status, 16, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) return fail(BSK_ERR_HIP);
+    HIP_TRYX(c, hipMemcpyAsync(&total, c->d_out_off + N, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRYX(c, hipMemcpyAsync(status, c->d_status, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRYX(c, hipStreamSynchronize(st));
     if (status[0] & ERR_LINE_LENGTHS) {
         // the first offending record names the error (faidx.go:131)
         uint64_t start = 0;
@@ -833,13 +737,13 @@ int faidx_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hip
             }
         }
         c->set_error("different line length in sequence: " + id + ". Please format the file with 'seqkit seq'");
-        return fail(BSK_ERR_FORMAT);
+        return BSK_ERR_FORMAT;
     }
     rc = kernel_error_to_status(c, status[0]);
-    if (rc != BSK_OK) return fail(rc);
+    if (rc != BSK_OK) return rc;
     rc = ensure_out(c, total);
-    if (rc != BSK_OK) return fail(rc);
-    if (launch_faidx_rows(d_buf, c->table, P, d_lb, c->d_out_off, c->d_out, st) != hipSuccess) return fail(BSK_ERR_HIP);
+    if (rc != BSK_OK) return rc;
+    HIP_TRYX(c, launch_faidx_rows(d_buf, c->table, P, d_lb, c->d_out_off, c->d_out, st));
     out->d_data = c->d_out;
     out->len = total;
     out->records = N;
@@ -856,29 +760,18 @@ int pair_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, size_t n_first, 
     const Options& o = c->opts;
     const bool fastq = format == BSK_FORMAT_FASTQ;
     for (int k = 0; k < 4; ++k) { outs[k].d_data = nullptr; outs[k].len = 0; outs[k].records = 0; }
-    int rc = build_index(c, d_buf, n, format, st);
-    if (rc == BSK_OK) rc = check_u32_records(c, "pair");  // (group << 32 | index) keys, u32 permutations
+    TextTableH tt;
+    RmDupParams P;
+    int rc = group_index(c, d_buf, n, format, "pair", st, &tt, &P);
     if (rc != BSK_OK) return rc;
     if (c->table.n == 0) {
         bsk_out tmp;
         return empty_result(c, &tmp);
     }
-    TextTableH tt;
-    rc = prepare_text(c, d_buf, format, st, &tt);
-    if (rc != BSK_OK) return rc;
     const uint64_t N = c->table.n;
-    RmDupParams P;
-    memset(&P, 0, sizeof P);
-    P.fastq = fastq;
-    P.id_mode = id_mode_of(c);
-    P.line_width = fastq ? 0 : (int)o.ci("LineWidth");
-    P.buf_end = d_buf + n;
-    rc = grow(c, &c->d_keys, &c->keys_cap, N, N / 8 + 16);
-    if (rc != BSK_OK) return rc;
-    rc = ensure_record_scratch(c);
-    if (rc != BSK_OK) return rc;
     size_t tmp_bytes = 0;
-    if (group_sort_temp_bytes(N, &tmp_bytes) != hipSuccess) { c->set_error("libbsk: rocPRIM sort size query failed"); return BSK_ERR_HIP; }
+    rc = sort_query(c, group_sort_temp_bytes(N, &tmp_bytes));
+    if (rc != BSK_OK) return rc;
     Arena A;
     const uint64_t o_has = A.take(N), o_list = A.take(2 * N * 8), o_tmp = A.take(tmp_bytes ? tmp_bytes : 16),
                    o_state = A.take(N), o_partner = A.take(N * 4), o_fmt = A.take(N * 4), o_len = A.take(N * 4),
@@ -894,23 +787,13 @@ int pair_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, size_t n_first, 
     uint64_t* d_off = A.at<uint64_t>(o_off);
     uint64_t* d_offw = A.at<uint64_t>(o_offw);
     uint64_t* d_tot = A.at<uint64_t>(o_tot);
-    // groups by ID (XXH64, first occurrence, exact verification of every other member)
-    HIP_TRYX(c, launch_rmdup_hash(d_buf, n, c->table, tt, P, c->d_keys, nullptr, st));
-    HIP_TRYX(c, hipMemsetAsync(d_has, 0, N, st));
-    rc = group_resolve(c, d_buf, tt, P, d_has, st);
+    rc = group_by_key(c, d_buf, n, tt, P, d_has, st);  // groups by ID
     if (rc != BSK_OK) return rc;
     HIP_TRYX(c, hipMemsetAsync(d_tot, 0, 8 * 8, st));
     HIP_TRYX(c, hipMemsetAsync(c->d_counter, 0, 4 * sizeof(uint64_t), st));
     HIP_TRYX(c, launch_count_below(c->table.start, N, n_first, c->d_counter, st));
-    uint64_t first2 = 0, status = 0;
-    HIP_TRYX(c, hipMemcpyAsync(&first2, c->d_counter, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRYX(c, hipMemcpyAsync(&status, c->d_status, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRYX(c, hipStreamSynchronize(st));
-    if (status & ERR_HASH_COLLISION) {
-        c->set_error("libbsk: two distinct subjects share one 64-bit XXH64 key; refusing to guess (rerun on the CPU path)");
-        return BSK_ERR_UNSUPPORTED;
-    }
-    rc = kernel_error_to_status(c, status);
+    uint64_t first2 = 0, status = 0;  // first2: the first record of file 2, back with the status of the grouping
+    rc = group_status(c, st, c->d_counter, &first2);
     if (rc != BSK_OK) return rc;
     HIP_TRYX(c, launch_group_all(c->d_keys, N, d_list, st));
     HIP_TRYX(c, launch_group_sort(A.at<uint8_t>(o_tmp), tmp_bytes, d_list, d_list + N, N, st, N, /*index_ordered=*/true));
@@ -979,27 +862,15 @@ int common_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, const uint64_t
                       hipStream_t st, bsk_out* out) {
     const Options& o = c->opts;
     const bool fastq = format == BSK_FORMAT_FASTQ;
-    int rc = build_index(c, d_buf, n, format, st);
-    if (rc == BSK_OK) rc = check_u32_records(c, "common");  // (group << 32 | index) keys, u32 permutations
+    TextTableH tt;
+    RmDupParams P;
+    int rc = group_index(c, d_buf, n, format, "common", st, &tt, &P);
     if (rc != BSK_OK) return rc;
     if (c->table.n == 0) return empty_result(c, out);
-    TextTableH tt;
-    rc = prepare_text(c, d_buf, format, st, &tt);
-    if (rc != BSK_OK) return rc;
     const uint64_t N = c->table.n;
-    RmDupParams P;
-    memset(&P, 0, sizeof P);
-    P.fastq = fastq;
     P.by_seq = o.b("BySeq");
     P.by_name = o.b("ByName");
     P.ignore_case = o.b("IgnoreCase");
-    P.id_mode = id_mode_of(c);
-    P.line_width = fastq ? 0 : (int)o.ci("LineWidth");
-    P.buf_end = d_buf + n;
-    rc = grow(c, &c->d_keys, &c->keys_cap, N, N / 8 + 16);
-    if (rc != BSK_OK) return rc;
-    rc = ensure_record_scratch(c);
-    if (rc != BSK_OK) return rc;
     Arena A;
     const uint64_t o_has = A.take(N), o_masks = A.take(N * 8), o_ends = A.take((uint64_t)nfiles * 8);
     rc = arena_reserve(c, &A);
@@ -1008,20 +879,11 @@ int common_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, const uint64_t
     uint64_t* d_masks = A.at<uint64_t>(o_masks);
     uint64_t* d_ends = A.at<uint64_t>(o_ends);
     HIP_TRYX(c, hipMemcpyAsync(d_ends, file_ends, (size_t)nfiles * 8, hipMemcpyHostToDevice, st));
-    HIP_TRYX(c, launch_rmdup_hash(d_buf, n, c->table, tt, P, c->d_keys, nullptr, st));
-    HIP_TRYX(c, hipMemsetAsync(d_has, 0, N, st));
-    rc = group_resolve(c, d_buf, tt, P, d_has, st);
+    rc = group_by_key(c, d_buf, n, tt, P, d_has, st);
     if (rc != BSK_OK) return rc;
     HIP_TRYX(c, hipMemsetAsync(d_masks, 0, N * 8, st));
     HIP_TRYX(c, launch_common_masks(c->d_keys, c->table.start, N, d_ends, nfiles, d_masks, st));
-    uint64_t status = 0;
-    HIP_TRYX(c, hipMemcpyAsync(&status, c->d_status, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRYX(c, hipStreamSynchronize(st));  // (file_ends is the caller's memory)
-    if (status & ERR_HASH_COLLISION) {
-        c->set_error("libbsk: two distinct subjects share one 64-bit XXH64 key; refusing to guess (rerun on the CPU path)");
-        return BSK_ERR_UNSUPPORTED;
-    }
-    rc = kernel_error_to_status(c, status);
+    rc = group_status(c, st);  // (the synchronisation also ends the copy out of file_ends, the caller's memory)
     if (rc != BSK_OK) return rc;
     SeqParams F = format_params(c, fastq);
     F.text_w = tt.text_w; F.lin_off = tt.lin_off; F.lin = tt.lin;
@@ -1036,14 +898,7 @@ int common_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, const uint64_t
     out->len = 0;
     out->records = 0;
     if (total == 0) return BSK_OK;
-    rc = ensure_out(c, total);
-    if (rc != BSK_OK) return rc;
-    apply_long(c, &F);
-    { const int rce = emit_records(c, d_buf, n, F, total, kept, st); if (rce != BSK_OK) return rce; }
-    out->d_data = c->d_out;
-    out->len = total;
-    out->records = kept;
-    return BSK_OK;
+    return emit_result(c, d_buf, n, F, total, kept, st, out);
 }
 
 // ---------------------------------------------------------------------------
@@ -1053,26 +908,15 @@ int common_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, const uint64_t
 int concat_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, size_t n_first, int format, hipStream_t st, bsk_out* out) {
     const Options& o = c->opts;
     const bool fastq = format == BSK_FORMAT_FASTQ;
-    int rc = build_index(c, d_buf, n, format, st);
-    if (rc == BSK_OK) rc = check_u32_records(c, "concat");  // (group << 32 | index) keys, u32 permutations
+    TextTableH tt;
+    RmDupParams P;
+    int rc = group_index(c, d_buf, n, format, "concat", st, &tt, &P);
     if (rc != BSK_OK) return rc;
     if (c->table.n == 0) return empty_result(c, out);
-    TextTableH tt;
-    rc = prepare_text(c, d_buf, format, st, &tt);
-    if (rc != BSK_OK) return rc;
     const uint64_t N = c->table.n;
-    RmDupParams P;
-    memset(&P, 0, sizeof P);
-    P.fastq = fastq;
-    P.id_mode = id_mode_of(c);
-    P.line_width = fastq ? 0 : (int)o.ci("LineWidth");
-    P.buf_end = d_buf + n;
-    rc = grow(c, &c->d_keys, &c->keys_cap, N, N / 8 + 16);
-    if (rc != BSK_OK) return rc;
-    rc = ensure_record_scratch(c);
-    if (rc != BSK_OK) return rc;
     size_t tmp_bytes = 0;
-    if (group_sort_temp_bytes(N, &tmp_bytes) != hipSuccess) { c->set_error("libbsk: rocPRIM sort size query failed"); return BSK_ERR_HIP; }
+    rc = sort_query(c, group_sort_temp_bytes(N, &tmp_bytes));
+    if (rc != BSK_OK) return rc;
     Arena A;
     const uint64_t o_has = A.take(N), o_list = A.take(2 * N * 8), o_tmp = A.take(tmp_bytes ? tmp_bytes : 16),
                    o_seg = A.take(3 * N * 4), o_cnt = A.take(N * 4), o_cntoff = A.take((N + 1) * 8);
@@ -1083,21 +927,12 @@ int concat_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, size_t n_first
     uint32_t* d_seg = A.at<uint32_t>(o_seg);
     uint32_t* d_cnt = A.at<uint32_t>(o_cnt);
     uint64_t* d_cntoff = A.at<uint64_t>(o_cntoff);
-    HIP_TRYX(c, launch_rmdup_hash(d_buf, n, c->table, tt, P, c->d_keys, nullptr, st));
-    HIP_TRYX(c, hipMemsetAsync(d_has, 0, N, st));
-    rc = group_resolve(c, d_buf, tt, P, d_has, st);
+    rc = group_by_key(c, d_buf, n, tt, P, d_has, st);
     if (rc != BSK_OK) return rc;
     HIP_TRYX(c, hipMemsetAsync(c->d_counter, 0, 4 * sizeof(uint64_t), st));
     HIP_TRYX(c, launch_count_below(c->table.start, N, n_first, c->d_counter, st));
-    uint64_t first2 = 0, status = 0;
-    HIP_TRYX(c, hipMemcpyAsync(&first2, c->d_counter, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRYX(c, hipMemcpyAsync(&status, c->d_status, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRYX(c, hipStreamSynchronize(st));
-    if (status & ERR_HASH_COLLISION) {
-        c->set_error("libbsk: two distinct subjects share one 64-bit XXH64 key; refusing to guess (rerun on the CPU path)");
-        return BSK_ERR_UNSUPPORTED;
-    }
-    rc = kernel_error_to_status(c, status);
+    uint64_t first2 = 0, status = 0;  // first2: the first record of file 2, back with the status of the grouping
+    rc = group_status(c, st, c->d_counter, &first2);
     if (rc != BSK_OK) return rc;
     HIP_TRYX(c, launch_group_all(c->d_keys, N, d_list, st));
     HIP_TRYX(c, launch_group_sort(A.at<uint8_t>(o_tmp), tmp_bytes, d_list, d_list + N, N, st, N, /*index_ordered=*/true));
@@ -1129,32 +964,22 @@ int concat_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, size_t n_first
     if (rc != BSK_OK) return rc;
     const uint8_t* seg_done = nullptr;
     bool emit_old = true;
-    {
+    if (fastq && elements > 0 && segcopy_on(c, total)) {
         // FASTQ: the elements are slices of the shard -- the segmented copy writes them (ops_segcopy.hip, k_concat_segs)
-        const char* sg = c->tune.get("segcopy");
-        const bool force = sg && strcmp(sg, "force") == 0;
-        if (fastq && elements > 0 && !(sg && strcmp(sg, "off") == 0) && (force || total >= (4u << 20))) {
-            const uint64_t ns = 5 * elements;
-            rc = grow(c, &c->d_seg_src, &c->seg_src_cap, 2 * ns + 2 + (N + 7) / 8 + 1, ns / 4 + 16);
-            if (rc != BSK_OK) return rc;
-            rc = grow(c, &c->d_seg_first, &c->seg_first_cap, seg_tiles(total) + 1, 64);
-            if (rc != BSK_OK) return rc;
-            uint64_t* seg_src = c->d_seg_src;
-            uint64_t* seg_off2 = c->d_seg_src + ns;  // [ns + 1]
-            uint64_t* d_other = c->d_seg_src + 2 * ns + 1;
-            uint8_t* d_done = reinterpret_cast<uint8_t*>(c->d_seg_src + 2 * ns + 2);
-            HIP_TRYX(c, hipMemsetAsync(d_other, 0, sizeof(uint64_t), st));
-            HIP_TRYX(c, hipMemcpyAsync(seg_off2 + ns, &total, sizeof total, hipMemcpyHostToDevice, st));
-            HIP_TRYX(c, launch_concat_segs(d_buf, n, c->table, Q, d_list + N, d_seg, c->d_out_len, c->d_out_off, d_cntoff, seg_src,
-                                           seg_off2, d_done, d_other, st));
-            HIP_TRYX(c, launch_seg_first(seg_off2, ns, c->d_seg_first, st));
-            HIP_TRYX(c, launch_seg_copy(seg_src, seg_off2, ns, c->d_seg_first, c->d_out, total, d_buf, d_buf + n, st));
-            uint64_t other = 0;
-            HIP_TRYX(c, hipMemcpyAsync(&other, d_other, sizeof other, hipMemcpyDeviceToHost, st));
-            HIP_TRYX(c, hipStreamSynchronize(st));
-            seg_done = d_done;
-            emit_old = other != 0;
-        }
+        const uint64_t ns = 5 * elements;
+        rc = seg_begin(c, 2 * ns + 1 + (N + 7) / 8, total, st);  // sources [ns], offsets [ns + 1], one "done" byte per record
+        if (rc != BSK_OK) return rc;
+        uint64_t* seg_src = c->d_seg_src;
+        uint64_t* seg_off2 = c->d_seg_src + ns;
+        uint8_t* d_done = reinterpret_cast<uint8_t*>(c->d_seg_src + 2 * ns + 1);
+        HIP_TRYX(c, hipMemcpyAsync(seg_off2 + ns, &total, sizeof total, hipMemcpyHostToDevice, st));
+        HIP_TRYX(c, launch_concat_segs(d_buf, n, c->table, Q, d_list + N, d_seg, c->d_out_len, c->d_out_off, d_cntoff, seg_src,
+                                       seg_off2, d_done, seg_other(c), st));
+        uint64_t other = 0;
+        rc = seg_run(c, SegList{seg_src, seg_off2, ns, total}, c->d_out, d_buf, n, st, &other);
+        if (rc != BSK_OK) return rc;
+        seg_done = d_done;
+        emit_old = other != 0;
     }
     if (emit_old)
         HIP_TRYX(c, launch_concat_emit(d_buf, c->table, tt, Q, d_list + N, d_seg, c->d_out_len, c->d_out_off, c->d_out,
@@ -1211,17 +1036,7 @@ int faidx_query_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int forma
         HIP_TRYX(c, launch_grep_match(d_buf, n, c->table, &tt, G, d_hits, st));
         HIP_TRYX(c, launch_seq_size(d_buf, c->table, P, c->d_out_len, c->d_status, st));
         HIP_TRYX(c, launch_mask_u32(c->d_out_len, d_hits, N, st));
-        uint64_t total = 0, kept = 0;
-        rc = finish_sizes(c, st, &total, &kept);
-        if (rc != BSK_OK) return rc;
-        rc = ensure_out(c, total);
-        if (rc != BSK_OK) return rc;
-        apply_long(c, &P);
-        { const int rce = emit_records(c, d_buf, n, P, total, kept, st); if (rce != BSK_OK) return rce; }
-        out->d_data = c->d_out;
-        out->len = total;
-        out->records = kept;
-        return BSK_OK;
+        return emit_sized(c, d_buf, n, P, st, out);
     }
     rc = bind_features(c, d_buf, n, format, st, &P);
     if (rc != BSK_OK) return rc;
@@ -1234,17 +1049,7 @@ int faidx_query_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int forma
     rc = ensure_record_scratch(c);
     if (rc != BSK_OK) return rc;
     HIP_TRYX(c, launch_seq_size(d_buf, c->table, P, c->d_out_len, c->d_status, st));
-    uint64_t total = 0, kept = 0;
-    rc = finish_sizes(c, st, &total, &kept);
-    if (rc != BSK_OK) return rc;
-    rc = ensure_out(c, total);
-    if (rc != BSK_OK) return rc;
-    apply_long(c, &P);
-    { const int rce = emit_records(c, d_buf, n, P, total, kept, st); if (rce != BSK_OK) return rce; }
-    out->d_data = c->d_out;
-    out->len = total;
-    out->records = kept;
-    return BSK_OK;
+    return emit_sized(c, d_buf, n, P, st, out);
 }
 
 }  // namespace bsk

@@ -318,8 +318,8 @@ int replace_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, h
     if (rc != BSK_OK) return rc;
     rc = ensure_record_scratch(c);
     if (rc != BSK_OK) return rc;
-    uint64_t total = 0, kept = 0;
     if (o.b("BySeq")) {
+        uint64_t total = 0, kept = 0;
         {
             Timed t(c, "k_repl_seq_size", st);
             HIP_TRYX(c, launch_repl_seq(S.ncap, false, d_buf, c->table, tt.text_w, tt.lin_off, tt.lin, R, c->d_out_len, nullptr, nullptr, st));
@@ -334,6 +334,9 @@ int replace_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, h
             Timed t(c, "k_repl_seq_write", st);
             HIP_TRYX(c, launch_repl_seq(S.ncap, true, d_buf, c->table, tt.text_w, tt.lin_off, tt.lin, R, c->d_out_len, c->d_out_off, c->d_out, st));
         }
+        out->d_data = c->d_out;
+        out->len = total;
+        out->records = kept;
     } else {
         Arena A;
         const uint64_t o_len = A.take(N * 4), o_off = A.take((N + 1) * 8);
@@ -362,18 +365,10 @@ int replace_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, h
         P.text_w = tt.text_w; P.lin_off = tt.lin_off; P.lin = tt.lin;
         P.rep_len = d_len; P.rep_off = d_off; P.rep_stage = S.d_stage;
         HIP_TRYX(c, launch_seq_size(d_buf, c->table, P, c->d_out_len, c->d_status, st));
-        rc = finish_sizes(c, st, &total, &kept);
-        if (rc != BSK_OK) return rc;
-        rc = ensure_out(c, total);
-        if (rc != BSK_OK) return rc;
-        apply_long(c, &P);
-        rc = emit_records(c, d_buf, n, P, total, kept, st);
+        rc = emit_sized(c, d_buf, n, P, st, out);
         if (rc != BSK_OK) return rc;
     }
     c->nr_base += N;
-    out->d_data = c->d_out;
-    out->len = total;
-    out->records = kept;
     return BSK_OK;
 }
 

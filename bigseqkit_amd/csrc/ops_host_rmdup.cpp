@@ -266,7 +266,7 @@ int rmdup_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hip
             rc = with_k2 ? rmdup_settle_overflow(c, d_first, st, c->h_ctl[3]) : BSK_OK;  // (k1 alone: no list, the bytes tell)
             if (rc == BSK_ERR_FILTER_FALLBACK) by_buckets = false;  // (the list did not fit: the table path compares bytes)
             else if (rc != BSK_OK) return rc;
-            else if (verify_bytes && !c->tune.is("segcopy", "off") && !c->tune.is("rmdup_place", "off")) {
+            else if (verify_bytes && segcopy_on(c) && !c->tune.is("rmdup_place", "off")) {
                 // round 5: the comparison, the output offsets and the segment list of the copy in ONE pass over the table
                 // (k_rmdup_place: decoupled look-back) instead of verify + three scan launches + segment build + first-of-tile
                 rc = grow(c, &c->d_seg_src, &c->seg_src_cap, N + 1, N / 8 + 16);

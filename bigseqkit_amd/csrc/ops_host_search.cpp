@@ -697,24 +697,12 @@ int grep_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipS
     out->records = 0;
     if (total == 0) return BSK_OK;
     SeqParams P = format_params(c, fastq);
-    if (fastq) {
-        const int rs = try_records_as_slices(c, d_buf, n, P, total, kept, st, out);
-        if (rs < 0) return -rs;
-        if (rs == 1) return BSK_OK;
-    }
-    rc = ensure_out(c, total);
-    if (rc != BSK_OK) return rc;
     if (!fastq && tt.text_w == c->d_text_w) {  // the search ran on linear copies: the emit reads the wrapped text in place
         rc = prepare_text(c, d_buf, format, st, &tt, false, /*keep_out_len=*/true);
         if (rc != BSK_OK) return rc;
     }
     P.text_w = tt.text_w; P.lin_off = tt.lin_off; P.lin = tt.lin;
-    apply_long(c, &P);
-    { const int rce = emit_records(c, d_buf, n, P, total, kept, st); if (rce != BSK_OK) return rce; }
-    out->d_data = c->d_out;
-    out->len = total;
-    out->records = kept;
-    return BSK_OK;
+    return emit_result(c, d_buf, n, P, total, kept, st, out, /*allow_slices=*/fastq);
 }
 
 // ---------------------------------------------------------------------------

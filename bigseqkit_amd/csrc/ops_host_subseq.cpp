@@ -378,17 +378,7 @@ int subseq_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hi
     rc = ensure_record_scratch(c);
     if (rc != BSK_OK) return rc;
     HIP_TRYX(c, launch_seq_size(d_buf, c->table, P, c->d_out_len, c->d_status, st));
-    uint64_t total = 0, kept = 0;
-    rc = finish_sizes(c, st, &total, &kept);
-    if (rc != BSK_OK) return rc;
-    rc = ensure_out(c, total);
-    if (rc != BSK_OK) return rc;
-    apply_long(c, &P);
-    { const int rce = emit_records(c, d_buf, n, P, total, kept, st); if (rce != BSK_OK) return rce; }
-    out->d_data = c->d_out;
-    out->len = total;
-    out->records = kept;
-    return BSK_OK;
+    return emit_sized(c, d_buf, n, P, st, out);
 }
 
 
