@@ -202,6 +202,74 @@ __device__ __forceinline__ uint4 load16_tile(const uint8_t* __restrict__ buf, ui
     else return load16(buf, n, idx);
 }
 
+// ---------------------------------------------------------------------------
+// The tile grid of a range and the loads of one tile (stream_range).
+//   * The grid begins on a 128-byte line of MEMORY (by absolute address, whatever the alignment of `buf`): a tile that
+//     ends inside a line makes the wave fetch that line again one tile later, and a non-temporal line has left L2 by then.
+//     Range starts are record starts -- any residue mod 128 -- so a grid on `rs & ~15` did that seven times out of eight.
+//     Where the line of `rs` begins in front of `buf` (a view that is not line-aligned, rs < 128) the grid keeps `rs & ~15`:
+//     no byte in front of the caller's pointer is ever read.  The bytes between the grid's start and `rs` (up to 127) are
+//     masked by the edge rules of the first tile, as the up to 15 of the old grid were.
+//   * A tile wholly inside [rs, re) and [0, n) -- all but the first and the last of a range -- is loaded from a scalar
+//     base with one 32-bit lane offset and no bounds test; the first and the last keep load16's per-lane test, and skip
+//     (wave-uniform) every 1 KiB piece that lies wholly outside [rs, re): its registers read as zero, which is what the
+//     edge masks make of those bytes anyway.
+// ---------------------------------------------------------------------------
+constexpr uint64_t LINE_BYTES = 128;
+// load16 for the first and the last tile of a range.  Only the last 16-byte pieces of a shard take the byte loop, and it
+// stays a LOOP: unrolled sixteen times in every copy of the tile loads, its sixteen 64-bit lane offsets were hoisted out
+// of the tile loop and spilled.
+template <bool NT>
+__device__ __forceinline__ uint4 load16_edge(const uint8_t* __restrict__ buf, uint64_t n, uint64_t idx) {
+    if (idx + 16 <= n) {
+        typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+        const u32x4_t* q = reinterpret_cast<const u32x4_t*>(buf + idx);
+        const u32x4_t v = NT ? __builtin_nontemporal_load(q) : *q;
+        return make_uint4(v.x, v.y, v.z, v.w);
+    }
+    uint4 w = make_uint4(0, 0, 0, 0);
+    const uint32_t left = idx < n ? (uint32_t)(n - idx) : 0u;
+#pragma nounroll
+    for (uint32_t b = 0; b < left; ++b) {
+        const uint32_t c = (uint32_t)buf[idx + b] << ((b & 3u) * 8u), d = b >> 2;
+        w.x |= d == 0u ? c : 0u;
+        w.y |= d == 1u ? c : 0u;
+        w.z |= d == 2u ? c : 0u;
+        w.w |= d == 3u ? c : 0u;
+    }
+    return w;
+}
+__device__ __forceinline__ uint64_t tile_grid_start(const uint8_t* __restrict__ buf, uint64_t rs) {
+    const uint64_t in_line = (uint64_t)(uintptr_t)(buf + rs) & (LINE_BYTES - 1);  // bytes of rs's line in front of rs
+    return in_line <= rs ? rs - in_line : rs & ~(uint64_t)15;
+}
+template <bool NT>
+__device__ __forceinline__ void load_tile(uint4 (&dst)[NPIECE], const uint8_t* __restrict__ buf, uint64_t n, uint64_t rs,
+                                          uint64_t re, uint64_t tile_idx) {
+    const uint32_t lane16 = (threadIdx.x & 63u) * 16u;
+    if (tile_idx >= rs && tile_idx + TILE <= re && tile_idx + TILE <= n) {  // (wave-uniform) an interior tile
+        const uint8_t* __restrict__ base = buf + tile_idx;
+#pragma unroll
+        for (int p = 0; p < NPIECE; ++p) {
+            typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+            const u32x4_t* q = reinterpret_cast<const u32x4_t*>(base + (lane16 + (uint32_t)(p * PIECE_BYTES)));
+            const u32x4_t v = NT ? __builtin_nontemporal_load(q) : *q;
+            dst[p] = make_uint4(v.x, v.y, v.z, v.w);
+        }
+    } else {
+        // (the lane offset behind an empty asm: taken as invariant, the per-lane addresses of these pieces -- 64 bits each, for
+        // every copy of the tile loads -- were computed in front of the range loop and spilled)
+        uint32_t edge16 = lane16;
+        asm volatile("" : "+v"(edge16));
+#pragma unroll
+        for (int p = 0; p < NPIECE; ++p) {
+            const uint64_t piece_idx = tile_idx + (uint64_t)(p * PIECE_BYTES);
+            if (piece_idx < re && piece_idx + PIECE_BYTES > rs) dst[p] = load16_edge<NT>(buf, n, piece_idx + edge16);
+            else dst[p] = make_uint4(0, 0, 0, 0);
+        }
+    }
+}
+
 struct Piece {  // what a lane keeps of one 16-byte piece (dense path; packed flags, see pack_flags)
     uint32_t m_nl_a;  // newlines in the low nibbles, a in the high nibbles   (a = q>=20 for FASTQ, gap for FASTA)
     uint32_t m_b_c;   // b in the low nibbles, c in the high nibbles          (b = q>=30, c = gap; FASTQ -a only)
@@ -426,23 +494,18 @@ __device__ __forceinline__ uint32_t stream_range(Lds<FASTQ, ALL, CV>& L, const u
     uint32_t run_a = 0, run_b = 0, run_c = 0;  // running counters (mod 2^32)
     uint32_t quiet_tiles = 0;                  // consecutive tiles without a newline
 
-    const uint64_t idx0 = rs & ~(uint64_t)15;
+    const uint64_t idx0 = tile_grid_start(buf, rs);  // (on a 128-byte line of memory: up to 127 bytes in front of rs)
     const uint64_t ntiles = (re - idx0 + TILE - 1) / TILE;
 
     constexpr bool TILE_NT = sink_tile_nt<Sink>::value && FASTQ && !ALL;
     uint4 cur[NPIECE], nxt[NPIECE];
-#pragma unroll
-    for (int p = 0; p < NPIECE; ++p) cur[p] = load16_tile<TILE_NT>(buf, n, idx0 + (uint64_t)p * PIECE_BYTES + (uint64_t)lane * 16);
+    load_tile<TILE_NT>(cur, buf, n, rs, re, idx0);
 
     for (uint64_t t = 0; t < ntiles; ++t) {
         const uint64_t tile_idx = idx0 + t * TILE;
         const uint32_t tile_rel = (uint32_t)(tile_idx - rs);
         // prefetch the next tile while this one is processed
-        if (BSK_PREFETCH && t + 1 < ntiles) {
-#pragma unroll
-            for (int p = 0; p < NPIECE; ++p)
-                nxt[p] = load16_tile<TILE_NT>(buf, n, tile_idx + TILE + (uint64_t)p * PIECE_BYTES + (uint64_t)lane * 16);
-        }
+        if (BSK_PREFETCH && t + 1 < ntiles) load_tile<TILE_NT>(nxt, buf, n, rs, re, tile_idx + TILE);
         const bool edge = (tile_idx < rs) || (tile_idx + TILE > re);  // wave-uniform
 
         // sinks that look at the raw text of a tile (the fused pattern filter, stream_filter.hip) see it here, while
@@ -744,8 +807,15 @@ __device__ __forceinline__ uint32_t stream_range(Lds<FASTQ, ALL, CV>& L, const u
                         mc = g;
                     } else {
                         // (pieces of the chunks that a long line covers are counted by those chunks' ranges)
+                        // (byte by byte where a piece straddles an end of [skip_from, count_resume): the tile grid lies on
+                        // lines of memory, those two on multiples of the nominal chunk from the start of the shard)
                         const uint64_t I = tile_idx + (uint64_t)p * PIECE_BYTES + (uint64_t)lane * 16;
-                        ma = (I >= skip_from && I < count_resume) ? 0u : g;
+                        ma = g;
+                        if (I + 16 > skip_from && I < count_resume) {
+                            const uint32_t xl = I >= skip_from ? 0u : (uint32_t)(skip_from - I);
+                            const uint32_t xh = count_resume - I >= 16u ? 16u : (uint32_t)(count_resume - I);
+                            ma = (xl == 0u && xh == 16u) ? 0u : (xh > xl ? g & ~packed_from_mask16(((1u << xh) - 1u) & ~((1u << xl) - 1u)) : g);
+                        }
                     }
                 }
                 if (edge) {
@@ -870,15 +940,16 @@ __device__ __forceinline__ uint32_t stream_range(Lds<FASTQ, ALL, CV>& L, const u
                     t = tgt - 1;
                     quiet_tiles = 0;
                     const uint64_t tgt_idx = idx0 + tgt * TILE;
-#pragma unroll
-                    for (int p = 0; p < NPIECE; ++p) cur[p] = load16_tile<TILE_NT>(buf, n, tgt_idx + (uint64_t)p * PIECE_BYTES + (uint64_t)lane * 16);
+                    load_tile<TILE_NT>(cur, buf, n, rs, re, tgt_idx);
                     continue;
                 }
             }
+            if constexpr (BSK_PREFETCH) {
 #pragma unroll
-            for (int p = 0; p < NPIECE; ++p)
-                cur[p] = BSK_PREFETCH ? nxt[p]
-                                      : load16_tile<TILE_NT>(buf, n, tile_idx + TILE + (uint64_t)p * PIECE_BYTES + (uint64_t)lane * 16);
+                for (int p = 0; p < NPIECE; ++p) cur[p] = nxt[p];
+            } else {
+                load_tile<TILE_NT>(cur, buf, n, rs, re, tile_idx + TILE);
+            }
         }
     }
 
