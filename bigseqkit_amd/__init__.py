@@ -8,7 +8,7 @@ from ._lib import BskError, FORMAT_FASTA, FORMAT_FASTQ, lib  # noqa: F401  (fail
 from .options import (SeqKitConfig, SeqKitStatsOptions, SeqKitSeqOptions, SeqKitGrepOptions,  # noqa: F401
                       SeqKitLocateOptions, SeqKitSubseqOptions, SeqKitTranslateOptions, SeqKitRmDupOptions,
                       SeqKitFq2FaOptions, SeqKitRangeOptions, SeqKitHeadOptions, SeqKitDuplicateOptions, SeqKitRenameOptions, SeqKitSortOptions, SeqKitFaidxOptions, SeqKitPairOptions, SeqKitCommonOptions, SeqKitConcatOptions, SeqKitReplaceOptions, SeqKitFa2FqOptions, SeqKitSampleOptions,
-                      SeqKitShuffleOptions)
+                      SeqKitShuffleOptions, SeqKitHeadGenomeOptions)
 from .api import (SeqFrame, ReadFASTA, ReadFASTAN, ReadFASTQ, ReadFASTQN, Operator, Stats, StatsString,  # noqa: F401
                   stats_map, Seq, build_index, Grep, GrepCount, Subseq, Translate, RmDup, Locate, Fq2Fa, Range, Head,
-                  Duplicate, Count, Rename, Sort, Faidx, Pair, Common, Concat, FaidxQuery, Replace, Fa2Fq, Sample, Shuffle)
+                  Duplicate, Count, Rename, Sort, Faidx, Pair, Common, Concat, FaidxQuery, Replace, Fa2Fq, Sample, Shuffle, HeadGenome)

@@ -138,6 +138,9 @@ SIGNATURES = {
     "bsk_sample_set_count": (_i, [_vp, C.c_uint64]),
     "bsk_sample_set_first_record": (_i, [_vp, C.c_uint64]),
     "bsk_shuffle_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, _vp, _p(Out)]),
+    "bsk_head_genome_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, _vp, _p(Out)]),
+    "bsk_head_genome_reset": (_i, [_vp]),
+    "bsk_head_genome_state": (_i, [_vp, _p(C.c_int), _p(C.c_uint64)]),
     "bsk_range_needs_count": (_i, [_vp, _p(C.c_int)]),
     "bsk_range_set_count": (_i, [_vp, C.c_uint64]),
     "bsk_range_bounds": (_i, [_vp, _p(_i64), _p(_i64)]),

@@ -10,7 +10,7 @@ import os
 
 from . import _lib
 from ._lib import lib, check, BskError, FORMAT_FASTA, FORMAT_FASTQ
-from .options import SeqKitStatsOptions, SeqKitSeqOptions, SeqKitGrepOptions, SeqKitSubseqOptions, SeqKitTranslateOptions, SeqKitRmDupOptions, SeqKitLocateOptions, SeqKitFq2FaOptions, SeqKitHeadOptions, SeqKitDuplicateOptions, SeqKitRenameOptions, SeqKitSortOptions, SeqKitFaidxOptions, SeqKitPairOptions, SeqKitCommonOptions, SeqKitConcatOptions, SeqKitReplaceOptions, SeqKitFa2FqOptions, SeqKitSampleOptions, SeqKitShuffleOptions
+from .options import SeqKitStatsOptions, SeqKitSeqOptions, SeqKitGrepOptions, SeqKitSubseqOptions, SeqKitTranslateOptions, SeqKitRmDupOptions, SeqKitLocateOptions, SeqKitFq2FaOptions, SeqKitHeadOptions, SeqKitDuplicateOptions, SeqKitRenameOptions, SeqKitSortOptions, SeqKitFaidxOptions, SeqKitPairOptions, SeqKitCommonOptions, SeqKitConcatOptions, SeqKitReplaceOptions, SeqKitFa2FqOptions, SeqKitSampleOptions, SeqKitShuffleOptions, SeqKitHeadGenomeOptions
 
 
 class SeqFrame:
@@ -434,6 +434,25 @@ def Sample(input, o, device=0):
 def Shuffle(input, o=None, device=0):
     """bigseqkit/shuffle.go:33-46 (PARITY SHUF): the records in ascending order of their draws; global, several shards are joined"""
     return _run_records("Shuffle", lib.bsk_shuffle_run, _one_shard(input), o or SeqKitShuffleOptions(), device)[0]
+
+
+def HeadGenome(input, o=None, device=0):
+    """bigseqkit/head_genome.go:37-77 (PARITY HEADG): the records of the first genome.  ONE cut over the whole input: the
+    shards go through one context in order, which carries the prefix words, n_1 and "cut reached" from shard to shard, and
+    nothing is launched for the shards behind the cut."""
+    chunks = []
+    with Operator("HeadGenome", (o or SeqKitHeadGenomeOptions()).to_json(), device) as op:
+        for pid, ptr, n, on_dev, keep in input.partitions():
+            out = _lib.Out()
+            check(lib.bsk_head_genome_run(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, None, C.byref(out)), op.ctx)
+            buf = C.create_string_buffer(max(1, out.len))
+            check(lib.bsk_out_to_host(op.ctx, C.byref(out), buf, out.len), op.ctx)
+            chunks.append(buf.raw[:out.len])
+            cut = C.c_int()
+            check(lib.bsk_head_genome_state(op.ctx, C.byref(cut), None), op.ctx)
+            if cut.value:
+                break
+    return b"".join(chunks)
 
 
 def build_index(input, device=0):

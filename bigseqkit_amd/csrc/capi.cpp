@@ -149,6 +149,7 @@ RecordOp record_op(const bsk_ctx* c) {
         case Op::Range: case Op::Head: return {records_run_device, RecordOp::NoStore};
         case Op::Sample: return {records_run_device, RecordOp::Chunks};  // the context carries the running record index
         case Op::Shuffle: return {records_run_device, RecordOp::Whole};
+        case Op::HeadGenome: return {head_genome_run_device, RecordOp::Chunks};  // the context carries prefix, n_1 and "cut reached"
         case Op::Faidx: return {faidx_run_device, RecordOp::NoStore};
         default: return {};  // stats; pair / common / concat read several texts
     }
@@ -283,6 +284,7 @@ int bsk_create(const char* op_name_, const char* opts_json, int device, bsk_ctx*
     c->op = op;
     c->device = device;
     c->tune.load_env();  // the environment's switches become this context's defaults, once
+    if (const char* w = getenv("BSK_HG_WINDOW")) c->tune.v["head_genome_window"] = w;  // (the short spelling of BSK_HEAD_GENOME_WINDOW)
     try {
         c->opts = Options::from_json(op, opts_json && *opts_json ? opts_json : "{}");
         c->opts_json = c->opts.to_json();
@@ -301,6 +303,7 @@ int bsk_create(const char* op_name_, const char* opts_json, int device, bsk_ctx*
             case Op::Replace: validate_replace_opts(c); break;
             case Op::Fa2Fq: validate_fa2fq_opts(c); break;
             case Op::Sample: case Op::Shuffle: validate_sample_opts(c); break;
+            case Op::HeadGenome: validate_head_genome_opts(c); break;
             default: break;  // validated by the op's own module once it is built
         }
     } catch (const std::exception& e) {
@@ -372,6 +375,8 @@ void bsk_destroy(bsk_ctx* c) {
         if (c->d_id_prog) hipFree(c->d_id_prog);
         bsk::replace_free(c);
         bsk::fa2fq_free(c);
+        for (void* p : {(void*)c->d_hg_words, (void*)c->d_hg_off, (void*)c->d_hg_counts, (void*)c->d_hg_res})
+            if (p) hipFree(p);
         if (c->d_vm_progs) hipFree(c->d_vm_progs);
         if (c->d_id_off) hipFree(c->d_id_off);
         if (c->d_id_len) hipFree(c->d_id_len);
@@ -1196,6 +1201,26 @@ int bsk_shuffle_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int 
     return run_record_op(c, Op::Shuffle, shard, n, on_device, format, stream, out);
 }
 
+int bsk_head_genome_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,
+                        bsk_out* out) {
+    return run_record_op(c, Op::HeadGenome, shard, n, on_device, format, stream, out);
+}
+
+int bsk_head_genome_reset(bsk_ctx* c) {
+    if (!c || c->op != Op::HeadGenome) return BSK_ERR_INVALID_ARG;
+    bsk_call_scope scope__(c);  // (no device needed: a context made for its options alone takes it too)
+    if (!scope__.owns) return fail_busy();
+    head_genome_reset(c);
+    return BSK_OK;
+}
+
+int bsk_head_genome_state(const bsk_ctx* c, int* cut_reached, uint64_t* records) {
+    if (!c || c->op != Op::HeadGenome) return BSK_ERR_INVALID_ARG;
+    if (cut_reached) *cut_reached = c->hg.cut ? 1 : 0;
+    if (records) *records = c->hg.records;
+    return BSK_OK;
+}
+
 int bsk_duplicate_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,
                       bsk_out* out) {
     return run_record_op(c, Op::Duplicate, shard, n, on_device, format, stream, out);
@@ -1467,6 +1492,11 @@ int bsk_profile_dump(bsk_ctx* c, char* buf, size_t cap) {
         snprintf(num, sizeof num, "translate_stream_fallback=0.000000/%llu;", (unsigned long long)c->translate_stream_fallbacks);
         out += num;
     }
+    if (c->hg_indexed_bytes) {  // (not a stage: the bytes head-genome's window index passes read -- its cost follows the first genome)
+        char num[96];
+        snprintf(num, sizeof num, "hg_indexed_bytes=0.000000/%llu;", (unsigned long long)c->hg_indexed_bytes);
+        out += num;
+    }
     if (out.size() + 1 > cap) { c->set_error("libbsk: bsk_profile_dump: buffer too small"); return BSK_ERR_CAPACITY; }
     memcpy(buf, out.c_str(), out.size() + 1);
     return BSK_OK;
@@ -1478,6 +1508,7 @@ int bsk_profile_reset(bsk_ctx* c) {
     uint64_t l;
     bsk_profile_read(c, "", &d, &l);
     c->prof.clear();
+    c->hg_indexed_bytes = 0;
     return BSK_OK;
 }
 

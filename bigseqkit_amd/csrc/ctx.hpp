@@ -27,7 +27,7 @@
 // of per process.  Names (lower case, without the BSK_ prefix) and meanings: INTEGRATION.md "Switches".
 struct bsk_tuning {
     static const char* const* names() {
-        static const char* const N[] = {"filter", "grep_shiftand", "index", "locate_nopre", "long_bytes", "min_range_bytes", "names",
+        static const char* const N[] = {"filter", "grep_shiftand", "head_genome_window", "index", "locate_nopre", "long_bytes", "min_range_bytes", "names",
                                         "names_scale", "out", "pin_alphabet", "ranges_per_wave", "replace", "rmdup", "rmdup_buckets", "rmdup_hash", "rmdup_k1_bits", "rmdup_k2_bits", "rmdup_keys", "rmdup_place", "rmdup_xcheck", "rmdup_xlocal", "scan", "segcopy",
                                         "sort", "stage_bytes", "stats_a", "stats_fasta", "stats_prep", "stats_tail", "subseq", "subseq_scale", "text", "translate", "translate_index", "translate_probe", "translate_stream", "tr_lanes", nullptr};
         return N;
@@ -151,6 +151,24 @@ struct bsk_ctx {
     uint64_t sample_next = 0, sample_first = 0;
     uint64_t sample_threshold = 0;     // ceil(fraction * 2^53) (after bsk_sample_set_count when -n asks for it)
     bool sample_needs_count = false, sample_resolved = false;
+    // head-genome (ops_host_headgenome.cpp; PARITY.md HEADG): ONE cut over the whole input, so what the loop of
+    // head_genome.go:53-108 carries from record to record lives here across the shards of a call sequence, the chunks of
+    // bsk_run_to_store and the streamed pieces of the command line -- the prefix words (of the first record of the input),
+    // n_1 (the shared-word count of the first COMPARED record; < 0: none compared yet), "cut reached" and the number of
+    // records kept so far.  bsk_head_genome_reset puts it back for the next file.
+    struct HeadGenomeState {
+        bool have_prefix = false, uploaded = false, cut = false;
+        std::string words;               // the prefix words back to back
+        std::vector<uint32_t> off{0};    // word k = words[off[k], off[k + 1])
+        int64_t n1 = -1;
+        uint64_t records = 0;
+    } hg;
+    uint8_t* d_hg_words = nullptr;
+    uint32_t* d_hg_off = nullptr;
+    uint32_t* d_hg_counts = nullptr;     // n_i of the records of the running window
+    uint64_t* d_hg_res = nullptr;        // what a window reports (ops_headgenome.hpp HG_*)
+    uint64_t hg_words_cap = 0, hg_off_cap = 0, hg_counts_cap = 0;
+    uint64_t hg_indexed_bytes = 0;       // bytes the window index passes read since bsk_profile_reset (bsk_profile_dump)
     uint64_t avg_record_bytes = 0;   // bytes per record in the head of the last indexed shard (0: unknown)
     bsk::RecordTable sparse;         // one-pass index: per-range slices, compacted into `table`
     uint64_t* d_range_count = nullptr;  // [cap_ranges]

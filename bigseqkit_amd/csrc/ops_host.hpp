@@ -68,6 +68,9 @@ void validate_records_opts(bsk_ctx* c);
 int range_resolve(bsk_ctx* c, int64_t n_records);
 void validate_sample_opts(bsk_ctx* c);
 int sample_resolve(bsk_ctx* c, uint64_t n_records);
+void validate_head_genome_opts(bsk_ctx* c);
+void head_genome_reset(bsk_ctx* c);
+int head_genome_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, bsk_out* out);
 int fq2fa_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, bsk_out* out);
 int records_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, bsk_out* out);
 int rename_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, bsk_out* out);

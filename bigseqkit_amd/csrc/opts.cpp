@@ -76,7 +76,8 @@ Options Options::defaults(Op op) {
             break;
         case Op::Fa2Fq: o.fields = {fs("FastaFile", ""), fb("OnlyPositiveStrand", false)}; break;   // bigseqkit/fa2fq.go:17-23
         case Op::Sample: o.fields = {fi("Seed", 11), fi("Number", 0), ff("Proportion", 0)}; break;   // bigseqkit/sample.go:19-26
-        case Op::Shuffle: o.fields = {fi("Seed", 23)}; break;                                         // bigseqkit/shuffle.go:16-21
+        case Op::Shuffle: o.fields = {fi("Seed", 23)}; break;
+        case Op::HeadGenome: o.fields = {fi("MiniCommonWords", 1)}; break;                            // bigseqkit/head_genome.go:14-24                                         // bigseqkit/shuffle.go:16-21
         case Op::Common:  // bigseqkit/common.go:21-29
             o.fields = {fb("ByName", false), fb("BySeq", false), fb("IgnoreCase", false), fb("OnlyPositiveStrand", false)};
             break;
@@ -232,7 +233,8 @@ bool op_from_name(const std::string& name, Op* out) {
         {"Sort", Op::Sort}, {"Faidx", Op::Faidx}, {"Pair", Op::Pair},
         {"PairPrepare", Op::Pair}, {"Common", Op::Common}, {"CommonPrepare", Op::Common},
         {"Concat", Op::Concat}, {"ConcatPrepare", Op::Concat}, {"Replace", Op::Replace},
-        {"Fa2Fq", Op::Fa2Fq}, {"Sample", Op::Sample}, {"Shuffle", Op::Shuffle}};
+        {"Fa2Fq", Op::Fa2Fq}, {"Sample", Op::Sample}, {"Shuffle", Op::Shuffle},
+        {"HeadGenome", Op::HeadGenome}};
     for (auto& t : tbl)
         if (name == t.n) { *out = t.op; return true; }
     return false;
@@ -261,6 +263,7 @@ const char* op_name(Op op) {
         case Op::Fa2Fq: return "Fa2Fq";
         case Op::Sample: return "Sample";
         case Op::Shuffle: return "Shuffle";
+        case Op::HeadGenome: return "HeadGenome";
     }
     return "";
 }

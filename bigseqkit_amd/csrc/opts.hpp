@@ -11,6 +11,7 @@
 //   Fq2FaOptions      bigseqkit/fq2fa.go:11-18;  RangeOptions bigseqkit/range.go:14-24;  HeadOptions bigseqkit/head.go:12-22;
 //   DuplicateOptions  bigseqkit/duplicate.go:9-19;  ReplaceOptions bigseqkit/replace.go:9-37;
 //   Fa2FqOptions      bigseqkit/fa2fq.go:11-23;  SampleOptions bigseqkit/sample.go:12-26;  ShuffleOptions bigseqkit/shuffle.go:11-21
+//   HeadGenomeOptions bigseqkit/head_genome.go:14-24
 #pragma once
 #include <cstdint>
 #include <stdexcept>
@@ -36,7 +37,7 @@ struct Field {
     std::vector<std::string> sl;
 };
 
-enum class Op { Stats, Seq, Grep, Locate, Subseq, Translate, RmDup, Fq2Fa, Range, Head, Duplicate, Rename, Sort, Faidx, Pair, Common, Concat, Replace, Fa2Fq, Sample, Shuffle };
+enum class Op { Stats, Seq, Grep, Locate, Subseq, Translate, RmDup, Fq2Fa, Range, Head, Duplicate, Rename, Sort, Faidx, Pair, Common, Concat, Replace, Fa2Fq, Sample, Shuffle, HeadGenome };
 
 class Options {
    public:

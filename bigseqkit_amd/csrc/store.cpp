@@ -372,6 +372,8 @@ int bsk_run_to_store(bsk_ctx* c, const void* host_shard, size_t n, int format, i
     if (!c->tune.is("pin_alphabet", "1")) c->nr_base = 0;
     // sample: the record index goes on across the chunks likewise, from bsk_sample_set_first_record's value (0 by default)
     if (!c->tune.is("pin_alphabet", "1")) c->sample_next = c->sample_first;
+    // head-genome: prefix, n_1 and "cut reached" go on across the chunks likewise; a call is a file of its own otherwise
+    if (c->op == Op::HeadGenome && !c->tune.is("pin_alphabet", "1")) head_genome_reset(c);
     // (the chunks' outputs are drained from the two output buffers while the next chunk computes: one block each, whatever
     // the switch "out" says)
     struct Contig { bsk_ctx* c; bool was; ~Contig() { c->force_contiguous = was; } } contig{c, c->force_contiguous};

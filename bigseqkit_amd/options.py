@@ -36,6 +36,7 @@ _FIELDS = {
     "Fa2Fq": ["FastaFile", "OnlyPositiveStrand"],   # bigseqkit/fa2fq.go:11-15
     "Sample": ["Seed", "Number", "Proportion"],   # bigseqkit/sample.go:12-17
     "Shuffle": ["Seed"],                           # bigseqkit/shuffle.go:11-14
+    "HeadGenome": ["MiniCommonWords"],             # bigseqkit/head_genome.go:14-17
     "Common": ["ByName", "BySeq", "IgnoreCase", "OnlyPositiveStrand"],   # bigseqkit/common.go:13-19
     "Faidx": ["UseRegexp", "IgnoreCase", "FullHead", "RegionFile", "Regions"],   # bigseqkit/faidx.go:11-18
     "Sort": ["InNaturalOrder", "BySeq", "ByName", "ByLength", "ByBases", "GapLetters", "Reverse", "IgnoreCase",
@@ -79,6 +80,9 @@ class _CmdOptions(_Builder):
         # name.capitalize() is looked up on the option struct, then on Config
         for k, v in kwargs.items():
             name = k[0].upper() + k[1:]
+            if "_" in k:  # snake case (mini_common_words, line_width, id_regexp): the field that reads the same without them
+                flat = k.replace("_", "").lower()
+                name = next((f for f in tuple(self._fields) + tuple(_CONFIG_FIELDS) if f.lower() == flat), name)
             if name in self._fields:
                 self._v[name] = v
             elif name in _CONFIG_FIELDS:
@@ -122,3 +126,4 @@ SeqKitReplaceOptions = _make("Replace")
 SeqKitFa2FqOptions = _make("Fa2Fq")
 SeqKitSampleOptions = _make("Sample")
 SeqKitShuffleOptions = _make("Shuffle")
+SeqKitHeadGenomeOptions = _make("HeadGenome")

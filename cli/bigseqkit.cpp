@@ -170,6 +170,27 @@ const Command kCommands[] = {
       {"two-pass", '2', BOOL, "", "false"}}},
     {"shuffle", "Shuffle",                                                             // cli/shuffle.go:44-46
      {{"rand-seed", 's', INT, "Seed", "23"}, {"two-pass", '2', BOOL, "", "false"}, {"keep-temp", 'k', BOOL, "", "false"}}},
+    {"head-genome", "HeadGenome", {{"mini-common-words", 'm', INT, "MiniCommonWords", "1"}},          // cli/head_genome.go:25-53
+     "print sequences of the first genome with common prefixes in name\n"
+     "For a FASTA file containing multiple contigs of strains (see example below),\n"
+     "these's no list of IDs available for retrieving sequences of a certain strain,\n"
+     "while descriptions of each strain share the same prefix.\n"
+     "This command is used to restrieve sequences of the first strain,\n"
+     "i.e., \"Vibrio cholerae strain M29\".\n"
+     ">NZ_JFGR01000001.1 Vibrio cholerae strain M29 Contig_1, whole genome shotgun sequence\n"
+     ">NZ_JFGR01000002.1 Vibrio cholerae strain M29 Contig_2, whole genome shotgun sequence\n"
+     ">NZ_JFGR01000003.1 Vibrio cholerae strain M29 Contig_3, whole genome shotgun sequence\n"
+     ">NZ_JSTP01000001.1 Vibrio cholerae strain 2012HC-12 NODE_79, whole genome shotgun sequence\n"
+     ">NZ_JSTP01000002.1 Vibrio cholerae strain 2012HC-12 NODE_78, whole genome shotgun sequence\n"
+     "Attention:\n"
+     "  1. Sequences in file should be well organized.\n"
+     "\n"
+     "Usage:\n"
+     "  bigseqkit head-genome [flags]\n"
+     "\n"
+     "Flags:\n"
+     "  -h, --help                    help for head-genome\n"
+     "  -m, --mini-common-words int   minimal shared prefix words (default 1)\n"},
     {"rmdup", "RmDup",
      {{"by-name", 'n', BOOL, "ByName", "false"}, {"by-seq", 's', BOOL, "BySeq", "false"},
       {"ignore-case", 'i', BOOL, "IgnoreCase", "false"}, {"dup-seqs-file", 'd', STR, "DupSeqsFile", ""},
@@ -389,12 +410,12 @@ Invocation parse_invocation(const std::vector<std::string>& args) {
 
     // getFlagPositiveInt / getFlagNonNegativeInt (bigseqkit-cli/helper.go:248-265), message as written
     for (const char* nm : {"line-width", "max-mismatch", "up-stream", "down-stream", "validate-seq-length", "alphabet-guess-seq-length",
-                           "qual-ascii-base", "transl-table"}) {
+                           "qual-ascii-base", "transl-table", "mini-common-words"}) {
         const Flag* f = find_flag(*cmd, nm, 0);
         if (!f) continue;
         auto it = val.scalar.find(nm);
         long v = strtol((it != val.scalar.end() ? it->second : std::string(f->def)).c_str(), nullptr, 10);
-        const bool positive = !strcmp(nm, "qual-ascii-base") || !strcmp(nm, "transl-table");
+        const bool positive = !strcmp(nm, "qual-ascii-base") || !strcmp(nm, "transl-table") || !strcmp(nm, "mini-common-words");
         if (positive ? v <= 0 : v < 0) die(std::string("value of flag --") + nm + " should be greater than 0");
         if (!strcmp(nm, "validate-seq-length") && v > 0 && v < 1000)
             die("value of flag --validate-seq-length too small, should >= 1000");
@@ -515,6 +536,10 @@ int run_op(const std::string& use, bsk_ctx* ctx, const Part& in, int64_t pid, ui
     if (use == "range" || use == "head") return bsk_range_run(ctx, p, n, dev, in.fmt, pid, first_record, nullptr, out);
     if (use == "sample") return bsk_sample_run(ctx, p, n, dev, in.fmt, pid, first_record, nullptr, out);
     if (use == "shuffle") return bsk_shuffle_run(ctx, p, n, dev, in.fmt, pid, nullptr, out);
+    if (use == "head-genome") {  // every input is a run of its own (cli/head_genome.go:11-15)
+        bsk_head_genome_reset(ctx);
+        return bsk_head_genome_run(ctx, p, n, dev, in.fmt, pid, nullptr, out);
+    }
     return bsk_rmdup_run(ctx, p, n, dev, in.fmt, pid, nullptr, out);
 }
 
@@ -909,6 +934,67 @@ static bool parallel_pread(int fd, uint8_t* buf, size_t len, size_t off, int thr
     bool ok = true;
     for (auto& j : jobs) ok = j.get() && ok;
     return ok;
+}
+
+// head-genome (cli/head_genome.go:11-15): every file is a run of its own, the results in the order of the files.  The answer
+// is a prefix of the file, so the file is not brought to the GPU whole: pieces of its mapping that end on record starts go
+// through ONE context, which carries the prefix words, n_1 and "cut reached" from piece to piece (PARITY.md HEADG), and the
+// reading stops with the piece that holds the cut -- only the pages of the mapping that were handed over are ever read.  The
+// first piece holds 64 MiB and every next one twice the last, up to 1 GiB; BSK_STREAM_PIECE_BYTES pins the size (tests).
+Output run_head_genome(const Invocation& inv) {
+    const int device = (int)strtol(inv.pget("device").c_str(), nullptr, 10);
+    Output res;
+    bsk_ctx* ctx = nullptr;
+    if (bsk_create(inv.cmd->op, inv.js.c_str(), device, &ctx) != BSK_OK) die(bsk_global_error());
+    bsk_ctx_set(ctx, "out", "slices");
+    const char* pinned = getenv("BSK_STREAM_PIECE_BYTES");
+    for (auto& path : inv.files) {
+        if (bsk_head_genome_reset(ctx) != BSK_OK) die(bsk_last_error(ctx));
+        const int fd = open(path.c_str(), O_RDONLY);
+        if (fd < 0) die("open " + path + ": no such file or directory");
+        struct stat sb;
+        std::string whole;  // (a pipe: read to its end first)
+        const uint8_t* text = nullptr;
+        size_t size = 0;
+        const bool mapped = fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode);
+        if (mapped) {
+            size = (size_t)sb.st_size;
+            if (size) {
+                text = (const uint8_t*)mmap(nullptr, size, PROT_READ, MAP_SHARED, fd, 0);
+                if (text == MAP_FAILED) die("mmap " + path + " failed");
+            }
+        } else {
+            whole = read_file(path);
+            text = (const uint8_t*)whole.data();
+            size = whole.size();
+        }
+        close(fd);
+        const int fmt = sniff_format(path, size ? std::string((const char*)text, 1) : std::string());
+        res.fmt = fmt;
+        size_t piece = pinned ? std::max<size_t>(1, (size_t)strtoull(pinned, nullptr, 10)) : ((size_t)64 << 20);
+        size_t lo = 0;
+        int64_t k = 0;
+        while (lo < size) {
+            size_t hi = size;
+            if (size - lo > piece) {
+                size_t at = 0;
+                if (bsk_find_record_start(text, size, lo + piece, fmt, &at) == BSK_OK && at > lo && at < size) hi = at;
+            }
+            bsk_out out;
+            if (bsk_head_genome_run(ctx, text + lo, hi - lo, 0, fmt, k++, nullptr, &out) != BSK_OK) die(bsk_last_error(ctx));
+            const size_t at = res.text.size();
+            res.text.resize(at + out.len);
+            if (out.len && bsk_out_to_host(ctx, &out, &res.text[at], out.len) != BSK_OK) die(bsk_last_error(ctx));
+            int cut = 0;
+            bsk_head_genome_state(ctx, &cut, nullptr);
+            if (cut) break;  // the rest of the file is never read
+            lo = hi;
+            if (!pinned) piece = std::min<size_t>(piece * 2, (size_t)1 << 30);
+        }
+        if (mapped && size) munmap((void*)text, size);
+    }
+    bsk_destroy(ctx);
+    return res;
 }
 
 int run_devices(const Invocation& inv) {
@@ -1308,12 +1394,20 @@ static int run_main(int argc, char** argv) {
         return 0;
     }
     if (std::string(inv.cmd->use) == "sample" && inv.files.size() > 1) die("only 1 file needed");  // cli/sample.go:11-13
+    if (std::string(inv.cmd->use) == "head-genome" && !inv.pget("devices").empty())
+        die("'head-genome' runs on one device (bigseqkit head-genome ... --device N): the cut is sequential over the whole input, "
+            "a worker could not judge its shard before the shards in front of it are done, so --devices is refused");
     if (!inv.pget("devices").empty()) return run_devices(inv);  // several GPUs: worker threads + librccl, in this process
     if (inv.files.empty()) die("no input files (stdin is not supported by the IgnisHPC CLI either)");
     g_faidx_query = faidx_query;
     const std::string use_cmd = inv.cmd->use;
     const bool joins_on_host = use_cmd == "concat" || use_cmd == "common" || use_cmd == "pair";
     if (!joins_on_host && bsk_device_count() <= 0) die("no HIP device visible (the hot path has no CPU fallback)");
+    if (use_cmd == "head-genome") {
+        Output o = run_head_genome(inv);
+        store(inv, o, inv.files);
+        return 0;
+    }
     std::vector<Part> inputs = read_parts(inv.files, joins_on_host ? -1 : (int)strtol(inv.pget("device").c_str(), nullptr, 10), use_cmd);
     if (std::string(inv.cmd->use) == "concat") {
         if (inputs.size() != 2) die("2 files needed");

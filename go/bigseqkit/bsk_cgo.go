@@ -16,6 +16,7 @@
 //   Fa2Fq                 bigseqkit/fa2fq.go:42-56      MapPartitions(Fa2Fq)
 //   Sample                bigseqkit/sample.go:48-76     Count() for -n + Sample(false, fraction, seed): bsk_sample_run per partition
 //   Shuffle               bigseqkit/shuffle.go:33-46    PartitionByRandom: bsk_shuffle_run over the joined partitions
+//   HeadGenome            bigseqkit/head_genome.go:37-77 MapPartitionsWithIndex(HeadGenome): ONE cut, bsk_head_genome_run over the joined partitions
 //   RmDup                 bigseqkit/rmdup.go:70-108     MapPartitions(RmDupPrepare) + GroupByKey + Flatmap(RmDupCheck)
 //   ReadFASTA/Q[N]        bigseqkit/helper.go:148-178   PlainFile(path, delim) + ReadFixer
 //   StoreFASTX[N]         bigseqkit/helper.go:180-195   SaveAsTextFile / FileStore
@@ -46,6 +47,7 @@ static bsk_run_fn bsk_fn_rmdup(void)     { return bsk_rmdup_run; }
 static bsk_run_fn bsk_fn_replace(void)   { return bsk_replace_run; }
 static bsk_run_fn bsk_fn_fa2fq(void)     { return bsk_fa2fq_run; }
 static bsk_run_fn bsk_fn_shuffle(void)   { return bsk_shuffle_run; }
+static bsk_run_fn bsk_fn_head_genome(void) { return bsk_head_genome_run; }
 */
 import "C"
 
@@ -411,6 +413,19 @@ func Shuffle(input *SeqFrame, o *SeqKitShuffleOptions) (*Result, error) {
 	}
 	o.inner.setDefaults()
 	return mapPartitions("Shuffle", C.bsk_fn_shuffle(), OptionsToString(o.inner), joined(input), nil, 1)
+}
+
+// HeadGenome: bigseqkit/head_genome.go:37-77.  The records of the first genome (PARITY.md HEADG): one cut over the whole
+// input, so the partitions are joined and seen by ONE context, which stops reading at the cut (growing windows).
+func HeadGenome(input *SeqFrame, o *SeqKitHeadGenomeOptions) (*Result, error) {
+	if o == nil {
+		o = &SeqKitHeadGenomeOptions{}
+	}
+	o.inner.setDefaults()
+	if *o.inner.MiniCommonWords < 1 { // getFlagPositiveInt (also checked by bsk_create)
+		return nil, errors.New("value of flag --mini-common-words should be greater than 0")
+	}
+	return mapPartitions("HeadGenome", C.bsk_fn_head_genome(), OptionsToString(o.inner), joined(input), nil, 1)
 }
 
 // Sample: bigseqkit/sample.go:48-76.  The verdict on a record depends on (seed, its index in the whole input) alone

@@ -387,6 +387,23 @@ int bsk_sample_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int
 int bsk_shuffle_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,
                     bsk_out* out);
 
+/* ---- HeadGenome (bigseqkit/head_genome.go, bigseqkit-lib/head_genome.go:53-108; options {"MiniCommonWords": 1}; PARITY.md
+ * HEADG): the records of the first genome.  The words of a record are the maximal runs of its description other than ' '
+ * and '\t'; the prefix is the words of the first record of the input; n_i = leading words of record i equal to the prefix's.
+ * The output is the records before the first i >= 1 with n_i < MiniCommonWords or n_i != n_1, each as Format(LineWidth)
+ * (== Seq without options).  A kept record without a description fails the call: "no description: <ID>".  ONE cut over
+ * the whole input: the context carries the prefix, n_1, "cut reached" and the record count from call to call, so the shards
+ * of an input are run IN ORDER on one context and give the same bytes however the input was cut; a shard behind the cut
+ * gives nothing and costs nothing.  bsk_head_genome_state says whether the cut is reached (the caller stops reading) and
+ * how many records were kept so far; bsk_head_genome_reset starts the next input.  Through bsk_run_to_store a call is an
+ * input of its own unless the switch pin_alphabet says that several calls carry one.  On a device-resident shard the
+ * search runs over growing windows of the text (switch head_genome_window, bytes; 0: the whole shard at once), so its cost
+ * follows the first genome, not the shard. */
+int bsk_head_genome_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,
+                        bsk_out* out);
+int bsk_head_genome_reset(bsk_ctx* ctx);
+int bsk_head_genome_state(const bsk_ctx* ctx, int* cut_reached, uint64_t* records);
+
 /* ---- Duplicate (bigseqkit/duplicate.go:31-43, bigseqkit-lib/duplicate.go:13-30): every record Times times, copies
  * adjacent. */
 int bsk_duplicate_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,
