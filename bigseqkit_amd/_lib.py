@@ -138,6 +138,13 @@ SIGNATURES = {
     "bsk_sample_set_count": (_i, [_vp, C.c_uint64]),
     "bsk_sample_set_first_record": (_i, [_vp, C.c_uint64]),
     "bsk_shuffle_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, _vp, _p(Out)]),
+    "bsk_shuffle_hist_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp, _p(C.c_uint64)]),
+    "bsk_shuffle_hist_get": (_i, [_vp, _p(C.c_uint64), _p(C.c_uint64)]),
+    "bsk_shuffle_hist_reset": (_i, [_vp]),
+    "bsk_shuffle_plan": (_i, [_p(C.c_uint64), C.c_uint64, _p(C.c_uint64), _p(C.c_int)]),
+    "bsk_shuffle_bucket_begin": (_i, [_vp, C.c_uint32, C.c_uint32]),
+    "bsk_shuffle_bucket_add": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp]),
+    "bsk_shuffle_bucket_finish": (_i, [_vp, _vp, _p(Out)]),
     "bsk_head_genome_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, _vp, _p(Out)]),
     "bsk_head_genome_reset": (_i, [_vp]),
     "bsk_head_genome_state": (_i, [_vp, _p(C.c_int), _p(C.c_uint64)]),

@@ -436,6 +436,66 @@ def Shuffle(input, o=None, device=0):
     return _run_records("Shuffle", lib.bsk_shuffle_run, _one_shard(input), o or SeqKitShuffleOptions(), device)[0]
 
 
+SHUFFLE_BINS = 4096
+
+
+def ShuffleHistRun(op, input):
+    """bsk_shuffle_hist_run over the shards of `input`, in order: the record count of every shard (the histogram accumulates
+    in the operator's context)"""
+    counts, first = [], 0
+    for pid, ptr, n, on_dev, keep in input.partitions():
+        k = C.c_uint64()
+        check(lib.bsk_shuffle_hist_run(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None, C.byref(k)), op.ctx)
+        counts.append(k.value)
+        first += k.value
+    return counts
+
+
+def ShuffleHistGet(op):
+    """bsk_shuffle_hist_get: (bytes[4096], records[4096])"""
+    b, r = (C.c_uint64 * SHUFFLE_BINS)(), (C.c_uint64 * SHUFFLE_BINS)()
+    check(lib.bsk_shuffle_hist_get(op.ctx, b, r), op.ctx)
+    return list(b), list(r)
+
+
+def ShuffleHistReset(op):
+    """bsk_shuffle_hist_reset: the context is about to see another input"""
+    check(lib.bsk_shuffle_hist_reset(op.ctx), op.ctx)
+
+
+def ShufflePlan(hist_bytes, budget_bytes):
+    """bsk_shuffle_plan (no device): bounds[b] = first fine bin of bucket b, bounds[-1] = 4096"""
+    h = (C.c_uint64 * SHUFFLE_BINS)(*hist_bytes)
+    bounds = (C.c_uint64 * (SHUFFLE_BINS + 1))()
+    nb = C.c_int()
+    check(lib.bsk_shuffle_plan(h, budget_bytes, bounds, C.byref(nb)))
+    return list(bounds[:nb.value + 1])
+
+
+def ShuffleBucket(op, input, counts, lo_bin, hi_bin):
+    """bsk_shuffle_bucket_begin / _add over the shards of `input` / _finish: the bytes of the bucket [lo_bin, hi_bin)"""
+    check(lib.bsk_shuffle_bucket_begin(op.ctx, lo_bin, hi_bin), op.ctx)
+    first = 0
+    for (pid, ptr, n, on_dev, keep), cnt in zip(input.partitions(), counts):
+        check(lib.bsk_shuffle_bucket_add(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None), op.ctx)
+        first += cnt
+    out = _lib.Out()
+    check(lib.bsk_shuffle_bucket_finish(op.ctx, None, C.byref(out)), op.ctx)
+    buf = C.create_string_buffer(max(1, out.len))
+    check(lib.bsk_out_to_host(op.ctx, C.byref(out), buf, out.len), op.ctx)
+    return buf.raw[:out.len]
+
+
+def ShuffleBuckets(input, o=None, budget_bytes=1 << 30, device=0):
+    """Shuffle of an input of any size on one device (PARITY SHUF): the histogram of the draws over all shards, the plan of
+    buckets of at most `budget_bytes`, then one collect sequence per bucket; the same bytes as Shuffle.  The input is read
+    once plus once per bucket."""
+    with Operator("Shuffle", (o or SeqKitShuffleOptions()).to_json(), device) as op:
+        counts = ShuffleHistRun(op, input)
+        bounds = ShufflePlan(ShuffleHistGet(op)[0], budget_bytes)
+        return b"".join(ShuffleBucket(op, input, counts, lo, hi) for lo, hi in zip(bounds[:-1], bounds[1:]))
+
+
 def HeadGenome(input, o=None, device=0):
     """bigseqkit/head_genome.go:37-77 (PARITY HEADG): the records of the first genome.  ONE cut over the whole input: the
     shards go through one context in order, which carries the prefix words, n_1 and "cut reached" from shard to shard, and

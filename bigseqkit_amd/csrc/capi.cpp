@@ -14,6 +14,7 @@
 #include "ctx.hpp"
 #include "ops_host.hpp"
 #include "ops_host_internal.hpp"
+#include "ops_sample.hpp"
 #include "ops_segcopy.hpp"
 #include "stats_host.hpp"
 #include "stream_stats.hpp"
@@ -376,6 +377,8 @@ void bsk_destroy(bsk_ctx* c) {
         bsk::replace_free(c);
         bsk::fa2fq_free(c);
         for (void* p : {(void*)c->d_hg_words, (void*)c->d_hg_off, (void*)c->d_hg_counts, (void*)c->d_hg_res})
+            if (p) hipFree(p);
+        for (void* p : {(void*)c->shb.d_hist, (void*)c->shb.d_acc, (void*)c->shb.d_draw, (void*)c->shb.d_off, (void*)c->shb.d_len})
             if (p) hipFree(p);
         if (c->d_vm_progs) hipFree(c->d_vm_progs);
         if (c->d_id_off) hipFree(c->d_id_off);
@@ -1199,6 +1202,77 @@ int bsk_sample_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int f
 int bsk_shuffle_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,
                     bsk_out* out) {
     return run_record_op(c, Op::Shuffle, shard, n, on_device, format, stream, out);
+}
+
+// ---- shuffle in buckets of the draw (include/bsk.h; the passes are in ops_host_next.cpp)
+int bsk_shuffle_hist_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                         void* stream, uint64_t* n_records) {
+    return record_call(c, nullptr, Op::Shuffle, true, "", shard, n, on_device, format, stream, CallValues(),
+                       [&](const uint8_t* d, hipStream_t st) { return shuffle_hist_device(c, d, n, format, first_record, st, n_records); });
+}
+
+int bsk_shuffle_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) {
+    if (!c) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: null context");
+    if (c->op != Op::Shuffle) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: not a Shuffle context");
+    if (c->device < 0) return fail(c, BSK_ERR_NO_DEVICE, "libbsk: context was created without a device");
+    BSK_ENTER(c);
+    return shuffle_hist_get(c, bytes, records);
+}
+
+int bsk_shuffle_hist_reset(bsk_ctx* c) {
+    if (!c) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: null context");
+    if (c->op != Op::Shuffle) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: not a Shuffle context");
+    if (c->device < 0) return fail(c, BSK_ERR_NO_DEVICE, "libbsk: context was created without a device");
+    BSK_ENTER(c);
+    HIP_TRY(c, hipDeviceSynchronize());
+    if (c->shb.d_hist) HIP_TRY(c, hipMemset(c->shb.d_hist, 0, 2 * SHUFFLE_BINS * sizeof(uint64_t)));
+    return BSK_OK;
+}
+
+int bsk_shuffle_plan(const uint64_t* bytes, uint64_t budget_bytes, uint64_t* bounds, int* n_buckets) {
+    if (!bytes || !bounds || !n_buckets) return fail(nullptr, BSK_ERR_INVALID_ARG, "libbsk: bsk_shuffle_plan: null argument");
+    int nb = 0;
+    uint64_t sum = 0;
+    bounds[0] = 0;
+    for (uint32_t b = 0; b < SHUFFLE_BINS; ++b) {
+        if (bytes[b] > budget_bytes)
+            return fail(nullptr, BSK_ERR_UNSUPPORTED, "libbsk: shuffle: fine bin " + std::to_string(b) + " of the draw holds " + std::to_string(bytes[b]) +
+                        " bytes, more than the budget of " + std::to_string(budget_bytes) + " bytes of a bucket (4096 bins: the input is too large for this budget)");
+        if (sum + bytes[b] > budget_bytes) {  // (sum > 0 here: the bin alone fits)
+            bounds[++nb] = b;
+            sum = 0;
+        }
+        sum += bytes[b];
+    }
+    bounds[++nb] = SHUFFLE_BINS;
+    *n_buckets = nb;
+    return BSK_OK;
+}
+
+int bsk_shuffle_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin_exclusive) {
+    if (!c) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: null context");
+    if (c->op != Op::Shuffle) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: not a Shuffle context");
+    if (c->device < 0) return fail(c, BSK_ERR_NO_DEVICE, "libbsk: context was created without a device");
+    if (lo_bin >= hi_bin_exclusive || hi_bin_exclusive > SHUFFLE_BINS)
+        return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_shuffle_bucket_begin: the bins must be 0 <= lo < hi <= 4096");
+    BSK_ENTER(c);
+    return shuffle_bucket_begin(c, lo_bin, hi_bin_exclusive);
+}
+
+int bsk_shuffle_bucket_add(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                           void* stream) {
+    return record_call(c, nullptr, Op::Shuffle, true, "", shard, n, on_device, format, stream, CallValues(),
+                       [&](const uint8_t* d, hipStream_t st) { return shuffle_bucket_add(c, d, n, format, first_record, st); });
+}
+
+int bsk_shuffle_bucket_finish(bsk_ctx* c, void* stream, bsk_out* out) {
+    if (!c) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: null context");
+    if (c->op != Op::Shuffle || !out) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: not a Shuffle context");
+    if (c->device < 0) return fail(c, BSK_ERR_NO_DEVICE, "libbsk: context was created without a device");
+    out->d_seg_src = nullptr; out->d_seg_off = nullptr; out->n_segments = 0;
+    BSK_ENTER(c);
+    c->pend_out.kind = 0;
+    return shuffle_bucket_finish(c, (hipStream_t)stream, out);
 }
 
 int bsk_head_genome_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,

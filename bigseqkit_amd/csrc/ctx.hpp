@@ -163,6 +163,20 @@ struct bsk_ctx {
         int64_t n1 = -1;
         uint64_t records = 0;
     } hg;
+    // shuffle in buckets of the draw (ops_host_next.cpp; PARITY.md SHUF): the fine-bin histogram, which accumulates over the
+    // shards of a call sequence, and the open bucket -- the texts of its records back to back (every shard's share begins on
+    // a 256-byte boundary) and (draw, byte offset, length) per record, in the order they were added
+    struct ShuffleBuckets {
+        uint64_t* d_hist = nullptr;      // bytes[4096] ++ records[4096]
+        bool open = false;
+        uint64_t lo = 0, hi = 0;         // the draws of the open bucket, both inclusive
+        uint8_t* d_acc = nullptr;
+        uint64_t acc_cap = 0, acc_used = 0;
+        uint64_t* d_draw = nullptr;
+        uint64_t* d_off = nullptr;
+        uint32_t* d_len = nullptr;
+        uint64_t rec_cap = 0, n = 0;
+    } shb;
     uint8_t* d_hg_words = nullptr;
     uint32_t* d_hg_off = nullptr;
     uint32_t* d_hg_counts = nullptr;     // n_i of the records of the running window

@@ -2,6 +2,8 @@
 // itself is moved by the segmented copy.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
 #include "ops_records.hpp"  // ERR_RECORD_TOO_LARGE
 #include "ops_sample.hpp"
 #include "record_text_dev.hpp"
@@ -61,6 +63,88 @@ __global__ __launch_bounds__(256) void k_shuffle_fix(const uint8_t* __restrict__
     o[n - 1] = (uint8_t)'\n';
 }
 
+// ---- shuffle in buckets of the draw (PARITY.md SHUF): the 64-bit draw range is cut into SHUFFLE_BINS fine bins, a bucket is a run
+// of consecutive bins, the output is bucket 0 sorted by draw, then bucket 1, ...
+
+// bytes (text + '\n') and records per fine bin, privatised per block: 4096 x (u64 + u32) = 48 KiB of LDS, merged with one
+// global atomic per counter and non-empty bin.  A block walks many records (grid-stride) so that the zeroing and the merge
+// of its 48 KiB are paid once.
+__global__ __launch_bounds__(256) void k_shuffle_hist(const uint8_t* __restrict__ buf, uint64_t buf_n, RecordTable t, int fastq,
+                                                      uint64_t first_record, uint64_t key, unsigned long long* __restrict__ g_bytes,
+                                                      unsigned long long* __restrict__ g_records) {
+    __shared__ unsigned long long s_bytes[SHUFFLE_BINS];
+    __shared__ uint32_t s_records[SHUFFLE_BINS];
+    for (uint32_t b = threadIdx.x; b < SHUFFLE_BINS; b += blockDim.x) { s_bytes[b] = 0; s_records[b] = 0; }
+    __syncthreads();
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < t.n; i += stride) {
+        const uint32_t bin = (uint32_t)(sample_draw(key, first_record + i) >> SHUFFLE_BIN_SHIFT);
+        atomicAdd(&s_bytes[bin], (unsigned long long)(record_text_len(buf, buf_n, t, fastq, i) + 1u));
+        atomicAdd(&s_records[bin], 1u);
+    }
+    __syncthreads();
+    for (uint32_t b = threadIdx.x; b < SHUFFLE_BINS; b += blockDim.x) {
+        const uint32_t r = s_records[b];
+        if (r == 0) continue;
+        atomicAdd(&g_bytes[b], s_bytes[b]);
+        atomicAdd(&g_records[b], (unsigned long long)r);
+    }
+}
+
+// the verdict of a bucket: out_len[i] = text + '\n' of record i when lo <= draw <= hi, else 0; keep[i] = 1 / 0
+__global__ __launch_bounds__(256) void k_shuffle_pick(const uint8_t* __restrict__ buf, uint64_t buf_n, RecordTable t, int fastq,
+                                                      uint64_t first_record, uint64_t key, uint64_t lo, uint64_t hi,
+                                                      uint32_t* __restrict__ out_len, uint32_t* __restrict__ keep,
+                                                      uint64_t* __restrict__ status) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= t.n) return;
+    const uint64_t d = sample_draw(key, first_record + i);
+    uint64_t bytes = 0;
+    if (lo <= d && d <= hi) bytes = record_text_len(buf, buf_n, t, fastq, i) + 1u;
+    if (bytes > 0xFFFFFFFFull) {
+        atomicOr((unsigned long long*)&status[0], (unsigned long long)ERR_RECORD_TOO_LARGE);
+        bytes = 0;
+    }
+    out_len[i] = (uint32_t)bytes;
+    keep[i] = bytes ? 1u : 0u;
+}
+
+// the kept records of the shard join the accumulation, in shard order: (draw, byte offset, length) at n0 + keep_off[i]
+__global__ __launch_bounds__(256) void k_shuffle_append(uint64_t n, uint64_t first_record, uint64_t key, const uint32_t* __restrict__ out_len,
+                                                        const uint64_t* __restrict__ out_off, const uint64_t* __restrict__ keep_off,
+                                                        uint64_t n0, uint64_t bytes0, uint64_t* __restrict__ acc_draw,
+                                                        uint64_t* __restrict__ acc_off, uint32_t* __restrict__ acc_len) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t len = out_len[i];
+    if (len == 0) return;
+    const uint64_t j = n0 + keep_off[i];
+    acc_draw[j] = sample_draw(key, first_record + i);
+    acc_off[j] = bytes0 + out_off[i];
+    acc_len[j] = len;
+}
+
+// k_shuffle_segments over (offset, length) arrays instead of a record table: segment j = accumulated record perm[j]
+__global__ __launch_bounds__(256) void k_shuffle_bucket_segments(uint64_t n, const uint8_t* __restrict__ acc, const uint64_t* __restrict__ acc_off,
+                                                                 const uint32_t* __restrict__ acc_len, const uint32_t* __restrict__ perm,
+                                                                 uint64_t* __restrict__ seg_src, uint32_t* __restrict__ len_perm) {
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t i = perm[j];
+    seg_src[j] = (uint64_t)(uintptr_t)(acc + acc_off[i]);
+    len_perm[j] = acc_len[i];
+}
+
+// the path without the segmented copy: segment j byte by byte
+__global__ __launch_bounds__(256) void k_shuffle_bucket_bytes(uint64_t n, const uint64_t* __restrict__ seg_src, const uint64_t* __restrict__ seg_off,
+                                                              uint8_t* __restrict__ out) {
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const uint8_t* s = (const uint8_t*)(uintptr_t)seg_src[j];
+    const uint64_t a = seg_off[j], b = seg_off[j + 1];
+    for (uint64_t k = a; k < b; ++k) out[k] = s[k - a];
+}
+
 inline dim3 grid_of(uint64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 }  // namespace
@@ -91,6 +175,46 @@ hipError_t launch_shuffle_fix(const uint8_t* buf, const RecordTable& t, const ui
                               const uint64_t* seg_off, const uint64_t* seg_src, uint8_t* out, bool all, hipStream_t st) {
     if (t.n == 0) return hipSuccess;
     hipLaunchKernelGGL(k_shuffle_fix, grid_of(t.n), dim3(256), 0, st, buf, t, perm, len_perm, seg_off, seg_src, out, all ? 1 : 0);
+    return hipGetLastError();
+}
+
+hipError_t launch_shuffle_hist(const uint8_t* buf, uint64_t buf_n, const RecordTable& t, int fastq, uint64_t first_record, int64_t seed,
+                               uint64_t* bytes, uint64_t* records, int num_cus, hipStream_t st) {
+    if (t.n == 0) return hipSuccess;
+    // three blocks of 48 KiB fit the LDS of a CU
+    const uint64_t blocks = std::min<uint64_t>((t.n + 255) / 256, (uint64_t)std::max(1, num_cus) * 3);
+    hipLaunchKernelGGL(k_shuffle_hist, dim3((unsigned)blocks), dim3(256), 0, st, buf, buf_n, t, fastq, first_record, sample_key(seed),
+                       (unsigned long long*)bytes, (unsigned long long*)records);
+    return hipGetLastError();
+}
+
+hipError_t launch_shuffle_pick(const uint8_t* buf, uint64_t buf_n, const RecordTable& t, int fastq, uint64_t first_record, int64_t seed,
+                               uint64_t lo, uint64_t hi, uint32_t* out_len, uint32_t* keep, uint64_t* status, hipStream_t st) {
+    if (t.n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_shuffle_pick, grid_of(t.n), dim3(256), 0, st, buf, buf_n, t, fastq, first_record, sample_key(seed), lo, hi,
+                       out_len, keep, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_shuffle_append(uint64_t n, uint64_t first_record, int64_t seed, const uint32_t* out_len, const uint64_t* out_off,
+                                 const uint64_t* keep_off, uint64_t n0, uint64_t bytes0, uint64_t* acc_draw, uint64_t* acc_off,
+                                 uint32_t* acc_len, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_shuffle_append, grid_of(n), dim3(256), 0, st, n, first_record, sample_key(seed), out_len, out_off, keep_off, n0,
+                       bytes0, acc_draw, acc_off, acc_len);
+    return hipGetLastError();
+}
+
+hipError_t launch_shuffle_bucket_segments(uint64_t n, const uint8_t* acc, const uint64_t* acc_off, const uint32_t* acc_len,
+                                          const uint32_t* perm, uint64_t* seg_src, uint32_t* len_perm, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_shuffle_bucket_segments, grid_of(n), dim3(256), 0, st, n, acc, acc_off, acc_len, perm, seg_src, len_perm);
+    return hipGetLastError();
+}
+
+hipError_t launch_shuffle_bucket_bytes(uint64_t n, const uint64_t* seg_src, const uint64_t* seg_off, uint8_t* out, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_shuffle_bucket_bytes, grid_of(n), dim3(256), 0, st, n, seg_src, seg_off, out);
     return hipGetLastError();
 }
 

@@ -706,6 +706,13 @@ static size_t whole_file_limit() {
     return lim;
 }
 
+// BSK_SHUFFLE_BUDGET_BYTES: the bytes a bucket of `shuffle` may hold (run_shuffle_buckets); 0: unset
+static uint64_t shuffle_budget() {
+    const char* e = getenv("BSK_SHUFFLE_BUDGET_BYTES");
+    return e ? (uint64_t)strtoull(e, nullptr, 10) : 0;
+}
+bool g_shuffle_unfit = false;  // read_parts: the whole-file load of a `shuffle` input failed and a budget is set
+
 std::vector<Part> read_parts(const std::vector<std::string>& files, int device = -1, const std::string& use = "") {
     std::vector<Part> parts;
     for (auto& f : files) {
@@ -734,7 +741,14 @@ std::vector<Part> read_parts(const std::vector<std::string>& files, int device =
                 if (use != "stats") {
                     close(fd);
                     const std::string what = std::string(bsk_global_error()) + " -- '" + use + "': " + f + " (" + std::to_string(p.n) + " bytes) must fit one GPU next to its result; ";
-                    if (use == "shuffle") die(what + "shuffle orders all records of its input in one pass and runs on one device");
+                    if (use == "shuffle" && shuffle_budget() > 0) {  // (the mapped files go through the buckets of the draw instead)
+                        g_shuffle_unfit = true;
+                        release(parts);
+                        return parts;
+                    }
+                    if (use == "shuffle")
+                        die(what + "shuffle orders all records of its input in one pass and runs on one device "
+                                   "(BSK_SHUFFLE_BUDGET_BYTES=<bytes> shuffles it in buckets of at most that many bytes, read once per bucket)");
                     die(what + "cut it over several GPUs (--devices 0-7: fq2fa, grep, locate, rmdup, sample, seq, stats, subseq, translate)");
                 }
                 // stats: the file stays on the host, its mapping is streamed in record-aligned chunks
@@ -993,6 +1007,99 @@ Output run_head_genome(const Invocation& inv) {
         }
         if (mapped && size) munmap((void*)text, size);
     }
+    bsk_destroy(ctx);
+    return res;
+}
+
+// shuffle in buckets of the draw (include/bsk.h; PARITY.md SHUF): the way of `shuffle` for an input that is larger than the
+// byte budget of a bucket (BSK_SHUFFLE_BUDGET_BYTES) or that could not be loaded whole.  The files stay on the host, mapped;
+// several files are unioned in order (cli/shuffle.go:11-15), the record index runs over all of them.  Record-aligned pieces
+// (BSK_STREAM_PIECE_BYTES, default 1 GiB) go through ONE context: once for the histogram of the draws -- each piece's first
+// record index is remembered -- and then once per bucket of the plan; every finished bucket is appended to the output.  The
+// input is read 1 + (number of buckets) times.  A piece never spans two files, so a file that ends without a newline behaves
+// like the union of the whole-file path: its last record gets the newline.
+
+Output run_shuffle_buckets(const Invocation& inv) {
+    const int device = (int)strtol(inv.pget("device").c_str(), nullptr, 10);
+    const uint64_t budget = shuffle_budget();
+    Output res;
+    bsk_ctx* ctx = nullptr;
+    if (bsk_create(inv.cmd->op, inv.js.c_str(), device, &ctx) != BSK_OK) die(bsk_global_error());
+    const bool timing = getenv("BSK_CLI_TIMING") != nullptr;
+    if (timing) bsk_profile_enable(ctx, 1);
+    struct File { std::string whole; const uint8_t* text = nullptr; size_t size = 0; bool mapped = false; };
+    struct Piece { const uint8_t* p; size_t n; uint64_t first; };
+    std::vector<File> files(inv.files.size());
+    std::vector<Piece> pieces;
+    const char* pinned = getenv("BSK_STREAM_PIECE_BYTES");
+    const size_t piece = pinned ? std::max<size_t>(1, (size_t)strtoull(pinned, nullptr, 10)) : ((size_t)1 << 30);
+    int fmt = -1;
+    for (size_t fi = 0; fi < inv.files.size(); ++fi) {
+        const std::string& path = inv.files[fi];
+        File& f = files[fi];
+        const int fd = open(path.c_str(), O_RDONLY);
+        if (fd < 0) die("open " + path + ": no such file or directory");
+        struct stat sb;
+        f.mapped = fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode);
+        if (f.mapped) {
+            f.size = (size_t)sb.st_size;
+            if (f.size) {
+                f.text = (const uint8_t*)mmap(nullptr, f.size, PROT_READ, MAP_SHARED, fd, 0);
+                if (f.text == MAP_FAILED) die("mmap " + path + " failed");
+            }
+        } else {  // (a pipe: read to its end first)
+            f.whole = read_file(path);
+            f.text = (const uint8_t*)f.whole.data();
+            f.size = f.whole.size();
+        }
+        close(fd);
+        const int ffmt = sniff_format(path, f.size ? std::string((const char*)f.text, 1) : std::string());
+        if (fmt >= 0 && ffmt != fmt) die("shuffle: inputs of different formats");
+        fmt = ffmt;
+        for (size_t lo = 0; lo < f.size;) {
+            size_t hi = f.size;
+            if (f.size - lo > piece) {
+                size_t at = 0;
+                if (bsk_find_record_start(f.text, f.size, lo + piece, fmt, &at) == BSK_OK && at > lo && at < f.size) hi = at;
+            }
+            pieces.push_back({f.text + lo, hi - lo, 0});
+            lo = hi;
+        }
+    }
+    res.fmt = fmt < 0 ? BSK_FORMAT_FASTA : fmt;
+    uint64_t g = 0;
+    int64_t k = 0;
+    for (auto& pc : pieces) {
+        uint64_t cnt = 0;
+        pc.first = g;
+        if (bsk_shuffle_hist_run(ctx, pc.p, pc.n, 0, res.fmt, k++, g, nullptr, &cnt) != BSK_OK) die(bsk_last_error(ctx));
+        g += cnt;
+    }
+    mark("shuffle: histogram of the draws");
+    std::vector<uint64_t> hist(4096), bounds(4097);
+    int n_buckets = 0;
+    if (bsk_shuffle_hist_get(ctx, hist.data(), nullptr) != BSK_OK) die(bsk_last_error(ctx));
+    if (bsk_shuffle_plan(hist.data(), budget, bounds.data(), &n_buckets) != BSK_OK) die(bsk_global_error());
+    for (int b = 0; b < n_buckets; ++b) {
+        if (bsk_shuffle_bucket_begin(ctx, (uint32_t)bounds[b], (uint32_t)bounds[b + 1]) != BSK_OK) die(bsk_last_error(ctx));
+        k = 0;
+        for (auto& pc : pieces)
+            if (bsk_shuffle_bucket_add(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr) != BSK_OK) die(bsk_last_error(ctx));
+        bsk_out out;
+        if (bsk_shuffle_bucket_finish(ctx, nullptr, &out) != BSK_OK) die(bsk_last_error(ctx));
+        const size_t at = res.text.size();
+        res.text.resize(at + out.len);
+        if (out.len && bsk_out_to_host(ctx, &out, &res.text[at], out.len) != BSK_OK) die(bsk_last_error(ctx));
+    }
+    mark("shuffle: buckets");
+    if (timing) {
+        std::vector<char> buf(1 << 16);
+        if (bsk_profile_dump(ctx, buf.data(), buf.size()) == BSK_OK)
+            fprintf(stderr, "[timing] shuffle in %d bucket(s) of at most %llu bytes, %zu piece(s); stages: %s\n", n_buckets,
+                    (unsigned long long)budget, pieces.size(), buf.data());
+    }
+    for (auto& f : files)
+        if (f.mapped && f.size) munmap((void*)f.text, f.size);
     bsk_destroy(ctx);
     return res;
 }
@@ -1408,7 +1515,24 @@ static int run_main(int argc, char** argv) {
         store(inv, o, inv.files);
         return 0;
     }
+    if (use_cmd == "shuffle" && shuffle_budget() > 0) {
+        // more bytes than a bucket may hold: not loaded whole (a pipe has no size: it takes the whole-file path)
+        uint64_t total = 0;
+        struct stat sb;
+        for (auto& f : inv.files)
+            if (stat(f.c_str(), &sb) == 0 && S_ISREG(sb.st_mode)) total += (uint64_t)sb.st_size;
+        if (total > shuffle_budget()) {
+            Output o = run_shuffle_buckets(inv);
+            store(inv, o, inv.files);
+            return 0;
+        }
+    }
     std::vector<Part> inputs = read_parts(inv.files, joins_on_host ? -1 : (int)strtol(inv.pget("device").c_str(), nullptr, 10), use_cmd);
+    if (g_shuffle_unfit) {
+        Output o = run_shuffle_buckets(inv);
+        store(inv, o, inv.files);
+        return 0;
+    }
     if (std::string(inv.cmd->use) == "concat") {
         if (inputs.size() != 2) die("2 files needed");
         if (inputs[0].fmt != inputs[1].fmt) die("concat: inputs of different formats");

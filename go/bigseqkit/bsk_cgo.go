@@ -16,6 +16,7 @@
 //   Fa2Fq                 bigseqkit/fa2fq.go:42-56      MapPartitions(Fa2Fq)
 //   Sample                bigseqkit/sample.go:48-76     Count() for -n + Sample(false, fraction, seed): bsk_sample_run per partition
 //   Shuffle               bigseqkit/shuffle.go:33-46    PartitionByRandom: bsk_shuffle_run over the joined partitions
+//   ShuffleBuckets        (the same order as Shuffle)   histogram of the draws + plan + one collect sequence per bucket: any input size
 //   HeadGenome            bigseqkit/head_genome.go:37-77 MapPartitionsWithIndex(HeadGenome): ONE cut, bsk_head_genome_run over the joined partitions
 //   RmDup                 bigseqkit/rmdup.go:70-108     MapPartitions(RmDupPrepare) + GroupByKey + Flatmap(RmDupCheck)
 //   ReadFASTA/Q[N]        bigseqkit/helper.go:148-178   PlainFile(path, delim) + ReadFixer
@@ -413,6 +414,76 @@ func Shuffle(input *SeqFrame, o *SeqKitShuffleOptions) (*Result, error) {
 	}
 	o.inner.setDefaults()
 	return mapPartitions("Shuffle", C.bsk_fn_shuffle(), OptionsToString(o.inner), joined(input), nil, 1)
+}
+
+// ShuffleBuckets: the result of Shuffle for an input of any size on one device (PARITY.md SHUF).  The draws are cut into
+// buckets of at most budgetBytes of output: bsk_shuffle_hist_run over all partitions, bsk_shuffle_plan, then per bucket
+// bsk_shuffle_bucket_begin / _add over all partitions / _finish.  The input is read once plus once per bucket; a result
+// part per bucket, in order.
+func ShuffleBuckets(input *SeqFrame, o *SeqKitShuffleOptions, budgetBytes uint64) (*Result, error) {
+	if o == nil {
+		o = &SeqKitShuffleOptions{}
+	}
+	o.inner.setDefaults()
+	op, err := newBskOp("Shuffle", OptionsToString(o.inner), input.Device)
+	if err != nil {
+		return nil, err
+	}
+	defer op.Close()
+	ptrOf := func(d []byte) unsafe.Pointer {
+		if len(d) == 0 {
+			return nil
+		}
+		return unsafe.Pointer(&d[0])
+	}
+	counts := make([]uint64, len(input.Shards))
+	var first uint64
+	for pid, s := range input.Shards {
+		var k C.uint64_t
+		if rc := C.bsk_shuffle_hist_run(op.ctx, ptrOf(s.Data), C.size_t(len(s.Data)), 0, C.int(input.Format), C.int64_t(pid),
+			C.uint64_t(first), nil, &k); rc != C.BSK_OK {
+			return nil, op.err()
+		}
+		counts[pid] = uint64(k)
+		first += uint64(k)
+	}
+	var hist [4096]C.uint64_t
+	if rc := C.bsk_shuffle_hist_get(op.ctx, &hist[0], nil); rc != C.BSK_OK {
+		return nil, op.err()
+	}
+	var bounds [4097]C.uint64_t
+	var nb C.int
+	if rc := C.bsk_shuffle_plan(&hist[0], C.uint64_t(budgetBytes), &bounds[0], &nb); rc != C.BSK_OK {
+		return nil, errors.New(C.GoString(C.bsk_global_error()))
+	}
+	res := &Result{Parts: make([][]byte, int(nb))}
+	for b := 0; b < int(nb); b++ {
+		if rc := C.bsk_shuffle_bucket_begin(op.ctx, C.uint32_t(bounds[b]), C.uint32_t(bounds[b+1])); rc != C.BSK_OK {
+			return nil, op.err()
+		}
+		first = 0
+		for pid, s := range input.Shards {
+			if rc := C.bsk_shuffle_bucket_add(op.ctx, ptrOf(s.Data), C.size_t(len(s.Data)), 0, C.int(input.Format), C.int64_t(pid),
+				C.uint64_t(first), nil); rc != C.BSK_OK {
+				return nil, op.err()
+			}
+			first += counts[pid]
+		}
+		var out C.bsk_out
+		if rc := C.bsk_shuffle_bucket_finish(op.ctx, nil, &out); rc != C.BSK_OK {
+			return nil, op.err()
+		}
+		buf := make([]byte, int(out.len))
+		if out.len > 0 {
+			if rc := C.bsk_out_to_host(op.ctx, &out, unsafe.Pointer(&buf[0]), out.len); rc != C.BSK_OK {
+				return nil, op.err()
+			}
+		}
+		res.Parts[b] = buf
+		res.Bytes += uint64(out.len)
+		res.Records += uint64(out.records)
+	}
+	return res, nil
 }
 
 // HeadGenome: bigseqkit/head_genome.go:37-77.  The records of the first genome (PARITY.md HEADG): one cut over the whole

@@ -387,6 +387,34 @@ int bsk_sample_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int
 int bsk_shuffle_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,
                     bsk_out* out);
 
+/* ---- Shuffle in buckets of the draw: the same result for an input of any size on one device (PARITY.md SHUF).  The upper 12
+ * bits of draw(seed, g) are the "fine bin" of record g (4096 bins); a bucket is a run of consecutive bins, and the shuffled
+ * output is bucket 0's records in ascending order of their draws, then bucket 1's, ...  The bytes do not depend on the
+ * buckets or on how the input is cut into shards.  The input is read once for the histogram and once per bucket:
+ *   bsk_shuffle_hist_run      every shard in turn (first_record = index of its first record in the whole input; *n_records =
+ *                             the records of the shard): bytes (text + newline) and records per fine bin accumulate in the context
+ *   bsk_shuffle_hist_get      the histogram: bytes[4096], records[4096]
+ *   bsk_shuffle_hist_reset    the histogram back to zero: the context is about to see another input
+ *   bsk_shuffle_plan          pure host function, no context: consecutive bins are grouped greedily into buckets of at most
+ *                             budget_bytes; bounds[b] = first bin of bucket b, bounds[*n_buckets] = 4096 (bounds: room for 4097).
+ *                             Empty bins join their neighbour, an empty histogram is one bucket.  A single bin above the budget
+ *                             is BSK_ERR_UNSUPPORTED (bsk_global_error names its bytes and the budget).
+ *   bsk_shuffle_bucket_begin / _add / _finish
+ *                             one bucket: begin names its bins [lo_bin, hi_bin_exclusive), add collects the shard's records whose
+ *                             draw falls into them (every shard of the input, any order), finish sorts them by draw and returns
+ *                             them as one block, valid until the next call on the context.  add or finish without begin, and begin
+ *                             inside an open bucket, are BSK_ERR_INVALID_ARG; 2^32 or more records in one bucket are
+ *                             BSK_ERR_UNSUPPORTED (the whole input may hold more).  An error in add or finish closes the bucket. */
+int bsk_shuffle_hist_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                         void* stream, uint64_t* n_records);
+int bsk_shuffle_hist_get(bsk_ctx* ctx, uint64_t* bytes, uint64_t* records);
+int bsk_shuffle_hist_reset(bsk_ctx* ctx);
+int bsk_shuffle_plan(const uint64_t* bytes, uint64_t budget_bytes, uint64_t* bounds, int* n_buckets);
+int bsk_shuffle_bucket_begin(bsk_ctx* ctx, uint32_t lo_bin, uint32_t hi_bin_exclusive);
+int bsk_shuffle_bucket_add(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                           void* stream);
+int bsk_shuffle_bucket_finish(bsk_ctx* ctx, void* stream, bsk_out* out);
+
 /* ---- HeadGenome (bigseqkit/head_genome.go, bigseqkit-lib/head_genome.go:53-108; options {"MiniCommonWords": 1}; PARITY.md
  * HEADG): the records of the first genome.  The words of a record are the maximal runs of its description other than ' '
  * and '\t'; the prefix is the words of the first record of the input; n_i = leading words of record i equal to the prefix's.
