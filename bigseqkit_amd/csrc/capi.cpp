@@ -1204,7 +1204,7 @@ int bsk_shuffle_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int 
     return run_record_op(c, Op::Shuffle, shard, n, on_device, format, stream, out);
 }
 
-// ---- shuffle in buckets of the draw (include/bsk.h; the passes are in ops_host_next.cpp)
+// ---- shuffle in buckets of the draw (include/bsk.h; the passes are in ops_host_shuffle.cpp)
 int bsk_shuffle_hist_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                          void* stream, uint64_t* n_records) {
     return record_call(c, nullptr, Op::Shuffle, true, "", shard, n, on_device, format, stream, CallValues(),

@@ -163,9 +163,10 @@ struct bsk_ctx {
         int64_t n1 = -1;
         uint64_t records = 0;
     } hg;
-    // shuffle in buckets of the draw (ops_host_next.cpp; PARITY.md SHUF): the fine-bin histogram, which accumulates over the
+    // shuffle in buckets of the draw (ops_host_shuffle.cpp; PARITY.md SHUF): the fine-bin histogram, which accumulates over the
     // shards of a call sequence, and the open bucket -- the texts of its records back to back (every shard's share begins on
-    // a 256-byte boundary) and (draw, byte offset, length) per record, in the order they were added
+    // a 256-byte boundary) and (draw, byte offset, length) per record, in the order they were added; `total` = the bytes of
+    // those records (acc_used without the padding): the size of the bucket's output, known without a read-back
     struct ShuffleBuckets {
         uint64_t* d_hist = nullptr;      // bytes[4096] ++ records[4096]
         bool open = false;
@@ -175,7 +176,7 @@ struct bsk_ctx {
         uint64_t* d_draw = nullptr;
         uint64_t* d_off = nullptr;
         uint32_t* d_len = nullptr;
-        uint64_t rec_cap = 0, n = 0;
+        uint64_t rec_cap = 0, n = 0, total = 0;
     } shb;
     uint8_t* d_hg_words = nullptr;
     uint32_t* d_hg_off = nullptr;

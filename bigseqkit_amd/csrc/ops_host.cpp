@@ -750,6 +750,46 @@ int try_records_as_slices(bsk_ctx* c, const uint8_t* d_buf, size_t n, const SeqP
     return 1;
 }
 
+// ---- the prologue of the operators that print record text (ops_host_internal.hpp)
+int index_record_text(bsk_ctx* c, const uint8_t* d_buf, size_t* n, int format, int* fastq, hipStream_t st, bool status_when_empty,
+                      const std::function<int(size_t n, int fastq)>& queue) {
+    *fastq = format == BSK_FORMAT_FASTQ;
+    int rc = build_index(c, d_buf, *n, format, st);
+    for (int attempt = 0;; ++attempt) {
+        if (*fastq && !c->norm_active &&
+            (rc == BSK_ERR_MULTILINE_FASTQ || (rc != BSK_OK && (c->last_kernel_flags & STRICT_FASTQ_FLAGS)))) {
+            // FASTQ records on more than four lines (helper.go:252-269; at the head of the shard, or -- the strict reader
+            // complained -- further down): these operators print the record TEXT, wrapped as it stands, so the multi-line
+            // reader only says where the records begin and the text leaves like FASTA text does: from one record start to
+            // the next, minus the final newline
+            const std::string msg = c->last_error;
+            const int rc0 = rc;
+            size_t n_eff = *n;
+            HIP_TRYX(c, hipMemsetAsync(c->d_status, 0, 2 * sizeof(uint64_t), st));
+            rc = normalize_multiline_fastq(c, d_buf, *n, st, nullptr, &n_eff);
+            if (rc != BSK_OK) {
+                if (rc0 != BSK_ERR_MULTILINE_FASTQ) { c->set_error(msg); return rc0; }  // (not FASTQ either way: the first complaint stands)
+                return rc;
+            }
+            *fastq = 0;
+            *n = n_eff;
+        }
+        if (rc != BSK_OK) return rc;
+        if (c->table.n == 0 && !status_when_empty) return BSK_OK;
+        if (c->table.n && queue) {
+            rc = queue(*n, *fastq);
+            if (rc != BSK_OK) return rc;
+        }
+        uint64_t status = 0;
+        HIP_TRYX(c, hipMemcpyAsync(&status, c->d_status, sizeof status, hipMemcpyDeviceToHost, st));
+        HIP_TRYX(c, hipStreamSynchronize(st));
+        rc = kernel_error_to_status(c, status);
+        // (the index pass leaves its complaints in the status word: a shard that is wrapped behind its head is seen here)
+        if (rc != BSK_OK && attempt == 0 && *fastq && !c->norm_active && (status & STRICT_FASTQ_FLAGS)) continue;
+        return rc;
+    }
+}
+
 // ---- the segmented copy as a step (ops_host_internal.hpp)
 int seg_begin(bsk_ctx* c, uint64_t seg_words, uint64_t total, hipStream_t st) {
     int rc = grow(c, &c->d_seg_src, &c->seg_src_cap, seg_words, seg_words / 8 + 16);

@@ -68,7 +68,7 @@ void validate_records_opts(bsk_ctx* c);
 int range_resolve(bsk_ctx* c, int64_t n_records);
 void validate_sample_opts(bsk_ctx* c);
 int sample_resolve(bsk_ctx* c, uint64_t n_records);
-// shuffle in buckets of the draw (ops_host_next.cpp; include/bsk.h)
+// shuffle in buckets of the draw (ops_host_shuffle.cpp; include/bsk.h)
 int shuffle_hist_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st, uint64_t* n_records);
 int shuffle_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records);
 int shuffle_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin);

@@ -1,4 +1,4 @@
-// Internal to the host side of libbsk (ops_host.cpp, ops_host_next.cpp): scratch helpers and the pieces of the
+// Internal to the host side of libbsk (the ops_host*.cpp files): scratch helpers and the pieces of the
 // seq-style "size -> scan -> emit" flow that several operators share.  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -89,6 +90,36 @@ int check_u32_records(bsk_ctx* c, const char* op);  // 32-bit permutations: 2^32
 int group_index(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, const char* op, hipStream_t st, TextTableH* tt, RmDupParams* P);
 int group_by_key(bsk_ctx* c, const uint8_t* d_buf, size_t n, const TextTableH& tt, const RmDupParams& P, uint8_t* d_has, hipStream_t st);
 int group_status(bsk_ctx* c, hipStream_t st, const uint64_t* d_extra = nullptr, uint64_t* extra = nullptr);
+// The prologue of an operator that prints the record TEXT (range / head, duplicate, sample, shuffle and its bucket passes):
+//   index_record_text   before: the shard and its format.  After: c->table; *fastq and *n are what the size kernels take -- a
+//                 FASTQ shard whose records are wrapped (at its head, or the strict reader complained) is read by the
+//                 multi-line reader and leaves as text from one record start to the next: *fastq = 0, *n = the byte behind
+//                 the last record; a shard that is FASTQ under neither reader keeps the strict reader's complaint.  Then
+//                 `queue(*n, *fastq)` -- the caller's size kernels and asynchronous read-backs -- has run, and the ONE
+//                 synchronisation of the step has brought back its words and the status word, which is checked; complaints
+//                 of the strict reader that show only there cost one retry (multi-line reader, `queue` again).
+//                 An empty table (the caller looks at c->table.n): `queue` is not called, and nothing is read back -- the
+//                 caller ends with empty_result, which reads the status -- unless `status_when_empty`: then the status is
+//                 read and checked like that of any other shard (the histogram pass, which has no result to end with).
+int index_record_text(bsk_ctx* c, const uint8_t* d_buf, size_t* n, int format, int* fastq, hipStream_t st, bool status_when_empty,
+                      const std::function<int(size_t n, int fastq)>& queue);
+// shuffle: `N` records -- record i = len[i] bytes (text + '\n') at text + off[i], inside text[0, extent), `total` bytes in all --
+// leave in ascending order of their draws: one 64-bit radix sort with counting values, segment j = record perm[j], scan, the
+// segmented copy (segcopy=off: byte by byte).  draws == null: draw(Seed, i), written here (stage stage_keys); the sort is
+// stage_sort.  check_newline: a record may lack its '\n' in the text (the last one of a shard) and gets it in the output.
+// stage_segments brackets the segment kernel alone, stage_emit (either may be null) everything from that kernel on.  The
+// arena is carved here, in one reservation; the synchronisation is the one of seg_run (segcopy=off: none).
+struct ShuffleRecords {
+    const uint8_t* text; uint64_t extent;
+    const uint64_t* off; const uint32_t* len;
+    uint64_t N, total;
+    const uint64_t* draws;
+    bool check_newline;
+    const char *stage_keys, *stage_sort, *stage_segments, *stage_emit;
+};
+int shuffle_order_emit(bsk_ctx* c, const ShuffleRecords& R, hipStream_t st, bsk_out* out);
+// the temporary-storage query of a rocPRIM sort (the *_temp_bytes functions of ops_sort / ops_group / ops_sample)
+int sort_query(bsk_ctx* c, hipError_t e);
 // FASTA text view of the shard's records (text_dev.hpp); null pointers for FASTQ
 int prepare_text(bsk_ctx* c, const uint8_t* d_buf, int format, hipStream_t st, TextTableH* tt, bool flatten = false,
                  bool keep_out_len = false, uint64_t buf_n = 0);  // buf_n: bytes in the shard (flatten: bounds its wide loads)

@@ -11,7 +11,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include <type_traits>
 #include <unordered_set>
 #include <vector>
 
@@ -33,8 +32,7 @@
 
 namespace bsk {
 
-// the temporary-storage query of a rocPRIM sort (the *_temp_bytes functions of ops_sort / ops_group / ops_sample)
-static int sort_query(bsk_ctx* c, hipError_t e) {
+int sort_query(bsk_ctx* c, hipError_t e) {
     if (e == hipSuccess) return BSK_OK;
     c->set_error("libbsk: rocPRIM sort size query failed");
     return BSK_ERR_HIP;
@@ -168,53 +166,6 @@ int fq2fa_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hip
     return emit_sized(c, d_buf, n, P, st, out);
 }
 
-// shuffle: the records in ascending order of their draws -- keys, one radix sort, the segments of the copy in that order
-static int shuffle_emit(bsk_ctx* c, const uint8_t* d_buf, size_t n, uint64_t total, hipStream_t st, bsk_out* out) {
-    const RecordTable& t = c->table;
-    const uint64_t N = t.n;
-    size_t tmp_bytes = 0;
-    int rc = sort_query(c, sort_pairs_bits_iota_temp_bytes(N, 0, 64, &tmp_bytes));
-    if (rc != BSK_OK) return rc;
-    Arena A;
-    const uint64_t o_keys = A.take(2 * N * 8), o_perm = A.take(N * 4), o_len = A.take(N * 4), o_off = A.take((N + 1) * 8),
-                   o_tmp = A.take(tmp_bytes ? tmp_bytes : 16);
-    rc = arena_reserve(c, &A);
-    if (rc != BSK_OK) return rc;
-    uint64_t* keys = A.at<uint64_t>(o_keys);
-    uint32_t* perm = A.at<uint32_t>(o_perm);
-    uint32_t* len_perm = A.at<uint32_t>(o_len);
-    uint64_t* seg_off = A.at<uint64_t>(o_off);
-    rc = seg_begin(c, N, total, st);
-    if (rc != BSK_OK) return rc;
-    rc = ensure_out(c, total);
-    if (rc != BSK_OK) return rc;
-    {
-        Timed tm(c, "k_shuffle_keys", st);
-        HIP_TRYX(c, launch_shuffle_keys(N, c->opts.i("Seed"), keys, st));
-    }
-    {
-        Timed tm(c, "radix_sort", st);  // (the values are 0 .. N - 1: no iota array is written or read)
-        HIP_TRYX(c, launch_sort_pairs_bits_iota(A.at<uint8_t>(o_tmp), tmp_bytes, keys, keys + N, perm, N, 0, 64, st));
-    }
-    {
-        Timed tm(c, "k_shuffle_segments", st);
-        HIP_TRYX(c, launch_shuffle_segments(d_buf, n, t, c->d_out_len, perm, c->d_seg_src, len_perm, seg_other(c), st));
-    }
-    HIP_TRYX(c, launch_scan_u32(len_perm, seg_off, N, c->d_scan_tmp, st));
-    if (!segcopy_on(c)) {
-        HIP_TRYX(c, launch_shuffle_fix(d_buf, t, perm, len_perm, seg_off, c->d_seg_src, c->d_out, true, st));
-    } else {
-        uint64_t other = 0;
-        rc = seg_run(c, SegList{c->d_seg_src, seg_off, N, total}, c->d_out, d_buf, n, st, &other);
-        if (rc != BSK_OK) return rc;
-        if (other) HIP_TRYX(c, launch_shuffle_fix(d_buf, t, perm, len_perm, seg_off, c->d_seg_src, c->d_out, false, st));
-    }
-    out->d_data = c->d_out;
-    out->len = total;
-    out->records = N;
-    return BSK_OK;
-}
-
 // RangePrepare + RangeFilter (bigseqkit-lib/range.go:26-43), Duplicate.Call (duplicate.go:24-30); sample and shuffle
 // (PARITY.md SAMPLE, SHUF) take the same way: a size per record, the scan, the verbatim copy
 int records_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, bsk_out* out) {
@@ -244,52 +195,28 @@ int records_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, h
         P.hi = c->range_end;
         P.times = 1;
     }
-    int rc = build_index(c, d_buf, n, format, st);
-    uint64_t total = 0, kept = 0, status = 0;
-    for (int attempt = 0;; ++attempt) {
-        if (P.fastq && !c->norm_active &&
-            (rc == BSK_ERR_MULTILINE_FASTQ || (rc != BSK_OK && (c->last_kernel_flags & STRICT_FASTQ_FLAGS)))) {
-            // FASTQ records on more than four lines (helper.go:252-269; at the head of the shard, or -- the strict reader
-            // complained -- further down): these operators print the record TEXT, wrapped as it stands, so the multi-line
-            // reader only says where the records begin and the text leaves like FASTA text does: from one record start to
-            // the next, minus the final newline
-            const std::string msg = c->last_error;
-            const int rc0 = rc;
-            size_t n_eff = n;
-            HIP_TRYX(c, hipMemsetAsync(c->d_status, 0, 2 * sizeof(uint64_t), st));
-            rc = normalize_multiline_fastq(c, d_buf, n, st, nullptr, &n_eff);
-            if (rc != BSK_OK) {
-                if (rc0 != BSK_ERR_MULTILINE_FASTQ) { c->set_error(msg); return rc0; }  // (not FASTQ either way: the first complaint stands)
-                return rc;
-            }
-            P.fastq = 0;
-            n = n_eff;
-        }
-        if (rc != BSK_OK) return rc;
-        if (c->table.n == 0) return empty_result(c, out);
-        rc = ensure_record_scratch(c);
-        if (rc != BSK_OK) return rc;
+    uint64_t total = 0, kept = 0;
+    int rc = index_record_text(c, d_buf, &n, format, &P.fastq, st, false, [&](size_t n_eff, int fastq) -> int {
+        const int rs = ensure_record_scratch(c);
+        if (rs != BSK_OK) return rs;
         if (c->op == Op::Sample) {
             Timed tm(c, "k_sample_size", st);
-            const SampleParams S{P.fastq, c->sample_next, c->opts.i("Seed"), c->sample_threshold};
-            HIP_TRYX(c, launch_sample_size(d_buf, n, c->table, S, c->d_out_len, c->d_status, st));
+            SampleParams S{fastq, c->sample_next, c->opts.i("Seed"), 0, 0};
+            sample_draw_interval(c->sample_threshold, &S.lo, &S.hi);
+            HIP_TRYX(c, launch_sample_size(d_buf, n_eff, c->table, S, c->d_out_len, nullptr, c->d_status, st));
         } else {
             Timed tm(c, "k_records_size", st);
-            HIP_TRYX(c, launch_records_size(d_buf, n, c->table, P, c->d_out_len, c->d_status, st));
+            HIP_TRYX(c, launch_records_size(d_buf, n_eff, c->table, P, c->d_out_len, c->d_status, st));  // (P.fastq: the effective one)
         }
         HIP_TRYX(c, launch_scan_u32(c->d_out_len, c->d_out_off, c->table.n, c->d_scan_tmp, st));
         HIP_TRYX(c, hipMemsetAsync(c->d_counter, 0, 4 * sizeof(uint64_t), st));
         HIP_TRYX(c, launch_count_nonzero(c->d_out_len, c->table.n, c->d_counter, st));
         HIP_TRYX(c, hipMemcpyAsync(&total, c->d_out_off + c->table.n, sizeof total, hipMemcpyDeviceToHost, st));
         HIP_TRYX(c, hipMemcpyAsync(&kept, c->d_counter, sizeof kept, hipMemcpyDeviceToHost, st));
-        HIP_TRYX(c, hipMemcpyAsync(&status, c->d_status, sizeof status, hipMemcpyDeviceToHost, st));
-        HIP_TRYX(c, hipStreamSynchronize(st));
-        rc = kernel_error_to_status(c, status);
-        // (the index pass leaves its complaints in the status word: a shard that is wrapped behind its head is seen here)
-        if (rc != BSK_OK && attempt == 0 && P.fastq && !c->norm_active && (status & STRICT_FASTQ_FLAGS)) continue;
-        if (rc != BSK_OK) return rc;
-        break;
-    }
+        return BSK_OK;
+    });
+    if (rc != BSK_OK) return rc;
+    if (c->table.n == 0) return empty_result(c, out);
     out->d_data = nullptr;
     out->len = 0;
     out->records = 0;
@@ -297,7 +224,9 @@ int records_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, h
     if (total == 0) return BSK_OK;
     if (c->op == Op::Shuffle) {
         rc = check_u32_records(c, "shuffle");  // 32-bit permutation
-        return rc != BSK_OK ? rc : shuffle_emit(c, d_buf, n, total, st, out);
+        if (rc != BSK_OK) return rc;
+        return shuffle_order_emit(c, ShuffleRecords{d_buf, n, c->table.start, c->d_out_len, c->table.n, total, nullptr, true,
+                                                    "k_shuffle_keys", "radix_sort", "k_shuffle_segments", nullptr}, st, out);
     }
     const bool segments = P.times == 1 && segcopy_on(c);
     // sample with out=slices: the kept records are verbatim pieces of the shard, in file order -- the segment list IS the result
@@ -354,290 +283,6 @@ int records_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, h
     out->len = total;
     out->records = kept * P.times;
     return BSK_OK;
-}
-
-// ---------------------------------------------------------------------------
-// shuffle in buckets of the draw (include/bsk.h; PARITY.md SHUF): the histogram pass, the collect pass of one bucket and its
-// finish.  The order of the output is the order of the draws, and a draw is a pure function of (seed, global record index),
-// so the records whose draws lie in one interval can be collected from the input piece by piece and sorted on their own.
-// ---------------------------------------------------------------------------
-// The record table of a shard for these passes, with the multi-line FASTQ fallback of records_run_device: wrapped records
-// leave as the text from one record start to the next (*fastq = 0, *n = the byte behind the last record).
-static bool shuffle_wrapped(const bsk_ctx* c, int fastq, int rc) {
-    return fastq && !c->norm_active && (rc == BSK_ERR_MULTILINE_FASTQ || (rc != BSK_OK && (c->last_kernel_flags & STRICT_FASTQ_FLAGS)));
-}
-
-static int shuffle_to_multiline(bsk_ctx* c, const uint8_t* d_buf, size_t* n, int* fastq, int* rc, hipStream_t st) {
-    const std::string msg = c->last_error;
-    const int rc0 = *rc;
-    size_t n_eff = *n;
-    HIP_TRYX(c, hipMemsetAsync(c->d_status, 0, 2 * sizeof(uint64_t), st));
-    *rc = normalize_multiline_fastq(c, d_buf, *n, st, nullptr, &n_eff);
-    if (*rc != BSK_OK) {
-        if (rc0 != BSK_ERR_MULTILINE_FASTQ) { c->set_error(msg); *rc = rc0; }  // (not FASTQ either way: the first complaint stands)
-        return *rc;
-    }
-    *fastq = 0;
-    *n = n_eff;
-    return BSK_OK;
-}
-
-static int shuffle_hist_alloc(bsk_ctx* c, hipStream_t st) {
-    if (c->shb.d_hist) return BSK_OK;
-    HIP_TRYX(c, hipMalloc((void**)&c->shb.d_hist, 2 * SHUFFLE_BINS * sizeof(uint64_t)));
-    HIP_TRYX(c, hipMemsetAsync(c->shb.d_hist, 0, 2 * SHUFFLE_BINS * sizeof(uint64_t), st));
-    return BSK_OK;
-}
-
-int shuffle_hist_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st, uint64_t* n_records) {
-    c->last_kernel_flags = 0;
-    int fastq = format == BSK_FORMAT_FASTQ;
-    int rc = shuffle_hist_alloc(c, st);
-    if (rc != BSK_OK) return rc;
-    rc = build_index(c, d_buf, n, format, st);
-    // the counters accumulate, so the index pass's complaints (a shard that is wrapped behind its head) are read BEFORE the
-    // histogram kernel runs: this is the one synchronisation of the pass, nothing is read back after the kernel
-    for (int attempt = 0;; ++attempt) {
-        if (shuffle_wrapped(c, fastq, rc)) {
-            if (shuffle_to_multiline(c, d_buf, &n, &fastq, &rc, st) != BSK_OK) return rc;
-        }
-        if (rc != BSK_OK) return rc;
-        uint64_t status = 0;
-        HIP_TRYX(c, hipMemcpyAsync(&status, c->d_status, sizeof status, hipMemcpyDeviceToHost, st));
-        HIP_TRYX(c, hipStreamSynchronize(st));
-        rc = kernel_error_to_status(c, status);
-        if (rc != BSK_OK && attempt == 0 && fastq && !c->norm_active && (status & STRICT_FASTQ_FLAGS)) continue;
-        if (rc != BSK_OK) return rc;
-        break;
-    }
-    if (n_records) *n_records = c->table.n;
-    if (c->table.n == 0) return BSK_OK;
-    Timed tm(c, "k_shuffle_hist", st);
-    HIP_TRYX(c, launch_shuffle_hist(d_buf, n, c->table, fastq, first_record, c->opts.i("Seed"), c->shb.d_hist, c->shb.d_hist + SHUFFLE_BINS,
-                                    c->num_cus, st));
-    return BSK_OK;
-}
-
-int shuffle_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) {
-    int rc = shuffle_hist_alloc(c, nullptr);
-    if (rc != BSK_OK) return rc;
-    HIP_TRYX(c, hipDeviceSynchronize());
-    if (bytes) HIP_TRYX(c, hipMemcpy(bytes, c->shb.d_hist, SHUFFLE_BINS * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (records) HIP_TRYX(c, hipMemcpy(records, c->shb.d_hist + SHUFFLE_BINS, SHUFFLE_BINS * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    return BSK_OK;
-}
-
-// the accumulation for `bytes` bytes and `recs` records; what it holds moves along when it has to grow
-static int shuffle_acc_reserve(bsk_ctx* c, uint64_t bytes, uint64_t recs, hipStream_t st) {
-    bsk_ctx::ShuffleBuckets& B = c->shb;
-    auto regrow = [&](auto** p, uint64_t used, uint64_t cap) -> int {
-        using T = std::remove_reference_t<decltype(**p)>;
-        T* nb = nullptr;
-        HIP_TRYX(c, hipMalloc((void**)&nb, std::max<uint64_t>(cap, 1) * sizeof(T)));
-        if (*p && used) HIP_TRYX(c, hipMemcpyAsync(nb, *p, used * sizeof(T), hipMemcpyDeviceToDevice, st));
-        HIP_TRYX(c, hipStreamSynchronize(st));
-        if (*p) HIP_TRYX(c, hipFree(*p));
-        *p = nb;
-        return BSK_OK;
-    };
-    int rc = BSK_OK;
-    if (bytes > B.acc_cap || !B.d_acc) {
-        const uint64_t cap = bytes + bytes / 4 + 4096;
-        rc = regrow(&B.d_acc, B.acc_used, cap);
-        if (rc != BSK_OK) return rc;
-        B.acc_cap = cap;
-    }
-    if (recs > B.rec_cap || !B.d_draw) {
-        const uint64_t cap = recs + recs / 4 + 256;
-        rc = regrow(&B.d_draw, B.n, cap);
-        if (rc == BSK_OK) rc = regrow(&B.d_off, B.n, cap);
-        if (rc == BSK_OK) rc = regrow(&B.d_len, B.n, cap);
-        if (rc != BSK_OK) return rc;
-        B.rec_cap = cap;
-    }
-    return BSK_OK;
-}
-
-static void shuffle_bucket_close(bsk_ctx* c) {
-    c->shb.open = false;
-    c->shb.n = 0;
-    c->shb.acc_used = 0;
-}
-
-int shuffle_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin) {
-    bsk_ctx::ShuffleBuckets& B = c->shb;
-    if (B.open) {
-        c->set_error("libbsk: bsk_shuffle_bucket_begin: a bucket is open (bsk_shuffle_bucket_finish ends it)");
-        return BSK_ERR_INVALID_ARG;
-    }
-    B.lo = (uint64_t)lo_bin << SHUFFLE_BIN_SHIFT;
-    B.hi = hi_bin >= SHUFFLE_BINS ? ~0ull : ((uint64_t)hi_bin << SHUFFLE_BIN_SHIFT) - 1;
-    B.n = 0;
-    B.acc_used = 0;
-    if (B.d_hist) {
-        // the histogram of this context says what the bucket will hold: the accumulation is allocated once (every shard's
-        // share begins on a 256-byte boundary; a shard more than expected grows it)
-        std::vector<uint64_t> h(2 * SHUFFLE_BINS);
-        HIP_TRYX(c, hipDeviceSynchronize());
-        HIP_TRYX(c, hipMemcpy(h.data(), B.d_hist, h.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        uint64_t bytes = 0, recs = 0;
-        for (uint32_t b = lo_bin; b < hi_bin; ++b) { bytes += h[b]; recs += h[SHUFFLE_BINS + b]; }
-        if (recs >= (1ull << 32)) {
-            c->set_error("libbsk: shuffle: 2^32 or more records in one bucket are not supported (a smaller budget makes more buckets)");
-            return BSK_ERR_UNSUPPORTED;
-        }
-        if (recs) {
-            const int rc = shuffle_acc_reserve(c, bytes + 16 * 256, recs, nullptr);
-            if (rc != BSK_OK) return rc;
-        }
-    }
-    B.open = true;
-    return BSK_OK;
-}
-
-static int shuffle_bucket_add_open(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st) {
-    bsk_ctx::ShuffleBuckets& B = c->shb;
-    c->last_kernel_flags = 0;
-    int fastq = format == BSK_FORMAT_FASTQ;
-    const int64_t seed = c->opts.i("Seed");
-    int rc = build_index(c, d_buf, n, format, st);
-    uint64_t total = 0, kept = 0, status = 0, N = 0;
-    Arena A;
-    uint32_t* keep = nullptr;
-    uint64_t* keep_off = nullptr;
-    for (int attempt = 0;; ++attempt) {
-        if (shuffle_wrapped(c, fastq, rc)) {
-            if (shuffle_to_multiline(c, d_buf, &n, &fastq, &rc, st) != BSK_OK) return rc;
-        }
-        if (rc != BSK_OK) return rc;
-        N = c->table.n;
-        if (N == 0) {
-            bsk_out none;
-            return empty_result(c, &none);
-        }
-        rc = ensure_record_scratch(c);
-        if (rc != BSK_OK) return rc;
-        A = Arena();
-        const uint64_t o_keep = A.take(N * 4), o_koff = A.take((N + 1) * 8);
-        rc = arena_reserve(c, &A);
-        if (rc != BSK_OK) return rc;
-        keep = A.at<uint32_t>(o_keep);
-        keep_off = A.at<uint64_t>(o_koff);
-        {
-            Timed tm(c, "k_shuffle_pick", st);
-            HIP_TRYX(c, launch_shuffle_pick(d_buf, n, c->table, fastq, first_record, seed, B.lo, B.hi, c->d_out_len, keep, c->d_status, st));
-        }
-        HIP_TRYX(c, launch_scan_u32(c->d_out_len, c->d_out_off, N, c->d_scan_tmp, st));
-        HIP_TRYX(c, launch_scan_u32(keep, keep_off, N, c->d_scan_tmp, st));
-        HIP_TRYX(c, hipMemcpyAsync(&total, c->d_out_off + N, sizeof total, hipMemcpyDeviceToHost, st));
-        HIP_TRYX(c, hipMemcpyAsync(&kept, keep_off + N, sizeof kept, hipMemcpyDeviceToHost, st));
-        HIP_TRYX(c, hipMemcpyAsync(&status, c->d_status, sizeof status, hipMemcpyDeviceToHost, st));
-        HIP_TRYX(c, hipStreamSynchronize(st));
-        rc = kernel_error_to_status(c, status);
-        if (rc != BSK_OK && attempt == 0 && fastq && !c->norm_active && (status & STRICT_FASTQ_FLAGS)) continue;
-        if (rc != BSK_OK) return rc;
-        break;
-    }
-    if (kept == 0) return BSK_OK;
-    if (B.n + kept >= (1ull << 32)) {
-        c->set_error("libbsk: shuffle: 2^32 or more records in one bucket are not supported (a smaller budget makes more buckets)");
-        return BSK_ERR_UNSUPPORTED;
-    }
-    const uint64_t at = (B.acc_used + 255) & ~255ull;  // (the segmented copy stores aligned 16-byte words)
-    rc = shuffle_acc_reserve(c, at + total, B.n + kept, st);
-    if (rc != BSK_OK) return rc;
-    uint8_t* dst = B.d_acc + at;
-    rc = seg_begin(c, N, total, st);
-    if (rc != BSK_OK) return rc;
-    if (!segcopy_on(c)) {
-        // every kept record byte by byte: the fix-up kernel writes the records whose source is 0
-        HIP_TRYX(c, hipMemsetAsync(c->d_seg_src, 0, N * sizeof(uint64_t), st));
-        HIP_TRYX(c, launch_seg_fix_text(d_buf, c->table, c->d_out_len, c->d_out_off, c->d_seg_src, dst, st));
-    } else {
-        {
-            Timed tm(c, "k_seg_prep", st);
-            HIP_TRYX(c, launch_seg_build_text(d_buf, n, c->table, c->d_out_len, c->d_seg_src, seg_other(c), st));
-        }
-        uint64_t other = 0;
-        rc = seg_run(c, SegList{c->d_seg_src, c->d_out_off, N, total}, dst, d_buf, n, st, &other);
-        if (rc != BSK_OK) return rc;
-        // a last record of the input without its newline gets one here: in the output it can land anywhere
-        if (other) HIP_TRYX(c, launch_seg_fix_text(d_buf, c->table, c->d_out_len, c->d_out_off, c->d_seg_src, dst, st));
-    }
-    HIP_TRYX(c, launch_shuffle_append(N, first_record, seed, c->d_out_len, c->d_out_off, keep_off, B.n, at, B.d_draw, B.d_off, B.d_len, st));
-    B.acc_used = at + total;
-    B.n += kept;
-    return BSK_OK;
-}
-
-int shuffle_bucket_add(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st) {
-    if (!c->shb.open) {
-        c->set_error("libbsk: bsk_shuffle_bucket_add: no bucket is open (bsk_shuffle_bucket_begin first)");
-        return BSK_ERR_INVALID_ARG;
-    }
-    const int rc = shuffle_bucket_add_open(c, d_buf, n, format, first_record, st);
-    if (rc != BSK_OK) shuffle_bucket_close(c);
-    return rc;
-}
-
-static int shuffle_bucket_emit(bsk_ctx* c, hipStream_t st, bsk_out* out) {
-    bsk_ctx::ShuffleBuckets& B = c->shb;
-    const uint64_t N = B.n;
-    out->d_data = nullptr;
-    out->len = 0;
-    out->records = 0;
-    if (N == 0) return BSK_OK;
-    size_t tmp_bytes = 0;
-    int rc = sort_query(c, sort_pairs_bits_iota_temp_bytes(N, 0, 64, &tmp_bytes));
-    if (rc != BSK_OK) return rc;
-    Arena A;
-    const uint64_t o_keys = A.take(N * 8), o_perm = A.take(N * 4), o_len = A.take(N * 4), o_off = A.take((N + 1) * 8),
-                   o_tmp = A.take(tmp_bytes ? tmp_bytes : 16);
-    rc = arena_reserve(c, &A);
-    if (rc != BSK_OK) return rc;
-    uint32_t* perm = A.at<uint32_t>(o_perm);
-    uint32_t* len_perm = A.at<uint32_t>(o_len);
-    uint64_t* seg_off = A.at<uint64_t>(o_off);
-    {
-        Timed tm(c, "shuffle_bucket_sort", st);  // (the values are 0 .. N - 1: no iota array is written or read)
-        HIP_TRYX(c, launch_sort_pairs_bits_iota(A.at<uint8_t>(o_tmp), tmp_bytes, B.d_draw, A.at<uint64_t>(o_keys), perm, N, 0, 64, st));
-    }
-    // the bytes of the bucket are the sum of its lengths whatever their order; the tiles of the copy are sized for it
-    uint64_t total = 0;
-    rc = grow(c, &c->d_scan_tmp, &c->scan_tmp_cap, 3 * ((N + 2047) / 2048) + 6, 16);  // (as ensure_record_scratch sizes it)
-    if (rc != BSK_OK) return rc;
-    rc = grow(c, &c->d_seg_src, &c->seg_src_cap, N, N / 8 + 16);
-    if (rc != BSK_OK) return rc;
-    Timed tm(c, "shuffle_bucket_copy", st);
-    HIP_TRYX(c, launch_shuffle_bucket_segments(N, B.d_acc, B.d_off, B.d_len, perm, c->d_seg_src, len_perm, st));
-    HIP_TRYX(c, launch_scan_u32(len_perm, seg_off, N, c->d_scan_tmp, st));
-    HIP_TRYX(c, hipMemcpyAsync(&total, seg_off + N, sizeof total, hipMemcpyDeviceToHost, st));
-    HIP_TRYX(c, hipStreamSynchronize(st));
-    rc = ensure_out(c, total);
-    if (rc != BSK_OK) return rc;
-    if (!segcopy_on(c)) {
-        HIP_TRYX(c, launch_shuffle_bucket_bytes(N, c->d_seg_src, seg_off, c->d_out, st));
-    } else {
-        rc = seg_begin(c, N, total, st);
-        if (rc != BSK_OK) return rc;
-        uint64_t other = 0;
-        rc = seg_run(c, SegList{c->d_seg_src, seg_off, N, total}, c->d_out, B.d_acc, B.acc_used, st, &other);
-        if (rc != BSK_OK) return rc;
-    }
-    out->d_data = c->d_out;
-    out->len = total;
-    out->records = N;
-    return BSK_OK;
-}
-
-int shuffle_bucket_finish(bsk_ctx* c, hipStream_t st, bsk_out* out) {
-    if (!c->shb.open) {
-        c->set_error("libbsk: bsk_shuffle_bucket_finish: no bucket is open (bsk_shuffle_bucket_begin first)");
-        return BSK_ERR_INVALID_ARG;
-    }
-    const int rc = shuffle_bucket_emit(c, st, out);
-    shuffle_bucket_close(c);
-    return rc;
 }
 
 // ---------------------------------------------------------------------------

@@ -1,0 +1,280 @@
+// Host side of `shuffle` (PARITY.md SHUF): the order-and-emit that the one-pass shuffle (records_run_device, ops_host_next.cpp)
+// and the finish of a bucket share, and the passes of the shuffle in buckets of the draw.  The kernels are in ops_sample.hip.
+#include <hip/hip_runtime_api.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <optional>
+#include <type_traits>
+#include <vector>
+
+#include "../../include/bsk.h"
+#include "ctx.hpp"
+#include "ops_host.hpp"
+#include "ops_host_internal.hpp"
+#include "ops_records.hpp"
+#include "ops_sample.hpp"
+#include "ops_segcopy.hpp"
+#include "ops_sort.hpp"
+
+namespace bsk {
+
+// (ops_host_internal.hpp)
+int shuffle_order_emit(bsk_ctx* c, const ShuffleRecords& R, hipStream_t st, bsk_out* out) {
+    const uint64_t N = R.N;
+    out->d_data = nullptr;
+    out->len = 0;
+    out->records = 0;
+    if (N == 0) return BSK_OK;
+    size_t tmp_bytes = 0;
+    int rc = sort_query(c, sort_pairs_bits_iota_temp_bytes(N, 0, 64, &tmp_bytes));
+    if (rc != BSK_OK) return rc;
+    Arena A;
+    const uint64_t o_sorted = A.take(N * 8), o_perm = A.take(N * 4), o_len = A.take(N * 4), o_off = A.take((N + 1) * 8),
+                   o_tmp = A.take(tmp_bytes ? tmp_bytes : 16), o_keys = A.take(R.draws ? 0 : N * 8);
+    rc = arena_reserve(c, &A);
+    if (rc != BSK_OK) return rc;
+    uint32_t* perm = A.at<uint32_t>(o_perm);
+    uint32_t* len_perm = A.at<uint32_t>(o_len);
+    uint64_t* seg_off = A.at<uint64_t>(o_off);
+    // the scan of N lengths: N need not be the record count of c->table that ensure_record_scratch sized the scratch for
+    rc = grow(c, &c->d_scan_tmp, &c->scan_tmp_cap, 3 * ((N + 2047) / 2048) + 6, 16);
+    if (rc != BSK_OK) return rc;
+    rc = seg_begin(c, N, R.total, st);
+    if (rc != BSK_OK) return rc;
+    rc = ensure_out(c, R.total);
+    if (rc != BSK_OK) return rc;
+    const uint64_t* draws = R.draws;
+    if (!draws) {
+        Timed tm(c, R.stage_keys, st);
+        HIP_TRYX(c, launch_shuffle_keys(N, c->opts.i("Seed"), A.at<uint64_t>(o_keys), st));
+        draws = A.at<uint64_t>(o_keys);
+    }
+    {
+        Timed tm(c, R.stage_sort, st);  // (the values are 0 .. N - 1: no iota array is written or read)
+        HIP_TRYX(c, launch_sort_pairs_bits_iota(A.at<uint8_t>(o_tmp), tmp_bytes, draws, A.at<uint64_t>(o_sorted), perm, N, 0, 64, st));
+    }
+    std::optional<Timed> emit;
+    if (R.stage_emit) emit.emplace(c, R.stage_emit, st);
+    {
+        std::optional<Timed> tm;
+        if (R.stage_segments) tm.emplace(c, R.stage_segments, st);
+        HIP_TRYX(c, launch_shuffle_segments(N, R.text, R.extent, R.off, R.len, perm, c->d_seg_src, len_perm,
+                                            R.check_newline ? seg_other(c) : nullptr, st));
+    }
+    HIP_TRYX(c, launch_scan_u32(len_perm, seg_off, N, c->d_scan_tmp, st));
+    if (!segcopy_on(c)) {
+        HIP_TRYX(c, launch_shuffle_fix(N, R.text, R.off, perm, len_perm, seg_off, c->d_seg_src, c->d_out, true, st));
+    } else {
+        uint64_t other = 0;
+        rc = seg_run(c, SegList{c->d_seg_src, seg_off, N, R.total}, c->d_out, R.text, R.extent, st, &other);
+        if (rc != BSK_OK) return rc;
+        if (other) HIP_TRYX(c, launch_shuffle_fix(N, R.text, R.off, perm, len_perm, seg_off, c->d_seg_src, c->d_out, false, st));
+    }
+    out->d_data = c->d_out;
+    out->len = R.total;
+    out->records = N;
+    return BSK_OK;
+}
+
+// ---------------------------------------------------------------------------
+// shuffle in buckets of the draw (include/bsk.h; PARITY.md SHUF): the histogram pass, the collect pass of one bucket and its
+// finish.  The order of the output is the order of the draws, and a draw is a pure function of (seed, global record index),
+// so the records whose draws lie in one interval can be collected from the input piece by piece and sorted on their own.
+// ---------------------------------------------------------------------------
+static int shuffle_hist_alloc(bsk_ctx* c, hipStream_t st) {
+    if (c->shb.d_hist) return BSK_OK;
+    HIP_TRYX(c, hipMalloc((void**)&c->shb.d_hist, 2 * SHUFFLE_BINS * sizeof(uint64_t)));
+    HIP_TRYX(c, hipMemsetAsync(c->shb.d_hist, 0, 2 * SHUFFLE_BINS * sizeof(uint64_t), st));
+    return BSK_OK;
+}
+
+int shuffle_hist_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st, uint64_t* n_records) {
+    c->last_kernel_flags = 0;
+    int fastq = 0;
+    int rc = shuffle_hist_alloc(c, st);
+    if (rc != BSK_OK) return rc;
+    // the counters accumulate, so the index pass's complaints (a shard that is wrapped behind its head) are read BEFORE the
+    // histogram kernel runs -- of an empty table too: this is the one synchronisation of the pass, nothing is read back after
+    // the kernel
+    rc = index_record_text(c, d_buf, &n, format, &fastq, st, true, nullptr);
+    if (rc != BSK_OK) return rc;
+    if (n_records) *n_records = c->table.n;
+    if (c->table.n == 0) return BSK_OK;
+    Timed tm(c, "k_shuffle_hist", st);
+    HIP_TRYX(c, launch_shuffle_hist(d_buf, n, c->table, fastq, first_record, c->opts.i("Seed"), c->shb.d_hist, c->shb.d_hist + SHUFFLE_BINS,
+                                    c->num_cus, st));
+    return BSK_OK;
+}
+
+int shuffle_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) {
+    int rc = shuffle_hist_alloc(c, nullptr);
+    if (rc != BSK_OK) return rc;
+    HIP_TRYX(c, hipDeviceSynchronize());
+    if (bytes) HIP_TRYX(c, hipMemcpy(bytes, c->shb.d_hist, SHUFFLE_BINS * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (records) HIP_TRYX(c, hipMemcpy(records, c->shb.d_hist + SHUFFLE_BINS, SHUFFLE_BINS * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return BSK_OK;
+}
+
+// the accumulation for `bytes` bytes and `recs` records; what it holds moves along when it has to grow
+static int shuffle_acc_reserve(bsk_ctx* c, uint64_t bytes, uint64_t recs, hipStream_t st) {
+    bsk_ctx::ShuffleBuckets& B = c->shb;
+    auto regrow = [&](auto** p, uint64_t used, uint64_t cap) -> int {
+        using T = std::remove_reference_t<decltype(**p)>;
+        T* nb = nullptr;
+        HIP_TRYX(c, hipMalloc((void**)&nb, std::max<uint64_t>(cap, 1) * sizeof(T)));
+        if (*p && used) HIP_TRYX(c, hipMemcpyAsync(nb, *p, used * sizeof(T), hipMemcpyDeviceToDevice, st));
+        HIP_TRYX(c, hipStreamSynchronize(st));
+        if (*p) HIP_TRYX(c, hipFree(*p));
+        *p = nb;
+        return BSK_OK;
+    };
+    int rc = BSK_OK;
+    if (bytes > B.acc_cap || !B.d_acc) {
+        const uint64_t cap = bytes + bytes / 4 + 4096;
+        rc = regrow(&B.d_acc, B.acc_used, cap);
+        if (rc != BSK_OK) return rc;
+        B.acc_cap = cap;
+    }
+    if (recs > B.rec_cap || !B.d_draw) {
+        const uint64_t cap = recs + recs / 4 + 256;
+        rc = regrow(&B.d_draw, B.n, cap);
+        if (rc == BSK_OK) rc = regrow(&B.d_off, B.n, cap);
+        if (rc == BSK_OK) rc = regrow(&B.d_len, B.n, cap);
+        if (rc != BSK_OK) return rc;
+        B.rec_cap = cap;
+    }
+    return BSK_OK;
+}
+
+static void shuffle_bucket_close(bsk_ctx* c) {
+    c->shb.open = false;
+    c->shb.n = 0;
+    c->shb.acc_used = 0;
+    c->shb.total = 0;
+}
+
+int shuffle_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin) {
+    bsk_ctx::ShuffleBuckets& B = c->shb;
+    if (B.open) {
+        c->set_error("libbsk: bsk_shuffle_bucket_begin: a bucket is open (bsk_shuffle_bucket_finish ends it)");
+        return BSK_ERR_INVALID_ARG;
+    }
+    B.lo = (uint64_t)lo_bin << SHUFFLE_BIN_SHIFT;
+    B.hi = hi_bin >= SHUFFLE_BINS ? ~0ull : ((uint64_t)hi_bin << SHUFFLE_BIN_SHIFT) - 1;
+    B.n = 0;
+    B.acc_used = 0;
+    B.total = 0;
+    if (B.d_hist) {
+        // the histogram of this context says what the bucket will hold: the accumulation is allocated once (every shard's
+        // share begins on a 256-byte boundary; a shard more than expected grows it)
+        std::vector<uint64_t> h(2 * SHUFFLE_BINS);
+        HIP_TRYX(c, hipDeviceSynchronize());
+        HIP_TRYX(c, hipMemcpy(h.data(), B.d_hist, h.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        uint64_t bytes = 0, recs = 0;
+        for (uint32_t b = lo_bin; b < hi_bin; ++b) { bytes += h[b]; recs += h[SHUFFLE_BINS + b]; }
+        if (recs >= (1ull << 32)) {
+            c->set_error("libbsk: shuffle: 2^32 or more records in one bucket are not supported (a smaller budget makes more buckets)");
+            return BSK_ERR_UNSUPPORTED;
+        }
+        if (recs) {
+            const int rc = shuffle_acc_reserve(c, bytes + 16 * 256, recs, nullptr);
+            if (rc != BSK_OK) return rc;
+        }
+    }
+    B.open = true;
+    return BSK_OK;
+}
+
+static int shuffle_bucket_add_open(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st) {
+    bsk_ctx::ShuffleBuckets& B = c->shb;
+    c->last_kernel_flags = 0;
+    int fastq = 0;
+    const int64_t seed = c->opts.i("Seed");
+    uint64_t total = 0, kept = 0;
+    Arena A;
+    uint64_t* keep_off = nullptr;
+    int rc = index_record_text(c, d_buf, &n, format, &fastq, st, false, [&](size_t n_eff, int fastq_eff) -> int {
+        const uint64_t N = c->table.n;
+        const int rs = ensure_record_scratch(c);
+        if (rs != BSK_OK) return rs;
+        A = Arena();
+        const uint64_t o_keep = A.take(N * 4), o_koff = A.take((N + 1) * 8);
+        const int ra = arena_reserve(c, &A);
+        if (ra != BSK_OK) return ra;
+        uint32_t* keep = A.at<uint32_t>(o_keep);
+        keep_off = A.at<uint64_t>(o_koff);
+        {
+            Timed tm(c, "k_shuffle_pick", st);
+            HIP_TRYX(c, launch_sample_size(d_buf, n_eff, c->table, SampleParams{fastq_eff, first_record, seed, B.lo, B.hi}, c->d_out_len, keep,
+                                           c->d_status, st));
+        }
+        HIP_TRYX(c, launch_scan_u32(c->d_out_len, c->d_out_off, N, c->d_scan_tmp, st));
+        HIP_TRYX(c, launch_scan_u32(keep, keep_off, N, c->d_scan_tmp, st));
+        HIP_TRYX(c, hipMemcpyAsync(&total, c->d_out_off + N, sizeof total, hipMemcpyDeviceToHost, st));
+        HIP_TRYX(c, hipMemcpyAsync(&kept, keep_off + N, sizeof kept, hipMemcpyDeviceToHost, st));
+        return BSK_OK;
+    });
+    if (rc != BSK_OK) return rc;
+    const uint64_t N = c->table.n;
+    if (N == 0) {
+        bsk_out none;
+        return empty_result(c, &none);
+    }
+    if (kept == 0) return BSK_OK;
+    if (B.n + kept >= (1ull << 32)) {
+        c->set_error("libbsk: shuffle: 2^32 or more records in one bucket are not supported (a smaller budget makes more buckets)");
+        return BSK_ERR_UNSUPPORTED;
+    }
+    const uint64_t at = (B.acc_used + 255) & ~255ull;  // (the segmented copy stores aligned 16-byte words)
+    rc = shuffle_acc_reserve(c, at + total, B.n + kept, st);
+    if (rc != BSK_OK) return rc;
+    uint8_t* dst = B.d_acc + at;
+    rc = seg_begin(c, N, total, st);
+    if (rc != BSK_OK) return rc;
+    if (!segcopy_on(c)) {
+        // every kept record byte by byte: the fix-up kernel writes the records whose source is 0
+        HIP_TRYX(c, hipMemsetAsync(c->d_seg_src, 0, N * sizeof(uint64_t), st));
+        HIP_TRYX(c, launch_seg_fix_text(d_buf, c->table, c->d_out_len, c->d_out_off, c->d_seg_src, dst, st));
+    } else {
+        {
+            Timed tm(c, "k_seg_prep", st);
+            HIP_TRYX(c, launch_seg_build_text(d_buf, n, c->table, c->d_out_len, c->d_seg_src, seg_other(c), st));
+        }
+        uint64_t other = 0;
+        rc = seg_run(c, SegList{c->d_seg_src, c->d_out_off, N, total}, dst, d_buf, n, st, &other);
+        if (rc != BSK_OK) return rc;
+        // a last record of the input without its newline gets one here: in the output it can land anywhere
+        if (other) HIP_TRYX(c, launch_seg_fix_text(d_buf, c->table, c->d_out_len, c->d_out_off, c->d_seg_src, dst, st));
+    }
+    HIP_TRYX(c, launch_shuffle_append(N, first_record, seed, c->d_out_len, c->d_out_off, keep_off, B.n, at, B.d_draw, B.d_off, B.d_len, st));
+    B.acc_used = at + total;
+    B.total += total;
+    B.n += kept;
+    return BSK_OK;
+}
+
+int shuffle_bucket_add(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st) {
+    if (!c->shb.open) {
+        c->set_error("libbsk: bsk_shuffle_bucket_add: no bucket is open (bsk_shuffle_bucket_begin first)");
+        return BSK_ERR_INVALID_ARG;
+    }
+    const int rc = shuffle_bucket_add_open(c, d_buf, n, format, first_record, st);
+    if (rc != BSK_OK) shuffle_bucket_close(c);
+    return rc;
+}
+
+int shuffle_bucket_finish(bsk_ctx* c, hipStream_t st, bsk_out* out) {
+    if (!c->shb.open) {
+        c->set_error("libbsk: bsk_shuffle_bucket_finish: no bucket is open (bsk_shuffle_bucket_begin first)");
+        return BSK_ERR_INVALID_ARG;
+    }
+    const bsk_ctx::ShuffleBuckets& B = c->shb;
+    // the bytes of the bucket are the sum of what its shards added, whatever the order: nothing is read back for them
+    const int rc = shuffle_order_emit(c, ShuffleRecords{B.d_acc, B.acc_used, B.d_off, B.d_len, B.n, B.total, B.d_draw, false, nullptr,
+                                                        "shuffle_bucket_sort", nullptr, "shuffle_bucket_copy"}, st, out);
+    shuffle_bucket_close(c);
+    return rc;
+}
+
+}  // namespace bsk

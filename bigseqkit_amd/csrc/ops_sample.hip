@@ -12,18 +12,23 @@
 namespace bsk {
 namespace {
 
+// the verdict of a closed interval of the draw: out_len[i] = text + '\n' of record i when lo <= draw <= hi, else 0, and -- with a
+// keep array -- keep[i] = 1 / 0.  `sample` passes the interval of its threshold (sample_interval), a bucket of `shuffle` its own.
 __global__ __launch_bounds__(256) void k_sample_size(const uint8_t* __restrict__ buf, uint64_t buf_n, RecordTable t, int fastq,
-                                                     uint64_t first_record, uint64_t key, uint64_t threshold,
-                                                     uint32_t* __restrict__ out_len, uint64_t* __restrict__ status) {
+                                                     uint64_t first_record, uint64_t key, uint64_t lo, uint64_t hi,
+                                                     uint32_t* __restrict__ out_len, uint32_t* __restrict__ keep,
+                                                     uint64_t* __restrict__ status) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= t.n) return;
+    const uint64_t d = sample_draw(key, first_record + i);
     uint64_t bytes = 0;
-    if (sample_keeps(key, first_record + i, threshold)) bytes = record_text_len(buf, buf_n, t, fastq, i) + 1u;
+    if (lo <= d && d <= hi) bytes = record_text_len(buf, buf_n, t, fastq, i) + 1u;
     if (bytes > 0xFFFFFFFFull) {
         atomicOr((unsigned long long*)&status[0], (unsigned long long)ERR_RECORD_TOO_LARGE);
         bytes = 0;
     }
     out_len[i] = (uint32_t)bytes;
+    if (keep) keep[i] = bytes ? 1u : 0u;
 }
 
 __global__ __launch_bounds__(256) void k_shuffle_keys(uint64_t n, uint64_t key, uint64_t* __restrict__ keys) {
@@ -32,35 +37,41 @@ __global__ __launch_bounds__(256) void k_shuffle_keys(uint64_t n, uint64_t key, 
     keys[i] = sample_draw(key, i);
 }
 
-__global__ __launch_bounds__(256) void k_shuffle_segments(const uint8_t* __restrict__ buf, uint64_t buf_n, RecordTable t,
-                                                          const uint32_t* __restrict__ out_len, const uint32_t* __restrict__ perm,
-                                                          uint64_t* __restrict__ seg_src, uint32_t* __restrict__ len_perm,
-                                                          unsigned long long* __restrict__ n_other) {
+// segment j = record perm[j] of the n records (off[], len[]) that lie in base[0, extent).  With a counter n_other the byte
+// behind the text is looked at: a record that is not followed by its '\n' gets source 0 and is counted (k_shuffle_fix writes
+// it); without one (the texts of an accumulation all end in their newline) no text byte is read.
+__global__ __launch_bounds__(256) void k_shuffle_segments(uint64_t n, const uint8_t* __restrict__ base, uint64_t extent,
+                                                          const uint64_t* __restrict__ off, const uint32_t* __restrict__ len,
+                                                          const uint32_t* __restrict__ perm, uint64_t* __restrict__ seg_src,
+                                                          uint32_t* __restrict__ len_perm, unsigned long long* __restrict__ n_other) {
     const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= t.n) return;
+    if (j >= n) return;
     const uint32_t i = perm[j];
-    const uint32_t n = out_len[i];
+    const uint32_t m = len[i];
     uint64_t s = 0;
-    if (n) {
-        const uint64_t st = t.start[i];
-        if (st + n <= buf_n && buf[st + n - 1] == '\n') s = (uint64_t)(uintptr_t)(buf + st);
+    if (m) {
+        const uint64_t at = off[i];
+        if (!n_other || (at + m <= extent && base[at + m - 1] == '\n')) s = (uint64_t)(uintptr_t)(base + at);
         else atomicAdd(n_other, 1ull);  // the last record of a shard without a final newline
     }
     seg_src[j] = s;
-    len_perm[j] = n;
+    len_perm[j] = m;
 }
 
-__global__ __launch_bounds__(256) void k_shuffle_fix(const uint8_t* __restrict__ buf, RecordTable t, const uint32_t* __restrict__ perm,
-                                                     const uint32_t* __restrict__ len_perm, const uint64_t* __restrict__ seg_off,
-                                                     const uint64_t* __restrict__ seg_src, uint8_t* __restrict__ out, int all) {
+// segment j byte by byte: len_perm[j] - 1 bytes from base + off[perm[j]], then '\n'.  all = 0: only the segments the copy
+// left out (source 0)
+__global__ __launch_bounds__(256) void k_shuffle_fix(uint64_t n, const uint8_t* __restrict__ base, const uint64_t* __restrict__ off,
+                                                     const uint32_t* __restrict__ perm, const uint32_t* __restrict__ len_perm,
+                                                     const uint64_t* __restrict__ seg_off, const uint64_t* __restrict__ seg_src,
+                                                     uint8_t* __restrict__ out, int all) {
     const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= t.n) return;
-    const uint32_t n = len_perm[j];
-    if (n == 0 || (!all && seg_src[j] != 0)) return;
-    const uint8_t* s = buf + t.start[perm[j]];
+    if (j >= n) return;
+    const uint32_t m = len_perm[j];
+    if (m == 0 || (!all && seg_src[j] != 0)) return;
+    const uint8_t* s = base + off[perm[j]];
     uint8_t* o = out + seg_off[j];
-    for (uint32_t k = 0; k + 1 < n; ++k) o[k] = s[k];
-    o[n - 1] = (uint8_t)'\n';
+    for (uint32_t k = 0; k + 1 < m; ++k) o[k] = s[k];
+    o[m - 1] = (uint8_t)'\n';
 }
 
 // ---- shuffle in buckets of the draw (PARITY.md SHUF): the 64-bit draw range is cut into SHUFFLE_BINS fine bins, a bucket is a run
@@ -91,24 +102,6 @@ __global__ __launch_bounds__(256) void k_shuffle_hist(const uint8_t* __restrict_
     }
 }
 
-// the verdict of a bucket: out_len[i] = text + '\n' of record i when lo <= draw <= hi, else 0; keep[i] = 1 / 0
-__global__ __launch_bounds__(256) void k_shuffle_pick(const uint8_t* __restrict__ buf, uint64_t buf_n, RecordTable t, int fastq,
-                                                      uint64_t first_record, uint64_t key, uint64_t lo, uint64_t hi,
-                                                      uint32_t* __restrict__ out_len, uint32_t* __restrict__ keep,
-                                                      uint64_t* __restrict__ status) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= t.n) return;
-    const uint64_t d = sample_draw(key, first_record + i);
-    uint64_t bytes = 0;
-    if (lo <= d && d <= hi) bytes = record_text_len(buf, buf_n, t, fastq, i) + 1u;
-    if (bytes > 0xFFFFFFFFull) {
-        atomicOr((unsigned long long*)&status[0], (unsigned long long)ERR_RECORD_TOO_LARGE);
-        bytes = 0;
-    }
-    out_len[i] = (uint32_t)bytes;
-    keep[i] = bytes ? 1u : 0u;
-}
-
 // the kept records of the shard join the accumulation, in shard order: (draw, byte offset, length) at n0 + keep_off[i]
 __global__ __launch_bounds__(256) void k_shuffle_append(uint64_t n, uint64_t first_record, uint64_t key, const uint32_t* __restrict__ out_len,
                                                         const uint64_t* __restrict__ out_off, const uint64_t* __restrict__ keep_off,
@@ -124,36 +117,21 @@ __global__ __launch_bounds__(256) void k_shuffle_append(uint64_t n, uint64_t fir
     acc_len[j] = len;
 }
 
-// k_shuffle_segments over (offset, length) arrays instead of a record table: segment j = accumulated record perm[j]
-__global__ __launch_bounds__(256) void k_shuffle_bucket_segments(uint64_t n, const uint8_t* __restrict__ acc, const uint64_t* __restrict__ acc_off,
-                                                                 const uint32_t* __restrict__ acc_len, const uint32_t* __restrict__ perm,
-                                                                 uint64_t* __restrict__ seg_src, uint32_t* __restrict__ len_perm) {
-    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    const uint32_t i = perm[j];
-    seg_src[j] = (uint64_t)(uintptr_t)(acc + acc_off[i]);
-    len_perm[j] = acc_len[i];
-}
-
-// the path without the segmented copy: segment j byte by byte
-__global__ __launch_bounds__(256) void k_shuffle_bucket_bytes(uint64_t n, const uint64_t* __restrict__ seg_src, const uint64_t* __restrict__ seg_off,
-                                                              uint8_t* __restrict__ out) {
-    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    const uint8_t* s = (const uint8_t*)(uintptr_t)seg_src[j];
-    const uint64_t a = seg_off[j], b = seg_off[j + 1];
-    for (uint64_t k = a; k < b; ++k) out[k] = s[k - a];
-}
-
 inline dim3 grid_of(uint64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 }  // namespace
 
+void sample_draw_interval(uint64_t threshold, uint64_t* lo, uint64_t* hi) {
+    const DrawInterval I = sample_interval(threshold);
+    *lo = I.lo;
+    *hi = I.hi;
+}
+
 hipError_t launch_sample_size(const uint8_t* buf, uint64_t buf_n, const RecordTable& t, const SampleParams& P, uint32_t* out_len,
-                              uint64_t* status, hipStream_t st) {
+                              uint32_t* keep, uint64_t* status, hipStream_t st) {
     if (t.n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_sample_size, grid_of(t.n), dim3(256), 0, st, buf, buf_n, t, P.fastq, P.first_record, sample_key(P.seed),
-                       P.threshold, out_len, status);
+    hipLaunchKernelGGL(k_sample_size, grid_of(t.n), dim3(256), 0, st, buf, buf_n, t, P.fastq, P.first_record, sample_key(P.seed), P.lo,
+                       P.hi, out_len, keep, status);
     return hipGetLastError();
 }
 
@@ -163,18 +141,18 @@ hipError_t launch_shuffle_keys(uint64_t n, int64_t seed, uint64_t* keys, hipStre
     return hipGetLastError();
 }
 
-hipError_t launch_shuffle_segments(const uint8_t* buf, uint64_t buf_n, const RecordTable& t, const uint32_t* out_len,
+hipError_t launch_shuffle_segments(uint64_t n, const uint8_t* base, uint64_t extent, const uint64_t* off, const uint32_t* len,
                                    const uint32_t* perm, uint64_t* seg_src, uint32_t* len_perm, uint64_t* n_other, hipStream_t st) {
-    if (t.n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_shuffle_segments, grid_of(t.n), dim3(256), 0, st, buf, buf_n, t, out_len, perm, seg_src, len_perm,
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_shuffle_segments, grid_of(n), dim3(256), 0, st, n, base, extent, off, len, perm, seg_src, len_perm,
                        (unsigned long long*)n_other);
     return hipGetLastError();
 }
 
-hipError_t launch_shuffle_fix(const uint8_t* buf, const RecordTable& t, const uint32_t* perm, const uint32_t* len_perm,
+hipError_t launch_shuffle_fix(uint64_t n, const uint8_t* base, const uint64_t* off, const uint32_t* perm, const uint32_t* len_perm,
                               const uint64_t* seg_off, const uint64_t* seg_src, uint8_t* out, bool all, hipStream_t st) {
-    if (t.n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_shuffle_fix, grid_of(t.n), dim3(256), 0, st, buf, t, perm, len_perm, seg_off, seg_src, out, all ? 1 : 0);
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_shuffle_fix, grid_of(n), dim3(256), 0, st, n, base, off, perm, len_perm, seg_off, seg_src, out, all ? 1 : 0);
     return hipGetLastError();
 }
 
@@ -188,33 +166,12 @@ hipError_t launch_shuffle_hist(const uint8_t* buf, uint64_t buf_n, const RecordT
     return hipGetLastError();
 }
 
-hipError_t launch_shuffle_pick(const uint8_t* buf, uint64_t buf_n, const RecordTable& t, int fastq, uint64_t first_record, int64_t seed,
-                               uint64_t lo, uint64_t hi, uint32_t* out_len, uint32_t* keep, uint64_t* status, hipStream_t st) {
-    if (t.n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_shuffle_pick, grid_of(t.n), dim3(256), 0, st, buf, buf_n, t, fastq, first_record, sample_key(seed), lo, hi,
-                       out_len, keep, status);
-    return hipGetLastError();
-}
-
 hipError_t launch_shuffle_append(uint64_t n, uint64_t first_record, int64_t seed, const uint32_t* out_len, const uint64_t* out_off,
                                  const uint64_t* keep_off, uint64_t n0, uint64_t bytes0, uint64_t* acc_draw, uint64_t* acc_off,
                                  uint32_t* acc_len, hipStream_t st) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(k_shuffle_append, grid_of(n), dim3(256), 0, st, n, first_record, sample_key(seed), out_len, out_off, keep_off, n0,
                        bytes0, acc_draw, acc_off, acc_len);
-    return hipGetLastError();
-}
-
-hipError_t launch_shuffle_bucket_segments(uint64_t n, const uint8_t* acc, const uint64_t* acc_off, const uint32_t* acc_len,
-                                          const uint32_t* perm, uint64_t* seg_src, uint32_t* len_perm, hipStream_t st) {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_shuffle_bucket_segments, grid_of(n), dim3(256), 0, st, n, acc, acc_off, acc_len, perm, seg_src, len_perm);
-    return hipGetLastError();
-}
-
-hipError_t launch_shuffle_bucket_bytes(uint64_t n, const uint64_t* seg_src, const uint64_t* seg_off, uint8_t* out, hipStream_t st) {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_shuffle_bucket_bytes, grid_of(n), dim3(256), 0, st, n, seg_src, seg_off, out);
     return hipGetLastError();
 }
 

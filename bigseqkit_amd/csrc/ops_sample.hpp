@@ -14,20 +14,24 @@ struct SampleParams {
     int fastq;
     uint64_t first_record;  // index of record 0 of this shard (or chunk) in the whole input
     int64_t seed;
-    uint64_t threshold;     // ceil(fraction * 2^53): record g is kept iff (draw(seed, g) >> 11) < threshold
+    uint64_t lo, hi;        // record g is kept iff lo <= draw(seed, g) <= hi
 };
+// `sample`: (draw >> 11) < threshold, threshold = ceil(fraction * 2^53), as that interval (sample_dev.hpp sample_interval)
+void sample_draw_interval(uint64_t threshold, uint64_t* lo, uint64_t* hi);
 
-// out_len[i] = text + '\n' of record i when it is kept, else 0
+// out_len[i] = text + '\n' of record i when it is kept, else 0; keep (may be null): keep[i] = 1 / 0.  `sample` and the collect
+// pass of a bucket of `shuffle` (stages k_sample_size, k_shuffle_pick)
 hipError_t launch_sample_size(const uint8_t* buf, uint64_t buf_n, const RecordTable& t, const SampleParams& P, uint32_t* out_len,
-                              uint64_t* status, hipStream_t st);
+                              uint32_t* keep, uint64_t* status, hipStream_t st);
 // keys[i] = draw(seed, i)
 hipError_t launch_shuffle_keys(uint64_t n, int64_t seed, uint64_t* keys, hipStream_t st);
-// segment j = record perm[j]: len_perm[j] = out_len[perm[j]], seg_src[j] = its address in the shard when the byte after the
-// text is the '\n' (else 0, counted in *n_other and written by launch_shuffle_fix)
-hipError_t launch_shuffle_segments(const uint8_t* buf, uint64_t buf_n, const RecordTable& t, const uint32_t* out_len,
+// The n records (off[i], len[i]: text + '\n') of the text base[0, extent) in the order perm: segment j = record perm[j],
+// len_perm[j] = len[perm[j]], seg_src[j] = base + off[perm[j]].  n_other != null: only when the byte after the text is the
+// '\n' -- else 0, counted in *n_other and written by launch_shuffle_fix; null: the texts all end in their newline
+hipError_t launch_shuffle_segments(uint64_t n, const uint8_t* base, uint64_t extent, const uint64_t* off, const uint32_t* len,
                                    const uint32_t* perm, uint64_t* seg_src, uint32_t* len_perm, uint64_t* n_other, hipStream_t st);
 // text + '\n' of the segments the copy left out, byte by byte (all: of every segment -- the path without the segmented copy)
-hipError_t launch_shuffle_fix(const uint8_t* buf, const RecordTable& t, const uint32_t* perm, const uint32_t* len_perm,
+hipError_t launch_shuffle_fix(uint64_t n, const uint8_t* base, const uint64_t* off, const uint32_t* perm, const uint32_t* len_perm,
                               const uint64_t* seg_off, const uint64_t* seg_src, uint8_t* out, bool all, hipStream_t st);
 
 // ---- shuffle in buckets of the draw: SHUFFLE_BINS fine bins = the upper 12 bits of the draw; a bucket is a run of bins
@@ -37,17 +41,9 @@ constexpr int SHUFFLE_BIN_SHIFT = 52;
 // counters accumulate over the calls
 hipError_t launch_shuffle_hist(const uint8_t* buf, uint64_t buf_n, const RecordTable& t, int fastq, uint64_t first_record, int64_t seed,
                                uint64_t* bytes, uint64_t* records, int num_cus, hipStream_t st);
-// out_len[i] = text + '\n' of record i when lo <= draw <= hi (both inclusive), else 0; keep[i] = 1 / 0
-hipError_t launch_shuffle_pick(const uint8_t* buf, uint64_t buf_n, const RecordTable& t, int fastq, uint64_t first_record, int64_t seed,
-                               uint64_t lo, uint64_t hi, uint32_t* out_len, uint32_t* keep, uint64_t* status, hipStream_t st);
 // kept record i -> entry n0 + keep_off[i] of the accumulation: its draw, bytes0 + out_off[i], out_len[i]
 hipError_t launch_shuffle_append(uint64_t n, uint64_t first_record, int64_t seed, const uint32_t* out_len, const uint64_t* out_off,
                                  const uint64_t* keep_off, uint64_t n0, uint64_t bytes0, uint64_t* acc_draw, uint64_t* acc_off,
                                  uint32_t* acc_len, hipStream_t st);
-// segment j = accumulated record perm[j]: seg_src[j] = acc + acc_off[perm[j]], len_perm[j] = acc_len[perm[j]]
-hipError_t launch_shuffle_bucket_segments(uint64_t n, const uint8_t* acc, const uint64_t* acc_off, const uint32_t* acc_len,
-                                          const uint32_t* perm, uint64_t* seg_src, uint32_t* len_perm, hipStream_t st);
-// out[seg_off[j], seg_off[j + 1]) = the bytes at seg_src[j], byte by byte (the path without the segmented copy)
-hipError_t launch_shuffle_bucket_bytes(uint64_t n, const uint64_t* seg_src, const uint64_t* seg_off, uint8_t* out, hipStream_t st);
 
 }  // namespace bsk

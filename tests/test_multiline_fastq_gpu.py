@@ -179,6 +179,55 @@ def test_records_wrapped_only_further_down(monkeypatch):
     assert "unmatched length" in str(e.value)
 
 
+def test_sample_and_shuffle_wrapped_only_further_down(monkeypatch):
+    # the input of test_records_wrapped_only_further_down through sample, shuffle and the shuffle in buckets: the strict reader's
+    # complaint shows in the status word only, and the one retry of the shared prologue takes the multi-line reader
+    import ctypes as C
+    import sample_ref as R
+    monkeypatch.setenv("BSK_MIN_RANGE_BYTES", "4096")
+    rng = random.Random(3400)
+    plain = "".join("@p%d\n%s\n+\n%s\n" % (i, "ACGT" * 20, "IIII" * 20) for i in range(5000)).encode()   # > 256 KiB
+    assert len(plain) > 300 * 1024
+    data = plain + wrapped_fastq(rng, 200, 11)
+    assert bsk.Sample(frame(data), bsk.SeqKitSampleOptions().Seed(23).Proportion(0.5)) == R.sample(data, True, 23, 0, 0.5)
+    shuffled = R.shuffle(data, True, 23)
+    so = bsk.SeqKitShuffleOptions().Seed(23)
+    assert bsk.Shuffle(frame(data), so) == shuffled
+    hb = [0] * 4096
+    for g, r in enumerate(R.records(data, True)):
+        hb[R.draw(23, g) >> 52] += len(r) + 1
+    budget = sum(hb) // 2 + max(hb)         # the first bucket passes half of the bytes, the rest fits the second
+    assert len(bsk.ShufflePlan(hb, budget)) - 1 == 2
+    assert bsk.ShuffleBuckets(frame(data), so, budget) == shuffled
+    # a shard that is FASTQ under neither reader keeps the strict reader's complaint, status and text as `seq` gives them
+    bad = plain + b"@x\nACGT\n+\nIII\n"
+    with pytest.raises(bsk.BskError) as e:
+        run("seq", frame(bad), {})
+    code, text = e.value.code, str(e.value)
+    assert "unmatched length" in text
+    fb = frame(bad)
+    (pid, ptr, n, on_dev, keep), = fb.partitions()
+    with bsk.Operator("Shuffle", so.to_json(), 0) as op:
+        calls = [lambda: bsk.Range(fb, _Opts({"Range": "1:10"})),
+                 lambda: bsk.Sample(fb, bsk.SeqKitSampleOptions().Seed(23).Proportion(0.5)),
+                 lambda: bsk.Shuffle(fb, so),
+                 lambda: bsk.ShuffleHistRun(op, fb)]
+        for call in calls:
+            with pytest.raises(bsk.BskError) as e:
+                call()
+            assert (e.value.code, str(e.value)) == (code, text)
+        _lib.check(_lib.lib.bsk_shuffle_bucket_begin(op.ctx, 0, 4096), op.ctx)
+        assert _lib.lib.bsk_shuffle_bucket_add(op.ctx, ptr, n, 1 if on_dev else 0, fb.format, pid, 0, None) == code
+        with pytest.raises(bsk.BskError) as e:
+            _lib.check(code, op.ctx)
+        assert str(e.value) == text
+        # the failed add closed the bucket
+        out = _lib.Out()
+        assert _lib.lib.bsk_shuffle_bucket_finish(op.ctx, None, C.byref(out)) == _lib.BSK_ERR_INVALID_ARG
+        _lib.check(_lib.lib.bsk_shuffle_bucket_begin(op.ctx, 0, 4096), op.ctx)
+        _lib.check(_lib.lib.bsk_shuffle_bucket_finish(op.ctx, None, C.byref(out)), op.ctx)
+
+
 def test_two_input_operators_on_multiline_fastq(monkeypatch):
     # pair / common / concat read several texts: every text is rewritten by itself
     monkeypatch.setenv("BSK_MIN_RANGE_BYTES", "2048")

@@ -138,6 +138,24 @@ def test_empty_and_single_record(fastq):
         assert len(R.records(data, fastq)) == n
 
 
+@pytest.mark.parametrize("parts", [1, 3])
+@pytest.mark.parametrize("fastq", [True, False])
+def test_the_verdict_as_an_interval_of_the_draw(fastq, parts):
+    """the kernel compares the draw with a closed interval in place of (draw >> 11) < T: T = 2^53 (all of [0, 2^64 - 1]), the
+    smallest T there is (1: [0, 2047], from the smallest fraction the options accept) and one in between"""
+    rng = random.Random(90 + fastq)
+    data = seqgen.random_fastq(rng, 30, 1, 60) if fastq else seqgen.random_fasta(rng, 30, 1, 90)
+    recs = R.records(data, fastq)
+    assert len(recs) == 30
+    assert gpu_sample(data, fastq, parts=parts, proportion=1.0) == b"".join(r + b"\n" for r in recs)
+    tiny = 2.0 ** -149                       # the smallest positive float32: Proportion is one in the reference's options
+    assert R.f32(tiny) == tiny and R.threshold(tiny) == 1 and R.f32(tiny / 2) == 0
+    for p in (tiny, 0.5):
+        for seed in (11, 23):
+            assert gpu_sample(data, fastq, parts=parts, proportion=p, seed=seed) == R.sample(data, fastq, seed, 0, p), (p, seed)
+    assert 0 < len(R.records(R.sample(data, fastq, 11, 0, 0.5), fastq)) < 30
+
+
 @pytest.mark.parametrize("out", ["slices", "block"])
 @pytest.mark.parametrize("segcopy", ["off", "force", None])
 def test_output_contracts_and_copy_paths(out, segcopy, monkeypatch):

@@ -116,13 +116,14 @@ HIPCC = "/opt/rocm/bin/hipcc"
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_kernels_use_no_scratch(tmp_path):
-    """the compiler's resource report for gfx950: no scratch and no spill in the kernels of the bucket path; the 48 KiB of LDS
+    """the compiler's resource report for gfx950: no scratch and no spill in any kernel of `sample` / `shuffle`; the 48 KiB of LDS
     are the histogram's alone"""
     src = os.path.join(ROOT, "bigseqkit_amd", "csrc", "ops_sample.hip")
     r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Rpass-analysis=kernel-resource-usage", "-c", src,
                         "-o", str(tmp_path / "o.o")], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
-    want = ("k_shuffle_hist", "k_shuffle_pick", "k_shuffle_append", "k_shuffle_bucket_segments", "k_shuffle_bucket_bytes")
+    want = ("k_sample_size", "k_shuffle_keys", "k_shuffle_segments", "k_shuffle_fix", "k_shuffle_hist", "k_shuffle_append")
+    assert sorted(re.findall(r"void (k_\w+)\(", open(src).read())) == sorted(want)          # every kernel of the file
     seen = {}
     for b in r.stderr.split("Function Name: ")[1:]:
         sym = b.split(" ", 1)[0]
