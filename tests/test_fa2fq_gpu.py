@@ -63,6 +63,35 @@ def run(tmp_path, fastq, fasta, opts=None, parts=1, fasta_format=False):
     return bsk.Fa2Fq(read(fastq, parts), _Opts(opts_json(path, opts or {})))
 
 
+_NEXT_BASE = {65: 67, 67: 71, 71: 84, 84: 65}
+
+
+def fasta_entry(rng, name, head, seq):
+    """The FASTA record made from one read (ID `name`, full header `head`), or None: the read is left out, or a random slice
+    of it is kept as it is, under another name, reverse-complemented or with one base changed.  (Reads shorter than 12 bases
+    give slices of any length, the empty one included.)"""
+    L = len(seq)
+    fate = rng.random()
+    if fate < 0.12:
+        return None  # not in the FASTA file
+    m = rng.randint(min(12, L), L)
+    a = rng.randint(0, L - m)
+    s = seq[a:a + m]
+    if fate < 0.24:
+        name = rng.choice([name + b"x", b"R" + name[1:], head + b" d"])  # renamed: absent
+    elif fate < 0.52:
+        pass
+    elif fate < 0.82:
+        s = rc(s)
+    elif m:
+        k = rng.randrange(m)
+        s = s[:k] + bytes([_NEXT_BASE.get(s[k], 65)]) + s[k + 1:]
+        if rng.random() < 0.5:
+            s = rc(s)
+    w = rng.choice([0, 0, 7, 60])
+    return b">" + name + b"\n" + (s if not w else b"\n".join(s[k:k + w] for k in range(0, len(s), w))) + b"\n"
+
+
 def random_case(rng):
     """A FASTQ shard and a FASTA made from it: a random slice of a random subset, some reverse-complemented, some renamed,
     some with one base changed."""
@@ -73,25 +102,9 @@ def random_case(rng):
         L = rng.choice([rng.randint(30, 90), rng.randint(30, 90), rng.randint(90, 400)])
         seq = dna(rng, L)
         fq.append(record(head, seq, rng=rng))
-        fate = rng.random()
-        if fate < 0.12:
-            continue  # not in the FASTA file
-        m = rng.randint(12, L)
-        a = rng.randint(0, L - m)
-        s = seq[a:a + m]
-        if fate < 0.24:
-            name = rng.choice([name + b"x", b"R" + name[1:], head + b" d"])  # renamed: absent
-        elif fate < 0.52:
-            pass
-        elif fate < 0.82:
-            s = rc(s)
-        else:
-            k = rng.randrange(m)
-            s = s[:k] + bytes([{65: 67, 67: 71, 71: 84, 84: 65}[s[k]]]) + s[k + 1:]
-            if rng.random() < 0.5:
-                s = rc(s)
-        w = rng.choice([0, 0, 7, 60])
-        fa.append(b">" + name + b"\n" + (s if not w else b"\n".join(s[k:k + w] for k in range(0, len(s), w))) + b"\n")
+        entry = fasta_entry(rng, name, head, seq)
+        if entry is not None:
+            fa.append(entry)
     rng.shuffle(fa)
     opts = {"OnlyPositiveStrand": True} if rng.random() < 0.15 else {}
     return b"".join(fq), b"".join(fa), opts
