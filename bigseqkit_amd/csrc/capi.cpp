@@ -79,16 +79,6 @@ void validate_stats(bsk_ctx* c) {  // bigseqkit-lib/stats.go:27-46
     // (more than MAX_GAP_LETTERS distinct letters: counted by a pass of their own over the record table, stats_run_device)
 }
 
-int ensure_ranges(bsk_ctx* c, uint32_t nranges) {
-    if (nranges <= c->cap_ranges && c->d_anchors) return BSK_OK;
-    if (c->d_anchors) HIP_TRY(c, hipFree(c->d_anchors));
-    c->d_anchors = nullptr;
-    // anchors[nranges + 1] followed by the queue word, then k_prep's raw anchors [nranges + 1] (FASTA)
-    HIP_TRY(c, hipMalloc((void**)&c->d_anchors, 2 * ((size_t)nranges + 2) * sizeof(uint64_t)));
-    c->cap_ranges = nranges;
-    return BSK_OK;
-}
-
 // the switches a context caches in fields (read again after bsk_ctx_set)
 static void apply_tuning(bsk_ctx* c) {
     c->use_dpp = !c->tune.is("scan", "shfl");
@@ -491,7 +481,7 @@ static int stats_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int form
             tickets = nsplit + (uint32_t)((n - (uint64_t)nsplit * chunk + small - 1) / small);
         }
     } else {
-        int rc = ensure_ranges(c, nranges);
+        int rc = ensure_range_arrays(c, nranges);
         if (rc != BSK_OK) return rc;
     }
     // overflow list for lengths >= hist_cap
@@ -534,8 +524,7 @@ static int stats_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int form
     }
     // (without k_prep: the queue is two words of the control block, zero whenever no k_stats runs)
     uint64_t* anchors = self_anchor ? nullptr : c->d_anchors;
-    uint32_t* queue = self_anchor ? reinterpret_cast<uint32_t*>(c->d_ctl + bsk_ctx::CTL_STATS_QUEUE)
-                                  : reinterpret_cast<uint32_t*>(c->d_anchors + (size_t)nranges + 1);
+    uint32_t* queue = self_anchor ? reinterpret_cast<uint32_t*>(c->d_ctl + bsk_ctx::CTL_STATS_QUEUE) : range_queue(c, nranges);
     D.r_head = D.r_tail = nullptr;
     D.r_flags = nullptr;
     if (!fastq) {

@@ -102,9 +102,8 @@ int group_resolve(bsk_ctx* c, const uint8_t* d_buf, const TextTableH& tt, const 
             HIP_TRYX(c, launch_rmdup_resolve_first(d_buf, c->table, tt, P, d_first, c->d_keys, c->d_out_len, c->d_status, d_has, st));
             return BSK_OK;
         }
-        status &= ~(uint64_t)ERR_BUCKET_OVERFLOW;
-        HIP_TRYX(c, hipMemcpyAsync(c->d_status, &status, sizeof status, hipMemcpyHostToDevice, st));
-        HIP_TRYX(c, hipStreamSynchronize(st));
+        rc = clear_status_bits(c, &status, ERR_BUCKET_OVERFLOW, st);
+        if (rc != BSK_OK) return rc;
     }
     uint64_t cap = 0;
     uint64_t* tk = nullptr;
@@ -217,24 +216,115 @@ int prep_ranges(bsk_ctx* c, const uint8_t* d_buf, size_t n, bool fastq, int bloc
     const uint32_t nranges = (uint32_t)nr;
     uint64_t chunk = (n + nranges - 1) / nranges;
     chunk = (chunk + 15) & ~(uint64_t)15;
-    if (nranges > c->cap_ranges || !c->d_anchors || !c->d_range_count) {
-        if (c->d_anchors) HIP_TRYX(c, hipFree(c->d_anchors));
-        if (c->d_range_count) HIP_TRYX(c, hipFree(c->d_range_count));
-        if (c->d_range_base) HIP_TRYX(c, hipFree(c->d_range_base));
-        c->d_anchors = nullptr; c->d_range_count = nullptr; c->d_range_base = nullptr;
-        HIP_TRYX(c, hipMalloc((void**)&c->d_anchors, 2 * ((size_t)nranges + 2) * sizeof(uint64_t)));  // (+ k_prep's raw anchors)
-        HIP_TRYX(c, hipMalloc((void**)&c->d_range_count, ((size_t)nranges + 1) * sizeof(uint64_t)));
-        HIP_TRYX(c, hipMalloc((void**)&c->d_range_base, ((size_t)nranges + 2) * sizeof(uint64_t)));
-        c->cap_ranges = nranges;
-    }
-    uint32_t* queue = reinterpret_cast<uint32_t*>(c->d_anchors + (size_t)nranges + 1);
+    const int rc = ensure_range_arrays(c, nranges);
+    if (rc != BSK_OK) return rc;
     {
         Timed t(c, "k_prep", st);
-        HIP_TRYX(c, launch_prep(fastq, d_buf, n, chunk, nranges, c->d_anchors, queue, st, /*line_mode=*/!fastq,
+        HIP_TRYX(c, launch_prep(fastq, d_buf, n, chunk, nranges, c->d_anchors, range_queue(c, nranges), st, /*line_mode=*/!fastq,
                                 /*raw=*/fastq ? nullptr : c->d_anchors + (size_t)nranges + 2));
     }
     *nranges_out = nranges;
     *chunk_out = chunk;
+    return BSK_OK;
+}
+
+// the steps around the kernel of a streaming pass (contracts: ops_host_internal.hpp)
+int ensure_range_arrays(bsk_ctx* c, uint32_t nranges) {
+    if (nranges <= c->cap_ranges && c->d_anchors && c->d_range_count && c->d_range_base) return BSK_OK;
+    c->cap_ranges = 0;
+    for (uint64_t** p : {&c->d_anchors, &c->d_range_count, &c->d_range_base}) {
+        if (*p) HIP_TRYX(c, hipFree(*p));
+        *p = nullptr;
+    }
+    HIP_TRYX(c, hipMalloc((void**)&c->d_anchors, 2 * ((size_t)nranges + 2) * sizeof(uint64_t)));  // (+ the queue word, k_prep's raw anchors)
+    HIP_TRYX(c, hipMalloc((void**)&c->d_range_count, ((size_t)nranges + 1) * sizeof(uint64_t)));
+    HIP_TRYX(c, hipMalloc((void**)&c->d_range_base, ((size_t)nranges + 2) * sizeof(uint64_t)));
+    c->cap_ranges = nranges;
+    return BSK_OK;
+}
+
+int ensure_table(bsk_ctx* c, RecordTable& t, uint64_t cap) {
+    if (cap <= t.cap && t.start) return BSK_OK;
+    for (void* p : {(void*)t.start, (void*)t.l_head, (void*)t.l_seq, (void*)t.aux, (void*)t.text_w})
+        if (p) HIP_TRYX(c, hipFree(p));
+    t = RecordTable();
+    HIP_TRYX(c, hipMalloc((void**)&t.start, (cap + 1) * sizeof(uint64_t)));
+    HIP_TRYX(c, hipMalloc((void**)&t.l_head, cap * sizeof(uint32_t)));
+    HIP_TRYX(c, hipMalloc((void**)&t.l_seq, cap * sizeof(uint32_t)));
+    HIP_TRYX(c, hipMalloc((void**)&t.aux, cap * sizeof(uint32_t)));
+    HIP_TRYX(c, hipMalloc((void**)&t.text_w, cap * sizeof(uint32_t)));
+    t.cap = cap;
+    return BSK_OK;
+}
+
+int clear_status_bits(bsk_ctx* c, uint64_t* status, uint64_t bits, hipStream_t st) {
+    *status &= ~bits;
+    HIP_TRYX(c, hipMemcpyAsync(c->d_status, status, sizeof *status, hipMemcpyHostToDevice, st));
+    HIP_TRYX(c, hipStreamSynchronize(st));
+    return BSK_OK;
+}
+
+uint64_t head_record_count(const uint8_t* head, size_t hb, bool fastq) {
+    uint64_t recs = 0;
+    if (fastq) { for (size_t i = 0; i < hb; ++i) recs += head[i] == '\n'; return recs / 4; }
+    for (size_t i = 0; i + 1 < hb; ++i) recs += (head[i] == '\n' && head[i + 1] == '>');
+    return recs + 1;
+}
+
+int run_slice_pass(bsk_ctx* c, const uint8_t* d_buf, size_t n, const SlicePass& S, hipStream_t st, bsk_out* out) {
+    const int blocks = std::max(1, c->num_cus * S.per_cu);
+    uint32_t nranges = 0;
+    uint64_t chunk = 0;
+    int rc = prep_ranges(c, d_buf, n, /*fastq=*/true, blocks, st, &nranges, &chunk);
+    if (rc != BSK_OK) return rc;
+    rc = sample_head(c, d_buf, n, st);  // (the call's one head sample, pinned)
+    if (rc != BSK_OK) return rc;
+    if (!c->norm_active && fastq_head_multiline(c->h_head, c->head_len)) return BSK_ERR_MULTILINE_FASTQ;
+    double ratio = 0;
+    rc = S.ratio(c->h_head, c->head_len, &ratio);
+    if (rc != BSK_OK) return rc;
+    const char* scale = c->tune.get(S.scale_switch);
+    if (scale) ratio *= atof(scale);  // tests: force the overflow -> fallback route
+    uint64_t slice_cap = (uint64_t)((double)chunk * ratio * 1.25) + (scale ? 16 : 4096);
+    slice_cap = (slice_cap + 15) & ~(uint64_t)15;
+    if (slice_cap >= (1ull << 32) || slice_cap * nranges > S.budget) return BSK_ERR_FILTER_FALLBACK;
+    rc = grow(c, &c->d_slices, &c->slices_cap, slice_cap * nranges, 256);
+    if (rc != BSK_OK) return rc;
+    rc = grow(c, &c->d_names_aux, &c->names_aux_cap, 2 * ((uint64_t)nranges + 2), 16);
+    if (rc != BSK_OK) return rc;
+    uint64_t* range_bytes = c->d_names_aux;  // [nranges], and behind it the scanned record counts
+    uint64_t* d_count_base = c->d_names_aux + nranges + 2;
+    {
+        Timed t(c, S.stage_pass, st);
+        HIP_TRYX(c, S.launch(blocks, nranges, range_queue(c, nranges), c->d_slices, slice_cap, range_bytes, c->d_range_count));
+    }
+    {
+        Timed t(c, "k_range_scan", st);
+        HIP_TRYX(c, launch_scan_small2(range_bytes, c->d_range_base, c->d_fin + bsk_ctx::FIN_AUX0, c->d_range_count, d_count_base,
+                                       c->d_fin + bsk_ctx::FIN_AUX1, nranges, st));
+    }
+    rc = ctl_readback(c, st);  // bytes, records, status: one copy
+    if (rc != BSK_OK) return rc;
+    const uint64_t total = c->fin(bsk_ctx::FIN_AUX0), records = c->fin(bsk_ctx::FIN_AUX1);
+    uint64_t status = c->status_word();
+    if (status & ERR_CAPACITY) {
+        rc = clear_status_bits(c, &status, ERR_CAPACITY, st);
+        if (rc != BSK_OK) return rc;
+        if (status == 0) return BSK_ERR_FILTER_FALLBACK;
+    }
+    if (status) return kernel_error_to_status(c, status);
+    c->table.n = 0;  // no record table was built for this shard
+    if (total && slices_wanted(c))  // round 6: the per-range slices ARE the result, in order (include/bsk.h bsk_out.d_seg_*)
+        return out_as_slices(c, out, c->d_slices, slice_cap, c->d_range_base, nranges, total, records, st);
+    rc = ensure_out(c, total);
+    if (rc != BSK_OK) return rc;
+    if (total) {
+        Timed t(c, S.stage_compact, st);
+        HIP_TRYX(c, launch_slices_compact(c->d_slices, slice_cap, range_bytes, c->d_range_base, nranges, c->d_out, st));
+    }
+    out->d_data = c->d_out;
+    out->len = total;
+    out->records = records;
     return BSK_OK;
 }
 
@@ -268,7 +358,7 @@ int build_index_ex(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipSt
     int rcp = prep_ranges(c, d_buf, n, fastq, blocks, st, &nranges, &chunk);
     if (rcp != BSK_OK) return rcp;
     uint64_t* anchors = c->d_anchors;
-    uint32_t* queue = reinterpret_cast<uint32_t*>(c->d_anchors + (size_t)nranges + 1);
+    uint32_t* queue = range_queue(c, nranges);
     IndexDev D;
     D.parts = nullptr;
     if (!fastq) {
@@ -285,18 +375,11 @@ int build_index_ex(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipSt
     D.range_base = c->d_range_base;
     D.status = c->d_status;
     D.sparse_cap = 0;
-    auto alloc_table = [&](RecordTable& t, uint64_t cap) -> int {
-        if (cap <= t.cap && t.start) return BSK_OK;
-        for (void* p : {(void*)t.start, (void*)t.l_head, (void*)t.l_seq, (void*)t.aux, (void*)t.text_w})
-            if (p) HIP_TRYX(c, hipFree(p));
-        t = RecordTable();
-        HIP_TRYX(c, hipMalloc((void**)&t.start, (cap + 1) * sizeof(uint64_t)));
-        HIP_TRYX(c, hipMalloc((void**)&t.l_head, cap * sizeof(uint32_t)));
-        HIP_TRYX(c, hipMalloc((void**)&t.l_seq, cap * sizeof(uint32_t)));
-        HIP_TRYX(c, hipMalloc((void**)&t.aux, cap * sizeof(uint32_t)));
-        HIP_TRYX(c, hipMalloc((void**)&t.text_w, cap * sizeof(uint32_t)));
-        t.cap = cap;
-        return BSK_OK;
+    // the filter's pending-hit list was full: its bits leave the status word, the caller takes the unfiltered path
+    auto filter_gave_up = [&](uint64_t status) -> int {
+        if (!(status & ERR_FILTER_OVERFLOW)) return BSK_OK;
+        const int rc = clear_status_bits(c, &status, ERR_FILTER_OVERFLOW | ERR_CAPACITY, st);
+        return rc != BSK_OK ? rc : BSK_ERR_FILTER_FALLBACK;
     };
     uint64_t total = 0;
     bool done = false;
@@ -312,15 +395,12 @@ int build_index_ex(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipSt
         const size_t hb = c->head_len;
         const uint8_t* head = c->h_head;
         if (fastq && !c->norm_active && fastq_head_multiline(head, hb)) return BSK_ERR_MULTILINE_FASTQ;
-        uint64_t recs = 0;
-        if (fastq) { for (size_t i = 0; i < hb; ++i) recs += head[i] == '\n'; recs /= 4; }
-        else { for (size_t i = 0; i + 1 < hb; ++i) recs += (head[i] == '\n' && head[i + 1] == '>'); recs += 1; }
-        const double avg = (double)hb / (double)std::max<uint64_t>(recs, 1);
+        const double avg = (double)hb / (double)std::max<uint64_t>(head_record_count(head, hb, fastq), 1);
         c->avg_record_bytes = (uint64_t)avg;  // lanes per record of the per-record kernels (a filtered table is no measure)
         const uint64_t sparse_cap = (uint64_t)((double)chunk / std::max(avg * 0.5, 6.0)) + 64;
         const uint64_t need = sparse_cap * nranges;
         if (need * 20 <= (uint64_t)n + (64ull << 20)) {  // never reserve more than the shard itself
-            int rc2 = alloc_table(c->sparse, need);
+            int rc2 = ensure_table(c, c->sparse, need);
             if (rc2 != BSK_OK) return rc2;
             D.t = c->sparse;
             D.write = 2;
@@ -345,20 +425,14 @@ int build_index_ex(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipSt
             }
             total = c->fin(bsk_ctx::FIN_TABLE_N);
             uint64_t status = c->status_word();
-            if (status & ERR_FILTER_OVERFLOW) {
-                status &= ~(uint64_t)(ERR_FILTER_OVERFLOW | ERR_CAPACITY);
-                HIP_TRYX(c, hipMemcpyAsync(c->d_status, &status, sizeof status, hipMemcpyHostToDevice, st));
-                HIP_TRYX(c, hipStreamSynchronize(st));
-                return BSK_ERR_FILTER_FALLBACK;
-            }
+            if (const int rcf = filter_gave_up(status)) return rcf;
             if (status & ERR_CAPACITY) {
-                status &= ~(uint64_t)ERR_CAPACITY;  // retry exactly
-                HIP_TRYX(c, hipMemcpyAsync(c->d_status, &status, sizeof status, hipMemcpyHostToDevice, st));
-                HIP_TRYX(c, hipStreamSynchronize(st));
+                const int rcc = clear_status_bits(c, &status, ERR_CAPACITY, st);  // retry exactly
+                if (rcc != BSK_OK) return rcc;
                 HIP_TRYX(c, launch_reset_queue(queue, st));
                 if (D.parts) HIP_TRYX(c, hipMemsetAsync(c->d_parts, 0, (size_t)nranges * sizeof(RangePart), st));
             } else {
-                int rc3 = alloc_table(c->table, total + total / 8 + 16);
+                int rc3 = ensure_table(c, c->table, total + total / 8 + 16);
                 if (rc3 != BSK_OK) return rc3;
                 c->table.n = total;
                 if (total && hash) {
@@ -387,15 +461,10 @@ int build_index_ex(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipSt
             uint64_t status = 0;
             HIP_TRYX(c, hipMemcpyAsync(&status, c->d_status, sizeof status, hipMemcpyDeviceToHost, st));
             HIP_TRYX(c, hipStreamSynchronize(st));
-            if (status & ERR_FILTER_OVERFLOW) {
-                status &= ~(uint64_t)(ERR_FILTER_OVERFLOW | ERR_CAPACITY);
-                HIP_TRYX(c, hipMemcpyAsync(c->d_status, &status, sizeof status, hipMemcpyHostToDevice, st));
-                HIP_TRYX(c, hipStreamSynchronize(st));
-                return BSK_ERR_FILTER_FALLBACK;
-            }
+            if (const int rcf = filter_gave_up(status)) return rcf;
         }
         HIP_TRYX(c, hipStreamSynchronize(st));
-        int rc4 = alloc_table(c->table, total + total / 8 + 16);
+        int rc4 = ensure_table(c, c->table, total + total / 8 + 16);
         if (rc4 != BSK_OK) return rc4;
         c->table.n = total;
         if (total == 0) return BSK_OK;
@@ -432,8 +501,7 @@ int build_index_light(bsk_ctx* c, const uint8_t* d_buf, size_t n, hipStream_t st
     HIP_TRYX(c, hipMemcpyAsync(head.data(), d_buf, hb, hipMemcpyDeviceToHost, st));
     HIP_TRYX(c, hipStreamSynchronize(st));
     if (head[0] != '>') return BSK_ERR_FILTER_FALLBACK;
-    uint64_t recs = 1;
-    for (size_t i = 0; i + 1 < hb; ++i) recs += (head[i] == '\n' && head[i + 1] == '>');
+    const uint64_t recs = head_record_count(head.data(), hb, /*fastq=*/false);
     // the sample must look like this path's text: letters A C G T (any case) on the sequence lines
     {
         bool in_head = true;
@@ -452,21 +520,13 @@ int build_index_light(bsk_ctx* c, const uint8_t* d_buf, size_t n, hipStream_t st
     const uint32_t nranges = (uint32_t)pick_nranges(n, waves, c->min_range_bytes, (int)c->tune.num("ranges_per_wave"));
     uint64_t chunk = (n + nranges - 1) / nranges;
     chunk = (chunk + 15) & ~(uint64_t)15;
-    if (nranges > c->cap_ranges || !c->d_anchors || !c->d_range_count) {
-        if (c->d_anchors) HIP_TRYX(c, hipFree(c->d_anchors));
-        if (c->d_range_count) HIP_TRYX(c, hipFree(c->d_range_count));
-        if (c->d_range_base) HIP_TRYX(c, hipFree(c->d_range_base));
-        c->d_anchors = nullptr; c->d_range_count = nullptr; c->d_range_base = nullptr;
-        HIP_TRYX(c, hipMalloc((void**)&c->d_anchors, 2 * ((size_t)nranges + 2) * sizeof(uint64_t)));
-        HIP_TRYX(c, hipMalloc((void**)&c->d_range_count, ((size_t)nranges + 1) * sizeof(uint64_t)));
-        HIP_TRYX(c, hipMalloc((void**)&c->d_range_base, ((size_t)nranges + 2) * sizeof(uint64_t)));
-        c->cap_ranges = nranges;
-    }
-    uint32_t* queue = reinterpret_cast<uint32_t*>(c->d_anchors + (size_t)nranges + 1);
+    int rc = ensure_range_arrays(c, nranges);
+    if (rc != BSK_OK) return rc;
+    uint32_t* queue = range_queue(c, nranges);
     const uint64_t sparse_cap = (uint64_t)((double)chunk / std::max(avg * 0.5, 6.0)) + 64;
     const uint64_t need = sparse_cap * nranges;
     if (need * 8 > (uint64_t)n / 4 + (64ull << 20)) return BSK_ERR_FILTER_FALLBACK;  // (tiny records: the full pass is the better one)
-    int rc = grow(c, &c->d_keys_sparse, &c->keys_sparse_cap, need, 16);  // (the slices: plain u64 scratch of the context)
+    rc = grow(c, &c->d_keys_sparse, &c->keys_sparse_cap, need, 16);  // (the slices: plain u64 scratch of the context)
     if (rc != BSK_OK) return rc;
     uint64_t n_eff = n;
     {   // effective end of the shard (trailing blank lines dropped), as k_prep computes it -- from the last bytes on the host
@@ -491,26 +551,14 @@ int build_index_light(bsk_ctx* c, const uint8_t* d_buf, size_t n, hipStream_t st
     HIP_TRYX(c, hipMemcpyAsync(&status, c->d_status, sizeof status, hipMemcpyDeviceToHost, st));
     HIP_TRYX(c, hipStreamSynchronize(st));
     auto give_up = [&](uint64_t bits) -> int {
-        status &= ~bits;
-        HIP_TRYX(c, hipMemcpyAsync(c->d_status, &status, sizeof status, hipMemcpyHostToDevice, st));
-        HIP_TRYX(c, hipStreamSynchronize(st));
-        return BSK_ERR_FILTER_FALLBACK;
+        const int rcg = clear_status_bits(c, &status, bits, st);
+        return rcg != BSK_OK ? rcg : BSK_ERR_FILTER_FALLBACK;
     };
     if (status & ERR_CAPACITY) return give_up(ERR_CAPACITY);
     if (total == 0 || total >= (1ull << 32)) return BSK_ERR_FILTER_FALLBACK;
     RecordTable& t = c->table;
-    const uint64_t cap = total + total / 8 + 16;
-    if (cap > t.cap || !t.start) {
-        for (void* p : {(void*)t.start, (void*)t.l_head, (void*)t.l_seq, (void*)t.aux, (void*)t.text_w})
-            if (p) HIP_TRYX(c, hipFree(p));
-        t = RecordTable();
-        HIP_TRYX(c, hipMalloc((void**)&t.start, (cap + 1) * sizeof(uint64_t)));
-        HIP_TRYX(c, hipMalloc((void**)&t.l_head, cap * sizeof(uint32_t)));
-        HIP_TRYX(c, hipMalloc((void**)&t.l_seq, cap * sizeof(uint32_t)));
-        HIP_TRYX(c, hipMalloc((void**)&t.aux, cap * sizeof(uint32_t)));
-        HIP_TRYX(c, hipMalloc((void**)&t.text_w, cap * sizeof(uint32_t)));
-        t.cap = cap;
-    }
+    rc = ensure_table(c, t, total + total / 8 + 16);
+    if (rc != BSK_OK) return rc;
     t.n = total;
     t.id_off = nullptr;
     t.id_len = nullptr;
@@ -1262,18 +1310,8 @@ int normalize_multiline_fastq(bsk_ctx* c, const uint8_t* d_buf, size_t n, hipStr
         HIP_TRYX(c, hipStreamSynchronize(st));
         if (status) return format_error(status);
         RecordTable& t = c->table;
-        if (nrec + 1 > t.cap || !t.start) {
-            for (void* q : {(void*)t.start, (void*)t.l_head, (void*)t.l_seq, (void*)t.aux, (void*)t.text_w})
-                if (q) HIP_TRYX(c, hipFree(q));
-            t = RecordTable();
-            const uint64_t cap = nrec + nrec / 8 + 16;
-            HIP_TRYX(c, hipMalloc((void**)&t.start, (cap + 1) * sizeof(uint64_t)));
-            HIP_TRYX(c, hipMalloc((void**)&t.l_head, cap * sizeof(uint32_t)));
-            HIP_TRYX(c, hipMalloc((void**)&t.l_seq, cap * sizeof(uint32_t)));
-            HIP_TRYX(c, hipMalloc((void**)&t.aux, cap * sizeof(uint32_t)));
-            HIP_TRYX(c, hipMalloc((void**)&t.text_w, cap * sizeof(uint32_t)));
-            t.cap = cap;
-        }
+        const int rct = ensure_table(c, t, nrec + nrec / 8 + 16);
+        if (rct != BSK_OK) return rct;
         t.n = nrec;
         uint64_t end = n;
         if (nrec) {

@@ -188,7 +188,7 @@ int seg_run(bsk_ctx* c, const SegList& L, uint8_t* d_out, const uint8_t* d_buf, 
 // Round 6, results as ordered slices (include/bsk.h bsk_out.d_seg_*): does the running call leave its text where it is?
 inline bool slices_wanted(const bsk_ctx* c) { return c->out_slices && !c->force_contiguous; }
 // ... the text as segments of the shard (kind 1: what launch_seg_copy would move) / as the per-range slices of a streaming
-// pass (kind 2: what launch_names_compact would gather; range_base = [nranges + 1] scanned bytes)
+// pass (kind 2: what launch_slices_compact would gather; range_base = [nranges + 1] scanned bytes)
 void out_as_segments(bsk_ctx* c, bsk_out* out, const uint64_t* seg_src, const uint64_t* seg_off, uint64_t nseg, const uint32_t* first4k,
                      const uint8_t* lo, const uint8_t* hi, uint64_t total, uint64_t records);
 int out_as_slices(bsk_ctx* c, bsk_out* out, const uint8_t* slices, uint64_t slice_cap, const uint64_t* range_base, uint32_t nranges,
@@ -209,10 +209,45 @@ int bind_features(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStr
 bool has_unquoted_comma(const std::string& p);
 extern const char* const HELP_UNQUOTED_COMMA;
 void parse_region_opt(const std::string& region, const char* cmd, int* start, int* end);  // reRegion + the range checks of Before()
-// ranges of the streaming kernels for a shard: anchors in c->d_anchors (k_prep), the work queue behind them
-// force_chunk != 0: ranges of that nominal size (a multiple of 16) instead of the number pick_nranges chooses
+// The steps around the kernel of a streaming pass (stream_*.hip, k_translate_stream), each written once:
+//   ensure_range_arrays  before: a number of ranges.  After: c->d_anchors (anchors[nranges + 1], the queue word, k_prep's raw
+//                 anchors), c->d_range_count [nranges + 1] and c->d_range_base [nranges + 2] hold that many, c->cap_ranges
+//                 says so.  The ONLY code that allocates or frees the three or writes cap_ranges: they grow together.
+//   range_queue   the queue word behind the anchors of `nranges` ranges
+//   prep_ranges   before: the shard and the blocks of the pass.  After: the arrays grown, anchors and queue written by k_prep
+//                 (queued, stage k_prep).  force_chunk != 0: ranges of that nominal size (a multiple of 16) instead of the
+//                 number pick_nranges chooses
+//   ensure_table  before: a capacity in records.  After: the five arrays of `t` hold `cap` records (start: cap + 1); a table
+//                 that grows is a new, empty one (n = 0, no ID spans)
+//   clear_status_bits    before: *status = the device status word as just read back.  After: `bits` cleared in *status and in
+//                 c->d_status -- one copy, one synchronisation (the host word lives on the caller's stack)
+//   head_record_count    records that begin in the head sample: FASTQ newlines / 4, FASTA "\n>" + 1
+int ensure_range_arrays(bsk_ctx* c, uint32_t nranges);
+inline uint32_t* range_queue(const bsk_ctx* c, uint32_t nranges) { return reinterpret_cast<uint32_t*>(c->d_anchors + (size_t)nranges + 1); }
 int prep_ranges(bsk_ctx* c, const uint8_t* d_buf, size_t n, bool fastq, int blocks, hipStream_t st, uint32_t* nranges_out,
                 uint64_t* chunk_out, uint64_t force_chunk = 0);
+int ensure_table(bsk_ctx* c, RecordTable& t, uint64_t cap);
+int clear_status_bits(bsk_ctx* c, uint64_t* status, uint64_t bits, hipStream_t st);
+uint64_t head_record_count(const uint8_t* head, size_t hb, bool fastq);
+// A FASTQ pass whose kernel writes the result itself, range r into slice r of c->d_slices (seq -n, subseq -r).
+//   run_slice_pass  before: the shard.  After: `out` is the text -- gathered into c->d_out (stage_compact), or with out=slices
+//                 the slices themselves (out_as_slices) -- and c->table.n = 0: no record table was built.  In between, in
+//                 this order: prep_ranges for num_cus * per_cu blocks; the head sample (wrapped records:
+//                 BSK_ERR_MULTILINE_FASTQ); ratio(head, hb, &r) = output bytes per input byte, or a status of its own
+//                 (BSK_ERR_FILTER_FALLBACK: not this pass's input); slice_cap = chunk * r * 1.25 + 4096, rounded up to 16
+//                 (with the test switch `scale_switch` set: r times its value, + 16); slices beyond `budget` bytes or of
+//                 2^32: BSK_ERR_FILTER_FALLBACK; launch (stage_pass); the scan of bytes and records per range
+//                 (k_range_scan); ONE read-back.  A slice that was too small: BSK_ERR_FILTER_FALLBACK, the bit cleared.
+struct SlicePass {
+    int per_cu;
+    const char* scale_switch;
+    uint64_t budget;
+    const char *stage_pass, *stage_compact;
+    std::function<int(const uint8_t* head, size_t hb, double* ratio)> ratio;
+    std::function<hipError_t(int blocks, uint32_t nranges, uint32_t* queue, uint8_t* slices, uint64_t slice_cap, uint64_t* range_bytes,
+                             uint64_t* range_count)> launch;
+};
+int run_slice_pass(bsk_ctx* c, const uint8_t* d_buf, size_t n, const SlicePass& S, hipStream_t st, bsk_out* out);
 const char* alphabet_letters(Alphabet a);
 void complement_table(Alphabet ab, uint8_t m[256]);
 // lines of a text file ("\r\n" trimmed, empty lines skipped): pattern files, region files

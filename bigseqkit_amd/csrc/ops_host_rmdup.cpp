@@ -258,9 +258,8 @@ int rmdup_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hip
         if (rc != BSK_OK) return rc;
         uint64_t status = c->status_word();
         if (status & ERR_BUCKET_OVERFLOW) {
-            status &= ~(uint64_t)ERR_BUCKET_OVERFLOW;
-            HIP_TRYX(c, hipMemcpyAsync(c->d_status, &status, sizeof status, hipMemcpyHostToDevice, st));
-            HIP_TRYX(c, hipStreamSynchronize(st));
+            rc = clear_status_bits(c, &status, ERR_BUCKET_OVERFLOW, st);
+            if (rc != BSK_OK) return rc;
             by_buckets = false;
         } else if (by_keys) {
             rc = with_k2 ? rmdup_settle_overflow(c, d_first, st, c->h_ctl[3]) : BSK_OK;  // (k1 alone: no list, the bytes tell)
@@ -835,12 +834,11 @@ int rmdup_dist_xapply(bsk_ctx* c, const uint8_t* d_verdict_back, uint64_t* n_fla
         rc = ctl_readback(c, st);
         if (rc != BSK_OK) return rc;
         c->dist_local_pairs = c->fin(bsk_ctx::FIN_AUX0);
-        const uint64_t status = c->status_word();
+        uint64_t status = c->status_word();
         if (status & ERR_HASH_COLLISION) {
-            uint64_t rest = status & ~(uint64_t)ERR_HASH_COLLISION;
-            HIP_TRYX(c, hipMemcpyAsync(c->d_status, &rest, sizeof rest, hipMemcpyHostToDevice, st));
-            HIP_TRYX(c, hipStreamSynchronize(st));
-            if (rest) return kernel_error_to_status(c, rest);
+            rc = clear_status_bits(c, &status, ERR_HASH_COLLISION, st);
+            if (rc != BSK_OK) return rc;
+            if (status) return kernel_error_to_status(c, status);
         } else {
             rc = kernel_error_to_status(c, status);
             if (rc != BSK_OK) return rc;

@@ -45,75 +45,34 @@ namespace bsk {
 // sized from the header density of the shard head, one scan over the ranges, one gather.  BSK_ERR_FILTER_FALLBACK: a
 // slice was too small (or the estimate does not fit); the caller takes the record-table path.
 static int seq_names_run(bsk_ctx* c, const uint8_t* d_buf, size_t n, hipStream_t st, bsk_out* out) {
-    const Options& o = c->opts;
-    const int blocks = std::max(1, c->num_cus * names_max_blocks_per_cu(c->use_dpp));
-    uint32_t nranges = 0;
-    uint64_t chunk = 0;
-    int rc = prep_ranges(c, d_buf, n, /*fastq=*/true, blocks, st, &nranges, &chunk);
-    if (rc != BSK_OK) return rc;
-    rc = sample_head(c, d_buf, n, st);  // (the call's one head sample, pinned)
-    if (rc != BSK_OK) return rc;
-    const size_t hb = c->head_len;
-    const uint8_t* head = c->h_head;
-    if (!c->norm_active && fastq_head_multiline(head, hb)) return BSK_ERR_MULTILINE_FASTQ;
-    uint64_t hdr = 0, line = 0;
-    for_lines(head, hb, [&](size_t s0, size_t e0, bool) {  // (a header cut by the end of the sample counts as far as it goes)
-        if ((line & 3) == 0) hdr += e0 - s0;
-        ++line;
-    });
-    double ratio = (double)(hdr + 64) / (double)hb;
-    if (const char* sc = c->tune.get("names_scale")) ratio *= atof(sc);  // tests: force the overflow -> fallback route
-    uint64_t slice_cap = (uint64_t)((double)chunk * ratio * 1.25) + (c->tune.get("names_scale") ? 16 : 4096);
-    slice_cap = (slice_cap + 15) & ~(uint64_t)15;
-    if (slice_cap >= (1ull << 32) || slice_cap * nranges > (uint64_t)n + (64ull << 20)) return BSK_ERR_FILTER_FALLBACK;
-    rc = grow(c, &c->d_slices, &c->slices_cap, slice_cap * nranges, 256);
-    if (rc != BSK_OK) return rc;
-    rc = grow(c, &c->d_names_aux, &c->names_aux_cap, 2 * ((uint64_t)nranges + 2), 16);
-    if (rc != BSK_OK) return rc;
-    NamesDev D;
-    D.slices = c->d_slices;
-    D.slice_cap = slice_cap;
-    D.range_bytes = c->d_names_aux;
-    D.range_count = c->d_range_count;
-    D.status = c->d_status;
-    D.only_id = o.b("OnlyId") ? 1 : 0;
-    D.id_mode = id_mode_of(c);
-    uint64_t* d_count_base = c->d_names_aux + nranges + 2;
-    {
-        Timed t(c, "k_names", st);
-        HIP_TRYX(c, launch_names(c->use_dpp, blocks, d_buf, n, c->d_anchors,
-                                 nranges, reinterpret_cast<uint32_t*>(c->d_anchors + (size_t)nranges + 1), D, st));
-    }
-    {
-        Timed t(c, "k_range_scan", st);
-        HIP_TRYX(c, launch_scan_small2(D.range_bytes, c->d_range_base, c->d_fin + bsk_ctx::FIN_AUX0, D.range_count, d_count_base,
-                                       c->d_fin + bsk_ctx::FIN_AUX1, nranges, st));
-    }
-    rc = ctl_readback(c, st);  // bytes, records, status: one copy
-    if (rc != BSK_OK) return rc;
-    const uint64_t total = c->fin(bsk_ctx::FIN_AUX0), records = c->fin(bsk_ctx::FIN_AUX1);
-    uint64_t status = c->status_word();
-    if (status & ERR_CAPACITY) {
-        status &= ~(uint64_t)ERR_CAPACITY;
-        HIP_TRYX(c, hipMemcpyAsync(c->d_status, &status, sizeof status, hipMemcpyHostToDevice, st));
-        HIP_TRYX(c, hipStreamSynchronize(st));
-        if (status == 0) return BSK_ERR_FILTER_FALLBACK;
-    }
-    if (status) return kernel_error_to_status(c, status);
-    c->table.n = 0;  // no record table was built for this shard
-    if (total && slices_wanted(c))  // round 6: the per-range slices ARE the result, in order (include/bsk.h bsk_out.d_seg_*)
-        return out_as_slices(c, out, D.slices, D.slice_cap, c->d_range_base, nranges, total, records, st);
-    rc = ensure_out(c, total);
-    if (rc != BSK_OK) return rc;
-    if (total) {
-        Timed t(c, "k_names_compact", st);
-        HIP_TRYX(c, launch_names_compact(D, c->d_range_base, nranges, c->d_out, st));
-    }
-    c->table.n = 0;  // no record table was built for this shard
-    out->d_data = c->d_out;
-    out->len = total;
-    out->records = records;
-    return BSK_OK;
+    SlicePass S;
+    S.per_cu = names_max_blocks_per_cu(c->use_dpp);
+    S.scale_switch = "names_scale";
+    S.budget = (uint64_t)n + (64ull << 20);
+    S.stage_pass = "k_names";
+    S.stage_compact = "k_names_compact";
+    S.ratio = [](const uint8_t* head, size_t hb, double* ratio) -> int {  // header bytes per input byte
+        uint64_t hdr = 0, line = 0;
+        for_lines(head, hb, [&](size_t s0, size_t e0, bool) {  // (a header cut by the end of the sample counts as far as it goes)
+            if ((line & 3) == 0) hdr += e0 - s0;
+            ++line;
+        });
+        *ratio = (double)(hdr + 64) / (double)hb;
+        return BSK_OK;
+    };
+    S.launch = [&](int blocks, uint32_t nranges, uint32_t* queue, uint8_t* slices, uint64_t slice_cap, uint64_t* range_bytes,
+                   uint64_t* range_count) {
+        NamesDev D;
+        D.slices = slices;
+        D.slice_cap = slice_cap;
+        D.range_bytes = range_bytes;
+        D.range_count = range_count;
+        D.status = c->d_status;
+        D.only_id = c->opts.b("OnlyId") ? 1 : 0;
+        D.id_mode = id_mode_of(c);
+        return launch_names(c->use_dpp, blocks, d_buf, n, c->d_anchors, nranges, queue, D, st);
+    };
+    return run_slice_pass(c, d_buf, n, S, st, out);
 }
 
 int seq_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, bsk_out* out) {

@@ -336,9 +336,7 @@ int translate_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format,
         !c->tune.is("translate_stream", "off") && !P.init_m && !P.trim && !P.append_frame && !c->id_custom && (P.line_width == 0 || P.line_width >= 16)) {
         rc = sample_head(c, d_buf, n, st);
         if (rc != BSK_OK) return rc;
-        uint64_t heads = 1;
-        for (size_t i = 0; i + 1 < c->head_len; ++i) heads += (c->h_head[i] == '\n' && c->h_head[i + 1] == '>');
-        const uint64_t avg = c->head_len / heads;
+        const uint64_t avg = c->head_len / head_record_count(c->h_head, c->head_len, /*fastq=*/false);
         if (avg >= 1500 || c->tune.is("translate_stream", "force")) {   // (a wave per record: from ~3 k bases; shorter records take 4 / 16 lanes)
             Alphabet ab = partition_alphabet(c, d_buf, n, format, st, &rc);
             if (rc != BSK_OK) return rc;
@@ -357,7 +355,7 @@ int translate_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format,
             want_chunk = std::max<uint64_t>(16, want_chunk & ~15ull);
             rc = prep_ranges(c, d_buf, n, false, blocks, st, &nranges, &chunk, want_chunk);
             if (rc != BSK_OK) return rc;
-            uint32_t* queue = reinterpret_cast<uint32_t*>(c->d_anchors + (size_t)nranges + 1);
+            uint32_t* queue = range_queue(c, nranges);
             // six frames of L bases are 2 L residues + their line breaks + six headers: the reserved room is checked per record
             const uint64_t out_cap = (uint64_t)n * (uint64_t)std::max(1, P.nframes) * 3 / 8 + (64ull << 20);
             rc = ensure_out(c, out_cap);

@@ -1756,9 +1756,7 @@ hipError_t launch_translate_stream(int blocks, const uint8_t* buf, uint64_t buf_
     return hipGetLastError();
 }
 int translate_stream_max_blocks_per_cu() {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k_translate_stream, 256, 0) != hipSuccess || nb < 1) nb = 1;
-    return nb;
+    return blocks_per_cu((const void*)k_translate_stream, 256);
 }
 
 hipError_t launch_translate_size(const uint8_t* buf, const RecordTable& t, const TextTableH& tt,

@@ -179,9 +179,7 @@ hipError_t launch_fasta_starts(int blocks, const uint8_t* buf, uint64_t n_eff, u
 }
 
 int fasta_starts_max_blocks_per_cu() {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k_fasta_starts, WAVES_PER_BLOCK * WAVE, 0) != hipSuccess || nb < 1) nb = 1;
-    return nb;
+    return blocks_per_cu((const void*)k_fasta_starts, WAVES_PER_BLOCK * WAVE);
 }
 
 hipError_t launch_fasta_starts_compact(const uint64_t* sparse, uint64_t sparse_cap, const uint64_t* range_count,

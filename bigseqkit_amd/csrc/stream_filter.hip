@@ -423,10 +423,7 @@ hipError_t launch_filter(bool dpp, int blocks, const uint8_t* buf, uint64_t n, c
 }
 
 int filter_max_blocks_per_cu(bool dpp) {
-    int nb = 0;
-    const void* f = dpp ? (const void*)k_filter<true> : (const void*)k_filter<false>;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, f, WAVES_PER_BLOCK * WAVE, 0) != hipSuccess || nb < 1) nb = 1;
-    return nb;
+    return blocks_per_cu(dpp ? (const void*)k_filter<true> : (const void*)k_filter<false>, WAVES_PER_BLOCK * WAVE);
 }
 
 }  // namespace bsk

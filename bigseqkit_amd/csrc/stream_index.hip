@@ -722,11 +722,9 @@ hipError_t launch_index(bool fastq, bool dpp, int blocks, const uint8_t* buf, ui
 }
 
 int index_max_blocks_per_cu(bool fastq, bool dpp) {
-    int nb = 0;
     const void* f = fastq ? (dpp ? (const void*)k_index<true, true> : (const void*)k_index<true, false>)
                           : (dpp ? (const void*)k_index<false, true> : (const void*)k_index<false, false>);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, f, WAVES_PER_BLOCK * WAVE, 0) != hipSuccess || nb < 1) nb = 1;
-    return nb;
+    return blocks_per_cu(f, WAVES_PER_BLOCK * WAVE);
 }
 
 hipError_t launch_scan_small(const uint64_t* in, uint64_t* out, uint32_t n, hipStream_t st, uint64_t* total_at) {

@@ -396,17 +396,14 @@ hipError_t launch_names(bool dpp, int blocks, const uint8_t* buf, uint64_t n, co
 }
 
 int names_max_blocks_per_cu(bool dpp) {
-    int nb = 0;
-    const void* f = dpp ? (const void*)k_names<true> : (const void*)k_names<false>;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, f, WAVES_PER_BLOCK * WAVE, 0) != hipSuccess || nb < 1) nb = 1;
-    return nb;
+    return blocks_per_cu(dpp ? (const void*)k_names<true> : (const void*)k_names<false>, WAVES_PER_BLOCK * WAVE);
 }
 
-hipError_t launch_names_compact(const NamesDev& D, const uint64_t* range_base, uint32_t nranges, uint8_t* out, hipStream_t st) {
-    const uint32_t cpr = (uint32_t)((D.slice_cap + COMPACT_CHUNK - 1) / COMPACT_CHUNK);
+hipError_t launch_slices_compact(const uint8_t* slices, uint64_t slice_cap, const uint64_t* range_bytes, const uint64_t* range_base,
+                                 uint32_t nranges, uint8_t* out, hipStream_t st) {
+    const uint32_t cpr = (uint32_t)((slice_cap + COMPACT_CHUNK - 1) / COMPACT_CHUNK);
     if (nranges == 0 || cpr == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_names_compact, dim3(nranges * cpr), dim3(256), 0, st, D.slices, D.slice_cap, D.range_bytes, range_base,
-                       cpr, out);
+    hipLaunchKernelGGL(k_names_compact, dim3(nranges * cpr), dim3(256), 0, st, slices, slice_cap, range_bytes, range_base, cpr, out);
     return hipGetLastError();
 }
 

@@ -19,7 +19,9 @@ struct NamesDev {
 hipError_t launch_names(bool dpp, int blocks, const uint8_t* buf, uint64_t n, const uint64_t* anchors, uint32_t nranges,
                         uint32_t* queue, const NamesDev& D, hipStream_t st);
 int names_max_blocks_per_cu(bool dpp);
-// out[range_base[r] .. + range_bytes[r]) = slice r
-hipError_t launch_names_compact(const NamesDev& D, const uint64_t* range_base, uint32_t nranges, uint8_t* out, hipStream_t st);
+// the per-range slices of a streaming pass (this one, stream_subseq.hip) as one text: out[range_base[r] .. + range_bytes[r]) =
+// slices[r * slice_cap ..)
+hipError_t launch_slices_compact(const uint8_t* slices, uint64_t slice_cap, const uint64_t* range_bytes, const uint64_t* range_base,
+                                 uint32_t nranges, uint8_t* out, hipStream_t st);
 
 }  // namespace bsk

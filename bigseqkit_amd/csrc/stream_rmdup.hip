@@ -398,9 +398,7 @@ hipError_t launch_rmdup_stream(bool dpp, bool fold, int mode, int blocks, const 
 }
 
 int rmdup_stream_max_blocks_per_cu(bool dpp, bool fold, int mode) {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel_of(dpp, fold, mode), WAVES_PER_BLOCK * WAVE, 0) != hipSuccess || nb < 1) nb = 1;
-    return nb;
+    return blocks_per_cu(kernel_of(dpp, fold, mode), WAVES_PER_BLOCK * WAVE);
 }
 
 hipError_t launch_rmdup_compact(const RecordTable& sparse, uint64_t sparse_cap, const uint64_t* range_count,

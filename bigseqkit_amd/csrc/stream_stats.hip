@@ -786,9 +786,8 @@ hipError_t launch_stats(bool fastq, bool all, bool dpp, int blocks, const uint8_
 }
 
 int stats_max_blocks_per_cu(bool fastq, bool all, bool dpp, bool a_dense) {
-    int nb = 0;
     const void* f = nullptr;
-#define BSK_PICK(FQ, AL, RO)                                                             \
+#define BSK_PICK(FQ, AL, RO)                                                            \
     f = dpp ? (const void*)k_stats<FQ, AL, true, RO> : (const void*)k_stats<FQ, AL, false, RO>;
     if (fastq && all && a_dense) { BSK_PICK(true, true, false) }
     else if (fastq && all) { BSK_PICK(true, true, true) }
@@ -798,8 +797,7 @@ int stats_max_blocks_per_cu(bool fastq, bool all, bool dpp, bool a_dense) {
     else if (a_dense) { BSK_PICK(false, false, false) }
     else { BSK_PICK(false, false, true) }
 #undef BSK_PICK
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, f, WAVES_PER_BLOCK * WAVE, 0) != hipSuccess || nb < 1) nb = 1;
-    return nb;
+    return blocks_per_cu(f, WAVES_PER_BLOCK * WAVE);
 }
 
 hipError_t launch_stream_read(int blocks, const uint8_t* buf, uint64_t n, uint64_t chunk, uint32_t nranges,

@@ -18,6 +18,14 @@ constexpr uint32_t ERR_ANCHOR = 16u;        // a range did not end on a record b
 constexpr uint32_t ERR_LINE_TOO_LONG = 32u; // a line longer than 2^31 bytes
 constexpr uint32_t ERR_CAPACITY = 64u;      // an output table was too small
 
+// blocks of `threads` threads that one CU holds of `kernel` at once: what every *_max_blocks_per_cu answers for the kernel
+// it selects (every streaming .hip file sees this header).  A query that fails, or answers 0, counts as one block.
+inline int blocks_per_cu(const void* kernel, int threads) {
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, threads, 0) != hipSuccess || nb < 1) nb = 1;
+    return nb;
+}
+
 // constants of the byte predicates (only read by the -a kernels)
 struct PredConsts {
     uint32_t k20, k30;  // (0x80 - threshold) replicated in the 4 bytes

@@ -246,10 +246,7 @@ hipError_t launch_subseq_stream(bool dpp, int blocks, const uint8_t* buf, uint64
 }
 
 int subseq_stream_max_blocks_per_cu(bool dpp) {
-    int nb = 0;
-    const void* f = dpp ? (const void*)k_subseq_stream<true> : (const void*)k_subseq_stream<false>;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, f, WAVES_PER_BLOCK * WAVE, 0) != hipSuccess || nb < 1) nb = 1;
-    return nb;
+    return blocks_per_cu(dpp ? (const void*)k_subseq_stream<true> : (const void*)k_subseq_stream<false>, WAVES_PER_BLOCK * WAVE);
 }
 
 }  // namespace bsk

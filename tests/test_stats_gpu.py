@@ -180,6 +180,28 @@ def test_more_than_eight_gap_letters(gaps, monkeypatch):
     check_parity(one_line, False, {"All": True, "GapLetters": gaps})
 
 
+def test_one_context_shrinks_and_grows_its_ranges_with_more_than_eight_gap_letters(monkeypatch):
+    """`stats -a` with nine gap letters runs two streaming passes per shard, k_stats and the index pass of the record table, on
+    the same range arrays of the context (anchors, counts per range, their scan).  One context takes shards of 1, 16 and 1
+    ranges: the arrays are sized by one function (ensure_range_arrays) whichever pass comes first, and the map -- the context
+    accumulates -- equals the oracle's for the text so far after every shard.  (At these sizes the allocator's granule would
+    hide an array that is too short: this pins the sequence, the single owner is the guarantee.)"""
+    monkeypatch.setenv("BSK_MIN_RANGE_BYTES", "4096")
+    rng = random.Random(2718)
+    a, b, c = (seqgen.random_fastq(rng, 300, 50, 150, alphabet="ACGTNacgtn-.*Xx") for _ in range(3))
+    shards = [a, (b + c) * 17, c]   # ~64 KiB, ~2 MiB, ~64 KiB: pick_nranges gives 1, 16 and 1 ranges
+    assert all(oracle.is_strict_4line_fastq(s) for s in shards)
+    assert len(a) < 128 << 10 and len(c) < 128 << 10 and len(shards[1]) // (128 << 10) == 16
+    opts = {"All": True, "GapLetters": "-.*NnXx ~"}
+    with bsk.Operator("Stats", json.dumps(opts), 0) as op:
+        seen = b""
+        for k, s in enumerate(shards):
+            t = dev(s)
+            _lib.check(lib.bsk_stats_run(op.ctx, C.c_void_p(t.data_ptr()), len(s), 1, bsk.FORMAT_FASTQ, k, None, None), op.ctx)
+            seen += s
+            assert bsk.api._collect_map(op, None) == oracle.stats_map(seen, True, json.dumps(opts)), k
+
+
 def test_host_resident_shard():
     rng = random.Random(13)
     data = seqgen.random_fastq(rng, 800, 0, 150)
