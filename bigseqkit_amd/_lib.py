@@ -145,6 +145,19 @@ SIGNATURES = {
     "bsk_shuffle_bucket_begin": (_i, [_vp, C.c_uint32, C.c_uint32]),
     "bsk_shuffle_bucket_add": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp]),
     "bsk_shuffle_bucket_finish": (_i, [_vp, _vp, _p(Out)]),
+    "bsk_sort_sample_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, C.c_double, _vp, _p(C.c_uint64)]),
+    "bsk_sort_sample_reset": (_i, [_vp]),
+    "bsk_sort_sample_count": (_i, [_vp, _p(C.c_uint64)]),
+    "bsk_sort_pick_splitters": (_i, [C.c_char_p, _p(C.c_uint64), C.c_uint64, C.c_uint32, C.c_char_p, C.c_uint64, _p(C.c_uint64), _p(C.c_uint32)]),
+    "bsk_sort_splitters_build": (_i, [_vp, C.c_uint32, _p(C.c_uint32)]),
+    "bsk_sort_splitters_set": (_i, [_vp, C.c_char_p, _p(C.c_uint64), C.c_uint32]),
+    "bsk_sort_splitters_get": (_i, [_vp, C.c_char_p, C.c_uint64, _p(C.c_uint64), _p(C.c_uint32), _p(C.c_uint64)]),
+    "bsk_sort_hist_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp, _p(C.c_uint64)]),
+    "bsk_sort_hist_get": (_i, [_vp, _p(C.c_uint64), _p(C.c_uint64)]),
+    "bsk_sort_hist_reset": (_i, [_vp]),
+    "bsk_sort_bucket_begin": (_i, [_vp, C.c_uint32, C.c_uint32]),
+    "bsk_sort_bucket_add": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp]),
+    "bsk_sort_bucket_finish": (_i, [_vp, _vp, _p(Out)]),
     "bsk_head_genome_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, _vp, _p(Out)]),
     "bsk_head_genome_reset": (_i, [_vp]),
     "bsk_head_genome_state": (_i, [_vp, _p(C.c_int), _p(C.c_uint64)]),

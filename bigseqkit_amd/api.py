@@ -6,6 +6,7 @@ Same entry points, argument meaning and error behaviour as
 sequence of C-ABI calls into libbsk.so (include/bsk.h) instead of IgnisHPC tasks.
 """
 import ctypes as C
+import json
 import os
 
 from . import _lib
@@ -494,6 +495,145 @@ def ShuffleBuckets(input, o=None, budget_bytes=1 << 30, device=0):
         counts = ShuffleHistRun(op, input)
         bounds = ShufflePlan(ShuffleHistGet(op)[0], budget_bytes)
         return b"".join(ShuffleBucket(op, input, counts, lo, hi) for lo, hi in zip(bounds[:-1], bounds[1:]))
+
+
+SORT_BINS = 4096
+SORT_SAMPLES_PER_BIN = 32   # a starting value from sample-sort practice, not a measurement
+
+
+def _pack_strings(strings):
+    offs = (C.c_uint64 * (len(strings) + 1))()
+    at = 0
+    for j, s in enumerate(strings):
+        at += len(s)
+        offs[j + 1] = at
+    return b"".join(strings), offs
+
+
+def SortPickSplitters(keys, max_bins=SORT_BINS):
+    """bsk_sort_pick_splitters (no device): at most max_bins - 1 strictly ascending splitters at the quantiles of `keys`"""
+    blob, offs = _pack_strings(keys)
+    out = C.create_string_buffer(max(1, len(blob)))
+    o = (C.c_uint64 * max_bins)()
+    k = C.c_uint32()
+    check(lib.bsk_sort_pick_splitters(blob, offs, len(keys), max_bins, out, len(blob), o, C.byref(k)))
+    return [out.raw[o[j]:o[j + 1]] for j in range(k.value)]
+
+
+def SortSampleRun(op, input, rate):
+    """bsk_sort_sample_run over the shards of `input`, in order: the record count of every shard (the sample accumulates in
+    the operator's context)"""
+    counts, first = [], 0
+    for pid, ptr, n, on_dev, keep in input.partitions():
+        k = C.c_uint64()
+        check(lib.bsk_sort_sample_run(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, rate, None, C.byref(k)), op.ctx)
+        counts.append(k.value)
+        first += k.value
+    return counts
+
+
+def SortSampleReset(op):
+    check(lib.bsk_sort_sample_reset(op.ctx), op.ctx)
+
+
+def SortSampleCount(op):
+    k = C.c_uint64()
+    check(lib.bsk_sort_sample_count(op.ctx, C.byref(k)), op.ctx)
+    return k.value
+
+
+def SortSplittersBuild(op, max_bins=SORT_BINS):
+    """bsk_sort_splitters_build: splitters from the context's sample, installed; the number of fine bins"""
+    k = C.c_uint32()
+    check(lib.bsk_sort_splitters_build(op.ctx, max_bins, C.byref(k)), op.ctx)
+    return k.value
+
+
+def SortSplittersSet(op, splitters):
+    """bsk_sort_splitters_set: splitters (byte strings, strictly ascending under the padded comparison) installed by hand"""
+    blob, offs = _pack_strings(splitters)
+    check(lib.bsk_sort_splitters_set(op.ctx, blob, offs, len(splitters)), op.ctx)
+
+
+def SortSplittersGet(op):
+    """bsk_sort_splitters_get: the installed splitters"""
+    k, nb = C.c_uint32(), C.c_uint64()
+    check(lib.bsk_sort_splitters_get(op.ctx, None, 0, None, C.byref(k), C.byref(nb)), op.ctx)
+    buf = C.create_string_buffer(max(1, nb.value))
+    offs = (C.c_uint64 * (k.value + 1))()
+    check(lib.bsk_sort_splitters_get(op.ctx, buf, nb.value, offs, C.byref(k), C.byref(nb)), op.ctx)
+    return [buf.raw[offs[j]:offs[j + 1]] for j in range(k.value)]
+
+
+def SortHistRun(op, input):
+    """bsk_sort_hist_run over the shards of `input`, in order: the record count of every shard"""
+    counts, first = [], 0
+    for pid, ptr, n, on_dev, keep in input.partitions():
+        k = C.c_uint64()
+        check(lib.bsk_sort_hist_run(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None, C.byref(k)), op.ctx)
+        counts.append(k.value)
+        first += k.value
+    return counts
+
+
+def SortHistGet(op):
+    """bsk_sort_hist_get: (bytes[4096], records[4096])"""
+    b, r = (C.c_uint64 * SORT_BINS)(), (C.c_uint64 * SORT_BINS)()
+    check(lib.bsk_sort_hist_get(op.ctx, b, r), op.ctx)
+    return list(b), list(r)
+
+
+def SortHistReset(op):
+    check(lib.bsk_sort_hist_reset(op.ctx), op.ctx)
+
+
+def SortBucket(op, input, counts, lo_bin, hi_bin):
+    """bsk_sort_bucket_begin / _add over the shards of `input`, in order / _finish: the sorted bytes of the bucket [lo_bin, hi_bin)"""
+    check(lib.bsk_sort_bucket_begin(op.ctx, lo_bin, hi_bin), op.ctx)
+    first = 0
+    for (pid, ptr, n, on_dev, keep), cnt in zip(input.partitions(), counts):
+        check(lib.bsk_sort_bucket_add(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None), op.ctx)
+        first += cnt
+    out = _lib.Out()
+    check(lib.bsk_sort_bucket_finish(op.ctx, None, C.byref(out)), op.ctx)
+    buf = C.create_string_buffer(max(1, out.len))
+    check(lib.bsk_out_to_host(op.ctx, C.byref(out), buf, out.len), op.ctx)
+    return buf.raw[:out.len]
+
+
+def SortBucketsPlan(op, input, o, budget_bytes, splitters=None, rate=None, device=0):
+    """The passes of SortBuckets in front of the buckets, on an open Sort operator: the splitters (given by hand, or built from
+    a sample of the keys at `rate`; default: about SORT_SAMPLES_PER_BIN samples per fine bin, from a count of the records --
+    Count(input), one more index pass over every shard; a caller that knows the number of records passes the rate),
+    the histogram and the plan (ShufflePlan).  Returns the buckets [(lo_bin, hi_bin)] in output order -- from the last to
+    the first with Reverse -- and the record count of every shard."""
+    if splitters is None:
+        if rate is None:
+            total = sum(Count(input, device))
+            rate = min(1.0, SORT_SAMPLES_PER_BIN * SORT_BINS / max(1, total))
+        SortSampleReset(op)
+        SortSampleRun(op, input, rate)
+        SortSplittersBuild(op)
+    else:
+        SortSplittersSet(op, splitters)
+    SortHistReset(op)
+    counts = SortHistRun(op, input)
+    bounds = ShufflePlan(SortHistGet(op)[0], budget_bytes)
+    buckets = list(zip(bounds[:-1], bounds[1:]))
+    if json.loads(o.to_json()).get("Reverse"):
+        buckets.reverse()
+    return buckets, counts
+
+
+def SortBuckets(input, o=None, budget_bytes=1 << 30, device=0, splitters=None, rate=None):
+    """Sort of an input of any size on one device (PARITY SORT, "Buckets"): a sample of the keys gives the splitters, the
+    histogram over all shards the plan of buckets of at most `budget_bytes`, then one collect sequence per bucket, every
+    bucket sorted by Sort's own code; the same bytes as Sort.  The input is read twice plus once per bucket -- and once more,
+    by the index pass alone, for the count of the records that gives the default sample rate (`rate` given: not)."""
+    o = o or SeqKitSortOptions()
+    with Operator("Sort", o.to_json(), device) as op:
+        buckets, counts = SortBucketsPlan(op, input, o, budget_bytes, splitters, rate, device)
+        return b"".join(SortBucket(op, input, counts, lo, hi) for lo, hi in buckets)
 
 
 def HeadGenome(input, o=None, device=0):

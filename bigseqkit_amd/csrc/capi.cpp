@@ -15,6 +15,7 @@
 #include "ops_host.hpp"
 #include "ops_host_internal.hpp"
 #include "ops_sample.hpp"
+#include "ops_sort_buckets.hpp"
 #include "ops_segcopy.hpp"
 #include "stats_host.hpp"
 #include "stream_stats.hpp"
@@ -369,6 +370,8 @@ void bsk_destroy(bsk_ctx* c) {
         for (void* p : {(void*)c->d_hg_words, (void*)c->d_hg_off, (void*)c->d_hg_counts, (void*)c->d_hg_res})
             if (p) hipFree(p);
         for (void* p : {(void*)c->shb.d_hist, (void*)c->shb.d_acc, (void*)c->shb.d_draw, (void*)c->shb.d_off, (void*)c->shb.d_len})
+            if (p) hipFree(p);
+        for (void* p : {(void*)c->sob.d_hist, (void*)c->sob.d_acc, (void*)c->sob.d_spl, (void*)c->sob.d_spl_off})
             if (p) hipFree(p);
         if (c->d_vm_progs) hipFree(c->d_vm_progs);
         if (c->d_id_off) hipFree(c->d_id_off);
@@ -1262,6 +1265,154 @@ int bsk_shuffle_bucket_finish(bsk_ctx* c, void* stream, bsk_out* out) {
     BSK_ENTER(c);
     c->pend_out.kind = 0;
     return shuffle_bucket_finish(c, (hipStream_t)stream, out);
+}
+
+// ---- sort in buckets of the key (include/bsk.h; the passes are in ops_host_sortbuckets.cpp).  A wrapped FASTQ shard runs once
+// more as its 4-line rewrite (run_multiline), like bsk_sort_run's
+static int sort_ctx_check(bsk_ctx* c) {
+    if (!c) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: null context");
+    if (c->op != Op::Sort) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: not a Sort context");
+    if (c->device < 0) return fail(c, BSK_ERR_NO_DEVICE, "libbsk: context was created without a device");
+    return BSK_OK;
+}
+
+int bsk_sort_sample_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                        double rate, void* stream, uint64_t* n_records) {
+    return record_call(c, nullptr, Op::Sort, true, "", shard, n, on_device, format, stream, CallValues(), [&](const uint8_t* d, hipStream_t st) {
+        return run_multiline(c, [&](const uint8_t* t, const uint64_t* e) { return sort_sample_device(c, t, e[0], format, first_record, rate, st, n_records); },
+                             d, {n}, format, st);
+    });
+}
+
+int bsk_sort_sample_reset(bsk_ctx* c) {
+    if (!c) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: null context");
+    if (c->op != Op::Sort) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: not a Sort context");
+    bsk_call_scope scope(c);
+    if (!scope.owns) return fail_busy();
+    sort_sample_reset(c);
+    return BSK_OK;
+}
+
+int bsk_sort_sample_count(bsk_ctx* c, uint64_t* n_samples) {
+    if (!c || !n_samples) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: null argument");
+    if (c->op != Op::Sort) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: not a Sort context");
+    bsk_call_scope scope(c);
+    if (!scope.owns) return fail_busy();
+    *n_samples = c->sob.sample_keys.size();
+    return BSK_OK;
+}
+
+// splitter j = bytes[offsets[j], offsets[j + 1])
+static std::vector<std::string> strings_of(const uint8_t* bytes, const uint64_t* offsets, uint64_t k) {
+    std::vector<std::string> v;
+    v.reserve((size_t)k);
+    for (uint64_t j = 0; j < k; ++j) v.emplace_back(reinterpret_cast<const char*>(bytes) + offsets[j], (size_t)(offsets[j + 1] - offsets[j]));
+    return v;
+}
+
+int bsk_sort_pick_splitters(const uint8_t* keys, const uint64_t* key_offsets, uint64_t n_keys, uint32_t max_bins, uint8_t* bytes,
+                            uint64_t bytes_cap, uint64_t* offsets, uint32_t* k) {
+    if ((n_keys && (!keys || !key_offsets)) || !offsets || !k || max_bins < 1 || max_bins > SORT_BINS)
+        return fail(nullptr, BSK_ERR_INVALID_ARG, "libbsk: bsk_sort_pick_splitters: null argument, or max_bins outside 1 .. 4096");
+    for (uint64_t j = 0; j < n_keys; ++j)
+        if (key_offsets[j] > key_offsets[j + 1]) return fail(nullptr, BSK_ERR_INVALID_ARG, "libbsk: bsk_sort_pick_splitters: the key offsets go backwards");
+    const std::vector<std::string> sp = sort_pick_splitters(strings_of(keys, key_offsets, n_keys), max_bins);
+    uint64_t at = 0;
+    offsets[0] = 0;
+    for (size_t j = 0; j < sp.size(); ++j) {
+        if (at + sp[j].size() > bytes_cap || (sp[j].size() && !bytes)) return fail(nullptr, BSK_ERR_CAPACITY, "libbsk: bsk_sort_pick_splitters: output buffer too small");
+        memcpy(bytes + at, sp[j].data(), sp[j].size());
+        at += sp[j].size();
+        offsets[j + 1] = at;
+    }
+    *k = (uint32_t)sp.size();
+    return BSK_OK;
+}
+
+int bsk_sort_splitters_build(bsk_ctx* c, uint32_t max_bins, uint32_t* n_bins) {
+    const int rc = sort_ctx_check(c);
+    if (rc != BSK_OK) return rc;
+    if (max_bins < 1 || max_bins > SORT_BINS) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_sort_splitters_build: max_bins must be 1 .. 4096");
+    BSK_ENTER(c);
+    return sort_splitters_build(c, max_bins, n_bins);
+}
+
+int bsk_sort_splitters_set(bsk_ctx* c, const uint8_t* bytes, const uint64_t* offsets, uint32_t k) {
+    const int rc = sort_ctx_check(c);
+    if (rc != BSK_OK) return rc;
+    if (k && !offsets) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_sort_splitters_set: null argument");
+    for (uint32_t j = 0; j < k; ++j)
+        if (offsets[j] > offsets[j + 1] || (offsets[j + 1] && !bytes))
+            return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_sort_splitters_set: the offsets go backwards");
+    BSK_ENTER(c);
+    return sort_splitters_install(c, strings_of(bytes, offsets, k));
+}
+
+int bsk_sort_splitters_get(bsk_ctx* c, uint8_t* bytes, uint64_t bytes_cap, uint64_t* offsets, uint32_t* k, uint64_t* n_bytes) {
+    if (!c || !k) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: null argument");
+    if (c->op != Op::Sort) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: not a Sort context");
+    bsk_call_scope scope(c);
+    if (!scope.owns) return fail_busy();
+    const bsk_ctx::SortBuckets& B = c->sob;
+    *k = (uint32_t)(B.spl_off.size() - 1);
+    if (n_bytes) *n_bytes = B.spl_bytes.size();
+    if (!bytes && !offsets) return BSK_OK;  // (the sizes alone)
+    if (B.spl_bytes.size() > bytes_cap || (!bytes && !B.spl_bytes.empty()) || !offsets)
+        return fail(c, BSK_ERR_CAPACITY, "libbsk: bsk_sort_splitters_get: output buffer too small");
+    if (!B.spl_bytes.empty()) memcpy(bytes, B.spl_bytes.data(), B.spl_bytes.size());
+    for (size_t j = 0; j < B.spl_off.size(); ++j) offsets[j] = B.spl_off[j];
+    return BSK_OK;
+}
+
+int bsk_sort_hist_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                      void* stream, uint64_t* n_records) {
+    return record_call(c, nullptr, Op::Sort, true, "", shard, n, on_device, format, stream, CallValues(), [&](const uint8_t* d, hipStream_t st) {
+        return run_multiline(c, [&](const uint8_t* t, const uint64_t* e) { return sort_hist_device(c, t, e[0], format, st, n_records); }, d, {n}, format, st);
+    });
+}
+
+int bsk_sort_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) {
+    const int rc = sort_ctx_check(c);
+    if (rc != BSK_OK) return rc;
+    BSK_ENTER(c);
+    return sort_hist_get(c, bytes, records);
+}
+
+int bsk_sort_hist_reset(bsk_ctx* c) {
+    const int rc = sort_ctx_check(c);
+    if (rc != BSK_OK) return rc;
+    BSK_ENTER(c);
+    return sort_hist_reset(c);
+}
+
+int bsk_sort_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin_exclusive) {
+    const int rc = sort_ctx_check(c);
+    if (rc != BSK_OK) return rc;
+    if (lo_bin >= hi_bin_exclusive || hi_bin_exclusive > SORT_BINS)
+        return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_sort_bucket_begin: the bins must be 0 <= lo < hi <= 4096");
+    BSK_ENTER(c);
+    return sort_bucket_begin(c, lo_bin, hi_bin_exclusive);
+}
+
+int bsk_sort_bucket_add(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                        void* stream) {
+    return record_call(c, nullptr, Op::Sort, true, "", shard, n, on_device, format, stream, CallValues(), [&](const uint8_t* d, hipStream_t st) {
+        const int rc = run_multiline(c, [&](const uint8_t* t, const uint64_t* e) { return sort_bucket_add(c, t, e[0], format, first_record, st); },
+                                     d, {n}, format, st);
+        if (rc != BSK_OK) sort_bucket_abort(c);  // an error in add closes the bucket
+        return rc;
+    });
+}
+
+int bsk_sort_bucket_finish(bsk_ctx* c, void* stream, bsk_out* out) {
+    if (!c) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: null context");
+    if (c->op != Op::Sort || !out) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: not a Sort context");
+    if (c->device < 0) return fail(c, BSK_ERR_NO_DEVICE, "libbsk: context was created without a device");
+    out->d_seg_src = nullptr; out->d_seg_off = nullptr; out->n_segments = 0;
+    BSK_ENTER(c);
+    c->pend_out.kind = 0;
+    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), (hipStream_t)stream));
+    return sort_bucket_finish(c, (hipStream_t)stream, out);
 }
 
 int bsk_head_genome_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,

@@ -29,7 +29,7 @@ struct bsk_tuning {
     static const char* const* names() {
         static const char* const N[] = {"filter", "grep_shiftand", "head_genome_window", "index", "locate_nopre", "long_bytes", "min_range_bytes", "names",
                                         "names_scale", "out", "pin_alphabet", "ranges_per_wave", "replace", "rmdup", "rmdup_buckets", "rmdup_hash", "rmdup_k1_bits", "rmdup_k2_bits", "rmdup_keys", "rmdup_place", "rmdup_xcheck", "rmdup_xlocal", "scan", "segcopy",
-                                        "sort", "stage_bytes", "stats_a", "stats_fasta", "stats_prep", "stats_tail", "subseq", "subseq_scale", "text", "translate", "translate_index", "translate_probe", "translate_stream", "tr_lanes", nullptr};
+                                        "sort", "sort_sample_cap", "stage_bytes", "stats_a", "stats_fasta", "stats_prep", "stats_tail", "subseq", "subseq_scale", "text", "translate", "translate_index", "translate_probe", "translate_stream", "tr_lanes", nullptr};
         return N;
     }
     std::map<std::string, std::string> v;
@@ -163,21 +163,43 @@ struct bsk_ctx {
         int64_t n1 = -1;
         uint64_t records = 0;
     } hg;
-    // shuffle in buckets of the draw (ops_host_shuffle.cpp; PARITY.md SHUF): the fine-bin histogram, which accumulates over the
-    // shards of a call sequence, and the open bucket -- the texts of its records back to back (every shard's share begins on
-    // a 256-byte boundary) and (draw, byte offset, length) per record, in the order they were added; `total` = the bytes of
-    // those records (acc_used without the padding): the size of the bucket's output, known without a read-back
-    struct ShuffleBuckets {
-        uint64_t* d_hist = nullptr;      // bytes[4096] ++ records[4096]
-        bool open = false;
-        uint64_t lo = 0, hi = 0;         // the draws of the open bucket, both inclusive
+    // The accumulation of an open bucket (shuffle in buckets of the draw, sort in buckets of the key; bucket_accumulate in
+    // ops_host_shuffle.cpp): the texts of its records back to back and -- for a caller that wants them -- (draw, byte offset,
+    // length) per record, in the order they were added.  `total` = the bytes of those records (acc_used without any padding):
+    // the size of the bucket's output, known without a read-back
+    struct BucketAcc {
         uint8_t* d_acc = nullptr;
         uint64_t acc_cap = 0, acc_used = 0;
         uint64_t* d_draw = nullptr;
         uint64_t* d_off = nullptr;
         uint32_t* d_len = nullptr;
         uint64_t rec_cap = 0, n = 0, total = 0;
+    };
+    // shuffle in buckets of the draw (ops_host_shuffle.cpp; PARITY.md SHUF): the fine-bin histogram, which accumulates over the
+    // shards of a call sequence, and the open bucket (every shard's share of its accumulation begins on a 256-byte boundary)
+    struct ShuffleBuckets : BucketAcc {
+        uint64_t* d_hist = nullptr;      // bytes[4096] ++ records[4096]
+        bool open = false;
+        uint64_t lo = 0, hi = 0;         // the draws of the open bucket, both inclusive
     } shb;
+    // sort in buckets of the key (ops_host_sortbuckets.cpp; PARITY.md SORT): the sample of keys with their draws (host side; it
+    // thins itself by halving `threshold`), the installed splitters (host copy and packed on the device), the fine-bin
+    // histogram, and the open bucket, whose accumulation is packed: sort_run_device reads it as one text
+    struct SortBuckets : BucketAcc {
+        std::vector<std::string> sample_keys;
+        std::vector<uint64_t> sample_draws;
+        uint64_t threshold = 0;          // records with (draw >> 11) < threshold are in the sample (0: none taken yet)
+        bool sampling = false;           // a rate was applied since the last reset
+        std::string spl_bytes;
+        std::vector<uint32_t> spl_off{0};
+        uint8_t* d_spl = nullptr;
+        uint32_t* d_spl_off = nullptr;
+        uint64_t* d_hist = nullptr;      // bytes[4096] ++ records[4096]
+        bool open = false;
+        uint32_t lo = 0, hi = 0;         // the bins of the open bucket, hi exclusive
+        uint64_t next_first = 0;         // the shards of a bucket arrive in input order: the lowest first_record the next may have
+        int format = -1;                 // of the accumulated text
+    };                                   // (the member `sob` is the last one of the context: see there)
     uint8_t* d_hg_words = nullptr;
     uint32_t* d_hg_off = nullptr;
     uint32_t* d_hg_counts = nullptr;     // n_i of the records of the running window
@@ -405,6 +427,12 @@ struct bsk_ctx {
     }
     void warn(const std::string& m, bool unless_quiet = false) const { log("WARN", m, unless_quiet); }
     void info(const std::string& m, bool unless_quiet = false) const { log("INFO", m, unless_quiet); }
+    // Behind everything else, so that the members in front of it keep the offsets they had before `sort` had buckets.  With
+    // this state beside `shb` the calls that index a FASTA shard (bsk_shuffle_hist_run, bsk_shuffle_bucket_add) took 0.06 ms
+    // longer on the host in seven of eight processes; here they take the time they took before (profiles/sort_buckets.md,
+    // "The unchanged path", series A against B / C).  The mechanism is not known: a member added behind `sob`, or ahead of the
+    // members of the index passes, wants scripts/bench_bucket_calls.py run against the commit before it.
+    SortBuckets sob;
 };
 
 // the scope of one C-ABI call that runs on the context's device state (BSK_ENTER in capi.cpp / store.cpp)

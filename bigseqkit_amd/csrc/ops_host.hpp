@@ -74,6 +74,20 @@ int shuffle_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records);
 int shuffle_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin);
 int shuffle_bucket_add(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st);
 int shuffle_bucket_finish(bsk_ctx* c, hipStream_t st, bsk_out* out);
+// sort in buckets of the key (ops_host_sortbuckets.cpp; include/bsk.h)
+std::vector<std::string> sort_pick_splitters(std::vector<std::string> keys, uint32_t max_bins);
+int sort_sample_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, double rate, hipStream_t st,
+                       uint64_t* n_records);
+void sort_sample_reset(bsk_ctx* c);
+int sort_splitters_install(bsk_ctx* c, const std::vector<std::string>& splitters);
+int sort_splitters_build(bsk_ctx* c, uint32_t max_bins, uint32_t* n_bins);
+int sort_hist_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, uint64_t* n_records);
+int sort_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records);
+int sort_hist_reset(bsk_ctx* c);
+int sort_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin);
+int sort_bucket_add(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st);
+void sort_bucket_abort(bsk_ctx* c);  // an add that failed for good closes the bucket
+int sort_bucket_finish(bsk_ctx* c, hipStream_t st, bsk_out* out);
 void validate_head_genome_opts(bsk_ctx* c);
 void head_genome_reset(bsk_ctx* c);
 int head_genome_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, bsk_out* out);

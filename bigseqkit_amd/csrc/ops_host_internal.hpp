@@ -118,6 +118,45 @@ struct ShuffleRecords {
     const char *stage_keys, *stage_sort, *stage_segments, *stage_emit;
 };
 int shuffle_order_emit(bsk_ctx* c, const ShuffleRecords& R, hipStream_t st, bsk_out* out);
+// The accumulate step of an open bucket (shuffle in buckets of the draw, sort in buckets of the key), written once:
+//   bucket_acc_reserve   the accumulation holds `bytes` bytes and -- with_records -- `recs` records; what it holds moves along
+//   queue(n, fastq)      before: c->table describes the shard d_buf[0, n).  The record scratch, then `keep` and its scan carved
+//                 out of the arena A (a caller with arrays of its own in the arena takes them from A BEFORE this call and derives
+//                 their pointers inside `pick`, which runs after the reservation), pick(n, fastq, out_len, keep) -- the caller's
+//                 launch: out_len[i] = text + '\n' of a record that joins the bucket, else 0; keep[i] = 1 / 0 --, the two scans,
+//                 and the asynchronous read-backs of `total` and `kept`.  The caller synchronises (shuffle: the one
+//                 synchronisation of index_record_text, whose `queue` this is)
+//   collect()     after that synchronisation: 2^32 records in the bucket are refused in the name of `op`; the accumulation
+//                 grown; launch_seg_build_text / seg_run, or the byte-wise copy with segcopy=off; the newline of a last record
+//                 without one; append(N, keep_off, n0, bytes0) -- the caller's launch for what it keeps per record, null:
+//                 nothing.  The segmented copy stores aligned 16-byte words, so a share starts on a 256-byte boundary of the
+//                 accumulation -- unless `packed`: then the share is copied into c->d_out and from there to its packed place by
+//                 one device-to-device copy, and the accumulation reads as one text.
+struct BucketAccumulate {
+    bsk_ctx* c;
+    bsk_ctx::BucketAcc* B;
+    const uint8_t* d_buf;
+    hipStream_t st;
+    const char* op;
+    bool packed;
+    std::function<int(size_t n, int fastq, uint32_t* out_len, uint32_t* keep)> pick;
+    std::function<hipError_t(uint64_t N, const uint64_t* keep_off, uint64_t n0, uint64_t bytes0)> append;
+    Arena A;
+    uint64_t total = 0, kept = 0;
+    int queue(size_t n, int fastq);
+    int collect();
+    uint64_t o_koff = 0;  // (between queue and collect)
+    size_t n_eff = 0;
+};
+int bucket_acc_reserve(bsk_ctx* c, bsk_ctx::BucketAcc* B, uint64_t bytes, uint64_t recs, bool with_records, hipStream_t st);
+inline void bucket_acc_clear(bsk_ctx::BucketAcc* B) { B->n = 0; B->acc_used = 0; B->total = 0; }
+// The key of `sort` on the host side (ops_host_next.cpp), shared by sort_run_device and the bucket passes
+// (ops_host_sortbuckets.cpp): the parameters that the options and the shard give, and for -N (IDs / names) the rewritten keys
+// in an allocation of their own -- P.nat / P.nat_off point into it, it lives as long as `nat`.  One synchronisation.
+struct SortParams;
+struct SortNatKeys { uint8_t* p = nullptr; ~SortNatKeys() { if (p) hipFree(p); } };
+void sort_key_params(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, SortParams* P);
+int sort_natural_keys(bsk_ctx* c, const uint8_t* d_buf, SortParams* P, hipStream_t st, SortNatKeys* nat);
 // the temporary-storage query of a rocPRIM sort (the *_temp_bytes functions of ops_sort / ops_group / ops_sample)
 int sort_query(bsk_ctx* c, hipError_t e);
 // FASTA text view of the shard's records (text_dev.hpp); null pointers for FASTQ

@@ -371,6 +371,44 @@ void validate_sort_opts(bsk_ctx* c) {
     if (o.i("SeqPrefixLength") < 0) throw OptError("value of flag -L (--seq-prefix-length) should be >= 0");
 }
 
+void sort_key_params(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, SortParams* Pp) {
+    const Options& o = c->opts;
+    SortParams& P = *Pp;
+    memset(&P, 0, sizeof P);
+    P.fastq = format == BSK_FORMAT_FASTQ;
+    P.mode = o.b("ByBases") ? 4 : o.b("ByLength") ? 3 : o.b("BySeq") ? 2 : o.b("ByName") ? 1 : 0;
+    P.ignore_case = o.b("IgnoreCase");
+    P.id_mode = id_mode_of(c);
+    P.prefix_len = (uint32_t)std::min<int64_t>(o.i("SeqPrefixLength"), 0xFFFFFFFFll);
+    set_bits(P.gap_set, o.s("GapLetters"));
+    P.buf_end = d_buf + n;
+}
+
+int sort_natural_keys(bsk_ctx* c, const uint8_t* d_buf, SortParams* Pp, hipStream_t st, SortNatKeys* nat) {
+    SortParams& P = *Pp;
+    const uint64_t N = c->table.n;
+    if (!(c->opts.b("InNaturalOrder") && P.mode <= 1)) return BSK_OK;
+    // natural order (sort.go:130-133: IDs / names only): keys rewritten so that byte order is natural order
+    int rc = ensure_record_scratch(c);
+    if (rc != BSK_OK) return rc;
+    uint32_t* d_nlen = c->d_out_len;     // scratch of N entries, free until the size pass
+    uint64_t* d_noff = c->d_out_off;     // [N + 1]
+    uint64_t nat_bytes = 0;
+    HIP_TRYX(c, launch_sort_natlen(d_buf, c->table, P, d_nlen, st));
+    HIP_TRYX(c, launch_scan_u32(d_nlen, d_noff, N, c->d_scan_tmp, st));
+    HIP_TRYX(c, hipMemcpyAsync(&nat_bytes, d_noff + N, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRYX(c, hipStreamSynchronize(st));
+    // the offsets must survive the size pass below: keep them (and the keys) in their own allocation
+    HIP_TRYX(c, hipMalloc((void**)&nat->p, nat_bytes + 16 + (N + 1) * 8));
+    uint64_t* d_noff2 = reinterpret_cast<uint64_t*>(nat->p);
+    uint8_t* d_keys_nat = nat->p + (N + 1) * 8;
+    HIP_TRYX(c, hipMemcpyAsync(d_noff2, d_noff, (N + 1) * 8, hipMemcpyDeviceToDevice, st));
+    HIP_TRYX(c, launch_sort_natkeys(d_buf, c->table, P, d_noff2, d_keys_nat, st));
+    P.nat = d_keys_nat;
+    P.nat_off = d_noff2;
+    return BSK_OK;
+}
+
 int sort_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, bsk_out* out) {
     const Options& o = c->opts;
     const bool fastq = format == BSK_FORMAT_FASTQ;
@@ -383,14 +421,7 @@ int sort_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipS
     if (rc != BSK_OK) return rc;
     const uint64_t N = c->table.n;
     SortParams P;
-    memset(&P, 0, sizeof P);
-    P.fastq = fastq;
-    P.mode = o.b("ByBases") ? 4 : o.b("ByLength") ? 3 : o.b("BySeq") ? 2 : o.b("ByName") ? 1 : 0;
-    P.ignore_case = o.b("IgnoreCase");
-    P.id_mode = id_mode_of(c);
-    P.prefix_len = (uint32_t)std::min<int64_t>(o.i("SeqPrefixLength"), 0xFFFFFFFFll);
-    set_bits(P.gap_set, o.s("GapLetters"));
-    P.buf_end = d_buf + n;
+    sort_key_params(c, d_buf, n, format, &P);
     const bool desc = o.b("Reverse");  // SortByKey(!reverse, ...)
     // scratch: keys x2, perm x2, key lengths, rocPRIM temporary storage
     size_t tmp_bytes = 0;
@@ -420,28 +451,9 @@ int sort_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipS
         HIP_TRYX(c, launch_sort_pairs(d_tmp, tmp_bytes, kin, kout, pin, pout, N, desc, 32, st));
         std::swap(pin, pout);
     } else {
-        struct FreeNat { uint8_t* p = nullptr; ~FreeNat() { if (p) hipFree(p); } } nat;  // (sort -N: keys in an allocation of their own)
-        if (o.b("InNaturalOrder") && P.mode <= 1) {
-            // natural order (sort.go:130-133: IDs / names only): keys rewritten so that byte order is natural order
-            uint32_t* d_nlen = c->d_out_len;     // scratch of N entries, free until the size pass
-            uint64_t* d_noff = c->d_out_off;     // [N + 1]
-            rc = ensure_record_scratch(c);
-            if (rc != BSK_OK) return rc;
-            d_nlen = c->d_out_len; d_noff = c->d_out_off;
-            uint64_t nat_bytes = 0;
-            HIP_TRYX(c, launch_sort_natlen(d_buf, c->table, P, d_nlen, st));
-            HIP_TRYX(c, launch_scan_u32(d_nlen, d_noff, N, c->d_scan_tmp, st));
-            HIP_TRYX(c, hipMemcpyAsync(&nat_bytes, d_noff + N, 8, hipMemcpyDeviceToHost, st));
-            HIP_TRYX(c, hipStreamSynchronize(st));
-            // the offsets must survive the size pass below: keep them (and the keys) in their own allocation
-            HIP_TRYX(c, hipMalloc((void**)&nat.p, nat_bytes + 16 + (N + 1) * 8));
-            uint64_t* d_noff2 = reinterpret_cast<uint64_t*>(nat.p);
-            uint8_t* d_keys_nat = nat.p + (N + 1) * 8;
-            HIP_TRYX(c, hipMemcpyAsync(d_noff2, d_noff, (N + 1) * 8, hipMemcpyDeviceToDevice, st));
-            HIP_TRYX(c, launch_sort_natkeys(d_buf, c->table, P, d_noff2, d_keys_nat, st));
-            P.nat = d_keys_nat;
-            P.nat_off = d_noff2;
-        }
+        SortNatKeys nat;  // (sort -N: keys in an allocation of their own)
+        rc = sort_natural_keys(c, d_buf, &P, st, &nat);
+        if (rc != BSK_OK) return rc;
         uint32_t maxlen = 0;
         HIP_TRYX(c, hipMemsetAsync(d_klen + N, 0, 4, st));
         HIP_TRYX(c, launch_sort_keylen(d_buf, c->table, P, d_klen, d_klen + N, st));

@@ -116,9 +116,9 @@ int shuffle_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) {
     return BSK_OK;
 }
 
-// the accumulation for `bytes` bytes and `recs` records; what it holds moves along when it has to grow
-static int shuffle_acc_reserve(bsk_ctx* c, uint64_t bytes, uint64_t recs, hipStream_t st) {
-    bsk_ctx::ShuffleBuckets& B = c->shb;
+// ---- the accumulate step of an open bucket (ops_host_internal.hpp)
+int bucket_acc_reserve(bsk_ctx* c, bsk_ctx::BucketAcc* Bp, uint64_t bytes, uint64_t recs, bool with_records, hipStream_t st) {
+    bsk_ctx::BucketAcc& B = *Bp;
     auto regrow = [&](auto** p, uint64_t used, uint64_t cap) -> int {
         using T = std::remove_reference_t<decltype(**p)>;
         T* nb = nullptr;
@@ -136,7 +136,7 @@ static int shuffle_acc_reserve(bsk_ctx* c, uint64_t bytes, uint64_t recs, hipStr
         if (rc != BSK_OK) return rc;
         B.acc_cap = cap;
     }
-    if (recs > B.rec_cap || !B.d_draw) {
+    if (with_records && (recs > B.rec_cap || !B.d_draw)) {
         const uint64_t cap = recs + recs / 4 + 256;
         rc = regrow(&B.d_draw, B.n, cap);
         if (rc == BSK_OK) rc = regrow(&B.d_off, B.n, cap);
@@ -147,11 +147,69 @@ static int shuffle_acc_reserve(bsk_ctx* c, uint64_t bytes, uint64_t recs, hipStr
     return BSK_OK;
 }
 
+int BucketAccumulate::queue(size_t n, int fastq) {
+    const uint64_t N = c->table.n;
+    n_eff = n;
+    const int rs = ensure_record_scratch(c);
+    if (rs != BSK_OK) return rs;
+    const uint64_t o_keep = A.take(N * 4);
+    o_koff = A.take((N + 1) * 8);
+    const int ra = arena_reserve(c, &A);
+    if (ra != BSK_OK) return ra;
+    uint32_t* keep = A.at<uint32_t>(o_keep);
+    uint64_t* keep_off = A.at<uint64_t>(o_koff);
+    const int rp = pick(n, fastq, c->d_out_len, keep);
+    if (rp != BSK_OK) return rp;
+    HIP_TRYX(c, launch_scan_u32(c->d_out_len, c->d_out_off, N, c->d_scan_tmp, st));
+    HIP_TRYX(c, launch_scan_u32(keep, keep_off, N, c->d_scan_tmp, st));
+    HIP_TRYX(c, hipMemcpyAsync(&total, c->d_out_off + N, sizeof total, hipMemcpyDeviceToHost, st));
+    HIP_TRYX(c, hipMemcpyAsync(&kept, keep_off + N, sizeof kept, hipMemcpyDeviceToHost, st));
+    return BSK_OK;
+}
+
+int BucketAccumulate::collect() {
+    const uint64_t N = c->table.n;
+    if (kept == 0) return BSK_OK;
+    if (B->n + kept >= (1ull << 32)) {
+        c->set_error(std::string("libbsk: ") + op + ": 2^32 or more records in one bucket are not supported (a smaller budget makes more buckets)");
+        return BSK_ERR_UNSUPPORTED;
+    }
+    const uint64_t at = packed ? B->acc_used : (B->acc_used + 255) & ~255ull;  // (the segmented copy stores aligned 16-byte words)
+    int rc = bucket_acc_reserve(c, B, at + total + (packed ? 64 : 0), B->n + kept, (bool)append, st);  // (packed: read as a shard, with the slack of one)
+    if (rc != BSK_OK) return rc;
+    if (packed) {
+        rc = ensure_out(c, total);
+        if (rc != BSK_OK) return rc;
+    }
+    uint8_t* dst = packed ? c->d_out : B->d_acc + at;
+    rc = seg_begin(c, N, total, st);
+    if (rc != BSK_OK) return rc;
+    if (!segcopy_on(c)) {
+        // every kept record byte by byte: the fix-up kernel writes the records whose source is 0
+        HIP_TRYX(c, hipMemsetAsync(c->d_seg_src, 0, N * sizeof(uint64_t), st));
+        HIP_TRYX(c, launch_seg_fix_text(d_buf, c->table, c->d_out_len, c->d_out_off, c->d_seg_src, dst, st));
+    } else {
+        {
+            Timed tm(c, "k_seg_prep", st);
+            HIP_TRYX(c, launch_seg_build_text(d_buf, n_eff, c->table, c->d_out_len, c->d_seg_src, seg_other(c), st));
+        }
+        uint64_t other = 0;
+        rc = seg_run(c, SegList{c->d_seg_src, c->d_out_off, N, total}, dst, d_buf, n_eff, st, &other);
+        if (rc != BSK_OK) return rc;
+        // a last record of the input without its newline gets one here: in the output it can land anywhere
+        if (other) HIP_TRYX(c, launch_seg_fix_text(d_buf, c->table, c->d_out_len, c->d_out_off, c->d_seg_src, dst, st));
+    }
+    if (packed) HIP_TRYX(c, hipMemcpyAsync(B->d_acc + at, dst, total, hipMemcpyDeviceToDevice, st));
+    if (append) HIP_TRYX(c, append(N, A.at<uint64_t>(o_koff), B->n, at));
+    B->acc_used = at + total;
+    B->total += total;
+    B->n += kept;
+    return BSK_OK;
+}
+
 static void shuffle_bucket_close(bsk_ctx* c) {
     c->shb.open = false;
-    c->shb.n = 0;
-    c->shb.acc_used = 0;
-    c->shb.total = 0;
+    bucket_acc_clear(&c->shb);
 }
 
 int shuffle_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin) {
@@ -178,7 +236,7 @@ int shuffle_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin) {
             return BSK_ERR_UNSUPPORTED;
         }
         if (recs) {
-            const int rc = shuffle_acc_reserve(c, bytes + 16 * 256, recs, nullptr);
+            const int rc = bucket_acc_reserve(c, &B, bytes + 16 * 256, recs, true, nullptr);
             if (rc != BSK_OK) return rc;
         }
     }
@@ -191,67 +249,25 @@ static int shuffle_bucket_add_open(bsk_ctx* c, const uint8_t* d_buf, size_t n, i
     c->last_kernel_flags = 0;
     int fastq = 0;
     const int64_t seed = c->opts.i("Seed");
-    uint64_t total = 0, kept = 0;
-    Arena A;
-    uint64_t* keep_off = nullptr;
-    int rc = index_record_text(c, d_buf, &n, format, &fastq, st, false, [&](size_t n_eff, int fastq_eff) -> int {
-        const uint64_t N = c->table.n;
-        const int rs = ensure_record_scratch(c);
-        if (rs != BSK_OK) return rs;
-        A = Arena();
-        const uint64_t o_keep = A.take(N * 4), o_koff = A.take((N + 1) * 8);
-        const int ra = arena_reserve(c, &A);
-        if (ra != BSK_OK) return ra;
-        uint32_t* keep = A.at<uint32_t>(o_keep);
-        keep_off = A.at<uint64_t>(o_koff);
-        {
-            Timed tm(c, "k_shuffle_pick", st);
-            HIP_TRYX(c, launch_sample_size(d_buf, n_eff, c->table, SampleParams{fastq_eff, first_record, seed, B.lo, B.hi}, c->d_out_len, keep,
-                                           c->d_status, st));
-        }
-        HIP_TRYX(c, launch_scan_u32(c->d_out_len, c->d_out_off, N, c->d_scan_tmp, st));
-        HIP_TRYX(c, launch_scan_u32(keep, keep_off, N, c->d_scan_tmp, st));
-        HIP_TRYX(c, hipMemcpyAsync(&total, c->d_out_off + N, sizeof total, hipMemcpyDeviceToHost, st));
-        HIP_TRYX(c, hipMemcpyAsync(&kept, keep_off + N, sizeof kept, hipMemcpyDeviceToHost, st));
+    BucketAccumulate S{c, &B, d_buf, st, "shuffle", false};
+    S.pick = [&](size_t n_eff, int fastq_eff, uint32_t* out_len, uint32_t* keep) -> int {
+        Timed tm(c, "k_shuffle_pick", st);
+        HIP_TRYX(c, launch_sample_size(d_buf, n_eff, c->table, SampleParams{fastq_eff, first_record, seed, B.lo, B.hi}, out_len, keep, c->d_status, st));
         return BSK_OK;
+    };
+    S.append = [&](uint64_t N, const uint64_t* keep_off, uint64_t n0, uint64_t bytes0) {
+        return launch_shuffle_append(N, first_record, seed, c->d_out_len, c->d_out_off, keep_off, n0, bytes0, B.d_draw, B.d_off, B.d_len, st);
+    };
+    const int rc = index_record_text(c, d_buf, &n, format, &fastq, st, false, [&](size_t n_eff, int fastq_eff) -> int {
+        S.A = Arena();  // (the strict reader's late complaints run the step once more)
+        return S.queue(n_eff, fastq_eff);
     });
     if (rc != BSK_OK) return rc;
-    const uint64_t N = c->table.n;
-    if (N == 0) {
+    if (c->table.n == 0) {
         bsk_out none;
         return empty_result(c, &none);
     }
-    if (kept == 0) return BSK_OK;
-    if (B.n + kept >= (1ull << 32)) {
-        c->set_error("libbsk: shuffle: 2^32 or more records in one bucket are not supported (a smaller budget makes more buckets)");
-        return BSK_ERR_UNSUPPORTED;
-    }
-    const uint64_t at = (B.acc_used + 255) & ~255ull;  // (the segmented copy stores aligned 16-byte words)
-    rc = shuffle_acc_reserve(c, at + total, B.n + kept, st);
-    if (rc != BSK_OK) return rc;
-    uint8_t* dst = B.d_acc + at;
-    rc = seg_begin(c, N, total, st);
-    if (rc != BSK_OK) return rc;
-    if (!segcopy_on(c)) {
-        // every kept record byte by byte: the fix-up kernel writes the records whose source is 0
-        HIP_TRYX(c, hipMemsetAsync(c->d_seg_src, 0, N * sizeof(uint64_t), st));
-        HIP_TRYX(c, launch_seg_fix_text(d_buf, c->table, c->d_out_len, c->d_out_off, c->d_seg_src, dst, st));
-    } else {
-        {
-            Timed tm(c, "k_seg_prep", st);
-            HIP_TRYX(c, launch_seg_build_text(d_buf, n, c->table, c->d_out_len, c->d_seg_src, seg_other(c), st));
-        }
-        uint64_t other = 0;
-        rc = seg_run(c, SegList{c->d_seg_src, c->d_out_off, N, total}, dst, d_buf, n, st, &other);
-        if (rc != BSK_OK) return rc;
-        // a last record of the input without its newline gets one here: in the output it can land anywhere
-        if (other) HIP_TRYX(c, launch_seg_fix_text(d_buf, c->table, c->d_out_len, c->d_out_off, c->d_seg_src, dst, st));
-    }
-    HIP_TRYX(c, launch_shuffle_append(N, first_record, seed, c->d_out_len, c->d_out_off, keep_off, B.n, at, B.d_draw, B.d_off, B.d_len, st));
-    B.acc_used = at + total;
-    B.total += total;
-    B.n += kept;
-    return BSK_OK;
+    return S.collect();
 }
 
 int shuffle_bucket_add(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st) {

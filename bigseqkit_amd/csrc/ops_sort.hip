@@ -5,6 +5,7 @@
 #include <rocprim/iterator/counting_iterator.hpp>
 
 #include "ops_sort.hpp"
+#include "sort_key_dev.hpp"
 #include "text_dev.hpp"
 
 namespace bsk {
@@ -15,53 +16,6 @@ __device__ __forceinline__ bool in_set256(const uint32_t* s, uint8_t b) { return
 __global__ void k_iota(uint32_t* __restrict__ perm, uint64_t n) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) perm[i] = (uint32_t)i;
-}
-
-// where the string key of record i lives: head bytes [off, off + len) for modes 0 / 1, the sequence for mode 2
-__device__ __forceinline__ uint32_t key_span(const uint8_t* __restrict__ buf, const RecordTable& t, const SortParams& P,
-                                             uint64_t i, uint32_t* off) {
-    *off = 0;
-    if (P.mode == 2) {
-        const uint32_t L = t.l_seq[i];
-        return (P.prefix_len == 0 || L <= P.prefix_len) ? L : P.prefix_len;  // sort.go:74-87
-    }
-    const uint8_t* h = buf + t.start[i] + 1;
-    const uint32_t lh = t.l_head[i];
-    const uint32_t hl = lh > 0 ? lh - 1 : 0;
-    if (P.mode == 1) return hl;                                  // record.Name
-    return id_span_rec(t, i, h, hl, P.id_mode, off, P.buf_end);         // record.ID
-}
-
-// Natural order (natsort.Compare, PARITY.md SORT): the key is cut into runs of digits and runs of other bytes; digit runs
-// compare as integers, other runs as strings, a key that runs out first comes first.  Rewritten so that plain byte order
-// gives the same result:  digit run -> '0', number of significant digits, the significant digits;  other run -> its
-// bytes (lower-cased with -i) and a 0 terminator.  One thread per record (keys are IDs / headers: short).
-template <bool WRITE>
-__device__ __forceinline__ uint32_t natural_key(const uint8_t* __restrict__ k, uint32_t len, bool fold, uint8_t* __restrict__ o) {
-    uint32_t n = 0, i = 0;
-    while (i < len) {
-        if (k[i] >= '0' && k[i] <= '9') {
-            uint32_t j = i;
-            while (j < len && k[j] >= '0' && k[j] <= '9') ++j;
-            uint32_t z = i;
-            while (z + 1 < j && k[z] == '0') ++z;  // leading zeros do not count (an all-zero run keeps one '0')
-            const uint32_t nd = j - z;
-            if (WRITE) { o[n] = '0'; o[n + 1] = (uint8_t)(nd > 255u ? 255u : nd); for (uint32_t q = 0; q < nd; ++q) o[n + 2 + q] = k[z + q]; }
-            n += 2 + nd;
-            i = j;
-        } else {
-            while (i < len && !(k[i] >= '0' && k[i] <= '9')) {
-                uint8_t c = k[i];
-                if (fold && c >= 'A' && c <= 'Z') c += 32;
-                if (WRITE) o[n] = c;
-                ++n;
-                ++i;
-            }
-            if (WRITE) o[n] = 0;
-            ++n;
-        }
-    }
-    return n;
 }
 
 __global__ __launch_bounds__(256) void k_sort_natlen(const uint8_t* __restrict__ buf, RecordTable t, SortParams P,
@@ -110,26 +64,8 @@ __global__ __launch_bounds__(256) void k_sort_chunk(const uint8_t* __restrict__ 
     uint64_t key = 0;
     if (b0 < len) {
         const uint32_t nb = len - b0 < 8u ? len - b0 : 8u;
-        if (P.nat) {
-            const uint8_t* h = P.nat + P.nat_off[i] + b0;  // already folded
-            for (uint32_t k = 0; k < nb; ++k) key |= (uint64_t)h[k] << (56u - 8u * k);
-        } else if (P.mode == 2) {
-            const Text T = text_of(buf, t, tt, i);
-            for (uint32_t k = 0; k < nb; ++k) {
-                uint8_t c = T.at(b0 + k);
-                if (P.ignore_case && c >= 'A' && c <= 'Z') c += 32;
-                key |= (uint64_t)c << (56u - 8u * k);
-            }
-        } else {
-            uint32_t off;
-            key_span(buf, t, P, i, &off);
-            const uint8_t* h = buf + t.start[i] + 1 + off + b0;
-            for (uint32_t k = 0; k < nb; ++k) {
-                uint8_t c = h[k];
-                if (P.ignore_case && c >= 'A' && c <= 'Z') c += 32;
-                key |= (uint64_t)c << (56u - 8u * k);
-            }
-        }
+        const SortKeyView K = sort_key_view(buf, t, tt, P, nullptr, i);  // (string keys: modes 0..2)
+        for (uint32_t k = 0; k < nb; ++k) key |= (uint64_t)K.at(b0 + k) << (56u - 8u * k);
     }
     keys[j] = key;
 }

@@ -706,12 +706,12 @@ static size_t whole_file_limit() {
     return lim;
 }
 
-// BSK_SHUFFLE_BUDGET_BYTES: the bytes a bucket of `shuffle` may hold (run_shuffle_buckets); 0: unset
-static uint64_t shuffle_budget() {
-    const char* e = getenv("BSK_SHUFFLE_BUDGET_BYTES");
+// BSK_SHUFFLE_BUDGET_BYTES / BSK_SORT_BUDGET_BYTES: the bytes a bucket of `shuffle` / `sort` may hold (run_buckets); 0: unset
+static uint64_t bucket_budget(const std::string& use) {
+    const char* e = use == "shuffle" ? getenv("BSK_SHUFFLE_BUDGET_BYTES") : use == "sort" ? getenv("BSK_SORT_BUDGET_BYTES") : nullptr;
     return e ? (uint64_t)strtoull(e, nullptr, 10) : 0;
 }
-bool g_shuffle_unfit = false;  // read_parts: the whole-file load of a `shuffle` input failed and a budget is set
+bool g_buckets_unfit = false;  // read_parts: the whole-file load of a `shuffle` / `sort` input failed and a budget is set
 
 std::vector<Part> read_parts(const std::vector<std::string>& files, int device = -1, const std::string& use = "") {
     std::vector<Part> parts;
@@ -741,14 +741,17 @@ std::vector<Part> read_parts(const std::vector<std::string>& files, int device =
                 if (use != "stats") {
                     close(fd);
                     const std::string what = std::string(bsk_global_error()) + " -- '" + use + "': " + f + " (" + std::to_string(p.n) + " bytes) must fit one GPU next to its result; ";
-                    if (use == "shuffle" && shuffle_budget() > 0) {  // (the mapped files go through the buckets of the draw instead)
-                        g_shuffle_unfit = true;
+                    if (bucket_budget(use) > 0) {  // (the mapped files go through the buckets of the draw / of the key instead)
+                        g_buckets_unfit = true;
                         release(parts);
                         return parts;
                     }
                     if (use == "shuffle")
                         die(what + "shuffle orders all records of its input in one pass and runs on one device "
                                    "(BSK_SHUFFLE_BUDGET_BYTES=<bytes> shuffles it in buckets of at most that many bytes, read once per bucket)");
+                    if (use == "sort")
+                        die(what + "sort orders all records of its input in one pass and runs on one device "
+                                   "(BSK_SORT_BUDGET_BYTES=<bytes> sorts it in buckets of at most that many bytes, read twice and once per bucket)");
                     die(what + "cut it over several GPUs (--devices 0-7: fq2fa, grep, locate, rmdup, sample, seq, stats, subseq, translate)");
                 }
                 // stats: the file stays on the host, its mapping is streamed in record-aligned chunks
@@ -1011,17 +1014,24 @@ Output run_head_genome(const Invocation& inv) {
     return res;
 }
 
-// shuffle in buckets of the draw (include/bsk.h; PARITY.md SHUF): the way of `shuffle` for an input that is larger than the
-// byte budget of a bucket (BSK_SHUFFLE_BUDGET_BYTES) or that could not be loaded whole.  The files stay on the host, mapped;
-// several files are unioned in order (cli/shuffle.go:11-15), the record index runs over all of them.  Record-aligned pieces
-// (BSK_STREAM_PIECE_BYTES, default 1 GiB) go through ONE context: once for the histogram of the draws -- each piece's first
-// record index is remembered -- and then once per bucket of the plan; every finished bucket is appended to the output.  The
-// input is read 1 + (number of buckets) times.  A piece never spans two files, so a file that ends without a newline behaves
-// like the union of the whole-file path: its last record gets the newline.
-
-Output run_shuffle_buckets(const Invocation& inv) {
+// shuffle in buckets of the draw, sort in buckets of the key (include/bsk.h; PARITY.md SHUF, SORT): the way of the two commands
+// for an input that is larger than the byte budget of a bucket (BSK_SHUFFLE_BUDGET_BYTES, BSK_SORT_BUDGET_BYTES) or that could
+// not be loaded whole.  The files stay on the host, mapped; several files are unioned in order (cli/shuffle.go:11-15,
+// cli/sort.go), the record index runs over all of them.  Record-aligned pieces (BSK_STREAM_PIECE_BYTES, default 1 GiB) go
+// through ONE context.  The mapping, the piece list, the plan and the timing line are shared; the passes differ:
+//   shuffle   once for the histogram of the draws -- each piece's first record index is remembered -- and then once per bucket
+//             of the plan: the input is read 1 + B times
+//   sort      once for the sample of keys (which gives the splitters), once for the histogram and once per bucket, the pieces of a
+//             bucket in input order: 2 + B times, and the FIRST piece once more (bsk_index_build: its record count).  The sample
+//             rate comes from the file sizes and the record density of that piece and aims at about 32 samples per fine bin -- a starting value from sample-sort practice, not a measurement.
+//             With -r the buckets leave from the last to the first.
+// Every finished bucket is appended to the output.  A piece never spans two files, so a file that ends without a newline
+// behaves like the union of the whole-file path: its last record gets the newline.
+Output run_buckets(const Invocation& inv) {
+    const std::string use = inv.cmd->use;
+    const bool sort = use == "sort";
     const int device = (int)strtol(inv.pget("device").c_str(), nullptr, 10);
-    const uint64_t budget = shuffle_budget();
+    const uint64_t budget = bucket_budget(use);
     Output res;
     bsk_ctx* ctx = nullptr;
     if (bsk_create(inv.cmd->op, inv.js.c_str(), device, &ctx) != BSK_OK) die(bsk_global_error());
@@ -1034,6 +1044,7 @@ Output run_shuffle_buckets(const Invocation& inv) {
     const char* pinned = getenv("BSK_STREAM_PIECE_BYTES");
     const size_t piece = pinned ? std::max<size_t>(1, (size_t)strtoull(pinned, nullptr, 10)) : ((size_t)1 << 30);
     int fmt = -1;
+    uint64_t total_bytes = 0;
     for (size_t fi = 0; fi < inv.files.size(); ++fi) {
         const std::string& path = inv.files[fi];
         File& f = files[fi];
@@ -1054,8 +1065,9 @@ Output run_shuffle_buckets(const Invocation& inv) {
         }
         close(fd);
         const int ffmt = sniff_format(path, f.size ? std::string((const char*)f.text, 1) : std::string());
-        if (fmt >= 0 && ffmt != fmt) die("shuffle: inputs of different formats");
+        if (fmt >= 0 && ffmt != fmt) die(use + ": inputs of different formats");
         fmt = ffmt;
+        total_bytes += f.size;
         for (size_t lo = 0; lo < f.size;) {
             size_t hi = f.size;
             if (f.size - lo > piece) {
@@ -1067,35 +1079,72 @@ Output run_shuffle_buckets(const Invocation& inv) {
         }
     }
     res.fmt = fmt < 0 ? BSK_FORMAT_FASTA : fmt;
-    uint64_t g = 0;
-    int64_t k = 0;
-    for (auto& pc : pieces) {
-        uint64_t cnt = 0;
-        pc.first = g;
-        if (bsk_shuffle_hist_run(ctx, pc.p, pc.n, 0, res.fmt, k++, g, nullptr, &cnt) != BSK_OK) die(bsk_last_error(ctx));
-        g += cnt;
+    // the pass over all pieces that counts the records: it leaves every piece's first record index
+    auto count_pass = [&](auto&& call) {
+        uint64_t g = 0;
+        int64_t k = 0;
+        for (auto& pc : pieces) {
+            uint64_t cnt = 0;
+            pc.first = g;
+            if (call(pc, k++, g, &cnt) != BSK_OK) die(bsk_last_error(ctx));
+            g += cnt;
+        }
+    };
+    if (sort) {
+        double rate = 1.0;
+        if (!pieces.empty()) {
+            uint64_t cnt = 0;
+            if (bsk_index_build(ctx, pieces[0].p, pieces[0].n, 0, res.fmt, nullptr, &cnt) != BSK_OK) die(bsk_last_error(ctx));
+            const double records = (double)total_bytes * (double)cnt / (double)std::max<size_t>(pieces[0].n, 1);
+            rate = std::min(1.0, 32.0 * 4096.0 / std::max(records, 1.0));
+        }
+        count_pass([&](const Piece& pc, int64_t k, uint64_t g, uint64_t* cnt) {
+            return bsk_sort_sample_run(ctx, pc.p, pc.n, 0, res.fmt, k, g, rate, nullptr, cnt);
+        });
+        uint32_t n_bins = 0;
+        if (bsk_sort_splitters_build(ctx, 4096, &n_bins) != BSK_OK) die(bsk_last_error(ctx));
+        mark("sort: sample of the keys, splitters");
+        count_pass([&](const Piece& pc, int64_t k, uint64_t g, uint64_t* cnt) {
+            return bsk_sort_hist_run(ctx, pc.p, pc.n, 0, res.fmt, k, g, nullptr, cnt);
+        });
+        mark("sort: histogram of the bins");
+    } else {
+        count_pass([&](const Piece& pc, int64_t k, uint64_t g, uint64_t* cnt) {
+            return bsk_shuffle_hist_run(ctx, pc.p, pc.n, 0, res.fmt, k, g, nullptr, cnt);
+        });
+        mark("shuffle: histogram of the draws");
     }
-    mark("shuffle: histogram of the draws");
     std::vector<uint64_t> hist(4096), bounds(4097);
     int n_buckets = 0;
-    if (bsk_shuffle_hist_get(ctx, hist.data(), nullptr) != BSK_OK) die(bsk_last_error(ctx));
-    if (bsk_shuffle_plan(hist.data(), budget, bounds.data(), &n_buckets) != BSK_OK) die(bsk_global_error());
-    for (int b = 0; b < n_buckets; ++b) {
-        if (bsk_shuffle_bucket_begin(ctx, (uint32_t)bounds[b], (uint32_t)bounds[b + 1]) != BSK_OK) die(bsk_last_error(ctx));
-        k = 0;
-        for (auto& pc : pieces)
-            if (bsk_shuffle_bucket_add(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr) != BSK_OK) die(bsk_last_error(ctx));
+    if ((sort ? bsk_sort_hist_get(ctx, hist.data(), nullptr) : bsk_shuffle_hist_get(ctx, hist.data(), nullptr)) != BSK_OK) die(bsk_last_error(ctx));
+    if (bsk_shuffle_plan(hist.data(), budget, bounds.data(), &n_buckets) != BSK_OK) {
+        std::string msg = bsk_global_error();
+        if (sort) msg += " -- sort: a fine bin holds the records between two splitter keys; many equal keys, or a run that the sample missed, fill one";
+        die(msg);
+    }
+    const bool backwards = sort && inv.pget("reverse") == "true";
+    for (int i = 0; i < n_buckets; ++i) {
+        const int b = backwards ? n_buckets - 1 - i : i;
+        const uint32_t lo = (uint32_t)bounds[b], hi = (uint32_t)bounds[b + 1];
+        if ((sort ? bsk_sort_bucket_begin(ctx, lo, hi) : bsk_shuffle_bucket_begin(ctx, lo, hi)) != BSK_OK) die(bsk_last_error(ctx));
+        int64_t k = 0;
+        for (auto& pc : pieces) {
+            const int rc = sort ? bsk_sort_bucket_add(ctx, pc.p, pc.n, 0, res.fmt, k, pc.first, nullptr)
+                                : bsk_shuffle_bucket_add(ctx, pc.p, pc.n, 0, res.fmt, k, pc.first, nullptr);
+            ++k;
+            if (rc != BSK_OK) die(bsk_last_error(ctx));
+        }
         bsk_out out;
-        if (bsk_shuffle_bucket_finish(ctx, nullptr, &out) != BSK_OK) die(bsk_last_error(ctx));
+        if ((sort ? bsk_sort_bucket_finish(ctx, nullptr, &out) : bsk_shuffle_bucket_finish(ctx, nullptr, &out)) != BSK_OK) die(bsk_last_error(ctx));
         const size_t at = res.text.size();
         res.text.resize(at + out.len);
         if (out.len && bsk_out_to_host(ctx, &out, &res.text[at], out.len) != BSK_OK) die(bsk_last_error(ctx));
     }
-    mark("shuffle: buckets");
+    mark(sort ? "sort: buckets" : "shuffle: buckets");
     if (timing) {
         std::vector<char> buf(1 << 16);
         if (bsk_profile_dump(ctx, buf.data(), buf.size()) == BSK_OK)
-            fprintf(stderr, "[timing] shuffle in %d bucket(s) of at most %llu bytes, %zu piece(s); stages: %s\n", n_buckets,
+            fprintf(stderr, "[timing] %s in %d bucket(s) of at most %llu bytes, %zu piece(s); stages: %s\n", use.c_str(), n_buckets,
                     (unsigned long long)budget, pieces.size(), buf.data());
     }
     for (auto& f : files)
@@ -1515,21 +1564,21 @@ static int run_main(int argc, char** argv) {
         store(inv, o, inv.files);
         return 0;
     }
-    if (use_cmd == "shuffle" && shuffle_budget() > 0) {
+    if (bucket_budget(use_cmd) > 0) {  // (shuffle, sort)
         // more bytes than a bucket may hold: not loaded whole (a pipe has no size: it takes the whole-file path)
         uint64_t total = 0;
         struct stat sb;
         for (auto& f : inv.files)
             if (stat(f.c_str(), &sb) == 0 && S_ISREG(sb.st_mode)) total += (uint64_t)sb.st_size;
-        if (total > shuffle_budget()) {
-            Output o = run_shuffle_buckets(inv);
+        if (total > bucket_budget(use_cmd)) {
+            Output o = run_buckets(inv);
             store(inv, o, inv.files);
             return 0;
         }
     }
     std::vector<Part> inputs = read_parts(inv.files, joins_on_host ? -1 : (int)strtol(inv.pget("device").c_str(), nullptr, 10), use_cmd);
-    if (g_shuffle_unfit) {
-        Output o = run_shuffle_buckets(inv);
+    if (g_buckets_unfit) {
+        Output o = run_buckets(inv);
         store(inv, o, inv.files);
         return 0;
     }

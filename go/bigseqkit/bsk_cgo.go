@@ -17,6 +17,7 @@
 //   Sample                bigseqkit/sample.go:48-76     Count() for -n + Sample(false, fraction, seed): bsk_sample_run per partition
 //   Shuffle               bigseqkit/shuffle.go:33-46    PartitionByRandom: bsk_shuffle_run over the joined partitions
 //   ShuffleBuckets        (the same order as Shuffle)   histogram of the draws + plan + one collect sequence per bucket: any input size
+//   SortBuckets           bigseqkit/sort.go:91-147      sample of the keys + splitters + histogram + plan + one collect sequence per bucket: any input size
 //   HeadGenome            bigseqkit/head_genome.go:37-77 MapPartitionsWithIndex(HeadGenome): ONE cut, bsk_head_genome_run over the joined partitions
 //   RmDup                 bigseqkit/rmdup.go:70-108     MapPartitions(RmDupPrepare) + GroupByKey + Flatmap(RmDupCheck)
 //   ReadFASTA/Q[N]        bigseqkit/helper.go:148-178   PlainFile(path, delim) + ReadFixer
@@ -480,6 +481,108 @@ func ShuffleBuckets(input *SeqFrame, o *SeqKitShuffleOptions, budgetBytes uint64
 			}
 		}
 		res.Parts[b] = buf
+		res.Bytes += uint64(out.len)
+		res.Records += uint64(out.records)
+	}
+	return res, nil
+}
+
+// SortBuckets: the result of Sort (bigseqkit/sort.go:91-147) for an input of any size on one device (PARITY.md SORT,
+// "Buckets").  A sample of the keys gives the splitters (about 32 samples per fine bin, from a count of the records:
+// bsk_sort_sample_run over all partitions, bsk_sort_splitters_build), the histogram of the bins the plan (bsk_sort_hist_run,
+// bsk_shuffle_plan), then per bucket bsk_sort_bucket_begin / _add over all partitions IN ORDER / _finish; with Reverse the
+// buckets leave from the last to the first.  The input is read twice plus once per bucket, and once more by the index pass
+// alone (bsk_index_build over all partitions: the count of the records that gives the sample rate); a result part per bucket.
+func SortBuckets(input *SeqFrame, o *SeqKitSortOptions, budgetBytes uint64) (*Result, error) {
+	if o == nil {
+		o = &SeqKitSortOptions{}
+	}
+	o.inner.setDefaults()
+	op, err := newBskOp("Sort", OptionsToString(o.inner), input.Device)
+	if err != nil {
+		return nil, err
+	}
+	defer op.Close()
+	ptrOf := func(d []byte) unsafe.Pointer {
+		if len(d) == 0 {
+			return nil
+		}
+		return unsafe.Pointer(&d[0])
+	}
+	counts := make([]uint64, len(input.Shards))
+	var total uint64
+	for pid, s := range input.Shards {
+		var k C.uint64_t
+		if rc := C.bsk_index_build(op.ctx, ptrOf(s.Data), C.size_t(len(s.Data)), 0, C.int(input.Format), nil, &k); rc != C.BSK_OK {
+			return nil, op.err()
+		}
+		counts[pid] = uint64(k)
+		total += uint64(k)
+	}
+	rate := 1.0
+	if total > 32*4096 {
+		rate = 32 * 4096 / float64(total)
+	}
+	var first uint64
+	for pid, s := range input.Shards {
+		var k C.uint64_t
+		if rc := C.bsk_sort_sample_run(op.ctx, ptrOf(s.Data), C.size_t(len(s.Data)), 0, C.int(input.Format), C.int64_t(pid),
+			C.uint64_t(first), C.double(rate), nil, &k); rc != C.BSK_OK {
+			return nil, op.err()
+		}
+		first += counts[pid]
+	}
+	var nbins C.uint32_t
+	if rc := C.bsk_sort_splitters_build(op.ctx, 4096, &nbins); rc != C.BSK_OK {
+		return nil, op.err()
+	}
+	first = 0
+	for pid, s := range input.Shards {
+		var k C.uint64_t
+		if rc := C.bsk_sort_hist_run(op.ctx, ptrOf(s.Data), C.size_t(len(s.Data)), 0, C.int(input.Format), C.int64_t(pid),
+			C.uint64_t(first), nil, &k); rc != C.BSK_OK {
+			return nil, op.err()
+		}
+		first += counts[pid]
+	}
+	var hist [4096]C.uint64_t
+	if rc := C.bsk_sort_hist_get(op.ctx, &hist[0], nil); rc != C.BSK_OK {
+		return nil, op.err()
+	}
+	var bounds [4097]C.uint64_t
+	var nb C.int
+	if rc := C.bsk_shuffle_plan(&hist[0], C.uint64_t(budgetBytes), &bounds[0], &nb); rc != C.BSK_OK {
+		return nil, errors.New(C.GoString(C.bsk_global_error()))
+	}
+	reverse := o.inner.Reverse != nil && *o.inner.Reverse
+	res := &Result{Parts: make([][]byte, int(nb))}
+	for i := 0; i < int(nb); i++ {
+		b := i
+		if reverse {
+			b = int(nb) - 1 - i
+		}
+		if rc := C.bsk_sort_bucket_begin(op.ctx, C.uint32_t(bounds[b]), C.uint32_t(bounds[b+1])); rc != C.BSK_OK {
+			return nil, op.err()
+		}
+		first = 0
+		for pid, s := range input.Shards {
+			if rc := C.bsk_sort_bucket_add(op.ctx, ptrOf(s.Data), C.size_t(len(s.Data)), 0, C.int(input.Format), C.int64_t(pid),
+				C.uint64_t(first), nil); rc != C.BSK_OK {
+				return nil, op.err()
+			}
+			first += counts[pid]
+		}
+		var out C.bsk_out
+		if rc := C.bsk_sort_bucket_finish(op.ctx, nil, &out); rc != C.BSK_OK {
+			return nil, op.err()
+		}
+		buf := make([]byte, int(out.len))
+		if out.len > 0 {
+			if rc := C.bsk_out_to_host(op.ctx, &out, unsafe.Pointer(&buf[0]), out.len); rc != C.BSK_OK {
+				return nil, op.err()
+			}
+		}
+		res.Parts[i] = buf
 		res.Bytes += uint64(out.len)
 		res.Records += uint64(out.records)
 	}

@@ -415,6 +415,59 @@ int bsk_shuffle_bucket_add(bsk_ctx* ctx, const void* shard, size_t n, int on_dev
                            void* stream);
 int bsk_shuffle_bucket_finish(bsk_ctx* ctx, void* stream, bsk_out* out);
 
+/* ---- Sort in buckets of the key: the bytes of bsk_sort_run for an input of any size on one device (PARITY.md SORT, "Buckets").
+ * The canonical key of a record is a byte string -- ID or whole header (lower-cased with IgnoreCase), its natural-order rewrite
+ * with InNaturalOrder, the sequence or its SeqPrefixLength prefix with BySeq, the 32-bit number as 4 big-endian bytes with
+ * ByLength / ByBases -- and two keys compare as bytes with the shorter one zero-padded.  With splitters s_0 < ... < s_(k-1)
+ * (k <= 4095, any byte strings) the "fine bin" of a record is the number of splitters <= its key; a bucket is a run of
+ * consecutive bins, and the output is bucket 0 sorted, then bucket 1, ... (Reverse: the buckets from the last to the first;
+ * every bucket is sorted descending by the context's own option).  The bytes depend neither on the splitters nor on the
+ * buckets nor on how the input is cut into shards.  The input is read once for the sample, once for the histogram and once
+ * per bucket:
+ *   bsk_sort_sample_run       every shard in turn: the records whose draw -- a function of first_record + i alone -- falls under
+ *                             `rate` (0 .. 1) leave their keys, cut at 256 bytes, in the context.  Above a cap (switch
+ *                             sort_sample_cap, default 262144 keys) the sample thins itself: the rate halves and the stored
+ *                             keys above it leave, so the sample is the same for any cut into shards.  *n_records = the records
+ *                             of the shard
+ *   bsk_sort_sample_reset     the sample cleared;  bsk_sort_sample_count: the keys it holds
+ *   bsk_sort_pick_splitters   pure host function, no context: keys (key j = keys[key_offsets[j], key_offsets[j + 1])) -> at most
+ *                             max_bins - 1 strictly ascending splitters at the quantiles, duplicates collapsed; offsets: room
+ *                             for max_bins entries.  No key: no splitter, one bin
+ *   bsk_sort_splitters_build  bsk_sort_pick_splitters on the context's sample, the result installed; *n_bins = splitters + 1
+ *   bsk_sort_splitters_set    installs splitters by hand (k <= 4095, at most 1 MiB); a list that is not strictly ascending
+ *                             under the padded comparison is BSK_ERR_INVALID_ARG
+ *   bsk_sort_splitters_get    the installed splitters: *k, *n_bytes, and -- with buffers -- bytes and offsets[k + 1]
+ *   bsk_sort_hist_run / _hist_get / _hist_reset
+ *                             as bsk_shuffle_hist_*: bytes[4096] and records[4096] per fine bin (the bins above k stay empty),
+ *                             so bsk_shuffle_plan is the plan.  The histogram belongs to the splitters it was taken with
+ *   bsk_sort_bucket_begin / _add / _finish
+ *                             one bucket: begin names its bins, add collects the shard's records whose bin falls into them --
+ *                             every shard of the input, IN INPUT ORDER (ties keep file order): a first_record that goes
+ *                             backwards is BSK_ERR_INVALID_ARG -- and finish sorts them as bsk_sort_run would and returns them
+ *                             as one block, valid until the next call on the context.  add or finish without begin, and begin
+ *                             inside an open bucket, are BSK_ERR_INVALID_ARG; 2^32 or more records in one bucket are
+ *                             BSK_ERR_UNSUPPORTED (the whole input may hold more).  An error in add or finish closes the bucket --
+ *                             but a bsk_sort_bucket_add that is refused before it runs (a bad argument, a context that is busy
+ *                             with another call, a host shard that could not be staged) has not touched the bucket: it stays open.
+ * Every one of them is BSK_ERR_INVALID_ARG, "not a Sort context", on a context of another operator. */
+int bsk_sort_sample_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                        double rate, void* stream, uint64_t* n_records);
+int bsk_sort_sample_reset(bsk_ctx* ctx);
+int bsk_sort_sample_count(bsk_ctx* ctx, uint64_t* n_samples);
+int bsk_sort_pick_splitters(const uint8_t* keys, const uint64_t* key_offsets, uint64_t n_keys, uint32_t max_bins, uint8_t* bytes,
+                            uint64_t bytes_cap, uint64_t* offsets, uint32_t* k);
+int bsk_sort_splitters_build(bsk_ctx* ctx, uint32_t max_bins, uint32_t* n_bins);
+int bsk_sort_splitters_set(bsk_ctx* ctx, const uint8_t* bytes, const uint64_t* offsets, uint32_t k);
+int bsk_sort_splitters_get(bsk_ctx* ctx, uint8_t* bytes, uint64_t bytes_cap, uint64_t* offsets, uint32_t* k, uint64_t* n_bytes);
+int bsk_sort_hist_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                      void* stream, uint64_t* n_records);
+int bsk_sort_hist_get(bsk_ctx* ctx, uint64_t* bytes, uint64_t* records);
+int bsk_sort_hist_reset(bsk_ctx* ctx);
+int bsk_sort_bucket_begin(bsk_ctx* ctx, uint32_t lo_bin, uint32_t hi_bin_exclusive);
+int bsk_sort_bucket_add(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                        void* stream);
+int bsk_sort_bucket_finish(bsk_ctx* ctx, void* stream, bsk_out* out);
+
 /* ---- HeadGenome (bigseqkit/head_genome.go, bigseqkit-lib/head_genome.go:53-108; options {"MiniCommonWords": 1}; PARITY.md
  * HEADG): the records of the first genome.  The words of a record are the maximal runs of its description other than ' '
  * and '\t'; the prefix is the words of the first record of the input; n_i = leading words of record i equal to the prefix's.
