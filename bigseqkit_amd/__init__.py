@@ -13,4 +13,5 @@ from .api import (SeqFrame, ReadFASTA, ReadFASTAN, ReadFASTQ, ReadFASTQN, Operat
                   stats_map, Seq, build_index, Grep, GrepCount, Subseq, Translate, RmDup, Locate, Fq2Fa, Range, Head,
                   Duplicate, Count, Rename, Sort, Faidx, Pair, Common, Concat, FaidxQuery, Replace, Fa2Fq, Sample, Shuffle, ShuffleBuckets, ShuffleHistRun, ShuffleHistGet, ShuffleHistReset, ShufflePlan, ShuffleBucket, HeadGenome,
                   SortBuckets, SortBucketsPlan, SortBucket, SortSampleRun, SortSampleReset, SortSampleCount, SortPickSplitters, SortSplittersBuild,
-                  SortSplittersSet, SortSplittersGet, SortHistRun, SortHistGet, SortHistReset)
+                  SortSplittersSet, SortSplittersGet, SortHistRun, SortHistGet, SortHistReset,
+                  RmDupBuckets, RmDupHistRun, RmDupHistGet, RmDupHistReset, RmDupVerdictBegin, RmDupVerdictGet, RmDupBucket, RmDupEmit)

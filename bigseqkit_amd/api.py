@@ -636,6 +636,84 @@ def SortBuckets(input, o=None, budget_bytes=1 << 30, device=0, splitters=None, r
         return b"".join(SortBucket(op, input, counts, lo, hi) for lo, hi in buckets)
 
 
+RMDUP_BINS = 4096
+RMDUP_BUCKET_RECORD_BYTES = 32   # BSK_RMDUP_BUCKET_RECORD_BYTES of include/bsk.h
+
+
+def RmDupHistRun(op, input):
+    """bsk_rmdup_hist_run over the shards of `input`, in order: the record count of every shard (the histogram accumulates
+    in the operator's context)"""
+    counts, first = [], 0
+    for pid, ptr, n, on_dev, keep in input.partitions():
+        k = C.c_uint64()
+        check(lib.bsk_rmdup_hist_run(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None, C.byref(k)), op.ctx)
+        counts.append(k.value)
+        first += k.value
+    return counts
+
+
+def RmDupHistGet(op):
+    """bsk_rmdup_hist_get: (bytes[4096], records[4096])"""
+    b, r = (C.c_uint64 * RMDUP_BINS)(), (C.c_uint64 * RMDUP_BINS)()
+    check(lib.bsk_rmdup_hist_get(op.ctx, b, r), op.ctx)
+    return list(b), list(r)
+
+
+def RmDupHistReset(op):
+    check(lib.bsk_rmdup_hist_reset(op.ctx), op.ctx)
+
+
+def RmDupVerdictBegin(op, total_records):
+    """bsk_rmdup_verdict_begin: a zeroed removed-bitmap for the records [0, total_records), no bin decided"""
+    check(lib.bsk_rmdup_verdict_begin(op.ctx, total_records), op.ctx)
+
+
+def RmDupVerdictGet(op, first, count):
+    """bsk_rmdup_verdict_get: one byte per record of [first, first + count), 1 = removed"""
+    buf = (C.c_uint8 * max(1, count))()
+    check(lib.bsk_rmdup_verdict_get(op.ctx, first, count, buf), op.ctx)
+    return bytes(buf[:count])
+
+
+def RmDupBucket(op, input, counts, lo_bin, hi_bin):
+    """bsk_rmdup_bucket_begin / _add over the shards of `input`, in order / _finish: (removed, flagged) of the bucket [lo_bin, hi_bin)"""
+    check(lib.bsk_rmdup_bucket_begin(op.ctx, lo_bin, hi_bin), op.ctx)
+    first = 0
+    for (pid, ptr, n, on_dev, keep), cnt in zip(input.partitions(), counts):
+        check(lib.bsk_rmdup_bucket_add(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None), op.ctx)
+        first += cnt
+    removed, flagged = C.c_uint64(), C.c_uint64()
+    check(lib.bsk_rmdup_bucket_finish(op.ctx, None, C.byref(removed), C.byref(flagged)), op.ctx)
+    return removed.value, flagged.value
+
+
+def RmDupEmit(op, input, counts):
+    """bsk_rmdup_emit_run over the shards of `input`, in order: the survivors, joined"""
+    chunks, first = [], 0
+    for (pid, ptr, n, on_dev, keep), cnt in zip(input.partitions(), counts):
+        out = _lib.Out()
+        check(lib.bsk_rmdup_emit_run(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None, C.byref(out)), op.ctx)
+        buf = C.create_string_buffer(max(1, out.len))
+        check(lib.bsk_out_to_host(op.ctx, C.byref(out), buf, out.len), op.ctx)
+        chunks.append(buf.raw[:out.len])
+        first += cnt
+    return b"".join(chunks)
+
+
+def RmDupBuckets(input, o=None, budget_bytes=1 << 30, device=0):
+    """RmDup of an input of any size on one device (PARITY RMDUPB): the histogram of the fine bins of the key over all shards,
+    the plan of buckets of at most `budget_bytes` of subjects, one collect sequence per bucket, which ends in the bucket's
+    share of the verdict, and one emit pass; the same bytes as RmDup.  The input is read twice plus once per bucket."""
+    with Operator("RmDup", (o or SeqKitRmDupOptions()).to_json(), device) as op:
+        RmDupHistReset(op)
+        counts = RmDupHistRun(op, input)
+        bounds = ShufflePlan(RmDupHistGet(op)[0], budget_bytes)
+        RmDupVerdictBegin(op, sum(counts))
+        for lo, hi in zip(bounds[:-1], bounds[1:]):
+            RmDupBucket(op, input, counts, lo, hi)
+        return RmDupEmit(op, input, counts)
+
+
 def HeadGenome(input, o=None, device=0):
     """bigseqkit/head_genome.go:37-77 (PARITY HEADG): the records of the first genome.  ONE cut over the whole input: the
     shards go through one context in order, which carries the prefix words, n_1 and "cut reached" from shard to shard, and

@@ -15,6 +15,7 @@
 #include "ops_host.hpp"
 #include "ops_host_internal.hpp"
 #include "ops_sample.hpp"
+#include "ops_rmdup_buckets.hpp"
 #include "ops_sort_buckets.hpp"
 #include "ops_segcopy.hpp"
 #include "stats_host.hpp"
@@ -372,6 +373,9 @@ void bsk_destroy(bsk_ctx* c) {
         for (void* p : {(void*)c->shb.d_hist, (void*)c->shb.d_acc, (void*)c->shb.d_draw, (void*)c->shb.d_off, (void*)c->shb.d_len})
             if (p) hipFree(p);
         for (void* p : {(void*)c->sob.d_hist, (void*)c->sob.d_acc, (void*)c->sob.d_spl, (void*)c->sob.d_spl_off})
+            if (p) hipFree(p);
+        for (void* p : {(void*)c->rdb.d_hist, (void*)c->rdb.d_acc, (void*)c->rdb.d_draw, (void*)c->rdb.d_off, (void*)c->rdb.d_len,
+                        (void*)c->rdb.d_key, (void*)c->rdb.d_bits})
             if (p) hipFree(p);
         if (c->d_vm_progs) hipFree(c->d_vm_progs);
         if (c->d_id_off) hipFree(c->d_id_off);
@@ -1455,6 +1459,93 @@ int bsk_translate_run(bsk_ctx* c, const void* shard, size_t n, int on_device, in
 int bsk_rmdup_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,
                   bsk_out* out) {
     return run_record_op(c, Op::RmDup, shard, n, on_device, format, stream, out);
+}
+
+// ---- rmdup in buckets of the key (include/bsk.h; the passes are in ops_host_rmdupbuckets.cpp).  A wrapped FASTQ shard runs once
+// more as its 4-line rewrite (run_multiline), like bsk_rmdup_run's
+static int rmdup_ctx_check(bsk_ctx* c) {
+    if (!c) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: null context");
+    if (c->op != Op::RmDup) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: not an RmDup context");
+    if (c->device < 0) return fail(c, BSK_ERR_NO_DEVICE, "libbsk: context was created without a device");
+    return BSK_OK;
+}
+
+int bsk_rmdup_hist_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                       void* stream, uint64_t* n_records) {
+    const int rcc = rmdup_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    return record_call(c, nullptr, Op::RmDup, true, "", shard, n, on_device, format, stream, CallValues(), [&](const uint8_t* d, hipStream_t st) {
+        return run_multiline(c, [&](const uint8_t* t, const uint64_t* e) { return rmdup_hist_device(c, t, e[0], format, st, n_records); }, d, {n}, format, st);
+    });
+}
+
+int bsk_rmdup_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) {
+    const int rcc = rmdup_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    BSK_ENTER(c);
+    return rmdup_hist_get(c, bytes, records);
+}
+
+int bsk_rmdup_hist_reset(bsk_ctx* c) {
+    const int rcc = rmdup_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    BSK_ENTER(c);
+    return rmdup_hist_reset(c);
+}
+
+int bsk_rmdup_verdict_begin(bsk_ctx* c, uint64_t total_records) {
+    const int rcc = rmdup_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    BSK_ENTER(c);
+    return rmdup_verdict_begin(c, total_records);
+}
+
+int bsk_rmdup_verdict_get(bsk_ctx* c, uint64_t first, uint64_t count, uint8_t* removed) {
+    const int rcc = rmdup_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    if (count && !removed) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_rmdup_verdict_get: null argument");
+    BSK_ENTER(c);
+    return rmdup_verdict_get(c, first, count, removed);
+}
+
+int bsk_rmdup_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin_exclusive) {
+    const int rcc = rmdup_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    if (lo_bin >= hi_bin_exclusive || hi_bin_exclusive > RMDUP_BINS)
+        return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_rmdup_bucket_begin: the bins must be 0 <= lo < hi <= 4096");
+    BSK_ENTER(c);
+    return rmdup_bucket_begin(c, lo_bin, hi_bin_exclusive);
+}
+
+int bsk_rmdup_bucket_add(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                         void* stream) {
+    const int rcc = rmdup_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    return record_call(c, nullptr, Op::RmDup, true, "", shard, n, on_device, format, stream, CallValues(), [&](const uint8_t* d, hipStream_t st) {
+        const int rc = run_multiline(c, [&](const uint8_t* t, const uint64_t* e) { return rmdup_bucket_add(c, t, e[0], format, first_record, st); },
+                                     d, {n}, format, st);
+        if (rc != BSK_OK) rmdup_bucket_abort(c);  // an error in add closes the bucket
+        return rc;
+    });
+}
+
+int bsk_rmdup_bucket_finish(bsk_ctx* c, void* stream, uint64_t* n_removed, uint64_t* n_flagged) {
+    const int rcc = rmdup_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    BSK_ENTER(c);
+    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), (hipStream_t)stream));
+    return rmdup_bucket_finish(c, (hipStream_t)stream, n_removed, n_flagged);
+}
+
+int bsk_rmdup_emit_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                       void* stream, bsk_out* out) {
+    const int rcc = rmdup_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    return record_call(c, out, Op::RmDup, out != nullptr, "", shard, n, on_device, format, stream, CallValues(), [&](const uint8_t* d, hipStream_t st) {
+        c->pend_out.kind = 0;
+        return run_multiline(c, [&](const uint8_t* t, const uint64_t* e) { return rmdup_emit_device(c, t, e[0], format, first_record, st, out); },
+                             d, {n}, format, st);
+    });
 }
 
 // ---- rmdup across ranks: the phases between which the caller runs the all-to-all exchanges (include/bsk.h)

@@ -433,6 +433,21 @@ struct bsk_ctx {
     // "The unchanged path", series A against B / C).  The mechanism is not known: a member added behind `sob`, or ahead of the
     // members of the index passes, wants scripts/bench_bucket_calls.py run against the commit before it.
     SortBuckets sob;
+    // rmdup in buckets of the key (ops_host_rmdupbuckets.cpp; PARITY.md RMDUPB): the fine-bin histogram, the removed-bitmap of
+    // the whole input with the bins that are decided, and the open bucket, whose accumulation holds SUBJECTS: d_draw = the
+    // global record index, d_off / d_len = the subject in d_acc, d_key = k1.  (Behind `sob`, for the reason given there.)
+    struct RmDupBuckets : BucketAcc {
+        uint64_t* d_key = nullptr;       // [rec_cap]
+        uint64_t* d_hist = nullptr;      // bytes[4096] ++ records[4096]
+        uint32_t* d_bits = nullptr;      // bit g set: record g of the input is removed
+        uint64_t bits_words = 0;
+        uint64_t total_records = 0;
+        bool verdict = false;            // bsk_rmdup_verdict_begin was called
+        std::vector<uint8_t> decided = std::vector<uint8_t>(4096, 0);
+        bool open = false;
+        uint32_t lo = 0, hi = 0;         // the bins of the open bucket, hi exclusive
+        uint64_t next_first = 0;         // the shards of a bucket arrive in input order
+    } rdb;
 };
 
 // the scope of one C-ABI call that runs on the context's device state (BSK_ENTER in capi.cpp / store.cpp)

@@ -706,9 +706,11 @@ static size_t whole_file_limit() {
     return lim;
 }
 
-// BSK_SHUFFLE_BUDGET_BYTES / BSK_SORT_BUDGET_BYTES: the bytes a bucket of `shuffle` / `sort` may hold (run_buckets); 0: unset
+// BSK_SHUFFLE_BUDGET_BYTES / BSK_SORT_BUDGET_BYTES / BSK_RMDUP_BUDGET_BYTES: the bytes a bucket of `shuffle` / `sort` / `rmdup` may
+// hold (run_buckets; rmdup: bytes of subjects and their per-record words, not of record text); 0: unset
 static uint64_t bucket_budget(const std::string& use) {
-    const char* e = use == "shuffle" ? getenv("BSK_SHUFFLE_BUDGET_BYTES") : use == "sort" ? getenv("BSK_SORT_BUDGET_BYTES") : nullptr;
+    const char* e = use == "shuffle" ? getenv("BSK_SHUFFLE_BUDGET_BYTES") : use == "sort" ? getenv("BSK_SORT_BUDGET_BYTES")
+                  : use == "rmdup" ? getenv("BSK_RMDUP_BUDGET_BYTES") : nullptr;
     return e ? (uint64_t)strtoull(e, nullptr, 10) : 0;
 }
 bool g_buckets_unfit = false;  // read_parts: the whole-file load of a `shuffle` / `sort` input failed and a budget is set
@@ -752,6 +754,9 @@ std::vector<Part> read_parts(const std::vector<std::string>& files, int device =
                     if (use == "sort")
                         die(what + "sort orders all records of its input in one pass and runs on one device "
                                    "(BSK_SORT_BUDGET_BYTES=<bytes> sorts it in buckets of at most that many bytes, read twice and once per bucket)");
+                    if (use == "rmdup")
+                        die(what + "cut it over several GPUs (--devices 0-7), or BSK_RMDUP_BUDGET_BYTES=<bytes> removes the duplicates in buckets of "
+                                   "the key that hold at most that many bytes of subjects, read twice and once per bucket");
                     die(what + "cut it over several GPUs (--devices 0-7: fq2fa, grep, locate, rmdup, sample, seq, stats, subseq, translate)");
                 }
                 // stats: the file stays on the host, its mapping is streamed in record-aligned chunks
@@ -1014,8 +1019,9 @@ Output run_head_genome(const Invocation& inv) {
     return res;
 }
 
-// shuffle in buckets of the draw, sort in buckets of the key (include/bsk.h; PARITY.md SHUF, SORT): the way of the two commands
-// for an input that is larger than the byte budget of a bucket (BSK_SHUFFLE_BUDGET_BYTES, BSK_SORT_BUDGET_BYTES) or that could
+// shuffle in buckets of the draw, sort and rmdup in buckets of the key (include/bsk.h; PARITY.md SHUF, SORT, RMDUPB): the way of the
+// three commands for an input that is larger than the byte budget of a bucket (BSK_SHUFFLE_BUDGET_BYTES, BSK_SORT_BUDGET_BYTES,
+// BSK_RMDUP_BUDGET_BYTES) or that could
 // not be loaded whole.  The files stay on the host, mapped; several files are unioned in order (cli/shuffle.go:11-15,
 // cli/sort.go), the record index runs over all of them.  Record-aligned pieces (BSK_STREAM_PIECE_BYTES, default 1 GiB) go
 // through ONE context.  The mapping, the piece list, the plan and the timing line are shared; the passes differ:
@@ -1025,11 +1031,14 @@ Output run_head_genome(const Invocation& inv) {
 //             bucket in input order: 2 + B times, and the FIRST piece once more (bsk_index_build: its record count).  The sample
 //             rate comes from the file sizes and the record density of that piece and aims at about 32 samples per fine bin -- a starting value from sample-sort practice, not a measurement.
 //             With -r the buckets leave from the last to the first.
+//   rmdup     once for the histogram of the bins of the key, once per bucket -- the pieces in input order; a bucket holds subjects
+//             and ends in its share of the verdict, it prints nothing -- and once for the emit, whose piece outputs are
+//             appended to the result: 2 + B times.  -d / -D are refused by the histogram pass.
 // Every finished bucket is appended to the output.  A piece never spans two files, so a file that ends without a newline
 // behaves like the union of the whole-file path: its last record gets the newline.
 Output run_buckets(const Invocation& inv) {
     const std::string use = inv.cmd->use;
-    const bool sort = use == "sort";
+    const bool sort = use == "sort", rmdup = use == "rmdup";
     const int device = (int)strtol(inv.pget("device").c_str(), nullptr, 10);
     const uint64_t budget = bucket_budget(use);
     Output res;
@@ -1080,6 +1089,7 @@ Output run_buckets(const Invocation& inv) {
     }
     res.fmt = fmt < 0 ? BSK_FORMAT_FASTA : fmt;
     // the pass over all pieces that counts the records: it leaves every piece's first record index
+    uint64_t last_count = 0;  // the records of the last piece
     auto count_pass = [&](auto&& call) {
         uint64_t g = 0;
         int64_t k = 0;
@@ -1088,6 +1098,7 @@ Output run_buckets(const Invocation& inv) {
             pc.first = g;
             if (call(pc, k++, g, &cnt) != BSK_OK) die(bsk_last_error(ctx));
             g += cnt;
+            last_count = cnt;
         }
     };
     if (sort) {
@@ -1108,6 +1119,11 @@ Output run_buckets(const Invocation& inv) {
             return bsk_sort_hist_run(ctx, pc.p, pc.n, 0, res.fmt, k, g, nullptr, cnt);
         });
         mark("sort: histogram of the bins");
+    } else if (rmdup) {
+        count_pass([&](const Piece& pc, int64_t k, uint64_t g, uint64_t* cnt) {
+            return bsk_rmdup_hist_run(ctx, pc.p, pc.n, 0, res.fmt, k, g, nullptr, cnt);
+        });
+        mark("rmdup: histogram of the bins");
     } else {
         count_pass([&](const Piece& pc, int64_t k, uint64_t g, uint64_t* cnt) {
             return bsk_shuffle_hist_run(ctx, pc.p, pc.n, 0, res.fmt, k, g, nullptr, cnt);
@@ -1116,14 +1132,42 @@ Output run_buckets(const Invocation& inv) {
     }
     std::vector<uint64_t> hist(4096), bounds(4097);
     int n_buckets = 0;
-    if ((sort ? bsk_sort_hist_get(ctx, hist.data(), nullptr) : bsk_shuffle_hist_get(ctx, hist.data(), nullptr)) != BSK_OK) die(bsk_last_error(ctx));
+    if ((sort ? bsk_sort_hist_get(ctx, hist.data(), nullptr) : rmdup ? bsk_rmdup_hist_get(ctx, hist.data(), nullptr)
+              : bsk_shuffle_hist_get(ctx, hist.data(), nullptr)) != BSK_OK) die(bsk_last_error(ctx));
     if (bsk_shuffle_plan(hist.data(), budget, bounds.data(), &n_buckets) != BSK_OK) {
         std::string msg = bsk_global_error();
         if (sort) msg += " -- sort: a fine bin holds the records between two splitter keys; many equal keys, or a run that the sample missed, fill one";
+        if (rmdup) msg += " -- rmdup: a fine bin holds the subjects whose key shares its upper 12 bits; the copies of one subject fill one";
         die(msg);
     }
+    uint64_t removed = 0, flagged = 0;
+    if (rmdup) {
+        // every bucket over all pieces, in order, ends in its share of the verdict; one emit pass prints the survivors in file order
+        const uint64_t total_records = pieces.empty() ? 0 : pieces.back().first + last_count;
+        if (bsk_rmdup_verdict_begin(ctx, total_records) != BSK_OK) die(bsk_last_error(ctx));
+        for (int b = 0; b < n_buckets; ++b) {
+            if (bsk_rmdup_bucket_begin(ctx, (uint32_t)bounds[b], (uint32_t)bounds[b + 1]) != BSK_OK) die(bsk_last_error(ctx));
+            int64_t k = 0;
+            for (auto& pc : pieces)
+                if (bsk_rmdup_bucket_add(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr) != BSK_OK) die(bsk_last_error(ctx));
+            uint64_t r = 0, f = 0;
+            if (bsk_rmdup_bucket_finish(ctx, nullptr, &r, &f) != BSK_OK) die(bsk_last_error(ctx));
+            removed += r;
+            flagged += f;
+        }
+        mark("rmdup: buckets");
+        int64_t k = 0;
+        for (auto& pc : pieces) {
+            bsk_out out;
+            if (bsk_rmdup_emit_run(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr, &out) != BSK_OK) die(bsk_last_error(ctx));
+            const size_t at = res.text.size();
+            res.text.resize(at + out.len);
+            if (out.len && bsk_out_to_host(ctx, &out, &res.text[at], out.len) != BSK_OK) die(bsk_last_error(ctx));
+        }
+        mark("rmdup: emit");
+    }
     const bool backwards = sort && inv.pget("reverse") == "true";
-    for (int i = 0; i < n_buckets; ++i) {
+    for (int i = 0; i < n_buckets && !rmdup; ++i) {  // (rmdup's buckets are done: they print nothing)
         const int b = backwards ? n_buckets - 1 - i : i;
         const uint32_t lo = (uint32_t)bounds[b], hi = (uint32_t)bounds[b + 1];
         if ((sort ? bsk_sort_bucket_begin(ctx, lo, hi) : bsk_shuffle_bucket_begin(ctx, lo, hi)) != BSK_OK) die(bsk_last_error(ctx));
@@ -1140,12 +1184,15 @@ Output run_buckets(const Invocation& inv) {
         res.text.resize(at + out.len);
         if (out.len && bsk_out_to_host(ctx, &out, &res.text[at], out.len) != BSK_OK) die(bsk_last_error(ctx));
     }
-    mark(sort ? "sort: buckets" : "shuffle: buckets");
+    if (!rmdup) mark(sort ? "sort: buckets" : "shuffle: buckets");
     if (timing) {
         std::vector<char> buf(1 << 16);
         if (bsk_profile_dump(ctx, buf.data(), buf.size()) == BSK_OK)
             fprintf(stderr, "[timing] %s in %d bucket(s) of at most %llu bytes, %zu piece(s); stages: %s\n", use.c_str(), n_buckets,
                     (unsigned long long)budget, pieces.size(), buf.data());
+        if (rmdup)
+            fprintf(stderr, "[timing] rmdup: %llu record(s) removed, %llu flagged (subject differed from the survivor of its key group)\n",
+                    (unsigned long long)removed, (unsigned long long)flagged);
     }
     for (auto& f : files)
         if (f.mapped && f.size) munmap((void*)f.text, f.size);
@@ -1564,7 +1611,7 @@ static int run_main(int argc, char** argv) {
         store(inv, o, inv.files);
         return 0;
     }
-    if (bucket_budget(use_cmd) > 0) {  // (shuffle, sort)
+    if (bucket_budget(use_cmd) > 0) {  // (shuffle, sort, rmdup)
         // more bytes than a bucket may hold: not loaded whole (a pipe has no size: it takes the whole-file path)
         uint64_t total = 0;
         struct stat sb;

@@ -468,6 +468,52 @@ int bsk_sort_bucket_add(bsk_ctx* ctx, const void* shard, size_t n, int on_device
                         void* stream);
 int bsk_sort_bucket_finish(bsk_ctx* ctx, void* stream, bsk_out* out);
 
+/* ---- RmDup in buckets of the key: the bytes of bsk_rmdup_run for an input of any size on one device (PARITY.md RMDUPB).
+ * The subject of a record is its ID, its whole header with ByName or its sequence with BySeq, lower-cased with IgnoreCase;
+ * record g (global index over the whole input) is removed iff a record g' < g has the same subject bytes.  The "fine bin" of
+ * a record is k1 >> 52 with k1 = XXH64(subject, seed 0), so equal subjects share a bin; a bucket is a run of consecutive
+ * bins and accumulates the SUBJECTS of its records, not their text.  A bucket does not print: it ends in a verdict, one bit
+ * per record of the whole input, and a last pass over the input emits the survivors in file order.  The keys only find
+ * candidates: every duplicate is byte-compared with the survivor of its key group, and the records that differ ("flagged")
+ * are settled exactly on the host, grouped by text.  The input is read once for the histogram, once per bucket and once for
+ * the emit.  The result depends neither on the buckets nor on how the input is cut into shards.
+ *   bsk_rmdup_hist_run / _hist_get / _hist_reset
+ *                             as bsk_shuffle_hist_*: records[4096] per fine bin, and bytes[bin] = what the accumulation will
+ *                             hold for the bin -- the subject bytes of its records plus BSK_RMDUP_BUCKET_RECORD_BYTES per record
+ *                             (k1, global index, offset, length) -- so bsk_shuffle_plan is the plan.  -d / -D side files are
+ *                             BSK_ERR_UNSUPPORTED here
+ *   bsk_rmdup_verdict_begin   a zeroed removed-bitmap for the records [0, total_records) -- the caller knows the total from the
+ *                             histogram pass -- and no bin decided
+ *   bsk_rmdup_verdict_get     one byte per record of [first, first + count): 1 = removed
+ *   bsk_rmdup_bucket_begin / _add / _finish
+ *                             one bucket: begin names its bins, add collects the subjects of the shard's records whose bin falls
+ *                             into them -- every shard of the input, IN INPUT ORDER: a first_record that goes backwards, and a
+ *                             shard that reaches past total_records, are BSK_ERR_INVALID_ARG -- and finish groups them, compares
+ *                             the bytes, settles the flagged records, sets the bits and marks the bins decided; *n_removed =
+ *                             the bits it set, *n_flagged = the records whose subject differed from their key group's survivor
+ *                             (more than 2^20 of them in one bucket fail the call).  add or finish without begin, begin inside an
+ *                             open bucket and begin before bsk_rmdup_verdict_begin are BSK_ERR_INVALID_ARG; 2^32 or more
+ *                             records in one bucket are BSK_ERR_UNSUPPORTED.  An error in add or finish closes the bucket --
+ *                             with the exception bsk_sort_bucket_add documents: an add that is refused before it runs has not
+ *                             touched the bucket
+ *   bsk_rmdup_emit_run        the survivors of the shard, in order, each as Format(LineWidth), as one block valid until the next
+ *                             call on the context; BSK_ERR_INVALID_ARG while some bin has not been decided (the message names
+ *                             the first one).  out=slices is BSK_ERR_UNSUPPORTED here
+ * Every one of them is BSK_ERR_INVALID_ARG, "not an RmDup context", on a context of another operator. */
+#define BSK_RMDUP_BUCKET_RECORD_BYTES 32
+int bsk_rmdup_hist_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                       void* stream, uint64_t* n_records);
+int bsk_rmdup_hist_get(bsk_ctx* ctx, uint64_t* bytes, uint64_t* records);
+int bsk_rmdup_hist_reset(bsk_ctx* ctx);
+int bsk_rmdup_verdict_begin(bsk_ctx* ctx, uint64_t total_records);
+int bsk_rmdup_verdict_get(bsk_ctx* ctx, uint64_t first, uint64_t count, uint8_t* removed);
+int bsk_rmdup_bucket_begin(bsk_ctx* ctx, uint32_t lo_bin, uint32_t hi_bin_exclusive);
+int bsk_rmdup_bucket_add(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                         void* stream);
+int bsk_rmdup_bucket_finish(bsk_ctx* ctx, void* stream, uint64_t* n_removed, uint64_t* n_flagged);
+int bsk_rmdup_emit_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                       void* stream, bsk_out* out);
+
 /* ---- HeadGenome (bigseqkit/head_genome.go, bigseqkit-lib/head_genome.go:53-108; options {"MiniCommonWords": 1}; PARITY.md
  * HEADG): the records of the first genome.  The words of a record are the maximal runs of its description other than ' '
  * and '\t'; the prefix is the words of the first record of the input; n_i = leading words of record i equal to the prefix's.
