@@ -167,6 +167,44 @@ def StatsString(name, format, input, o=None, device=0):
         return buf.value.decode()
 
 
+def _out_bytes(op, out):
+    """the text of a bsk_out, copied to the host"""
+    buf = C.create_string_buffer(max(1, out.len))
+    check(lib.bsk_out_to_host(op.ctx, C.byref(out), buf, out.len), op.ctx)
+    return buf.raw[:out.len]
+
+
+_BUCKET_BINS = 4096   # the fine bins of shuffle, sort and rmdup in buckets: bsk_shuffle_plan plans all three
+
+
+def _count_pass(fn, op, input, *extra):
+    """fn(ctx, shard ..., first_record, *extra, stream, &n_records) over the shards of `input`, in order, every shard told where
+    it starts: the record count of every shard"""
+    counts, first = [], 0
+    for pid, ptr, n, on_dev, keep in input.partitions():
+        k = C.c_uint64()
+        check(fn(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, *extra, None, C.byref(k)), op.ctx)
+        counts.append(k.value)
+        first += k.value
+    return counts
+
+
+def _hist_get(fn, op):
+    """(bytes[4096], records[4096])"""
+    b, r = (C.c_uint64 * _BUCKET_BINS)(), (C.c_uint64 * _BUCKET_BINS)()
+    check(fn(op.ctx, b, r), op.ctx)
+    return list(b), list(r)
+
+
+def _bucket_adds(begin, add, op, input, counts, lo_bin, hi_bin):
+    """the bucket [lo_bin, hi_bin) opened and every shard of `input` added to it, in order"""
+    check(begin(op.ctx, lo_bin, hi_bin), op.ctx)
+    first = 0
+    for (pid, ptr, n, on_dev, keep), cnt in zip(input.partitions(), counts):
+        check(add(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None), op.ctx)
+        first += cnt
+
+
 def _run_records(op_name, run_fn, input, o, device=0, stream=None, finish=None):
     """MapPartitions(libSource(op_name)) over the shards of `input`: the concatenated
     FileStore bytes (element + newline per output record) and the number of elements."""
@@ -175,9 +213,7 @@ def _run_records(op_name, run_fn, input, o, device=0, stream=None, finish=None):
         for pid, ptr, n, on_dev, keep in input.partitions():
             out = _lib.Out()
             check(run_fn(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, stream, C.byref(out)), op.ctx)
-            buf = C.create_string_buffer(max(1, out.len))
-            check(lib.bsk_out_to_host(op.ctx, C.byref(out), buf, out.len), op.ctx)
-            chunks.append(buf.raw[:out.len])
+            chunks.append(_out_bytes(op, out))
             nrec += out.records
         if finish is not None:  # After() with an error return
             check(finish(op.ctx), op.ctx)
@@ -288,9 +324,7 @@ def Faidx(input, o=None, device=0):
         for pid, ptr, n, on_dev, keep in input.partitions():
             out = _lib.Out()
             check(lib.bsk_faidx_run(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, base, None, C.byref(out)), op.ctx)
-            buf = C.create_string_buffer(max(1, out.len))
-            check(lib.bsk_out_to_host(op.ctx, C.byref(out), buf, out.len), op.ctx)
-            chunks.append(buf.raw[:out.len])
+            chunks.append(_out_bytes(op, out))
             base += n
     return b"".join(chunks)
 
@@ -342,9 +376,7 @@ def Common(inputA, inputB, o=None, *inputN, device=0):
     with Operator("Common", (o or SeqKitCommonOptions()).to_json(), device) as op:
         check(lib.bsk_common_run(op.ctx, C.c_void_p(both.data_ptr()) if both.numel() else None, both.numel(), arr, len(ends), 1,
                                  inputA.format, None, C.byref(out)), op.ctx)
-        buf = C.create_string_buffer(max(1, out.len))
-        check(lib.bsk_out_to_host(op.ctx, C.byref(out), buf, out.len), op.ctx)
-        return buf.raw[:out.len]
+        return _out_bytes(op, out)
 
 
 def Concat(inputA, inputB, o=None, device=0):
@@ -354,9 +386,7 @@ def Concat(inputA, inputB, o=None, device=0):
     with Operator("Concat", (o or SeqKitConcatOptions()).to_json(), device) as op:
         check(lib.bsk_concat_run(op.ctx, C.c_void_p(both.data_ptr()) if both.numel() else None, both.numel(), ends[0], 1,
                                  inputA.format, None, C.byref(out)), op.ctx)
-        buf = C.create_string_buffer(max(1, out.len))
-        check(lib.bsk_out_to_host(op.ctx, C.byref(out), buf, out.len), op.ctx)
-        return buf.raw[:out.len]
+        return _out_bytes(op, out)
 
 
 def FaidxQuery(input, o, device=0):
@@ -392,9 +422,7 @@ def _range(op_name, input, o, device):
         for (pid, ptr, n, on_dev, keep), cnt in zip(input.partitions(), counts):
             out = _lib.Out()
             check(lib.bsk_range_run(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None, C.byref(out)), op.ctx)
-            buf = C.create_string_buffer(max(1, out.len))
-            check(lib.bsk_out_to_host(op.ctx, C.byref(out), buf, out.len), op.ctx)
-            chunks.append(buf.raw[:out.len])
+            chunks.append(_out_bytes(op, out))
             first += cnt
     return b"".join(chunks)
 
@@ -425,9 +453,7 @@ def Sample(input, o, device=0):
         for (pid, ptr, n, on_dev, keep), cnt in zip(input.partitions(), counts):
             out = _lib.Out()
             check(lib.bsk_sample_run(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None, C.byref(out)), op.ctx)
-            buf = C.create_string_buffer(max(1, out.len))
-            check(lib.bsk_out_to_host(op.ctx, C.byref(out), buf, out.len), op.ctx)
-            chunks.append(buf.raw[:out.len])
+            chunks.append(_out_bytes(op, out))
             first += cnt
     return b"".join(chunks)
 
@@ -437,26 +463,18 @@ def Shuffle(input, o=None, device=0):
     return _run_records("Shuffle", lib.bsk_shuffle_run, _one_shard(input), o or SeqKitShuffleOptions(), device)[0]
 
 
-SHUFFLE_BINS = 4096
+SHUFFLE_BINS = _BUCKET_BINS
 
 
 def ShuffleHistRun(op, input):
     """bsk_shuffle_hist_run over the shards of `input`, in order: the record count of every shard (the histogram accumulates
     in the operator's context)"""
-    counts, first = [], 0
-    for pid, ptr, n, on_dev, keep in input.partitions():
-        k = C.c_uint64()
-        check(lib.bsk_shuffle_hist_run(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None, C.byref(k)), op.ctx)
-        counts.append(k.value)
-        first += k.value
-    return counts
+    return _count_pass(lib.bsk_shuffle_hist_run, op, input)
 
 
 def ShuffleHistGet(op):
     """bsk_shuffle_hist_get: (bytes[4096], records[4096])"""
-    b, r = (C.c_uint64 * SHUFFLE_BINS)(), (C.c_uint64 * SHUFFLE_BINS)()
-    check(lib.bsk_shuffle_hist_get(op.ctx, b, r), op.ctx)
-    return list(b), list(r)
+    return _hist_get(lib.bsk_shuffle_hist_get, op)
 
 
 def ShuffleHistReset(op):
@@ -475,16 +493,10 @@ def ShufflePlan(hist_bytes, budget_bytes):
 
 def ShuffleBucket(op, input, counts, lo_bin, hi_bin):
     """bsk_shuffle_bucket_begin / _add over the shards of `input` / _finish: the bytes of the bucket [lo_bin, hi_bin)"""
-    check(lib.bsk_shuffle_bucket_begin(op.ctx, lo_bin, hi_bin), op.ctx)
-    first = 0
-    for (pid, ptr, n, on_dev, keep), cnt in zip(input.partitions(), counts):
-        check(lib.bsk_shuffle_bucket_add(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None), op.ctx)
-        first += cnt
+    _bucket_adds(lib.bsk_shuffle_bucket_begin, lib.bsk_shuffle_bucket_add, op, input, counts, lo_bin, hi_bin)
     out = _lib.Out()
     check(lib.bsk_shuffle_bucket_finish(op.ctx, None, C.byref(out)), op.ctx)
-    buf = C.create_string_buffer(max(1, out.len))
-    check(lib.bsk_out_to_host(op.ctx, C.byref(out), buf, out.len), op.ctx)
-    return buf.raw[:out.len]
+    return _out_bytes(op, out)
 
 
 def ShuffleBuckets(input, o=None, budget_bytes=1 << 30, device=0):
@@ -497,7 +509,7 @@ def ShuffleBuckets(input, o=None, budget_bytes=1 << 30, device=0):
         return b"".join(ShuffleBucket(op, input, counts, lo, hi) for lo, hi in zip(bounds[:-1], bounds[1:]))
 
 
-SORT_BINS = 4096
+SORT_BINS = _BUCKET_BINS
 SORT_SAMPLES_PER_BIN = 32   # a starting value from sample-sort practice, not a measurement
 
 
@@ -523,13 +535,7 @@ def SortPickSplitters(keys, max_bins=SORT_BINS):
 def SortSampleRun(op, input, rate):
     """bsk_sort_sample_run over the shards of `input`, in order: the record count of every shard (the sample accumulates in
     the operator's context)"""
-    counts, first = [], 0
-    for pid, ptr, n, on_dev, keep in input.partitions():
-        k = C.c_uint64()
-        check(lib.bsk_sort_sample_run(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, rate, None, C.byref(k)), op.ctx)
-        counts.append(k.value)
-        first += k.value
-    return counts
+    return _count_pass(lib.bsk_sort_sample_run, op, input, rate)
 
 
 def SortSampleReset(op):
@@ -567,20 +573,12 @@ def SortSplittersGet(op):
 
 def SortHistRun(op, input):
     """bsk_sort_hist_run over the shards of `input`, in order: the record count of every shard"""
-    counts, first = [], 0
-    for pid, ptr, n, on_dev, keep in input.partitions():
-        k = C.c_uint64()
-        check(lib.bsk_sort_hist_run(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None, C.byref(k)), op.ctx)
-        counts.append(k.value)
-        first += k.value
-    return counts
+    return _count_pass(lib.bsk_sort_hist_run, op, input)
 
 
 def SortHistGet(op):
     """bsk_sort_hist_get: (bytes[4096], records[4096])"""
-    b, r = (C.c_uint64 * SORT_BINS)(), (C.c_uint64 * SORT_BINS)()
-    check(lib.bsk_sort_hist_get(op.ctx, b, r), op.ctx)
-    return list(b), list(r)
+    return _hist_get(lib.bsk_sort_hist_get, op)
 
 
 def SortHistReset(op):
@@ -589,16 +587,10 @@ def SortHistReset(op):
 
 def SortBucket(op, input, counts, lo_bin, hi_bin):
     """bsk_sort_bucket_begin / _add over the shards of `input`, in order / _finish: the sorted bytes of the bucket [lo_bin, hi_bin)"""
-    check(lib.bsk_sort_bucket_begin(op.ctx, lo_bin, hi_bin), op.ctx)
-    first = 0
-    for (pid, ptr, n, on_dev, keep), cnt in zip(input.partitions(), counts):
-        check(lib.bsk_sort_bucket_add(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None), op.ctx)
-        first += cnt
+    _bucket_adds(lib.bsk_sort_bucket_begin, lib.bsk_sort_bucket_add, op, input, counts, lo_bin, hi_bin)
     out = _lib.Out()
     check(lib.bsk_sort_bucket_finish(op.ctx, None, C.byref(out)), op.ctx)
-    buf = C.create_string_buffer(max(1, out.len))
-    check(lib.bsk_out_to_host(op.ctx, C.byref(out), buf, out.len), op.ctx)
-    return buf.raw[:out.len]
+    return _out_bytes(op, out)
 
 
 def SortBucketsPlan(op, input, o, budget_bytes, splitters=None, rate=None, device=0):
@@ -636,27 +628,19 @@ def SortBuckets(input, o=None, budget_bytes=1 << 30, device=0, splitters=None, r
         return b"".join(SortBucket(op, input, counts, lo, hi) for lo, hi in buckets)
 
 
-RMDUP_BINS = 4096
+RMDUP_BINS = _BUCKET_BINS
 RMDUP_BUCKET_RECORD_BYTES = 32   # BSK_RMDUP_BUCKET_RECORD_BYTES of include/bsk.h
 
 
 def RmDupHistRun(op, input):
     """bsk_rmdup_hist_run over the shards of `input`, in order: the record count of every shard (the histogram accumulates
     in the operator's context)"""
-    counts, first = [], 0
-    for pid, ptr, n, on_dev, keep in input.partitions():
-        k = C.c_uint64()
-        check(lib.bsk_rmdup_hist_run(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None, C.byref(k)), op.ctx)
-        counts.append(k.value)
-        first += k.value
-    return counts
+    return _count_pass(lib.bsk_rmdup_hist_run, op, input)
 
 
 def RmDupHistGet(op):
     """bsk_rmdup_hist_get: (bytes[4096], records[4096])"""
-    b, r = (C.c_uint64 * RMDUP_BINS)(), (C.c_uint64 * RMDUP_BINS)()
-    check(lib.bsk_rmdup_hist_get(op.ctx, b, r), op.ctx)
-    return list(b), list(r)
+    return _hist_get(lib.bsk_rmdup_hist_get, op)
 
 
 def RmDupHistReset(op):
@@ -677,11 +661,7 @@ def RmDupVerdictGet(op, first, count):
 
 def RmDupBucket(op, input, counts, lo_bin, hi_bin):
     """bsk_rmdup_bucket_begin / _add over the shards of `input`, in order / _finish: (removed, flagged) of the bucket [lo_bin, hi_bin)"""
-    check(lib.bsk_rmdup_bucket_begin(op.ctx, lo_bin, hi_bin), op.ctx)
-    first = 0
-    for (pid, ptr, n, on_dev, keep), cnt in zip(input.partitions(), counts):
-        check(lib.bsk_rmdup_bucket_add(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None), op.ctx)
-        first += cnt
+    _bucket_adds(lib.bsk_rmdup_bucket_begin, lib.bsk_rmdup_bucket_add, op, input, counts, lo_bin, hi_bin)
     removed, flagged = C.c_uint64(), C.c_uint64()
     check(lib.bsk_rmdup_bucket_finish(op.ctx, None, C.byref(removed), C.byref(flagged)), op.ctx)
     return removed.value, flagged.value
@@ -693,9 +673,7 @@ def RmDupEmit(op, input, counts):
     for (pid, ptr, n, on_dev, keep), cnt in zip(input.partitions(), counts):
         out = _lib.Out()
         check(lib.bsk_rmdup_emit_run(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None, C.byref(out)), op.ctx)
-        buf = C.create_string_buffer(max(1, out.len))
-        check(lib.bsk_out_to_host(op.ctx, C.byref(out), buf, out.len), op.ctx)
-        chunks.append(buf.raw[:out.len])
+        chunks.append(_out_bytes(op, out))
         first += cnt
     return b"".join(chunks)
 
@@ -723,9 +701,7 @@ def HeadGenome(input, o=None, device=0):
         for pid, ptr, n, on_dev, keep in input.partitions():
             out = _lib.Out()
             check(lib.bsk_head_genome_run(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, None, C.byref(out)), op.ctx)
-            buf = C.create_string_buffer(max(1, out.len))
-            check(lib.bsk_out_to_host(op.ctx, C.byref(out), buf, out.len), op.ctx)
-            chunks.append(buf.raw[:out.len])
+            chunks.append(_out_bytes(op, out))
             cut = C.c_int()
             check(lib.bsk_head_genome_state(op.ctx, C.byref(cut), None), op.ctx)
             if cut.value:

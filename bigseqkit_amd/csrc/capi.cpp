@@ -1016,6 +1016,39 @@ static int run_record_op(bsk_ctx* c, Op want, const void* shard, size_t n, int o
     });
 }
 
+// ---- the bucket paths of shuffle, sort and rmdup (include/bsk.h; the passes are in ops_host_shuffle.cpp,
+// ops_host_sortbuckets.cpp and ops_host_rmdupbuckets.cpp, the life cycle of a bucket in the first)
+static int bucket_ctx_check(bsk_ctx* c, Op op, const char* a_name, bool args_ok = true) {  // a_name: "a Sort", "an RmDup"
+    if (!c) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: null context");
+    if (c->op != op || !args_ok) return fail(c, BSK_ERR_INVALID_ARG, std::string("libbsk: not ") + a_name + " context");
+    if (c->device < 0) return fail(c, BSK_ERR_NO_DEVICE, "libbsk: context was created without a device");
+    return BSK_OK;
+}
+static int shuffle_ctx_check(bsk_ctx* c) { return bucket_ctx_check(c, Op::Shuffle, "a Shuffle"); }
+static int sort_ctx_check(bsk_ctx* c) { return bucket_ctx_check(c, Op::Sort, "a Sort"); }
+static int rmdup_ctx_check(bsk_ctx* c) { return bucket_ctx_check(c, Op::RmDup, "an RmDup"); }
+static bool bins_ok(uint32_t lo_bin, uint32_t hi_bin_exclusive) { return lo_bin < hi_bin_exclusive && hi_bin_exclusive <= BUCKET_BINS; }
+// the prologue of a finish that fills a bsk_out
+static int bucket_finish_check(bsk_ctx* c, Op op, const char* a_name, bsk_out* out) {
+    const int rc = bucket_ctx_check(c, op, a_name, out != nullptr);
+    if (rc != BSK_OK) return rc;
+    out->d_seg_src = nullptr; out->d_seg_off = nullptr; out->n_segments = 0;
+    return BSK_OK;
+}
+// A pass of sort or rmdup over one shard: record_call, then pass(text, n, stream) through run_multiline -- a wrapped FASTQ shard
+// runs once more as its 4-line rewrite, like bsk_sort_run's and bsk_rmdup_run's.  closes: an error closes the open bucket, here
+// and not in the pass, which the rewrite enters a second time.  The passes of shuffle differ in both: they go through
+// index_record_text, which has the multi-line reader inside, and shuffle_bucket_add closes its bucket itself.
+template <class Pass>
+static int bucket_pass(bsk_ctx* c, bsk_out* out, Op op, bool args_ok, bool closes, const void* shard, size_t n, int on_device, int format,
+                       void* stream, Pass pass) {
+    return record_call(c, out, op, args_ok, "", shard, n, on_device, format, stream, CallValues(), [&](const uint8_t* d, hipStream_t st) {
+        const int rc = run_multiline(c, [&](const uint8_t* t, const uint64_t* e) { return pass(t, (size_t)e[0], st); }, d, {n}, format, st);
+        if (rc != BSK_OK && closes) bucket_close(op == Op::Sort ? static_cast<bsk_ctx::BucketState*>(&c->sob) : &c->rdb);
+        return rc;
+    });
+}
+
 extern "C" {
 
 int bsk_index_build(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, void* stream,
@@ -1200,7 +1233,7 @@ int bsk_shuffle_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int 
     return run_record_op(c, Op::Shuffle, shard, n, on_device, format, stream, out);
 }
 
-// ---- shuffle in buckets of the draw (include/bsk.h; the passes are in ops_host_shuffle.cpp)
+// ---- shuffle in buckets of the draw
 int bsk_shuffle_hist_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                          void* stream, uint64_t* n_records) {
     return record_call(c, nullptr, Op::Shuffle, true, "", shard, n, on_device, format, stream, CallValues(),
@@ -1208,21 +1241,17 @@ int bsk_shuffle_hist_run(bsk_ctx* c, const void* shard, size_t n, int on_device,
 }
 
 int bsk_shuffle_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) {
-    if (!c) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: null context");
-    if (c->op != Op::Shuffle) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: not a Shuffle context");
-    if (c->device < 0) return fail(c, BSK_ERR_NO_DEVICE, "libbsk: context was created without a device");
+    const int rc = shuffle_ctx_check(c);
+    if (rc != BSK_OK) return rc;
     BSK_ENTER(c);
-    return shuffle_hist_get(c, bytes, records);
+    return bucket_hist_get(c, &c->shb, bytes, records);
 }
 
 int bsk_shuffle_hist_reset(bsk_ctx* c) {
-    if (!c) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: null context");
-    if (c->op != Op::Shuffle) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: not a Shuffle context");
-    if (c->device < 0) return fail(c, BSK_ERR_NO_DEVICE, "libbsk: context was created without a device");
+    const int rc = shuffle_ctx_check(c);
+    if (rc != BSK_OK) return rc;
     BSK_ENTER(c);
-    HIP_TRY(c, hipDeviceSynchronize());
-    if (c->shb.d_hist) HIP_TRY(c, hipMemset(c->shb.d_hist, 0, 2 * SHUFFLE_BINS * sizeof(uint64_t)));
-    return BSK_OK;
+    return bucket_hist_reset(c, &c->shb);
 }
 
 int bsk_shuffle_plan(const uint64_t* bytes, uint64_t budget_bytes, uint64_t* bounds, int* n_buckets) {
@@ -1230,7 +1259,7 @@ int bsk_shuffle_plan(const uint64_t* bytes, uint64_t budget_bytes, uint64_t* bou
     int nb = 0;
     uint64_t sum = 0;
     bounds[0] = 0;
-    for (uint32_t b = 0; b < SHUFFLE_BINS; ++b) {
+    for (uint32_t b = 0; b < BUCKET_BINS; ++b) {
         if (bytes[b] > budget_bytes)
             return fail(nullptr, BSK_ERR_UNSUPPORTED, "libbsk: shuffle: fine bin " + std::to_string(b) + " of the draw holds " + std::to_string(bytes[b]) +
                         " bytes, more than the budget of " + std::to_string(budget_bytes) + " bytes of a bucket (4096 bins: the input is too large for this budget)");
@@ -1240,17 +1269,15 @@ int bsk_shuffle_plan(const uint64_t* bytes, uint64_t budget_bytes, uint64_t* bou
         }
         sum += bytes[b];
     }
-    bounds[++nb] = SHUFFLE_BINS;
+    bounds[++nb] = BUCKET_BINS;
     *n_buckets = nb;
     return BSK_OK;
 }
 
 int bsk_shuffle_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin_exclusive) {
-    if (!c) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: null context");
-    if (c->op != Op::Shuffle) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: not a Shuffle context");
-    if (c->device < 0) return fail(c, BSK_ERR_NO_DEVICE, "libbsk: context was created without a device");
-    if (lo_bin >= hi_bin_exclusive || hi_bin_exclusive > SHUFFLE_BINS)
-        return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_shuffle_bucket_begin: the bins must be 0 <= lo < hi <= 4096");
+    const int rc = shuffle_ctx_check(c);
+    if (rc != BSK_OK) return rc;
+    if (!bins_ok(lo_bin, hi_bin_exclusive)) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_shuffle_bucket_begin: the bins must be 0 <= lo < hi <= 4096");
     BSK_ENTER(c);
     return shuffle_bucket_begin(c, lo_bin, hi_bin_exclusive);
 }
@@ -1262,29 +1289,18 @@ int bsk_shuffle_bucket_add(bsk_ctx* c, const void* shard, size_t n, int on_devic
 }
 
 int bsk_shuffle_bucket_finish(bsk_ctx* c, void* stream, bsk_out* out) {
-    if (!c) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: null context");
-    if (c->op != Op::Shuffle || !out) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: not a Shuffle context");
-    if (c->device < 0) return fail(c, BSK_ERR_NO_DEVICE, "libbsk: context was created without a device");
-    out->d_seg_src = nullptr; out->d_seg_off = nullptr; out->n_segments = 0;
+    const int rc = bucket_finish_check(c, Op::Shuffle, "a Shuffle", out);
+    if (rc != BSK_OK) return rc;
     BSK_ENTER(c);
     c->pend_out.kind = 0;
     return shuffle_bucket_finish(c, (hipStream_t)stream, out);
 }
 
-// ---- sort in buckets of the key (include/bsk.h; the passes are in ops_host_sortbuckets.cpp).  A wrapped FASTQ shard runs once
-// more as its 4-line rewrite (run_multiline), like bsk_sort_run's
-static int sort_ctx_check(bsk_ctx* c) {
-    if (!c) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: null context");
-    if (c->op != Op::Sort) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: not a Sort context");
-    if (c->device < 0) return fail(c, BSK_ERR_NO_DEVICE, "libbsk: context was created without a device");
-    return BSK_OK;
-}
-
+// ---- sort in buckets of the key
 int bsk_sort_sample_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                         double rate, void* stream, uint64_t* n_records) {
-    return record_call(c, nullptr, Op::Sort, true, "", shard, n, on_device, format, stream, CallValues(), [&](const uint8_t* d, hipStream_t st) {
-        return run_multiline(c, [&](const uint8_t* t, const uint64_t* e) { return sort_sample_device(c, t, e[0], format, first_record, rate, st, n_records); },
-                             d, {n}, format, st);
+    return bucket_pass(c, nullptr, Op::Sort, true, false, shard, n, on_device, format, stream, [&](const uint8_t* t, size_t m, hipStream_t st) {
+        return sort_sample_device(c, t, m, format, first_record, rate, st, n_records);
     });
 }
 
@@ -1316,7 +1332,7 @@ static std::vector<std::string> strings_of(const uint8_t* bytes, const uint64_t*
 
 int bsk_sort_pick_splitters(const uint8_t* keys, const uint64_t* key_offsets, uint64_t n_keys, uint32_t max_bins, uint8_t* bytes,
                             uint64_t bytes_cap, uint64_t* offsets, uint32_t* k) {
-    if ((n_keys && (!keys || !key_offsets)) || !offsets || !k || max_bins < 1 || max_bins > SORT_BINS)
+    if ((n_keys && (!keys || !key_offsets)) || !offsets || !k || max_bins < 1 || max_bins > BUCKET_BINS)
         return fail(nullptr, BSK_ERR_INVALID_ARG, "libbsk: bsk_sort_pick_splitters: null argument, or max_bins outside 1 .. 4096");
     for (uint64_t j = 0; j < n_keys; ++j)
         if (key_offsets[j] > key_offsets[j + 1]) return fail(nullptr, BSK_ERR_INVALID_ARG, "libbsk: bsk_sort_pick_splitters: the key offsets go backwards");
@@ -1336,7 +1352,7 @@ int bsk_sort_pick_splitters(const uint8_t* keys, const uint64_t* key_offsets, ui
 int bsk_sort_splitters_build(bsk_ctx* c, uint32_t max_bins, uint32_t* n_bins) {
     const int rc = sort_ctx_check(c);
     if (rc != BSK_OK) return rc;
-    if (max_bins < 1 || max_bins > SORT_BINS) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_sort_splitters_build: max_bins must be 1 .. 4096");
+    if (max_bins < 1 || max_bins > BUCKET_BINS) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_sort_splitters_build: max_bins must be 1 .. 4096");
     BSK_ENTER(c);
     return sort_splitters_build(c, max_bins, n_bins);
 }
@@ -1370,49 +1386,41 @@ int bsk_sort_splitters_get(bsk_ctx* c, uint8_t* bytes, uint64_t bytes_cap, uint6
 
 int bsk_sort_hist_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                       void* stream, uint64_t* n_records) {
-    return record_call(c, nullptr, Op::Sort, true, "", shard, n, on_device, format, stream, CallValues(), [&](const uint8_t* d, hipStream_t st) {
-        return run_multiline(c, [&](const uint8_t* t, const uint64_t* e) { return sort_hist_device(c, t, e[0], format, st, n_records); }, d, {n}, format, st);
-    });
+    return bucket_pass(c, nullptr, Op::Sort, true, false, shard, n, on_device, format, stream,
+                       [&](const uint8_t* t, size_t m, hipStream_t st) { return sort_hist_device(c, t, m, format, st, n_records); });
 }
 
 int bsk_sort_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) {
     const int rc = sort_ctx_check(c);
     if (rc != BSK_OK) return rc;
     BSK_ENTER(c);
-    return sort_hist_get(c, bytes, records);
+    return bucket_hist_get(c, &c->sob, bytes, records);
 }
 
 int bsk_sort_hist_reset(bsk_ctx* c) {
     const int rc = sort_ctx_check(c);
     if (rc != BSK_OK) return rc;
     BSK_ENTER(c);
-    return sort_hist_reset(c);
+    return bucket_hist_reset(c, &c->sob);
 }
 
 int bsk_sort_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin_exclusive) {
     const int rc = sort_ctx_check(c);
     if (rc != BSK_OK) return rc;
-    if (lo_bin >= hi_bin_exclusive || hi_bin_exclusive > SORT_BINS)
-        return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_sort_bucket_begin: the bins must be 0 <= lo < hi <= 4096");
+    if (!bins_ok(lo_bin, hi_bin_exclusive)) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_sort_bucket_begin: the bins must be 0 <= lo < hi <= 4096");
     BSK_ENTER(c);
     return sort_bucket_begin(c, lo_bin, hi_bin_exclusive);
 }
 
 int bsk_sort_bucket_add(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                         void* stream) {
-    return record_call(c, nullptr, Op::Sort, true, "", shard, n, on_device, format, stream, CallValues(), [&](const uint8_t* d, hipStream_t st) {
-        const int rc = run_multiline(c, [&](const uint8_t* t, const uint64_t* e) { return sort_bucket_add(c, t, e[0], format, first_record, st); },
-                                     d, {n}, format, st);
-        if (rc != BSK_OK) sort_bucket_abort(c);  // an error in add closes the bucket
-        return rc;
-    });
+    return bucket_pass(c, nullptr, Op::Sort, true, true, shard, n, on_device, format, stream,
+                       [&](const uint8_t* t, size_t m, hipStream_t st) { return sort_bucket_add(c, t, m, format, first_record, st); });
 }
 
 int bsk_sort_bucket_finish(bsk_ctx* c, void* stream, bsk_out* out) {
-    if (!c) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: null context");
-    if (c->op != Op::Sort || !out) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: not a Sort context");
-    if (c->device < 0) return fail(c, BSK_ERR_NO_DEVICE, "libbsk: context was created without a device");
-    out->d_seg_src = nullptr; out->d_seg_off = nullptr; out->n_segments = 0;
+    const int rc = bucket_finish_check(c, Op::Sort, "a Sort", out);
+    if (rc != BSK_OK) return rc;
     BSK_ENTER(c);
     c->pend_out.kind = 0;
     HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), (hipStream_t)stream));
@@ -1461,36 +1469,27 @@ int bsk_rmdup_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int fo
     return run_record_op(c, Op::RmDup, shard, n, on_device, format, stream, out);
 }
 
-// ---- rmdup in buckets of the key (include/bsk.h; the passes are in ops_host_rmdupbuckets.cpp).  A wrapped FASTQ shard runs once
-// more as its 4-line rewrite (run_multiline), like bsk_rmdup_run's
-static int rmdup_ctx_check(bsk_ctx* c) {
-    if (!c) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: null context");
-    if (c->op != Op::RmDup) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: not an RmDup context");
-    if (c->device < 0) return fail(c, BSK_ERR_NO_DEVICE, "libbsk: context was created without a device");
-    return BSK_OK;
-}
-
+// ---- rmdup in buckets of the key
 int bsk_rmdup_hist_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                        void* stream, uint64_t* n_records) {
     const int rcc = rmdup_ctx_check(c);
     if (rcc != BSK_OK) return rcc;
-    return record_call(c, nullptr, Op::RmDup, true, "", shard, n, on_device, format, stream, CallValues(), [&](const uint8_t* d, hipStream_t st) {
-        return run_multiline(c, [&](const uint8_t* t, const uint64_t* e) { return rmdup_hist_device(c, t, e[0], format, st, n_records); }, d, {n}, format, st);
-    });
+    return bucket_pass(c, nullptr, Op::RmDup, true, false, shard, n, on_device, format, stream,
+                       [&](const uint8_t* t, size_t m, hipStream_t st) { return rmdup_hist_device(c, t, m, format, st, n_records); });
 }
 
 int bsk_rmdup_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) {
     const int rcc = rmdup_ctx_check(c);
     if (rcc != BSK_OK) return rcc;
     BSK_ENTER(c);
-    return rmdup_hist_get(c, bytes, records);
+    return bucket_hist_get(c, &c->rdb, bytes, records);
 }
 
 int bsk_rmdup_hist_reset(bsk_ctx* c) {
     const int rcc = rmdup_ctx_check(c);
     if (rcc != BSK_OK) return rcc;
     BSK_ENTER(c);
-    return rmdup_hist_reset(c);
+    return bucket_hist_reset(c, &c->rdb);
 }
 
 int bsk_rmdup_verdict_begin(bsk_ctx* c, uint64_t total_records) {
@@ -1511,8 +1510,7 @@ int bsk_rmdup_verdict_get(bsk_ctx* c, uint64_t first, uint64_t count, uint8_t* r
 int bsk_rmdup_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin_exclusive) {
     const int rcc = rmdup_ctx_check(c);
     if (rcc != BSK_OK) return rcc;
-    if (lo_bin >= hi_bin_exclusive || hi_bin_exclusive > RMDUP_BINS)
-        return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_rmdup_bucket_begin: the bins must be 0 <= lo < hi <= 4096");
+    if (!bins_ok(lo_bin, hi_bin_exclusive)) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_rmdup_bucket_begin: the bins must be 0 <= lo < hi <= 4096");
     BSK_ENTER(c);
     return rmdup_bucket_begin(c, lo_bin, hi_bin_exclusive);
 }
@@ -1521,12 +1519,8 @@ int bsk_rmdup_bucket_add(bsk_ctx* c, const void* shard, size_t n, int on_device,
                          void* stream) {
     const int rcc = rmdup_ctx_check(c);
     if (rcc != BSK_OK) return rcc;
-    return record_call(c, nullptr, Op::RmDup, true, "", shard, n, on_device, format, stream, CallValues(), [&](const uint8_t* d, hipStream_t st) {
-        const int rc = run_multiline(c, [&](const uint8_t* t, const uint64_t* e) { return rmdup_bucket_add(c, t, e[0], format, first_record, st); },
-                                     d, {n}, format, st);
-        if (rc != BSK_OK) rmdup_bucket_abort(c);  // an error in add closes the bucket
-        return rc;
-    });
+    return bucket_pass(c, nullptr, Op::RmDup, true, true, shard, n, on_device, format, stream,
+                       [&](const uint8_t* t, size_t m, hipStream_t st) { return rmdup_bucket_add(c, t, m, format, first_record, st); });
 }
 
 int bsk_rmdup_bucket_finish(bsk_ctx* c, void* stream, uint64_t* n_removed, uint64_t* n_flagged) {
@@ -1541,11 +1535,8 @@ int bsk_rmdup_emit_run(bsk_ctx* c, const void* shard, size_t n, int on_device, i
                        void* stream, bsk_out* out) {
     const int rcc = rmdup_ctx_check(c);
     if (rcc != BSK_OK) return rcc;
-    return record_call(c, out, Op::RmDup, out != nullptr, "", shard, n, on_device, format, stream, CallValues(), [&](const uint8_t* d, hipStream_t st) {
-        c->pend_out.kind = 0;
-        return run_multiline(c, [&](const uint8_t* t, const uint64_t* e) { return rmdup_emit_device(c, t, e[0], format, first_record, st, out); },
-                             d, {n}, format, st);
-    });
+    return bucket_pass(c, out, Op::RmDup, out != nullptr, false, shard, n, on_device, format, stream,
+                       [&](const uint8_t* t, size_t m, hipStream_t st) { return rmdup_emit_device(c, t, m, format, first_record, st, out); });
 }
 
 // ---- rmdup across ranks: the phases between which the caller runs the all-to-all exchanges (include/bsk.h)

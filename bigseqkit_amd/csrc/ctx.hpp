@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "bucket_hist_dev.hpp"
 #include "index.hpp"
 #include "opts.hpp"
 #include "regex_nfa.hpp"
@@ -175,17 +176,23 @@ struct bsk_ctx {
         uint32_t* d_len = nullptr;
         uint64_t rec_cap = 0, n = 0, total = 0;
     };
-    // shuffle in buckets of the draw (ops_host_shuffle.cpp; PARITY.md SHUF): the fine-bin histogram, which accumulates over the
-    // shards of a call sequence, and the open bucket (every shard's share of its accumulation begins on a 256-byte boundary)
-    struct ShuffleBuckets : BucketAcc {
-        uint64_t* d_hist = nullptr;      // bytes[4096] ++ records[4096]
+    // What the three bucket paths keep on top of the accumulation, and the owner of their steps (bucket_hist_*, bucket_begin,
+    // bucket_require_open, bucket_in_order, bucket_close in ops_host_shuffle.cpp): the fine-bin histogram, which accumulates
+    // over the shards of a call sequence, and the open bucket
+    struct BucketState : BucketAcc {
+        uint64_t* d_hist = nullptr;      // bytes[BUCKET_BINS] ++ records[BUCKET_BINS]
         bool open = false;
-        uint64_t lo = 0, hi = 0;         // the draws of the open bucket, both inclusive
-    } shb;
+        uint32_t lo = 0, hi = 0;         // the bins of the open bucket, hi exclusive
+        uint64_t next_first = 0;         // sort, rmdup: the shards of a bucket arrive in input order, this is the lowest
+                                         // first_record the next may have.  shuffle does not enforce an order and leaves it 0
+    };
+    // shuffle in buckets of the draw (ops_host_shuffle.cpp; PARITY.md SHUF): every shard's share of the accumulation begins on
+    // a 256-byte boundary; the draws of the open bucket are those whose upper bits lie in [lo, hi)
+    struct ShuffleBuckets : BucketState {} shb;
     // sort in buckets of the key (ops_host_sortbuckets.cpp; PARITY.md SORT): the sample of keys with their draws (host side; it
-    // thins itself by halving `threshold`), the installed splitters (host copy and packed on the device), the fine-bin
-    // histogram, and the open bucket, whose accumulation is packed: sort_run_device reads it as one text
-    struct SortBuckets : BucketAcc {
+    // thins itself by halving `threshold`), the installed splitters (host copy and packed on the device), and the open bucket,
+    // whose accumulation is packed: sort_run_device reads it as one text
+    struct SortBuckets : BucketState {
         std::vector<std::string> sample_keys;
         std::vector<uint64_t> sample_draws;
         uint64_t threshold = 0;          // records with (draw >> 11) < threshold are in the sample (0: none taken yet)
@@ -194,12 +201,8 @@ struct bsk_ctx {
         std::vector<uint32_t> spl_off{0};
         uint8_t* d_spl = nullptr;
         uint32_t* d_spl_off = nullptr;
-        uint64_t* d_hist = nullptr;      // bytes[4096] ++ records[4096]
-        bool open = false;
-        uint32_t lo = 0, hi = 0;         // the bins of the open bucket, hi exclusive
-        uint64_t next_first = 0;         // the shards of a bucket arrive in input order: the lowest first_record the next may have
         int format = -1;                 // of the accumulated text
-    };                                   // (the member `sob` is the last one of the context: see there)
+    };                                   // (the member `sob` is the last but one of the context: see there)
     uint8_t* d_hg_words = nullptr;
     uint32_t* d_hg_off = nullptr;
     uint32_t* d_hg_counts = nullptr;     // n_i of the records of the running window
@@ -427,26 +430,23 @@ struct bsk_ctx {
     }
     void warn(const std::string& m, bool unless_quiet = false) const { log("WARN", m, unless_quiet); }
     void info(const std::string& m, bool unless_quiet = false) const { log("INFO", m, unless_quiet); }
-    // Behind everything else, so that the members in front of it keep the offsets they had before `sort` had buckets.  With
-    // this state beside `shb` the calls that index a FASTA shard (bsk_shuffle_hist_run, bsk_shuffle_bucket_add) took 0.06 ms
-    // longer on the host in seven of eight processes; here they take the time they took before (profiles/sort_buckets.md,
-    // "The unchanged path", series A against B / C).  The mechanism is not known: a member added behind `sob`, or ahead of the
-    // members of the index passes, wants scripts/bench_bucket_calls.py run against the commit before it.
+    // Behind everything else, so that the members in front of it keep the offsets they had before `sort` had buckets, and
+    // `shb` the size it had (BucketState is laid out for that).  With this state beside `shb` the calls that index a FASTA
+    // shard (bsk_shuffle_hist_run, bsk_shuffle_bucket_add) took 0.06 ms longer on the host in seven of eight processes; here
+    // they take the time they took before (profiles/sort_buckets.md, "The unchanged path", series A against B / C).  The
+    // mechanism is not known: a member added to BucketState, behind `sob`, or ahead of the members of the index passes, wants
+    // scripts/bench_bucket_calls.py run against the commit before it.
     SortBuckets sob;
-    // rmdup in buckets of the key (ops_host_rmdupbuckets.cpp; PARITY.md RMDUPB): the fine-bin histogram, the removed-bitmap of
-    // the whole input with the bins that are decided, and the open bucket, whose accumulation holds SUBJECTS: d_draw = the
-    // global record index, d_off / d_len = the subject in d_acc, d_key = k1.  (Behind `sob`, for the reason given there.)
-    struct RmDupBuckets : BucketAcc {
-        uint64_t* d_key = nullptr;       // [rec_cap]
-        uint64_t* d_hist = nullptr;      // bytes[4096] ++ records[4096]
+    // rmdup in buckets of the key (ops_host_rmdupbuckets.cpp; PARITY.md RMDUPB): the removed-bitmap of the whole input with the
+    // bins that are decided, and the open bucket, whose accumulation holds SUBJECTS: d_draw = the global record index,
+    // d_off / d_len = the subject in d_acc, d_key = k1.  (Behind `sob`, for the reason given there.)
+    struct RmDupBuckets : BucketState {
+        uint64_t* d_key = nullptr;       // [rec_cap]: grows with the three of BucketAcc (bucket_acc_reserve)
         uint32_t* d_bits = nullptr;      // bit g set: record g of the input is removed
         uint64_t bits_words = 0;
         uint64_t total_records = 0;
         bool verdict = false;            // bsk_rmdup_verdict_begin was called
-        std::vector<uint8_t> decided = std::vector<uint8_t>(4096, 0);
-        bool open = false;
-        uint32_t lo = 0, hi = 0;         // the bins of the open bucket, hi exclusive
-        uint64_t next_first = 0;         // the shards of a bucket arrive in input order
+        std::vector<uint8_t> decided = std::vector<uint8_t>(bsk::BUCKET_BINS, 0);
     } rdb;
 };
 

@@ -70,7 +70,6 @@ void validate_sample_opts(bsk_ctx* c);
 int sample_resolve(bsk_ctx* c, uint64_t n_records);
 // shuffle in buckets of the draw (ops_host_shuffle.cpp; include/bsk.h)
 int shuffle_hist_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st, uint64_t* n_records);
-int shuffle_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records);
 int shuffle_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin);
 int shuffle_bucket_add(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st);
 int shuffle_bucket_finish(bsk_ctx* c, hipStream_t st, bsk_out* out);
@@ -82,21 +81,15 @@ void sort_sample_reset(bsk_ctx* c);
 int sort_splitters_install(bsk_ctx* c, const std::vector<std::string>& splitters);
 int sort_splitters_build(bsk_ctx* c, uint32_t max_bins, uint32_t* n_bins);
 int sort_hist_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, uint64_t* n_records);
-int sort_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records);
-int sort_hist_reset(bsk_ctx* c);
 int sort_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin);
 int sort_bucket_add(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st);
-void sort_bucket_abort(bsk_ctx* c);  // an add that failed for good closes the bucket
 int sort_bucket_finish(bsk_ctx* c, hipStream_t st, bsk_out* out);
 // rmdup in buckets of the key (ops_host_rmdupbuckets.cpp; include/bsk.h)
 int rmdup_hist_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, uint64_t* n_records);
-int rmdup_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records);
-int rmdup_hist_reset(bsk_ctx* c);
 int rmdup_verdict_begin(bsk_ctx* c, uint64_t total_records);
 int rmdup_verdict_get(bsk_ctx* c, uint64_t first, uint64_t count, uint8_t* removed);
 int rmdup_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin);
 int rmdup_bucket_add(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st);
-void rmdup_bucket_abort(bsk_ctx* c);  // an add that failed for good closes the bucket
 int rmdup_bucket_finish(bsk_ctx* c, hipStream_t st, uint64_t* n_removed, uint64_t* n_flagged);
 int rmdup_emit_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st, bsk_out* out);
 void validate_head_genome_opts(bsk_ctx* c);

@@ -148,8 +148,32 @@ struct BucketAccumulate {
     uint64_t o_koff = 0;  // (between queue and collect)
     size_t n_eff = 0;
 };
-int bucket_acc_reserve(bsk_ctx* c, bsk_ctx::BucketAcc* B, uint64_t bytes, uint64_t recs, bool with_records, hipStream_t st);
+int bucket_acc_reserve(bsk_ctx* c, bsk_ctx::BucketAcc* B, uint64_t bytes, uint64_t recs, bool with_records, hipStream_t st,
+                       uint64_t** extra = nullptr);  // extra: one more array of `recs` words (rmdup's keys), grown with the three
 inline void bucket_acc_clear(bsk_ctx::BucketAcc* B) { B->n = 0; B->acc_used = 0; B->total = 0; }
+// The life cycle of a bucket (bsk_ctx::BucketState), written once for shuffle, sort and rmdup.  `op` is "shuffle" / "sort" /
+// "rmdup": the messages name bsk_<op>_bucket_<fn>.
+//   bucket_hist_alloc / _get / _reset   the counters exist and are zero / copied to the host (null: not wanted) / zeroed
+//   bucket_require_closed   INVALID_ARG "a bucket is open" in the name of bsk_<op>_<fn>
+//   bucket_begin    refuses an open bucket; the bucket is bins [lo, hi), empty, next_first 0; with a histogram in this context
+//                 its bytes and records over the bins are read back, 2^32 records refused, and reserve(bytes, recs) -- the
+//                 caller's bucket_acc_reserve -- called when there are records; then open
+//   bucket_require_open     INVALID_ARG "no bucket is open" in the name of bsk_<op>_bucket_<fn>
+//   bucket_in_order   INVALID_ARG when first_record lies below next_first (bsk_<op>_bucket_add)
+//   bucket_close    the end of finish, and of an add that failed for good
+int bucket_hist_alloc(bsk_ctx* c, bsk_ctx::BucketState* B, hipStream_t st);
+int bucket_hist_get(bsk_ctx* c, bsk_ctx::BucketState* B, uint64_t* bytes, uint64_t* records);
+int bucket_hist_reset(bsk_ctx* c, bsk_ctx::BucketState* B);
+int bucket_require_closed(bsk_ctx* c, const bsk_ctx::BucketState& B, const char* op, const char* fn);
+int bucket_begin(bsk_ctx* c, bsk_ctx::BucketState* B, const char* op, uint32_t lo_bin, uint32_t hi_bin,
+                 const std::function<int(uint64_t bytes, uint64_t recs)>& reserve);
+int bucket_require_open(bsk_ctx* c, const bsk_ctx::BucketState& B, const char* op, const char* fn);
+int bucket_in_order(bsk_ctx* c, const bsk_ctx::BucketState& B, const char* op, uint64_t first_record);
+int bucket_too_many(bsk_ctx* c, const char* op);  // UNSUPPORTED: 2^32 or more records in one bucket of <op>
+inline void bucket_close(bsk_ctx::BucketState* B) { B->open = false; bucket_acc_clear(B); }
+// the record table of a shard and the complaints of its index pass, read BEFORE any kernel walks the table (a shard that is
+// wrapped behind its head goes to the multi-line reader, run_multiline): one synchronisation
+int index_shard_status(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st);
 // The key of `sort` on the host side (ops_host_next.cpp), shared by sort_run_device and the bucket passes
 // (ops_host_sortbuckets.cpp): the parameters that the options and the shard give, and for -N (IDs / names) the rewritten keys
 // in an allocation of their own -- P.nat / P.nat_off point into it, it lives as long as `nat`.  One synchronisation.

@@ -25,17 +25,9 @@ namespace bsk {
 
 constexpr uint64_t RDB_FLAG_MAX = 1u << 20;  // more flagged records than this in one bucket: the call fails (as XFLAG_MAX)
 
-static int rdb_hist_alloc(bsk_ctx* c, hipStream_t st) {
-    if (c->rdb.d_hist) return BSK_OK;
-    HIP_TRYX(c, hipMalloc((void**)&c->rdb.d_hist, 2 * RMDUP_BINS * sizeof(uint64_t)));
-    HIP_TRYX(c, hipMemsetAsync(c->rdb.d_hist, 0, 2 * RMDUP_BINS * sizeof(uint64_t), st));
-    return BSK_OK;
-}
-
-// ---- what the histogram and the collect pass do first: the table of the shard, the complaints of the index pass (read BEFORE
-// any kernel walks the table: a shard that is wrapped behind its head goes to the multi-line reader, run_multiline), the text
-// view (-s on FASTA: every wrapped record flattened, as rmdup_run_device has it), the parameters and k1 of every record in
-// c->d_keys -- whole: the bin comes from all 64 bits
+// ---- what the histogram and the collect pass do first: the table of the shard and the complaints of the index pass
+// (index_shard_status), the text view (-s on FASTA: every wrapped record flattened, as rmdup_run_device has it), the
+// parameters and k1 of every record in c->d_keys -- whole: the bin comes from all 64 bits
 struct RdbShard {
     TextTableH tt;
     RmDupParams P;
@@ -53,17 +45,9 @@ static RmDupParams rdb_params(bsk_ctx* c, const uint8_t* d_buf, size_t n, bool f
     P.buf_end = d_buf + n;
     return P;
 }
-static int rdb_index_status(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st) {
-    int rc = build_index(c, d_buf, n, format, st);
-    if (rc != BSK_OK) return rc;
-    uint64_t status = 0;
-    HIP_TRYX(c, hipMemcpyAsync(&status, c->d_status, sizeof status, hipMemcpyDeviceToHost, st));
-    HIP_TRYX(c, hipStreamSynchronize(st));
-    return kernel_error_to_status(c, status);
-}
 static int rdb_index_shard(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, RdbShard* S) {
     const bool fastq = format == BSK_FORMAT_FASTQ;
-    int rc = rdb_index_status(c, d_buf, n, format, st);
+    int rc = index_shard_status(c, d_buf, n, format, st);
     if (rc != BSK_OK || c->table.n == 0) return rc;
     rc = prepare_text(c, d_buf, format, st, &S->tt, /*flatten=*/!fastq && c->opts.b("BySeq"), false, n);
     if (rc != BSK_OK) return rc;
@@ -87,7 +71,7 @@ int rmdup_hist_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hi
         c->set_error("libbsk: -d / -D side files are not available on the rmdup path in buckets of the key");
         return BSK_ERR_UNSUPPORTED;
     }
-    int rc = rdb_hist_alloc(c, st);
+    int rc = bucket_hist_alloc(c, &c->rdb, st);
     if (rc != BSK_OK) return rc;
     RdbShard S;
     rc = rdb_index_shard(c, d_buf, n, format, st, &S);  // (the counters accumulate: the complaints of the index pass come first)
@@ -95,32 +79,15 @@ int rmdup_hist_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hi
     if (n_records) *n_records = c->table.n;
     if (c->table.n == 0) return BSK_OK;
     Timed tm(c, "k_rdb_hist", st);
-    HIP_TRYX(c, launch_rdb_hist(d_buf, c->table, S.tt, S.P, c->d_keys, c->rdb.d_hist, c->rdb.d_hist + RMDUP_BINS, c->num_cus, st));
-    return BSK_OK;
-}
-
-int rmdup_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) {
-    int rc = rdb_hist_alloc(c, nullptr);
-    if (rc != BSK_OK) return rc;
-    HIP_TRYX(c, hipDeviceSynchronize());
-    if (bytes) HIP_TRYX(c, hipMemcpy(bytes, c->rdb.d_hist, RMDUP_BINS * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (records) HIP_TRYX(c, hipMemcpy(records, c->rdb.d_hist + RMDUP_BINS, RMDUP_BINS * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    return BSK_OK;
-}
-
-int rmdup_hist_reset(bsk_ctx* c) {
-    HIP_TRYX(c, hipDeviceSynchronize());
-    if (c->rdb.d_hist) HIP_TRYX(c, hipMemset(c->rdb.d_hist, 0, 2 * RMDUP_BINS * sizeof(uint64_t)));
+    HIP_TRYX(c, launch_rdb_hist(d_buf, c->table, S.tt, S.P, c->d_keys, c->rdb.d_hist, c->rdb.d_hist + BUCKET_BINS, c->num_cus, st));
     return BSK_OK;
 }
 
 // ---- the verdict
 int rmdup_verdict_begin(bsk_ctx* c, uint64_t total_records) {
     bsk_ctx::RmDupBuckets& B = c->rdb;
-    if (B.open) {
-        c->set_error("libbsk: bsk_rmdup_verdict_begin: a bucket is open (bsk_rmdup_bucket_finish ends it)");
-        return BSK_ERR_INVALID_ARG;
-    }
+    const int rc = bucket_require_closed(c, B, "rmdup", "verdict_begin");
+    if (rc != BSK_OK) return rc;
     const uint64_t words = (total_records + 31) / 32 + 1;
     HIP_TRYX(c, hipDeviceSynchronize());
     if (words > B.bits_words || !B.d_bits) {
@@ -161,71 +128,30 @@ int rmdup_verdict_get(bsk_ctx* c, uint64_t first, uint64_t count, uint8_t* remov
 }
 
 // ---- one bucket
-static void rdb_bucket_close(bsk_ctx* c) {
-    c->rdb.open = false;
-    bucket_acc_clear(&c->rdb);
-}
-
-// the accumulation for `bytes` subject bytes and `recs` records; the key array grows with the three of BucketAcc
+// the accumulation for `bytes` subject bytes and `recs` records, the keys among them
 static int rdb_reserve(bsk_ctx* c, uint64_t bytes, uint64_t recs, hipStream_t st) {
-    bsk_ctx::RmDupBuckets& B = c->rdb;
-    if (recs > B.rec_cap || !B.d_key || !B.d_draw) {
-        const uint64_t cap = recs + recs / 4 + 256;  // (the capacity bucket_acc_reserve gives the other three)
-        uint64_t* nk = nullptr;
-        HIP_TRYX(c, hipMalloc((void**)&nk, cap * sizeof(uint64_t)));
-        if (B.d_key && B.n) HIP_TRYX(c, hipMemcpyAsync(nk, B.d_key, B.n * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
-        HIP_TRYX(c, hipStreamSynchronize(st));
-        if (B.d_key) HIP_TRYX(c, hipFree(B.d_key));
-        B.d_key = nk;  // (the three of BucketAcc grow on the same condition just below: one capacity for all four)
-    }
-    return bucket_acc_reserve(c, &B, bytes, recs, true, st);
+    return bucket_acc_reserve(c, &c->rdb, bytes, recs, true, st, &c->rdb.d_key);
 }
 
 int rmdup_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin) {
-    bsk_ctx::RmDupBuckets& B = c->rdb;
-    if (B.open) {
-        c->set_error("libbsk: bsk_rmdup_bucket_begin: a bucket is open (bsk_rmdup_bucket_finish ends it)");
-        return BSK_ERR_INVALID_ARG;
-    }
-    if (!B.verdict) {
+    // (an open bucket has a verdict, so the order of this refusal and the one of bucket_begin does not show)
+    if (!c->rdb.verdict) {
         c->set_error("libbsk: bsk_rmdup_bucket_begin: no verdict to write to (bsk_rmdup_verdict_begin first)");
         return BSK_ERR_INVALID_ARG;
     }
-    B.lo = lo_bin;
-    B.hi = hi_bin;
-    B.next_first = 0;
-    bucket_acc_clear(&B);
-    if (B.d_hist) {
-        // the histogram of this context says what the bucket will hold: the accumulation is allocated once
-        std::vector<uint64_t> h(2 * RMDUP_BINS);
-        HIP_TRYX(c, hipDeviceSynchronize());
-        HIP_TRYX(c, hipMemcpy(h.data(), B.d_hist, h.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        uint64_t bytes = 0, recs = 0;
-        for (uint32_t b = lo_bin; b < hi_bin; ++b) { bytes += h[b]; recs += h[RMDUP_BINS + b]; }
-        if (recs >= (1ull << 32)) {
-            c->set_error("libbsk: rmdup: 2^32 or more records in one bucket are not supported (a smaller budget makes more buckets)");
-            return BSK_ERR_UNSUPPORTED;
-        }
-        if (recs) {
-            const int rc = rdb_reserve(c, bytes - recs * RMDUP_BUCKET_RECORD_BYTES, recs, nullptr);
-            if (rc != BSK_OK) return rc;
-        }
-    }
-    B.open = true;
-    return BSK_OK;
+    return bucket_begin(c, &c->rdb, "rmdup", lo_bin, hi_bin, [&](uint64_t bytes, uint64_t recs) {
+        return rdb_reserve(c, bytes - recs * RMDUP_BUCKET_RECORD_BYTES, recs, nullptr);  // (the histogram counts the per-record arrays in)
+    });
 }
 
 static int rdb_bucket_add_open(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st) {
     bsk_ctx::RmDupBuckets& B = c->rdb;
     c->last_kernel_flags = 0;
     // the survivor of a group is its lowest accumulated index because the accumulation receives its records in input order
-    if (first_record < B.next_first) {
-        c->set_error("libbsk: bsk_rmdup_bucket_add: first_record " + std::to_string(first_record) + " goes backwards (the shards of a bucket are "
-                     "added in input order; the next one starts at record " + std::to_string(B.next_first) + " or later)");
-        return BSK_ERR_INVALID_ARG;
-    }
+    int rc = bucket_in_order(c, B, "rmdup", first_record);
+    if (rc != BSK_OK) return rc;
     RdbShard S;
-    int rc = rdb_index_shard(c, d_buf, n, format, st, &S);
+    rc = rdb_index_shard(c, d_buf, n, format, st, &S);
     if (rc != BSK_OK) return rc;
     const uint64_t N = c->table.n;
     if (first_record > B.total_records || N > B.total_records - first_record) {
@@ -259,10 +185,7 @@ static int rdb_bucket_add_open(bsk_ctx* c, const uint8_t* d_buf, size_t n, int f
     if (rc != BSK_OK) return rc;
     const uint64_t long_count = c->h_ctl[8 + 2];  // (d_counter is d_ctl[8 ..])
     if (kept) {
-        if (B.n + kept >= (1ull << 32)) {
-            c->set_error("libbsk: rmdup: 2^32 or more records in one bucket are not supported (a smaller budget makes more buckets)");
-            return BSK_ERR_UNSUPPORTED;
-        }
+        if (B.n + kept >= (1ull << 32)) return bucket_too_many(c, "rmdup");
         rc = rdb_reserve(c, B.acc_used + total, B.n + kept, st);
         if (rc != BSK_OK) return rc;
         Timed tm(c, "k_rdb_pack", st);
@@ -280,16 +203,10 @@ static int rdb_bucket_add_open(bsk_ctx* c, const uint8_t* d_buf, size_t n, int f
 }
 
 int rmdup_bucket_add(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st) {
-    if (!c->rdb.open) {
-        c->set_error("libbsk: bsk_rmdup_bucket_add: no bucket is open (bsk_rmdup_bucket_begin first)");
-        return BSK_ERR_INVALID_ARG;
-    }
-    // (no close on an error here: a wrapped FASTQ shard comes back once more as its 4-line rewrite -- run_multiline -- and needs
-    // the bucket; the entry point closes it when the call has failed for good, rmdup_bucket_abort)
-    return rdb_bucket_add_open(c, d_buf, n, format, first_record, st);
+    const int rc = bucket_require_open(c, c->rdb, "rmdup", "add");
+    if (rc != BSK_OK) return rc;
+    return rdb_bucket_add_open(c, d_buf, n, format, first_record, st);  // (no close on an error here: see sort_bucket_add)
 }
-
-void rmdup_bucket_abort(bsk_ctx* c) { rdb_bucket_close(c); }
 
 // The flagged records -- accumulated indices whose subject differs from that of the record their key group names -- settled
 // exactly, as PARITY KEYS (b) does: grouped by TEXT on the host, the lowest global index of every text survives (all records of
@@ -412,17 +329,15 @@ static int rdb_bucket_decide(bsk_ctx* c, hipStream_t st, uint64_t* n_removed, ui
 
 int rmdup_bucket_finish(bsk_ctx* c, hipStream_t st, uint64_t* n_removed, uint64_t* n_flagged) {
     bsk_ctx::RmDupBuckets& B = c->rdb;
-    if (!B.open) {
-        c->set_error("libbsk: bsk_rmdup_bucket_finish: no bucket is open (bsk_rmdup_bucket_begin first)");
-        return BSK_ERR_INVALID_ARG;
-    }
+    int rc = bucket_require_open(c, B, "rmdup", "finish");
+    if (rc != BSK_OK) return rc;
     uint64_t removed = 0, flagged = 0;
-    const int rc = rdb_bucket_decide(c, st, &removed, &flagged);
+    rc = rdb_bucket_decide(c, st, &removed, &flagged);
     if (n_removed) *n_removed = removed;
     if (n_flagged) *n_flagged = flagged;
     if (rc == BSK_OK)
         for (uint32_t b = B.lo; b < B.hi; ++b) B.decided[b] = 1;
-    rdb_bucket_close(c);
+    bucket_close(&B);
     return rc;
 }
 
@@ -434,7 +349,7 @@ int rmdup_emit_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, ui
         c->set_error("libbsk: bsk_rmdup_emit_run: no verdict (bsk_rmdup_verdict_begin and the buckets first)");
         return BSK_ERR_INVALID_ARG;
     }
-    for (uint32_t b = 0; b < RMDUP_BINS; ++b)
+    for (uint32_t b = 0; b < BUCKET_BINS; ++b)
         if (!B.decided[b]) {
             c->set_error("libbsk: bsk_rmdup_emit_run: fine bin " + std::to_string(b) + " has not been decided (every bin belongs to a bucket that "
                          "was finished since bsk_rmdup_verdict_begin)");
@@ -445,7 +360,7 @@ int rmdup_emit_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, ui
         return BSK_ERR_UNSUPPORTED;
     }
     const bool fastq = format == BSK_FORMAT_FASTQ;
-    int rc = rdb_index_status(c, d_buf, n, format, st);
+    int rc = index_shard_status(c, d_buf, n, format, st);
     if (rc != BSK_OK) return rc;
     const uint64_t N = c->table.n;
     if (first_record > B.total_records || N > B.total_records - first_record) {

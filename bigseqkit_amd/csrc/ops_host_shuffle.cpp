@@ -82,17 +82,10 @@ int shuffle_order_emit(bsk_ctx* c, const ShuffleRecords& R, hipStream_t st, bsk_
 // finish.  The order of the output is the order of the draws, and a draw is a pure function of (seed, global record index),
 // so the records whose draws lie in one interval can be collected from the input piece by piece and sorted on their own.
 // ---------------------------------------------------------------------------
-static int shuffle_hist_alloc(bsk_ctx* c, hipStream_t st) {
-    if (c->shb.d_hist) return BSK_OK;
-    HIP_TRYX(c, hipMalloc((void**)&c->shb.d_hist, 2 * SHUFFLE_BINS * sizeof(uint64_t)));
-    HIP_TRYX(c, hipMemsetAsync(c->shb.d_hist, 0, 2 * SHUFFLE_BINS * sizeof(uint64_t), st));
-    return BSK_OK;
-}
-
 int shuffle_hist_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st, uint64_t* n_records) {
     c->last_kernel_flags = 0;
     int fastq = 0;
-    int rc = shuffle_hist_alloc(c, st);
+    int rc = bucket_hist_alloc(c, &c->shb, st);
     if (rc != BSK_OK) return rc;
     // the counters accumulate, so the index pass's complaints (a shard that is wrapped behind its head) are read BEFORE the
     // histogram kernel runs -- of an empty table too: this is the one synchronisation of the pass, nothing is read back after
@@ -102,22 +95,18 @@ int shuffle_hist_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, 
     if (n_records) *n_records = c->table.n;
     if (c->table.n == 0) return BSK_OK;
     Timed tm(c, "k_shuffle_hist", st);
-    HIP_TRYX(c, launch_shuffle_hist(d_buf, n, c->table, fastq, first_record, c->opts.i("Seed"), c->shb.d_hist, c->shb.d_hist + SHUFFLE_BINS,
+    HIP_TRYX(c, launch_shuffle_hist(d_buf, n, c->table, fastq, first_record, c->opts.i("Seed"), c->shb.d_hist, c->shb.d_hist + BUCKET_BINS,
                                     c->num_cus, st));
     return BSK_OK;
 }
 
-int shuffle_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) {
-    int rc = shuffle_hist_alloc(c, nullptr);
-    if (rc != BSK_OK) return rc;
-    HIP_TRYX(c, hipDeviceSynchronize());
-    if (bytes) HIP_TRYX(c, hipMemcpy(bytes, c->shb.d_hist, SHUFFLE_BINS * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (records) HIP_TRYX(c, hipMemcpy(records, c->shb.d_hist + SHUFFLE_BINS, SHUFFLE_BINS * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    return BSK_OK;
+int bucket_too_many(bsk_ctx* c, const char* op) {
+    c->set_error(std::string("libbsk: ") + op + ": 2^32 or more records in one bucket are not supported (a smaller budget makes more buckets)");
+    return BSK_ERR_UNSUPPORTED;
 }
 
 // ---- the accumulate step of an open bucket (ops_host_internal.hpp)
-int bucket_acc_reserve(bsk_ctx* c, bsk_ctx::BucketAcc* Bp, uint64_t bytes, uint64_t recs, bool with_records, hipStream_t st) {
+int bucket_acc_reserve(bsk_ctx* c, bsk_ctx::BucketAcc* Bp, uint64_t bytes, uint64_t recs, bool with_records, hipStream_t st, uint64_t** extra) {
     bsk_ctx::BucketAcc& B = *Bp;
     auto regrow = [&](auto** p, uint64_t used, uint64_t cap) -> int {
         using T = std::remove_reference_t<decltype(**p)>;
@@ -136,9 +125,10 @@ int bucket_acc_reserve(bsk_ctx* c, bsk_ctx::BucketAcc* Bp, uint64_t bytes, uint6
         if (rc != BSK_OK) return rc;
         B.acc_cap = cap;
     }
-    if (with_records && (recs > B.rec_cap || !B.d_draw)) {
+    if (with_records && (recs > B.rec_cap || !B.d_draw || (extra && !*extra))) {
         const uint64_t cap = recs + recs / 4 + 256;
-        rc = regrow(&B.d_draw, B.n, cap);
+        rc = extra ? regrow(extra, B.n, cap) : BSK_OK;
+        if (rc == BSK_OK) rc = regrow(&B.d_draw, B.n, cap);
         if (rc == BSK_OK) rc = regrow(&B.d_off, B.n, cap);
         if (rc == BSK_OK) rc = regrow(&B.d_len, B.n, cap);
         if (rc != BSK_OK) return rc;
@@ -170,10 +160,7 @@ int BucketAccumulate::queue(size_t n, int fastq) {
 int BucketAccumulate::collect() {
     const uint64_t N = c->table.n;
     if (kept == 0) return BSK_OK;
-    if (B->n + kept >= (1ull << 32)) {
-        c->set_error(std::string("libbsk: ") + op + ": 2^32 or more records in one bucket are not supported (a smaller budget makes more buckets)");
-        return BSK_ERR_UNSUPPORTED;
-    }
+    if (B->n + kept >= (1ull << 32)) return bucket_too_many(c, op);
     const uint64_t at = packed ? B->acc_used : (B->acc_used + 255) & ~255ull;  // (the segmented copy stores aligned 16-byte words)
     int rc = bucket_acc_reserve(c, B, at + total + (packed ? 64 : 0), B->n + kept, (bool)append, st);  // (packed: read as a shard, with the slack of one)
     if (rc != BSK_OK) return rc;
@@ -207,36 +194,70 @@ int BucketAccumulate::collect() {
     return BSK_OK;
 }
 
-static void shuffle_bucket_close(bsk_ctx* c) {
-    c->shb.open = false;
-    bucket_acc_clear(&c->shb);
+// ---- the life cycle of a bucket (ops_host_internal.hpp)
+constexpr size_t HIST_BYTES = 2 * BUCKET_BINS * sizeof(uint64_t);
+
+int bucket_hist_alloc(bsk_ctx* c, bsk_ctx::BucketState* B, hipStream_t st) {
+    if (B->d_hist) return BSK_OK;
+    HIP_TRYX(c, hipMalloc((void**)&B->d_hist, HIST_BYTES));
+    HIP_TRYX(c, hipMemsetAsync(B->d_hist, 0, HIST_BYTES, st));
+    return BSK_OK;
 }
 
-int shuffle_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin) {
-    bsk_ctx::ShuffleBuckets& B = c->shb;
-    if (B.open) {
-        c->set_error("libbsk: bsk_shuffle_bucket_begin: a bucket is open (bsk_shuffle_bucket_finish ends it)");
-        return BSK_ERR_INVALID_ARG;
-    }
-    B.lo = (uint64_t)lo_bin << SHUFFLE_BIN_SHIFT;
-    B.hi = hi_bin >= SHUFFLE_BINS ? ~0ull : ((uint64_t)hi_bin << SHUFFLE_BIN_SHIFT) - 1;
-    B.n = 0;
-    B.acc_used = 0;
-    B.total = 0;
+int bucket_hist_get(bsk_ctx* c, bsk_ctx::BucketState* B, uint64_t* bytes, uint64_t* records) {
+    int rc = bucket_hist_alloc(c, B, nullptr);
+    if (rc != BSK_OK) return rc;
+    HIP_TRYX(c, hipDeviceSynchronize());
+    if (bytes) HIP_TRYX(c, hipMemcpy(bytes, B->d_hist, HIST_BYTES / 2, hipMemcpyDeviceToHost));
+    if (records) HIP_TRYX(c, hipMemcpy(records, B->d_hist + BUCKET_BINS, HIST_BYTES / 2, hipMemcpyDeviceToHost));
+    return BSK_OK;
+}
+
+int bucket_hist_reset(bsk_ctx* c, bsk_ctx::BucketState* B) {
+    HIP_TRYX(c, hipDeviceSynchronize());
+    if (B->d_hist) HIP_TRYX(c, hipMemset(B->d_hist, 0, HIST_BYTES));
+    return BSK_OK;
+}
+
+int bucket_require_closed(bsk_ctx* c, const bsk_ctx::BucketState& B, const char* op, const char* fn) {
+    if (!B.open) return BSK_OK;
+    c->set_error(std::string("libbsk: bsk_") + op + "_" + fn + ": a bucket is open (bsk_" + op + "_bucket_finish ends it)");
+    return BSK_ERR_INVALID_ARG;
+}
+
+int bucket_require_open(bsk_ctx* c, const bsk_ctx::BucketState& B, const char* op, const char* fn) {
+    if (B.open) return BSK_OK;
+    c->set_error(std::string("libbsk: bsk_") + op + "_bucket_" + fn + ": no bucket is open (bsk_" + op + "_bucket_begin first)");
+    return BSK_ERR_INVALID_ARG;
+}
+
+int bucket_in_order(bsk_ctx* c, const bsk_ctx::BucketState& B, const char* op, uint64_t first_record) {
+    if (first_record >= B.next_first) return BSK_OK;
+    c->set_error(std::string("libbsk: bsk_") + op + "_bucket_add: first_record " + std::to_string(first_record) + " goes backwards (the shards of a "
+                 "bucket are added in input order; the next one starts at record " + std::to_string(B.next_first) + " or later)");
+    return BSK_ERR_INVALID_ARG;
+}
+
+int bucket_begin(bsk_ctx* c, bsk_ctx::BucketState* Bp, const char* op, uint32_t lo_bin, uint32_t hi_bin,
+                 const std::function<int(uint64_t bytes, uint64_t recs)>& reserve) {
+    bsk_ctx::BucketState& B = *Bp;
+    int rc = bucket_require_closed(c, B, op, "bucket_begin");
+    if (rc != BSK_OK) return rc;
+    B.lo = lo_bin;
+    B.hi = hi_bin;
+    B.next_first = 0;
+    bucket_acc_clear(&B);
     if (B.d_hist) {
-        // the histogram of this context says what the bucket will hold: the accumulation is allocated once (every shard's
-        // share begins on a 256-byte boundary; a shard more than expected grows it)
-        std::vector<uint64_t> h(2 * SHUFFLE_BINS);
+        // the histogram of this context says what the bucket will hold: the accumulation is allocated once (a shard more than
+        // expected grows it)
+        std::vector<uint64_t> h(2 * BUCKET_BINS);
         HIP_TRYX(c, hipDeviceSynchronize());
-        HIP_TRYX(c, hipMemcpy(h.data(), B.d_hist, h.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        HIP_TRYX(c, hipMemcpy(h.data(), B.d_hist, HIST_BYTES, hipMemcpyDeviceToHost));
         uint64_t bytes = 0, recs = 0;
-        for (uint32_t b = lo_bin; b < hi_bin; ++b) { bytes += h[b]; recs += h[SHUFFLE_BINS + b]; }
-        if (recs >= (1ull << 32)) {
-            c->set_error("libbsk: shuffle: 2^32 or more records in one bucket are not supported (a smaller budget makes more buckets)");
-            return BSK_ERR_UNSUPPORTED;
-        }
+        for (uint32_t b = lo_bin; b < hi_bin; ++b) { bytes += h[b]; recs += h[BUCKET_BINS + b]; }
+        if (recs >= (1ull << 32)) return bucket_too_many(c, op);
         if (recs) {
-            const int rc = bucket_acc_reserve(c, &B, bytes + 16 * 256, recs, true, nullptr);
+            rc = reserve(bytes, recs);
             if (rc != BSK_OK) return rc;
         }
     }
@@ -244,15 +265,32 @@ int shuffle_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin) {
     return BSK_OK;
 }
 
+int index_shard_status(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st) {
+    const int rc = build_index(c, d_buf, n, format, st);
+    if (rc != BSK_OK) return rc;
+    uint64_t status = 0;
+    HIP_TRYX(c, hipMemcpyAsync(&status, c->d_status, sizeof status, hipMemcpyDeviceToHost, st));
+    HIP_TRYX(c, hipStreamSynchronize(st));
+    return kernel_error_to_status(c, status);
+}
+
+// ---- shuffle: one bucket.  Every shard's share of the accumulation begins on a 256-byte boundary, hence the slack
+int shuffle_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin) {
+    return bucket_begin(c, &c->shb, "shuffle", lo_bin, hi_bin,
+                        [&](uint64_t bytes, uint64_t recs) { return bucket_acc_reserve(c, &c->shb, bytes + 16 * 256, recs, true, nullptr); });
+}
+
 static int shuffle_bucket_add_open(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st) {
     bsk_ctx::ShuffleBuckets& B = c->shb;
     c->last_kernel_flags = 0;
     int fastq = 0;
     const int64_t seed = c->opts.i("Seed");
+    // the draws of the bucket, both inclusive: those whose upper bits are the bins [lo, hi)
+    const uint64_t lo = (uint64_t)B.lo << SHUFFLE_BIN_SHIFT, hi = B.hi >= BUCKET_BINS ? ~0ull : ((uint64_t)B.hi << SHUFFLE_BIN_SHIFT) - 1;
     BucketAccumulate S{c, &B, d_buf, st, "shuffle", false};
     S.pick = [&](size_t n_eff, int fastq_eff, uint32_t* out_len, uint32_t* keep) -> int {
         Timed tm(c, "k_shuffle_pick", st);
-        HIP_TRYX(c, launch_sample_size(d_buf, n_eff, c->table, SampleParams{fastq_eff, first_record, seed, B.lo, B.hi}, out_len, keep, c->d_status, st));
+        HIP_TRYX(c, launch_sample_size(d_buf, n_eff, c->table, SampleParams{fastq_eff, first_record, seed, lo, hi}, out_len, keep, c->d_status, st));
         return BSK_OK;
     };
     S.append = [&](uint64_t N, const uint64_t* keep_off, uint64_t n0, uint64_t bytes0) {
@@ -271,25 +309,21 @@ static int shuffle_bucket_add_open(bsk_ctx* c, const uint8_t* d_buf, size_t n, i
 }
 
 int shuffle_bucket_add(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st) {
-    if (!c->shb.open) {
-        c->set_error("libbsk: bsk_shuffle_bucket_add: no bucket is open (bsk_shuffle_bucket_begin first)");
-        return BSK_ERR_INVALID_ARG;
-    }
-    const int rc = shuffle_bucket_add_open(c, d_buf, n, format, first_record, st);
-    if (rc != BSK_OK) shuffle_bucket_close(c);
+    int rc = bucket_require_open(c, c->shb, "shuffle", "add");
+    if (rc != BSK_OK) return rc;
+    rc = shuffle_bucket_add_open(c, d_buf, n, format, first_record, st);
+    if (rc != BSK_OK) bucket_close(&c->shb);
     return rc;
 }
 
 int shuffle_bucket_finish(bsk_ctx* c, hipStream_t st, bsk_out* out) {
-    if (!c->shb.open) {
-        c->set_error("libbsk: bsk_shuffle_bucket_finish: no bucket is open (bsk_shuffle_bucket_begin first)");
-        return BSK_ERR_INVALID_ARG;
-    }
+    int rc = bucket_require_open(c, c->shb, "shuffle", "finish");
+    if (rc != BSK_OK) return rc;
     const bsk_ctx::ShuffleBuckets& B = c->shb;
     // the bytes of the bucket are the sum of what its shards added, whatever the order: nothing is read back for them
-    const int rc = shuffle_order_emit(c, ShuffleRecords{B.d_acc, B.acc_used, B.d_off, B.d_len, B.n, B.total, B.d_draw, false, nullptr,
+    rc = shuffle_order_emit(c, ShuffleRecords{B.d_acc, B.acc_used, B.d_off, B.d_len, B.n, B.total, B.d_draw, false, nullptr,
                                                         "shuffle_bucket_sort", nullptr, "shuffle_bucket_copy"}, st, out);
-    shuffle_bucket_close(c);
+    bucket_close(&c->shb);
     return rc;
 }
 

@@ -36,7 +36,7 @@ static int cmp_padded(const uint8_t* a, size_t la, const uint8_t* b, size_t lb) 
 // plain one of byte strings.
 std::vector<std::string> sort_pick_splitters(std::vector<std::string> keys, uint32_t max_bins) {
     std::vector<std::string> out;
-    const uint32_t bins = std::min<uint32_t>(std::max<uint32_t>(max_bins, 1), SORT_BINS);
+    const uint32_t bins = std::min<uint32_t>(std::max<uint32_t>(max_bins, 1), BUCKET_BINS);
     if (keys.empty() || bins < 2) return out;
     for (std::string& k : keys) while (!k.empty() && k.back() == '\0') k.pop_back();
     std::sort(keys.begin(), keys.end());
@@ -48,27 +48,15 @@ std::vector<std::string> sort_pick_splitters(std::vector<std::string> keys, uint
     return out;
 }
 
-static int sort_hist_alloc(bsk_ctx* c, hipStream_t st) {
-    if (c->sob.d_hist) return BSK_OK;
-    HIP_TRYX(c, hipMalloc((void**)&c->sob.d_hist, 2 * SORT_BINS * sizeof(uint64_t)));
-    HIP_TRYX(c, hipMemsetAsync(c->sob.d_hist, 0, 2 * SORT_BINS * sizeof(uint64_t), st));
-    return BSK_OK;
-}
-
-// ---- what every pass does first: the table of the shard, the complaints of the index pass (read BEFORE any kernel walks the
-// table: a shard that is wrapped behind its head goes to the multi-line reader, run_multiline), the text view and the -N keys
+// ---- what every pass does first: the table of the shard and the complaints of the index pass (index_shard_status), the text
+// view and the -N keys
 struct SortShard {
     TextTableH tt;
     SortParams P;
     SortNatKeys nat;
 };
 static int sort_index_shard(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, SortShard* S) {
-    int rc = build_index(c, d_buf, n, format, st);
-    if (rc != BSK_OK) return rc;
-    uint64_t status = 0;
-    HIP_TRYX(c, hipMemcpyAsync(&status, c->d_status, sizeof status, hipMemcpyDeviceToHost, st));
-    HIP_TRYX(c, hipStreamSynchronize(st));
-    rc = kernel_error_to_status(c, status);
+    int rc = index_shard_status(c, d_buf, n, format, st);
     if (rc != BSK_OK || c->table.n == 0) return rc;
     rc = prepare_text(c, d_buf, format, st, &S->tt);
     if (rc != BSK_OK) return rc;
@@ -228,7 +216,7 @@ int sort_splitters_build(bsk_ctx* c, uint32_t max_bins, uint32_t* n_bins) {
 // ---- the histogram pass
 int sort_hist_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, uint64_t* n_records) {
     c->last_kernel_flags = 0;
-    int rc = sort_hist_alloc(c, st);
+    int rc = bucket_hist_alloc(c, &c->sob, st);
     if (rc != BSK_OK) return rc;
     SortShard S;
     rc = sort_index_shard(c, d_buf, n, format, st, &S);  // (the counters accumulate: the complaints of the index pass come first)
@@ -248,77 +236,30 @@ int sort_hist_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hip
         HIP_TRYX(c, launch_sort_bins(K, c->table, splitters_of(c), A.at<uint16_t>(o_bins), st));
     }
     Timed tm(c, "k_sort_hist", st);
-    HIP_TRYX(c, launch_sort_hist(d_buf, n, c->table, S.P.fastq, A.at<uint16_t>(o_bins), c->sob.d_hist, c->sob.d_hist + SORT_BINS, c->num_cus, st));
-    return BSK_OK;
-}
-
-int sort_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) {
-    int rc = sort_hist_alloc(c, nullptr);
-    if (rc != BSK_OK) return rc;
-    HIP_TRYX(c, hipDeviceSynchronize());
-    if (bytes) HIP_TRYX(c, hipMemcpy(bytes, c->sob.d_hist, SORT_BINS * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (records) HIP_TRYX(c, hipMemcpy(records, c->sob.d_hist + SORT_BINS, SORT_BINS * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    return BSK_OK;
-}
-
-int sort_hist_reset(bsk_ctx* c) {
-    HIP_TRYX(c, hipDeviceSynchronize());
-    if (c->sob.d_hist) HIP_TRYX(c, hipMemset(c->sob.d_hist, 0, 2 * SORT_BINS * sizeof(uint64_t)));
+    HIP_TRYX(c, launch_sort_hist(d_buf, n, c->table, S.P.fastq, A.at<uint16_t>(o_bins), c->sob.d_hist, c->sob.d_hist + BUCKET_BINS, c->num_cus, st));
     return BSK_OK;
 }
 
 // ---- one bucket
-static void sort_bucket_close(bsk_ctx* c) {
-    c->sob.open = false;
-    bucket_acc_clear(&c->sob);
-}
-
 int sort_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin) {
-    bsk_ctx::SortBuckets& B = c->sob;
-    if (B.open) {
-        c->set_error("libbsk: bsk_sort_bucket_begin: a bucket is open (bsk_sort_bucket_finish ends it)");
-        return BSK_ERR_INVALID_ARG;
-    }
-    B.lo = lo_bin;
-    B.hi = hi_bin;
-    B.next_first = 0;
-    B.format = -1;
-    bucket_acc_clear(&B);
-    if (B.d_hist) {
-        // the histogram of this context says what the bucket will hold: the accumulation is allocated once
-        std::vector<uint64_t> h(2 * SORT_BINS);
-        HIP_TRYX(c, hipDeviceSynchronize());
-        HIP_TRYX(c, hipMemcpy(h.data(), B.d_hist, h.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        uint64_t bytes = 0, recs = 0;
-        for (uint32_t b = lo_bin; b < hi_bin; ++b) { bytes += h[b]; recs += h[SORT_BINS + b]; }
-        if (recs >= (1ull << 32)) {
-            c->set_error("libbsk: sort: 2^32 or more records in one bucket are not supported (a smaller budget makes more buckets)");
-            return BSK_ERR_UNSUPPORTED;
-        }
-        if (recs) {
-            const int rc = bucket_acc_reserve(c, &B, bytes, 0, false, nullptr);
-            if (rc != BSK_OK) return rc;
-        }
-    }
-    B.open = true;
-    return BSK_OK;
+    const int rc = bucket_begin(c, &c->sob, "sort", lo_bin, hi_bin,
+                                [&](uint64_t bytes, uint64_t) { return bucket_acc_reserve(c, &c->sob, bytes, 0, false, nullptr); });
+    if (rc == BSK_OK) c->sob.format = -1;
+    return rc;
 }
 
 static int sort_bucket_add_open(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st) {
     bsk_ctx::SortBuckets& B = c->sob;
     c->last_kernel_flags = 0;
     // ties keep file order because the accumulation receives its records in input order
-    if (first_record < B.next_first) {
-        c->set_error("libbsk: bsk_sort_bucket_add: first_record " + std::to_string(first_record) + " goes backwards (the shards of a bucket are "
-                     "added in input order; the next one starts at record " + std::to_string(B.next_first) + " or later)");
-        return BSK_ERR_INVALID_ARG;
-    }
+    int rc = bucket_in_order(c, B, "sort", first_record);
+    if (rc != BSK_OK) return rc;
     if (B.format >= 0 && B.format != format) {
         c->set_error("libbsk: bsk_sort_bucket_add: the shards of a bucket have one format");
         return BSK_ERR_INVALID_ARG;
     }
     SortShard S;
-    int rc = sort_index_shard(c, d_buf, n, format, st, &S);
+    rc = sort_index_shard(c, d_buf, n, format, st, &S);
     if (rc != BSK_OK) return rc;
     const uint64_t N = c->table.n;
     if (N == 0) return BSK_OK;
@@ -352,24 +293,17 @@ static int sort_bucket_add_open(bsk_ctx* c, const uint8_t* d_buf, size_t n, int 
 }
 
 int sort_bucket_add(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st) {
-    if (!c->sob.open) {
-        c->set_error("libbsk: bsk_sort_bucket_add: no bucket is open (bsk_sort_bucket_begin first)");
-        return BSK_ERR_INVALID_ARG;
-    }
+    const int rc = bucket_require_open(c, c->sob, "sort", "add");
+    if (rc != BSK_OK) return rc;
     // (no close on an error here: a wrapped FASTQ shard comes back once more as its 4-line rewrite -- run_multiline -- and needs
-    // the bucket; the entry point closes it when the call has failed for good, sort_bucket_abort)
+    // the bucket; the entry point closes it when the call has failed for good, bucket_close.  rmdup_bucket_add does the same)
     return sort_bucket_add_open(c, d_buf, n, format, first_record, st);
 }
 
-void sort_bucket_abort(bsk_ctx* c) { sort_bucket_close(c); }
-
 int sort_bucket_finish(bsk_ctx* c, hipStream_t st, bsk_out* out) {
     bsk_ctx::SortBuckets& B = c->sob;
-    if (!B.open) {
-        c->set_error("libbsk: bsk_sort_bucket_finish: no bucket is open (bsk_sort_bucket_begin first)");
-        return BSK_ERR_INVALID_ARG;
-    }
-    int rc = BSK_OK;
+    int rc = bucket_require_open(c, B, "sort", "finish");
+    if (rc != BSK_OK) return rc;
     if (B.n == 0) {
         rc = empty_result(c, out);
     } else {
@@ -377,7 +311,7 @@ int sort_bucket_finish(bsk_ctx* c, hipStream_t st, bsk_out* out) {
         Timed tm(c, "sort_bucket_sort", st);
         rc = sort_run_device(c, B.d_acc, B.acc_used, B.format, st, out);
     }
-    sort_bucket_close(c);
+    bucket_close(&B);
     return rc;
 }
 

@@ -14,29 +14,13 @@ namespace {
 constexpr uint32_t PACK_LANES = 8;        // lanes per record of the pack and of the comparison
 constexpr uint32_t PACK_STEP = 16u * PACK_LANES;
 
-// bytes (subject + RMDUP_BUCKET_RECORD_BYTES) and records per fine bin, privatised per block: 4096 x (u64 + u32) = 48 KiB of
-// LDS, merged with one global atomic per counter and non-empty bin; a block walks many records (grid-stride).  The shape of
-// k_shuffle_hist and k_sort_hist.
+// bytes (subject + RMDUP_BUCKET_RECORD_BYTES) and records per fine bin (bucket_hist_dev.hpp); the bin is the upper 12 bits of k1
 __global__ __launch_bounds__(256) void k_rdb_hist(const uint8_t* __restrict__ buf, RecordTable t, TextTable tt, RmDupParams P,
                                                   const uint64_t* __restrict__ keys, unsigned long long* __restrict__ g_bytes,
                                                   unsigned long long* __restrict__ g_records) {
-    __shared__ unsigned long long s_bytes[RMDUP_BINS];
-    __shared__ uint32_t s_records[RMDUP_BINS];
-    for (uint32_t b = threadIdx.x; b < RMDUP_BINS; b += blockDim.x) { s_bytes[b] = 0; s_records[b] = 0; }
-    __syncthreads();
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < t.n; i += stride) {
-        const uint32_t bin = (uint32_t)(keys[i] >> RMDUP_BIN_SHIFT);
-        atomicAdd(&s_bytes[bin], (unsigned long long)subject_of(buf, t, tt, P, i).len + RMDUP_BUCKET_RECORD_BYTES);
-        atomicAdd(&s_records[bin], 1u);
-    }
-    __syncthreads();
-    for (uint32_t b = threadIdx.x; b < RMDUP_BINS; b += blockDim.x) {
-        const uint32_t r = s_records[b];
-        if (r == 0) continue;
-        atomicAdd(&g_bytes[b], s_bytes[b]);
-        atomicAdd(&g_records[b], (unsigned long long)r);
-    }
+    bucket_hist(t.n, g_bytes, g_records, [&](uint64_t i) {
+        return BinBytes{(uint32_t)(keys[i] >> RMDUP_BIN_SHIFT), (unsigned long long)subject_of(buf, t, tt, P, i).len + RMDUP_BUCKET_RECORD_BYTES};
+    });
 }
 
 __global__ __launch_bounds__(256) void k_rdb_pick(const uint8_t* __restrict__ buf, RecordTable t, TextTable tt, RmDupParams P,
@@ -197,9 +181,7 @@ inline TextTable dev_tt(const TextTableH& tt) { return TextTable{tt.text_w, tt.l
 hipError_t launch_rdb_hist(const uint8_t* buf, const RecordTable& t, const TextTableH& tt, const RmDupParams& P, const uint64_t* keys,
                            uint64_t* bytes, uint64_t* records, int num_cus, hipStream_t st) {
     if (t.n == 0) return hipSuccess;
-    // three blocks of 48 KiB fit the LDS of a CU
-    const uint64_t blocks = std::min<uint64_t>((t.n + 255) / 256, (uint64_t)std::max(1, num_cus) * 3);
-    hipLaunchKernelGGL(k_rdb_hist, dim3((unsigned)blocks), dim3(256), 0, st, buf, t, dev_tt(tt), P, keys, (unsigned long long*)bytes,
+    hipLaunchKernelGGL(k_rdb_hist, dim3(bucket_hist_blocks(t.n, num_cus)), dim3(256), 0, st, buf, t, dev_tt(tt), P, keys, (unsigned long long*)bytes,
                        (unsigned long long*)records);
     return hipGetLastError();
 }

@@ -9,13 +9,13 @@
 #include <cstdint>
 
 #include "../../include/bsk.h"
+#include "bucket_hist_dev.hpp"
 #include "index.hpp"
 #include "ops_rmdup.hpp"
 #include "ops_translate.hpp"  // TextTableH
 
 namespace bsk {
 
-constexpr uint32_t RMDUP_BINS = 4096;  // the counters of the histogram (== SHUFFLE_BINS: bsk_shuffle_plan is the plan)
 constexpr uint32_t RMDUP_BIN_SHIFT = 52;
 // what a record costs the accumulation next to its subject bytes: k1 (8), global index (8), offset (8), length (4), rounded
 // up to a multiple of 8
@@ -23,8 +23,8 @@ constexpr uint64_t RMDUP_BUCKET_RECORD_BYTES = BSK_RMDUP_BUCKET_RECORD_BYTES;  /
 // a subject of at least this many bytes is packed by a block of its own (launch_find_long on the pick's lengths)
 constexpr uint32_t RMDUP_PACK_LONG = 1u << 16;
 
-// subject bytes + RMDUP_BUCKET_RECORD_BYTES and records per fine bin (bin = keys[i] >> 52), added to bytes[RMDUP_BINS] /
-// records[RMDUP_BINS]
+// subject bytes + RMDUP_BUCKET_RECORD_BYTES and records per fine bin (bin = keys[i] >> 52), added to bytes[BUCKET_BINS] /
+// records[BUCKET_BINS]
 hipError_t launch_rdb_hist(const uint8_t* buf, const RecordTable& t, const TextTableH& tt, const RmDupParams& P, const uint64_t* keys,
                            uint64_t* bytes, uint64_t* records, int num_cus, hipStream_t st);
 // the pick of a bucket: sub_len[i] = bytes of the subject of record i when lo <= bin < hi, else 0; keep[i] = 1 / 0 (an empty

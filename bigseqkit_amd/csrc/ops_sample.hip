@@ -74,32 +74,16 @@ __global__ __launch_bounds__(256) void k_shuffle_fix(uint64_t n, const uint8_t* 
     o[m - 1] = (uint8_t)'\n';
 }
 
-// ---- shuffle in buckets of the draw (PARITY.md SHUF): the 64-bit draw range is cut into SHUFFLE_BINS fine bins, a bucket is a run
+// ---- shuffle in buckets of the draw (PARITY.md SHUF): the 64-bit draw range is cut into BUCKET_BINS fine bins, a bucket is a run
 // of consecutive bins, the output is bucket 0 sorted by draw, then bucket 1, ...
 
-// bytes (text + '\n') and records per fine bin, privatised per block: 4096 x (u64 + u32) = 48 KiB of LDS, merged with one
-// global atomic per counter and non-empty bin.  A block walks many records (grid-stride) so that the zeroing and the merge
-// of its 48 KiB are paid once.
+// bytes (text + '\n') and records per fine bin (bucket_hist_dev.hpp); the bin is the upper 12 bits of the draw
 __global__ __launch_bounds__(256) void k_shuffle_hist(const uint8_t* __restrict__ buf, uint64_t buf_n, RecordTable t, int fastq,
                                                       uint64_t first_record, uint64_t key, unsigned long long* __restrict__ g_bytes,
                                                       unsigned long long* __restrict__ g_records) {
-    __shared__ unsigned long long s_bytes[SHUFFLE_BINS];
-    __shared__ uint32_t s_records[SHUFFLE_BINS];
-    for (uint32_t b = threadIdx.x; b < SHUFFLE_BINS; b += blockDim.x) { s_bytes[b] = 0; s_records[b] = 0; }
-    __syncthreads();
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < t.n; i += stride) {
-        const uint32_t bin = (uint32_t)(sample_draw(key, first_record + i) >> SHUFFLE_BIN_SHIFT);
-        atomicAdd(&s_bytes[bin], (unsigned long long)(record_text_len(buf, buf_n, t, fastq, i) + 1u));
-        atomicAdd(&s_records[bin], 1u);
-    }
-    __syncthreads();
-    for (uint32_t b = threadIdx.x; b < SHUFFLE_BINS; b += blockDim.x) {
-        const uint32_t r = s_records[b];
-        if (r == 0) continue;
-        atomicAdd(&g_bytes[b], s_bytes[b]);
-        atomicAdd(&g_records[b], (unsigned long long)r);
-    }
+    bucket_hist(t.n, g_bytes, g_records, [&](uint64_t i) {
+        return BinBytes{(uint32_t)(sample_draw(key, first_record + i) >> SHUFFLE_BIN_SHIFT), record_text_len(buf, buf_n, t, fastq, i) + 1u};
+    });
 }
 
 // the kept records of the shard join the accumulation, in shard order: (draw, byte offset, length) at n0 + keep_off[i]
@@ -159,9 +143,7 @@ hipError_t launch_shuffle_fix(uint64_t n, const uint8_t* base, const uint64_t* o
 hipError_t launch_shuffle_hist(const uint8_t* buf, uint64_t buf_n, const RecordTable& t, int fastq, uint64_t first_record, int64_t seed,
                                uint64_t* bytes, uint64_t* records, int num_cus, hipStream_t st) {
     if (t.n == 0) return hipSuccess;
-    // three blocks of 48 KiB fit the LDS of a CU
-    const uint64_t blocks = std::min<uint64_t>((t.n + 255) / 256, (uint64_t)std::max(1, num_cus) * 3);
-    hipLaunchKernelGGL(k_shuffle_hist, dim3((unsigned)blocks), dim3(256), 0, st, buf, buf_n, t, fastq, first_record, sample_key(seed),
+    hipLaunchKernelGGL(k_shuffle_hist, dim3(bucket_hist_blocks(t.n, num_cus)), dim3(256), 0, st, buf, buf_n, t, fastq, first_record, sample_key(seed),
                        (unsigned long long*)bytes, (unsigned long long*)records);
     return hipGetLastError();
 }

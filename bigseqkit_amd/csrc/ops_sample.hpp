@@ -6,6 +6,7 @@
 
 #include <cstdint>
 
+#include "bucket_hist_dev.hpp"
 #include "index.hpp"
 
 namespace bsk {
@@ -34,8 +35,7 @@ hipError_t launch_shuffle_segments(uint64_t n, const uint8_t* base, uint64_t ext
 hipError_t launch_shuffle_fix(uint64_t n, const uint8_t* base, const uint64_t* off, const uint32_t* perm, const uint32_t* len_perm,
                               const uint64_t* seg_off, const uint64_t* seg_src, uint8_t* out, bool all, hipStream_t st);
 
-// ---- shuffle in buckets of the draw: SHUFFLE_BINS fine bins = the upper 12 bits of the draw; a bucket is a run of bins
-constexpr uint32_t SHUFFLE_BINS = 4096;
+// ---- shuffle in buckets of the draw: BUCKET_BINS fine bins = the upper 12 bits of the draw; a bucket is a run of bins
 constexpr int SHUFFLE_BIN_SHIFT = 52;
 // bytes[bin] += text + '\n', records[bin] += 1 for every record of the table (bin of draw(seed, first_record + i)); the
 // counters accumulate over the calls

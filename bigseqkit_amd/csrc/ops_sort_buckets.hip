@@ -93,30 +93,15 @@ __global__ __launch_bounds__(256) void k_sort_bins(KeySourceDev S, RecordTable t
     bins[i] = (uint16_t)lo;
 }
 
-// bytes (text + '\n') and records per fine bin, privatised per block: 4096 x (u64 + u32) = 48 KiB of LDS, merged with one
-// global atomic per counter and non-empty bin; a block walks many records (grid-stride).  The shape of k_shuffle_hist, fed by
-// the array of k_sort_bins: the bucket passes need that kernel on its own, and a search fused in here would carry its
-// registers into a kernel whose occupancy the LDS already caps at three blocks per CU.
+// bytes (text + '\n') and records per fine bin (bucket_hist_dev.hpp), fed by the array of k_sort_bins: the bucket passes need
+// that kernel on its own, and a search fused in here would carry its registers into a kernel whose occupancy the LDS already
+// caps at three blocks per CU.
 __global__ __launch_bounds__(256) void k_sort_hist(const uint8_t* __restrict__ buf, uint64_t buf_n, RecordTable t, int fastq,
                                                    const uint16_t* __restrict__ bins, unsigned long long* __restrict__ g_bytes,
                                                    unsigned long long* __restrict__ g_records) {
-    __shared__ unsigned long long s_bytes[SORT_BINS];
-    __shared__ uint32_t s_records[SORT_BINS];
-    for (uint32_t b = threadIdx.x; b < SORT_BINS; b += blockDim.x) { s_bytes[b] = 0; s_records[b] = 0; }
-    __syncthreads();
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < t.n; i += stride) {
-        const uint32_t bin = bins[i] & (SORT_BINS - 1u);
-        atomicAdd(&s_bytes[bin], (unsigned long long)(record_text_len(buf, buf_n, t, fastq, i) + 1u));
-        atomicAdd(&s_records[bin], 1u);
-    }
-    __syncthreads();
-    for (uint32_t b = threadIdx.x; b < SORT_BINS; b += blockDim.x) {
-        const uint32_t r = s_records[b];
-        if (r == 0) continue;
-        atomicAdd(&g_bytes[b], s_bytes[b]);
-        atomicAdd(&g_records[b], (unsigned long long)r);
-    }
+    bucket_hist(t.n, g_bytes, g_records, [&](uint64_t i) {
+        return BinBytes{bins[i] & (BUCKET_BINS - 1u), record_text_len(buf, buf_n, t, fastq, i) + 1u};
+    });
 }
 
 __global__ __launch_bounds__(256) void k_sort_pick(const uint8_t* __restrict__ buf, uint64_t buf_n, RecordTable t, int fastq,
@@ -176,9 +161,7 @@ hipError_t launch_sort_bins(const SortKeySource& S, const RecordTable& t, const 
 hipError_t launch_sort_hist(const uint8_t* buf, uint64_t buf_n, const RecordTable& t, int fastq, const uint16_t* bins, uint64_t* bytes,
                             uint64_t* records, int num_cus, hipStream_t st) {
     if (t.n == 0) return hipSuccess;
-    // three blocks of 48 KiB fit the LDS of a CU
-    const uint64_t blocks = std::min<uint64_t>((t.n + 255) / 256, (uint64_t)std::max(1, num_cus) * 3);
-    hipLaunchKernelGGL(k_sort_hist, dim3((unsigned)blocks), dim3(256), 0, st, buf, buf_n, t, fastq, bins, (unsigned long long*)bytes,
+    hipLaunchKernelGGL(k_sort_hist, dim3(bucket_hist_blocks(t.n, num_cus)), dim3(256), 0, st, buf, buf_n, t, fastq, bins, (unsigned long long*)bytes,
                        (unsigned long long*)records);
     return hipGetLastError();
 }

@@ -6,14 +6,14 @@
 
 #include <cstdint>
 
+#include "bucket_hist_dev.hpp"
 #include "index.hpp"
 #include "ops_sort.hpp"
 #include "ops_translate.hpp"  // TextTableH
 
 namespace bsk {
 
-constexpr uint32_t SORT_BINS = 4096;               // the counters of the histogram (== SHUFFLE_BINS: bsk_shuffle_plan is the plan)
-constexpr uint32_t SORT_MAX_SPLITTERS = SORT_BINS - 1;
+constexpr uint32_t SORT_MAX_SPLITTERS = BUCKET_BINS - 1;  // (bucket_hist_dev.hpp: the counters of the histogram)
 constexpr uint32_t SORT_SAMPLE_KEY_BYTES = 256;    // a sample key is cut here: a truncated key is still a valid splitter
 constexpr int64_t SORT_SAMPLE_SEED = 0x534F5254;   // the fixed key of the sample's draw (sample_dev.hpp)
 
@@ -44,7 +44,7 @@ hipError_t launch_sort_sample_emit(const SortKeySource& S, const RecordTable& t,
                                    uint32_t* lens, hipStream_t st);
 // bins[i] = number of splitters <= key of record i
 hipError_t launch_sort_bins(const SortKeySource& S, const RecordTable& t, const SortSplitters& sp, uint16_t* bins, hipStream_t st);
-// bytes (text + '\n') and records per fine bin, added to bytes[SORT_BINS] / records[SORT_BINS]
+// bytes (text + '\n') and records per fine bin, added to bytes[BUCKET_BINS] / records[BUCKET_BINS]
 hipError_t launch_sort_hist(const uint8_t* buf, uint64_t buf_n, const RecordTable& t, int fastq, const uint16_t* bins, uint64_t* bytes,
                             uint64_t* records, int num_cus, hipStream_t st);
 // the pick of a bucket: out_len[i] = text + '\n' of record i when lo <= bins[i] < hi, else 0; keep[i] = 1 / 0

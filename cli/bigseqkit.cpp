@@ -1041,6 +1041,7 @@ Output run_buckets(const Invocation& inv) {
     const bool sort = use == "sort", rmdup = use == "rmdup";
     const int device = (int)strtol(inv.pget("device").c_str(), nullptr, 10);
     const uint64_t budget = bucket_budget(use);
+    constexpr uint32_t kBins = 4096;  // the fine bins of all three (include/bsk.h)
     Output res;
     bsk_ctx* ctx = nullptr;
     if (bsk_create(inv.cmd->op, inv.js.c_str(), device, &ctx) != BSK_OK) die(bsk_global_error());
@@ -1088,6 +1089,17 @@ Output run_buckets(const Invocation& inv) {
         }
     }
     res.fmt = fmt < 0 ? BSK_FORMAT_FASTA : fmt;
+    // the entry points of the passes that the three commands share, and what their timing marks say
+    struct Entry {
+        decltype(&bsk_shuffle_hist_run) hist_run;
+        decltype(&bsk_shuffle_hist_get) hist_get;
+        decltype(&bsk_shuffle_bucket_begin) bucket_begin;
+        decltype(&bsk_shuffle_bucket_add) bucket_add;
+        const char *mark_hist, *mark_buckets;
+    };
+    const Entry E = sort    ? Entry{bsk_sort_hist_run, bsk_sort_hist_get, bsk_sort_bucket_begin, bsk_sort_bucket_add, "sort: histogram of the bins", "sort: buckets"}
+                    : rmdup ? Entry{bsk_rmdup_hist_run, bsk_rmdup_hist_get, bsk_rmdup_bucket_begin, bsk_rmdup_bucket_add, "rmdup: histogram of the bins", "rmdup: buckets"}
+                            : Entry{bsk_shuffle_hist_run, bsk_shuffle_hist_get, bsk_shuffle_bucket_begin, bsk_shuffle_bucket_add, "shuffle: histogram of the draws", "shuffle: buckets"};
     // the pass over all pieces that counts the records: it leaves every piece's first record index
     uint64_t last_count = 0;  // the records of the last piece
     auto count_pass = [&](auto&& call) {
@@ -1101,39 +1113,38 @@ Output run_buckets(const Invocation& inv) {
             last_count = cnt;
         }
     };
+    // bucket [lo, hi) of the plan opened and every piece added to it, in input order
+    auto fill_bucket = [&](uint32_t lo, uint32_t hi) {
+        if (E.bucket_begin(ctx, lo, hi) != BSK_OK) die(bsk_last_error(ctx));
+        int64_t k = 0;
+        for (auto& pc : pieces)
+            if (E.bucket_add(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr) != BSK_OK) die(bsk_last_error(ctx));
+    };
+    auto append_out = [&](const bsk_out& out) {
+        const size_t at = res.text.size();
+        res.text.resize(at + out.len);
+        if (out.len && bsk_out_to_host(ctx, &out, &res.text[at], out.len) != BSK_OK) die(bsk_last_error(ctx));
+    };
     if (sort) {
         double rate = 1.0;
         if (!pieces.empty()) {
             uint64_t cnt = 0;
             if (bsk_index_build(ctx, pieces[0].p, pieces[0].n, 0, res.fmt, nullptr, &cnt) != BSK_OK) die(bsk_last_error(ctx));
             const double records = (double)total_bytes * (double)cnt / (double)std::max<size_t>(pieces[0].n, 1);
-            rate = std::min(1.0, 32.0 * 4096.0 / std::max(records, 1.0));
+            rate = std::min(1.0, 32.0 * (double)kBins / std::max(records, 1.0));
         }
         count_pass([&](const Piece& pc, int64_t k, uint64_t g, uint64_t* cnt) {
             return bsk_sort_sample_run(ctx, pc.p, pc.n, 0, res.fmt, k, g, rate, nullptr, cnt);
         });
         uint32_t n_bins = 0;
-        if (bsk_sort_splitters_build(ctx, 4096, &n_bins) != BSK_OK) die(bsk_last_error(ctx));
+        if (bsk_sort_splitters_build(ctx, kBins, &n_bins) != BSK_OK) die(bsk_last_error(ctx));
         mark("sort: sample of the keys, splitters");
-        count_pass([&](const Piece& pc, int64_t k, uint64_t g, uint64_t* cnt) {
-            return bsk_sort_hist_run(ctx, pc.p, pc.n, 0, res.fmt, k, g, nullptr, cnt);
-        });
-        mark("sort: histogram of the bins");
-    } else if (rmdup) {
-        count_pass([&](const Piece& pc, int64_t k, uint64_t g, uint64_t* cnt) {
-            return bsk_rmdup_hist_run(ctx, pc.p, pc.n, 0, res.fmt, k, g, nullptr, cnt);
-        });
-        mark("rmdup: histogram of the bins");
-    } else {
-        count_pass([&](const Piece& pc, int64_t k, uint64_t g, uint64_t* cnt) {
-            return bsk_shuffle_hist_run(ctx, pc.p, pc.n, 0, res.fmt, k, g, nullptr, cnt);
-        });
-        mark("shuffle: histogram of the draws");
     }
-    std::vector<uint64_t> hist(4096), bounds(4097);
+    count_pass([&](const Piece& pc, int64_t k, uint64_t g, uint64_t* cnt) { return E.hist_run(ctx, pc.p, pc.n, 0, res.fmt, k, g, nullptr, cnt); });
+    mark(E.mark_hist);
+    std::vector<uint64_t> hist(kBins), bounds(kBins + 1);
     int n_buckets = 0;
-    if ((sort ? bsk_sort_hist_get(ctx, hist.data(), nullptr) : rmdup ? bsk_rmdup_hist_get(ctx, hist.data(), nullptr)
-              : bsk_shuffle_hist_get(ctx, hist.data(), nullptr)) != BSK_OK) die(bsk_last_error(ctx));
+    if (E.hist_get(ctx, hist.data(), nullptr) != BSK_OK) die(bsk_last_error(ctx));
     if (bsk_shuffle_plan(hist.data(), budget, bounds.data(), &n_buckets) != BSK_OK) {
         std::string msg = bsk_global_error();
         if (sort) msg += " -- sort: a fine bin holds the records between two splitter keys; many equal keys, or a run that the sample missed, fill one";
@@ -1146,45 +1157,32 @@ Output run_buckets(const Invocation& inv) {
         const uint64_t total_records = pieces.empty() ? 0 : pieces.back().first + last_count;
         if (bsk_rmdup_verdict_begin(ctx, total_records) != BSK_OK) die(bsk_last_error(ctx));
         for (int b = 0; b < n_buckets; ++b) {
-            if (bsk_rmdup_bucket_begin(ctx, (uint32_t)bounds[b], (uint32_t)bounds[b + 1]) != BSK_OK) die(bsk_last_error(ctx));
-            int64_t k = 0;
-            for (auto& pc : pieces)
-                if (bsk_rmdup_bucket_add(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr) != BSK_OK) die(bsk_last_error(ctx));
+            fill_bucket((uint32_t)bounds[b], (uint32_t)bounds[b + 1]);
             uint64_t r = 0, f = 0;
             if (bsk_rmdup_bucket_finish(ctx, nullptr, &r, &f) != BSK_OK) die(bsk_last_error(ctx));
             removed += r;
             flagged += f;
         }
-        mark("rmdup: buckets");
+        mark(E.mark_buckets);
         int64_t k = 0;
         for (auto& pc : pieces) {
             bsk_out out;
             if (bsk_rmdup_emit_run(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr, &out) != BSK_OK) die(bsk_last_error(ctx));
-            const size_t at = res.text.size();
-            res.text.resize(at + out.len);
-            if (out.len && bsk_out_to_host(ctx, &out, &res.text[at], out.len) != BSK_OK) die(bsk_last_error(ctx));
+            append_out(out);
         }
         mark("rmdup: emit");
-    }
-    const bool backwards = sort && inv.pget("reverse") == "true";
-    for (int i = 0; i < n_buckets && !rmdup; ++i) {  // (rmdup's buckets are done: they print nothing)
-        const int b = backwards ? n_buckets - 1 - i : i;
-        const uint32_t lo = (uint32_t)bounds[b], hi = (uint32_t)bounds[b + 1];
-        if ((sort ? bsk_sort_bucket_begin(ctx, lo, hi) : bsk_shuffle_bucket_begin(ctx, lo, hi)) != BSK_OK) die(bsk_last_error(ctx));
-        int64_t k = 0;
-        for (auto& pc : pieces) {
-            const int rc = sort ? bsk_sort_bucket_add(ctx, pc.p, pc.n, 0, res.fmt, k, pc.first, nullptr)
-                                : bsk_shuffle_bucket_add(ctx, pc.p, pc.n, 0, res.fmt, k, pc.first, nullptr);
-            ++k;
-            if (rc != BSK_OK) die(bsk_last_error(ctx));
+    } else {
+        // every finished bucket is appended to the output; sort -r: from the last to the first
+        const bool backwards = sort && inv.pget("reverse") == "true";
+        for (int i = 0; i < n_buckets; ++i) {
+            const int b = backwards ? n_buckets - 1 - i : i;
+            fill_bucket((uint32_t)bounds[b], (uint32_t)bounds[b + 1]);
+            bsk_out out;
+            if ((sort ? bsk_sort_bucket_finish(ctx, nullptr, &out) : bsk_shuffle_bucket_finish(ctx, nullptr, &out)) != BSK_OK) die(bsk_last_error(ctx));
+            append_out(out);
         }
-        bsk_out out;
-        if ((sort ? bsk_sort_bucket_finish(ctx, nullptr, &out) : bsk_shuffle_bucket_finish(ctx, nullptr, &out)) != BSK_OK) die(bsk_last_error(ctx));
-        const size_t at = res.text.size();
-        res.text.resize(at + out.len);
-        if (out.len && bsk_out_to_host(ctx, &out, &res.text[at], out.len) != BSK_OK) die(bsk_last_error(ctx));
+        mark(E.mark_buckets);
     }
-    if (!rmdup) mark(sort ? "sort: buckets" : "shuffle: buckets");
     if (timing) {
         std::vector<char> buf(1 << 16);
         if (bsk_profile_dump(ctx, buf.data(), buf.size()) == BSK_OK)

@@ -134,7 +134,10 @@ def test_verdict_bits(n):
 
 
 # ------------------------------------------------------------------ more records than the grid stride of the histogram
-def test_counts_past_the_grid_of_the_histogram():
+@pytest.mark.parametrize("parts", [1, 3])
+def test_counts_past_the_grid_of_the_histogram(parts):
+    """one shard: a launch with more records than the lanes of the histogram's grid, so its loop takes a second stride; three
+    shards: every launch stays below the grid, the counters add up over the launches"""
     import torch
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     n = 3 * cus * 256 + 1234
@@ -142,7 +145,7 @@ def test_counts_past_the_grid_of_the_histogram():
     data = b"".join(b">%x\nA\n" % i for i in ids)
     subs = [b"%x" % i for i in ids]
     hb, hr = R.py_hist(subs)
-    got, nb, removed, flagged, bits, hist = run(frame(data, False, 3), {}, sum(hb) // 4 + 1)
+    got, nb, removed, flagged, bits, hist = run(frame(data, False, parts), {}, sum(hb) // 4 + 1)
     assert hist == (hb, hr) and sum(hist[1]) == n
     assert nb >= 4 and removed == 5000 and flagged == 0
     assert bits == R.py_verdict(subs)

@@ -379,9 +379,10 @@ def test_a_shard_of_one_record_between_two_larger_ones():
         assert got == oracle.sort(data, True, json.dumps(o)) and nb >= 3, (o, nb)
 
 
-def test_past_the_grid_stride_of_the_histogram():
+@pytest.mark.parametrize("parts", [1, 3])
+def test_past_the_grid_stride_of_the_histogram(parts):
     """more records than the lanes of the histogram's grid (three blocks per CU), few bytes each; the last record has no newline
-    and lands inside the output"""
+    and lands inside the output.  One shard: a launch takes a second stride of the grid; three: every launch stays below it"""
     import torch
     n = 3 * torch.cuda.get_device_properties(0).multi_processor_count * 256 + 77
     ids = list(range(n))
@@ -394,7 +395,7 @@ def test_past_the_grid_stride_of_the_histogram():
     keys = [r[1] for r in recs]
     sp = bsk.SortPickSplitters(py_sample(keys, rate=default_rate(n)))
     hb, hr = py_hist(recs, keys, sp)
-    f = frame(data, False, 3)
+    f = frame(data, False, parts)
     with bsk.Operator("Sort", "{}", 0) as op:
         buckets, counts = bsk.SortBucketsPlan(op, f, Opts({}), sum(hb) // 3 + max(hb))
         assert bsk.SortSplittersGet(op) == sp and bsk.SortHistGet(op) == (hb, hr)
