@@ -14,4 +14,5 @@ from .api import (SeqFrame, ReadFASTA, ReadFASTAN, ReadFASTQ, ReadFASTQN, Operat
                   Duplicate, Count, Rename, Sort, Faidx, Pair, Common, Concat, FaidxQuery, Replace, Fa2Fq, Sample, Shuffle, ShuffleBuckets, ShuffleHistRun, ShuffleHistGet, ShuffleHistReset, ShufflePlan, ShuffleBucket, HeadGenome,
                   SortBuckets, SortBucketsPlan, SortBucket, SortSampleRun, SortSampleReset, SortSampleCount, SortPickSplitters, SortSplittersBuild,
                   SortSplittersSet, SortSplittersGet, SortHistRun, SortHistGet, SortHistReset,
-                  RmDupBuckets, RmDupHistRun, RmDupHistGet, RmDupHistReset, RmDupVerdictBegin, RmDupVerdictGet, RmDupBucket, RmDupEmit)
+                  RmDupBuckets, RmDupHistRun, RmDupHistGet, RmDupHistReset, RmDupVerdictBegin, RmDupVerdictGet, RmDupBucket, RmDupEmit,
+                  RenameBuckets, RenameHistRun, RenameHistGet, RenameHistReset, RenameVerdictBegin, RenameVerdictGet, RenameBucket, RenameEmit)

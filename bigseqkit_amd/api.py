@@ -692,6 +692,67 @@ def RmDupBuckets(input, o=None, budget_bytes=1 << 30, device=0):
         return RmDupEmit(op, input, counts)
 
 
+def RenameHistRun(op, input):
+    """bsk_rename_hist_run over the shards of `input`, in order: the record count of every shard (the histogram accumulates
+    in the operator's context)"""
+    return _count_pass(lib.bsk_rename_hist_run, op, input)
+
+
+def RenameHistGet(op):
+    """bsk_rename_hist_get: (bytes[4096], records[4096])"""
+    return _hist_get(lib.bsk_rename_hist_get, op)
+
+
+def RenameHistReset(op):
+    check(lib.bsk_rename_hist_reset(op.ctx), op.ctx)
+
+
+def RenameVerdictBegin(op, total_records):
+    """bsk_rename_verdict_begin: zeroed ordinals for the records [0, total_records), no bin decided"""
+    check(lib.bsk_rename_verdict_begin(op.ctx, total_records), op.ctx)
+
+
+def RenameVerdictGet(op, first, count):
+    """bsk_rename_verdict_get: the ordinal of every record of [first, first + count) inside its group of equal subjects"""
+    buf = (C.c_uint32 * max(1, count))()
+    check(lib.bsk_rename_verdict_get(op.ctx, first, count, buf), op.ctx)
+    return list(buf[:count])
+
+
+def RenameBucket(op, input, counts, lo_bin, hi_bin):
+    """bsk_rename_bucket_begin / _add over the shards of `input`, in order / _finish: (renamed, flagged) of the bucket [lo_bin, hi_bin)"""
+    _bucket_adds(lib.bsk_rename_bucket_begin, lib.bsk_rename_bucket_add, op, input, counts, lo_bin, hi_bin)
+    renamed, flagged = C.c_uint64(), C.c_uint64()
+    check(lib.bsk_rename_bucket_finish(op.ctx, None, C.byref(renamed), C.byref(flagged)), op.ctx)
+    return renamed.value, flagged.value
+
+
+def RenameEmit(op, input, counts):
+    """bsk_rename_emit_run over the shards of `input`, in order: the records, renamed, joined"""
+    chunks, first = [], 0
+    for (pid, ptr, n, on_dev, keep), cnt in zip(input.partitions(), counts):
+        out = _lib.Out()
+        check(lib.bsk_rename_emit_run(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None, C.byref(out)), op.ctx)
+        chunks.append(_out_bytes(op, out))
+        first += cnt
+    return b"".join(chunks)
+
+
+def RenameBuckets(input, o=None, budget_bytes=1 << 30, device=0):
+    """Rename of an input of any size on one device (PARITY RENB): the histogram of the fine bins of the key over all shards, the
+    plan of buckets of at most `budget_bytes` of subjects, one collect sequence per bucket, which ends in the bucket's share of
+    the ordinals, and one emit pass; the same bytes as Rename.  The input is read twice plus once per bucket; the ordinals
+    (4 bytes per record of the input) lie outside the budget."""
+    with Operator("Rename", (o or SeqKitRenameOptions()).to_json(), device) as op:
+        RenameHistReset(op)
+        counts = RenameHistRun(op, input)
+        bounds = ShufflePlan(RenameHistGet(op)[0], budget_bytes)
+        RenameVerdictBegin(op, sum(counts))
+        for lo, hi in zip(bounds[:-1], bounds[1:]):
+            RenameBucket(op, input, counts, lo, hi)
+        return RenameEmit(op, input, counts)
+
+
 def HeadGenome(input, o=None, device=0):
     """bigseqkit/head_genome.go:37-77 (PARITY HEADG): the records of the first genome.  ONE cut over the whole input: the
     shards go through one context in order, which carries the prefix words, n_1 and "cut reached" from shard to shard, and

@@ -375,7 +375,7 @@ void bsk_destroy(bsk_ctx* c) {
         for (void* p : {(void*)c->sob.d_hist, (void*)c->sob.d_acc, (void*)c->sob.d_spl, (void*)c->sob.d_spl_off})
             if (p) hipFree(p);
         for (void* p : {(void*)c->rdb.d_hist, (void*)c->rdb.d_acc, (void*)c->rdb.d_draw, (void*)c->rdb.d_off, (void*)c->rdb.d_len,
-                        (void*)c->rdb.d_key, (void*)c->rdb.d_bits})
+                        (void*)c->rdb.d_key, (void*)c->rdb.d_bits, (void*)c->rdb.d_ord})
             if (p) hipFree(p);
         if (c->d_vm_progs) hipFree(c->d_vm_progs);
         if (c->d_id_off) hipFree(c->d_id_off);
@@ -1016,8 +1016,8 @@ static int run_record_op(bsk_ctx* c, Op want, const void* shard, size_t n, int o
     });
 }
 
-// ---- the bucket paths of shuffle, sort and rmdup (include/bsk.h; the passes are in ops_host_shuffle.cpp,
-// ops_host_sortbuckets.cpp and ops_host_rmdupbuckets.cpp, the life cycle of a bucket in the first)
+// ---- the bucket paths of shuffle, sort, rmdup and rename (include/bsk.h; the passes are in ops_host_shuffle.cpp,
+// ops_host_sortbuckets.cpp, ops_host_rmdupbuckets.cpp and ops_host_renamebuckets.cpp, the life cycle of a bucket in the first)
 static int bucket_ctx_check(bsk_ctx* c, Op op, const char* a_name, bool args_ok = true) {  // a_name: "a Sort", "an RmDup"
     if (!c) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: null context");
     if (c->op != op || !args_ok) return fail(c, BSK_ERR_INVALID_ARG, std::string("libbsk: not ") + a_name + " context");
@@ -1027,6 +1027,7 @@ static int bucket_ctx_check(bsk_ctx* c, Op op, const char* a_name, bool args_ok 
 static int shuffle_ctx_check(bsk_ctx* c) { return bucket_ctx_check(c, Op::Shuffle, "a Shuffle"); }
 static int sort_ctx_check(bsk_ctx* c) { return bucket_ctx_check(c, Op::Sort, "a Sort"); }
 static int rmdup_ctx_check(bsk_ctx* c) { return bucket_ctx_check(c, Op::RmDup, "an RmDup"); }
+static int rename_ctx_check(bsk_ctx* c) { return bucket_ctx_check(c, Op::Rename, "a Rename"); }
 static bool bins_ok(uint32_t lo_bin, uint32_t hi_bin_exclusive) { return lo_bin < hi_bin_exclusive && hi_bin_exclusive <= BUCKET_BINS; }
 // the prologue of a finish that fills a bsk_out
 static int bucket_finish_check(bsk_ctx* c, Op op, const char* a_name, bsk_out* out) {
@@ -1035,7 +1036,7 @@ static int bucket_finish_check(bsk_ctx* c, Op op, const char* a_name, bsk_out* o
     out->d_seg_src = nullptr; out->d_seg_off = nullptr; out->n_segments = 0;
     return BSK_OK;
 }
-// A pass of sort or rmdup over one shard: record_call, then pass(text, n, stream) through run_multiline -- a wrapped FASTQ shard
+// A pass of sort, rmdup or rename (whose buckets are c->rdb as well) over one shard: record_call, then pass(text, n, stream) through run_multiline -- a wrapped FASTQ shard
 // runs once more as its 4-line rewrite, like bsk_sort_run's and bsk_rmdup_run's.  closes: an error closes the open bucket, here
 // and not in the pass, which the rewrite enters a second time.  The passes of shuffle differ in both: they go through
 // index_record_text, which has the multi-line reader inside, and shuffle_bucket_add closes its bucket itself.
@@ -1512,7 +1513,7 @@ int bsk_rmdup_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin_exclusiv
     if (rcc != BSK_OK) return rcc;
     if (!bins_ok(lo_bin, hi_bin_exclusive)) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_rmdup_bucket_begin: the bins must be 0 <= lo < hi <= 4096");
     BSK_ENTER(c);
-    return rmdup_bucket_begin(c, lo_bin, hi_bin_exclusive);
+    return rdb_bucket_begin(c, lo_bin, hi_bin_exclusive);
 }
 
 int bsk_rmdup_bucket_add(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
@@ -1520,7 +1521,7 @@ int bsk_rmdup_bucket_add(bsk_ctx* c, const void* shard, size_t n, int on_device,
     const int rcc = rmdup_ctx_check(c);
     if (rcc != BSK_OK) return rcc;
     return bucket_pass(c, nullptr, Op::RmDup, true, true, shard, n, on_device, format, stream,
-                       [&](const uint8_t* t, size_t m, hipStream_t st) { return rmdup_bucket_add(c, t, m, format, first_record, st); });
+                       [&](const uint8_t* t, size_t m, hipStream_t st) { return rdb_bucket_add(c, t, m, format, first_record, st); });
 }
 
 int bsk_rmdup_bucket_finish(bsk_ctx* c, void* stream, uint64_t* n_removed, uint64_t* n_flagged) {
@@ -1537,6 +1538,76 @@ int bsk_rmdup_emit_run(bsk_ctx* c, const void* shard, size_t n, int on_device, i
     if (rcc != BSK_OK) return rcc;
     return bucket_pass(c, out, Op::RmDup, out != nullptr, false, shard, n, on_device, format, stream,
                        [&](const uint8_t* t, size_t m, hipStream_t st) { return rmdup_emit_device(c, t, m, format, first_record, st, out); });
+}
+
+// ---- rename in buckets of the key: the histogram, the begin and the add of a bucket are rmdup's steps on a Rename context
+int bsk_rename_hist_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                        void* stream, uint64_t* n_records) {
+    const int rcc = rename_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    return bucket_pass(c, nullptr, Op::Rename, true, false, shard, n, on_device, format, stream,
+                       [&](const uint8_t* t, size_t m, hipStream_t st) { return rdb_hist_device(c, t, m, format, st, n_records); });
+}
+
+int bsk_rename_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) {
+    const int rcc = rename_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    BSK_ENTER(c);
+    return bucket_hist_get(c, &c->rdb, bytes, records);
+}
+
+int bsk_rename_hist_reset(bsk_ctx* c) {
+    const int rcc = rename_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    BSK_ENTER(c);
+    return bucket_hist_reset(c, &c->rdb);
+}
+
+int bsk_rename_verdict_begin(bsk_ctx* c, uint64_t total_records) {
+    const int rcc = rename_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    BSK_ENTER(c);
+    return rename_verdict_begin(c, total_records);
+}
+
+int bsk_rename_verdict_get(bsk_ctx* c, uint64_t first, uint64_t count, uint32_t* ord) {
+    const int rcc = rename_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    if (count && !ord) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_rename_verdict_get: null argument");
+    BSK_ENTER(c);
+    return rename_verdict_get(c, first, count, ord);
+}
+
+int bsk_rename_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin_exclusive) {
+    const int rcc = rename_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    if (!bins_ok(lo_bin, hi_bin_exclusive)) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_rename_bucket_begin: the bins must be 0 <= lo < hi <= 4096");
+    BSK_ENTER(c);
+    return rdb_bucket_begin(c, lo_bin, hi_bin_exclusive);
+}
+
+int bsk_rename_bucket_add(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                          void* stream) {
+    const int rcc = rename_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    return bucket_pass(c, nullptr, Op::Rename, true, true, shard, n, on_device, format, stream,
+                       [&](const uint8_t* t, size_t m, hipStream_t st) { return rdb_bucket_add(c, t, m, format, first_record, st); });
+}
+
+int bsk_rename_bucket_finish(bsk_ctx* c, void* stream, uint64_t* n_renamed, uint64_t* n_flagged) {
+    const int rcc = rename_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    BSK_ENTER(c);
+    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), (hipStream_t)stream));
+    return rename_bucket_finish(c, (hipStream_t)stream, n_renamed, n_flagged);
+}
+
+int bsk_rename_emit_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                        void* stream, bsk_out* out) {
+    const int rcc = rename_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    return bucket_pass(c, out, Op::Rename, out != nullptr, false, shard, n, on_device, format, stream,
+                       [&](const uint8_t* t, size_t m, hipStream_t st) { return rename_emit_device(c, t, m, format, first_record, st, out); });
 }
 
 // ---- rmdup across ranks: the phases between which the caller runs the all-to-all exchanges (include/bsk.h)

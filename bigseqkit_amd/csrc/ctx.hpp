@@ -447,6 +447,12 @@ struct bsk_ctx {
         uint64_t total_records = 0;
         bool verdict = false;            // bsk_rmdup_verdict_begin was called
         std::vector<uint8_t> decided = std::vector<uint8_t>(bsk::BUCKET_BINS, 0);
+        // rename in buckets of the key (ops_host_renamebuckets.cpp; PARITY.md RENB) keeps its state here too -- a context is an
+        // RmDup or a Rename one, never both: the verdict is d_ord[g] = the ordinal of record g inside its group of equal subjects,
+        // d_bits stays null
+        uint32_t* d_ord = nullptr;
+        uint64_t ord_cap = 0;            // in records
+        uint64_t renamed = 0;            // non-zero ordinals written since the verdict began (the emit picks its kernel by it)
     } rdb;
 };
 

@@ -88,10 +88,18 @@ int sort_bucket_finish(bsk_ctx* c, hipStream_t st, bsk_out* out);
 int rmdup_hist_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, uint64_t* n_records);
 int rmdup_verdict_begin(bsk_ctx* c, uint64_t total_records);
 int rmdup_verdict_get(bsk_ctx* c, uint64_t first, uint64_t count, uint8_t* removed);
-int rmdup_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin);
-int rmdup_bucket_add(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st);
 int rmdup_bucket_finish(bsk_ctx* c, hipStream_t st, uint64_t* n_removed, uint64_t* n_flagged);
 int rmdup_emit_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st, bsk_out* out);
+// ... the steps that `rename` in buckets of the key shares with it, on an RmDup or a Rename context: the histogram without the
+// refusal of rmdup's side files, the begin and the add of a bucket
+int rdb_hist_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, uint64_t* n_records);
+int rdb_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin);
+int rdb_bucket_add(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st);
+// rename in buckets of the key (ops_host_renamebuckets.cpp; include/bsk.h)
+int rename_verdict_begin(bsk_ctx* c, uint64_t total_records);
+int rename_verdict_get(bsk_ctx* c, uint64_t first, uint64_t count, uint32_t* ord);
+int rename_bucket_finish(bsk_ctx* c, hipStream_t st, uint64_t* n_renamed, uint64_t* n_flagged);
+int rename_emit_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st, bsk_out* out);
 void validate_head_genome_opts(bsk_ctx* c);
 void head_genome_reset(bsk_ctx* c);
 int head_genome_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, bsk_out* out);

@@ -171,6 +171,34 @@ int bucket_require_open(bsk_ctx* c, const bsk_ctx::BucketState& B, const char* o
 int bucket_in_order(bsk_ctx* c, const bsk_ctx::BucketState& B, const char* op, uint64_t first_record);
 int bucket_too_many(bsk_ctx* c, const char* op);  // UNSUPPORTED: 2^32 or more records in one bucket of <op>
 inline void bucket_close(bsk_ctx::BucketState* B) { B->open = false; bucket_acc_clear(B); }
+// The steps of a bucket of `rmdup` that a bucket of `rename` takes as well (ops_host_rmdupbuckets.cpp; both on c->rdb, the
+// messages name the operator of the context -- rdb_op_name: "rmdup" / "rename"):
+//   rdb_params          the subject of a record: rmdup's options, or for rename the ID / the whole header (ByName) as it stands
+//   rdb_group_keys      the open bucket (B.n > 0): first[i] = the lowest accumulated index under the key of record i, at *o_first
+//                 of the arena *A (carved and reserved there; more may be taken behind it with arena_reserve_keep); c->d_xflag
+//                 holds RDB_FLAG_MAX + 1 words, the count in front zeroed
+//   rdb_flagged_texts   after the comparison: the m flagged records (c->d_xflag) in input order, the global index of every
+//                 accumulated record and the flagged subjects, gathered on the host; settle(list, gidx, blob, off) decides them --
+//                 subject of list[j] = blob[off[j], off[j + 1]).  BSK_ERR_HIP from either gets the message
+//   rdb_too_many_flagged   UNSUPPORTED: more than RDB_FLAG_MAX flagged records in one bucket
+//   rdb_emit_ready / rdb_emit_in_range   the refusals of an emit pass: no verdict, the first undecided bin / a shard past the verdict
+struct RmDupParams;
+constexpr uint64_t RDB_FLAG_MAX = 1u << 20;  // (as XFLAG_MAX)
+using RdbSettle = std::function<int(const std::vector<uint32_t>& list, const std::vector<uint64_t>& gidx, const std::string& blob,
+                                    const std::vector<uint64_t>& off)>;
+const char* rdb_op_name(const bsk_ctx* c);
+RmDupParams rdb_params(bsk_ctx* c, const uint8_t* d_buf, size_t n, bool fastq);
+int rdb_group_keys(bsk_ctx* c, hipStream_t st, Arena* A, uint64_t* o_first);
+int rdb_flagged_texts(bsk_ctx* c, uint32_t m, hipStream_t st, const RdbSettle& settle);
+int rdb_too_many_flagged(bsk_ctx* c);
+int rdb_emit_ready(bsk_ctx* c);
+int rdb_emit_in_range(bsk_ctx* c, uint64_t first_record, uint64_t N);
+// The tail of `rename` (ops_host_next.cpp), shared by rename_run_device and the emit pass of the buckets: before, c->table and
+// the text view `tt` of the shard, ren_ord[i] = the ordinal of record i (0: the record leaves as Format(LineWidth) prints it).
+// The sizes, their scan, the block and the emit -- one kernel over all records when `many` of them are renamed, else
+// emit_records -- and `out` filled
+int rename_emit(bsk_ctx* c, const uint8_t* d_buf, size_t n, bool fastq, const TextTableH& tt, const uint32_t* ren_ord, bool many,
+                hipStream_t st, bsk_out* out);
 // the record table of a shard and the complaints of its index pass, read BEFORE any kernel walks the table (a shard that is
 // wrapped behind its head goes to the multi-line reader, run_multiline): one synchronisation
 int index_shard_status(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st);

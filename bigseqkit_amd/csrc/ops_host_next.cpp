@@ -330,19 +330,24 @@ int rename_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hi
         HIP_TRYX(c, launch_group_sort(A.at<uint8_t>(o_tmp), tmp_bytes, d_list, d_list + m, m, st, N));
         HIP_TRYX(c, launch_group_ordinals(d_list + m, m, A.at<uint32_t>(o_ord), st));
     }
+    return rename_emit(c, d_buf, n, fastq, tt, A.at<uint32_t>(o_ord), m * 4 > N, st, out);
+}
+
+int rename_emit(bsk_ctx* c, const uint8_t* d_buf, size_t n, bool fastq, const TextTableH& tt, const uint32_t* ren_ord, bool many,
+                hipStream_t st, bsk_out* out) {
     SeqParams F = format_params(c, fastq);
     F.text_w = tt.text_w; F.lin_off = tt.lin_off; F.lin = tt.lin;
     F.buf_end = d_buf + n;
-    F.ren_ord = A.at<uint32_t>(o_ord);
+    F.ren_ord = ren_ord;
     HIP_TRYX(c, hipMemsetAsync(c->d_status, 0, 2 * sizeof(uint64_t), st));
     HIP_TRYX(c, launch_seq_size(d_buf, c->table, F, c->d_out_len, c->d_status, st));
     uint64_t total = 0, kept = 0;
-    rc = finish_sizes(c, st, &total, &kept);
+    int rc = finish_sizes(c, st, &total, &kept);
     if (rc != BSK_OK) return rc;
     rc = ensure_out(c, total);
     if (rc != BSK_OK) return rc;
     apply_long(c, &F);
-    if (m * 4 > N) {
+    if (many) {
         // many renamed records: their heads are rewritten record by record anyway, and one kernel over all records beats
         // the segmented copy of the rest plus that kernel (every ID twice: 59 vs 63 ms)
         HIP_TRYX(c, launch_seq_emit(d_buf, c->table, F, c->d_out_len, c->d_out_off, c->d_out, st, total, kept));

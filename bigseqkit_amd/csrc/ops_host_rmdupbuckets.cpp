@@ -2,6 +2,9 @@
 // collect pass of one bucket and its finish, and the emit pass.  The kernels are in ops_rmdup_buckets.hip; the keys are those of
 // launch_rmdup_hash, the grouping of a bucket is launch_bucket_pass + launch_bucket_dedupe (ops_rmdup.hip), and the emit ends
 // with the tail of rmdup_dist_emit.
+// `rename` in buckets of the key (ops_host_renamebuckets.cpp; PARITY.md RENB) groups by the same subject under the same key: the
+// steps down to first[] -- rdb_hist_device, rdb_bucket_begin, rdb_bucket_add, rdb_group_keys -- and rdb_flagged_texts serve both
+// operators on c->rdb (declared in ops_host_internal.hpp); their messages name the operator of the context.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -23,8 +26,6 @@
 
 namespace bsk {
 
-constexpr uint64_t RDB_FLAG_MAX = 1u << 20;  // more flagged records than this in one bucket: the call fails (as XFLAG_MAX)
-
 // ---- what the histogram and the collect pass do first: the table of the shard and the complaints of the index pass
 // (index_shard_status), the text view (-s on FASTA: every wrapped record flattened, as rmdup_run_device has it), the
 // parameters and k1 of every record in c->d_keys -- whole: the bin comes from all 64 bits
@@ -32,14 +33,17 @@ struct RdbShard {
     TextTableH tt;
     RmDupParams P;
 };
-static RmDupParams rdb_params(bsk_ctx* c, const uint8_t* d_buf, size_t n, bool fastq) {
+const char* rdb_op_name(const bsk_ctx* c) { return c->op == Op::Rename ? "rename" : "rmdup"; }
+static std::string rdb_fn(const bsk_ctx* c, const char* fn) { return std::string("bsk_") + rdb_op_name(c) + "_" + fn; }
+RmDupParams rdb_params(bsk_ctx* c, const uint8_t* d_buf, size_t n, bool fastq) {
     const Options& o = c->opts;
+    const bool rmdup = c->op == Op::RmDup;  // (rename: the ID, or the whole header with ByName, as it stands)
     RmDupParams P;
     memset(&P, 0, sizeof P);
     P.fastq = fastq;
-    P.by_seq = o.b("BySeq");
+    P.by_seq = rmdup && o.b("BySeq");
     P.by_name = o.b("ByName");
-    P.ignore_case = o.b("IgnoreCase");
+    P.ignore_case = rmdup && o.b("IgnoreCase");
     P.id_mode = id_mode_of(c);
     P.line_width = fastq ? 0 : (int)o.ci("LineWidth");
     P.buf_end = d_buf + n;
@@ -49,9 +53,9 @@ static int rdb_index_shard(bsk_ctx* c, const uint8_t* d_buf, size_t n, int forma
     const bool fastq = format == BSK_FORMAT_FASTQ;
     int rc = index_shard_status(c, d_buf, n, format, st);
     if (rc != BSK_OK || c->table.n == 0) return rc;
-    rc = prepare_text(c, d_buf, format, st, &S->tt, /*flatten=*/!fastq && c->opts.b("BySeq"), false, n);
-    if (rc != BSK_OK) return rc;
     S->P = rdb_params(c, d_buf, n, fastq);
+    rc = prepare_text(c, d_buf, format, st, &S->tt, /*flatten=*/!fastq && S->P.by_seq, false, n);
+    if (rc != BSK_OK) return rc;
     const uint64_t N = c->table.n;
     rc = ensure_record_scratch(c);
     if (rc != BSK_OK) return rc;
@@ -71,6 +75,10 @@ int rmdup_hist_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hi
         c->set_error("libbsk: -d / -D side files are not available on the rmdup path in buckets of the key");
         return BSK_ERR_UNSUPPORTED;
     }
+    return rdb_hist_device(c, d_buf, n, format, st, n_records);
+}
+int rdb_hist_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, uint64_t* n_records) {
+    c->last_kernel_flags = 0;
     int rc = bucket_hist_alloc(c, &c->rdb, st);
     if (rc != BSK_OK) return rc;
     RdbShard S;
@@ -133,13 +141,13 @@ static int rdb_reserve(bsk_ctx* c, uint64_t bytes, uint64_t recs, hipStream_t st
     return bucket_acc_reserve(c, &c->rdb, bytes, recs, true, st, &c->rdb.d_key);
 }
 
-int rmdup_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin) {
+int rdb_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin) {
     // (an open bucket has a verdict, so the order of this refusal and the one of bucket_begin does not show)
     if (!c->rdb.verdict) {
-        c->set_error("libbsk: bsk_rmdup_bucket_begin: no verdict to write to (bsk_rmdup_verdict_begin first)");
+        c->set_error("libbsk: " + rdb_fn(c, "bucket_begin") + ": no verdict to write to (" + rdb_fn(c, "verdict_begin") + " first)");
         return BSK_ERR_INVALID_ARG;
     }
-    return bucket_begin(c, &c->rdb, "rmdup", lo_bin, hi_bin, [&](uint64_t bytes, uint64_t recs) {
+    return bucket_begin(c, &c->rdb, rdb_op_name(c), lo_bin, hi_bin, [&](uint64_t bytes, uint64_t recs) {
         return rdb_reserve(c, bytes - recs * RMDUP_BUCKET_RECORD_BYTES, recs, nullptr);  // (the histogram counts the per-record arrays in)
     });
 }
@@ -148,15 +156,16 @@ static int rdb_bucket_add_open(bsk_ctx* c, const uint8_t* d_buf, size_t n, int f
     bsk_ctx::RmDupBuckets& B = c->rdb;
     c->last_kernel_flags = 0;
     // the survivor of a group is its lowest accumulated index because the accumulation receives its records in input order
-    int rc = bucket_in_order(c, B, "rmdup", first_record);
+    int rc = bucket_in_order(c, B, rdb_op_name(c), first_record);
     if (rc != BSK_OK) return rc;
     RdbShard S;
     rc = rdb_index_shard(c, d_buf, n, format, st, &S);
     if (rc != BSK_OK) return rc;
     const uint64_t N = c->table.n;
     if (first_record > B.total_records || N > B.total_records - first_record) {
-        c->set_error("libbsk: bsk_rmdup_bucket_add: the shard's records " + std::to_string(first_record) + " .. " + std::to_string(first_record + N) +
-                     " reach past the total_records = " + std::to_string(B.total_records) + " of bsk_rmdup_verdict_begin");
+        c->set_error("libbsk: " + rdb_fn(c, "bucket_add") + ": the shard's records " + std::to_string(first_record) + " .. " +
+                     std::to_string(first_record + N) + " reach past the total_records = " + std::to_string(B.total_records) + " of " +
+                     rdb_fn(c, "verdict_begin"));
         return BSK_ERR_INVALID_ARG;
     }
     if (N == 0) return BSK_OK;
@@ -185,7 +194,7 @@ static int rdb_bucket_add_open(bsk_ctx* c, const uint8_t* d_buf, size_t n, int f
     if (rc != BSK_OK) return rc;
     const uint64_t long_count = c->h_ctl[8 + 2];  // (d_counter is d_ctl[8 ..])
     if (kept) {
-        if (B.n + kept >= (1ull << 32)) return bucket_too_many(c, "rmdup");
+        if (B.n + kept >= (1ull << 32)) return bucket_too_many(c, rdb_op_name(c));
         rc = rdb_reserve(c, B.acc_used + total, B.n + kept, st);
         if (rc != BSK_OK) return rc;
         Timed tm(c, "k_rdb_pack", st);
@@ -202,18 +211,18 @@ static int rdb_bucket_add_open(bsk_ctx* c, const uint8_t* d_buf, size_t n, int f
     return BSK_OK;
 }
 
-int rmdup_bucket_add(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st) {
-    const int rc = bucket_require_open(c, c->rdb, "rmdup", "add");
+int rdb_bucket_add(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st) {
+    const int rc = bucket_require_open(c, c->rdb, rdb_op_name(c), "add");
     if (rc != BSK_OK) return rc;
     return rdb_bucket_add_open(c, d_buf, n, format, first_record, st);  // (no close on an error here: see sort_bucket_add)
 }
 
-// The flagged records -- accumulated indices whose subject differs from that of the record their key group names -- settled
-// exactly, as PARITY KEYS (b) does: grouped by TEXT on the host, the lowest global index of every text survives (all records of
-// one text share k1, hence the group, hence the flag), the others get their bit.  *losers = their number.
-static int rdb_settle_flagged(bsk_ctx* c, uint32_t m, hipStream_t st, uint64_t* losers) {
+// The flagged records -- accumulated indices whose subject differs from that of the record their key group names -- on their
+// way to the host, where they are settled exactly, as PARITY KEYS (b) does: the m entries of c->d_xflag in ascending accumulated
+// order (which is input order), the global index of every accumulated record, and the subject of flagged record list[j] =
+// blob[off[j], off[j + 1]).  All records of one text share k1, hence the group, hence the flag: settle() groups them by TEXT.
+int rdb_flagged_texts(bsk_ctx* c, uint32_t m, hipStream_t st, const RdbSettle& settle) {
     bsk_ctx::RmDupBuckets& B = c->rdb;
-    *losers = 0;
     std::vector<uint32_t> list(m);
     HIP_TRYX(c, hipMemcpy(list.data(), c->d_xflag + 1, (size_t)m * 4, hipMemcpyDeviceToHost));
     std::sort(list.begin(), list.end());  // (accumulated order is input order)
@@ -227,40 +236,53 @@ static int rdb_settle_flagged(bsk_ctx* c, uint32_t m, hipStream_t st, uint64_t* 
     uint32_t* d_list = nullptr;
     uint64_t* d_off = nullptr;
     uint8_t* d_blob = nullptr;
-    uint64_t* d_lose = nullptr;
-    auto cleanup = [&] { for (void* p : {(void*)d_list, (void*)d_off, (void*)d_blob, (void*)d_lose}) if (p) hipFree(p); };
     int rc = BSK_OK;
-    do {
-        if (hipMalloc((void**)&d_list, (size_t)m * 4) != hipSuccess || hipMalloc((void**)&d_off, (size_t)(m + 1) * 8) != hipSuccess ||
-            hipMalloc((void**)&d_blob, std::max<uint64_t>(off[m], 1)) != hipSuccess ||
-            hipMemcpyAsync(d_list, list.data(), (size_t)m * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
-            hipMemcpyAsync(d_off, off.data(), (size_t)(m + 1) * 8, hipMemcpyHostToDevice, st) != hipSuccess ||
-            launch_rdb_gather(B.d_acc, B.d_off, B.d_len, d_list, d_off, m, d_blob, st) != hipSuccess ||
-            (off[m] && hipMemcpyAsync(&blob[0], d_blob, off[m], hipMemcpyDeviceToHost, st) != hipSuccess) ||
-            hipStreamSynchronize(st) != hipSuccess) { rc = BSK_ERR_HIP; break; }
+    if (hipMalloc((void**)&d_list, (size_t)m * 4) != hipSuccess || hipMalloc((void**)&d_off, (size_t)(m + 1) * 8) != hipSuccess ||
+        hipMalloc((void**)&d_blob, std::max<uint64_t>(off[m], 1)) != hipSuccess ||
+        hipMemcpyAsync(d_list, list.data(), (size_t)m * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(d_off, off.data(), (size_t)(m + 1) * 8, hipMemcpyHostToDevice, st) != hipSuccess ||
+        launch_rdb_gather(B.d_acc, B.d_off, B.d_len, d_list, d_off, m, d_blob, st) != hipSuccess ||
+        (off[m] && hipMemcpyAsync(&blob[0], d_blob, off[m], hipMemcpyDeviceToHost, st) != hipSuccess) ||
+        hipStreamSynchronize(st) != hipSuccess)
+        rc = BSK_ERR_HIP;
+    for (void* p : {(void*)d_list, (void*)d_off, (void*)d_blob}) if (p) hipFree(p);
+    if (rc == BSK_OK) rc = settle(list, gidx, blob, off);
+    if (rc == BSK_ERR_HIP)
+        c->set_error(std::string("libbsk: ") + rdb_op_name(c) + ": settling the records that differ from their key group failed on the device");
+    return rc;
+}
+
+// rmdup: the lowest global index of every text survives, the others get their bit.  *losers = their number.
+static int rdb_settle_flagged(bsk_ctx* c, uint32_t m, hipStream_t st, uint64_t* losers) {
+    *losers = 0;
+    return rdb_flagged_texts(c, m, st, [&](const std::vector<uint32_t>& list, const std::vector<uint64_t>& gidx, const std::string& blob,
+                                           const std::vector<uint64_t>& off) {
         std::unordered_map<std::string, uint32_t> seen;  // text -> its first flagged record
         std::vector<uint64_t> lose;
         for (uint32_t j = 0; j < m; ++j)
             if (!seen.emplace(blob.substr(off[j], off[j + 1] - off[j]), list[j]).second) lose.push_back(gidx[list[j]]);
         *losers = lose.size();
-        if (lose.empty()) break;
-        if (hipMalloc((void**)&d_lose, lose.size() * 8) != hipSuccess ||
-            hipMemcpyAsync(d_lose, lose.data(), lose.size() * 8, hipMemcpyHostToDevice, st) != hipSuccess ||
-            launch_rdb_mark(d_lose, lose.size(), B.d_bits, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { rc = BSK_ERR_HIP; break; }
-    } while (false);
-    cleanup();
-    if (rc != BSK_OK) c->set_error("libbsk: rmdup: settling the records that differ from their key group failed on the device");
-    return rc;
+        if (lose.empty()) return (int)BSK_OK;
+        uint64_t* d_lose = nullptr;
+        const bool ok = hipMalloc((void**)&d_lose, lose.size() * 8) == hipSuccess &&
+                        hipMemcpyAsync(d_lose, lose.data(), lose.size() * 8, hipMemcpyHostToDevice, st) == hipSuccess &&
+                        launch_rdb_mark(d_lose, lose.size(), c->rdb.d_bits, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
+        if (d_lose) hipFree(d_lose);
+        return ok ? (int)BSK_OK : (int)BSK_ERR_HIP;
+    });
 }
 
-static int rdb_bucket_decide(bsk_ctx* c, hipStream_t st, uint64_t* n_removed, uint64_t* n_flagged) {
+// The key grouping of the open bucket (B.n > 0 records): first[i] = the lowest accumulated index that shares the key of
+// record i -- the radix-bucket pass on the accumulated keys, or the one big table in HBM.  first[] lies at *o_first of the
+// arena *A, which is carved and reserved here; a caller that takes more of it afterwards keeps A->used bytes
+// (arena_reserve_keep) and derives the pointer again.  c->d_xflag holds RDB_FLAG_MAX + 1 words afterwards, the first one zeroed.
+int rdb_group_keys(bsk_ctx* c, hipStream_t st, Arena* Ap, uint64_t* o_first_out) {
     bsk_ctx::RmDupBuckets& B = c->rdb;
     const uint64_t N = B.n;
-    if (N == 0) return BSK_OK;
+    Arena& A = *Ap;
     uint32_t k1_bits = 64;
     if (const char* e = c->tune.get("rmdup_k1_bits"))  // tests: only the low bits of k1 group (different subjects under one key)
         if (atoi(e) >= 16 && atoi(e) < 64) k1_bits = (uint32_t)atoi(e);
-    Arena A;
     const uint32_t nb = 1u << RMDUP_BUCKET_BITS;
     const uint64_t o_kc = A.take(N * 8), o_sk = A.take(N * 8), o_vo = A.take(N * 4), o_first = A.take(N * 4), o_bs = A.take((nb + 2) * 4),
                    o_hist = A.take(nb * 4), o_has = A.take(N);
@@ -301,6 +323,24 @@ static int rdb_bucket_decide(bsk_ctx* c, hipStream_t st, uint64_t* n_removed, ui
     rc = grow(c, &c->d_xflag, &c->xflag_cap, RDB_FLAG_MAX + 1);
     if (rc != BSK_OK) return rc;
     HIP_TRYX(c, hipMemsetAsync(c->d_xflag, 0, sizeof(uint32_t), st));
+    *o_first_out = o_first;
+    return BSK_OK;
+}
+
+int rdb_too_many_flagged(bsk_ctx* c) {
+    c->set_error(std::string("libbsk: ") + rdb_op_name(c) + ": more than 2^20 records of one bucket differ from the survivor of their key group; refusing (keys that collide that often are no keys)");
+    return BSK_ERR_UNSUPPORTED;
+}
+
+static int rdb_bucket_decide(bsk_ctx* c, hipStream_t st, uint64_t* n_removed, uint64_t* n_flagged) {
+    bsk_ctx::RmDupBuckets& B = c->rdb;
+    const uint64_t N = B.n;
+    if (N == 0) return BSK_OK;
+    Arena A;
+    uint64_t o_first = 0;
+    int rc = rdb_group_keys(c, st, &A, &o_first);
+    if (rc != BSK_OK) return rc;
+    const uint32_t* first = A.at<uint32_t>(o_first);
     uint64_t* d_removed = c->d_fin + bsk_ctx::FIN_AUX0;
     HIP_TRYX(c, hipMemsetAsync(d_removed, 0, sizeof(uint64_t), st));
     {
@@ -313,10 +353,7 @@ static int rdb_bucket_decide(bsk_ctx* c, hipStream_t st, uint64_t* n_removed, ui
     if (rc != BSK_OK) return rc;
     *n_removed = c->fin(bsk_ctx::FIN_AUX0);
     *n_flagged = m;
-    if (m > RDB_FLAG_MAX) {
-        c->set_error("libbsk: rmdup: more than 2^20 records of one bucket differ from the survivor of their key group; refusing (keys that collide that often are no keys)");
-        return BSK_ERR_UNSUPPORTED;
-    }
+    if (m > RDB_FLAG_MAX) return rdb_too_many_flagged(c);
     if (m) {
         Timed t(c, "rdb_settle_flagged", st);
         uint64_t losers = 0;
@@ -342,32 +379,46 @@ int rmdup_bucket_finish(bsk_ctx* c, hipStream_t st, uint64_t* n_removed, uint64_
 }
 
 // ---- the emit pass: the survivors of the shard, in order, each as Format(LineWidth)
-int rmdup_emit_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st, bsk_out* out) {
+// the refusals of an emit pass: no verdict, an undecided bin (the first is named) / a shard that reaches past the verdict
+int rdb_emit_ready(bsk_ctx* c) {
     const bsk_ctx::RmDupBuckets& B = c->rdb;
-    c->last_kernel_flags = 0;
     if (!B.verdict) {
-        c->set_error("libbsk: bsk_rmdup_emit_run: no verdict (bsk_rmdup_verdict_begin and the buckets first)");
+        c->set_error("libbsk: " + rdb_fn(c, "emit_run") + ": no verdict (" + rdb_fn(c, "verdict_begin") + " and the buckets first)");
         return BSK_ERR_INVALID_ARG;
     }
     for (uint32_t b = 0; b < BUCKET_BINS; ++b)
         if (!B.decided[b]) {
-            c->set_error("libbsk: bsk_rmdup_emit_run: fine bin " + std::to_string(b) + " has not been decided (every bin belongs to a bucket that "
-                         "was finished since bsk_rmdup_verdict_begin)");
+            c->set_error("libbsk: " + rdb_fn(c, "emit_run") + ": fine bin " + std::to_string(b) + " has not been decided (every bin belongs to a bucket that "
+                         "was finished since " + rdb_fn(c, "verdict_begin") + ")");
             return BSK_ERR_INVALID_ARG;
         }
+    return BSK_OK;
+}
+int rdb_emit_in_range(bsk_ctx* c, uint64_t first_record, uint64_t N) {
+    const bsk_ctx::RmDupBuckets& B = c->rdb;
+    if (first_record > B.total_records || N > B.total_records - first_record) {
+        c->set_error("libbsk: " + rdb_fn(c, "emit_run") + ": the shard's records " + std::to_string(first_record) + " .. " + std::to_string(first_record + N) +
+                     " reach past the total_records = " + std::to_string(B.total_records) + " of " + rdb_fn(c, "verdict_begin"));
+        return BSK_ERR_INVALID_ARG;
+    }
+    return BSK_OK;
+}
+
+int rmdup_emit_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st, bsk_out* out) {
+    const bsk_ctx::RmDupBuckets& B = c->rdb;
+    c->last_kernel_flags = 0;
+    int rc = rdb_emit_ready(c);
+    if (rc != BSK_OK) return rc;
     if (slices_wanted(c)) {
         c->set_error("libbsk: bsk_rmdup_emit_run: out=slices is not available on the rmdup path in buckets of the key");
         return BSK_ERR_UNSUPPORTED;
     }
     const bool fastq = format == BSK_FORMAT_FASTQ;
-    int rc = index_shard_status(c, d_buf, n, format, st);
+    rc = index_shard_status(c, d_buf, n, format, st);
     if (rc != BSK_OK) return rc;
     const uint64_t N = c->table.n;
-    if (first_record > B.total_records || N > B.total_records - first_record) {
-        c->set_error("libbsk: bsk_rmdup_emit_run: the shard's records " + std::to_string(first_record) + " .. " + std::to_string(first_record + N) +
-                     " reach past the total_records = " + std::to_string(B.total_records) + " of bsk_rmdup_verdict_begin");
-        return BSK_ERR_INVALID_ARG;
-    }
+    rc = rdb_emit_in_range(c, first_record, N);
+    if (rc != BSK_OK) return rc;
     if (N == 0) return empty_result(c, out);
     TextTableH tt;
     rc = prepare_text(c, d_buf, format, st, &tt);

@@ -706,14 +706,15 @@ static size_t whole_file_limit() {
     return lim;
 }
 
-// BSK_SHUFFLE_BUDGET_BYTES / BSK_SORT_BUDGET_BYTES / BSK_RMDUP_BUDGET_BYTES: the bytes a bucket of `shuffle` / `sort` / `rmdup` may
-// hold (run_buckets; rmdup: bytes of subjects and their per-record words, not of record text); 0: unset
+// BSK_SHUFFLE_BUDGET_BYTES / BSK_SORT_BUDGET_BYTES / BSK_RMDUP_BUDGET_BYTES / BSK_RENAME_BUDGET_BYTES: the bytes a bucket of
+// `shuffle` / `sort` / `rmdup` / `rename` may hold (run_buckets; rmdup, rename: bytes of subjects and their per-record words, not
+// of record text); 0: unset
 static uint64_t bucket_budget(const std::string& use) {
     const char* e = use == "shuffle" ? getenv("BSK_SHUFFLE_BUDGET_BYTES") : use == "sort" ? getenv("BSK_SORT_BUDGET_BYTES")
-                  : use == "rmdup" ? getenv("BSK_RMDUP_BUDGET_BYTES") : nullptr;
+                  : use == "rmdup" ? getenv("BSK_RMDUP_BUDGET_BYTES") : use == "rename" ? getenv("BSK_RENAME_BUDGET_BYTES") : nullptr;
     return e ? (uint64_t)strtoull(e, nullptr, 10) : 0;
 }
-bool g_buckets_unfit = false;  // read_parts: the whole-file load of a `shuffle` / `sort` input failed and a budget is set
+bool g_buckets_unfit = false;  // read_parts: the whole-file load of a `shuffle` / `sort` / `rmdup` / `rename` input failed and a budget is set
 
 std::vector<Part> read_parts(const std::vector<std::string>& files, int device = -1, const std::string& use = "") {
     std::vector<Part> parts;
@@ -757,6 +758,10 @@ std::vector<Part> read_parts(const std::vector<std::string>& files, int device =
                     if (use == "rmdup")
                         die(what + "cut it over several GPUs (--devices 0-7), or BSK_RMDUP_BUDGET_BYTES=<bytes> removes the duplicates in buckets of "
                                    "the key that hold at most that many bytes of subjects, read twice and once per bucket");
+                    if (use == "rename")
+                        die(what + "rename numbers the records of an ID over its whole input and runs on one device "
+                                   "(BSK_RENAME_BUDGET_BYTES=<bytes> renames it in buckets of the key that hold at most that many bytes of "
+                                   "subjects, read twice and once per bucket)");
                     die(what + "cut it over several GPUs (--devices 0-7: fq2fa, grep, locate, rmdup, sample, seq, stats, subseq, translate)");
                 }
                 // stats: the file stays on the host, its mapping is streamed in record-aligned chunks
@@ -1019,9 +1024,9 @@ Output run_head_genome(const Invocation& inv) {
     return res;
 }
 
-// shuffle in buckets of the draw, sort and rmdup in buckets of the key (include/bsk.h; PARITY.md SHUF, SORT, RMDUPB): the way of the
-// three commands for an input that is larger than the byte budget of a bucket (BSK_SHUFFLE_BUDGET_BYTES, BSK_SORT_BUDGET_BYTES,
-// BSK_RMDUP_BUDGET_BYTES) or that could
+// shuffle in buckets of the draw, sort, rmdup and rename in buckets of the key (include/bsk.h; PARITY.md SHUF, SORT, RMDUPB, RENB):
+// the way of the four commands for an input that is larger than the byte budget of a bucket (BSK_SHUFFLE_BUDGET_BYTES,
+// BSK_SORT_BUDGET_BYTES, BSK_RMDUP_BUDGET_BYTES, BSK_RENAME_BUDGET_BYTES) or that could
 // not be loaded whole.  The files stay on the host, mapped; several files are unioned in order (cli/shuffle.go:11-15,
 // cli/sort.go), the record index runs over all of them.  Record-aligned pieces (BSK_STREAM_PIECE_BYTES, default 1 GiB) go
 // through ONE context.  The mapping, the piece list, the plan and the timing line are shared; the passes differ:
@@ -1034,14 +1039,15 @@ Output run_head_genome(const Invocation& inv) {
 //   rmdup     once for the histogram of the bins of the key, once per bucket -- the pieces in input order; a bucket holds subjects
 //             and ends in its share of the verdict, it prints nothing -- and once for the emit, whose piece outputs are
 //             appended to the result: 2 + B times.  -d / -D are refused by the histogram pass.
+//   rename    the passes of rmdup; a bucket ends in its share of the ordinals, and the emit prints every record, renamed
 // Every finished bucket is appended to the output.  A piece never spans two files, so a file that ends without a newline
 // behaves like the union of the whole-file path: its last record gets the newline.
 Output run_buckets(const Invocation& inv) {
     const std::string use = inv.cmd->use;
-    const bool sort = use == "sort", rmdup = use == "rmdup";
+    const bool sort = use == "sort", rmdup = use == "rmdup", rename = use == "rename";
     const int device = (int)strtol(inv.pget("device").c_str(), nullptr, 10);
     const uint64_t budget = bucket_budget(use);
-    constexpr uint32_t kBins = 4096;  // the fine bins of all three (include/bsk.h)
+    constexpr uint32_t kBins = 4096;  // the fine bins of all four (include/bsk.h)
     Output res;
     bsk_ctx* ctx = nullptr;
     if (bsk_create(inv.cmd->op, inv.js.c_str(), device, &ctx) != BSK_OK) die(bsk_global_error());
@@ -1089,7 +1095,7 @@ Output run_buckets(const Invocation& inv) {
         }
     }
     res.fmt = fmt < 0 ? BSK_FORMAT_FASTA : fmt;
-    // the entry points of the passes that the three commands share, and what their timing marks say
+    // the entry points of the passes that the four commands share, and what their timing marks say
     struct Entry {
         decltype(&bsk_shuffle_hist_run) hist_run;
         decltype(&bsk_shuffle_hist_get) hist_get;
@@ -1099,6 +1105,7 @@ Output run_buckets(const Invocation& inv) {
     };
     const Entry E = sort    ? Entry{bsk_sort_hist_run, bsk_sort_hist_get, bsk_sort_bucket_begin, bsk_sort_bucket_add, "sort: histogram of the bins", "sort: buckets"}
                     : rmdup ? Entry{bsk_rmdup_hist_run, bsk_rmdup_hist_get, bsk_rmdup_bucket_begin, bsk_rmdup_bucket_add, "rmdup: histogram of the bins", "rmdup: buckets"}
+                    : rename ? Entry{bsk_rename_hist_run, bsk_rename_hist_get, bsk_rename_bucket_begin, bsk_rename_bucket_add, "rename: histogram of the bins", "rename: buckets"}
                             : Entry{bsk_shuffle_hist_run, bsk_shuffle_hist_get, bsk_shuffle_bucket_begin, bsk_shuffle_bucket_add, "shuffle: histogram of the draws", "shuffle: buckets"};
     // the pass over all pieces that counts the records: it leaves every piece's first record index
     uint64_t last_count = 0;  // the records of the last piece
@@ -1149,17 +1156,19 @@ Output run_buckets(const Invocation& inv) {
         std::string msg = bsk_global_error();
         if (sort) msg += " -- sort: a fine bin holds the records between two splitter keys; many equal keys, or a run that the sample missed, fill one";
         if (rmdup) msg += " -- rmdup: a fine bin holds the subjects whose key shares its upper 12 bits; the copies of one subject fill one";
+        if (rename) msg += " -- rename: a fine bin holds the IDs (-n: the names) whose key shares its upper 12 bits, once per record; the records of one ID fill one";
         die(msg);
     }
-    uint64_t removed = 0, flagged = 0;
-    if (rmdup) {
-        // every bucket over all pieces, in order, ends in its share of the verdict; one emit pass prints the survivors in file order
+    uint64_t removed = 0, flagged = 0;  // (rename: renamed)
+    if (rmdup || rename) {
+        // every bucket over all pieces, in order, ends in its share of the verdict; one emit pass prints the survivors (rename:
+        // every record under its new name) in file order
         const uint64_t total_records = pieces.empty() ? 0 : pieces.back().first + last_count;
-        if (bsk_rmdup_verdict_begin(ctx, total_records) != BSK_OK) die(bsk_last_error(ctx));
+        if ((rename ? bsk_rename_verdict_begin : bsk_rmdup_verdict_begin)(ctx, total_records) != BSK_OK) die(bsk_last_error(ctx));
         for (int b = 0; b < n_buckets; ++b) {
             fill_bucket((uint32_t)bounds[b], (uint32_t)bounds[b + 1]);
             uint64_t r = 0, f = 0;
-            if (bsk_rmdup_bucket_finish(ctx, nullptr, &r, &f) != BSK_OK) die(bsk_last_error(ctx));
+            if ((rename ? bsk_rename_bucket_finish : bsk_rmdup_bucket_finish)(ctx, nullptr, &r, &f) != BSK_OK) die(bsk_last_error(ctx));
             removed += r;
             flagged += f;
         }
@@ -1167,10 +1176,10 @@ Output run_buckets(const Invocation& inv) {
         int64_t k = 0;
         for (auto& pc : pieces) {
             bsk_out out;
-            if (bsk_rmdup_emit_run(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr, &out) != BSK_OK) die(bsk_last_error(ctx));
+            if ((rename ? bsk_rename_emit_run : bsk_rmdup_emit_run)(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr, &out) != BSK_OK) die(bsk_last_error(ctx));
             append_out(out);
         }
-        mark("rmdup: emit");
+        mark(rename ? "rename: emit" : "rmdup: emit");
     } else {
         // every finished bucket is appended to the output; sort -r: from the last to the first
         const bool backwards = sort && inv.pget("reverse") == "true";
@@ -1190,6 +1199,9 @@ Output run_buckets(const Invocation& inv) {
                     (unsigned long long)budget, pieces.size(), buf.data());
         if (rmdup)
             fprintf(stderr, "[timing] rmdup: %llu record(s) removed, %llu flagged (subject differed from the survivor of its key group)\n",
+                    (unsigned long long)removed, (unsigned long long)flagged);
+        if (rename)
+            fprintf(stderr, "[timing] rename: %llu record(s) renamed, %llu flagged (subject differed from the first of its key group)\n",
                     (unsigned long long)removed, (unsigned long long)flagged);
     }
     for (auto& f : files)
@@ -1609,7 +1621,7 @@ static int run_main(int argc, char** argv) {
         store(inv, o, inv.files);
         return 0;
     }
-    if (bucket_budget(use_cmd) > 0) {  // (shuffle, sort, rmdup)
+    if (bucket_budget(use_cmd) > 0) {  // (shuffle, sort, rmdup, rename)
         // more bytes than a bucket may hold: not loaded whole (a pipe has no size: it takes the whole-file path)
         uint64_t total = 0;
         struct stat sb;

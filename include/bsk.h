@@ -514,6 +514,41 @@ int bsk_rmdup_bucket_finish(bsk_ctx* ctx, void* stream, uint64_t* n_removed, uin
 int bsk_rmdup_emit_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                        void* stream, bsk_out* out);
 
+/* ---- Rename in buckets of the key: the bytes of bsk_rename_run for an input of any size on one device (PARITY.md RENB).
+ * The subject of a record is its ID, or its whole header with ByName, as it stands; ord[g] = the number of records g' < g
+ * (global index over the whole input) with the same subject bytes, and record g is printed as bsk_rename_run prints a record
+ * with that ordinal: header "<ID>_<ord> <Desc>" when ord > 0, else unchanged, each record as Format(LineWidth).  The fine bin,
+ * the cost of a bin, the accumulation of SUBJECTS and the key grouping are those of the RmDup buckets above -- the histogram of
+ * a Rename context equals that of an RmDup context with the same ByName --, and so are the reads of the input: once for the
+ * histogram, once per bucket and once for the emit.  A bucket ends in its share of the verdict, which is one uint32_t per
+ * record of the whole input: 4 * (total_records + 1) bytes of device memory OUTSIDE the budget of the buckets, allocated by
+ * bsk_rename_verdict_begin.  Records whose subject differs from the first of their key group ("flagged") are ranked exactly
+ * on the host, grouped by text.
+ *   bsk_rename_hist_run / _hist_get / _hist_reset      as bsk_rmdup_hist_*; bsk_shuffle_plan is the plan
+ *   bsk_rename_verdict_begin  zeroed ordinals for the records [0, total_records), no bin decided
+ *   bsk_rename_verdict_get    ord[j] = the ordinal of record first + j, j < count
+ *   bsk_rename_bucket_begin / _add / _finish
+ *                             as bsk_rmdup_bucket_*, with the same refusals; finish writes the non-zero ordinals of the bucket's
+ *                             records: *n_renamed = their number, *n_flagged = the records whose subject differed from the
+ *                             first of their key group (more than 2^20 of them in one bucket fail the call)
+ *   bsk_rename_emit_run       the records of the shard, in order, renamed, as one block valid until the next call on the
+ *                             context; BSK_ERR_INVALID_ARG while some bin has not been decided (the message names the first
+ *                             one).  out=slices is what it is on bsk_rename_run: the block all the same
+ * Every one of them is BSK_ERR_INVALID_ARG, "not a Rename context", on a context of another operator; the bsk_rmdup_* entry
+ * points refuse a Rename context likewise. */
+int bsk_rename_hist_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                        void* stream, uint64_t* n_records);
+int bsk_rename_hist_get(bsk_ctx* ctx, uint64_t* bytes, uint64_t* records);
+int bsk_rename_hist_reset(bsk_ctx* ctx);
+int bsk_rename_verdict_begin(bsk_ctx* ctx, uint64_t total_records);
+int bsk_rename_verdict_get(bsk_ctx* ctx, uint64_t first, uint64_t count, uint32_t* ord);
+int bsk_rename_bucket_begin(bsk_ctx* ctx, uint32_t lo_bin, uint32_t hi_bin_exclusive);
+int bsk_rename_bucket_add(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                          void* stream);
+int bsk_rename_bucket_finish(bsk_ctx* ctx, void* stream, uint64_t* n_renamed, uint64_t* n_flagged);
+int bsk_rename_emit_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                        void* stream, bsk_out* out);
+
 /* ---- HeadGenome (bigseqkit/head_genome.go, bigseqkit-lib/head_genome.go:53-108; options {"MiniCommonWords": 1}; PARITY.md
  * HEADG): the records of the first genome.  The words of a record are the maximal runs of its description other than ' '
  * and '\t'; the prefix is the words of the first record of the input; n_i = leading words of record i equal to the prefix's.
