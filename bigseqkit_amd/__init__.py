@@ -15,4 +15,5 @@ from .api import (SeqFrame, ReadFASTA, ReadFASTAN, ReadFASTQ, ReadFASTQN, Operat
                   SortBuckets, SortBucketsPlan, SortBucket, SortSampleRun, SortSampleReset, SortSampleCount, SortPickSplitters, SortSplittersBuild,
                   SortSplittersSet, SortSplittersGet, SortHistRun, SortHistGet, SortHistReset,
                   RmDupBuckets, RmDupHistRun, RmDupHistGet, RmDupHistReset, RmDupVerdictBegin, RmDupVerdictGet, RmDupBucket, RmDupEmit,
-                  RenameBuckets, RenameHistRun, RenameHistGet, RenameHistReset, RenameVerdictBegin, RenameVerdictGet, RenameBucket, RenameEmit)
+                  RenameBuckets, RenameHistRun, RenameHistGet, RenameHistReset, RenameVerdictBegin, RenameVerdictGet, RenameBucket, RenameEmit,
+                  CommonBuckets, CommonHistRun, CommonHistGet, CommonHistReset, CommonVerdictBegin, CommonVerdictGet, CommonBucket, CommonEmit)

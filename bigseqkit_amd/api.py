@@ -753,6 +753,83 @@ def RenameBuckets(input, o=None, budget_bytes=1 << 30, device=0):
         return RenameEmit(op, input, counts)
 
 
+def _union_frame(inputs):
+    """the shards of the files of `common`, in command order, as one frame: the global record index runs over all of them"""
+    if any(f.format != inputs[0].format for f in inputs):
+        raise ValueError("common: inputs of different formats")
+    return SeqFrame(inputs[0].format, [s for f in inputs for s in f.shards])
+
+
+def CommonHistRun(op, inputs):
+    """bsk_common_hist_run over the shards of every file of `inputs`, in order: per file, the record count of every shard (the
+    histogram accumulates in the operator's context)"""
+    flat = _count_pass(lib.bsk_common_hist_run, op, _union_frame(inputs))
+    counts, at = [], 0
+    for f in inputs:
+        counts.append(flat[at:at + len(f.shards)])
+        at += len(f.shards)
+    return counts
+
+
+def CommonHistGet(op):
+    """bsk_common_hist_get: (bytes[4096], records[4096])"""
+    return _hist_get(lib.bsk_common_hist_get, op)
+
+
+def CommonHistReset(op):
+    check(lib.bsk_common_hist_reset(op.ctx), op.ctx)
+
+
+def CommonVerdictBegin(op, file_records):
+    """bsk_common_verdict_begin: zeroed keep bits for the records of the first file, no bin decided; file_records[f] = the
+    records of file f (2 .. 64 files)"""
+    arr = (C.c_uint64 * max(1, len(file_records)))(*file_records)
+    check(lib.bsk_common_verdict_begin(op.ctx, arr, len(file_records)), op.ctx)
+
+
+def CommonVerdictGet(op, first, count):
+    """bsk_common_verdict_get: one byte per record of [first, first + count) of the first file, 1 = kept"""
+    buf = (C.c_uint8 * max(1, count))()
+    check(lib.bsk_common_verdict_get(op.ctx, first, count, buf), op.ctx)
+    return bytes(buf[:count])
+
+
+def CommonBucket(op, inputs, counts, lo_bin, hi_bin):
+    """bsk_common_bucket_begin / _add over the shards of every file of `inputs`, in order, the first file first / _finish:
+    (kept, flagged) of the bucket [lo_bin, hi_bin); `counts` is what CommonHistRun returned"""
+    _bucket_adds(lib.bsk_common_bucket_begin, lib.bsk_common_bucket_add, op, _union_frame(inputs), [k for c in counts for k in c], lo_bin, hi_bin)
+    kept, flagged = C.c_uint64(), C.c_uint64()
+    check(lib.bsk_common_bucket_finish(op.ctx, None, C.byref(kept), C.byref(flagged)), op.ctx)
+    return kept.value, flagged.value
+
+
+def CommonEmit(op, input, counts):
+    """bsk_common_emit_run over the shards of the FIRST file, in order (`counts`: the record count of each): the kept records, joined"""
+    chunks, first = [], 0
+    for (pid, ptr, n, on_dev, keep), cnt in zip(input.partitions(), counts):
+        out = _lib.Out()
+        check(lib.bsk_common_emit_run(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None, C.byref(out)), op.ctx)
+        chunks.append(_out_bytes(op, out))
+        first += cnt
+    return b"".join(chunks)
+
+
+def CommonBuckets(inputA, inputB, o=None, *inputN, budget_bytes=1 << 30, device=0):
+    """Common of files of any size on one device (PARITY COMB): the histogram of the fine bins of the key over the shards of all
+    files, the plan of buckets of at most `budget_bytes` of subjects, one collect sequence per bucket over all files, which ends
+    in the bucket's share of the keep bits of the first file, and one emit pass over the first file; the same bytes as Common.
+    The files are read once plus once per bucket, the first file once more.  An empty file gives an empty result."""
+    inputs = [inputA, inputB, *inputN]
+    with Operator("Common", (o or SeqKitCommonOptions()).to_json(), device) as op:
+        CommonHistReset(op)
+        counts = CommonHistRun(op, inputs)
+        bounds = ShufflePlan(CommonHistGet(op)[0], budget_bytes)
+        CommonVerdictBegin(op, [sum(c) for c in counts])
+        for lo, hi in zip(bounds[:-1], bounds[1:]):
+            CommonBucket(op, inputs, counts, lo, hi)
+        return CommonEmit(op, inputA, counts[0])
+
+
 def HeadGenome(input, o=None, device=0):
     """bigseqkit/head_genome.go:37-77 (PARITY HEADG): the records of the first genome.  ONE cut over the whole input: the
     shards go through one context in order, which carries the prefix words, n_1 and "cut reached" from shard to shard, and

@@ -1016,8 +1016,9 @@ static int run_record_op(bsk_ctx* c, Op want, const void* shard, size_t n, int o
     });
 }
 
-// ---- the bucket paths of shuffle, sort, rmdup and rename (include/bsk.h; the passes are in ops_host_shuffle.cpp,
-// ops_host_sortbuckets.cpp, ops_host_rmdupbuckets.cpp and ops_host_renamebuckets.cpp, the life cycle of a bucket in the first)
+// ---- the bucket paths of shuffle, sort, rmdup, rename and common (include/bsk.h; the passes are in ops_host_shuffle.cpp,
+// ops_host_sortbuckets.cpp, ops_host_rmdupbuckets.cpp, ops_host_renamebuckets.cpp and ops_host_commonbuckets.cpp, the life cycle
+// of a bucket in the first)
 static int bucket_ctx_check(bsk_ctx* c, Op op, const char* a_name, bool args_ok = true) {  // a_name: "a Sort", "an RmDup"
     if (!c) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: null context");
     if (c->op != op || !args_ok) return fail(c, BSK_ERR_INVALID_ARG, std::string("libbsk: not ") + a_name + " context");
@@ -1028,6 +1029,7 @@ static int shuffle_ctx_check(bsk_ctx* c) { return bucket_ctx_check(c, Op::Shuffl
 static int sort_ctx_check(bsk_ctx* c) { return bucket_ctx_check(c, Op::Sort, "a Sort"); }
 static int rmdup_ctx_check(bsk_ctx* c) { return bucket_ctx_check(c, Op::RmDup, "an RmDup"); }
 static int rename_ctx_check(bsk_ctx* c) { return bucket_ctx_check(c, Op::Rename, "a Rename"); }
+static int common_ctx_check(bsk_ctx* c) { return bucket_ctx_check(c, Op::Common, "a Common"); }
 static bool bins_ok(uint32_t lo_bin, uint32_t hi_bin_exclusive) { return lo_bin < hi_bin_exclusive && hi_bin_exclusive <= BUCKET_BINS; }
 // the prologue of a finish that fills a bsk_out
 static int bucket_finish_check(bsk_ctx* c, Op op, const char* a_name, bsk_out* out) {
@@ -1036,7 +1038,7 @@ static int bucket_finish_check(bsk_ctx* c, Op op, const char* a_name, bsk_out* o
     out->d_seg_src = nullptr; out->d_seg_off = nullptr; out->n_segments = 0;
     return BSK_OK;
 }
-// A pass of sort, rmdup or rename (whose buckets are c->rdb as well) over one shard: record_call, then pass(text, n, stream) through run_multiline -- a wrapped FASTQ shard
+// A pass of sort, rmdup, rename or common (the buckets of the last two are c->rdb as well) over one shard: record_call, then pass(text, n, stream) through run_multiline -- a wrapped FASTQ shard
 // runs once more as its 4-line rewrite, like bsk_sort_run's and bsk_rmdup_run's.  closes: an error closes the open bucket, here
 // and not in the pass, which the rewrite enters a second time.  The passes of shuffle differ in both: they go through
 // index_record_text, which has the multi-line reader inside, and shuffle_bucket_add closes its bucket itself.
@@ -1608,6 +1610,80 @@ int bsk_rename_emit_run(bsk_ctx* c, const void* shard, size_t n, int on_device, 
     if (rcc != BSK_OK) return rcc;
     return bucket_pass(c, out, Op::Rename, out != nullptr, false, shard, n, on_device, format, stream,
                        [&](const uint8_t* t, size_t m, hipStream_t st) { return rename_emit_device(c, t, m, format, first_record, st, out); });
+}
+
+// ---- common in buckets of the key: the histogram, the begin and the add of a bucket are rmdup's steps on a Common context,
+// over the shards of every file
+int bsk_common_hist_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                        void* stream, uint64_t* n_records) {
+    const int rcc = common_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    return bucket_pass(c, nullptr, Op::Common, true, false, shard, n, on_device, format, stream,
+                       [&](const uint8_t* t, size_t m, hipStream_t st) { return rdb_hist_device(c, t, m, format, st, n_records); });
+}
+
+int bsk_common_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) {
+    const int rcc = common_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    BSK_ENTER(c);
+    return bucket_hist_get(c, &c->rdb, bytes, records);
+}
+
+int bsk_common_hist_reset(bsk_ctx* c) {
+    const int rcc = common_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    BSK_ENTER(c);
+    return bucket_hist_reset(c, &c->rdb);
+}
+
+int bsk_common_verdict_begin(bsk_ctx* c, const uint64_t* file_records, uint32_t n_files) {
+    const int rcc = common_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    if (!file_records) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_common_verdict_begin: null argument");
+    if (n_files < 2 || n_files > 64)
+        return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_common_verdict_begin: " + std::to_string(n_files) + " files (2 .. 64 files are compared)");
+    BSK_ENTER(c);
+    return common_verdict_begin(c, file_records, n_files);
+}
+
+int bsk_common_verdict_get(bsk_ctx* c, uint64_t first, uint64_t count, uint8_t* kept) {
+    const int rcc = common_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    if (count && !kept) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_common_verdict_get: null argument");
+    BSK_ENTER(c);
+    return common_verdict_get(c, first, count, kept);
+}
+
+int bsk_common_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin_exclusive) {
+    const int rcc = common_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    if (!bins_ok(lo_bin, hi_bin_exclusive)) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_common_bucket_begin: the bins must be 0 <= lo < hi <= 4096");
+    BSK_ENTER(c);
+    return rdb_bucket_begin(c, lo_bin, hi_bin_exclusive);
+}
+
+int bsk_common_bucket_add(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                          void* stream) {
+    const int rcc = common_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    return bucket_pass(c, nullptr, Op::Common, true, true, shard, n, on_device, format, stream,
+                       [&](const uint8_t* t, size_t m, hipStream_t st) { return rdb_bucket_add(c, t, m, format, first_record, st); });
+}
+
+int bsk_common_bucket_finish(bsk_ctx* c, void* stream, uint64_t* n_kept, uint64_t* n_flagged) {
+    const int rcc = common_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    BSK_ENTER(c);
+    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), (hipStream_t)stream));
+    return common_bucket_finish(c, (hipStream_t)stream, n_kept, n_flagged);
+}
+
+int bsk_common_emit_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                        void* stream, bsk_out* out) {
+    const int rcc = common_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    return bucket_pass(c, out, Op::Common, out != nullptr, false, shard, n, on_device, format, stream,
+                       [&](const uint8_t* t, size_t m, hipStream_t st) { return common_emit_device(c, t, m, format, first_record, st, out); });
 }
 
 // ---- rmdup across ranks: the phases between which the caller runs the all-to-all exchanges (include/bsk.h)

@@ -453,6 +453,10 @@ struct bsk_ctx {
         uint32_t* d_ord = nullptr;
         uint64_t ord_cap = 0;            // in records
         uint64_t renamed = 0;            // non-zero ordinals written since the verdict began (the emit picks its kernel by it)
+        // common in buckets of the key (ops_host_commonbuckets.cpp; PARITY.md COMB), on a Common context: d_bits holds the KEEP
+        // bits of the records of the FIRST file only, total_records = the records of all files, and file_sums[f] = the records
+        // of the files 0 .. f (bsk_common_verdict_begin), so file_sums[0] records have a bit
+        std::vector<uint64_t> file_sums;
     } rdb;
 };
 

@@ -90,7 +90,7 @@ int rmdup_verdict_begin(bsk_ctx* c, uint64_t total_records);
 int rmdup_verdict_get(bsk_ctx* c, uint64_t first, uint64_t count, uint8_t* removed);
 int rmdup_bucket_finish(bsk_ctx* c, hipStream_t st, uint64_t* n_removed, uint64_t* n_flagged);
 int rmdup_emit_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st, bsk_out* out);
-// ... the steps that `rename` in buckets of the key shares with it, on an RmDup or a Rename context: the histogram without the
+// ... the steps that `rename` and `common` in buckets of the key share with it, on an RmDup, a Rename or a Common context: the histogram without the
 // refusal of rmdup's side files, the begin and the add of a bucket
 int rdb_hist_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, uint64_t* n_records);
 int rdb_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin);
@@ -100,6 +100,12 @@ int rename_verdict_begin(bsk_ctx* c, uint64_t total_records);
 int rename_verdict_get(bsk_ctx* c, uint64_t first, uint64_t count, uint32_t* ord);
 int rename_bucket_finish(bsk_ctx* c, hipStream_t st, uint64_t* n_renamed, uint64_t* n_flagged);
 int rename_emit_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st, bsk_out* out);
+// common in buckets of the key (ops_host_commonbuckets.cpp; include/bsk.h): the histogram, the begin and the add of a bucket are
+// the rdb_* steps above on a Common context
+int common_verdict_begin(bsk_ctx* c, const uint64_t* file_records, uint32_t n_files);
+int common_verdict_get(bsk_ctx* c, uint64_t first, uint64_t count, uint8_t* kept);
+int common_bucket_finish(bsk_ctx* c, hipStream_t st, uint64_t* n_kept, uint64_t* n_flagged);
+int common_emit_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st, bsk_out* out);
 void validate_head_genome_opts(bsk_ctx* c);
 void head_genome_reset(bsk_ctx* c);
 int head_genome_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, bsk_out* out);

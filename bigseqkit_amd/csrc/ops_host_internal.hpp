@@ -171,9 +171,10 @@ int bucket_require_open(bsk_ctx* c, const bsk_ctx::BucketState& B, const char* o
 int bucket_in_order(bsk_ctx* c, const bsk_ctx::BucketState& B, const char* op, uint64_t first_record);
 int bucket_too_many(bsk_ctx* c, const char* op);  // UNSUPPORTED: 2^32 or more records in one bucket of <op>
 inline void bucket_close(bsk_ctx::BucketState* B) { B->open = false; bucket_acc_clear(B); }
-// The steps of a bucket of `rmdup` that a bucket of `rename` takes as well (ops_host_rmdupbuckets.cpp; both on c->rdb, the
-// messages name the operator of the context -- rdb_op_name: "rmdup" / "rename"):
-//   rdb_params          the subject of a record: rmdup's options, or for rename the ID / the whole header (ByName) as it stands
+// The steps of a bucket of `rmdup` that a bucket of `rename` and one of `common` take as well (ops_host_rmdupbuckets.cpp; all on
+// c->rdb, the messages name the operator of the context -- rdb_op_name: "rmdup" / "rename" / "common"):
+//   rdb_params          the subject of a record: rmdup's options (common's are the same three), or for rename the ID / the whole
+//                 header (ByName) as it stands
 //   rdb_group_keys      the open bucket (B.n > 0): first[i] = the lowest accumulated index under the key of record i, at *o_first
 //                 of the arena *A (carved and reserved there; more may be taken behind it with arena_reserve_keep); c->d_xflag
 //                 holds RDB_FLAG_MAX + 1 words, the count in front zeroed

@@ -4,7 +4,8 @@
 // with the tail of rmdup_dist_emit.
 // `rename` in buckets of the key (ops_host_renamebuckets.cpp; PARITY.md RENB) groups by the same subject under the same key: the
 // steps down to first[] -- rdb_hist_device, rdb_bucket_begin, rdb_bucket_add, rdb_group_keys -- and rdb_flagged_texts serve both
-// operators on c->rdb (declared in ops_host_internal.hpp); their messages name the operator of the context.
+// operators on c->rdb (declared in ops_host_internal.hpp); their messages name the operator of the context.  `common` in buckets
+// of the key (ops_host_commonbuckets.cpp; PARITY.md COMB) takes the same steps over the union of its files.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -33,11 +34,11 @@ struct RdbShard {
     TextTableH tt;
     RmDupParams P;
 };
-const char* rdb_op_name(const bsk_ctx* c) { return c->op == Op::Rename ? "rename" : "rmdup"; }
+const char* rdb_op_name(const bsk_ctx* c) { return c->op == Op::Rename ? "rename" : c->op == Op::Common ? "common" : "rmdup"; }
 static std::string rdb_fn(const bsk_ctx* c, const char* fn) { return std::string("bsk_") + rdb_op_name(c) + "_" + fn; }
 RmDupParams rdb_params(bsk_ctx* c, const uint8_t* d_buf, size_t n, bool fastq) {
     const Options& o = c->opts;
-    const bool rmdup = c->op == Op::RmDup;  // (rename: the ID, or the whole header with ByName, as it stands)
+    const bool rmdup = c->op == Op::RmDup || c->op == Op::Common;  // (common has rmdup's three options; rename: the ID, or the whole header with ByName, as it stands)
     RmDupParams P;
     memset(&P, 0, sizeof P);
     P.fastq = fastq;

@@ -706,12 +706,13 @@ static size_t whole_file_limit() {
     return lim;
 }
 
-// BSK_SHUFFLE_BUDGET_BYTES / BSK_SORT_BUDGET_BYTES / BSK_RMDUP_BUDGET_BYTES / BSK_RENAME_BUDGET_BYTES: the bytes a bucket of
-// `shuffle` / `sort` / `rmdup` / `rename` may hold (run_buckets; rmdup, rename: bytes of subjects and their per-record words, not
-// of record text); 0: unset
+// BSK_SHUFFLE_BUDGET_BYTES / BSK_SORT_BUDGET_BYTES / BSK_RMDUP_BUDGET_BYTES / BSK_RENAME_BUDGET_BYTES / BSK_COMMON_BUDGET_BYTES: the
+// bytes a bucket of `shuffle` / `sort` / `rmdup` / `rename` / `common` may hold (run_buckets; rmdup, rename, common: bytes of
+// subjects and their per-record words, not of record text); 0: unset
 static uint64_t bucket_budget(const std::string& use) {
     const char* e = use == "shuffle" ? getenv("BSK_SHUFFLE_BUDGET_BYTES") : use == "sort" ? getenv("BSK_SORT_BUDGET_BYTES")
-                  : use == "rmdup" ? getenv("BSK_RMDUP_BUDGET_BYTES") : use == "rename" ? getenv("BSK_RENAME_BUDGET_BYTES") : nullptr;
+                  : use == "rmdup" ? getenv("BSK_RMDUP_BUDGET_BYTES") : use == "rename" ? getenv("BSK_RENAME_BUDGET_BYTES")
+                  : use == "common" ? getenv("BSK_COMMON_BUDGET_BYTES") : nullptr;
     return e ? (uint64_t)strtoull(e, nullptr, 10) : 0;
 }
 bool g_buckets_unfit = false;  // read_parts: the whole-file load of a `shuffle` / `sort` / `rmdup` / `rename` input failed and a budget is set
@@ -1024,10 +1025,10 @@ Output run_head_genome(const Invocation& inv) {
     return res;
 }
 
-// shuffle in buckets of the draw, sort, rmdup and rename in buckets of the key (include/bsk.h; PARITY.md SHUF, SORT, RMDUPB, RENB):
-// the way of the four commands for an input that is larger than the byte budget of a bucket (BSK_SHUFFLE_BUDGET_BYTES,
-// BSK_SORT_BUDGET_BYTES, BSK_RMDUP_BUDGET_BYTES, BSK_RENAME_BUDGET_BYTES) or that could
-// not be loaded whole.  The files stay on the host, mapped; several files are unioned in order (cli/shuffle.go:11-15,
+// shuffle in buckets of the draw, sort, rmdup, rename and common in buckets of the key (include/bsk.h; PARITY.md SHUF, SORT,
+// RMDUPB, RENB, COMB): the way of the five commands for an input that is larger than the byte budget of a bucket
+// (BSK_SHUFFLE_BUDGET_BYTES, BSK_SORT_BUDGET_BYTES, BSK_RMDUP_BUDGET_BYTES, BSK_RENAME_BUDGET_BYTES, BSK_COMMON_BUDGET_BYTES) or
+// -- the first four -- that could not be loaded whole.  The files stay on the host, mapped; several files are unioned in order (cli/shuffle.go:11-15,
 // cli/sort.go), the record index runs over all of them.  Record-aligned pieces (BSK_STREAM_PIECE_BYTES, default 1 GiB) go
 // through ONE context.  The mapping, the piece list, the plan and the timing line are shared; the passes differ:
 //   shuffle   once for the histogram of the draws -- each piece's first record index is remembered -- and then once per bucket
@@ -1040,21 +1041,25 @@ Output run_head_genome(const Invocation& inv) {
 //             and ends in its share of the verdict, it prints nothing -- and once for the emit, whose piece outputs are
 //             appended to the result: 2 + B times.  -d / -D are refused by the histogram pass.
 //   rename    the passes of rmdup; a bucket ends in its share of the ordinals, and the emit prints every record, renamed
+//   common    the passes of rmdup over the pieces of ALL files (at least two, of one format), which are not a union to print but the
+//             sets to compare: the histogram pass leaves the record count of every file, a bucket ends in its share of the keep
+//             bits of the FIRST file, and the emit runs over the pieces of the first file only: 1 + B times, the first file once more
 // Every finished bucket is appended to the output.  A piece never spans two files, so a file that ends without a newline
 // behaves like the union of the whole-file path: its last record gets the newline.
 Output run_buckets(const Invocation& inv) {
     const std::string use = inv.cmd->use;
-    const bool sort = use == "sort", rmdup = use == "rmdup", rename = use == "rename";
+    const bool sort = use == "sort", rmdup = use == "rmdup", rename = use == "rename", common = use == "common";
+    if (common && inv.files.size() < 2) die("at least 2 files needed");  // cli/common.go
     const int device = (int)strtol(inv.pget("device").c_str(), nullptr, 10);
     const uint64_t budget = bucket_budget(use);
-    constexpr uint32_t kBins = 4096;  // the fine bins of all four (include/bsk.h)
+    constexpr uint32_t kBins = 4096;  // the fine bins of all five (include/bsk.h)
     Output res;
     bsk_ctx* ctx = nullptr;
     if (bsk_create(inv.cmd->op, inv.js.c_str(), device, &ctx) != BSK_OK) die(bsk_global_error());
     const bool timing = getenv("BSK_CLI_TIMING") != nullptr;
     if (timing) bsk_profile_enable(ctx, 1);
     struct File { std::string whole; const uint8_t* text = nullptr; size_t size = 0; bool mapped = false; };
-    struct Piece { const uint8_t* p; size_t n; uint64_t first; };
+    struct Piece { const uint8_t* p; size_t n; uint64_t first; size_t file; uint64_t count; };
     std::vector<File> files(inv.files.size());
     std::vector<Piece> pieces;
     const char* pinned = getenv("BSK_STREAM_PIECE_BYTES");
@@ -1090,12 +1095,12 @@ Output run_buckets(const Invocation& inv) {
                 size_t at = 0;
                 if (bsk_find_record_start(f.text, f.size, lo + piece, fmt, &at) == BSK_OK && at > lo && at < f.size) hi = at;
             }
-            pieces.push_back({f.text + lo, hi - lo, 0});
+            pieces.push_back({f.text + lo, hi - lo, 0, fi, 0});
             lo = hi;
         }
     }
     res.fmt = fmt < 0 ? BSK_FORMAT_FASTA : fmt;
-    // the entry points of the passes that the four commands share, and what their timing marks say
+    // the entry points of the passes that the five commands share, and what their timing marks say
     struct Entry {
         decltype(&bsk_shuffle_hist_run) hist_run;
         decltype(&bsk_shuffle_hist_get) hist_get;
@@ -1106,6 +1111,7 @@ Output run_buckets(const Invocation& inv) {
     const Entry E = sort    ? Entry{bsk_sort_hist_run, bsk_sort_hist_get, bsk_sort_bucket_begin, bsk_sort_bucket_add, "sort: histogram of the bins", "sort: buckets"}
                     : rmdup ? Entry{bsk_rmdup_hist_run, bsk_rmdup_hist_get, bsk_rmdup_bucket_begin, bsk_rmdup_bucket_add, "rmdup: histogram of the bins", "rmdup: buckets"}
                     : rename ? Entry{bsk_rename_hist_run, bsk_rename_hist_get, bsk_rename_bucket_begin, bsk_rename_bucket_add, "rename: histogram of the bins", "rename: buckets"}
+                    : common ? Entry{bsk_common_hist_run, bsk_common_hist_get, bsk_common_bucket_begin, bsk_common_bucket_add, "common: histogram of the bins", "common: buckets"}
                             : Entry{bsk_shuffle_hist_run, bsk_shuffle_hist_get, bsk_shuffle_bucket_begin, bsk_shuffle_bucket_add, "shuffle: histogram of the draws", "shuffle: buckets"};
     // the pass over all pieces that counts the records: it leaves every piece's first record index
     uint64_t last_count = 0;  // the records of the last piece
@@ -1117,6 +1123,7 @@ Output run_buckets(const Invocation& inv) {
             pc.first = g;
             if (call(pc, k++, g, &cnt) != BSK_OK) die(bsk_last_error(ctx));
             g += cnt;
+            pc.count = cnt;
             last_count = cnt;
         }
     };
@@ -1157,10 +1164,33 @@ Output run_buckets(const Invocation& inv) {
         if (sort) msg += " -- sort: a fine bin holds the records between two splitter keys; many equal keys, or a run that the sample missed, fill one";
         if (rmdup) msg += " -- rmdup: a fine bin holds the subjects whose key shares its upper 12 bits; the copies of one subject fill one";
         if (rename) msg += " -- rename: a fine bin holds the IDs (-n: the names) whose key shares its upper 12 bits, once per record; the records of one ID fill one";
+        if (common) msg += " -- common: a fine bin holds the subjects of all files whose key shares its upper 12 bits, once per record; the copies of one subject fill one";
         die(msg);
     }
-    uint64_t removed = 0, flagged = 0;  // (rename: renamed)
-    if (rmdup || rename) {
+    uint64_t removed = 0, flagged = 0;  // (rename: renamed; common: kept)
+    if (common) {
+        // every bucket over the pieces of all files, in order, ends in its share of the keep bits of the first file; one emit pass
+        // over the pieces of the first file prints its kept records in file order
+        std::vector<uint64_t> file_records(files.size(), 0);
+        for (auto& pc : pieces) file_records[pc.file] += pc.count;
+        if (bsk_common_verdict_begin(ctx, file_records.data(), (uint32_t)file_records.size()) != BSK_OK) die(bsk_last_error(ctx));
+        for (int b = 0; b < n_buckets; ++b) {
+            fill_bucket((uint32_t)bounds[b], (uint32_t)bounds[b + 1]);
+            uint64_t r = 0, f = 0;
+            if (bsk_common_bucket_finish(ctx, nullptr, &r, &f) != BSK_OK) die(bsk_last_error(ctx));
+            removed += r;
+            flagged += f;
+        }
+        mark(E.mark_buckets);
+        int64_t k = 0;
+        for (auto& pc : pieces) {
+            if (pc.file != 0) break;
+            bsk_out out;
+            if (bsk_common_emit_run(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr, &out) != BSK_OK) die(bsk_last_error(ctx));
+            append_out(out);
+        }
+        mark("common: emit");
+    } else if (rmdup || rename) {
         // every bucket over all pieces, in order, ends in its share of the verdict; one emit pass prints the survivors (rename:
         // every record under its new name) in file order
         const uint64_t total_records = pieces.empty() ? 0 : pieces.back().first + last_count;
@@ -1202,6 +1232,9 @@ Output run_buckets(const Invocation& inv) {
                     (unsigned long long)removed, (unsigned long long)flagged);
         if (rename)
             fprintf(stderr, "[timing] rename: %llu record(s) renamed, %llu flagged (subject differed from the first of its key group)\n",
+                    (unsigned long long)removed, (unsigned long long)flagged);
+        if (common)
+            fprintf(stderr, "[timing] common: %llu record(s) kept, %llu flagged (subject differed from the first of its key group)\n",
                     (unsigned long long)removed, (unsigned long long)flagged);
     }
     for (auto& f : files)
@@ -1621,7 +1654,7 @@ static int run_main(int argc, char** argv) {
         store(inv, o, inv.files);
         return 0;
     }
-    if (bucket_budget(use_cmd) > 0) {  // (shuffle, sort, rmdup, rename)
+    if (bucket_budget(use_cmd) > 0) {  // (shuffle, sort, rmdup, rename, common)
         // more bytes than a bucket may hold: not loaded whole (a pipe has no size: it takes the whole-file path)
         uint64_t total = 0;
         struct stat sb;

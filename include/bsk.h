@@ -549,6 +549,48 @@ int bsk_rename_bucket_finish(bsk_ctx* ctx, void* stream, uint64_t* n_renamed, ui
 int bsk_rename_emit_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                         void* stream, bsk_out* out);
 
+/* ---- Common in buckets of the key: the bytes of bsk_common_run for files of any size on one device (PARITY.md COMB).  The
+ * files are unioned in command order, g is the global record index over the union, and file_records[f] the number of records
+ * of file f.  The subject of a record is its ID, its whole header with ByName or its sequence with BySeq, lower-cased with
+ * IgnoreCase; record g is kept iff it lies in the FIRST file, no record g' < g has the same subject bytes, and every file
+ * holds a record with those bytes.  The fine bin, the cost of a bin, the accumulation of SUBJECTS and the key grouping are
+ * those of the RmDup buckets above -- the histogram of a Common context over the union equals that of an RmDup context with
+ * the same three options.  The verdict is one KEEP bit per record of the first file only, (file_records[0] + 31) / 32 + 1
+ * words of device memory OUTSIDE the budget of the buckets.  The files are read once for the histogram, once per bucket, and
+ * the first file once more for the emit.  Records whose subject differs from the first of their key group ("flagged") are
+ * settled exactly on the host, grouped by text.
+ *   bsk_common_hist_run / _hist_get / _hist_reset      as bsk_rmdup_hist_*, over the shards of every file; bsk_shuffle_plan is
+ *                             the plan
+ *   bsk_common_verdict_begin  zeroed keep bits for the records of the first file and no bin decided; n_files outside 2 .. 64
+ *                             and a null array are BSK_ERR_INVALID_ARG
+ *   bsk_common_verdict_get    kept[j] = 1 when record first + j of the first file is kept, j < count; reaching past
+ *                             file_records[0] is BSK_ERR_INVALID_ARG
+ *   bsk_common_bucket_begin / _add / _finish
+ *                             as bsk_rmdup_bucket_*, with the same refusals; add receives every shard of EVERY file in input
+ *                             order, the first file first, under its global first_record -- one that goes backwards, and a
+ *                             shard that reaches past the sum of file_records, are BSK_ERR_INVALID_ARG.  finish sets the keep
+ *                             bits of the bucket's subjects: *n_kept = their number, *n_flagged = the records whose subject
+ *                             differed from the first of their key group (more than 2^20 of them in one bucket fail the call)
+ *   bsk_common_emit_run       the kept records of a shard of the FIRST file, in order, each as Format(LineWidth), as one block
+ *                             valid until the next call on the context; a shard that reaches past file_records[0] and an
+ *                             undecided bin (the message names the first) are BSK_ERR_INVALID_ARG.  out=slices is
+ *                             BSK_ERR_UNSUPPORTED here
+ * Every one of them is BSK_ERR_INVALID_ARG, "not a Common context", on a context of another operator; the bsk_rmdup_* and
+ * bsk_rename_* entry points refuse a Common context likewise.  bsk_common_run still runs on a context that has been through
+ * the buckets. */
+int bsk_common_hist_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                        void* stream, uint64_t* n_records);
+int bsk_common_hist_get(bsk_ctx* ctx, uint64_t* bytes, uint64_t* records);
+int bsk_common_hist_reset(bsk_ctx* ctx);
+int bsk_common_verdict_begin(bsk_ctx* ctx, const uint64_t* file_records, uint32_t n_files);
+int bsk_common_verdict_get(bsk_ctx* ctx, uint64_t first, uint64_t count, uint8_t* kept);
+int bsk_common_bucket_begin(bsk_ctx* ctx, uint32_t lo_bin, uint32_t hi_bin_exclusive);
+int bsk_common_bucket_add(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                          void* stream);
+int bsk_common_bucket_finish(bsk_ctx* ctx, void* stream, uint64_t* n_kept, uint64_t* n_flagged);
+int bsk_common_emit_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                        void* stream, bsk_out* out);
+
 /* ---- HeadGenome (bigseqkit/head_genome.go, bigseqkit-lib/head_genome.go:53-108; options {"MiniCommonWords": 1}; PARITY.md
  * HEADG): the records of the first genome.  The words of a record are the maximal runs of its description other than ' '
  * and '\t'; the prefix is the words of the first record of the input; n_i = leading words of record i equal to the prefix's.
