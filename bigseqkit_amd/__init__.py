@@ -16,4 +16,6 @@ from .api import (SeqFrame, ReadFASTA, ReadFASTAN, ReadFASTQ, ReadFASTQN, Operat
                   SortSplittersSet, SortSplittersGet, SortHistRun, SortHistGet, SortHistReset,
                   RmDupBuckets, RmDupHistRun, RmDupHistGet, RmDupHistReset, RmDupVerdictBegin, RmDupVerdictGet, RmDupBucket, RmDupEmit,
                   RenameBuckets, RenameHistRun, RenameHistGet, RenameHistReset, RenameVerdictBegin, RenameVerdictGet, RenameBucket, RenameEmit,
-                  CommonBuckets, CommonHistRun, CommonHistGet, CommonHistReset, CommonVerdictBegin, CommonVerdictGet, CommonBucket, CommonEmit)
+                  CommonBuckets, CommonHistRun, CommonHistGet, CommonHistReset, CommonVerdictBegin, CommonVerdictGet, CommonBucket, CommonEmit,
+                  PairBuckets, PairHistRun, PairHistGet, PairHistReset, PairVerdictBegin, PairVerdictGet, PairBucket, PairOrderBegin, PairEmit,
+                  PairOrderHistRun, PairOrderHistGet, PairOrderBucket)

@@ -185,7 +185,22 @@ SIGNATURES = {
     "bsk_common_bucket_add": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp]),
     "bsk_common_bucket_finish": (_i, [_vp, _vp, _p(C.c_uint64), _p(C.c_uint64)]),
     "bsk_common_emit_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp, _p(Out)]),
-    "bsk_head_genome_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, _vp, _p(Out)]),
+    "bsk_pair_hist_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp, _p(C.c_uint64)]),
+    "bsk_pair_hist_get": (_i, [_vp, _p(C.c_uint64), _p(C.c_uint64)]),
+    "bsk_pair_hist_reset": (_i, [_vp]),
+    "bsk_pair_verdict_begin": (_i, [_vp, _p(C.c_uint64)]),
+    "bsk_pair_verdict_get": (_i, [_vp, C.c_uint64, C.c_uint64, _p(C.c_uint64)]),
+    "bsk_pair_bucket_begin": (_i, [_vp, C.c_uint32, C.c_uint32]),
+    "bsk_pair_bucket_add": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp]),
+    "bsk_pair_bucket_finish": (_i, [_vp, _vp, _p(C.c_uint64), _p(C.c_uint64)]),
+    "bsk_pair_order_begin": (_i, [_vp, _vp, _p(C.c_uint64), _p(C.c_int)]),
+    "bsk_pair_emit_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp, _p(Out)]),
+    "bsk_pair_order_hist_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp, _p(C.c_uint64)]),
+    "bsk_pair_order_hist_get": (_i, [_vp, _p(C.c_uint64), _p(C.c_uint64)]),
+    "bsk_pair_order_bucket_begin": (_i, [_vp, C.c_uint32, C.c_uint32]),
+    "bsk_pair_order_bucket_add": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp]),
+    "bsk_pair_order_bucket_finish": (_i, [_vp, _vp, _p(Out)]),
+    "bsk_head_genome_run":(_i, [_vp, _vp, _sz, _i, _i, _i64, _vp, _p(Out)]),
     "bsk_head_genome_reset": (_i, [_vp]),
     "bsk_head_genome_state": (_i, [_vp, _p(C.c_int), _p(C.c_uint64)]),
     "bsk_range_needs_count": (_i, [_vp, _p(C.c_int)]),

@@ -830,6 +830,126 @@ def CommonBuckets(inputA, inputB, o=None, *inputN, budget_bytes=1 << 30, device=
         return CommonEmit(op, inputA, counts[0])
 
 
+def _pair_frames(inputA, inputB):
+    if inputA.format != inputB.format:
+        raise ValueError("pair: inputs of different formats")
+    return [inputA, inputB]
+
+
+def PairHistRun(op, inputs):
+    """bsk_pair_hist_run over the shards of file 1, then file 2: per file, the record count of every shard (the histogram
+    accumulates in the operator's context)"""
+    flat = _count_pass(lib.bsk_pair_hist_run, op, _union_frame(inputs))
+    na = len(inputs[0].shards)
+    return [flat[:na], flat[na:]]
+
+
+def PairHistGet(op):
+    """bsk_pair_hist_get: (bytes[4096], records[4096])"""
+    return _hist_get(lib.bsk_pair_hist_get, op)
+
+
+def PairHistReset(op):
+    check(lib.bsk_pair_hist_reset(op.ctx), op.ctx)
+
+
+def PairVerdictBegin(op, file_records):
+    """bsk_pair_verdict_begin: zeroed paired bits for the records of both files, no bin decided; file_records = [n1, n2]"""
+    arr = (C.c_uint64 * 2)(*file_records)
+    check(lib.bsk_pair_verdict_begin(op.ctx, arr), op.ctx)
+
+
+def PairVerdictGet(op, first, count):
+    """bsk_pair_verdict_get: pos of the global records [first, first + count) after PairOrderBegin; None = unpaired"""
+    buf = (C.c_uint64 * max(1, count))()
+    check(lib.bsk_pair_verdict_get(op.ctx, first, count, buf), op.ctx)
+    return [None if v == 0xFFFFFFFFFFFFFFFF else v for v in buf[:count]]
+
+
+def PairBucket(op, inputs, counts, lo_bin, hi_bin):
+    """bsk_pair_bucket_begin / _add over the shards of file 1, then file 2 / _finish: (pairs, flagged) of the match bucket
+    [lo_bin, hi_bin); `counts` is what PairHistRun returned"""
+    _bucket_adds(lib.bsk_pair_bucket_begin, lib.bsk_pair_bucket_add, op, _union_frame(inputs), [k for c in counts for k in c], lo_bin, hi_bin)
+    pairs, flagged = C.c_uint64(), C.c_uint64()
+    check(lib.bsk_pair_bucket_finish(op.ctx, None, C.byref(pairs), C.byref(flagged)), op.ctx)
+    return pairs.value, flagged.value
+
+
+def PairOrderBegin(op):
+    """bsk_pair_order_begin, the rank step: (P, file 2 is in mate order)"""
+    pairs, ordered = C.c_uint64(), C.c_int()
+    check(lib.bsk_pair_order_begin(op.ctx, None, C.byref(pairs), C.byref(ordered)), op.ctx)
+    return pairs.value, bool(ordered.value)
+
+
+def PairEmit(op, input, counts, first):
+    """bsk_pair_emit_run over the shards of ONE file, in order, the first of them global record `first` (`counts`: the record
+    count of each): the three outputs of the entry point, each joined over the shards"""
+    chunks = ([], [], [])
+    for (pid, ptr, n, on_dev, keep), cnt in zip(input.partitions(), counts):
+        outs = (_lib.Out * 3)()
+        check(lib.bsk_pair_emit_run(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None, outs), op.ctx)
+        for k in range(3):
+            chunks[k].append(_out_bytes(op, outs[k]))
+        first += cnt
+    return tuple(b"".join(c) for c in chunks)
+
+
+def PairOrderHistRun(op, input, counts, first):
+    """bsk_pair_order_hist_run over the shards of file 2, in order, the first of them global record `first`"""
+    for (pid, ptr, n, on_dev, keep), cnt in zip(input.partitions(), counts):
+        k = C.c_uint64()
+        check(lib.bsk_pair_order_hist_run(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None, C.byref(k)), op.ctx)
+        first += cnt
+
+
+def PairOrderHistGet(op):
+    """bsk_pair_order_hist_get: (bytes[4096], records[4096]) of the order bins"""
+    return _hist_get(lib.bsk_pair_order_hist_get, op)
+
+
+def PairOrderBucket(op, input, counts, first, lo_bin, hi_bin):
+    """bsk_pair_order_bucket_begin / _add over the shards of file 2 / _finish: the share of paired.2 of the order bucket
+    [lo_bin, hi_bin)"""
+    check(lib.bsk_pair_order_bucket_begin(op.ctx, lo_bin, hi_bin), op.ctx)
+    for (pid, ptr, n, on_dev, keep), cnt in zip(input.partitions(), counts):
+        check(lib.bsk_pair_order_bucket_add(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None), op.ctx)
+        first += cnt
+    out = _lib.Out()
+    check(lib.bsk_pair_order_bucket_finish(op.ctx, None, C.byref(out)), op.ctx)
+    return _out_bytes(op, out)
+
+
+def PairBuckets(inputA, inputB, o=None, budget_bytes=1 << 30, device=0, order="auto"):
+    """Pair of two files of any size on one device (PARITY PAIRB) -> (paired.1, paired.2, unpaired.1, unpaired.2), the same
+    bytes as Pair.  The match phase: the histogram of the fine bins of the key over both files, the plan of buckets of at most
+    `budget_bytes` of subjects, one collect sequence per bucket, which ends in the bucket's share of the paired bits and the
+    mates.  Then the rank step and one emit pass over either file.  When file 2 is not in the order of its mates -- or with
+    order="buckets" -- paired.2 comes from the order phase: the histogram of the positions over file 2, the plan under the
+    same budget, one collect sequence per bucket."""
+    if order not in ("auto", "buckets"):
+        raise ValueError("PairBuckets: order is 'auto' or 'buckets'")
+    inputs = _pair_frames(inputA, inputB)
+    with Operator("Pair", (o or SeqKitPairOptions()).to_json(), device) as op:
+        if order == "buckets":
+            check(lib.bsk_ctx_set(op.ctx, b"pair_order", b"buckets"), op.ctx)
+        PairHistReset(op)
+        counts = PairHistRun(op, inputs)
+        bounds = ShufflePlan(PairHistGet(op)[0], budget_bytes)
+        n1 = sum(counts[0])
+        PairVerdictBegin(op, [n1, sum(counts[1])])
+        for lo, hi in zip(bounds[:-1], bounds[1:]):
+            PairBucket(op, inputs, counts, lo, hi)
+        pairs, ordered = PairOrderBegin(op)
+        paired1, unpaired1, _ = PairEmit(op, inputA, counts[0], 0)
+        _, unpaired2, paired2 = PairEmit(op, inputB, counts[1], n1)
+        if pairs and (order == "buckets" or not ordered):
+            PairOrderHistRun(op, inputB, counts[1], n1)
+            obounds = ShufflePlan(PairOrderHistGet(op)[0], budget_bytes)
+            paired2 = b"".join(PairOrderBucket(op, inputB, counts[1], n1, lo, hi) for lo, hi in zip(obounds[:-1], obounds[1:]))
+        return paired1, paired2, unpaired1, unpaired2
+
+
 def HeadGenome(input, o=None, device=0):
     """bigseqkit/head_genome.go:37-77 (PARITY HEADG): the records of the first genome.  ONE cut over the whole input: the
     shards go through one context in order, which carries the prefix words, n_1 and "cut reached" from shard to shard, and

@@ -19,7 +19,7 @@ struct BinBytes { uint32_t bin; unsigned long long bytes; };
 
 // bytes and records per fine bin, privatised per block: 4096 x (u64 + u32) = 48 KiB of LDS, merged with one global atomic per
 // counter and non-empty bin.  A block walks many records (grid-stride) so that the zeroing and the merge of its 48 KiB are
-// paid once.  of(i) = BinBytes of record i, bin < BUCKET_BINS.
+// paid once.  of(i) = BinBytes of record i; bin = BUCKET_BINS: the record is not counted.
 template <class F>
 __device__ __forceinline__ void bucket_hist(uint64_t n, unsigned long long* __restrict__ g_bytes, unsigned long long* __restrict__ g_records,
                                             F of) {
@@ -30,6 +30,7 @@ __device__ __forceinline__ void bucket_hist(uint64_t n, unsigned long long* __re
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const BinBytes r = of(i);
+        if (r.bin >= BUCKET_BINS) continue;  // (a record that counts nowhere: the unpaired ones of pair's order histogram)
         atomicAdd(&s_bytes[r.bin], r.bytes);
         atomicAdd(&s_records[r.bin], 1u);
     }

@@ -377,6 +377,9 @@ void bsk_destroy(bsk_ctx* c) {
         for (void* p : {(void*)c->rdb.d_hist, (void*)c->rdb.d_acc, (void*)c->rdb.d_draw, (void*)c->rdb.d_off, (void*)c->rdb.d_len,
                         (void*)c->rdb.d_key, (void*)c->rdb.d_bits, (void*)c->rdb.d_ord})
             if (p) hipFree(p);
+        for (void* p : {(void*)c->pab.order.d_hist, (void*)c->pab.order.d_acc, (void*)c->pab.order.d_draw, (void*)c->pab.order.d_off,
+                        (void*)c->pab.order.d_len, (void*)c->pab.d_mates, (void*)c->pab.d_wpre, (void*)c->pab.d_cnt, (void*)c->pab.d_base})
+            if (p) hipFree(p);
         if (c->d_vm_progs) hipFree(c->d_vm_progs);
         if (c->d_id_off) hipFree(c->d_id_off);
         if (c->d_id_len) hipFree(c->d_id_len);
@@ -1030,6 +1033,7 @@ static int sort_ctx_check(bsk_ctx* c) { return bucket_ctx_check(c, Op::Sort, "a 
 static int rmdup_ctx_check(bsk_ctx* c) { return bucket_ctx_check(c, Op::RmDup, "an RmDup"); }
 static int rename_ctx_check(bsk_ctx* c) { return bucket_ctx_check(c, Op::Rename, "a Rename"); }
 static int common_ctx_check(bsk_ctx* c) { return bucket_ctx_check(c, Op::Common, "a Common"); }
+static int pair_ctx_check(bsk_ctx* c) { return bucket_ctx_check(c, Op::Pair, "a Pair"); }
 static bool bins_ok(uint32_t lo_bin, uint32_t hi_bin_exclusive) { return lo_bin < hi_bin_exclusive && hi_bin_exclusive <= BUCKET_BINS; }
 // the prologue of a finish that fills a bsk_out
 static int bucket_finish_check(bsk_ctx* c, Op op, const char* a_name, bsk_out* out) {
@@ -1684,6 +1688,133 @@ int bsk_common_emit_run(bsk_ctx* c, const void* shard, size_t n, int on_device, 
     if (rcc != BSK_OK) return rcc;
     return bucket_pass(c, out, Op::Common, out != nullptr, false, shard, n, on_device, format, stream,
                        [&](const uint8_t* t, size_t m, hipStream_t st) { return common_emit_device(c, t, m, format, first_record, st, out); });
+}
+
+// ---- pair in buckets of the key (ops_host_pairbuckets.cpp): the match phase takes rmdup's steps on a Pair context over file 1
+// followed by file 2; the order phase has a bucket state of its own (c->pab.order), which its add closes when it fails for good
+int bsk_pair_hist_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                      void* stream, uint64_t* n_records) {
+    const int rcc = pair_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    return bucket_pass(c, nullptr, Op::Pair, true, false, shard, n, on_device, format, stream,
+                       [&](const uint8_t* t, size_t m, hipStream_t st) { return rdb_hist_device(c, t, m, format, st, n_records); });
+}
+
+int bsk_pair_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) {
+    const int rcc = pair_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    BSK_ENTER(c);
+    return bucket_hist_get(c, &c->rdb, bytes, records);
+}
+
+int bsk_pair_hist_reset(bsk_ctx* c) {
+    const int rcc = pair_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    BSK_ENTER(c);
+    return bucket_hist_reset(c, &c->rdb);
+}
+
+int bsk_pair_verdict_begin(bsk_ctx* c, const uint64_t* file_records) {
+    const int rcc = pair_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    if (!file_records) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_pair_verdict_begin: null argument");
+    BSK_ENTER(c);
+    return pair_verdict_begin(c, file_records);
+}
+
+int bsk_pair_verdict_get(bsk_ctx* c, uint64_t first, uint64_t count, uint64_t* pos) {
+    const int rcc = pair_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    if (count && !pos) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_pair_verdict_get: null argument");
+    BSK_ENTER(c);
+    return pair_verdict_get(c, first, count, pos);
+}
+
+int bsk_pair_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin_exclusive) {
+    const int rcc = pair_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    if (!bins_ok(lo_bin, hi_bin_exclusive)) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_pair_bucket_begin: the bins must be 0 <= lo < hi <= 4096");
+    BSK_ENTER(c);
+    return pair_bucket_begin(c, lo_bin, hi_bin_exclusive);
+}
+
+int bsk_pair_bucket_add(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                        void* stream) {
+    const int rcc = pair_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    return bucket_pass(c, nullptr, Op::Pair, true, true, shard, n, on_device, format, stream,
+                       [&](const uint8_t* t, size_t m, hipStream_t st) { return pair_bucket_add(c, t, m, format, first_record, st); });
+}
+
+int bsk_pair_bucket_finish(bsk_ctx* c, void* stream, uint64_t* n_pairs, uint64_t* n_flagged) {
+    const int rcc = pair_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    BSK_ENTER(c);
+    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), (hipStream_t)stream));
+    return pair_bucket_finish(c, (hipStream_t)stream, n_pairs, n_flagged);
+}
+
+int bsk_pair_order_begin(bsk_ctx* c, void* stream, uint64_t* n_pairs, int* in_mate_order) {
+    const int rcc = pair_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    BSK_ENTER(c);
+    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), (hipStream_t)stream));
+    return pair_order_begin(c, (hipStream_t)stream, n_pairs, in_mate_order);
+}
+
+int bsk_pair_emit_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                      void* stream, bsk_out* outs) {
+    const int rcc = pair_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    if (outs) for (int k = 0; k < 3; ++k) { outs[k].d_seg_src = nullptr; outs[k].d_seg_off = nullptr; outs[k].n_segments = 0; }
+    return bucket_pass(c, nullptr, Op::Pair, outs != nullptr, false, shard, n, on_device, format, stream,
+                       [&](const uint8_t* t, size_t m, hipStream_t st) { return pair_emit_device(c, t, m, format, first_record, st, outs); });
+}
+
+int bsk_pair_order_hist_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                            void* stream, uint64_t* n_records) {
+    const int rcc = pair_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    return bucket_pass(c, nullptr, Op::Pair, true, false, shard, n, on_device, format, stream, [&](const uint8_t* t, size_t m, hipStream_t st) {
+        return pair_order_hist_device(c, t, m, format, first_record, st, n_records);
+    });
+}
+
+int bsk_pair_order_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) {
+    const int rcc = pair_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    BSK_ENTER(c);
+    return pair_order_hist_get(c, bytes, records);
+}
+
+int bsk_pair_order_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin_exclusive) {
+    const int rcc = pair_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    if (!bins_ok(lo_bin, hi_bin_exclusive))
+        return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_pair_order_bucket_begin: the bins must be 0 <= lo < hi <= 4096");
+    BSK_ENTER(c);
+    return pair_order_bucket_begin(c, lo_bin, hi_bin_exclusive);
+}
+
+int bsk_pair_order_bucket_add(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                              void* stream) {
+    const int rcc = pair_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    // (bucket_pass with the bucket state of the order phase: an error closes c->pab.order, not c->rdb)
+    return record_call(c, nullptr, Op::Pair, true, "", shard, n, on_device, format, stream, CallValues(), [&](const uint8_t* d, hipStream_t st) {
+        const int rc = run_multiline(c, [&](const uint8_t* t, const uint64_t* e) { return pair_order_bucket_add(c, t, (size_t)e[0], format, first_record, st); },
+                                     d, {n}, format, st);
+        if (rc != BSK_OK) bucket_close(&c->pab.order);
+        return rc;
+    });
+}
+
+int bsk_pair_order_bucket_finish(bsk_ctx* c, void* stream, bsk_out* out) {
+    const int rcc = bucket_finish_check(c, Op::Pair, "a Pair", out);
+    if (rcc != BSK_OK) return rcc;
+    BSK_ENTER(c);
+    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), (hipStream_t)stream));
+    return pair_order_bucket_finish(c, (hipStream_t)stream, out);
 }
 
 // ---- rmdup across ranks: the phases between which the caller runs the all-to-all exchanges (include/bsk.h)

@@ -29,7 +29,7 @@
 struct bsk_tuning {
     static const char* const* names() {
         static const char* const N[] = {"filter", "grep_shiftand", "head_genome_window", "index", "locate_nopre", "long_bytes", "min_range_bytes", "names",
-                                        "names_scale", "out", "pin_alphabet", "ranges_per_wave", "replace", "rmdup", "rmdup_buckets", "rmdup_hash", "rmdup_k1_bits", "rmdup_k2_bits", "rmdup_keys", "rmdup_place", "rmdup_xcheck", "rmdup_xlocal", "scan", "segcopy",
+                                        "names_scale", "out", "pair_order", "pin_alphabet", "ranges_per_wave", "replace", "rmdup", "rmdup_buckets", "rmdup_hash", "rmdup_k1_bits", "rmdup_k2_bits", "rmdup_keys", "rmdup_place", "rmdup_xcheck", "rmdup_xlocal", "scan", "segcopy",
                                         "sort", "sort_sample_cap", "stage_bytes", "stats_a", "stats_fasta", "stats_prep", "stats_tail", "subseq", "subseq_scale", "text", "translate", "translate_index", "translate_probe", "translate_stream", "tr_lanes", nullptr};
         return N;
     }
@@ -458,6 +458,31 @@ struct bsk_ctx {
         // of the files 0 .. f (bsk_common_verdict_begin), so file_sums[0] records have a bit
         std::vector<uint64_t> file_sums;
     } rdb;
+    // pair in buckets of the key (ops_host_pairbuckets.cpp; PARITY.md PAIRB), on a Pair context.  The match phase runs on `rdb`
+    // over file 1 followed by file 2: rdb.d_bits holds the PAIRED bits of file 1 (words1 words) and, behind them, those of file 2
+    // (d_bits2, words2 words); file_sums = {n1, n1 + n2}.  d_mates[j] of record j of file 2 = the global index of its mate, and
+    // after the rank step (ranked) its output position; d_wpre / d_cnt / d_base are the counts of that step for both bitmaps,
+    // file 2 behind file 1.  first2 = the accumulated index of the open match bucket's first record of file 2.  `order` is the
+    // bucket state of the order phase, of the shuffle kind with a packed accumulation: d_draw = pos.  (Behind `rdb`, for the
+    // reason given at `sob`.)
+    struct PairBuckets {
+        BucketState order;
+        int order_format = -1;           // of the accumulated text
+        uint32_t* d_bits2 = nullptr;     // (inside the allocation of rdb.d_bits)
+        uint64_t words1 = 0, words2 = 0;
+        uint64_t* d_mates = nullptr;
+        uint64_t mates_cap = 0;
+        uint16_t* d_wpre = nullptr;
+        uint64_t wpre_cap = 0;
+        uint32_t* d_cnt = nullptr;
+        uint64_t* d_base = nullptr;
+        uint64_t cnt_cap = 0;
+        uint64_t blocks1 = 0, blocks2 = 0;
+        uint64_t first2 = ~0ull;
+        bool ranked = false, in_mate_order = false;
+        uint64_t pairs = 0;
+        uint32_t shift = 0;              // order bin = pos >> shift
+    } pab;
 };
 
 // the scope of one C-ABI call that runs on the context's device state (BSK_ENTER in capi.cpp / store.cpp)

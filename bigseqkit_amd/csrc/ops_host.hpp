@@ -106,6 +106,20 @@ int common_verdict_begin(bsk_ctx* c, const uint64_t* file_records, uint32_t n_fi
 int common_verdict_get(bsk_ctx* c, uint64_t first, uint64_t count, uint8_t* kept);
 int common_bucket_finish(bsk_ctx* c, hipStream_t st, uint64_t* n_kept, uint64_t* n_flagged);
 int common_emit_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st, bsk_out* out);
+// pair in buckets of the key (ops_host_pairbuckets.cpp; include/bsk.h): the match histogram is rdb_hist_device on a Pair
+// context, the begin and the add of a match bucket wrap rdb_bucket_begin / rdb_bucket_add; the order phase has its own passes
+int pair_verdict_begin(bsk_ctx* c, const uint64_t* file_records);
+int pair_verdict_get(bsk_ctx* c, uint64_t first, uint64_t count, uint64_t* pos);
+int pair_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin);
+int pair_bucket_add(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st);
+int pair_bucket_finish(bsk_ctx* c, hipStream_t st, uint64_t* n_pairs, uint64_t* n_flagged);
+int pair_order_begin(bsk_ctx* c, hipStream_t st, uint64_t* n_pairs, int* in_mate_order);
+int pair_emit_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st, bsk_out* outs);
+int pair_order_hist_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st, uint64_t* n_records);
+int pair_order_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records);
+int pair_order_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin);
+int pair_order_bucket_add(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st);
+int pair_order_bucket_finish(bsk_ctx* c, hipStream_t st, bsk_out* out);
 void validate_head_genome_opts(bsk_ctx* c);
 void head_genome_reset(bsk_ctx* c);
 int head_genome_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, bsk_out* out);

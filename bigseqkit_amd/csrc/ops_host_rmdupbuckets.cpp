@@ -5,7 +5,8 @@
 // `rename` in buckets of the key (ops_host_renamebuckets.cpp; PARITY.md RENB) groups by the same subject under the same key: the
 // steps down to first[] -- rdb_hist_device, rdb_bucket_begin, rdb_bucket_add, rdb_group_keys -- and rdb_flagged_texts serve both
 // operators on c->rdb (declared in ops_host_internal.hpp); their messages name the operator of the context.  `common` in buckets
-// of the key (ops_host_commonbuckets.cpp; PARITY.md COMB) takes the same steps over the union of its files.
+// of the key (ops_host_commonbuckets.cpp; PARITY.md COMB) takes the same steps over the union of its files, and so does the
+// match phase of `pair` in buckets of the key (ops_host_pairbuckets.cpp; PARITY.md PAIRB) over its two.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -34,7 +35,9 @@ struct RdbShard {
     TextTableH tt;
     RmDupParams P;
 };
-const char* rdb_op_name(const bsk_ctx* c) { return c->op == Op::Rename ? "rename" : c->op == Op::Common ? "common" : "rmdup"; }
+const char* rdb_op_name(const bsk_ctx* c) {
+    return c->op == Op::Rename ? "rename" : c->op == Op::Common ? "common" : c->op == Op::Pair ? "pair" : "rmdup";
+}
 static std::string rdb_fn(const bsk_ctx* c, const char* fn) { return std::string("bsk_") + rdb_op_name(c) + "_" + fn; }
 RmDupParams rdb_params(bsk_ctx* c, const uint8_t* d_buf, size_t n, bool fastq) {
     const Options& o = c->opts;
@@ -43,7 +46,7 @@ RmDupParams rdb_params(bsk_ctx* c, const uint8_t* d_buf, size_t n, bool fastq) {
     memset(&P, 0, sizeof P);
     P.fastq = fastq;
     P.by_seq = rmdup && o.b("BySeq");
-    P.by_name = o.b("ByName");
+    P.by_name = c->op != Op::Pair && o.b("ByName");  // (pair in buckets of the key, PARITY.md PAIRB: the ID, nothing else)
     P.ignore_case = rmdup && o.b("IgnoreCase");
     P.id_mode = id_mode_of(c);
     P.line_width = fastq ? 0 : (int)o.ci("LineWidth");

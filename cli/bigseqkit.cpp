@@ -706,13 +706,14 @@ static size_t whole_file_limit() {
     return lim;
 }
 
-// BSK_SHUFFLE_BUDGET_BYTES / BSK_SORT_BUDGET_BYTES / BSK_RMDUP_BUDGET_BYTES / BSK_RENAME_BUDGET_BYTES / BSK_COMMON_BUDGET_BYTES: the
-// bytes a bucket of `shuffle` / `sort` / `rmdup` / `rename` / `common` may hold (run_buckets; rmdup, rename, common: bytes of
-// subjects and their per-record words, not of record text); 0: unset
+// BSK_SHUFFLE_BUDGET_BYTES / BSK_SORT_BUDGET_BYTES / BSK_RMDUP_BUDGET_BYTES / BSK_RENAME_BUDGET_BYTES / BSK_COMMON_BUDGET_BYTES /
+// BSK_PAIR_BUDGET_BYTES: the bytes a bucket of `shuffle` / `sort` / `rmdup` / `rename` / `common` / `pair` may hold (run_buckets;
+// rmdup, rename, common and the match buckets of pair: bytes of subjects and their per-record words, not of record text; the
+// order buckets of pair: bytes of record text, under the same budget); 0: unset
 static uint64_t bucket_budget(const std::string& use) {
     const char* e = use == "shuffle" ? getenv("BSK_SHUFFLE_BUDGET_BYTES") : use == "sort" ? getenv("BSK_SORT_BUDGET_BYTES")
                   : use == "rmdup" ? getenv("BSK_RMDUP_BUDGET_BYTES") : use == "rename" ? getenv("BSK_RENAME_BUDGET_BYTES")
-                  : use == "common" ? getenv("BSK_COMMON_BUDGET_BYTES") : nullptr;
+                  : use == "common" ? getenv("BSK_COMMON_BUDGET_BYTES") : use == "pair" ? getenv("BSK_PAIR_BUDGET_BYTES") : nullptr;
     return e ? (uint64_t)strtoull(e, nullptr, 10) : 0;
 }
 bool g_buckets_unfit = false;  // read_parts: the whole-file load of a `shuffle` / `sort` / `rmdup` / `rename` input failed and a budget is set
@@ -1044,12 +1045,23 @@ Output run_head_genome(const Invocation& inv) {
 //   common    the passes of rmdup over the pieces of ALL files (at least two, of one format), which are not a union to print but the
 //             sets to compare: the histogram pass leaves the record count of every file, a bucket ends in its share of the keep
 //             bits of the FIRST file, and the emit runs over the pieces of the first file only: 1 + B times, the first file once more
+//   pair      (PARITY.md PAIRB) two files of one format, four outputs in -O <dir>, written share by share.  The match phase: the
+//             passes of rmdup over the pieces of both files, a bucket ends in its share of the paired bits and the mates; the rank
+//             step; the emit over both files prints paired.1, the unpaired files (-u) and -- file 2 in the order of its mates --
+//             paired.2.  Otherwise the order phase prints paired.2: a histogram of the positions over file 2, the plan under the
+//             same budget, one pass over file 2 per bucket.  File 1 is read 2 + B1 times; file 2 1 + B1 + 1 times when it is in
+//             mate order, else 1 + B1 + 1 + B2 times and once more with -u
 // Every finished bucket is appended to the output.  A piece never spans two files, so a file that ends without a newline
 // behaves like the union of the whole-file path: its last record gets the newline.
 Output run_buckets(const Invocation& inv) {
     const std::string use = inv.cmd->use;
-    const bool sort = use == "sort", rmdup = use == "rmdup", rename = use == "rename", common = use == "common";
+    const bool sort = use == "sort", rmdup = use == "rmdup", rename = use == "rename", common = use == "common", pair = use == "pair";
     if (common && inv.files.size() < 2) die("at least 2 files needed");  // cli/common.go
+    const std::string outdir = pair ? inv.pget("out-dir") : std::string();
+    if (pair) {  // cli/pair.go:13-66, the checks of the whole-file path
+        if (inv.files.size() < 2) die("2 files needed");
+        if (outdir.empty()) die("out-dir required");
+    }
     const int device = (int)strtol(inv.pget("device").c_str(), nullptr, 10);
     const uint64_t budget = bucket_budget(use);
     constexpr uint32_t kBins = 4096;  // the fine bins of all five (include/bsk.h)
@@ -1060,13 +1072,13 @@ Output run_buckets(const Invocation& inv) {
     if (timing) bsk_profile_enable(ctx, 1);
     struct File { std::string whole; const uint8_t* text = nullptr; size_t size = 0; bool mapped = false; };
     struct Piece { const uint8_t* p; size_t n; uint64_t first; size_t file; uint64_t count; };
-    std::vector<File> files(inv.files.size());
+    std::vector<File> files(pair ? 2 : inv.files.size());
     std::vector<Piece> pieces;
     const char* pinned = getenv("BSK_STREAM_PIECE_BYTES");
     const size_t piece = pinned ? std::max<size_t>(1, (size_t)strtoull(pinned, nullptr, 10)) : ((size_t)1 << 30);
     int fmt = -1;
     uint64_t total_bytes = 0;
-    for (size_t fi = 0; fi < inv.files.size(); ++fi) {
+    for (size_t fi = 0; fi < files.size(); ++fi) {
         const std::string& path = inv.files[fi];
         File& f = files[fi];
         const int fd = open(path.c_str(), O_RDONLY);
@@ -1112,6 +1124,7 @@ Output run_buckets(const Invocation& inv) {
                     : rmdup ? Entry{bsk_rmdup_hist_run, bsk_rmdup_hist_get, bsk_rmdup_bucket_begin, bsk_rmdup_bucket_add, "rmdup: histogram of the bins", "rmdup: buckets"}
                     : rename ? Entry{bsk_rename_hist_run, bsk_rename_hist_get, bsk_rename_bucket_begin, bsk_rename_bucket_add, "rename: histogram of the bins", "rename: buckets"}
                     : common ? Entry{bsk_common_hist_run, bsk_common_hist_get, bsk_common_bucket_begin, bsk_common_bucket_add, "common: histogram of the bins", "common: buckets"}
+                    : pair ? Entry{bsk_pair_hist_run, bsk_pair_hist_get, bsk_pair_bucket_begin, bsk_pair_bucket_add, "pair: histogram of the bins", "pair: match buckets"}
                             : Entry{bsk_shuffle_hist_run, bsk_shuffle_hist_get, bsk_shuffle_bucket_begin, bsk_shuffle_bucket_add, "shuffle: histogram of the draws", "shuffle: buckets"};
     // the pass over all pieces that counts the records: it leaves every piece's first record index
     uint64_t last_count = 0;  // the records of the last piece
@@ -1165,10 +1178,83 @@ Output run_buckets(const Invocation& inv) {
         if (rmdup) msg += " -- rmdup: a fine bin holds the subjects whose key shares its upper 12 bits; the copies of one subject fill one";
         if (rename) msg += " -- rename: a fine bin holds the IDs (-n: the names) whose key shares its upper 12 bits, once per record; the records of one ID fill one";
         if (common) msg += " -- common: a fine bin holds the subjects of all files whose key shares its upper 12 bits, once per record; the copies of one subject fill one";
+        if (pair) msg += " -- pair: a fine bin holds the IDs of both files whose key shares its upper 12 bits, once per record; the records of one ID fill one";
         die(msg);
     }
-    uint64_t removed = 0, flagged = 0;  // (rename: renamed; common: kept)
-    if (common) {
+    uint64_t removed = 0, flagged = 0;  // (rename: renamed; common: kept; pair: pairs)
+    int n_order_buckets = 0;            // (pair)
+    if (pair) {
+        const bool unp = inv.pget("save-unpaired") == "true";
+        if (!is_dir(outdir) && mkdir(outdir.c_str(), 0755) != 0) die("cannot create directory " + outdir);
+        const char* names[4] = {"paired.1", "paired.2", "unpaired.1", "unpaired.2"};
+        std::ofstream outf[4];
+        for (int k = 0; k < (unp ? 4 : 2); ++k) {
+            outf[k].open(outdir + "/" + names[k], std::ios::binary);
+            if (!outf[k]) die("cannot create " + outdir + "/" + names[k]);
+        }
+        std::string share;
+        auto write_share = [&](int k, const bsk_out& out) {
+            if (!out.len || !outf[k].is_open()) return;
+            share.resize(out.len);
+            if (bsk_out_to_host(ctx, &out, &share[0], out.len) != BSK_OK) die(bsk_last_error(ctx));
+            outf[k].write(share.data(), (std::streamsize)share.size());
+            if (!outf[k]) die("write " + outdir + "/" + names[k] + " failed");
+        };
+        // every match bucket over the pieces of both files, in order, ends in its share of the paired bits and the mates
+        uint64_t file_records[2] = {0, 0};
+        for (auto& pc : pieces) file_records[pc.file] += pc.count;
+        if (bsk_pair_verdict_begin(ctx, file_records) != BSK_OK) die(bsk_last_error(ctx));
+        for (int b = 0; b < n_buckets; ++b) {
+            fill_bucket((uint32_t)bounds[b], (uint32_t)bounds[b + 1]);
+            uint64_t r = 0, f = 0;
+            if (bsk_pair_bucket_finish(ctx, nullptr, &r, &f) != BSK_OK) die(bsk_last_error(ctx));
+            removed += r;
+            flagged += f;
+        }
+        mark(E.mark_buckets);
+        uint64_t n_pairs = 0;
+        int in_mate_order = 0;
+        if (bsk_pair_order_begin(ctx, nullptr, &n_pairs, &in_mate_order) != BSK_OK) die(bsk_last_error(ctx));
+        const char* forced = getenv("BSK_PAIR_ORDER");  // (the switch pair_order of the context: the emit leaves paired.2 to the order phase)
+        const bool by_emit = in_mate_order && !(forced && std::string(forced) == "buckets");
+        // the emit: paired.1 and unpaired.1 from the pieces of file 1; unpaired.2 -- and paired.2 when it is a filter of file 2 --
+        // from those of file 2, which are not read when neither is wanted
+        int64_t k = 0;
+        for (auto& pc : pieces) {
+            if (pc.file == 1 && !unp && !by_emit) break;
+            bsk_out outs[3];
+            if (bsk_pair_emit_run(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr, outs) != BSK_OK) die(bsk_last_error(ctx));
+            if (pc.file == 0) write_share(0, outs[0]);
+            else write_share(1, outs[2]);
+            write_share(pc.file == 0 ? 2 : 3, outs[1]);
+        }
+        mark("pair: emit");
+        if (n_pairs && !by_emit) {
+            // paired.2 in buckets of the position: the histogram over the pieces of file 2, the plan, one pass per bucket
+            for (auto& pc : pieces) {
+                uint64_t cnt = 0;
+                if (pc.file == 1 && bsk_pair_order_hist_run(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr, &cnt) != BSK_OK) die(bsk_last_error(ctx));
+            }
+            if (bsk_pair_order_hist_get(ctx, hist.data(), nullptr) != BSK_OK) die(bsk_last_error(ctx));
+            if (bsk_shuffle_plan(hist.data(), budget, bounds.data(), &n_order_buckets) != BSK_OK)
+                die(std::string(bsk_global_error()) + " -- pair: an order bin holds the text of the records of paired.2 whose positions share their upper bits, "
+                                                       "at most a 4096th of the pairs rounded up to a power of two");
+            for (int b = 0; b < n_order_buckets; ++b) {
+                if (bsk_pair_order_bucket_begin(ctx, (uint32_t)bounds[b], (uint32_t)bounds[b + 1]) != BSK_OK) die(bsk_last_error(ctx));
+                for (auto& pc : pieces)
+                    if (pc.file == 1 && bsk_pair_order_bucket_add(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr) != BSK_OK) die(bsk_last_error(ctx));
+                bsk_out out;
+                if (bsk_pair_order_bucket_finish(ctx, nullptr, &out) != BSK_OK) die(bsk_last_error(ctx));
+                write_share(1, out);
+            }
+            mark("pair: order buckets");
+        }
+        for (int j = 0; j < 4; ++j)
+            if (outf[j].is_open()) {
+                outf[j].close();
+                if (!outf[j]) die("write " + outdir + "/" + names[j] + " failed");
+            }
+    } else if (common) {
         // every bucket over the pieces of all files, in order, ends in its share of the keep bits of the first file; one emit pass
         // over the pieces of the first file prints its kept records in file order
         std::vector<uint64_t> file_records(files.size(), 0);
@@ -1236,6 +1322,9 @@ Output run_buckets(const Invocation& inv) {
         if (common)
             fprintf(stderr, "[timing] common: %llu record(s) kept, %llu flagged (subject differed from the first of its key group)\n",
                     (unsigned long long)removed, (unsigned long long)flagged);
+        if (pair)
+            fprintf(stderr, "[timing] pair: %llu pair(s), %llu flagged (subject differed from the first of its key group), %d order bucket(s)\n",
+                    (unsigned long long)removed, (unsigned long long)flagged, n_order_buckets);
     }
     for (auto& f : files)
         if (f.mapped && f.size) munmap((void*)f.text, f.size);
@@ -1654,7 +1743,7 @@ static int run_main(int argc, char** argv) {
         store(inv, o, inv.files);
         return 0;
     }
-    if (bucket_budget(use_cmd) > 0) {  // (shuffle, sort, rmdup, rename, common)
+    if (bucket_budget(use_cmd) > 0) {  // (shuffle, sort, rmdup, rename, common, pair)
         // more bytes than a bucket may hold: not loaded whole (a pipe has no size: it takes the whole-file path)
         uint64_t total = 0;
         struct stat sb;
@@ -1662,7 +1751,7 @@ static int run_main(int argc, char** argv) {
             if (stat(f.c_str(), &sb) == 0 && S_ISREG(sb.st_mode)) total += (uint64_t)sb.st_size;
         if (total > bucket_budget(use_cmd)) {
             Output o = run_buckets(inv);
-            store(inv, o, inv.files);
+            if (use_cmd != "pair") store(inv, o, inv.files);  // (pair has written its four files)
             return 0;
         }
     }
@@ -1732,7 +1821,12 @@ static int run_main(int argc, char** argv) {
         const int device = (int)strtol(inv.pget("device").c_str(), nullptr, 10);
         if (bsk_create("Pair", inv.js.c_str(), device, &c) != BSK_OK) die(bsk_global_error());
         bsk_out outs[4];
-        if (bsk_pair_run(c, both.data(), both.size(), n_first, 0, inputs[0].fmt, nullptr, outs) != BSK_OK) die(bsk_last_error(c));
+        const int prc = bsk_pair_run(c, both.data(), both.size(), n_first, 0, inputs[0].fmt, nullptr, outs);
+        if (prc == BSK_ERR_HIP)
+            die(std::string(bsk_last_error(c)) + " -- 'pair': both files (" + std::to_string(both.size()) + " bytes) must fit one GPU next to their grouping tables and "
+                "the four outputs; BSK_PAIR_BUDGET_BYTES=<bytes> pairs them in buckets of the key that hold at most that many bytes of IDs, and prints "
+                "paired.2 in buckets of at most that many bytes of text when file 2 is not in the order of its mates");
+        if (prc != BSK_OK) die(bsk_last_error(c));
         const char* names[4] = {"paired.1", "paired.2", "unpaired.1", "unpaired.2"};
         const bool unp = inv.pget("save-unpaired") == "true";
         for (int k = 0; k < (unp ? 4 : 2); ++k) {

@@ -591,6 +591,71 @@ int bsk_common_bucket_finish(bsk_ctx* ctx, void* stream, uint64_t* n_kept, uint6
 int bsk_common_emit_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                         void* stream, bsk_out* out);
 
+/* ---- Pair in buckets of the key: the four outputs of bsk_pair_run on file 1 followed by file 2, for files of any size on one
+ * device (PARITY.md PAIRB).  g is the global record index over file 1, then file 2; file_records[f] the records of file f.  The
+ * subject of a record is its ID under the context's ID rule; k(g) = the records g' < g of the same file with the same subject
+ * bytes; with c1, c2 records of a subject in the two files, g is paired iff k(g) < min(c1, c2), and its mate is the record of the
+ * other file with the same subject and the same k.  pos(g) of a paired record of file 1 = the paired records of file 1 in front
+ * of it, pos of a record of file 2 = the pos of its mate; P = the number of pairs.  paired.1 = the paired records of file 1 in
+ * file order, paired.2 = those of file 2 in ascending pos, unpaired.1 / unpaired.2 (SaveUnpaired) the rest in file order.
+ * Two bucket phases:
+ *   match   in buckets of the key.  The fine bin, the cost of a bin, the accumulation of SUBJECTS and the key grouping are
+ *           those of the RmDup buckets above -- the histogram of a Pair context over the union equals that of an RmDup context
+ *           with default options.  A bucket ends in its share of the verdict: one PAIRED bit per record of either file and 8
+ *           bytes per record of file 2 (the mate, later pos), device memory OUTSIDE the budget of the buckets
+ *   order   in buckets of pos.  With s the least shift with (P - 1) >> s < 4096, the order bin of a paired record of file 2 is
+ *           pos >> s; a bin costs the bytes of its record text (text + newline; a wrapped FASTQ shard: its 4-line rewrite);
+ *           bsk_shuffle_plan plans these too.  paired.2 = bucket 0's records in ascending pos, then bucket 1's, ...
+ * File 2 is "in mate order" iff pos of every paired record of file 2 equals the paired records of file 2 in front of it: then
+ * paired.2 is a filter of file 2, the emit pass prints it, and the order phase is not needed.
+ *   bsk_pair_hist_run / _hist_get / _hist_reset      as bsk_rmdup_hist_*, over the shards of file 1, then file 2
+ *   bsk_pair_verdict_begin    zeroed bits for file_records[0] + file_records[1] records, no bin decided, no positions
+ *   bsk_pair_bucket_begin / _add / _finish
+ *                             as bsk_rmdup_bucket_*, with the same refusals; add receives every shard of file 1, then of file 2,
+ *                             in input order under its global first_record; a shard that straddles the two files or reaches
+ *                             past the sum of file_records is BSK_ERR_INVALID_ARG.  finish: *n_pairs = the pairs the bucket
+ *                             found, *n_flagged = the records whose subject differed from the first of their key group (they
+ *                             are paired on the host by text; more than 2^20 of them in one bucket fail the call)
+ *   bsk_pair_order_begin      the rank step, once every bin is decided (else BSK_ERR_INVALID_ARG, the message names the first
+ *                             undecided bin): every mate becomes pos; *n_pairs = P, *in_mate_order = 1 / 0.  A second call
+ *                             reports the same.  No match bucket can begin afterwards
+ *   bsk_pair_verdict_get      pos[j] of global record first + j, j < count; ~0: unpaired.  Valid after bsk_pair_order_begin
+ *   bsk_pair_emit_run         a shard of ONE file under its global first_record, after bsk_pair_order_begin.  File 1: outs[0] =
+ *                             its share of paired.1, outs[1] = of unpaired.1.  File 2: outs[1] = its share of unpaired.2,
+ *                             outs[2] = of paired.2 when file 2 is in mate order and the switch pair_order is not "buckets",
+ *                             else empty.  Unpaired shares with SaveUnpaired only.  The blocks are valid until the next call on
+ *                             the context.  out=slices is BSK_ERR_UNSUPPORTED here
+ *   bsk_pair_order_hist_run / _hist_get
+ *                             the histogram of the order bins over the shards of file 2 (bsk_pair_order_begin zeroes it)
+ *   bsk_pair_order_bucket_begin / _add / _finish
+ *                             add takes the shards of file 2 in input order under their global first_record; finish returns
+ *                             the bucket's share of paired.2 and fails (BSK_ERR_INVALID_ARG) when the bucket did not receive
+ *                             exactly the records of its bins
+ * The switch pair_order=buckets (bsk_ctx_set; tests) makes the emit pass leave paired.2 to the order phase on ordered input too.
+ * Every one of them is BSK_ERR_INVALID_ARG, "not a Pair context", on a context of another operator; the bsk_rmdup_*,
+ * bsk_rename_* and bsk_common_* entry points refuse a Pair context likewise.  bsk_pair_run still runs on a context that has been
+ * through the buckets. */
+int bsk_pair_hist_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                      void* stream, uint64_t* n_records);
+int bsk_pair_hist_get(bsk_ctx* ctx, uint64_t* bytes, uint64_t* records);
+int bsk_pair_hist_reset(bsk_ctx* ctx);
+int bsk_pair_verdict_begin(bsk_ctx* ctx, const uint64_t file_records[2]);
+int bsk_pair_verdict_get(bsk_ctx* ctx, uint64_t first, uint64_t count, uint64_t* pos);
+int bsk_pair_bucket_begin(bsk_ctx* ctx, uint32_t lo_bin, uint32_t hi_bin_exclusive);
+int bsk_pair_bucket_add(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                        void* stream);
+int bsk_pair_bucket_finish(bsk_ctx* ctx, void* stream, uint64_t* n_pairs, uint64_t* n_flagged);
+int bsk_pair_order_begin(bsk_ctx* ctx, void* stream, uint64_t* n_pairs, int* in_mate_order);
+int bsk_pair_emit_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                      void* stream, bsk_out outs[3]);
+int bsk_pair_order_hist_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                            void* stream, uint64_t* n_records);
+int bsk_pair_order_hist_get(bsk_ctx* ctx, uint64_t* bytes, uint64_t* records);
+int bsk_pair_order_bucket_begin(bsk_ctx* ctx, uint32_t lo_bin, uint32_t hi_bin_exclusive);
+int bsk_pair_order_bucket_add(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                              void* stream);
+int bsk_pair_order_bucket_finish(bsk_ctx* ctx, void* stream, bsk_out* out);
+
 /* ---- HeadGenome (bigseqkit/head_genome.go, bigseqkit-lib/head_genome.go:53-108; options {"MiniCommonWords": 1}; PARITY.md
  * HEADG): the records of the first genome.  The words of a record are the maximal runs of its description other than ' '
  * and '\t'; the prefix is the words of the first record of the input; n_i = leading words of record i equal to the prefix's.
