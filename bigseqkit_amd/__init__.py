@@ -18,4 +18,6 @@ from .api import (SeqFrame, ReadFASTA, ReadFASTAN, ReadFASTQ, ReadFASTQN, Operat
                   RenameBuckets, RenameHistRun, RenameHistGet, RenameHistReset, RenameVerdictBegin, RenameVerdictGet, RenameBucket, RenameEmit,
                   CommonBuckets, CommonHistRun, CommonHistGet, CommonHistReset, CommonVerdictBegin, CommonVerdictGet, CommonBucket, CommonEmit,
                   PairBuckets, PairHistRun, PairHistGet, PairHistReset, PairVerdictBegin, PairVerdictGet, PairBucket, PairOrderBegin, PairEmit,
-                  PairOrderHistRun, PairOrderHistGet, PairOrderBucket)
+                  PairOrderHistRun, PairOrderHistGet, PairOrderBucket,
+                  ConcatBuckets, ConcatHistRun, ConcatHistGet, ConcatHistReset, ConcatVerdictBegin, ConcatVerdictGet, ConcatBucket,
+                  ConcatJoinBegin, ConcatWeighRun, ConcatWindowHistRun, ConcatWindowHistGet, ConcatWindowShift, ConcatWindow, ConcatTail)

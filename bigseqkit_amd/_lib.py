@@ -200,6 +200,22 @@ SIGNATURES = {
     "bsk_pair_order_bucket_begin": (_i, [_vp, C.c_uint32, C.c_uint32]),
     "bsk_pair_order_bucket_add": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp]),
     "bsk_pair_order_bucket_finish": (_i, [_vp, _vp, _p(Out)]),
+    "bsk_concat_hist_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp, _p(C.c_uint64)]),
+    "bsk_concat_hist_get": (_i, [_vp, _p(C.c_uint64), _p(C.c_uint64)]),
+    "bsk_concat_hist_reset": (_i, [_vp]),
+    "bsk_concat_verdict_begin": (_i, [_vp, _p(C.c_uint64)]),
+    "bsk_concat_verdict_get": (_i, [_vp, C.c_uint64, C.c_uint64, _p(C.c_uint64)]),
+    "bsk_concat_bucket_begin": (_i, [_vp, C.c_uint32, C.c_uint32]),
+    "bsk_concat_bucket_add": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp]),
+    "bsk_concat_bucket_finish": (_i, [_vp, _vp, _p(C.c_uint64), _p(C.c_uint64)]),
+    "bsk_concat_join_begin": (_i, [_vp, _vp]),
+    "bsk_concat_weigh_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp, _p(C.c_uint64)]),
+    "bsk_concat_window_hist_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp, _p(C.c_uint64)]),
+    "bsk_concat_window_hist_get": (_i, [_vp, _p(C.c_uint64), _p(C.c_uint64)]),
+    "bsk_concat_window_begin": (_i, [_vp, C.c_uint32, C.c_uint32]),
+    "bsk_concat_window_add": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp]),
+    "bsk_concat_window_finish": (_i, [_vp, _vp, _p(Out)]),
+    "bsk_concat_tail_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp, _p(Out)]),
     "bsk_head_genome_run":(_i, [_vp, _vp, _sz, _i, _i, _i64, _vp, _p(Out)]),
     "bsk_head_genome_reset": (_i, [_vp]),
     "bsk_head_genome_state": (_i, [_vp, _p(C.c_int), _p(C.c_uint64)]),

@@ -950,6 +950,140 @@ def PairBuckets(inputA, inputB, o=None, budget_bytes=1 << 30, device=0, order="a
         return paired1, paired2, unpaired1, unpaired2
 
 
+def _concat_frames(inputA, inputB):
+    if inputA.format != inputB.format:
+        raise ValueError("concat: inputs of different formats")
+    return [inputA, inputB]
+
+
+def ConcatHistRun(op, inputs):
+    """bsk_concat_hist_run over the shards of file 1, then file 2: per file, the record count of every shard (the histogram
+    accumulates in the operator's context)"""
+    flat = _count_pass(lib.bsk_concat_hist_run, op, _union_frame(inputs))
+    na = len(inputs[0].shards)
+    return [flat[:na], flat[na:]]
+
+
+def ConcatHistGet(op):
+    """bsk_concat_hist_get: (bytes[4096], records[4096])"""
+    return _hist_get(lib.bsk_concat_hist_get, op)
+
+
+def ConcatHistReset(op):
+    check(lib.bsk_concat_hist_reset(op.ctx), op.ctx)
+
+
+def ConcatVerdictBegin(op, file_records):
+    """bsk_concat_verdict_begin: a head word for the records of both files, no bin decided; file_records = [n1, n2]"""
+    arr = (C.c_uint64 * 2)(*file_records)
+    check(lib.bsk_concat_verdict_begin(op.ctx, arr), op.ctx)
+
+
+def ConcatVerdictGet(op, first, count):
+    """bsk_concat_verdict_get: head of the global records [first, first + count); None = file 1 has no record of that ID"""
+    buf = (C.c_uint64 * max(1, count))()
+    check(lib.bsk_concat_verdict_get(op.ctx, first, count, buf), op.ctx)
+    return [None if v == 0xFFFFFFFFFFFFFFFF else v for v in buf[:count]]
+
+
+def ConcatBucket(op, inputs, counts, lo_bin, hi_bin):
+    """bsk_concat_bucket_begin / _add over the shards of file 1, then file 2 / _finish: (matched, flagged) of the match bucket
+    [lo_bin, hi_bin); `counts` is what ConcatHistRun returned"""
+    _bucket_adds(lib.bsk_concat_bucket_begin, lib.bsk_concat_bucket_add, op, _union_frame(inputs), [k for c in counts for k in c], lo_bin, hi_bin)
+    matched, flagged = C.c_uint64(), C.c_uint64()
+    check(lib.bsk_concat_bucket_finish(op.ctx, None, C.byref(matched), C.byref(flagged)), op.ctx)
+    return matched.value, flagged.value
+
+
+def ConcatJoinBegin(op):
+    """bsk_concat_join_begin: zeroed weights, mark bits and window histogram, once every bin is decided"""
+    check(lib.bsk_concat_join_begin(op.ctx, None), op.ctx)
+
+
+def _concat_pass(fn, op, input, counts, first):
+    for (pid, ptr, n, on_dev, keep), cnt in zip(input.partitions(), counts):
+        k = C.c_uint64()
+        check(fn(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None, C.byref(k)), op.ctx)
+        first += cnt
+
+
+def ConcatWeighRun(op, input, counts, first):
+    """bsk_concat_weigh_run over the shards of file 2, in order, the first of them global record `first`"""
+    _concat_pass(lib.bsk_concat_weigh_run, op, input, counts, first)
+
+
+def ConcatWindowHistRun(op, input, counts):
+    """bsk_concat_window_hist_run over the shards of file 1, in order"""
+    _concat_pass(lib.bsk_concat_window_hist_run, op, input, counts, 0)
+
+
+def ConcatWindowHistGet(op):
+    """bsk_concat_window_hist_get: (cost[4096], records[4096]) of the window bins"""
+    return _hist_get(lib.bsk_concat_window_hist_get, op)
+
+
+def ConcatWindowShift(n1):
+    """the least shift s with (n1 - 1) >> s < 4096 (0 for an empty file 1)"""
+    s = 0
+    while n1 and (n1 - 1) >> s >= _BUCKET_BINS:
+        s += 1
+    return s
+
+
+def ConcatWindow(op, inputs, counts, lo_bin, hi_bin):
+    """bsk_concat_window_begin / _add over the shards of file 1 that reach into the window, then every shard of file 2 /
+    _finish: the share of the output of the window [lo_bin, hi_bin)"""
+    n1 = sum(counts[0])
+    s = ConcatWindowShift(n1)
+    check(lib.bsk_concat_window_begin(op.ctx, lo_bin, hi_bin), op.ctx)
+    first = 0
+    for f, (input, cnts) in enumerate(zip(inputs, counts)):
+        for (pid, ptr, n, on_dev, keep), cnt in zip(input.partitions(), cnts):
+            outside = f == 0 and (cnt == 0 or (first + cnt - 1) >> s < lo_bin or first >> s >= hi_bin)
+            if not outside:
+                check(lib.bsk_concat_window_add(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None), op.ctx)
+            first += cnt
+    out = _lib.Out()
+    check(lib.bsk_concat_window_finish(op.ctx, None, C.byref(out)), op.ctx)
+    return _out_bytes(op, out)
+
+
+def ConcatTail(op, input, counts, first):
+    """bsk_concat_tail_run over the shards of file 2, in order, the first of them global record `first`: with Full the records
+    of file 2 whose ID file 1 does not have, joined; else empty"""
+    chunks = []
+    for (pid, ptr, n, on_dev, keep), cnt in zip(input.partitions(), counts):
+        out = _lib.Out()
+        check(lib.bsk_concat_tail_run(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None, C.byref(out)), op.ctx)
+        chunks.append(_out_bytes(op, out))
+        first += cnt
+    return b"".join(chunks)
+
+
+def ConcatBuckets(inputA, inputB, o=None, budget_bytes=1 << 30, device=0):
+    """Concat of two files of any size on one device (PARITY CONB) -> the same bytes as Concat.  The match phase: the histogram
+    of the fine bins of the key over both files, the plan of buckets of at most `budget_bytes` of subjects, one collect sequence
+    per bucket, which ends in the bucket's share of the heads.  The join phase: the weights of the heads over file 2, the
+    histogram of the window costs over file 1, the plan of windows under the same budget -- a window bin above it is refused by
+    the plan, which names its bytes --, one collect sequence per window, and with Full the tail over file 2."""
+    inputs = _concat_frames(inputA, inputB)
+    with Operator("Concat", (o or SeqKitConcatOptions()).to_json(), device) as op:
+        ConcatHistReset(op)
+        counts = ConcatHistRun(op, inputs)
+        bounds = ShufflePlan(ConcatHistGet(op)[0], budget_bytes)
+        n1 = sum(counts[0])
+        ConcatVerdictBegin(op, [n1, sum(counts[1])])
+        for lo, hi in zip(bounds[:-1], bounds[1:]):
+            ConcatBucket(op, inputs, counts, lo, hi)
+        ConcatJoinBegin(op)
+        ConcatWeighRun(op, inputB, counts[1], n1)
+        ConcatWindowHistRun(op, inputA, counts[0])
+        wbounds = ShufflePlan(ConcatWindowHistGet(op)[0], budget_bytes)
+        chunks = [ConcatWindow(op, inputs, counts, lo, hi) for lo, hi in zip(wbounds[:-1], wbounds[1:])]
+        chunks.append(ConcatTail(op, inputB, counts[1], n1))
+        return b"".join(chunks)
+
+
 def HeadGenome(input, o=None, device=0):
     """bigseqkit/head_genome.go:37-77 (PARITY HEADG): the records of the first genome.  ONE cut over the whole input: the
     shards go through one context in order, which carries the prefix words, n_1 and "cut reached" from shard to shard, and

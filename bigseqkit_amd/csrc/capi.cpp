@@ -380,6 +380,9 @@ void bsk_destroy(bsk_ctx* c) {
         for (void* p : {(void*)c->pab.order.d_hist, (void*)c->pab.order.d_acc, (void*)c->pab.order.d_draw, (void*)c->pab.order.d_off,
                         (void*)c->pab.order.d_len, (void*)c->pab.d_mates, (void*)c->pab.d_wpre, (void*)c->pab.d_cnt, (void*)c->pab.d_base})
             if (p) hipFree(p);
+        for (void* p : {(void*)c->cab.win.d_hist, (void*)c->cab.win.d_acc, (void*)c->cab.win.d_draw, (void*)c->cab.win.d_off,
+                        (void*)c->cab.win.d_len, (void*)c->cab.d_head, (void*)c->cab.d_w, (void*)c->cab.d_c, (void*)c->cab.d_mark})
+            if (p) hipFree(p);
         if (c->d_vm_progs) hipFree(c->d_vm_progs);
         if (c->d_id_off) hipFree(c->d_id_off);
         if (c->d_id_len) hipFree(c->d_id_len);
@@ -1034,6 +1037,7 @@ static int rmdup_ctx_check(bsk_ctx* c) { return bucket_ctx_check(c, Op::RmDup, "
 static int rename_ctx_check(bsk_ctx* c) { return bucket_ctx_check(c, Op::Rename, "a Rename"); }
 static int common_ctx_check(bsk_ctx* c) { return bucket_ctx_check(c, Op::Common, "a Common"); }
 static int pair_ctx_check(bsk_ctx* c) { return bucket_ctx_check(c, Op::Pair, "a Pair"); }
+static int concat_ctx_check(bsk_ctx* c) { return bucket_ctx_check(c, Op::Concat, "a Concat"); }
 static bool bins_ok(uint32_t lo_bin, uint32_t hi_bin_exclusive) { return lo_bin < hi_bin_exclusive && hi_bin_exclusive <= BUCKET_BINS; }
 // the prologue of a finish that fills a bsk_out
 static int bucket_finish_check(bsk_ctx* c, Op op, const char* a_name, bsk_out* out) {
@@ -1815,6 +1819,140 @@ int bsk_pair_order_bucket_finish(bsk_ctx* c, void* stream, bsk_out* out) {
     BSK_ENTER(c);
     HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), (hipStream_t)stream));
     return pair_order_bucket_finish(c, (hipStream_t)stream, out);
+}
+
+// ---- concat in buckets of the key (ops_host_concatbuckets.cpp): the match phase takes rmdup's steps on a Concat context over
+// file 1 followed by file 2; the join phase has a bucket state of its own (c->cab.win), which its add closes when it fails
+int bsk_concat_hist_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                        void* stream, uint64_t* n_records) {
+    const int rcc = concat_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    return bucket_pass(c, nullptr, Op::Concat, true, false, shard, n, on_device, format, stream,
+                       [&](const uint8_t* t, size_t m, hipStream_t st) { return rdb_hist_device(c, t, m, format, st, n_records); });
+}
+
+int bsk_concat_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) {
+    const int rcc = concat_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    BSK_ENTER(c);
+    return bucket_hist_get(c, &c->rdb, bytes, records);
+}
+
+int bsk_concat_hist_reset(bsk_ctx* c) {
+    const int rcc = concat_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    BSK_ENTER(c);
+    return bucket_hist_reset(c, &c->rdb);
+}
+
+int bsk_concat_verdict_begin(bsk_ctx* c, const uint64_t* file_records) {
+    const int rcc = concat_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    if (!file_records) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_concat_verdict_begin: null argument");
+    BSK_ENTER(c);
+    return concat_verdict_begin(c, file_records);
+}
+
+int bsk_concat_verdict_get(bsk_ctx* c, uint64_t first, uint64_t count, uint64_t* head) {
+    const int rcc = concat_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    if (count && !head) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_concat_verdict_get: null argument");
+    BSK_ENTER(c);
+    return concat_verdict_get(c, first, count, head);
+}
+
+int bsk_concat_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin_exclusive) {
+    const int rcc = concat_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    if (!bins_ok(lo_bin, hi_bin_exclusive)) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_concat_bucket_begin: the bins must be 0 <= lo < hi <= 4096");
+    BSK_ENTER(c);
+    return concat_bucket_begin(c, lo_bin, hi_bin_exclusive);
+}
+
+int bsk_concat_bucket_add(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                          void* stream) {
+    const int rcc = concat_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    return bucket_pass(c, nullptr, Op::Concat, true, true, shard, n, on_device, format, stream,
+                       [&](const uint8_t* t, size_t m, hipStream_t st) { return concat_bucket_add(c, t, m, format, first_record, st); });
+}
+
+int bsk_concat_bucket_finish(bsk_ctx* c, void* stream, uint64_t* n_matched, uint64_t* n_flagged) {
+    const int rcc = concat_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    BSK_ENTER(c);
+    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), (hipStream_t)stream));
+    return concat_bucket_finish(c, (hipStream_t)stream, n_matched, n_flagged);
+}
+
+int bsk_concat_join_begin(bsk_ctx* c, void* stream) {
+    const int rcc = concat_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    BSK_ENTER(c);
+    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), (hipStream_t)stream));
+    return concat_join_begin(c, (hipStream_t)stream);
+}
+
+int bsk_concat_weigh_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                         void* stream, uint64_t* n_records) {
+    const int rcc = concat_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    return bucket_pass(c, nullptr, Op::Concat, true, false, shard, n, on_device, format, stream, [&](const uint8_t* t, size_t m, hipStream_t st) {
+        return concat_weigh_device(c, t, m, format, first_record, st, n_records);
+    });
+}
+
+int bsk_concat_window_hist_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                               void* stream, uint64_t* n_records) {
+    const int rcc = concat_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    return bucket_pass(c, nullptr, Op::Concat, true, false, shard, n, on_device, format, stream, [&](const uint8_t* t, size_t m, hipStream_t st) {
+        return concat_window_hist_device(c, t, m, format, first_record, st, n_records);
+    });
+}
+
+int bsk_concat_window_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) {
+    const int rcc = concat_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    BSK_ENTER(c);
+    return concat_window_hist_get(c, bytes, records);
+}
+
+int bsk_concat_window_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin_exclusive) {
+    const int rcc = concat_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    if (!bins_ok(lo_bin, hi_bin_exclusive)) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_concat_window_begin: the bins must be 0 <= lo < hi <= 4096");
+    BSK_ENTER(c);
+    return concat_window_begin(c, lo_bin, hi_bin_exclusive);
+}
+
+int bsk_concat_window_add(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                          void* stream) {
+    const int rcc = concat_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    // (bucket_pass with the bucket state of the join phase: an error closes c->cab.win, not c->rdb)
+    return record_call(c, nullptr, Op::Concat, true, "", shard, n, on_device, format, stream, CallValues(), [&](const uint8_t* d, hipStream_t st) {
+        const int rc = run_multiline(c, [&](const uint8_t* t, const uint64_t* e) { return concat_window_add(c, t, (size_t)e[0], format, first_record, st); },
+                                     d, {n}, format, st);
+        if (rc != BSK_OK) bucket_close(&c->cab.win);
+        return rc;
+    });
+}
+
+int bsk_concat_window_finish(bsk_ctx* c, void* stream, bsk_out* out) {
+    const int rcc = bucket_finish_check(c, Op::Concat, "a Concat", out);
+    if (rcc != BSK_OK) return rcc;
+    BSK_ENTER(c);
+    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), (hipStream_t)stream));
+    return concat_window_finish(c, (hipStream_t)stream, out);
+}
+
+int bsk_concat_tail_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                        void* stream, bsk_out* out) {
+    const int rcc = concat_ctx_check(c);
+    if (rcc != BSK_OK) return rcc;
+    return bucket_pass(c, out, Op::Concat, out != nullptr, false, shard, n, on_device, format, stream,
+                       [&](const uint8_t* t, size_t m, hipStream_t st) { return concat_tail_device(c, t, m, format, first_record, st, out); });
 }
 
 // ---- rmdup across ranks: the phases between which the caller runs the all-to-all exchanges (include/bsk.h)

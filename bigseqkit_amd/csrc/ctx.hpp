@@ -483,6 +483,29 @@ struct bsk_ctx {
         uint64_t pairs = 0;
         uint32_t shift = 0;              // order bin = pos >> shift
     } pab;
+    // concat in buckets of the key (ops_host_concatbuckets.cpp; PARITY.md CONB), on a Concat context.  The match phase runs on
+    // `rdb` over file 1 followed by file 2 (file_sums = {n1, n1 + n2}, d_bits stays null): the verdict is d_head[g] = the lowest
+    // record of file 1 with the subject of global record g, ~0 when file 1 has none.  The join phase (joined): d_w[h] / d_c[h] =
+    // the text bytes / the number of the records of file 2 whose head is h, `weighed` = the records of file 2 counted into them;
+    // `win` = the window histogram (bin = index in file 1 >> shift, bytes = cost) and the open window, whose accumulation is
+    // packed: the kept records of file 1, then (in_file2) those of file 2; d_mark = one bit per record of file 1, set for the heads
+    // of the window's records; kept1 / bytes1 = the records / bytes of the file-1 part, seen2 = the records of file 2 the window
+    // has looked at.  (Behind `pab`, for the reason given at `sob`.)
+    struct ConcatBuckets {
+        BucketState win;
+        int win_format = -1;             // of the accumulated text
+        uint64_t* d_head = nullptr;
+        uint64_t head_cap = 0;
+        uint64_t* d_w = nullptr;
+        uint64_t* d_c = nullptr;
+        uint64_t wc_cap = 0;
+        uint32_t* d_mark = nullptr;
+        uint64_t mark_words = 0;
+        bool joined = false, in_file2 = false;
+        uint64_t weighed = 0;
+        uint32_t shift = 0;              // window bin = index in file 1 >> shift
+        uint64_t kept1 = 0, bytes1 = 0, seen2 = 0;
+    } cab;
 };
 
 // the scope of one C-ABI call that runs on the context's device state (BSK_ENTER in capi.cpp / store.cpp)

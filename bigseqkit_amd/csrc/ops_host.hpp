@@ -120,6 +120,21 @@ int pair_order_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records);
 int pair_order_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin);
 int pair_order_bucket_add(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st);
 int pair_order_bucket_finish(bsk_ctx* c, hipStream_t st, bsk_out* out);
+// concat in buckets of the key (ops_host_concatbuckets.cpp; include/bsk.h): the match histogram is rdb_hist_device on a Concat
+// context, the begin and the add of a match bucket wrap rdb_bucket_begin / rdb_bucket_add; the join phase has its own passes
+int concat_verdict_begin(bsk_ctx* c, const uint64_t* file_records);
+int concat_verdict_get(bsk_ctx* c, uint64_t first, uint64_t count, uint64_t* head);
+int concat_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin);
+int concat_bucket_add(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st);
+int concat_bucket_finish(bsk_ctx* c, hipStream_t st, uint64_t* n_matched, uint64_t* n_flagged);
+int concat_join_begin(bsk_ctx* c, hipStream_t st);
+int concat_weigh_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st, uint64_t* n_records);
+int concat_window_hist_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st, uint64_t* n_records);
+int concat_window_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records);
+int concat_window_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin);
+int concat_window_add(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st);
+int concat_window_finish(bsk_ctx* c, hipStream_t st, bsk_out* out);
+int concat_tail_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, uint64_t first_record, hipStream_t st, bsk_out* out);
 void validate_head_genome_opts(bsk_ctx* c);
 void head_genome_reset(bsk_ctx* c);
 int head_genome_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, bsk_out* out);

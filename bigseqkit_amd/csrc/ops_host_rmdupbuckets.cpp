@@ -6,7 +6,8 @@
 // steps down to first[] -- rdb_hist_device, rdb_bucket_begin, rdb_bucket_add, rdb_group_keys -- and rdb_flagged_texts serve both
 // operators on c->rdb (declared in ops_host_internal.hpp); their messages name the operator of the context.  `common` in buckets
 // of the key (ops_host_commonbuckets.cpp; PARITY.md COMB) takes the same steps over the union of its files, and so does the
-// match phase of `pair` in buckets of the key (ops_host_pairbuckets.cpp; PARITY.md PAIRB) over its two.
+// match phase of `pair` in buckets of the key (ops_host_pairbuckets.cpp; PARITY.md PAIRB) over its two, and that of `concat` in
+// buckets of the key (ops_host_concatbuckets.cpp; PARITY.md CONB).
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -36,7 +37,7 @@ struct RdbShard {
     RmDupParams P;
 };
 const char* rdb_op_name(const bsk_ctx* c) {
-    return c->op == Op::Rename ? "rename" : c->op == Op::Common ? "common" : c->op == Op::Pair ? "pair" : "rmdup";
+    return c->op == Op::Rename ? "rename" : c->op == Op::Common ? "common" : c->op == Op::Pair ? "pair" : c->op == Op::Concat ? "concat" : "rmdup";
 }
 static std::string rdb_fn(const bsk_ctx* c, const char* fn) { return std::string("bsk_") + rdb_op_name(c) + "_" + fn; }
 RmDupParams rdb_params(bsk_ctx* c, const uint8_t* d_buf, size_t n, bool fastq) {
@@ -46,7 +47,8 @@ RmDupParams rdb_params(bsk_ctx* c, const uint8_t* d_buf, size_t n, bool fastq) {
     memset(&P, 0, sizeof P);
     P.fastq = fastq;
     P.by_seq = rmdup && o.b("BySeq");
-    P.by_name = c->op != Op::Pair && o.b("ByName");  // (pair in buckets of the key, PARITY.md PAIRB: the ID, nothing else)
+    // (pair and concat in buckets of the key, PARITY.md PAIRB / CONB: the ID, nothing else)
+    P.by_name = c->op != Op::Pair && c->op != Op::Concat && o.b("ByName");
     P.ignore_case = rmdup && o.b("IgnoreCase");
     P.id_mode = id_mode_of(c);
     P.line_width = fastq ? 0 : (int)o.ci("LineWidth");

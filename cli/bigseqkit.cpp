@@ -512,6 +512,7 @@ struct Output {
     std::string text;         // everything else: stats table, grep -C count, locate rows, or the host copy of the records
     bool is_text = false;     // `text` is the result (not record text)
     int fmt = -1;             // format of the record text in `text` (-1: line oriented)
+    bool stored = false;      // the result has been written already, share by share (run_buckets, concat): store() is not called
 };
 
 bool g_faidx_query = false;  // `faidx` with regions: records out, not index rows
@@ -707,13 +708,15 @@ static size_t whole_file_limit() {
 }
 
 // BSK_SHUFFLE_BUDGET_BYTES / BSK_SORT_BUDGET_BYTES / BSK_RMDUP_BUDGET_BYTES / BSK_RENAME_BUDGET_BYTES / BSK_COMMON_BUDGET_BYTES /
-// BSK_PAIR_BUDGET_BYTES: the bytes a bucket of `shuffle` / `sort` / `rmdup` / `rename` / `common` / `pair` may hold (run_buckets;
-// rmdup, rename, common and the match buckets of pair: bytes of subjects and their per-record words, not of record text; the
-// order buckets of pair: bytes of record text, under the same budget); 0: unset
+// BSK_PAIR_BUDGET_BYTES / BSK_CONCAT_BUDGET_BYTES: the bytes a bucket of `shuffle` / `sort` / `rmdup` / `rename` / `common` / `pair` /
+// `concat` may hold (run_buckets; rmdup, rename, common and the match buckets of pair and concat: bytes of subjects and their
+// per-record words, not of record text; the order buckets of pair: bytes of record text, the windows of concat: the cost of their
+// records, a bound of the text they collect and join -- both under the same budget); 0: unset
 static uint64_t bucket_budget(const std::string& use) {
     const char* e = use == "shuffle" ? getenv("BSK_SHUFFLE_BUDGET_BYTES") : use == "sort" ? getenv("BSK_SORT_BUDGET_BYTES")
                   : use == "rmdup" ? getenv("BSK_RMDUP_BUDGET_BYTES") : use == "rename" ? getenv("BSK_RENAME_BUDGET_BYTES")
-                  : use == "common" ? getenv("BSK_COMMON_BUDGET_BYTES") : use == "pair" ? getenv("BSK_PAIR_BUDGET_BYTES") : nullptr;
+                  : use == "common" ? getenv("BSK_COMMON_BUDGET_BYTES") : use == "pair" ? getenv("BSK_PAIR_BUDGET_BYTES")
+                  : use == "concat" ? getenv("BSK_CONCAT_BUDGET_BYTES") : nullptr;
     return e ? (uint64_t)strtoull(e, nullptr, 10) : 0;
 }
 bool g_buckets_unfit = false;  // read_parts: the whole-file load of a `shuffle` / `sort` / `rmdup` / `rename` input failed and a budget is set
@@ -1051,11 +1054,19 @@ Output run_head_genome(const Invocation& inv) {
 //             paired.2.  Otherwise the order phase prints paired.2: a histogram of the positions over file 2, the plan under the
 //             same budget, one pass over file 2 per bucket.  File 1 is read 2 + B1 times; file 2 1 + B1 + 1 times when it is in
 //             mate order, else 1 + B1 + 1 + B2 times and once more with -u
+//   concat    (PARITY.md CONB) two files of one format.  The match phase: the passes of rmdup over the pieces of both files, a bucket
+//             ends in its share of the heads.  The join phase: the weights of the heads over file 2, the histogram of the window
+//             costs over file 1, the plan of windows under the same budget, per window the pieces of file 1 that reach into it and
+//             every piece of file 2; every window's share is written as it finishes, and with -f the tail over file 2.  File 1 is
+//             read 1 + B1 times, once for the window histogram and once across all windows; file 2 1 + B1 times, once for the
+//             weights, once per window and once more with -f
 // Every finished bucket is appended to the output.  A piece never spans two files, so a file that ends without a newline
 // behaves like the union of the whole-file path: its last record gets the newline.
 Output run_buckets(const Invocation& inv) {
     const std::string use = inv.cmd->use;
-    const bool sort = use == "sort", rmdup = use == "rmdup", rename = use == "rename", common = use == "common", pair = use == "pair";
+    const bool sort = use == "sort", rmdup = use == "rmdup", rename = use == "rename", common = use == "common", pair = use == "pair",
+               concat = use == "concat";
+    if (concat && inv.files.size() != 2) die("2 files needed");  // cli/concat.go
     if (common && inv.files.size() < 2) die("at least 2 files needed");  // cli/common.go
     const std::string outdir = pair ? inv.pget("out-dir") : std::string();
     if (pair) {  // cli/pair.go:13-66, the checks of the whole-file path
@@ -1072,7 +1083,7 @@ Output run_buckets(const Invocation& inv) {
     if (timing) bsk_profile_enable(ctx, 1);
     struct File { std::string whole; const uint8_t* text = nullptr; size_t size = 0; bool mapped = false; };
     struct Piece { const uint8_t* p; size_t n; uint64_t first; size_t file; uint64_t count; };
-    std::vector<File> files(pair ? 2 : inv.files.size());
+    std::vector<File> files(pair || concat ? 2 : inv.files.size());
     std::vector<Piece> pieces;
     const char* pinned = getenv("BSK_STREAM_PIECE_BYTES");
     const size_t piece = pinned ? std::max<size_t>(1, (size_t)strtoull(pinned, nullptr, 10)) : ((size_t)1 << 30);
@@ -1124,6 +1135,7 @@ Output run_buckets(const Invocation& inv) {
                     : rmdup ? Entry{bsk_rmdup_hist_run, bsk_rmdup_hist_get, bsk_rmdup_bucket_begin, bsk_rmdup_bucket_add, "rmdup: histogram of the bins", "rmdup: buckets"}
                     : rename ? Entry{bsk_rename_hist_run, bsk_rename_hist_get, bsk_rename_bucket_begin, bsk_rename_bucket_add, "rename: histogram of the bins", "rename: buckets"}
                     : common ? Entry{bsk_common_hist_run, bsk_common_hist_get, bsk_common_bucket_begin, bsk_common_bucket_add, "common: histogram of the bins", "common: buckets"}
+                    : concat ? Entry{bsk_concat_hist_run, bsk_concat_hist_get, bsk_concat_bucket_begin, bsk_concat_bucket_add, "concat: histogram of the bins", "concat: match buckets"}
                     : pair ? Entry{bsk_pair_hist_run, bsk_pair_hist_get, bsk_pair_bucket_begin, bsk_pair_bucket_add, "pair: histogram of the bins", "pair: match buckets"}
                             : Entry{bsk_shuffle_hist_run, bsk_shuffle_hist_get, bsk_shuffle_bucket_begin, bsk_shuffle_bucket_add, "shuffle: histogram of the draws", "shuffle: buckets"};
     // the pass over all pieces that counts the records: it leaves every piece's first record index
@@ -1179,11 +1191,88 @@ Output run_buckets(const Invocation& inv) {
         if (rename) msg += " -- rename: a fine bin holds the IDs (-n: the names) whose key shares its upper 12 bits, once per record; the records of one ID fill one";
         if (common) msg += " -- common: a fine bin holds the subjects of all files whose key shares its upper 12 bits, once per record; the copies of one subject fill one";
         if (pair) msg += " -- pair: a fine bin holds the IDs of both files whose key shares its upper 12 bits, once per record; the records of one ID fill one";
+        if (concat) msg += " -- concat: a fine bin holds the IDs of both files whose key shares its upper 12 bits, once per record; the records of one ID fill one";
         die(msg);
     }
-    uint64_t removed = 0, flagged = 0;  // (rename: renamed; common: kept; pair: pairs)
-    int n_order_buckets = 0;            // (pair)
-    if (pair) {
+    uint64_t removed = 0, flagged = 0;  // (rename: renamed; common: kept; pair: pairs; concat: records with a head)
+    int n_order_buckets = 0;            // (pair; concat: windows)
+    if (concat) {
+        // one file (-o <file> --merge) or the standard output (-o -) receives the shares as they finish; a directory of part files
+        // is cut from the whole result, which is collected on the host then (store)
+        const std::string outp = inv.pget("out-file");
+        const bool to_stdout = outp == "-", to_file = !outp.empty() && !to_stdout && inv.pget("merge") == "true";
+        std::ofstream outf;
+        if (to_file) {
+            outf.open(outp, std::ios::binary);
+            if (!outf) die("cannot create " + outp);
+        }
+        res.stored = to_file || to_stdout;
+        std::string share;
+        auto write_share = [&](const bsk_out& out) {
+            if (!res.stored) return append_out(out);
+            if (!out.len) return;
+            share.resize(out.len);
+            if (bsk_out_to_host(ctx, &out, &share[0], out.len) != BSK_OK) die(bsk_last_error(ctx));
+            if (to_stdout) fwrite(share.data(), 1, share.size(), stdout);
+            else outf.write(share.data(), (std::streamsize)share.size());
+            if (to_file && !outf) die("write " + outp + " failed");
+        };
+        // every match bucket over the pieces of both files, in order, ends in its share of the heads
+        uint64_t file_records[2] = {0, 0};
+        for (auto& pc : pieces) file_records[pc.file] += pc.count;
+        if (bsk_concat_verdict_begin(ctx, file_records) != BSK_OK) die(bsk_last_error(ctx));
+        for (int b = 0; b < n_buckets; ++b) {
+            fill_bucket((uint32_t)bounds[b], (uint32_t)bounds[b + 1]);
+            uint64_t r = 0, f = 0;
+            if (bsk_concat_bucket_finish(ctx, nullptr, &r, &f) != BSK_OK) die(bsk_last_error(ctx));
+            removed += r;
+            flagged += f;
+        }
+        mark(E.mark_buckets);
+        // the weights over the pieces of file 2, the window histogram over those of file 1, the plan of the windows
+        if (bsk_concat_join_begin(ctx, nullptr) != BSK_OK) die(bsk_last_error(ctx));
+        int64_t k = 0;
+        for (int file = 1; file >= 0; --file)
+            for (auto& pc : pieces) {
+                uint64_t cnt = 0;
+                if ((int)pc.file == file && (file ? bsk_concat_weigh_run : bsk_concat_window_hist_run)(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr, &cnt) != BSK_OK)
+                    die(bsk_last_error(ctx));
+            }
+        if (bsk_concat_window_hist_get(ctx, hist.data(), nullptr) != BSK_OK) die(bsk_last_error(ctx));
+        if (bsk_shuffle_plan(hist.data(), budget, bounds.data(), &n_order_buckets) != BSK_OK)
+            die(std::string(bsk_global_error()) + " -- concat: a window bin holds the cost of at most a 4096th of the records of file 1, rounded up to a "
+                                                   "power of two: their text, the text of the records of file 2 with their IDs, and a bound of the joined "
+                                                   "records; an ID with many records in both files fills one");
+        mark("concat: weights, histogram of the windows");
+        uint32_t shift = 0;
+        while (file_records[0] && ((file_records[0] - 1) >> shift) >= kBins) ++shift;
+        for (int b = 0; b < n_order_buckets; ++b) {
+            const uint64_t lo = bounds[b], hi = bounds[b + 1];
+            if (bsk_concat_window_begin(ctx, (uint32_t)lo, (uint32_t)hi) != BSK_OK) die(bsk_last_error(ctx));
+            for (auto& pc : pieces) {
+                // (a piece of file 1 wholly outside the window adds nothing)
+                if (pc.file == 0 && (pc.count == 0 || ((pc.first + pc.count - 1) >> shift) < lo || (pc.first >> shift) >= hi)) continue;
+                if (bsk_concat_window_add(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr) != BSK_OK) die(bsk_last_error(ctx));
+            }
+            bsk_out out;
+            if (bsk_concat_window_finish(ctx, nullptr, &out) != BSK_OK) die(bsk_last_error(ctx));
+            write_share(out);
+        }
+        mark("concat: windows");
+        if (inv.pget("full") == "true") {
+            for (auto& pc : pieces) {
+                if (pc.file != 1) continue;
+                bsk_out out;
+                if (bsk_concat_tail_run(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr, &out) != BSK_OK) die(bsk_last_error(ctx));
+                write_share(out);
+            }
+            mark("concat: tail");
+        }
+        if (to_file) {
+            outf.close();
+            if (!outf) die("write " + outp + " failed");
+        }
+    } else if (pair) {
         const bool unp = inv.pget("save-unpaired") == "true";
         if (!is_dir(outdir) && mkdir(outdir.c_str(), 0755) != 0) die("cannot create directory " + outdir);
         const char* names[4] = {"paired.1", "paired.2", "unpaired.1", "unpaired.2"};
@@ -1324,6 +1413,9 @@ Output run_buckets(const Invocation& inv) {
                     (unsigned long long)removed, (unsigned long long)flagged);
         if (pair)
             fprintf(stderr, "[timing] pair: %llu pair(s), %llu flagged (subject differed from the first of its key group), %d order bucket(s)\n",
+                    (unsigned long long)removed, (unsigned long long)flagged, n_order_buckets);
+        if (concat)
+            fprintf(stderr, "[timing] concat: %llu record(s) with a head, %llu flagged (subject differed from the first of its key group), %d window(s)\n",
                     (unsigned long long)removed, (unsigned long long)flagged, n_order_buckets);
     }
     for (auto& f : files)
@@ -1743,7 +1835,7 @@ static int run_main(int argc, char** argv) {
         store(inv, o, inv.files);
         return 0;
     }
-    if (bucket_budget(use_cmd) > 0) {  // (shuffle, sort, rmdup, rename, common, pair)
+    if (bucket_budget(use_cmd) > 0) {  // (shuffle, sort, rmdup, rename, common, pair, concat)
         // more bytes than a bucket may hold: not loaded whole (a pipe has no size: it takes the whole-file path)
         uint64_t total = 0;
         struct stat sb;
@@ -1751,7 +1843,7 @@ static int run_main(int argc, char** argv) {
             if (stat(f.c_str(), &sb) == 0 && S_ISREG(sb.st_mode)) total += (uint64_t)sb.st_size;
         if (total > bucket_budget(use_cmd)) {
             Output o = run_buckets(inv);
-            if (use_cmd != "pair") store(inv, o, inv.files);  // (pair has written its four files)
+            if (use_cmd != "pair" && !o.stored) store(inv, o, inv.files);  // (pair has written its four files, concat its shares)
             return 0;
         }
     }
@@ -1772,7 +1864,12 @@ static int run_main(int argc, char** argv) {
         const int device = (int)strtol(inv.pget("device").c_str(), nullptr, 10);
         if (bsk_create("Concat", inv.js.c_str(), device, &c) != BSK_OK) die(bsk_global_error());
         bsk_out out;
-        if (bsk_concat_run(c, both.data(), both.size(), n_first, 0, inputs[0].fmt, nullptr, &out) != BSK_OK) die(bsk_last_error(c));
+        const int crc = bsk_concat_run(c, both.data(), both.size(), n_first, 0, inputs[0].fmt, nullptr, &out);
+        if (crc == BSK_ERR_HIP)
+            die(std::string(bsk_last_error(c)) + " -- 'concat': both files (" + std::to_string(both.size()) + " bytes) must fit one GPU next to their grouping tables and "
+                "the output; BSK_CONCAT_BUDGET_BYTES=<bytes> matches them in buckets of the key that hold at most that many bytes of IDs, and joins them in "
+                "windows of file 1 whose records, their mates of file 2 and their joined records are bounded by that many bytes");
+        if (crc != BSK_OK) die(bsk_last_error(c));
         Output o;
         o.fmt = inputs[0].fmt;
         o.text.resize(out.len);

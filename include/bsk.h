@@ -656,6 +656,70 @@ int bsk_pair_order_bucket_add(bsk_ctx* ctx, const void* shard, size_t n, int on_
                               void* stream);
 int bsk_pair_order_bucket_finish(bsk_ctx* ctx, void* stream, bsk_out* out);
 
+/* ---- Concat in buckets of the key: the bytes of bsk_concat_run on file 1 followed by file 2, for files of any size on one
+ * device (PARITY.md CONB).  g is the global record index over file 1 (n1 records), then file 2 (n2); the subject of a record is
+ * its ID under the context's ID rule.  head(g) = the lowest g' < n1 with the subject bytes of g, ~0 when file 1 has none; for a
+ * head h, C[h] = the records b of file 2 with head(b) == h and W[h] = the sum of their text costs t(b) (text + newline; a
+ * wrapped FASTQ shard: its 4-line rewrite).  Two phases:
+ *   match   in buckets of the key, as the match phase of Pair: fine bin, cost of a bin, accumulation of SUBJECTS and key
+ *           grouping are those of the RmDup buckets -- the histogram of a Concat context over the union equals that of an RmDup
+ *           context with default options.  A bucket ends in its share of the verdict: one 64-bit head per record of either
+ *           file, device memory OUTSIDE the budget of the buckets
+ *   join    in windows of file 1.  With s the least shift with (n1 - 1) >> s < 4096, the window bin of record a of file 1 is
+ *           a >> s; a bin costs the sum of cost(a) = t(a) * (1 + C[h]) + 2 * W[h], h = head(a), over its records -- a planning
+ *           bound, not a size; bsk_shuffle_plan plans these too, and refuses a bin above the budget.  A window [lo, hi) of bins
+ *           accumulates its records of file 1 and every record of file 2 whose head is the head of one of them, and runs the
+ *           one call on that: its share of the output.  The output = window 0's share, window 1's, ..., and with Full the tail:
+ *           the records of file 2 without a head, in file order
+ *   bsk_concat_hist_run / _hist_get / _hist_reset    as bsk_rmdup_hist_*, over the shards of file 1, then file 2
+ *   bsk_concat_verdict_begin  heads for file_records[0] + file_records[1] records, no bin decided, the join phase not begun
+ *   bsk_concat_bucket_begin / _add / _finish
+ *                             as bsk_pair_bucket_*, with the same refusals; finish: *n_matched = the records of the bucket that
+ *                             have a head, *n_flagged = the records whose subject differed from the first of their key group
+ *                             (settled on the host by text; more than 2^20 of them in one bucket fail the call).  No match
+ *                             bucket can begin after bsk_concat_join_begin
+ *   bsk_concat_join_begin     once every bin is decided (else BSK_ERR_INVALID_ARG, the message names the first undecided bin):
+ *                             zeroed W and C (16 bytes per record of file 1, outside the budget), the mark bits, the window
+ *                             histogram.  Every call below needs it
+ *   bsk_concat_verdict_get    head[j] of global record first + j, j < count; ~0: none
+ *   bsk_concat_weigh_run      a shard of file 2 under its global first_record: its records counted into W and C, each shard once
+ *   bsk_concat_window_hist_run / _window_hist_get
+ *                             the histogram of the window bins over the shards of file 1; refused until exactly n2 records
+ *                             have been weighed
+ *   bsk_concat_window_begin / _window_add / _window_finish
+ *                             add takes the shards of file 1, then of file 2, in input order under their global first_record (a
+ *                             shard of file 1 wholly outside the window adds nothing and may be left out; a shard of file 1
+ *                             after one of file 2 is BSK_ERR_INVALID_ARG); finish returns the window's share and fails
+ *                             (BSK_ERR_INVALID_ARG) when the window did not receive exactly the records of file 1 of its bins,
+ *                             or has not seen n2 records of file 2.  out=slices is BSK_ERR_UNSUPPORTED
+ *   bsk_concat_tail_run       a shard of file 2 under its global first_record: with Full its records without a head, as the one
+ *                             call prints an unmatched record; without Full an empty result.  out=slices is BSK_ERR_UNSUPPORTED
+ * Every one of them is BSK_ERR_INVALID_ARG, "not a Concat context", on a context of another operator; the bsk_rmdup_*,
+ * bsk_rename_*, bsk_common_* and bsk_pair_* entry points refuse a Concat context likewise.  bsk_concat_run still runs on a
+ * context that has been through the buckets; the 32-bit size of the elements of one record of file 1 remains its limit here. */
+int bsk_concat_hist_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                        void* stream, uint64_t* n_records);
+int bsk_concat_hist_get(bsk_ctx* ctx, uint64_t* bytes, uint64_t* records);
+int bsk_concat_hist_reset(bsk_ctx* ctx);
+int bsk_concat_verdict_begin(bsk_ctx* ctx, const uint64_t file_records[2]);
+int bsk_concat_verdict_get(bsk_ctx* ctx, uint64_t first, uint64_t count, uint64_t* head);
+int bsk_concat_bucket_begin(bsk_ctx* ctx, uint32_t lo_bin, uint32_t hi_bin_exclusive);
+int bsk_concat_bucket_add(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                          void* stream);
+int bsk_concat_bucket_finish(bsk_ctx* ctx, void* stream, uint64_t* n_matched, uint64_t* n_flagged);
+int bsk_concat_join_begin(bsk_ctx* ctx, void* stream);
+int bsk_concat_weigh_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                         void* stream, uint64_t* n_records);
+int bsk_concat_window_hist_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid,
+                               uint64_t first_record, void* stream, uint64_t* n_records);
+int bsk_concat_window_hist_get(bsk_ctx* ctx, uint64_t* bytes, uint64_t* records);
+int bsk_concat_window_begin(bsk_ctx* ctx, uint32_t lo_bin, uint32_t hi_bin_exclusive);
+int bsk_concat_window_add(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                          void* stream);
+int bsk_concat_window_finish(bsk_ctx* ctx, void* stream, bsk_out* out);
+int bsk_concat_tail_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
+                        void* stream, bsk_out* out);
+
 /* ---- HeadGenome (bigseqkit/head_genome.go, bigseqkit-lib/head_genome.go:53-108; options {"MiniCommonWords": 1}; PARITY.md
  * HEADG): the records of the first genome.  The words of a record are the maximal runs of its description other than ' '
  * and '\t'; the prefix is the words of the first record of the input; n_i = leading words of record i equal to the prefix's.
