@@ -256,6 +256,12 @@ SIGNATURES = {
     "bsk_rmdup_dist_flagged_settle": (_i, [_vp, _vp, _sz]),
     "bsk_rmdup_dist_stats": (_i, [_vp, _p(C.c_uint64), _p(C.c_uint64), _p(C.c_uint64)]),
     "bsk_shard_load": (_i, [_i, _u64, _sz, _i, _i, C.POINTER(_vp)]),
+    "bsk_bgzf_probe": (_i, [C.c_char_p, _sz]),
+    "bsk_bgzf_inflate_device": (_i, [_vp, _sz, _i, _p(_vp), _p(_sz)]),
+    "bsk_bgzf_load": (_i, [_i, _i, _i, _p(_vp), _p(_sz)]),
+    "bsk_bgzf_blocks_device": (_i, [_vp, _sz, _i, _p(C.c_uint64), _p(C.c_uint32), _p(C.c_uint32), _sz, _p(_sz)]),
+    "bsk_bgzf_inflate_host": (_i, [C.c_char_p, _sz, _vp, _sz, _p(_sz), _i]),
+    "bsk_selftest_bgzf_crc": (C.c_uint32, [C.c_char_p, _sz]),
     "bsk_synth_record_bytes": (_sz, [_i]),
     "bsk_synth_offset": (_u64, [_i, _u64]),
     "bsk_synth_host": (_i, [_i, _u64, C.c_uint, _u64, _vp, _sz]),

@@ -82,6 +82,100 @@ def ReadFASTQN(path, minPartitions, worker=None):
     return _read(path, FORMAT_FASTQ, minPartitions)
 
 
+# ---- BGZF input (include/bsk.h "BGZF input"; PARITY.md BGZF)
+def BgzfProbe(data):
+    """0: not gzip, 1: BGZF, 2: gzip that is not BGZF -- from the first bytes of a file"""
+    head = bytes(data[:12 + 65535])
+    return int(lib.bsk_bgzf_probe(head, len(head)))
+
+
+def _device_input(data, device):
+    """(tensor or None to keep alive, pointer, bytes) of a compressed input on `device`"""
+    import torch
+    if hasattr(data, "data_ptr"):
+        if not data.is_cuda:
+            data = data.to("cuda:%d" % device)
+        torch.cuda.synchronize(data.device)
+        return data, C.c_void_p(data.data_ptr()), int(data.numel())
+    t = torch.frombuffer(bytearray(data), dtype=torch.uint8).to("cuda:%d" % device) if len(data) else torch.empty(0, dtype=torch.uint8, device="cuda:%d" % device)
+    torch.cuda.synchronize(t.device)
+    return t, C.c_void_p(t.data_ptr() if len(data) else 0), len(data)
+
+
+def _adopt(d_text, n, device):
+    """the library's buffer as a tensor of torch's own (one copy on the device), the library's freed"""
+    import torch
+    out = torch.empty(n, dtype=torch.uint8, device="cuda:%d" % device)
+    try:
+        if n:
+            check(lib.bsk_device_copy(C.c_void_p(out.data_ptr()), d_text, n, 3))  # BSK_COPY_D2D
+    finally:
+        lib.bsk_device_free(d_text)
+    return out
+
+
+def BgzfInflate(data, device=0):
+    """the text of a BGZF file: bytes or a CUDA uint8 tensor in, a CUDA uint8 tensor out, inflated on the device.
+    device=-1: bytes in, bytes out, the same decoder on host threads"""
+    n_text = C.c_size_t()
+    if device < 0:
+        data = bytes(data)
+        check(lib.bsk_bgzf_inflate_host(data, len(data), None, 0, C.byref(n_text), 0))
+        buf = C.create_string_buffer(max(1, n_text.value))
+        check(lib.bsk_bgzf_inflate_host(data, len(data), buf, n_text.value, C.byref(n_text), 0))
+        return buf.raw[:n_text.value]
+    keep, ptr, n = _device_input(data, device)
+    d_text = C.c_void_p()
+    check(lib.bsk_bgzf_inflate_device(ptr, n, device, C.byref(d_text), C.byref(n_text)))
+    del keep
+    return _adopt(d_text, n_text.value, device)
+
+
+def BgzfBlocks(data, device=0):
+    """the block index: [(offset in the file, size of the block, bytes it holds), ...]"""
+    keep, ptr, n = _device_input(data, device)
+    count = C.c_size_t()
+    check(lib.bsk_bgzf_blocks_device(ptr, n, device, None, None, None, 0, C.byref(count)))
+    k = count.value
+    coff, csize, usize = (C.c_uint64 * max(1, k))(), (C.c_uint32 * max(1, k))(), (C.c_uint32 * max(1, k))()
+    check(lib.bsk_bgzf_blocks_device(ptr, n, device, coff, csize, usize, k, C.byref(count)))
+    del keep
+    return [(int(coff[i]), int(csize[i]), int(usize[i])) for i in range(k)]
+
+
+def _format_of(path, first):
+    """the format of a file: its first TEXT byte, else the suffix under a trailing .gz / .bgz"""
+    if first == b">":
+        return FORMAT_FASTA
+    if first == b"@":
+        return FORMAT_FASTQ
+    name = os.fspath(path).lower()
+    for z in (".gz", ".bgz"):
+        if name.endswith(z):
+            name = name[:-len(z)]
+    if name.endswith((".fa", ".fasta", ".fna", ".faa")):
+        return FORMAT_FASTA
+    if name.endswith((".fq", ".fastq")):
+        return FORMAT_FASTQ
+    raise BskError(_lib.BSK_ERR_FORMAT, "%s must be fasta or fastq" % os.fspath(path))
+
+
+def ReadSeqFile(path, device=0):
+    """a FASTA / FASTQ file, plain or BGZF, as a SeqFrame over one shard.  A BGZF file crosses to the device compressed and is
+    inflated there (bsk_bgzf_load); a plain one is read as ReadFASTA / ReadFASTQ read it.  gzip that is not BGZF is refused"""
+    with open(os.fspath(path), "rb") as f:
+        head = f.read(12 + 65535)
+        kind = BgzfProbe(head)
+        if kind == 2:
+            raise BskError(_lib.BSK_ERR_UNSUPPORTED, "%s is gzip but not BGZF: one gzip stream cannot be cut into independent blocks; recompress it with bgzip" % os.fspath(path))
+        if kind == 0:
+            return SeqFrame(_format_of(path, head[:1]), [head + f.read()])
+        d_text, n_text = C.c_void_p(), C.c_size_t()
+        check(lib.bsk_bgzf_load(f.fileno(), device, 0, C.byref(d_text), C.byref(n_text)))
+    t = _adopt(d_text, n_text.value, device)
+    return SeqFrame(_format_of(path, bytes(t[:1].cpu().numpy().tobytes())), [t])
+
+
 class Operator:
     """One plugin operator between Before() and After() (bsk_create .. bsk_destroy)."""
 

@@ -2,6 +2,8 @@
 // point replaces).  Host code only; kernels live in the .hip files.
 #include <hip/hip_runtime_api.h>
 
+#include <unistd.h>
+
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -12,6 +14,7 @@
 #include "../../include/bsk.h"
 #include "anchor.hpp"
 #include "ctx.hpp"
+#include "ops_bgzf.hpp"
 #include "ops_host.hpp"
 #include "ops_host_internal.hpp"
 #include "ops_sample.hpp"
@@ -690,6 +693,56 @@ int bsk_device_copy(void* dst, const void* src, size_t n, int kind) {
     if (hipMemcpy(dst, src, n, k) != hipSuccess) return fail_global(BSK_ERR_HIP, "libbsk: device copy failed");
     return BSK_OK;
 }
+
+// ---- BGZF input (ops_bgzf.hip): thin shells, the text of a failure goes to bsk_global_error()
+int bsk_bgzf_probe(const void* head, size_t n) { return bgzf_probe(head, n); }
+
+int bsk_bgzf_inflate_device(const void* d_comp, size_t n_comp, int device, void** d_text, size_t* n_text) {
+    if (!d_text || !n_text || (!d_comp && n_comp)) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bgzf: null argument");
+    std::string err;
+    const int rc = bgzf_inflate_device(d_comp, n_comp, device, d_text, n_text, nullptr, false, err);
+    return rc == BSK_OK ? rc : fail_global(rc, err);
+}
+
+int bsk_bgzf_load(int fd, int device, int threads, void** d_text, size_t* n_text) {
+    if (!d_text || !n_text || fd < 0) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bgzf: bad arguments");
+    *d_text = nullptr;
+    *n_text = 0;
+    const off_t size = lseek(fd, 0, SEEK_END);
+    if (size < 0) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bgzf: the file cannot be measured (a pipe goes through bsk_bgzf_inflate_host)");
+    void* d_comp = nullptr;
+    int rc = bsk_shard_load(fd, 0, (size_t)size, device, threads, &d_comp);
+    if (rc != BSK_OK) return rc;
+    std::string err;
+    rc = bgzf_inflate_device(d_comp, (size_t)size, device, d_text, n_text, nullptr, false, err);
+    hipFree(d_comp);
+    return rc == BSK_OK ? rc : fail_global(rc, err);
+}
+
+int bsk_bgzf_blocks_device(const void* d_comp, size_t n_comp, int device, uint64_t* coff, uint32_t* csize, uint32_t* usize, size_t cap,
+                           size_t* count) {
+    if (!count || (!d_comp && n_comp) || (cap && (!coff || !csize || !usize))) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bgzf: null argument");
+    std::string err;
+    BgzfIndex ix;
+    const int rc = bgzf_inflate_device(d_comp, n_comp, device, nullptr, nullptr, &ix, true, err);
+    if (rc != BSK_OK) return fail_global(rc, err);
+    *count = ix.coff.size();
+    for (size_t i = 0; i < ix.coff.size() && i < cap; ++i) {
+        coff[i] = ix.coff[i];
+        csize[i] = ix.csize[i];
+        usize[i] = ix.usize[i];
+    }
+    return BSK_OK;
+}
+
+int bsk_bgzf_inflate_host(const void* comp, size_t n_comp, void* out, size_t cap, size_t* n_out, int threads) {
+    if (!n_out || (!comp && n_comp)) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bgzf: null argument");
+    std::string err;
+    const int rc = bgzf_inflate_host(comp, n_comp, out, cap, n_out, threads, err);
+    return rc == BSK_OK ? rc : fail_global(rc, err);
+}
+
+uint32_t bsk_selftest_bgzf_crc(const void* data, size_t n) { return n <= 65536 ? bgzf_crc_chunked((const uint8_t*)data, (uint32_t)n, 1024) : 0; }
 
 void* bsk_host_alloc(size_t n) {
     void* p = nullptr;
@@ -2160,6 +2213,7 @@ int bsk_event_destroy(void* ev) {
 int bsk_profile_enable(bsk_ctx* c, int on) {
     if (!c) return BSK_ERR_INVALID_ARG;
     c->profile = on != 0;
+    bgzf_profile_enable(on != 0);  // (the BGZF calls have no context: their stages are the process's)
     return BSK_OK;
 }
 
@@ -2199,6 +2253,7 @@ int bsk_profile_dump(bsk_ctx* c, char* buf, size_t cap) {
         out += kv.first;
         out += num;
     }
+    out += bgzf_profile_text();  // bgzf_find, bgzf_sizes, bgzf_inflate
     if (c->translate_stream_fallbacks) {  // (not a stage: how often the one-pass translate did not fit and the tables ran instead)
         char num[96];
         snprintf(num, sizeof num, "translate_stream_fallback=0.000000/%llu;", (unsigned long long)c->translate_stream_fallbacks);
@@ -2220,6 +2275,7 @@ int bsk_profile_reset(bsk_ctx* c) {
     uint64_t l;
     bsk_profile_read(c, "", &d, &l);
     c->prof.clear();
+    bgzf_profile_reset();
     c->hg_indexed_bytes = 0;
     return BSK_OK;
 }

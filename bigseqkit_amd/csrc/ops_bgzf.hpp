@@ -1,0 +1,33 @@
+// BGZF input (PARITY.md BGZF): a compressed buffer in device memory becomes the text it holds, one block per wavefront
+// (ops_bgzf.hip), and the same decoder on host threads.  The entry points of the C ABI (capi.cpp) are thin shells of these.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+namespace bsk {
+
+// the blocks of a file, in file order: offset and size of the whole block, and the bytes it holds (ISIZE)
+struct BgzfIndex {
+    std::vector<uint64_t> coff;
+    std::vector<uint32_t> csize, xlen, usize;
+};
+
+// Every function returns a BSK_* code and leaves the text of a failure in `err`.
+// d_comp[0, n) in the memory of `device` -> a new buffer *d_text of *n_text bytes (hipFree).  index (may be null) receives the blocks.
+int bgzf_inflate_device(const void* d_comp, size_t n, int device, void** d_text, size_t* n_text, BgzfIndex* index, bool index_only, std::string& err);
+// the same decoder on `threads` host threads.  cap == 0: only *n_out is set
+int bgzf_inflate_host(const void* comp, size_t n, void* out, size_t cap, size_t* n_out, int threads, std::string& err);
+// 0: not gzip, 1: BGZF, 2: gzip that is not BGZF
+int bgzf_probe(const void* head, size_t n);
+// CRC32 of data[0, n), n <= 65536, the way the kernel takes it: chunks of `chunk` bytes measured from the end, folded with the
+// advance operator (the tests compare it with zlib's)
+uint32_t bgzf_crc_chunked(const uint8_t* data, uint32_t n, uint32_t chunk);
+
+// stages for bsk_profile_dump: "bgzf_find", "bgzf_sizes", "bgzf_inflate" (process-wide: these calls have no context)
+void bgzf_profile_enable(bool on);
+void bgzf_profile_reset();
+std::string bgzf_profile_text();  // "name=ms/launches;" per stage that ran
+
+}  // namespace bsk

@@ -297,13 +297,58 @@ std::string read_file(const std::string& path) {
     return text;
 }
 
-// bigseqkit-cli/helper.go:63-78
-int sniff_format(const std::string& file, const std::string& data) {
+// bigseqkit-cli/helper.go:63-78; `data` is the TEXT of the file -- of a compressed file (PARITY.md BGZF) what it inflates to --
+// and the suffix rule looks under a trailing .gz / .bgz
+int sniff_format(const std::string& file_, const std::string& data) {
+    std::string file = file_;
+    for (const char* z : {".gz", ".bgz"})
+        if (has_suffix(file, {z})) { file.resize(file.size() - strlen(z)); break; }
     if (has_suffix(file, {".fa", ".fna", ".ffn", ".faa", ".frn"})) return BSK_FORMAT_FASTA;
     if (has_suffix(file, {".fq", ".fastq"})) return BSK_FORMAT_FASTQ;
     if (!data.empty() && data[0] == '>') return BSK_FORMAT_FASTA;
     if (!data.empty() && data[0] == '@') return BSK_FORMAT_FASTQ;
     die(" <file> must be fasta or fastq");
+}
+
+// ---- compressed input (PARITY.md BGZF): BGZF is inflated, on the device where the part lives there; any other gzip is refused
+const char* const kPlainGzip = " is gzip but not BGZF: one gzip stream cannot be cut into independent blocks, so it is not read; "
+                               "recompress it with bgzip (gzip -dc FILE | bgzip > FILE.gz) or decompress it first";
+
+// what the first bytes of a regular file are (bsk_bgzf_probe): 0 plain, 1 BGZF, 2 other gzip.  A pipe is 0: it is looked at
+// once it has been read
+int probe_file(const std::string& path) {
+    const int fd = open(path.c_str(), O_RDONLY);
+    if (fd < 0) die("open " + path + ": no such file or directory");
+    struct stat sb;
+    int kind = 0;
+    if (fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode)) {
+        std::string head((size_t)12 + 65535, '\0');
+        const ssize_t got = pread(fd, &head[0], head.size(), 0);
+        kind = got > 0 ? bsk_bgzf_probe(head.data(), (size_t)got) : 0;
+    }
+    close(fd);
+    return kind;
+}
+
+// the paths that cut or stream a FILE by its bytes cannot take a compressed one: said before a device is touched
+void refuse_compressed(const std::vector<std::string>& files, const std::string& where, const std::string& instead) {
+    for (auto& f : files) {
+        const int kind = probe_file(f);
+        if (kind == 2) die(f + kPlainGzip);
+        if (kind == 1) die(f + " is BGZF-compressed, and " + where + " a file by its bytes, which a compressed file does not allow yet; " + instead);
+    }
+}
+
+// `text` as read from a file or a pipe: inflated in place when it is BGZF (host threads, the decoder of the device)
+void inflate_host_text(const std::string& path, std::string& text) {
+    const int kind = bsk_bgzf_probe(text.data(), text.size());
+    if (kind == 2) die(path + kPlainGzip);
+    if (kind != 1) return;
+    size_t n = 0;
+    if (bsk_bgzf_inflate_host(text.data(), text.size(), nullptr, 0, &n, 0) != BSK_OK) die(path + ": " + bsk_global_error());
+    std::string out(n, '\0');
+    if (n && bsk_bgzf_inflate_host(text.data(), text.size(), &out[0], n, &n, 0) != BSK_OK) die(path + ": " + bsk_global_error());
+    text.swap(out);
 }
 
 void usage() {
@@ -727,6 +772,7 @@ std::vector<Part> read_parts(const std::vector<std::string>& files, int device =
         Part p;
         if (device < 0) {
             p.host = read_file(f);
+            inflate_host_text(f, p.host);
             p.fmt = sniff_format(f, p.host);
         } else {
             const int fd = open(f.c_str(), O_RDONLY);
@@ -735,7 +781,23 @@ std::vector<Part> read_parts(const std::vector<std::string>& files, int device =
             if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) {  // (a pipe: read to its end first)
                 close(fd);
                 p.host = read_file(f);
+                inflate_host_text(f, p.host);
                 p.fmt = sniff_format(f, p.host);
+                parts.push_back(std::move(p));
+                continue;
+            }
+            const int kind = probe_file(f);
+            if (kind == 2) die(f + kPlainGzip);
+            if (kind == 1) {  // compressed across PCIe, inflated in HBM: from here on an ordinary device part
+                if (use == "stats" && sb.st_size > 0 && (size_t)sb.st_size >= whole_file_limit())
+                    refuse_compressed({f}, "'stats' streams a file that does not fit one GPU", "decompress it first (bgzip -d), or cut it into files that fit");
+                if (bsk_bgzf_load(fd, device, 0, &p.dptr, &p.n) != BSK_OK)
+                    die(f + ": " + bsk_global_error() + " -- a BGZF file is inflated whole on one device: it and its text must fit there; decompress it first (bgzip -d) to use the paths for larger inputs");
+                close(fd);
+                char first = 0;
+                if (p.n && bsk_device_copy(&first, p.dptr, 1, BSK_COPY_D2H) != BSK_OK) die(bsk_global_error());
+                p.fmt = sniff_format(f, p.n ? std::string(1, first) : std::string());
+                p.owned_alloc = true;
                 parts.push_back(std::move(p));
                 continue;
             }
@@ -988,7 +1050,7 @@ Output run_head_genome(const Invocation& inv) {
         std::string whole;  // (a pipe: read to its end first)
         const uint8_t* text = nullptr;
         size_t size = 0;
-        const bool mapped = fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode);
+        bool mapped = fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode);
         if (mapped) {
             size = (size_t)sb.st_size;
             if (size) {
@@ -1001,6 +1063,14 @@ Output run_head_genome(const Invocation& inv) {
             size = whole.size();
         }
         close(fd);
+        if (size && bsk_bgzf_probe(text, size) != 0) {  // (compressed: inflated on the host, then streamed like a pipe's text)
+            whole.assign((const char*)text, size);
+            if (mapped) munmap((void*)text, size);
+            mapped = false;
+            inflate_host_text(path, whole);
+            text = (const uint8_t*)whole.data();
+            size = whole.size();
+        }
         const int fmt = sniff_format(path, size ? std::string((const char*)text, 1) : std::string());
         res.fmt = fmt;
         size_t piece = pinned ? std::max<size_t>(1, (size_t)strtoull(pinned, nullptr, 10)) : ((size_t)64 << 20);
@@ -1073,6 +1143,7 @@ Output run_buckets(const Invocation& inv) {
         if (inv.files.size() < 2) die("2 files needed");
         if (outdir.empty()) die("out-dir required");
     }
+    refuse_compressed(inv.files, "the buckets of '" + use + "' read", "decompress it first (bgzip -d), or unset the budget if the file and its text fit one GPU");
     const int device = (int)strtol(inv.pget("device").c_str(), nullptr, 10);
     const uint64_t budget = bucket_budget(use);
     constexpr uint32_t kBins = 4096;  // the fine bins of all five (include/bsk.h)
@@ -1434,6 +1505,7 @@ int run_devices(const Invocation& inv) {
     if (inv.files.size() != 1) die("--devices: exactly one input file (it is cut into one shard per GPU)");
     const std::vector<int> devices = parse_devices(inv.pget("devices"));
     const int world = (int)devices.size();
+    refuse_compressed(inv.files, "--devices cuts", "run it on one device (--device N), or decompress it first (bgzip -d)");
     mark("start");
     if (bsk_device_count() <= 0) die("no HIP device visible (the hot path has no CPU fallback)");
     const std::string& path = inv.files[0];
@@ -1826,6 +1898,8 @@ static int run_main(int argc, char** argv) {
             "a worker could not judge its shard before the shards in front of it are done, so --devices is refused");
     if (!inv.pget("devices").empty()) return run_devices(inv);  // several GPUs: worker threads + librccl, in this process
     if (inv.files.empty()) die("no input files (stdin is not supported by the IgnisHPC CLI either)");
+    for (auto& f : inv.files)  // (gzip that is not BGZF is read by no path: said before a device is touched)
+        if (probe_file(f) == 2) die(f + kPlainGzip);
     g_faidx_query = faidx_query;
     const std::string use_cmd = inv.cmd->use;
     const bool joins_on_host = use_cmd == "concat" || use_cmd == "common" || use_cmd == "pair";

@@ -165,6 +165,30 @@ void bsk_host_free(void* p);
  * on streams of their own: reading the file and crossing PCIe overlap, 32 MiB per reader is pinned.  The caller cuts the
  * file at record starts (bsk_find_record_start on a window around size * k / world).  Errors: bsk_global_error(). */
 int bsk_shard_load(int fd, uint64_t offset, size_t n, int device, int threads, void** d_shard);
+
+/* BGZF input (PARITY.md BGZF): what `bgzip` writes, one gzip member per block of at most 64 KiB.  The blocks are independent,
+ * so one wavefront inflates one block; zlib defines the bytes.  Accepted: a file without the empty EOF block, blocks of ISIZE 0
+ * anywhere, extra subfields beside BC, an empty file.  Refused: bytes behind the last block that are no block header, a block
+ * that reaches past the end, ISIZE above 65536, a bad DEFLATE stream, a CRC32 or ISIZE that does not fit the bytes
+ * (BSK_ERR_FORMAT; the text names the block, its offset in the file and the reason), and gzip that is not BGZF
+ * (BSK_ERR_UNSUPPORTED; the text names bgzip).  Errors: bsk_global_error().
+ *   bsk_bgzf_probe           what the first bytes of a file are: 0 not gzip, 1 BGZF (the magic, FLG bit 2, a BC subfield of
+ *                            length 2), 2 gzip that is not BGZF.  18 bytes decide an ordinary header
+ *   bsk_bgzf_inflate_device  d_comp[0, n_comp) in the memory of `device` -> a NEW buffer *d_text of *n_text bytes
+ *                            (bsk_device_free).  An empty input and a lone EOF block give *n_text = 0
+ *   bsk_bgzf_load            bsk_shard_load of the whole file `fd`, inflated; the compressed copy is freed
+ *   bsk_bgzf_blocks_device   the block index: offset and size of every block in the file and the bytes it holds.  *count is
+ *                            always the number of blocks; the arrays (may be NULL with cap 0) receive the first `cap`
+ *   bsk_bgzf_inflate_host    the same decoder on `threads` host threads (<= 0: 8).  cap = 0 asks for the size: *n_out */
+int bsk_bgzf_probe(const void* head, size_t n);
+int bsk_bgzf_inflate_device(const void* d_comp, size_t n_comp, int device, void** d_text, size_t* n_text);
+int bsk_bgzf_load(int fd, int device, int threads, void** d_text, size_t* n_text);
+int bsk_bgzf_blocks_device(const void* d_comp, size_t n_comp, int device, uint64_t* coff, uint32_t* csize, uint32_t* usize, size_t cap,
+                           size_t* count);
+int bsk_bgzf_inflate_host(const void* comp, size_t n_comp, void* out, size_t cap, size_t* n_out, int threads);
+/* CRC32 of data[0, n), n <= 65536, taken as the kernel takes it: chunks of 1 KiB measured from the end, folded with the
+ * "advance by 1 KiB" operator.  For the tests, which compare it with zlib's. */
+uint32_t bsk_selftest_bgzf_crc(const void* data, size_t n);
 int bsk_stats_reset(bsk_ctx* ctx, void* stream); /* zero the ctx-owned vector, error flags and overflow list */
 /* The context's list of sequence lengths >= hist_cap (the part of the reference's map[int64]int64,
  * bigseqkit-lib/stats.go:86, that does not fit the dense vector).  _get copies it to the host (cap 0 + NULL: size
