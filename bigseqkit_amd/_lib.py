@@ -138,12 +138,7 @@ SIGNATURES = {
     "bsk_sample_set_count": (_i, [_vp, C.c_uint64]),
     "bsk_sample_set_first_record": (_i, [_vp, C.c_uint64]),
     "bsk_shuffle_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, _vp, _p(Out)]),
-    "bsk_shuffle_hist_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp, _p(C.c_uint64)]),
-    "bsk_shuffle_hist_get": (_i, [_vp, _p(C.c_uint64), _p(C.c_uint64)]),
-    "bsk_shuffle_hist_reset": (_i, [_vp]),
     "bsk_shuffle_plan": (_i, [_p(C.c_uint64), C.c_uint64, _p(C.c_uint64), _p(C.c_int)]),
-    "bsk_shuffle_bucket_begin": (_i, [_vp, C.c_uint32, C.c_uint32]),
-    "bsk_shuffle_bucket_add": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp]),
     "bsk_shuffle_bucket_finish": (_i, [_vp, _vp, _p(Out)]),
     "bsk_sort_sample_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, C.c_double, _vp, _p(C.c_uint64)]),
     "bsk_sort_sample_reset": (_i, [_vp]),
@@ -152,68 +147,30 @@ SIGNATURES = {
     "bsk_sort_splitters_build": (_i, [_vp, C.c_uint32, _p(C.c_uint32)]),
     "bsk_sort_splitters_set": (_i, [_vp, C.c_char_p, _p(C.c_uint64), C.c_uint32]),
     "bsk_sort_splitters_get": (_i, [_vp, C.c_char_p, C.c_uint64, _p(C.c_uint64), _p(C.c_uint32), _p(C.c_uint64)]),
-    "bsk_sort_hist_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp, _p(C.c_uint64)]),
-    "bsk_sort_hist_get": (_i, [_vp, _p(C.c_uint64), _p(C.c_uint64)]),
-    "bsk_sort_hist_reset": (_i, [_vp]),
-    "bsk_sort_bucket_begin": (_i, [_vp, C.c_uint32, C.c_uint32]),
-    "bsk_sort_bucket_add": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp]),
     "bsk_sort_bucket_finish": (_i, [_vp, _vp, _p(Out)]),
-    "bsk_rmdup_hist_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp, _p(C.c_uint64)]),
-    "bsk_rmdup_hist_get": (_i, [_vp, _p(C.c_uint64), _p(C.c_uint64)]),
-    "bsk_rmdup_hist_reset": (_i, [_vp]),
     "bsk_rmdup_verdict_begin": (_i, [_vp, C.c_uint64]),
     "bsk_rmdup_verdict_get": (_i, [_vp, C.c_uint64, C.c_uint64, _p(C.c_uint8)]),
-    "bsk_rmdup_bucket_begin": (_i, [_vp, C.c_uint32, C.c_uint32]),
-    "bsk_rmdup_bucket_add": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp]),
     "bsk_rmdup_bucket_finish": (_i, [_vp, _vp, _p(C.c_uint64), _p(C.c_uint64)]),
     "bsk_rmdup_emit_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp, _p(Out)]),
-    "bsk_rename_hist_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp, _p(C.c_uint64)]),
-    "bsk_rename_hist_get": (_i, [_vp, _p(C.c_uint64), _p(C.c_uint64)]),
-    "bsk_rename_hist_reset": (_i, [_vp]),
     "bsk_rename_verdict_begin": (_i, [_vp, C.c_uint64]),
     "bsk_rename_verdict_get": (_i, [_vp, C.c_uint64, C.c_uint64, _p(C.c_uint32)]),
-    "bsk_rename_bucket_begin": (_i, [_vp, C.c_uint32, C.c_uint32]),
-    "bsk_rename_bucket_add": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp]),
     "bsk_rename_bucket_finish": (_i, [_vp, _vp, _p(C.c_uint64), _p(C.c_uint64)]),
     "bsk_rename_emit_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp, _p(Out)]),
-    "bsk_common_hist_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp, _p(C.c_uint64)]),
-    "bsk_common_hist_get": (_i, [_vp, _p(C.c_uint64), _p(C.c_uint64)]),
-    "bsk_common_hist_reset": (_i, [_vp]),
     "bsk_common_verdict_begin": (_i, [_vp, _p(C.c_uint64), C.c_uint32]),
     "bsk_common_verdict_get": (_i, [_vp, C.c_uint64, C.c_uint64, _p(C.c_uint8)]),
-    "bsk_common_bucket_begin": (_i, [_vp, C.c_uint32, C.c_uint32]),
-    "bsk_common_bucket_add": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp]),
     "bsk_common_bucket_finish": (_i, [_vp, _vp, _p(C.c_uint64), _p(C.c_uint64)]),
     "bsk_common_emit_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp, _p(Out)]),
-    "bsk_pair_hist_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp, _p(C.c_uint64)]),
-    "bsk_pair_hist_get": (_i, [_vp, _p(C.c_uint64), _p(C.c_uint64)]),
-    "bsk_pair_hist_reset": (_i, [_vp]),
     "bsk_pair_verdict_begin": (_i, [_vp, _p(C.c_uint64)]),
     "bsk_pair_verdict_get": (_i, [_vp, C.c_uint64, C.c_uint64, _p(C.c_uint64)]),
-    "bsk_pair_bucket_begin": (_i, [_vp, C.c_uint32, C.c_uint32]),
-    "bsk_pair_bucket_add": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp]),
     "bsk_pair_bucket_finish": (_i, [_vp, _vp, _p(C.c_uint64), _p(C.c_uint64)]),
     "bsk_pair_order_begin": (_i, [_vp, _vp, _p(C.c_uint64), _p(C.c_int)]),
     "bsk_pair_emit_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp, _p(Out)]),
-    "bsk_pair_order_hist_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp, _p(C.c_uint64)]),
-    "bsk_pair_order_hist_get": (_i, [_vp, _p(C.c_uint64), _p(C.c_uint64)]),
-    "bsk_pair_order_bucket_begin": (_i, [_vp, C.c_uint32, C.c_uint32]),
-    "bsk_pair_order_bucket_add": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp]),
     "bsk_pair_order_bucket_finish": (_i, [_vp, _vp, _p(Out)]),
-    "bsk_concat_hist_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp, _p(C.c_uint64)]),
-    "bsk_concat_hist_get": (_i, [_vp, _p(C.c_uint64), _p(C.c_uint64)]),
-    "bsk_concat_hist_reset": (_i, [_vp]),
     "bsk_concat_verdict_begin": (_i, [_vp, _p(C.c_uint64)]),
     "bsk_concat_verdict_get": (_i, [_vp, C.c_uint64, C.c_uint64, _p(C.c_uint64)]),
-    "bsk_concat_bucket_begin": (_i, [_vp, C.c_uint32, C.c_uint32]),
-    "bsk_concat_bucket_add": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp]),
     "bsk_concat_bucket_finish": (_i, [_vp, _vp, _p(C.c_uint64), _p(C.c_uint64)]),
     "bsk_concat_join_begin": (_i, [_vp, _vp]),
     "bsk_concat_weigh_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp, _p(C.c_uint64)]),
-    "bsk_concat_window_hist_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp, _p(C.c_uint64)]),
-    "bsk_concat_window_hist_get": (_i, [_vp, _p(C.c_uint64), _p(C.c_uint64)]),
-    "bsk_concat_window_begin": (_i, [_vp, C.c_uint32, C.c_uint32]),
-    "bsk_concat_window_add": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp]),
     "bsk_concat_window_finish": (_i, [_vp, _vp, _p(Out)]),
     "bsk_concat_tail_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp, _p(Out)]),
     "bsk_head_genome_run":(_i, [_vp, _vp, _sz, _i, _i, _i64, _vp, _p(Out)]),
@@ -285,6 +242,22 @@ SIGNATURES = {
     "bsk_selftest_rmdup_keys": (_i, [_vp, _p(_u64), _p(_u64), _sz, _p(_sz)]),
     "bsk_selftest_stream_read": (_i, [_vp, _sz, _i, _i, _p(C.c_float)]),
 }
+
+# The key-bucket family: the entry points every prefix has under the same signature (include/bsk.h).  The order buckets of pair
+# have no histogram reset of their own; the windows of concat go without the "bucket_" in their names.
+_BUCKET_STEPS = {
+    "hist_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp, _p(C.c_uint64)]),
+    "hist_get": (_i, [_vp, _p(C.c_uint64), _p(C.c_uint64)]),
+    "hist_reset": (_i, [_vp]),
+    "bucket_begin": (_i, [_vp, C.c_uint32, C.c_uint32]),
+    "bucket_add": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp]),
+}
+for _prefix in ("shuffle", "sort", "rmdup", "rename", "common", "pair", "pair_order", "concat"):
+    for _step, _sig in _BUCKET_STEPS.items():
+        if (_prefix, _step) != ("pair_order", "hist_reset"):
+            SIGNATURES["bsk_%s_%s" % (_prefix, _step)] = _sig
+for _step, _own in (("hist_run", "hist_run"), ("hist_get", "hist_get"), ("bucket_begin", "begin"), ("bucket_add", "add")):
+    SIGNATURES["bsk_concat_window_" + _own] = _BUCKET_STEPS[_step]
 
 for _name, (_res, _args) in SIGNATURES.items():
     _f = getattr(lib, _name)  # AttributeError here == symbol missing from the build

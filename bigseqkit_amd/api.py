@@ -6,6 +6,7 @@ Same entry points, argument meaning and error behaviour as
 sequence of C-ABI calls into libbsk.so (include/bsk.h) instead of IgnisHPC tasks.
 """
 import ctypes as C
+import itertools
 import json
 import os
 
@@ -271,32 +272,71 @@ def _out_bytes(op, out):
 _BUCKET_BINS = 4096   # the fine bins of shuffle, sort and rmdup in buckets: bsk_shuffle_plan plans all three
 
 
-def _count_pass(fn, op, input, *extra):
+# The key-bucket family (shuffle, sort, rmdup, rename, common, pair and its order phase, concat): a command's entry points are
+# bsk_<prefix>_<step> with the same signatures (_lib.py), so one helper per kind of step serves all of them; the public
+# functions further down are one-liners over these.
+def _bsk(prefix, step):
+    return getattr(lib, "bsk_%s_%s" % (prefix, step))
+
+
+def _count_pass(fn, op, input, *extra, counts=None, first=0):
     """fn(ctx, shard ..., first_record, *extra, stream, &n_records) over the shards of `input`, in order, every shard told where
-    it starts: the record count of every shard"""
-    counts, first = [], 0
-    for pid, ptr, n, on_dev, keep in input.partitions():
+    it starts -- the first at global record `first`, the next behind the records the pass counted, or behind counts[j] where
+    the caller knows them: the record count of every shard"""
+    got = []
+    for (pid, ptr, n, on_dev, keep), cnt in zip(input.partitions(), itertools.repeat(None) if counts is None else counts):
         k = C.c_uint64()
         check(fn(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, *extra, None, C.byref(k)), op.ctx)
-        counts.append(k.value)
-        first += k.value
-    return counts
+        got.append(k.value)
+        first += k.value if cnt is None else cnt
+    return got
 
 
-def _hist_get(fn, op):
-    """(bytes[4096], records[4096])"""
+def _hist_get(prefix, op):
+    """bsk_<prefix>_hist_get: (bytes[4096], records[4096])"""
     b, r = (C.c_uint64 * _BUCKET_BINS)(), (C.c_uint64 * _BUCKET_BINS)()
-    check(fn(op.ctx, b, r), op.ctx)
+    check(_bsk(prefix, "hist_get")(op.ctx, b, r), op.ctx)
     return list(b), list(r)
 
 
-def _bucket_adds(begin, add, op, input, counts, lo_bin, hi_bin):
-    """the bucket [lo_bin, hi_bin) opened and every shard of `input` added to it, in order"""
-    check(begin(op.ctx, lo_bin, hi_bin), op.ctx)
-    first = 0
+def _hist_reset(prefix, op):
+    check(_bsk(prefix, "hist_reset")(op.ctx), op.ctx)
+
+
+def _bucket_adds(prefix, op, input, counts, lo_bin, hi_bin, first=0):
+    """bsk_<prefix>_bucket_begin, then _bucket_add of every shard of `input`, in order, the first at global record `first`"""
+    check(_bsk(prefix, "bucket_begin")(op.ctx, lo_bin, hi_bin), op.ctx)
     for (pid, ptr, n, on_dev, keep), cnt in zip(input.partitions(), counts):
-        check(add(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None), op.ctx)
+        check(_bsk(prefix, "bucket_add")(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None), op.ctx)
         first += cnt
+
+
+def _counted_bucket(prefix, op, input, counts, lo_bin, hi_bin):
+    """_bucket_adds, then bsk_<prefix>_bucket_finish: its two counters"""
+    _bucket_adds(prefix, op, input, counts, lo_bin, hi_bin)
+    a, b = C.c_uint64(), C.c_uint64()
+    check(_bsk(prefix, "bucket_finish")(op.ctx, None, C.byref(a), C.byref(b)), op.ctx)
+    return a.value, b.value
+
+
+def _out_bucket(prefix, op, input, counts, lo_bin, hi_bin, first=0):
+    """_bucket_adds, then bsk_<prefix>_bucket_finish: the bytes of its bsk_out"""
+    _bucket_adds(prefix, op, input, counts, lo_bin, hi_bin, first)
+    out = _lib.Out()
+    check(_bsk(prefix, "bucket_finish")(op.ctx, None, C.byref(out)), op.ctx)
+    return _out_bytes(op, out)
+
+
+def _emit_pass(fn, op, input, counts, first=0):
+    """fn(ctx, shard ..., first_record, stream, &out) over the shards of `input`, in order, the first at global record `first`:
+    the outputs, joined"""
+    chunks = []
+    for (pid, ptr, n, on_dev, keep), cnt in zip(input.partitions(), counts):
+        out = _lib.Out()
+        check(fn(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None, C.byref(out)), op.ctx)
+        chunks.append(_out_bytes(op, out))
+        first += cnt
+    return b"".join(chunks)
 
 
 def _run_records(op_name, run_fn, input, o, device=0, stream=None, finish=None):
@@ -568,12 +608,12 @@ def ShuffleHistRun(op, input):
 
 def ShuffleHistGet(op):
     """bsk_shuffle_hist_get: (bytes[4096], records[4096])"""
-    return _hist_get(lib.bsk_shuffle_hist_get, op)
+    return _hist_get("shuffle", op)
 
 
 def ShuffleHistReset(op):
     """bsk_shuffle_hist_reset: the context is about to see another input"""
-    check(lib.bsk_shuffle_hist_reset(op.ctx), op.ctx)
+    _hist_reset("shuffle", op)
 
 
 def ShufflePlan(hist_bytes, budget_bytes):
@@ -587,10 +627,7 @@ def ShufflePlan(hist_bytes, budget_bytes):
 
 def ShuffleBucket(op, input, counts, lo_bin, hi_bin):
     """bsk_shuffle_bucket_begin / _add over the shards of `input` / _finish: the bytes of the bucket [lo_bin, hi_bin)"""
-    _bucket_adds(lib.bsk_shuffle_bucket_begin, lib.bsk_shuffle_bucket_add, op, input, counts, lo_bin, hi_bin)
-    out = _lib.Out()
-    check(lib.bsk_shuffle_bucket_finish(op.ctx, None, C.byref(out)), op.ctx)
-    return _out_bytes(op, out)
+    return _out_bucket("shuffle", op, input, counts, lo_bin, hi_bin)
 
 
 def ShuffleBuckets(input, o=None, budget_bytes=1 << 30, device=0):
@@ -672,19 +709,16 @@ def SortHistRun(op, input):
 
 def SortHistGet(op):
     """bsk_sort_hist_get: (bytes[4096], records[4096])"""
-    return _hist_get(lib.bsk_sort_hist_get, op)
+    return _hist_get("sort", op)
 
 
 def SortHistReset(op):
-    check(lib.bsk_sort_hist_reset(op.ctx), op.ctx)
+    _hist_reset("sort", op)
 
 
 def SortBucket(op, input, counts, lo_bin, hi_bin):
     """bsk_sort_bucket_begin / _add over the shards of `input`, in order / _finish: the sorted bytes of the bucket [lo_bin, hi_bin)"""
-    _bucket_adds(lib.bsk_sort_bucket_begin, lib.bsk_sort_bucket_add, op, input, counts, lo_bin, hi_bin)
-    out = _lib.Out()
-    check(lib.bsk_sort_bucket_finish(op.ctx, None, C.byref(out)), op.ctx)
-    return _out_bytes(op, out)
+    return _out_bucket("sort", op, input, counts, lo_bin, hi_bin)
 
 
 def SortBucketsPlan(op, input, o, budget_bytes, splitters=None, rate=None, device=0):
@@ -734,11 +768,11 @@ def RmDupHistRun(op, input):
 
 def RmDupHistGet(op):
     """bsk_rmdup_hist_get: (bytes[4096], records[4096])"""
-    return _hist_get(lib.bsk_rmdup_hist_get, op)
+    return _hist_get("rmdup", op)
 
 
 def RmDupHistReset(op):
-    check(lib.bsk_rmdup_hist_reset(op.ctx), op.ctx)
+    _hist_reset("rmdup", op)
 
 
 def RmDupVerdictBegin(op, total_records):
@@ -755,21 +789,12 @@ def RmDupVerdictGet(op, first, count):
 
 def RmDupBucket(op, input, counts, lo_bin, hi_bin):
     """bsk_rmdup_bucket_begin / _add over the shards of `input`, in order / _finish: (removed, flagged) of the bucket [lo_bin, hi_bin)"""
-    _bucket_adds(lib.bsk_rmdup_bucket_begin, lib.bsk_rmdup_bucket_add, op, input, counts, lo_bin, hi_bin)
-    removed, flagged = C.c_uint64(), C.c_uint64()
-    check(lib.bsk_rmdup_bucket_finish(op.ctx, None, C.byref(removed), C.byref(flagged)), op.ctx)
-    return removed.value, flagged.value
+    return _counted_bucket("rmdup", op, input, counts, lo_bin, hi_bin)
 
 
 def RmDupEmit(op, input, counts):
     """bsk_rmdup_emit_run over the shards of `input`, in order: the survivors, joined"""
-    chunks, first = [], 0
-    for (pid, ptr, n, on_dev, keep), cnt in zip(input.partitions(), counts):
-        out = _lib.Out()
-        check(lib.bsk_rmdup_emit_run(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None, C.byref(out)), op.ctx)
-        chunks.append(_out_bytes(op, out))
-        first += cnt
-    return b"".join(chunks)
+    return _emit_pass(lib.bsk_rmdup_emit_run, op, input, counts)
 
 
 def RmDupBuckets(input, o=None, budget_bytes=1 << 30, device=0):
@@ -794,11 +819,11 @@ def RenameHistRun(op, input):
 
 def RenameHistGet(op):
     """bsk_rename_hist_get: (bytes[4096], records[4096])"""
-    return _hist_get(lib.bsk_rename_hist_get, op)
+    return _hist_get("rename", op)
 
 
 def RenameHistReset(op):
-    check(lib.bsk_rename_hist_reset(op.ctx), op.ctx)
+    _hist_reset("rename", op)
 
 
 def RenameVerdictBegin(op, total_records):
@@ -815,21 +840,12 @@ def RenameVerdictGet(op, first, count):
 
 def RenameBucket(op, input, counts, lo_bin, hi_bin):
     """bsk_rename_bucket_begin / _add over the shards of `input`, in order / _finish: (renamed, flagged) of the bucket [lo_bin, hi_bin)"""
-    _bucket_adds(lib.bsk_rename_bucket_begin, lib.bsk_rename_bucket_add, op, input, counts, lo_bin, hi_bin)
-    renamed, flagged = C.c_uint64(), C.c_uint64()
-    check(lib.bsk_rename_bucket_finish(op.ctx, None, C.byref(renamed), C.byref(flagged)), op.ctx)
-    return renamed.value, flagged.value
+    return _counted_bucket("rename", op, input, counts, lo_bin, hi_bin)
 
 
 def RenameEmit(op, input, counts):
     """bsk_rename_emit_run over the shards of `input`, in order: the records, renamed, joined"""
-    chunks, first = [], 0
-    for (pid, ptr, n, on_dev, keep), cnt in zip(input.partitions(), counts):
-        out = _lib.Out()
-        check(lib.bsk_rename_emit_run(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None, C.byref(out)), op.ctx)
-        chunks.append(_out_bytes(op, out))
-        first += cnt
-    return b"".join(chunks)
+    return _emit_pass(lib.bsk_rename_emit_run, op, input, counts)
 
 
 def RenameBuckets(input, o=None, budget_bytes=1 << 30, device=0):
@@ -867,11 +883,11 @@ def CommonHistRun(op, inputs):
 
 def CommonHistGet(op):
     """bsk_common_hist_get: (bytes[4096], records[4096])"""
-    return _hist_get(lib.bsk_common_hist_get, op)
+    return _hist_get("common", op)
 
 
 def CommonHistReset(op):
-    check(lib.bsk_common_hist_reset(op.ctx), op.ctx)
+    _hist_reset("common", op)
 
 
 def CommonVerdictBegin(op, file_records):
@@ -891,21 +907,12 @@ def CommonVerdictGet(op, first, count):
 def CommonBucket(op, inputs, counts, lo_bin, hi_bin):
     """bsk_common_bucket_begin / _add over the shards of every file of `inputs`, in order, the first file first / _finish:
     (kept, flagged) of the bucket [lo_bin, hi_bin); `counts` is what CommonHistRun returned"""
-    _bucket_adds(lib.bsk_common_bucket_begin, lib.bsk_common_bucket_add, op, _union_frame(inputs), [k for c in counts for k in c], lo_bin, hi_bin)
-    kept, flagged = C.c_uint64(), C.c_uint64()
-    check(lib.bsk_common_bucket_finish(op.ctx, None, C.byref(kept), C.byref(flagged)), op.ctx)
-    return kept.value, flagged.value
+    return _counted_bucket("common", op, _union_frame(inputs), [k for c in counts for k in c], lo_bin, hi_bin)
 
 
 def CommonEmit(op, input, counts):
     """bsk_common_emit_run over the shards of the FIRST file, in order (`counts`: the record count of each): the kept records, joined"""
-    chunks, first = [], 0
-    for (pid, ptr, n, on_dev, keep), cnt in zip(input.partitions(), counts):
-        out = _lib.Out()
-        check(lib.bsk_common_emit_run(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None, C.byref(out)), op.ctx)
-        chunks.append(_out_bytes(op, out))
-        first += cnt
-    return b"".join(chunks)
+    return _emit_pass(lib.bsk_common_emit_run, op, input, counts)
 
 
 def CommonBuckets(inputA, inputB, o=None, *inputN, budget_bytes=1 << 30, device=0):
@@ -940,11 +947,11 @@ def PairHistRun(op, inputs):
 
 def PairHistGet(op):
     """bsk_pair_hist_get: (bytes[4096], records[4096])"""
-    return _hist_get(lib.bsk_pair_hist_get, op)
+    return _hist_get("pair", op)
 
 
 def PairHistReset(op):
-    check(lib.bsk_pair_hist_reset(op.ctx), op.ctx)
+    _hist_reset("pair", op)
 
 
 def PairVerdictBegin(op, file_records):
@@ -963,10 +970,7 @@ def PairVerdictGet(op, first, count):
 def PairBucket(op, inputs, counts, lo_bin, hi_bin):
     """bsk_pair_bucket_begin / _add over the shards of file 1, then file 2 / _finish: (pairs, flagged) of the match bucket
     [lo_bin, hi_bin); `counts` is what PairHistRun returned"""
-    _bucket_adds(lib.bsk_pair_bucket_begin, lib.bsk_pair_bucket_add, op, _union_frame(inputs), [k for c in counts for k in c], lo_bin, hi_bin)
-    pairs, flagged = C.c_uint64(), C.c_uint64()
-    check(lib.bsk_pair_bucket_finish(op.ctx, None, C.byref(pairs), C.byref(flagged)), op.ctx)
-    return pairs.value, flagged.value
+    return _counted_bucket("pair", op, _union_frame(inputs), [k for c in counts for k in c], lo_bin, hi_bin)
 
 
 def PairOrderBegin(op):
@@ -991,27 +995,18 @@ def PairEmit(op, input, counts, first):
 
 def PairOrderHistRun(op, input, counts, first):
     """bsk_pair_order_hist_run over the shards of file 2, in order, the first of them global record `first`"""
-    for (pid, ptr, n, on_dev, keep), cnt in zip(input.partitions(), counts):
-        k = C.c_uint64()
-        check(lib.bsk_pair_order_hist_run(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None, C.byref(k)), op.ctx)
-        first += cnt
+    _count_pass(lib.bsk_pair_order_hist_run, op, input, counts=counts, first=first)
 
 
 def PairOrderHistGet(op):
     """bsk_pair_order_hist_get: (bytes[4096], records[4096]) of the order bins"""
-    return _hist_get(lib.bsk_pair_order_hist_get, op)
+    return _hist_get("pair_order", op)
 
 
 def PairOrderBucket(op, input, counts, first, lo_bin, hi_bin):
     """bsk_pair_order_bucket_begin / _add over the shards of file 2 / _finish: the share of paired.2 of the order bucket
     [lo_bin, hi_bin)"""
-    check(lib.bsk_pair_order_bucket_begin(op.ctx, lo_bin, hi_bin), op.ctx)
-    for (pid, ptr, n, on_dev, keep), cnt in zip(input.partitions(), counts):
-        check(lib.bsk_pair_order_bucket_add(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None), op.ctx)
-        first += cnt
-    out = _lib.Out()
-    check(lib.bsk_pair_order_bucket_finish(op.ctx, None, C.byref(out)), op.ctx)
-    return _out_bytes(op, out)
+    return _out_bucket("pair_order", op, input, counts, lo_bin, hi_bin, first)
 
 
 def PairBuckets(inputA, inputB, o=None, budget_bytes=1 << 30, device=0, order="auto"):
@@ -1060,11 +1055,11 @@ def ConcatHistRun(op, inputs):
 
 def ConcatHistGet(op):
     """bsk_concat_hist_get: (bytes[4096], records[4096])"""
-    return _hist_get(lib.bsk_concat_hist_get, op)
+    return _hist_get("concat", op)
 
 
 def ConcatHistReset(op):
-    check(lib.bsk_concat_hist_reset(op.ctx), op.ctx)
+    _hist_reset("concat", op)
 
 
 def ConcatVerdictBegin(op, file_records):
@@ -1083,10 +1078,7 @@ def ConcatVerdictGet(op, first, count):
 def ConcatBucket(op, inputs, counts, lo_bin, hi_bin):
     """bsk_concat_bucket_begin / _add over the shards of file 1, then file 2 / _finish: (matched, flagged) of the match bucket
     [lo_bin, hi_bin); `counts` is what ConcatHistRun returned"""
-    _bucket_adds(lib.bsk_concat_bucket_begin, lib.bsk_concat_bucket_add, op, _union_frame(inputs), [k for c in counts for k in c], lo_bin, hi_bin)
-    matched, flagged = C.c_uint64(), C.c_uint64()
-    check(lib.bsk_concat_bucket_finish(op.ctx, None, C.byref(matched), C.byref(flagged)), op.ctx)
-    return matched.value, flagged.value
+    return _counted_bucket("concat", op, _union_frame(inputs), [k for c in counts for k in c], lo_bin, hi_bin)
 
 
 def ConcatJoinBegin(op):
@@ -1094,26 +1086,19 @@ def ConcatJoinBegin(op):
     check(lib.bsk_concat_join_begin(op.ctx, None), op.ctx)
 
 
-def _concat_pass(fn, op, input, counts, first):
-    for (pid, ptr, n, on_dev, keep), cnt in zip(input.partitions(), counts):
-        k = C.c_uint64()
-        check(fn(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None, C.byref(k)), op.ctx)
-        first += cnt
-
-
 def ConcatWeighRun(op, input, counts, first):
     """bsk_concat_weigh_run over the shards of file 2, in order, the first of them global record `first`"""
-    _concat_pass(lib.bsk_concat_weigh_run, op, input, counts, first)
+    _count_pass(lib.bsk_concat_weigh_run, op, input, counts=counts, first=first)
 
 
 def ConcatWindowHistRun(op, input, counts):
     """bsk_concat_window_hist_run over the shards of file 1, in order"""
-    _concat_pass(lib.bsk_concat_window_hist_run, op, input, counts, 0)
+    _count_pass(lib.bsk_concat_window_hist_run, op, input, counts=counts)
 
 
 def ConcatWindowHistGet(op):
     """bsk_concat_window_hist_get: (cost[4096], records[4096]) of the window bins"""
-    return _hist_get(lib.bsk_concat_window_hist_get, op)
+    return _hist_get("concat_window", op)
 
 
 def ConcatWindowShift(n1):
@@ -1145,13 +1130,7 @@ def ConcatWindow(op, inputs, counts, lo_bin, hi_bin):
 def ConcatTail(op, input, counts, first):
     """bsk_concat_tail_run over the shards of file 2, in order, the first of them global record `first`: with Full the records
     of file 2 whose ID file 1 does not have, joined; else empty"""
-    chunks = []
-    for (pid, ptr, n, on_dev, keep), cnt in zip(input.partitions(), counts):
-        out = _lib.Out()
-        check(lib.bsk_concat_tail_run(op.ctx, ptr, n, 1 if on_dev else 0, input.format, pid, first, None, C.byref(out)), op.ctx)
-        chunks.append(_out_bytes(op, out))
-        first += cnt
-    return b"".join(chunks)
+    return _emit_pass(lib.bsk_concat_tail_run, op, input, counts, first)
 
 
 def ConcatBuckets(inputA, inputB, o=None, budget_bytes=1 << 30, device=0):

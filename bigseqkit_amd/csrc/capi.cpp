@@ -1,5 +1,8 @@
 // C ABI of libbsk.so (see include/bsk.h for the reference interface each entry
 // point replaces).  Host code only; kernels live in the .hip files.
+// Every exported function is written out under its name.  The record operators go through record_call / run_record_op; the
+// entry points of the key-bucket family (shuffle, sort, rmdup, rename, common, pair, concat in buckets) are one call each
+// into the helpers behind "the key-bucket family" below, which look the operator up in one row per Op.
 #include <hip/hip_runtime_api.h>
 
 #include <unistd.h>
@@ -1075,42 +1078,116 @@ static int run_record_op(bsk_ctx* c, Op want, const void* shard, size_t n, int o
     });
 }
 
-// ---- the bucket paths of shuffle, sort, rmdup, rename and common (include/bsk.h; the passes are in ops_host_shuffle.cpp,
-// ops_host_sortbuckets.cpp, ops_host_rmdupbuckets.cpp, ops_host_renamebuckets.cpp and ops_host_commonbuckets.cpp, the life cycle
-// of a bucket in the first)
-static int bucket_ctx_check(bsk_ctx* c, Op op, const char* a_name, bool args_ok = true) {  // a_name: "a Sort", "an RmDup"
+// ---- the key-bucket family: the bucket paths of shuffle, sort, rmdup, rename, common, pair and concat (include/bsk.h; the passes
+// are in ops_host_shuffle.cpp, ops_host_sortbuckets.cpp and ops_host_{rmdup,rename,common,pair,concat}buckets.cpp, the life cycle
+// of a bucket in the first).  One row per operator: what a refusal calls its context ("a Sort", "an RmDup") and the bucket state
+// of its key buckets; the order buckets of pair and the windows of concat have states of their own.  Every exported function
+// below is one call into one of the helpers that follow; a refusal that names the entry point takes the name from __func__.
+using BucketStateFn = bsk_ctx::BucketState* (*)(bsk_ctx*);
+static bsk_ctx::BucketState* shuffle_state(bsk_ctx* c) { return &c->shb; }
+static bsk_ctx::BucketState* sort_state(bsk_ctx* c) { return &c->sob; }
+static bsk_ctx::BucketState* rdb_state(bsk_ctx* c) { return &c->rdb; }
+static bsk_ctx::BucketState* pair_order_state(bsk_ctx* c) { return &c->pab.order; }
+static bsk_ctx::BucketState* concat_window_state(bsk_ctx* c) { return &c->cab.win; }
+struct BucketOp {
+    Op op;
+    const char* a_name;
+    BucketStateFn state;
+};
+static const BucketOp& bucket_op(Op op) {
+    static const BucketOp rows[] = {
+        {Op::Shuffle, "a Shuffle", shuffle_state}, {Op::Sort, "a Sort", sort_state},     {Op::RmDup, "an RmDup", rdb_state},
+        {Op::Rename, "a Rename", rdb_state},       {Op::Common, "a Common", rdb_state},  {Op::Pair, "a Pair", rdb_state},
+        {Op::Concat, "a Concat", rdb_state},
+    };
+    for (const BucketOp& r : rows)
+        if (r.op == op) return r;
+    abort();  // (an operator without bucket entry points: a mistake in this file)
+}
+static int bucket_ctx_check(bsk_ctx* c, Op op, bool args_ok = true) {
     if (!c) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: null context");
-    if (c->op != op || !args_ok) return fail(c, BSK_ERR_INVALID_ARG, std::string("libbsk: not ") + a_name + " context");
+    if (c->op != op || !args_ok) return fail(c, BSK_ERR_INVALID_ARG, std::string("libbsk: not ") + bucket_op(op).a_name + " context");
     if (c->device < 0) return fail(c, BSK_ERR_NO_DEVICE, "libbsk: context was created without a device");
     return BSK_OK;
 }
-static int shuffle_ctx_check(bsk_ctx* c) { return bucket_ctx_check(c, Op::Shuffle, "a Shuffle"); }
-static int sort_ctx_check(bsk_ctx* c) { return bucket_ctx_check(c, Op::Sort, "a Sort"); }
-static int rmdup_ctx_check(bsk_ctx* c) { return bucket_ctx_check(c, Op::RmDup, "an RmDup"); }
-static int rename_ctx_check(bsk_ctx* c) { return bucket_ctx_check(c, Op::Rename, "a Rename"); }
-static int common_ctx_check(bsk_ctx* c) { return bucket_ctx_check(c, Op::Common, "a Common"); }
-static int pair_ctx_check(bsk_ctx* c) { return bucket_ctx_check(c, Op::Pair, "a Pair"); }
-static int concat_ctx_check(bsk_ctx* c) { return bucket_ctx_check(c, Op::Concat, "a Concat"); }
-static bool bins_ok(uint32_t lo_bin, uint32_t hi_bin_exclusive) { return lo_bin < hi_bin_exclusive && hi_bin_exclusive <= BUCKET_BINS; }
-// the prologue of a finish that fills a bsk_out
-static int bucket_finish_check(bsk_ctx* c, Op op, const char* a_name, bsk_out* out) {
-    const int rc = bucket_ctx_check(c, op, a_name, out != nullptr);
+static std::string null_argument(const char* symbol, bool is_null) { return is_null ? std::string("libbsk: ") + symbol + ": null argument" : std::string(); }
+// an entry point without a shard: the context check, `refusal` (empty: none), the call scope, body()
+template <class Body>
+static int bucket_call(bsk_ctx* c, Op op, const std::string& refusal, Body body) {
+    const int rc = bucket_ctx_check(c, op);
     if (rc != BSK_OK) return rc;
-    out->d_seg_src = nullptr; out->d_seg_off = nullptr; out->n_segments = 0;
+    if (!refusal.empty()) return fail(c, BSK_ERR_INVALID_ARG, refusal);
+    BSK_ENTER(c);
+    return body();
+}
+// ... that queues kernels whose status it reads: the status words are cleared on `stream` first (a finish that returns two
+// counters, the steps between the phases of pair and concat)
+static int clear_status(bsk_ctx* c, void* stream) {
+    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), (hipStream_t)stream));
     return BSK_OK;
 }
-// A pass of sort, rmdup, rename or common (the buckets of the last two are c->rdb as well) over one shard: record_call, then pass(text, n, stream) through run_multiline -- a wrapped FASTQ shard
-// runs once more as its 4-line rewrite, like bsk_sort_run's and bsk_rmdup_run's.  closes: an error closes the open bucket, here
-// and not in the pass, which the rewrite enters a second time.  The passes of shuffle differ in both: they go through
-// index_record_text, which has the multi-line reader inside, and shuffle_bucket_add closes its bucket itself.
+template <class Body>
+static int bucket_call_cleared(bsk_ctx* c, Op op, void* stream, Body body) {
+    return bucket_call(c, op, "", [&] {
+        const int rc = clear_status(c, stream);
+        return rc != BSK_OK ? rc : body();
+    });
+}
+static int bucket_hist_get_call(bsk_ctx* c, Op op, uint64_t* bytes, uint64_t* records) {
+    return bucket_call(c, op, "", [&] { return bucket_hist_get(c, bucket_op(op).state(c), bytes, records); });
+}
+static int bucket_hist_reset_call(bsk_ctx* c, Op op) {
+    return bucket_call(c, op, "", [&] { return bucket_hist_reset(c, bucket_op(op).state(c)); });
+}
+static int bucket_begin_call(bsk_ctx* c, Op op, const char* symbol, uint32_t lo_bin, uint32_t hi_bin_exclusive, int (*begin)(bsk_ctx*, uint32_t, uint32_t)) {
+    const bool bins_ok = lo_bin < hi_bin_exclusive && hi_bin_exclusive <= BUCKET_BINS;
+    return bucket_call(c, op, bins_ok ? std::string() : std::string("libbsk: ") + symbol + ": the bins must be 0 <= lo < hi <= 4096",
+                       [&] { return begin(c, lo_bin, hi_bin_exclusive); });
+}
+// a finish that fills a bsk_out: the caller's output loses its slices; drops_pending: so does the context's pending result
+// (shuffle, sort); clears_status: as bucket_call_cleared (all but shuffle)
+static int bucket_finish_out(bsk_ctx* c, Op op, void* stream, bsk_out* out, bool drops_pending, bool clears_status,
+                             int (*finish)(bsk_ctx*, hipStream_t, bsk_out*)) {
+    int rc = bucket_ctx_check(c, op, out != nullptr);
+    if (rc != BSK_OK) return rc;
+    out->d_seg_src = nullptr; out->d_seg_off = nullptr; out->n_segments = 0;
+    BSK_ENTER(c);
+    if (drops_pending) c->pend_out.kind = 0;
+    if (clears_status) rc = clear_status(c, stream);
+    return rc != BSK_OK ? rc : finish(c, (hipStream_t)stream, out);
+}
+// A pass of the family over one shard (all but shuffle's): record_call, then pass(text, n, stream) through run_multiline -- a
+// wrapped FASTQ shard runs once more as its 4-line rewrite, like bsk_sort_run's and bsk_rmdup_run's.  closes (null: none): an
+// error closes that bucket, here and not in the pass, which the rewrite enters a second time.  The passes of shuffle differ in
+// both: they go through index_record_text, which has the multi-line reader inside, and shuffle_bucket_add closes its bucket itself.
 template <class Pass>
-static int bucket_pass(bsk_ctx* c, bsk_out* out, Op op, bool args_ok, bool closes, const void* shard, size_t n, int on_device, int format,
+static int bucket_pass(bsk_ctx* c, bsk_out* out, Op op, bool args_ok, BucketStateFn closes, const void* shard, size_t n, int on_device, int format,
                        void* stream, Pass pass) {
     return record_call(c, out, op, args_ok, "", shard, n, on_device, format, stream, CallValues(), [&](const uint8_t* d, hipStream_t st) {
         const int rc = run_multiline(c, [&](const uint8_t* t, const uint64_t* e) { return pass(t, (size_t)e[0], st); }, d, {n}, format, st);
-        if (rc != BSK_OK && closes) bucket_close(op == Op::Sort ? static_cast<bsk_ctx::BucketState*>(&c->sob) : &c->rdb);
+        if (rc != BSK_OK && closes) bucket_close(closes(c));
         return rc;
     });
+}
+// ... behind the context check (sort's passes go without it): a histogram pass, the add of a bucket -- `closes` is the
+// operator's own state unless given --, an emit pass
+template <class Pass>
+static int bucket_hist_pass(bsk_ctx* c, Op op, const void* shard, size_t n, int on_device, int format, void* stream, Pass pass) {
+    const int rc = bucket_ctx_check(c, op);
+    if (rc != BSK_OK) return rc;
+    return bucket_pass(c, nullptr, op, true, nullptr, shard, n, on_device, format, stream, pass);
+}
+template <class Pass>
+static int bucket_add_pass(bsk_ctx* c, Op op, BucketStateFn closes, const void* shard, size_t n, int on_device, int format, void* stream, Pass pass) {
+    const int rc = bucket_ctx_check(c, op);
+    if (rc != BSK_OK) return rc;
+    return bucket_pass(c, nullptr, op, true, closes ? closes : bucket_op(op).state, shard, n, on_device, format, stream, pass);
+}
+template <class Pass>
+static int bucket_emit_pass(bsk_ctx* c, Op op, const void* shard, size_t n, int on_device, int format, void* stream, bsk_out* out, Pass pass) {
+    const int rc = bucket_ctx_check(c, op);
+    if (rc != BSK_OK) return rc;
+    return bucket_pass(c, out, op, out != nullptr, nullptr, shard, n, on_device, format, stream, pass);
 }
 
 extern "C" {
@@ -1304,19 +1381,9 @@ int bsk_shuffle_hist_run(bsk_ctx* c, const void* shard, size_t n, int on_device,
                        [&](const uint8_t* d, hipStream_t st) { return shuffle_hist_device(c, d, n, format, first_record, st, n_records); });
 }
 
-int bsk_shuffle_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) {
-    const int rc = shuffle_ctx_check(c);
-    if (rc != BSK_OK) return rc;
-    BSK_ENTER(c);
-    return bucket_hist_get(c, &c->shb, bytes, records);
-}
+int bsk_shuffle_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) { return bucket_hist_get_call(c, Op::Shuffle, bytes, records); }
 
-int bsk_shuffle_hist_reset(bsk_ctx* c) {
-    const int rc = shuffle_ctx_check(c);
-    if (rc != BSK_OK) return rc;
-    BSK_ENTER(c);
-    return bucket_hist_reset(c, &c->shb);
-}
+int bsk_shuffle_hist_reset(bsk_ctx* c) { return bucket_hist_reset_call(c, Op::Shuffle); }
 
 int bsk_shuffle_plan(const uint64_t* bytes, uint64_t budget_bytes, uint64_t* bounds, int* n_buckets) {
     if (!bytes || !bounds || !n_buckets) return fail(nullptr, BSK_ERR_INVALID_ARG, "libbsk: bsk_shuffle_plan: null argument");
@@ -1339,11 +1406,7 @@ int bsk_shuffle_plan(const uint64_t* bytes, uint64_t budget_bytes, uint64_t* bou
 }
 
 int bsk_shuffle_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin_exclusive) {
-    const int rc = shuffle_ctx_check(c);
-    if (rc != BSK_OK) return rc;
-    if (!bins_ok(lo_bin, hi_bin_exclusive)) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_shuffle_bucket_begin: the bins must be 0 <= lo < hi <= 4096");
-    BSK_ENTER(c);
-    return shuffle_bucket_begin(c, lo_bin, hi_bin_exclusive);
+    return bucket_begin_call(c, Op::Shuffle, __func__, lo_bin, hi_bin_exclusive, shuffle_bucket_begin);
 }
 
 int bsk_shuffle_bucket_add(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
@@ -1353,17 +1416,13 @@ int bsk_shuffle_bucket_add(bsk_ctx* c, const void* shard, size_t n, int on_devic
 }
 
 int bsk_shuffle_bucket_finish(bsk_ctx* c, void* stream, bsk_out* out) {
-    const int rc = bucket_finish_check(c, Op::Shuffle, "a Shuffle", out);
-    if (rc != BSK_OK) return rc;
-    BSK_ENTER(c);
-    c->pend_out.kind = 0;
-    return shuffle_bucket_finish(c, (hipStream_t)stream, out);
+    return bucket_finish_out(c, Op::Shuffle, stream, out, /*drops_pending=*/true, /*clears_status=*/false, shuffle_bucket_finish);
 }
 
 // ---- sort in buckets of the key
 int bsk_sort_sample_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                         double rate, void* stream, uint64_t* n_records) {
-    return bucket_pass(c, nullptr, Op::Sort, true, false, shard, n, on_device, format, stream, [&](const uint8_t* t, size_t m, hipStream_t st) {
+    return bucket_pass(c, nullptr, Op::Sort, true, nullptr, shard, n, on_device, format, stream, [&](const uint8_t* t, size_t m, hipStream_t st) {
         return sort_sample_device(c, t, m, format, first_record, rate, st, n_records);
     });
 }
@@ -1414,7 +1473,7 @@ int bsk_sort_pick_splitters(const uint8_t* keys, const uint64_t* key_offsets, ui
 }
 
 int bsk_sort_splitters_build(bsk_ctx* c, uint32_t max_bins, uint32_t* n_bins) {
-    const int rc = sort_ctx_check(c);
+    const int rc = bucket_ctx_check(c, Op::Sort);
     if (rc != BSK_OK) return rc;
     if (max_bins < 1 || max_bins > BUCKET_BINS) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_sort_splitters_build: max_bins must be 1 .. 4096");
     BSK_ENTER(c);
@@ -1422,7 +1481,7 @@ int bsk_sort_splitters_build(bsk_ctx* c, uint32_t max_bins, uint32_t* n_bins) {
 }
 
 int bsk_sort_splitters_set(bsk_ctx* c, const uint8_t* bytes, const uint64_t* offsets, uint32_t k) {
-    const int rc = sort_ctx_check(c);
+    const int rc = bucket_ctx_check(c, Op::Sort);
     if (rc != BSK_OK) return rc;
     if (k && !offsets) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_sort_splitters_set: null argument");
     for (uint32_t j = 0; j < k; ++j)
@@ -1450,45 +1509,26 @@ int bsk_sort_splitters_get(bsk_ctx* c, uint8_t* bytes, uint64_t bytes_cap, uint6
 
 int bsk_sort_hist_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                       void* stream, uint64_t* n_records) {
-    return bucket_pass(c, nullptr, Op::Sort, true, false, shard, n, on_device, format, stream,
+    return bucket_pass(c, nullptr, Op::Sort, true, nullptr, shard, n, on_device, format, stream,
                        [&](const uint8_t* t, size_t m, hipStream_t st) { return sort_hist_device(c, t, m, format, st, n_records); });
 }
 
-int bsk_sort_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) {
-    const int rc = sort_ctx_check(c);
-    if (rc != BSK_OK) return rc;
-    BSK_ENTER(c);
-    return bucket_hist_get(c, &c->sob, bytes, records);
-}
+int bsk_sort_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) { return bucket_hist_get_call(c, Op::Sort, bytes, records); }
 
-int bsk_sort_hist_reset(bsk_ctx* c) {
-    const int rc = sort_ctx_check(c);
-    if (rc != BSK_OK) return rc;
-    BSK_ENTER(c);
-    return bucket_hist_reset(c, &c->sob);
-}
+int bsk_sort_hist_reset(bsk_ctx* c) { return bucket_hist_reset_call(c, Op::Sort); }
 
 int bsk_sort_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin_exclusive) {
-    const int rc = sort_ctx_check(c);
-    if (rc != BSK_OK) return rc;
-    if (!bins_ok(lo_bin, hi_bin_exclusive)) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_sort_bucket_begin: the bins must be 0 <= lo < hi <= 4096");
-    BSK_ENTER(c);
-    return sort_bucket_begin(c, lo_bin, hi_bin_exclusive);
+    return bucket_begin_call(c, Op::Sort, __func__, lo_bin, hi_bin_exclusive, sort_bucket_begin);
 }
 
 int bsk_sort_bucket_add(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                         void* stream) {
-    return bucket_pass(c, nullptr, Op::Sort, true, true, shard, n, on_device, format, stream,
+    return bucket_pass(c, nullptr, Op::Sort, true, sort_state, shard, n, on_device, format, stream,
                        [&](const uint8_t* t, size_t m, hipStream_t st) { return sort_bucket_add(c, t, m, format, first_record, st); });
 }
 
 int bsk_sort_bucket_finish(bsk_ctx* c, void* stream, bsk_out* out) {
-    const int rc = bucket_finish_check(c, Op::Sort, "a Sort", out);
-    if (rc != BSK_OK) return rc;
-    BSK_ENTER(c);
-    c->pend_out.kind = 0;
-    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), (hipStream_t)stream));
-    return sort_bucket_finish(c, (hipStream_t)stream, out);
+    return bucket_finish_out(c, Op::Sort, stream, out, /*drops_pending=*/true, /*clears_status=*/true, sort_bucket_finish);
 }
 
 int bsk_head_genome_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,
@@ -1536,476 +1576,273 @@ int bsk_rmdup_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int fo
 // ---- rmdup in buckets of the key
 int bsk_rmdup_hist_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                        void* stream, uint64_t* n_records) {
-    const int rcc = rmdup_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    return bucket_pass(c, nullptr, Op::RmDup, true, false, shard, n, on_device, format, stream,
-                       [&](const uint8_t* t, size_t m, hipStream_t st) { return rmdup_hist_device(c, t, m, format, st, n_records); });
+    return bucket_hist_pass(c, Op::RmDup, shard, n, on_device, format, stream,
+                            [&](const uint8_t* t, size_t m, hipStream_t st) { return rmdup_hist_device(c, t, m, format, st, n_records); });
 }
 
-int bsk_rmdup_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) {
-    const int rcc = rmdup_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    BSK_ENTER(c);
-    return bucket_hist_get(c, &c->rdb, bytes, records);
-}
+int bsk_rmdup_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) { return bucket_hist_get_call(c, Op::RmDup, bytes, records); }
 
-int bsk_rmdup_hist_reset(bsk_ctx* c) {
-    const int rcc = rmdup_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    BSK_ENTER(c);
-    return bucket_hist_reset(c, &c->rdb);
-}
+int bsk_rmdup_hist_reset(bsk_ctx* c) { return bucket_hist_reset_call(c, Op::RmDup); }
 
 int bsk_rmdup_verdict_begin(bsk_ctx* c, uint64_t total_records) {
-    const int rcc = rmdup_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    BSK_ENTER(c);
-    return rmdup_verdict_begin(c, total_records);
+    return bucket_call(c, Op::RmDup, "", [&] { return rmdup_verdict_begin(c, total_records); });
 }
 
 int bsk_rmdup_verdict_get(bsk_ctx* c, uint64_t first, uint64_t count, uint8_t* removed) {
-    const int rcc = rmdup_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    if (count && !removed) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_rmdup_verdict_get: null argument");
-    BSK_ENTER(c);
-    return rmdup_verdict_get(c, first, count, removed);
+    return bucket_call(c, Op::RmDup, null_argument(__func__, count && !removed), [&] { return rmdup_verdict_get(c, first, count, removed); });
 }
 
 int bsk_rmdup_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin_exclusive) {
-    const int rcc = rmdup_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    if (!bins_ok(lo_bin, hi_bin_exclusive)) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_rmdup_bucket_begin: the bins must be 0 <= lo < hi <= 4096");
-    BSK_ENTER(c);
-    return rdb_bucket_begin(c, lo_bin, hi_bin_exclusive);
+    return bucket_begin_call(c, Op::RmDup, __func__, lo_bin, hi_bin_exclusive, rdb_bucket_begin);
 }
 
 int bsk_rmdup_bucket_add(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                          void* stream) {
-    const int rcc = rmdup_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    return bucket_pass(c, nullptr, Op::RmDup, true, true, shard, n, on_device, format, stream,
-                       [&](const uint8_t* t, size_t m, hipStream_t st) { return rdb_bucket_add(c, t, m, format, first_record, st); });
+    return bucket_add_pass(c, Op::RmDup, nullptr, shard, n, on_device, format, stream,
+                           [&](const uint8_t* t, size_t m, hipStream_t st) { return rdb_bucket_add(c, t, m, format, first_record, st); });
 }
 
 int bsk_rmdup_bucket_finish(bsk_ctx* c, void* stream, uint64_t* n_removed, uint64_t* n_flagged) {
-    const int rcc = rmdup_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    BSK_ENTER(c);
-    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), (hipStream_t)stream));
-    return rmdup_bucket_finish(c, (hipStream_t)stream, n_removed, n_flagged);
+    return bucket_call_cleared(c, Op::RmDup, stream, [&] { return rmdup_bucket_finish(c, (hipStream_t)stream, n_removed, n_flagged); });
 }
 
 int bsk_rmdup_emit_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                        void* stream, bsk_out* out) {
-    const int rcc = rmdup_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    return bucket_pass(c, out, Op::RmDup, out != nullptr, false, shard, n, on_device, format, stream,
-                       [&](const uint8_t* t, size_t m, hipStream_t st) { return rmdup_emit_device(c, t, m, format, first_record, st, out); });
+    return bucket_emit_pass(c, Op::RmDup, shard, n, on_device, format, stream, out,
+                            [&](const uint8_t* t, size_t m, hipStream_t st) { return rmdup_emit_device(c, t, m, format, first_record, st, out); });
 }
 
 // ---- rename in buckets of the key: the histogram, the begin and the add of a bucket are rmdup's steps on a Rename context
 int bsk_rename_hist_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                         void* stream, uint64_t* n_records) {
-    const int rcc = rename_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    return bucket_pass(c, nullptr, Op::Rename, true, false, shard, n, on_device, format, stream,
-                       [&](const uint8_t* t, size_t m, hipStream_t st) { return rdb_hist_device(c, t, m, format, st, n_records); });
+    return bucket_hist_pass(c, Op::Rename, shard, n, on_device, format, stream,
+                            [&](const uint8_t* t, size_t m, hipStream_t st) { return rdb_hist_device(c, t, m, format, st, n_records); });
 }
 
-int bsk_rename_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) {
-    const int rcc = rename_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    BSK_ENTER(c);
-    return bucket_hist_get(c, &c->rdb, bytes, records);
-}
+int bsk_rename_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) { return bucket_hist_get_call(c, Op::Rename, bytes, records); }
 
-int bsk_rename_hist_reset(bsk_ctx* c) {
-    const int rcc = rename_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    BSK_ENTER(c);
-    return bucket_hist_reset(c, &c->rdb);
-}
+int bsk_rename_hist_reset(bsk_ctx* c) { return bucket_hist_reset_call(c, Op::Rename); }
 
 int bsk_rename_verdict_begin(bsk_ctx* c, uint64_t total_records) {
-    const int rcc = rename_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    BSK_ENTER(c);
-    return rename_verdict_begin(c, total_records);
+    return bucket_call(c, Op::Rename, "", [&] { return rename_verdict_begin(c, total_records); });
 }
 
 int bsk_rename_verdict_get(bsk_ctx* c, uint64_t first, uint64_t count, uint32_t* ord) {
-    const int rcc = rename_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    if (count && !ord) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_rename_verdict_get: null argument");
-    BSK_ENTER(c);
-    return rename_verdict_get(c, first, count, ord);
+    return bucket_call(c, Op::Rename, null_argument(__func__, count && !ord), [&] { return rename_verdict_get(c, first, count, ord); });
 }
 
 int bsk_rename_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin_exclusive) {
-    const int rcc = rename_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    if (!bins_ok(lo_bin, hi_bin_exclusive)) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_rename_bucket_begin: the bins must be 0 <= lo < hi <= 4096");
-    BSK_ENTER(c);
-    return rdb_bucket_begin(c, lo_bin, hi_bin_exclusive);
+    return bucket_begin_call(c, Op::Rename, __func__, lo_bin, hi_bin_exclusive, rdb_bucket_begin);
 }
 
 int bsk_rename_bucket_add(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                           void* stream) {
-    const int rcc = rename_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    return bucket_pass(c, nullptr, Op::Rename, true, true, shard, n, on_device, format, stream,
-                       [&](const uint8_t* t, size_t m, hipStream_t st) { return rdb_bucket_add(c, t, m, format, first_record, st); });
+    return bucket_add_pass(c, Op::Rename, nullptr, shard, n, on_device, format, stream,
+                           [&](const uint8_t* t, size_t m, hipStream_t st) { return rdb_bucket_add(c, t, m, format, first_record, st); });
 }
 
 int bsk_rename_bucket_finish(bsk_ctx* c, void* stream, uint64_t* n_renamed, uint64_t* n_flagged) {
-    const int rcc = rename_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    BSK_ENTER(c);
-    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), (hipStream_t)stream));
-    return rename_bucket_finish(c, (hipStream_t)stream, n_renamed, n_flagged);
+    return bucket_call_cleared(c, Op::Rename, stream, [&] { return rename_bucket_finish(c, (hipStream_t)stream, n_renamed, n_flagged); });
 }
 
 int bsk_rename_emit_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                         void* stream, bsk_out* out) {
-    const int rcc = rename_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    return bucket_pass(c, out, Op::Rename, out != nullptr, false, shard, n, on_device, format, stream,
-                       [&](const uint8_t* t, size_t m, hipStream_t st) { return rename_emit_device(c, t, m, format, first_record, st, out); });
+    return bucket_emit_pass(c, Op::Rename, shard, n, on_device, format, stream, out,
+                            [&](const uint8_t* t, size_t m, hipStream_t st) { return rename_emit_device(c, t, m, format, first_record, st, out); });
 }
 
 // ---- common in buckets of the key: the histogram, the begin and the add of a bucket are rmdup's steps on a Common context,
 // over the shards of every file
 int bsk_common_hist_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                         void* stream, uint64_t* n_records) {
-    const int rcc = common_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    return bucket_pass(c, nullptr, Op::Common, true, false, shard, n, on_device, format, stream,
-                       [&](const uint8_t* t, size_t m, hipStream_t st) { return rdb_hist_device(c, t, m, format, st, n_records); });
+    return bucket_hist_pass(c, Op::Common, shard, n, on_device, format, stream,
+                            [&](const uint8_t* t, size_t m, hipStream_t st) { return rdb_hist_device(c, t, m, format, st, n_records); });
 }
 
-int bsk_common_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) {
-    const int rcc = common_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    BSK_ENTER(c);
-    return bucket_hist_get(c, &c->rdb, bytes, records);
-}
+int bsk_common_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) { return bucket_hist_get_call(c, Op::Common, bytes, records); }
 
-int bsk_common_hist_reset(bsk_ctx* c) {
-    const int rcc = common_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    BSK_ENTER(c);
-    return bucket_hist_reset(c, &c->rdb);
-}
+int bsk_common_hist_reset(bsk_ctx* c) { return bucket_hist_reset_call(c, Op::Common); }
 
 int bsk_common_verdict_begin(bsk_ctx* c, const uint64_t* file_records, uint32_t n_files) {
-    const int rcc = common_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    if (!file_records) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_common_verdict_begin: null argument");
-    if (n_files < 2 || n_files > 64)
-        return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_common_verdict_begin: " + std::to_string(n_files) + " files (2 .. 64 files are compared)");
-    BSK_ENTER(c);
-    return common_verdict_begin(c, file_records, n_files);
+    std::string refusal = null_argument(__func__, !file_records);
+    if (refusal.empty() && (n_files < 2 || n_files > 64))
+        refusal = "libbsk: bsk_common_verdict_begin: " + std::to_string(n_files) + " files (2 .. 64 files are compared)";
+    return bucket_call(c, Op::Common, refusal, [&] { return common_verdict_begin(c, file_records, n_files); });
 }
 
 int bsk_common_verdict_get(bsk_ctx* c, uint64_t first, uint64_t count, uint8_t* kept) {
-    const int rcc = common_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    if (count && !kept) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_common_verdict_get: null argument");
-    BSK_ENTER(c);
-    return common_verdict_get(c, first, count, kept);
+    return bucket_call(c, Op::Common, null_argument(__func__, count && !kept), [&] { return common_verdict_get(c, first, count, kept); });
 }
 
 int bsk_common_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin_exclusive) {
-    const int rcc = common_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    if (!bins_ok(lo_bin, hi_bin_exclusive)) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_common_bucket_begin: the bins must be 0 <= lo < hi <= 4096");
-    BSK_ENTER(c);
-    return rdb_bucket_begin(c, lo_bin, hi_bin_exclusive);
+    return bucket_begin_call(c, Op::Common, __func__, lo_bin, hi_bin_exclusive, rdb_bucket_begin);
 }
 
 int bsk_common_bucket_add(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                           void* stream) {
-    const int rcc = common_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    return bucket_pass(c, nullptr, Op::Common, true, true, shard, n, on_device, format, stream,
-                       [&](const uint8_t* t, size_t m, hipStream_t st) { return rdb_bucket_add(c, t, m, format, first_record, st); });
+    return bucket_add_pass(c, Op::Common, nullptr, shard, n, on_device, format, stream,
+                           [&](const uint8_t* t, size_t m, hipStream_t st) { return rdb_bucket_add(c, t, m, format, first_record, st); });
 }
 
 int bsk_common_bucket_finish(bsk_ctx* c, void* stream, uint64_t* n_kept, uint64_t* n_flagged) {
-    const int rcc = common_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    BSK_ENTER(c);
-    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), (hipStream_t)stream));
-    return common_bucket_finish(c, (hipStream_t)stream, n_kept, n_flagged);
+    return bucket_call_cleared(c, Op::Common, stream, [&] { return common_bucket_finish(c, (hipStream_t)stream, n_kept, n_flagged); });
 }
 
 int bsk_common_emit_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                         void* stream, bsk_out* out) {
-    const int rcc = common_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    return bucket_pass(c, out, Op::Common, out != nullptr, false, shard, n, on_device, format, stream,
-                       [&](const uint8_t* t, size_t m, hipStream_t st) { return common_emit_device(c, t, m, format, first_record, st, out); });
+    return bucket_emit_pass(c, Op::Common, shard, n, on_device, format, stream, out,
+                            [&](const uint8_t* t, size_t m, hipStream_t st) { return common_emit_device(c, t, m, format, first_record, st, out); });
 }
 
 // ---- pair in buckets of the key (ops_host_pairbuckets.cpp): the match phase takes rmdup's steps on a Pair context over file 1
 // followed by file 2; the order phase has a bucket state of its own (c->pab.order), which its add closes when it fails for good
 int bsk_pair_hist_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                       void* stream, uint64_t* n_records) {
-    const int rcc = pair_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    return bucket_pass(c, nullptr, Op::Pair, true, false, shard, n, on_device, format, stream,
-                       [&](const uint8_t* t, size_t m, hipStream_t st) { return rdb_hist_device(c, t, m, format, st, n_records); });
+    return bucket_hist_pass(c, Op::Pair, shard, n, on_device, format, stream,
+                            [&](const uint8_t* t, size_t m, hipStream_t st) { return rdb_hist_device(c, t, m, format, st, n_records); });
 }
 
-int bsk_pair_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) {
-    const int rcc = pair_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    BSK_ENTER(c);
-    return bucket_hist_get(c, &c->rdb, bytes, records);
-}
+int bsk_pair_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) { return bucket_hist_get_call(c, Op::Pair, bytes, records); }
 
-int bsk_pair_hist_reset(bsk_ctx* c) {
-    const int rcc = pair_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    BSK_ENTER(c);
-    return bucket_hist_reset(c, &c->rdb);
-}
+int bsk_pair_hist_reset(bsk_ctx* c) { return bucket_hist_reset_call(c, Op::Pair); }
 
 int bsk_pair_verdict_begin(bsk_ctx* c, const uint64_t* file_records) {
-    const int rcc = pair_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    if (!file_records) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_pair_verdict_begin: null argument");
-    BSK_ENTER(c);
-    return pair_verdict_begin(c, file_records);
+    return bucket_call(c, Op::Pair, null_argument(__func__, !file_records), [&] { return pair_verdict_begin(c, file_records); });
 }
 
 int bsk_pair_verdict_get(bsk_ctx* c, uint64_t first, uint64_t count, uint64_t* pos) {
-    const int rcc = pair_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    if (count && !pos) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_pair_verdict_get: null argument");
-    BSK_ENTER(c);
-    return pair_verdict_get(c, first, count, pos);
+    return bucket_call(c, Op::Pair, null_argument(__func__, count && !pos), [&] { return pair_verdict_get(c, first, count, pos); });
 }
 
 int bsk_pair_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin_exclusive) {
-    const int rcc = pair_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    if (!bins_ok(lo_bin, hi_bin_exclusive)) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_pair_bucket_begin: the bins must be 0 <= lo < hi <= 4096");
-    BSK_ENTER(c);
-    return pair_bucket_begin(c, lo_bin, hi_bin_exclusive);
+    return bucket_begin_call(c, Op::Pair, __func__, lo_bin, hi_bin_exclusive, pair_bucket_begin);
 }
 
 int bsk_pair_bucket_add(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                         void* stream) {
-    const int rcc = pair_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    return bucket_pass(c, nullptr, Op::Pair, true, true, shard, n, on_device, format, stream,
-                       [&](const uint8_t* t, size_t m, hipStream_t st) { return pair_bucket_add(c, t, m, format, first_record, st); });
+    return bucket_add_pass(c, Op::Pair, nullptr, shard, n, on_device, format, stream,
+                           [&](const uint8_t* t, size_t m, hipStream_t st) { return pair_bucket_add(c, t, m, format, first_record, st); });
 }
 
 int bsk_pair_bucket_finish(bsk_ctx* c, void* stream, uint64_t* n_pairs, uint64_t* n_flagged) {
-    const int rcc = pair_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    BSK_ENTER(c);
-    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), (hipStream_t)stream));
-    return pair_bucket_finish(c, (hipStream_t)stream, n_pairs, n_flagged);
+    return bucket_call_cleared(c, Op::Pair, stream, [&] { return pair_bucket_finish(c, (hipStream_t)stream, n_pairs, n_flagged); });
 }
 
 int bsk_pair_order_begin(bsk_ctx* c, void* stream, uint64_t* n_pairs, int* in_mate_order) {
-    const int rcc = pair_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    BSK_ENTER(c);
-    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), (hipStream_t)stream));
-    return pair_order_begin(c, (hipStream_t)stream, n_pairs, in_mate_order);
+    return bucket_call_cleared(c, Op::Pair, stream, [&] { return pair_order_begin(c, (hipStream_t)stream, n_pairs, in_mate_order); });
 }
 
 int bsk_pair_emit_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                       void* stream, bsk_out* outs) {
-    const int rcc = pair_ctx_check(c);
+    // (three outputs: written out, bucket_emit_pass has one)
+    const int rcc = bucket_ctx_check(c, Op::Pair);
     if (rcc != BSK_OK) return rcc;
     if (outs) for (int k = 0; k < 3; ++k) { outs[k].d_seg_src = nullptr; outs[k].d_seg_off = nullptr; outs[k].n_segments = 0; }
-    return bucket_pass(c, nullptr, Op::Pair, outs != nullptr, false, shard, n, on_device, format, stream,
+    return bucket_pass(c, nullptr, Op::Pair, outs != nullptr, nullptr, shard, n, on_device, format, stream,
                        [&](const uint8_t* t, size_t m, hipStream_t st) { return pair_emit_device(c, t, m, format, first_record, st, outs); });
 }
 
 int bsk_pair_order_hist_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                             void* stream, uint64_t* n_records) {
-    const int rcc = pair_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    return bucket_pass(c, nullptr, Op::Pair, true, false, shard, n, on_device, format, stream, [&](const uint8_t* t, size_t m, hipStream_t st) {
+    return bucket_hist_pass(c, Op::Pair, shard, n, on_device, format, stream, [&](const uint8_t* t, size_t m, hipStream_t st) {
         return pair_order_hist_device(c, t, m, format, first_record, st, n_records);
     });
 }
 
 int bsk_pair_order_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) {
-    const int rcc = pair_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    BSK_ENTER(c);
-    return pair_order_hist_get(c, bytes, records);
+    return bucket_call(c, Op::Pair, "", [&] { return pair_order_hist_get(c, bytes, records); });
 }
 
 int bsk_pair_order_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin_exclusive) {
-    const int rcc = pair_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    if (!bins_ok(lo_bin, hi_bin_exclusive))
-        return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_pair_order_bucket_begin: the bins must be 0 <= lo < hi <= 4096");
-    BSK_ENTER(c);
-    return pair_order_bucket_begin(c, lo_bin, hi_bin_exclusive);
+    return bucket_begin_call(c, Op::Pair, __func__, lo_bin, hi_bin_exclusive, pair_order_bucket_begin);
 }
 
 int bsk_pair_order_bucket_add(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                               void* stream) {
-    const int rcc = pair_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    // (bucket_pass with the bucket state of the order phase: an error closes c->pab.order, not c->rdb)
-    return record_call(c, nullptr, Op::Pair, true, "", shard, n, on_device, format, stream, CallValues(), [&](const uint8_t* d, hipStream_t st) {
-        const int rc = run_multiline(c, [&](const uint8_t* t, const uint64_t* e) { return pair_order_bucket_add(c, t, (size_t)e[0], format, first_record, st); },
-                                     d, {n}, format, st);
-        if (rc != BSK_OK) bucket_close(&c->pab.order);
-        return rc;
-    });
+    // (an error closes the bucket of the order phase, c->pab.order, not c->rdb)
+    return bucket_add_pass(c, Op::Pair, pair_order_state, shard, n, on_device, format, stream,
+                           [&](const uint8_t* t, size_t m, hipStream_t st) { return pair_order_bucket_add(c, t, m, format, first_record, st); });
 }
 
 int bsk_pair_order_bucket_finish(bsk_ctx* c, void* stream, bsk_out* out) {
-    const int rcc = bucket_finish_check(c, Op::Pair, "a Pair", out);
-    if (rcc != BSK_OK) return rcc;
-    BSK_ENTER(c);
-    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), (hipStream_t)stream));
-    return pair_order_bucket_finish(c, (hipStream_t)stream, out);
+    return bucket_finish_out(c, Op::Pair, stream, out, /*drops_pending=*/false, /*clears_status=*/true, pair_order_bucket_finish);
 }
 
 // ---- concat in buckets of the key (ops_host_concatbuckets.cpp): the match phase takes rmdup's steps on a Concat context over
 // file 1 followed by file 2; the join phase has a bucket state of its own (c->cab.win), which its add closes when it fails
 int bsk_concat_hist_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                         void* stream, uint64_t* n_records) {
-    const int rcc = concat_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    return bucket_pass(c, nullptr, Op::Concat, true, false, shard, n, on_device, format, stream,
-                       [&](const uint8_t* t, size_t m, hipStream_t st) { return rdb_hist_device(c, t, m, format, st, n_records); });
+    return bucket_hist_pass(c, Op::Concat, shard, n, on_device, format, stream,
+                            [&](const uint8_t* t, size_t m, hipStream_t st) { return rdb_hist_device(c, t, m, format, st, n_records); });
 }
 
-int bsk_concat_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) {
-    const int rcc = concat_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    BSK_ENTER(c);
-    return bucket_hist_get(c, &c->rdb, bytes, records);
-}
+int bsk_concat_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) { return bucket_hist_get_call(c, Op::Concat, bytes, records); }
 
-int bsk_concat_hist_reset(bsk_ctx* c) {
-    const int rcc = concat_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    BSK_ENTER(c);
-    return bucket_hist_reset(c, &c->rdb);
-}
+int bsk_concat_hist_reset(bsk_ctx* c) { return bucket_hist_reset_call(c, Op::Concat); }
 
 int bsk_concat_verdict_begin(bsk_ctx* c, const uint64_t* file_records) {
-    const int rcc = concat_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    if (!file_records) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_concat_verdict_begin: null argument");
-    BSK_ENTER(c);
-    return concat_verdict_begin(c, file_records);
+    return bucket_call(c, Op::Concat, null_argument(__func__, !file_records), [&] { return concat_verdict_begin(c, file_records); });
 }
 
 int bsk_concat_verdict_get(bsk_ctx* c, uint64_t first, uint64_t count, uint64_t* head) {
-    const int rcc = concat_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    if (count && !head) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_concat_verdict_get: null argument");
-    BSK_ENTER(c);
-    return concat_verdict_get(c, first, count, head);
+    return bucket_call(c, Op::Concat, null_argument(__func__, count && !head), [&] { return concat_verdict_get(c, first, count, head); });
 }
 
 int bsk_concat_bucket_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin_exclusive) {
-    const int rcc = concat_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    if (!bins_ok(lo_bin, hi_bin_exclusive)) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_concat_bucket_begin: the bins must be 0 <= lo < hi <= 4096");
-    BSK_ENTER(c);
-    return concat_bucket_begin(c, lo_bin, hi_bin_exclusive);
+    return bucket_begin_call(c, Op::Concat, __func__, lo_bin, hi_bin_exclusive, concat_bucket_begin);
 }
 
 int bsk_concat_bucket_add(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                           void* stream) {
-    const int rcc = concat_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    return bucket_pass(c, nullptr, Op::Concat, true, true, shard, n, on_device, format, stream,
-                       [&](const uint8_t* t, size_t m, hipStream_t st) { return concat_bucket_add(c, t, m, format, first_record, st); });
+    return bucket_add_pass(c, Op::Concat, nullptr, shard, n, on_device, format, stream,
+                           [&](const uint8_t* t, size_t m, hipStream_t st) { return concat_bucket_add(c, t, m, format, first_record, st); });
 }
 
 int bsk_concat_bucket_finish(bsk_ctx* c, void* stream, uint64_t* n_matched, uint64_t* n_flagged) {
-    const int rcc = concat_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    BSK_ENTER(c);
-    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), (hipStream_t)stream));
-    return concat_bucket_finish(c, (hipStream_t)stream, n_matched, n_flagged);
+    return bucket_call_cleared(c, Op::Concat, stream, [&] { return concat_bucket_finish(c, (hipStream_t)stream, n_matched, n_flagged); });
 }
 
 int bsk_concat_join_begin(bsk_ctx* c, void* stream) {
-    const int rcc = concat_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    BSK_ENTER(c);
-    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), (hipStream_t)stream));
-    return concat_join_begin(c, (hipStream_t)stream);
+    return bucket_call_cleared(c, Op::Concat, stream, [&] { return concat_join_begin(c, (hipStream_t)stream); });
 }
 
 int bsk_concat_weigh_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                          void* stream, uint64_t* n_records) {
-    const int rcc = concat_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    return bucket_pass(c, nullptr, Op::Concat, true, false, shard, n, on_device, format, stream, [&](const uint8_t* t, size_t m, hipStream_t st) {
+    return bucket_hist_pass(c, Op::Concat, shard, n, on_device, format, stream, [&](const uint8_t* t, size_t m, hipStream_t st) {
         return concat_weigh_device(c, t, m, format, first_record, st, n_records);
     });
 }
 
 int bsk_concat_window_hist_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                                void* stream, uint64_t* n_records) {
-    const int rcc = concat_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    return bucket_pass(c, nullptr, Op::Concat, true, false, shard, n, on_device, format, stream, [&](const uint8_t* t, size_t m, hipStream_t st) {
+    return bucket_hist_pass(c, Op::Concat, shard, n, on_device, format, stream, [&](const uint8_t* t, size_t m, hipStream_t st) {
         return concat_window_hist_device(c, t, m, format, first_record, st, n_records);
     });
 }
 
 int bsk_concat_window_hist_get(bsk_ctx* c, uint64_t* bytes, uint64_t* records) {
-    const int rcc = concat_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    BSK_ENTER(c);
-    return concat_window_hist_get(c, bytes, records);
+    return bucket_call(c, Op::Concat, "", [&] { return concat_window_hist_get(c, bytes, records); });
 }
 
 int bsk_concat_window_begin(bsk_ctx* c, uint32_t lo_bin, uint32_t hi_bin_exclusive) {
-    const int rcc = concat_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    if (!bins_ok(lo_bin, hi_bin_exclusive)) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: bsk_concat_window_begin: the bins must be 0 <= lo < hi <= 4096");
-    BSK_ENTER(c);
-    return concat_window_begin(c, lo_bin, hi_bin_exclusive);
+    return bucket_begin_call(c, Op::Concat, __func__, lo_bin, hi_bin_exclusive, concat_window_begin);
 }
 
 int bsk_concat_window_add(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                           void* stream) {
-    const int rcc = concat_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    // (bucket_pass with the bucket state of the join phase: an error closes c->cab.win, not c->rdb)
-    return record_call(c, nullptr, Op::Concat, true, "", shard, n, on_device, format, stream, CallValues(), [&](const uint8_t* d, hipStream_t st) {
-        const int rc = run_multiline(c, [&](const uint8_t* t, const uint64_t* e) { return concat_window_add(c, t, (size_t)e[0], format, first_record, st); },
-                                     d, {n}, format, st);
-        if (rc != BSK_OK) bucket_close(&c->cab.win);
-        return rc;
-    });
+    // (an error closes the window of the join phase, c->cab.win, not c->rdb)
+    return bucket_add_pass(c, Op::Concat, concat_window_state, shard, n, on_device, format, stream,
+                           [&](const uint8_t* t, size_t m, hipStream_t st) { return concat_window_add(c, t, m, format, first_record, st); });
 }
 
 int bsk_concat_window_finish(bsk_ctx* c, void* stream, bsk_out* out) {
-    const int rcc = bucket_finish_check(c, Op::Concat, "a Concat", out);
-    if (rcc != BSK_OK) return rcc;
-    BSK_ENTER(c);
-    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, 8 * sizeof(uint64_t), (hipStream_t)stream));
-    return concat_window_finish(c, (hipStream_t)stream, out);
+    return bucket_finish_out(c, Op::Concat, stream, out, /*drops_pending=*/false, /*clears_status=*/true, concat_window_finish);
 }
 
 int bsk_concat_tail_run(bsk_ctx* c, const void* shard, size_t n, int on_device, int format, int64_t pid, uint64_t first_record,
                         void* stream, bsk_out* out) {
-    const int rcc = concat_ctx_check(c);
-    if (rcc != BSK_OK) return rcc;
-    return bucket_pass(c, out, Op::Concat, out != nullptr, false, shard, n, on_device, format, stream,
-                       [&](const uint8_t* t, size_t m, hipStream_t st) { return concat_tail_device(c, t, m, format, first_record, st, out); });
+    return bucket_emit_pass(c, Op::Concat, shard, n, on_device, format, stream, out,
+                            [&](const uint8_t* t, size_t m, hipStream_t st) { return concat_tail_device(c, t, m, format, first_record, st, out); });
 }
 
 // ---- rmdup across ranks: the phases between which the caller runs the all-to-all exchanges (include/bsk.h)

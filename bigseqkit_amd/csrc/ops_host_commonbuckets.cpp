@@ -3,7 +3,8 @@
 // grouping down to first[] are those of `rmdup` in buckets of the key (ops_host_rmdupbuckets.cpp: rdb_hist_device,
 // rdb_bucket_begin, rdb_bucket_add, rdb_group_keys), on the same state c->rdb over the union of the files; the kernels of what a
 // bucket decides are in ops_common_buckets.hip, and the emit ends as common_run_device does (launch_seq_size, finish_sizes,
-// emit_records).
+// emit_records).  The verdict opens with rdb_verdict_open, its bits are read by rdb_verdict_bits, the finish is
+// rdb_bucket_finish around comb_bucket_decide (rdb_flagged_read / rdb_flagged_settle), and the emit ends in rdb_emit_tail.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -37,21 +38,7 @@ int common_verdict_begin(bsk_ctx* c, const uint64_t* file_records, uint32_t n_fi
         total += file_records[f];
         sums[f] = total;
     }
-    const uint64_t words = (file_records[0] + 31) / 32 + 1;
-    HIP_TRYX(c, hipDeviceSynchronize());
-    if (words > B.bits_words || !B.d_bits) {
-        if (B.d_bits) HIP_TRYX(c, hipFree(B.d_bits));
-        B.d_bits = nullptr;
-        B.bits_words = 0;
-        HIP_TRYX(c, hipMalloc((void**)&B.d_bits, words * sizeof(uint32_t)));
-        B.bits_words = words;
-    }
-    HIP_TRYX(c, hipMemset(B.d_bits, 0, words * sizeof(uint32_t)));
-    B.total_records = total;
-    B.file_sums = std::move(sums);
-    B.verdict = true;
-    std::fill(B.decided.begin(), B.decided.end(), (uint8_t)0);
-    return BSK_OK;
+    return rdb_verdict_open(c, &B.d_bits, &B.bits_words, (file_records[0] + 31) / 32 + 1, std::move(sums));
 }
 
 int common_verdict_get(bsk_ctx* c, uint64_t first, uint64_t count, uint8_t* kept) {
@@ -67,15 +54,7 @@ int common_verdict_get(bsk_ctx* c, uint64_t first, uint64_t count, uint8_t* kept
         return BSK_ERR_INVALID_ARG;
     }
     if (count == 0) return BSK_OK;
-    const uint64_t w0 = first >> 5, w1 = (first + count - 1) >> 5;
-    std::vector<uint32_t> words(w1 - w0 + 1);
-    HIP_TRYX(c, hipDeviceSynchronize());
-    HIP_TRYX(c, hipMemcpy(words.data(), B.d_bits + w0, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    for (uint64_t j = 0; j < count; ++j) {
-        const uint64_t g = first + j;
-        kept[j] = (uint8_t)((words[(g >> 5) - w0] >> (g & 31u)) & 1u);
-    }
-    return BSK_OK;
+    return rdb_verdict_bits(c, B.d_bits, first, count, kept);
 }
 
 // ---- one bucket
@@ -140,36 +119,17 @@ static int comb_bucket_decide(bsk_ctx* c, hipStream_t st, uint64_t* n_kept, uint
         Timed t(c, "k_comb_decide", st);
         HIP_TRYX(c, launch_comb_decide(first, B.d_draw, d_masks, N, full, B.file_sums[0], B.d_bits, d_kept, st));
     }
-    uint32_t m = 0;
-    HIP_TRYX(c, hipMemcpyAsync(&m, c->d_xflag, sizeof m, hipMemcpyDeviceToHost, st));
-    rc = ctl_readback(c, st);  // (the synchronisation also ends the copy out of file_sums)
+    rc = rdb_flagged_read(c, st, n_kept, n_flagged);  // (the synchronisation also ends the copy out of file_sums)
     if (rc != BSK_OK) return rc;
-    *n_kept = c->fin(bsk_ctx::FIN_AUX0);
-    *n_flagged = m;
-    if (m > RDB_FLAG_MAX) return rdb_too_many_flagged(c);
-    if (m) {
-        Timed t(c, "comb_settle_flagged", st);
-        uint64_t more = 0;
-        rc = comb_settle_flagged(c, m, full, st, &more);
-        if (rc != BSK_OK) return rc;
-        *n_kept += more;
-    }
+    rc = rdb_flagged_settle(c, *n_flagged, "comb_settle_flagged", st, n_kept,
+                            [&](bsk_ctx*, uint32_t m, hipStream_t, uint64_t* more) { return comb_settle_flagged(c, m, full, st, more); });
+    if (rc != BSK_OK) return rc;
     HIP_TRYX(c, hipStreamSynchronize(st));  // (the arena is the next call's)
     return BSK_OK;
 }
 
 int common_bucket_finish(bsk_ctx* c, hipStream_t st, uint64_t* n_kept, uint64_t* n_flagged) {
-    bsk_ctx::RmDupBuckets& B = c->rdb;
-    int rc = bucket_require_open(c, B, "common", "finish");
-    if (rc != BSK_OK) return rc;
-    uint64_t kept = 0, flagged = 0;
-    rc = comb_bucket_decide(c, st, &kept, &flagged);
-    if (n_kept) *n_kept = kept;
-    if (n_flagged) *n_flagged = flagged;
-    if (rc == BSK_OK)
-        for (uint32_t b = B.lo; b < B.hi; ++b) B.decided[b] = 1;
-    bucket_close(&B);
-    return rc;
+    return rdb_bucket_finish(c, st, n_kept, n_flagged, comb_bucket_decide);
 }
 
 // ---- the emit pass: the kept records of a shard of the first file, in order, each as common_run_device prints a record
@@ -213,15 +173,7 @@ int common_emit_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, u
     out->len = 0;
     out->records = 0;
     if (total == 0) return BSK_OK;
-    rc = ensure_out(c, total);
-    if (rc != BSK_OK) return rc;
-    apply_long(c, &F);
-    rc = emit_records(c, d_buf, n, F, total, kept, st);
-    if (rc != BSK_OK) return rc;
-    out->d_data = c->d_out;
-    out->len = total;
-    out->records = kept;
-    return BSK_OK;
+    return rdb_emit_tail(c, d_buf, n, &F, total, kept, st, out);
 }
 
 }  // namespace bsk

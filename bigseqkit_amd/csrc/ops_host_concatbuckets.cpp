@@ -7,7 +7,8 @@
 //           BucketAccumulate, packed): the weights W and C of the heads over file 2, the window histogram of the costs over file 1,
 //           and per window the records of file 1 of its bins followed by the records of file 2 that they pull in -- on which
 //           concat_run_device runs: the window's share of the output.  The tail (Full) filters a shard of file 2 by "no head"
-// The kernels are in ops_concat_buckets.hip.
+// The kernels are in ops_concat_buckets.hip.  A match bucket finishes in rdb_bucket_finish around catb_bucket_decide
+// (rdb_flagged_read / rdb_flagged_settle); the verdict is opened here, not by rdb_verdict_open: see concat_verdict_begin.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -69,6 +70,7 @@ int concat_verdict_begin(bsk_ctx* c, const uint64_t* file_records) {
     if (rc != BSK_OK) return rc;
     const uint64_t n1 = file_records[0], n2 = file_records[1];
     if (n2 > ~n1) return catb_fail(c, "verdict_begin", "the sum of file_records does not fit 64 bits");
+    // (written out, not rdb_verdict_open: 64-bit words of 0xFF, and none to write for an empty input)
     HIP_TRYX(c, hipDeviceSynchronize());
     rc = grow(c, &P.d_head, &P.head_cap, n1 + n2);
     if (rc != BSK_OK) return rc;
@@ -152,35 +154,13 @@ static int catb_bucket_decide(bsk_ctx* c, hipStream_t st, uint64_t* n_matched, u
         HIP_TRYX(c, launch_catb_verify(B.d_acc, B.d_off, B.d_len, B.d_draw, first, N, B.file_sums[0], c->cab.d_head, c->d_xflag,
                                        (uint32_t)RDB_FLAG_MAX, d_matched, st));
     }
-    uint32_t m = 0;
-    HIP_TRYX(c, hipMemcpyAsync(&m, c->d_xflag, sizeof m, hipMemcpyDeviceToHost, st));
-    rc = ctl_readback(c, st);  // (the arena is the next call's)
+    rc = rdb_flagged_read(c, st, n_matched, n_flagged);  // (the arena is the next call's)
     if (rc != BSK_OK) return rc;
-    *n_matched = c->fin(bsk_ctx::FIN_AUX0);
-    *n_flagged = m;
-    if (m > RDB_FLAG_MAX) return rdb_too_many_flagged(c);
-    if (m) {
-        Timed t(c, "catb_settle_flagged", st);
-        uint64_t more = 0;
-        rc = catb_settle_flagged(c, m, st, &more);
-        if (rc != BSK_OK) return rc;
-        *n_matched += more;
-    }
-    return BSK_OK;
+    return rdb_flagged_settle(c, *n_flagged, "catb_settle_flagged", st, n_matched, catb_settle_flagged);
 }
 
 int concat_bucket_finish(bsk_ctx* c, hipStream_t st, uint64_t* n_matched, uint64_t* n_flagged) {
-    bsk_ctx::RmDupBuckets& B = c->rdb;
-    int rc = bucket_require_open(c, B, "concat", "finish");
-    if (rc != BSK_OK) return rc;
-    uint64_t matched = 0, flagged = 0;
-    rc = catb_bucket_decide(c, st, &matched, &flagged);
-    if (n_matched) *n_matched = matched;
-    if (n_flagged) *n_flagged = flagged;
-    if (rc == BSK_OK)
-        for (uint32_t b = B.lo; b < B.hi; ++b) B.decided[b] = 1;
-    bucket_close(&B);
-    return rc;
+    return rdb_bucket_finish(c, st, n_matched, n_flagged, catb_bucket_decide);
 }
 
 // ---- the join phase

@@ -171,10 +171,28 @@ int bucket_require_open(bsk_ctx* c, const bsk_ctx::BucketState& B, const char* o
 int bucket_in_order(bsk_ctx* c, const bsk_ctx::BucketState& B, const char* op, uint64_t first_record);
 int bucket_too_many(bsk_ctx* c, const char* op);  // UNSUPPORTED: 2^32 or more records in one bucket of <op>
 inline void bucket_close(bsk_ctx::BucketState* B) { B->open = false; bucket_acc_clear(B); }
-// The steps of a bucket of `rmdup` that a bucket of `rename` and one of `common` take as well (ops_host_rmdupbuckets.cpp; all on
-// c->rdb, the messages name the operator of the context -- rdb_op_name: "rmdup" / "rename" / "common"):
+// The steps of a bucket of `rmdup` that the buckets of `rename` and `common` and the match buckets of `pair` and `concat` take
+// as well (ops_host_rmdupbuckets.cpp; all on c->rdb, the messages name the operator of the context -- rdb_op_name: "rmdup" /
+// "rename" / "common" / "pair" / "concat"):
 //   rdb_params          the subject of a record: rmdup's options (common's are the same three), or for rename the ID / the whole
 //                 header (ByName) as it stands
+//   rdb_verdict_open    the body of a *_verdict_begin behind the operator's own checks: the device is idle; *d_arr holds
+//                 `words` zeroed 32-bit words (d_bits of rmdup, common and pair; d_ord of rename) and *cap says so; file_sums
+//                 (one file: {total_records}) and total_records = its last entry are recorded, the verdict exists and no bin is
+//                 decided.  What else an operator keeps (rename's count, the fields of PairBuckets) it sets itself afterwards.
+//                 concat's d_head is 64-bit words of 0xFF and none for an empty input: it stays with concat
+//   rdb_bucket_finish   bsk_<op>_bucket_finish: an open bucket is required; decide(c, st, &counted, &flagged) runs; the two
+//                 counters go to the caller (null: not wanted) whatever decide returned; a decided bucket marks its bins; the
+//                 bucket closes
+//   rdb_flagged_read / rdb_flagged_settle   the middle of every decide, in two halves because `rename` and `pair` queue the
+//                 kernels of their members between them: _read brings back m = c->d_xflag[0] with the control words in ONE
+//                 synchronisation, *counted = FIN_AUX0 (what the verify kernel counted), *n_flagged = m, and refuses more than
+//                 RDB_FLAG_MAX; _settle (m != 0) runs settle(c, m, st, &more) under the Timed stage and adds `more` to *counted.
+//                 Neither synchronises at its end: what a decide does there is its own (rmdup: nothing)
+//   rdb_verdict_bits    bits [first, first + count) of the bitmap d_bits as bytes (0 / 1); count != 0, the caller has checked
+//                 the range
+//   rdb_emit_tail       the end of an emit pass that prints records as Format(LineWidth) does: the block for `total` bytes,
+//                 apply_long, emit_records, `out` filled
 //   rdb_group_keys      the open bucket (B.n > 0): first[i] = the lowest accumulated index under the key of record i, at *o_first
 //                 of the arena *A (carved and reserved there; more may be taken behind it with arena_reserve_keep); c->d_xflag
 //                 holds RDB_FLAG_MAX + 1 words, the count in front zeroed
@@ -194,6 +212,22 @@ int rdb_flagged_texts(bsk_ctx* c, uint32_t m, hipStream_t st, const RdbSettle& s
 int rdb_too_many_flagged(bsk_ctx* c);
 int rdb_emit_ready(bsk_ctx* c);
 int rdb_emit_in_range(bsk_ctx* c, uint64_t first_record, uint64_t N);
+using RdbDecide = int (*)(bsk_ctx* c, hipStream_t st, uint64_t* n_counted, uint64_t* n_flagged);
+int rdb_verdict_open(bsk_ctx* c, uint32_t** d_arr, uint64_t* cap, uint64_t words, std::vector<uint64_t> file_sums);
+int rdb_bucket_finish(bsk_ctx* c, hipStream_t st, uint64_t* n_counted, uint64_t* n_flagged, RdbDecide decide);
+int rdb_flagged_read(bsk_ctx* c, hipStream_t st, uint64_t* counted, uint64_t* n_flagged);
+template <class Settle>
+inline int rdb_flagged_settle(bsk_ctx* c, uint64_t m, const char* stage, hipStream_t st, uint64_t* counted, Settle settle) {
+    if (!m) return BSK_OK;
+    Timed t(c, stage, st);
+    uint64_t more = 0;
+    const int rc = settle(c, (uint32_t)m, st, &more);
+    if (rc != BSK_OK) return rc;
+    *counted += more;
+    return BSK_OK;
+}
+int rdb_verdict_bits(bsk_ctx* c, const uint32_t* d_bits, uint64_t first, uint64_t count, uint8_t* bytes);
+int rdb_emit_tail(bsk_ctx* c, const uint8_t* d_buf, size_t n, SeqParams* F, uint64_t total, uint64_t kept, hipStream_t st, bsk_out* out);
 // The tail of `rename` (ops_host_next.cpp), shared by rename_run_device and the emit pass of the buckets: before, c->table and
 // the text view `tt` of the shard, ren_ord[i] = the ordinal of record i (0: the record leaves as Format(LineWidth) prints it).
 // The sizes, their scan, the block and the emit -- one kernel over all records when `many` of them are renamed, else

@@ -9,7 +9,9 @@
 //           BucketAccumulate): a bucket prints its run of paired.2.  Not needed when file 2 is in mate order: the emit pass
 //           prints paired.2 then, as a filter of file 2
 // The emit pass filters a shard of either file by the bits, as pair_run_device prints its outputs 0, 2 and 3.  The kernels
-// are in ops_pair_buckets.hip.
+// are in ops_pair_buckets.hip.  The verdict of the match phase opens with rdb_verdict_open (both bitmaps in one array), a match
+// bucket finishes in rdb_bucket_finish around pairb_bucket_decide, which reads the control words twice: rdb_flagged_read for the
+// members and the flagged records, and once more behind the scatter for its pairs.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -59,17 +61,13 @@ int pair_verdict_begin(bsk_ctx* c, const uint64_t* file_records) {
     const uint64_t n1 = file_records[0], n2 = file_records[1];
     if (n2 > ~n1) return pairb_fail(c, "verdict_begin", "the sum of file_records does not fit 64 bits");
     const uint64_t words1 = (n1 + 31) / 32 + 1, words2 = (n2 + 31) / 32 + 1, words = words1 + words2;
-    HIP_TRYX(c, hipDeviceSynchronize());
-    if (words > B.bits_words || !B.d_bits) {
-        if (B.d_bits) HIP_TRYX(c, hipFree(B.d_bits));
-        B.d_bits = nullptr;
-        B.bits_words = 0;
-        HIP_TRYX(c, hipMalloc((void**)&B.d_bits, words * sizeof(uint32_t)));
-        B.bits_words = words;
-    }
-    HIP_TRYX(c, hipMemset(B.d_bits, 0, words * sizeof(uint32_t)));
-    rc = grow(c, &P.d_mates, &P.mates_cap, n2);
+    rc = rdb_verdict_open(c, &B.d_bits, &B.bits_words, words, {n1, n1 + n2});
     if (rc != BSK_OK) return rc;
+    rc = grow(c, &P.d_mates, &P.mates_cap, n2);
+    if (rc != BSK_OK) {
+        B.verdict = false;  // (rdb_verdict_open has put one in place: without its mate words it must not be used)
+        return rc;
+    }
     P.d_bits2 = B.d_bits + words1;
     P.words1 = words1;
     P.words2 = words2;
@@ -78,10 +76,6 @@ int pair_verdict_begin(bsk_ctx* c, const uint64_t* file_records) {
     P.pairs = 0;
     P.shift = 0;
     P.first2 = ~0ull;
-    B.total_records = n1 + n2;
-    B.file_sums = {n1, n1 + n2};
-    B.verdict = true;
-    std::fill(B.decided.begin(), B.decided.end(), (uint8_t)0);
     return BSK_OK;
 }
 
@@ -194,13 +188,9 @@ static int pairb_bucket_decide(bsk_ctx* c, hipStream_t st, uint64_t* n_pairs, ui
         Timed t(c, "k_pairb_verify", st);
         HIP_TRYX(c, launch_pairb_verify(B.d_acc, B.d_off, B.d_len, first, N, d_list, d_members, c->d_xflag, (uint32_t)RDB_FLAG_MAX, st));
     }
-    uint32_t m = 0;
-    HIP_TRYX(c, hipMemcpyAsync(&m, c->d_xflag, sizeof m, hipMemcpyDeviceToHost, st));
-    rc = ctl_readback(c, st);
+    uint64_t members = 0;
+    rc = rdb_flagged_read(c, st, &members, n_flagged);
     if (rc != BSK_OK) return rc;
-    const uint64_t members = c->fin(bsk_ctx::FIN_AUX0);
-    *n_flagged = m;
-    if (m > RDB_FLAG_MAX) return rdb_too_many_flagged(c);
     if (members) {
         // the flagged records are not in the list: a member meets only the records of its own text
         const uint64_t first2 = std::min<uint64_t>(P.first2, N);  // (no record of file 2 in the bucket: every member is of file 1)
@@ -212,31 +202,14 @@ static int pairb_bucket_decide(bsk_ctx* c, hipStream_t st, uint64_t* n_pairs, ui
         Timed t(c, "k_pairb_scatter", st);
         HIP_TRYX(c, launch_pairb_scatter(d_state, d_partner, B.d_draw, N, B.file_sums[0], B.d_bits, P.d_bits2, P.d_mates, d_pairs, st));
     }
-    rc = ctl_readback(c, st);  // (the arena is the next call's)
+    rc = ctl_readback(c, st);  // (the control words a second time, for the pairs of the scatter; the arena is the next call's)
     if (rc != BSK_OK) return rc;
     *n_pairs = c->fin(bsk_ctx::FIN_AUX1);
-    if (m) {
-        Timed t(c, "pairb_settle_flagged", st);
-        uint64_t more = 0;
-        rc = pairb_settle_flagged(c, m, st, &more);
-        if (rc != BSK_OK) return rc;
-        *n_pairs += more;
-    }
-    return BSK_OK;
+    return rdb_flagged_settle(c, *n_flagged, "pairb_settle_flagged", st, n_pairs, pairb_settle_flagged);
 }
 
 int pair_bucket_finish(bsk_ctx* c, hipStream_t st, uint64_t* n_pairs, uint64_t* n_flagged) {
-    bsk_ctx::RmDupBuckets& B = c->rdb;
-    int rc = bucket_require_open(c, B, "pair", "finish");
-    if (rc != BSK_OK) return rc;
-    uint64_t pairs = 0, flagged = 0;
-    rc = pairb_bucket_decide(c, st, &pairs, &flagged);
-    if (n_pairs) *n_pairs = pairs;
-    if (n_flagged) *n_flagged = flagged;
-    if (rc == BSK_OK)
-        for (uint32_t b = B.lo; b < B.hi; ++b) B.decided[b] = 1;
-    bucket_close(&B);
-    return rc;
+    return rdb_bucket_finish(c, st, n_pairs, n_flagged, pairb_bucket_decide);
 }
 
 // ---- the rank step

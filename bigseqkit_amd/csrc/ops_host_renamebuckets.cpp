@@ -3,7 +3,8 @@
 // grouping down to first[] are those of `rmdup` in buckets of the key (ops_host_rmdupbuckets.cpp: rdb_hist_device,
 // rdb_bucket_begin, rdb_bucket_add, rdb_group_keys), on the same state c->rdb; the kernels of what a bucket decides are in
 // ops_rename_buckets.hip, the ordinals of the members come from ops_group.hpp, and the emit ends with the tail of
-// rename_run_device (rename_emit).
+// rename_run_device (rename_emit).  The verdict opens with rdb_verdict_open (on d_ord), the finish is rdb_bucket_finish around
+// renb_bucket_decide, whose middle is rdb_flagged_read / rdb_flagged_settle with the kernels of the members between them.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -25,21 +26,11 @@ namespace bsk {
 // ---- the verdict
 int rename_verdict_begin(bsk_ctx* c, uint64_t total_records) {
     bsk_ctx::RmDupBuckets& B = c->rdb;
-    const int rc = bucket_require_closed(c, B, "rename", "verdict_begin");
+    int rc = bucket_require_closed(c, B, "rename", "verdict_begin");
     if (rc != BSK_OK) return rc;
-    HIP_TRYX(c, hipDeviceSynchronize());
-    if (total_records + 1 > B.ord_cap || !B.d_ord) {
-        if (B.d_ord) HIP_TRYX(c, hipFree(B.d_ord));
-        B.d_ord = nullptr;
-        B.ord_cap = 0;
-        HIP_TRYX(c, hipMalloc((void**)&B.d_ord, (total_records + 1) * sizeof(uint32_t)));
-        B.ord_cap = total_records + 1;
-    }
-    HIP_TRYX(c, hipMemset(B.d_ord, 0, (total_records + 1) * sizeof(uint32_t)));
-    B.total_records = total_records;
-    B.verdict = true;
+    rc = rdb_verdict_open(c, &B.d_ord, &B.ord_cap, total_records + 1, {total_records});
+    if (rc != BSK_OK) return rc;
     B.renamed = 0;
-    std::fill(B.decided.begin(), B.decided.end(), (uint8_t)0);
     return BSK_OK;
 }
 
@@ -118,14 +109,9 @@ static int renb_bucket_decide(bsk_ctx* c, hipStream_t st, uint64_t* n_renamed, u
         Timed t(c, "k_renb_verify", st);
         HIP_TRYX(c, launch_renb_verify(B.d_acc, B.d_off, B.d_len, first, N, d_list, d_members, c->d_xflag, (uint32_t)RDB_FLAG_MAX, st));
     }
-    uint32_t m = 0;
-    HIP_TRYX(c, hipMemcpyAsync(&m, c->d_xflag, sizeof m, hipMemcpyDeviceToHost, st));
-    rc = ctl_readback(c, st);
+    rc = rdb_flagged_read(c, st, n_renamed, n_flagged);
     if (rc != BSK_OK) return rc;
-    const uint64_t members = c->fin(bsk_ctx::FIN_AUX0);
-    *n_renamed = members;
-    *n_flagged = m;
-    if (m > RDB_FLAG_MAX) return rdb_too_many_flagged(c);
+    const uint64_t members = *n_renamed;
     if (members) {
         // the flagged records are not in the list: a member counts only the earlier records of its own text
         {
@@ -136,30 +122,17 @@ static int renb_bucket_decide(bsk_ctx* c, hipStream_t st, uint64_t* n_renamed, u
         Timed t(c, "k_renb_scatter", st);
         HIP_TRYX(c, launch_renb_scatter(d_ord, B.d_draw, N, B.d_ord, st));
     }
-    if (m) {
-        Timed t(c, "renb_settle_flagged", st);
-        uint64_t more = 0;
-        rc = renb_settle_flagged(c, m, st, &more);
-        if (rc != BSK_OK) return rc;
-        *n_renamed += more;
-    }
+    rc = rdb_flagged_settle(c, *n_flagged, "renb_settle_flagged", st, n_renamed, renb_settle_flagged);
+    if (rc != BSK_OK) return rc;
     HIP_TRYX(c, hipStreamSynchronize(st));  // (the arena is the next call's)
     return BSK_OK;
 }
 
 int rename_bucket_finish(bsk_ctx* c, hipStream_t st, uint64_t* n_renamed, uint64_t* n_flagged) {
-    bsk_ctx::RmDupBuckets& B = c->rdb;
-    int rc = bucket_require_open(c, B, "rename", "finish");
-    if (rc != BSK_OK) return rc;
-    uint64_t renamed = 0, flagged = 0;
-    rc = renb_bucket_decide(c, st, &renamed, &flagged);
-    if (n_renamed) *n_renamed = renamed;
-    if (n_flagged) *n_flagged = flagged;
-    if (rc == BSK_OK) {
-        B.renamed += renamed;
-        for (uint32_t b = B.lo; b < B.hi; ++b) B.decided[b] = 1;
-    }
-    bucket_close(&B);
+    uint64_t renamed = 0;
+    if (!n_renamed) n_renamed = &renamed;  // (wanted here either way: a refused finish still leaves the caller's word alone)
+    const int rc = rdb_bucket_finish(c, st, n_renamed, n_flagged, renb_bucket_decide);
+    if (rc == BSK_OK) c->rdb.renamed += *n_renamed;
     return rc;
 }
 

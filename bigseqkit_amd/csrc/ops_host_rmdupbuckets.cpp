@@ -4,7 +4,9 @@
 // with the tail of rmdup_dist_emit.
 // `rename` in buckets of the key (ops_host_renamebuckets.cpp; PARITY.md RENB) groups by the same subject under the same key: the
 // steps down to first[] -- rdb_hist_device, rdb_bucket_begin, rdb_bucket_add, rdb_group_keys -- and rdb_flagged_texts serve both
-// operators on c->rdb (declared in ops_host_internal.hpp); their messages name the operator of the context.  `common` in buckets
+// operators on c->rdb (declared in ops_host_internal.hpp); their messages name the operator of the context.  So do the steps
+// around what a bucket decides, which this file owns for the whole family: rdb_verdict_open, rdb_bucket_finish,
+// rdb_flagged_read / rdb_flagged_settle, rdb_verdict_bits and rdb_emit_tail (documented there as well).  `common` in buckets
 // of the key (ops_host_commonbuckets.cpp; PARITY.md COMB) takes the same steps over the union of its files, and so does the
 // match phase of `pair` in buckets of the key (ops_host_pairbuckets.cpp; PARITY.md PAIRB) over its two, and that of `concat` in
 // buckets of the key (ops_host_concatbuckets.cpp; PARITY.md CONB).
@@ -98,23 +100,35 @@ int rdb_hist_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipS
 }
 
 // ---- the verdict
+int rdb_verdict_open(bsk_ctx* c, uint32_t** d_arr, uint64_t* cap, uint64_t words, std::vector<uint64_t> file_sums) {
+    bsk_ctx::RmDupBuckets& B = c->rdb;
+    HIP_TRYX(c, hipDeviceSynchronize());
+    const int rc = grow(c, d_arr, cap, words);
+    if (rc != BSK_OK) return rc;
+    HIP_TRYX(c, hipMemset(*d_arr, 0, words * sizeof(uint32_t)));
+    B.total_records = file_sums.back();
+    B.file_sums = std::move(file_sums);
+    B.verdict = true;
+    std::fill(B.decided.begin(), B.decided.end(), (uint8_t)0);
+    return BSK_OK;
+}
+
 int rmdup_verdict_begin(bsk_ctx* c, uint64_t total_records) {
     bsk_ctx::RmDupBuckets& B = c->rdb;
     const int rc = bucket_require_closed(c, B, "rmdup", "verdict_begin");
     if (rc != BSK_OK) return rc;
-    const uint64_t words = (total_records + 31) / 32 + 1;
+    return rdb_verdict_open(c, &B.d_bits, &B.bits_words, (total_records + 31) / 32 + 1, {total_records});
+}
+
+int rdb_verdict_bits(bsk_ctx* c, const uint32_t* d_bits, uint64_t first, uint64_t count, uint8_t* bytes) {
+    const uint64_t w0 = first >> 5, w1 = (first + count - 1) >> 5;
+    std::vector<uint32_t> words(w1 - w0 + 1);
     HIP_TRYX(c, hipDeviceSynchronize());
-    if (words > B.bits_words || !B.d_bits) {
-        if (B.d_bits) HIP_TRYX(c, hipFree(B.d_bits));
-        B.d_bits = nullptr;
-        B.bits_words = 0;
-        HIP_TRYX(c, hipMalloc((void**)&B.d_bits, words * sizeof(uint32_t)));
-        B.bits_words = words;
+    HIP_TRYX(c, hipMemcpy(words.data(), d_bits + w0, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (uint64_t j = 0; j < count; ++j) {
+        const uint64_t g = first + j;
+        bytes[j] = (uint8_t)((words[(g >> 5) - w0] >> (g & 31u)) & 1u);
     }
-    HIP_TRYX(c, hipMemset(B.d_bits, 0, words * sizeof(uint32_t)));
-    B.total_records = total_records;
-    B.verdict = true;
-    std::fill(B.decided.begin(), B.decided.end(), (uint8_t)0);
     return BSK_OK;
 }
 
@@ -130,15 +144,7 @@ int rmdup_verdict_get(bsk_ctx* c, uint64_t first, uint64_t count, uint8_t* remov
         return BSK_ERR_INVALID_ARG;
     }
     if (count == 0) return BSK_OK;
-    const uint64_t w0 = first >> 5, w1 = (first + count - 1) >> 5;
-    std::vector<uint32_t> words(w1 - w0 + 1);
-    HIP_TRYX(c, hipDeviceSynchronize());
-    HIP_TRYX(c, hipMemcpy(words.data(), B.d_bits + w0, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    for (uint64_t j = 0; j < count; ++j) {
-        const uint64_t g = first + j;
-        removed[j] = (uint8_t)((words[(g >> 5) - w0] >> (g & 31u)) & 1u);
-    }
-    return BSK_OK;
+    return rdb_verdict_bits(c, B.d_bits, first, count, removed);
 }
 
 // ---- one bucket
@@ -353,35 +359,37 @@ static int rdb_bucket_decide(bsk_ctx* c, hipStream_t st, uint64_t* n_removed, ui
         Timed t(c, "k_rdb_verify", st);
         HIP_TRYX(c, launch_rdb_verify(B.d_acc, B.d_off, B.d_len, B.d_draw, first, N, B.d_bits, c->d_xflag, (uint32_t)RDB_FLAG_MAX, d_removed, st));
     }
-    uint32_t m = 0;
-    HIP_TRYX(c, hipMemcpyAsync(&m, c->d_xflag, sizeof m, hipMemcpyDeviceToHost, st));
-    rc = ctl_readback(c, st);
+    rc = rdb_flagged_read(c, st, n_removed, n_flagged);
     if (rc != BSK_OK) return rc;
-    *n_removed = c->fin(bsk_ctx::FIN_AUX0);
-    *n_flagged = m;
-    if (m > RDB_FLAG_MAX) return rdb_too_many_flagged(c);
-    if (m) {
-        Timed t(c, "rdb_settle_flagged", st);
-        uint64_t losers = 0;
-        rc = rdb_settle_flagged(c, m, st, &losers);
-        if (rc != BSK_OK) return rc;
-        *n_removed += losers;
-    }
-    return BSK_OK;
+    return rdb_flagged_settle(c, *n_flagged, "rdb_settle_flagged", st, n_removed, rdb_settle_flagged);  // (no synchronisation behind it)
 }
 
-int rmdup_bucket_finish(bsk_ctx* c, hipStream_t st, uint64_t* n_removed, uint64_t* n_flagged) {
-    bsk_ctx::RmDupBuckets& B = c->rdb;
-    int rc = bucket_require_open(c, B, "rmdup", "finish");
+int rdb_flagged_read(bsk_ctx* c, hipStream_t st, uint64_t* counted, uint64_t* n_flagged) {
+    uint32_t m = 0;
+    HIP_TRYX(c, hipMemcpyAsync(&m, c->d_xflag, sizeof m, hipMemcpyDeviceToHost, st));
+    const int rc = ctl_readback(c, st);
     if (rc != BSK_OK) return rc;
-    uint64_t removed = 0, flagged = 0;
-    rc = rdb_bucket_decide(c, st, &removed, &flagged);
-    if (n_removed) *n_removed = removed;
+    *counted = c->fin(bsk_ctx::FIN_AUX0);
+    *n_flagged = m;
+    return m > RDB_FLAG_MAX ? rdb_too_many_flagged(c) : (int)BSK_OK;
+}
+
+int rdb_bucket_finish(bsk_ctx* c, hipStream_t st, uint64_t* n_counted, uint64_t* n_flagged, RdbDecide decide) {
+    bsk_ctx::RmDupBuckets& B = c->rdb;
+    int rc = bucket_require_open(c, B, rdb_op_name(c), "finish");
+    if (rc != BSK_OK) return rc;
+    uint64_t counted = 0, flagged = 0;
+    rc = decide(c, st, &counted, &flagged);
+    if (n_counted) *n_counted = counted;
     if (n_flagged) *n_flagged = flagged;
     if (rc == BSK_OK)
         for (uint32_t b = B.lo; b < B.hi; ++b) B.decided[b] = 1;
     bucket_close(&B);
     return rc;
+}
+
+int rmdup_bucket_finish(bsk_ctx* c, hipStream_t st, uint64_t* n_removed, uint64_t* n_flagged) {
+    return rdb_bucket_finish(c, st, n_removed, n_flagged, rdb_bucket_decide);
 }
 
 // ---- the emit pass: the survivors of the shard, in order, each as Format(LineWidth)
@@ -438,12 +446,16 @@ int rmdup_emit_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, ui
     uint64_t total = 0, kept = 0;
     rc = finish_sizes(c, st, &total, &kept);
     if (rc != BSK_OK) return rc;
-    rc = ensure_out(c, total);
-    if (rc != BSK_OK) return rc;
     SeqParams F = format_params(c, fastq);
     F.text_w = tt.text_w; F.lin_off = tt.lin_off; F.lin = tt.lin;
-    apply_long(c, &F);
-    rc = emit_records(c, d_buf, n, F, total, kept, st);
+    return rdb_emit_tail(c, d_buf, n, &F, total, kept, st, out);
+}
+
+int rdb_emit_tail(bsk_ctx* c, const uint8_t* d_buf, size_t n, SeqParams* F, uint64_t total, uint64_t kept, hipStream_t st, bsk_out* out) {
+    int rc = ensure_out(c, total);
+    if (rc != BSK_OK) return rc;
+    apply_long(c, F);
+    rc = emit_records(c, d_buf, n, *F, total, kept, st);
     if (rc != BSK_OK) return rc;
     out->d_data = c->d_out;
     out->len = total;

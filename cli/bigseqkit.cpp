@@ -752,16 +752,97 @@ static size_t whole_file_limit() {
     return lim;
 }
 
-// BSK_SHUFFLE_BUDGET_BYTES / BSK_SORT_BUDGET_BYTES / BSK_RMDUP_BUDGET_BYTES / BSK_RENAME_BUDGET_BYTES / BSK_COMMON_BUDGET_BYTES /
-// BSK_PAIR_BUDGET_BYTES / BSK_CONCAT_BUDGET_BYTES: the bytes a bucket of `shuffle` / `sort` / `rmdup` / `rename` / `common` / `pair` /
-// `concat` may hold (run_buckets; rmdup, rename, common and the match buckets of pair and concat: bytes of subjects and their
-// per-record words, not of record text; the order buckets of pair: bytes of record text, the windows of concat: the cost of their
-// records, a bound of the text they collect and join -- both under the same budget); 0: unset
+// The key-bucket family of the command line (run_buckets): one row per command.
+//   budget_env   the bytes a bucket may hold (rmdup, rename, common and the match buckets of pair and concat: bytes of subjects and
+//                their per-record words, not of record text; the order buckets of pair: bytes of record text, the windows of concat:
+//                the cost of their records, a bound of the text they collect and join -- both under the same budget); unset: 0
+//   hist_run .. bucket_add, mark_hist, mark_buckets   the entry points of the passes all of them share, and their timing marks
+//   plan_hint    what a fine bin holds, appended when bsk_shuffle_plan finds one above the budget
+//   finish_out / finish_counted   a bucket leaves as text, or ends in its share of a verdict and returns two counters; that verdict
+//   verdict_total / verdict_files   began with the records of the input, or with the records of every file
+//   emit_run, mark_emit, emit_first_file_only   the emit pass behind the buckets (rmdup, rename, common), over every piece or
+//                over those of the first file; pair and concat go on in tails of their own
+//   counted, group_first, second_phase   the words of the [timing] summary of a command with a verdict
+//   unfit_hint   read_parts: what to do about an input that could not be loaded whole (null: the answer of every other command)
+struct BucketCmd {
+    const char *use, *budget_env;
+    decltype(&bsk_shuffle_hist_run) hist_run;
+    decltype(&bsk_shuffle_hist_get) hist_get;
+    decltype(&bsk_shuffle_bucket_begin) bucket_begin;
+    decltype(&bsk_shuffle_bucket_add) bucket_add;
+    const char *mark_hist, *mark_buckets, *plan_hint;
+    decltype(&bsk_shuffle_bucket_finish) finish_out = nullptr;
+    decltype(&bsk_rmdup_bucket_finish) finish_counted = nullptr;
+    decltype(&bsk_rmdup_verdict_begin) verdict_total = nullptr;
+    int (*verdict_files)(bsk_ctx*, const uint64_t*, uint32_t) = nullptr;
+    decltype(&bsk_rmdup_emit_run) emit_run = nullptr;
+    const char* mark_emit = nullptr;
+    bool emit_first_file_only = false;
+    const char *counted = nullptr, *group_first = nullptr, *second_phase = nullptr, *unfit_hint = nullptr;
+};
+static int pair_verdict_files(bsk_ctx* c, const uint64_t* r, uint32_t) { return bsk_pair_verdict_begin(c, r); }
+static int concat_verdict_files(bsk_ctx* c, const uint64_t* r, uint32_t) { return bsk_concat_verdict_begin(c, r); }
+static const BucketCmd kBucketCmds[] = {
+    {.use = "shuffle", .budget_env = "BSK_SHUFFLE_BUDGET_BYTES",
+     .hist_run = bsk_shuffle_hist_run, .hist_get = bsk_shuffle_hist_get, .bucket_begin = bsk_shuffle_bucket_begin, .bucket_add = bsk_shuffle_bucket_add,
+     .mark_hist = "shuffle: histogram of the draws", .mark_buckets = "shuffle: buckets", .plan_hint = "",
+     .finish_out = bsk_shuffle_bucket_finish,
+     .unfit_hint = "shuffle orders all records of its input in one pass and runs on one device "
+                   "(BSK_SHUFFLE_BUDGET_BYTES=<bytes> shuffles it in buckets of at most that many bytes, read once per bucket)"},
+    {.use = "sort", .budget_env = "BSK_SORT_BUDGET_BYTES",
+     .hist_run = bsk_sort_hist_run, .hist_get = bsk_sort_hist_get, .bucket_begin = bsk_sort_bucket_begin, .bucket_add = bsk_sort_bucket_add,
+     .mark_hist = "sort: histogram of the bins", .mark_buckets = "sort: buckets",
+     .plan_hint = " -- sort: a fine bin holds the records between two splitter keys; many equal keys, or a run that the sample missed, fill one",
+     .finish_out = bsk_sort_bucket_finish,
+     .unfit_hint = "sort orders all records of its input in one pass and runs on one device "
+                   "(BSK_SORT_BUDGET_BYTES=<bytes> sorts it in buckets of at most that many bytes, read twice and once per bucket)"},
+    {.use = "rmdup", .budget_env = "BSK_RMDUP_BUDGET_BYTES",
+     .hist_run = bsk_rmdup_hist_run, .hist_get = bsk_rmdup_hist_get, .bucket_begin = bsk_rmdup_bucket_begin, .bucket_add = bsk_rmdup_bucket_add,
+     .mark_hist = "rmdup: histogram of the bins", .mark_buckets = "rmdup: buckets",
+     .plan_hint = " -- rmdup: a fine bin holds the subjects whose key shares its upper 12 bits; the copies of one subject fill one",
+     .finish_counted = bsk_rmdup_bucket_finish, .verdict_total = bsk_rmdup_verdict_begin,
+     .emit_run = bsk_rmdup_emit_run, .mark_emit = "rmdup: emit",
+     .counted = "record(s) removed", .group_first = "survivor",
+     .unfit_hint = "cut it over several GPUs (--devices 0-7), or BSK_RMDUP_BUDGET_BYTES=<bytes> removes the duplicates in buckets of "
+                   "the key that hold at most that many bytes of subjects, read twice and once per bucket"},
+    {.use = "rename", .budget_env = "BSK_RENAME_BUDGET_BYTES",
+     .hist_run = bsk_rename_hist_run, .hist_get = bsk_rename_hist_get, .bucket_begin = bsk_rename_bucket_begin, .bucket_add = bsk_rename_bucket_add,
+     .mark_hist = "rename: histogram of the bins", .mark_buckets = "rename: buckets",
+     .plan_hint = " -- rename: a fine bin holds the IDs (-n: the names) whose key shares its upper 12 bits, once per record; the records of one ID fill one",
+     .finish_counted = bsk_rename_bucket_finish, .verdict_total = bsk_rename_verdict_begin,
+     .emit_run = bsk_rename_emit_run, .mark_emit = "rename: emit",
+     .counted = "record(s) renamed", .group_first = "first",
+     .unfit_hint = "rename numbers the records of an ID over its whole input and runs on one device "
+                   "(BSK_RENAME_BUDGET_BYTES=<bytes> renames it in buckets of the key that hold at most that many bytes of "
+                   "subjects, read twice and once per bucket)"},
+    {.use = "common", .budget_env = "BSK_COMMON_BUDGET_BYTES",
+     .hist_run = bsk_common_hist_run, .hist_get = bsk_common_hist_get, .bucket_begin = bsk_common_bucket_begin, .bucket_add = bsk_common_bucket_add,
+     .mark_hist = "common: histogram of the bins", .mark_buckets = "common: buckets",
+     .plan_hint = " -- common: a fine bin holds the subjects of all files whose key shares its upper 12 bits, once per record; the copies of one subject fill one",
+     .finish_counted = bsk_common_bucket_finish, .verdict_files = bsk_common_verdict_begin,
+     .emit_run = bsk_common_emit_run, .mark_emit = "common: emit", .emit_first_file_only = true,  // (the kept records of the first file)
+     .counted = "record(s) kept", .group_first = "first"},
+    {.use = "pair", .budget_env = "BSK_PAIR_BUDGET_BYTES",
+     .hist_run = bsk_pair_hist_run, .hist_get = bsk_pair_hist_get, .bucket_begin = bsk_pair_bucket_begin, .bucket_add = bsk_pair_bucket_add,
+     .mark_hist = "pair: histogram of the bins", .mark_buckets = "pair: match buckets",
+     .plan_hint = " -- pair: a fine bin holds the IDs of both files whose key shares its upper 12 bits, once per record; the records of one ID fill one",
+     .finish_counted = bsk_pair_bucket_finish, .verdict_files = pair_verdict_files,
+     .counted = "pair(s)", .group_first = "first", .second_phase = "order bucket(s)"},
+    {.use = "concat", .budget_env = "BSK_CONCAT_BUDGET_BYTES",
+     .hist_run = bsk_concat_hist_run, .hist_get = bsk_concat_hist_get, .bucket_begin = bsk_concat_bucket_begin, .bucket_add = bsk_concat_bucket_add,
+     .mark_hist = "concat: histogram of the bins", .mark_buckets = "concat: match buckets",
+     .plan_hint = " -- concat: a fine bin holds the IDs of both files whose key shares its upper 12 bits, once per record; the records of one ID fill one",
+     .finish_counted = bsk_concat_bucket_finish, .verdict_files = concat_verdict_files,
+     .counted = "record(s) with a head", .group_first = "first", .second_phase = "window(s)"},
+};
+static const BucketCmd* bucket_cmd(const std::string& use) {
+    for (const BucketCmd& r : kBucketCmds)
+        if (use == r.use) return &r;
+    return nullptr;
+}
 static uint64_t bucket_budget(const std::string& use) {
-    const char* e = use == "shuffle" ? getenv("BSK_SHUFFLE_BUDGET_BYTES") : use == "sort" ? getenv("BSK_SORT_BUDGET_BYTES")
-                  : use == "rmdup" ? getenv("BSK_RMDUP_BUDGET_BYTES") : use == "rename" ? getenv("BSK_RENAME_BUDGET_BYTES")
-                  : use == "common" ? getenv("BSK_COMMON_BUDGET_BYTES") : use == "pair" ? getenv("BSK_PAIR_BUDGET_BYTES")
-                  : use == "concat" ? getenv("BSK_CONCAT_BUDGET_BYTES") : nullptr;
+    const BucketCmd* cmd = bucket_cmd(use);
+    const char* e = cmd ? getenv(cmd->budget_env) : nullptr;
     return e ? (uint64_t)strtoull(e, nullptr, 10) : 0;
 }
 bool g_buckets_unfit = false;  // read_parts: the whole-file load of a `shuffle` / `sort` / `rmdup` / `rename` input failed and a budget is set
@@ -816,19 +897,8 @@ std::vector<Part> read_parts(const std::vector<std::string>& files, int device =
                         release(parts);
                         return parts;
                     }
-                    if (use == "shuffle")
-                        die(what + "shuffle orders all records of its input in one pass and runs on one device "
-                                   "(BSK_SHUFFLE_BUDGET_BYTES=<bytes> shuffles it in buckets of at most that many bytes, read once per bucket)");
-                    if (use == "sort")
-                        die(what + "sort orders all records of its input in one pass and runs on one device "
-                                   "(BSK_SORT_BUDGET_BYTES=<bytes> sorts it in buckets of at most that many bytes, read twice and once per bucket)");
-                    if (use == "rmdup")
-                        die(what + "cut it over several GPUs (--devices 0-7), or BSK_RMDUP_BUDGET_BYTES=<bytes> removes the duplicates in buckets of "
-                                   "the key that hold at most that many bytes of subjects, read twice and once per bucket");
-                    if (use == "rename")
-                        die(what + "rename numbers the records of an ID over its whole input and runs on one device "
-                                   "(BSK_RENAME_BUDGET_BYTES=<bytes> renames it in buckets of the key that hold at most that many bytes of "
-                                   "subjects, read twice and once per bucket)");
+                    if (const BucketCmd* cmd = bucket_cmd(use))
+                        if (cmd->unfit_hint) die(what + cmd->unfit_hint);
                     die(what + "cut it over several GPUs (--devices 0-7: fq2fa, grep, locate, rmdup, sample, seq, stats, subseq, translate)");
                 }
                 // stats: the file stays on the host, its mapping is streamed in record-aligned chunks
@@ -1030,6 +1100,43 @@ static bool parallel_pread(int fd, uint8_t* buf, size_t len, size_t off, int thr
     return ok;
 }
 
+// A file of a streamed input on the host: a regular file is mapped -- only the pages that are handed on are ever read --, a pipe
+// is read to its end first (`whole`)
+struct MappedFile {
+    std::string whole;
+    const uint8_t* text = nullptr;
+    size_t size = 0;
+    bool mapped = false;
+    void unmap() {
+        if (mapped && size) munmap((void*)text, size);
+        mapped = false;
+    }
+};
+static void map_file(const std::string& path, MappedFile* f) {
+    const int fd = open(path.c_str(), O_RDONLY);
+    if (fd < 0) die("open " + path + ": no such file or directory");
+    struct stat sb;
+    f->mapped = fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode);
+    if (f->mapped) {
+        f->size = (size_t)sb.st_size;
+        if (f->size) {
+            f->text = (const uint8_t*)mmap(nullptr, f->size, PROT_READ, MAP_SHARED, fd, 0);
+            if (f->text == MAP_FAILED) die("mmap " + path + " failed");
+        }
+    } else {
+        f->whole = read_file(path);
+        f->text = (const uint8_t*)f->whole.data();
+        f->size = f->whole.size();
+    }
+    close(fd);
+}
+// the end of the piece of about `piece` bytes that begins at `lo`: the record start behind lo + piece, or the end of the file
+static size_t piece_end(const MappedFile& f, size_t lo, size_t piece, int fmt) {
+    size_t at = 0;
+    if (f.size - lo > piece && bsk_find_record_start(f.text, f.size, lo + piece, fmt, &at) == BSK_OK && at > lo && at < f.size) return at;
+    return f.size;
+}
+
 // head-genome (cli/head_genome.go:11-15): every file is a run of its own, the results in the order of the files.  The answer
 // is a prefix of the file, so the file is not brought to the GPU whole: pieces of its mapping that end on record starts go
 // through ONE context, which carries the prefix words, n_1 and "cut reached" from piece to piece (PARITY.md HEADG), and the
@@ -1044,46 +1151,25 @@ Output run_head_genome(const Invocation& inv) {
     const char* pinned = getenv("BSK_STREAM_PIECE_BYTES");
     for (auto& path : inv.files) {
         if (bsk_head_genome_reset(ctx) != BSK_OK) die(bsk_last_error(ctx));
-        const int fd = open(path.c_str(), O_RDONLY);
-        if (fd < 0) die("open " + path + ": no such file or directory");
-        struct stat sb;
-        std::string whole;  // (a pipe: read to its end first)
-        const uint8_t* text = nullptr;
-        size_t size = 0;
-        bool mapped = fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode);
-        if (mapped) {
-            size = (size_t)sb.st_size;
-            if (size) {
-                text = (const uint8_t*)mmap(nullptr, size, PROT_READ, MAP_SHARED, fd, 0);
-                if (text == MAP_FAILED) die("mmap " + path + " failed");
-            }
-        } else {
-            whole = read_file(path);
-            text = (const uint8_t*)whole.data();
-            size = whole.size();
+        MappedFile f;
+        map_file(path, &f);
+        if (f.size && bsk_bgzf_probe(f.text, f.size) != 0) {  // (compressed: inflated on the host, then streamed like a pipe's text)
+            std::string text((const char*)f.text, f.size);
+            f.unmap();
+            f.whole = std::move(text);
+            inflate_host_text(path, f.whole);
+            f.text = (const uint8_t*)f.whole.data();
+            f.size = f.whole.size();
         }
-        close(fd);
-        if (size && bsk_bgzf_probe(text, size) != 0) {  // (compressed: inflated on the host, then streamed like a pipe's text)
-            whole.assign((const char*)text, size);
-            if (mapped) munmap((void*)text, size);
-            mapped = false;
-            inflate_host_text(path, whole);
-            text = (const uint8_t*)whole.data();
-            size = whole.size();
-        }
-        const int fmt = sniff_format(path, size ? std::string((const char*)text, 1) : std::string());
+        const int fmt = sniff_format(path, f.size ? std::string((const char*)f.text, 1) : std::string());
         res.fmt = fmt;
         size_t piece = pinned ? std::max<size_t>(1, (size_t)strtoull(pinned, nullptr, 10)) : ((size_t)64 << 20);
         size_t lo = 0;
         int64_t k = 0;
-        while (lo < size) {
-            size_t hi = size;
-            if (size - lo > piece) {
-                size_t at = 0;
-                if (bsk_find_record_start(text, size, lo + piece, fmt, &at) == BSK_OK && at > lo && at < size) hi = at;
-            }
+        while (lo < f.size) {
+            const size_t hi = piece_end(f, lo, piece, fmt);
             bsk_out out;
-            if (bsk_head_genome_run(ctx, text + lo, hi - lo, 0, fmt, k++, nullptr, &out) != BSK_OK) die(bsk_last_error(ctx));
+            if (bsk_head_genome_run(ctx, f.text + lo, hi - lo, 0, fmt, k++, nullptr, &out) != BSK_OK) die(bsk_last_error(ctx));
             const size_t at = res.text.size();
             res.text.resize(at + out.len);
             if (out.len && bsk_out_to_host(ctx, &out, &res.text[at], out.len) != BSK_OK) die(bsk_last_error(ctx));
@@ -1093,16 +1179,15 @@ Output run_head_genome(const Invocation& inv) {
             lo = hi;
             if (!pinned) piece = std::min<size_t>(piece * 2, (size_t)1 << 30);
         }
-        if (mapped && size) munmap((void*)text, size);
+        f.unmap();
     }
     bsk_destroy(ctx);
     return res;
 }
 
-// shuffle in buckets of the draw, sort, rmdup, rename and common in buckets of the key (include/bsk.h; PARITY.md SHUF, SORT,
-// RMDUPB, RENB, COMB): the way of the five commands for an input that is larger than the byte budget of a bucket
-// (BSK_SHUFFLE_BUDGET_BYTES, BSK_SORT_BUDGET_BYTES, BSK_RMDUP_BUDGET_BYTES, BSK_RENAME_BUDGET_BYTES, BSK_COMMON_BUDGET_BYTES) or
-// -- the first four -- that could not be loaded whole.  The files stay on the host, mapped; several files are unioned in order (cli/shuffle.go:11-15,
+// shuffle in buckets of the draw, sort, rmdup, rename, common, pair and concat in buckets of the key (include/bsk.h; PARITY.md SHUF,
+// SORT, RMDUPB, RENB, COMB, PAIRB, CONB): the way of the seven commands for an input that is larger than the byte budget of a bucket
+// (budget_env of kBucketCmds) or -- the first four -- that could not be loaded whole.  The files stay on the host, mapped; several files are unioned in order (cli/shuffle.go:11-15,
 // cli/sort.go), the record index runs over all of them.  Record-aligned pieces (BSK_STREAM_PIECE_BYTES, default 1 GiB) go
 // through ONE context.  The mapping, the piece list, the plan and the timing line are shared; the passes differ:
 //   shuffle   once for the histogram of the draws -- each piece's first record index is remembered -- and then once per bucket
@@ -1132,12 +1217,268 @@ Output run_head_genome(const Invocation& inv) {
 //             weights, once per window and once more with -f
 // Every finished bucket is appended to the output.  A piece never spans two files, so a file that ends without a newline
 // behaves like the union of the whole-file path: its last record gets the newline.
+// The steps are written once: map_pieces (the files, their format and the pieces), plan_buckets (the passes in front of the buckets
+// and the plan), then for a command whose buckets leave as text print_buckets, else decide_buckets and -- rmdup, rename, common --
+// emit_pieces; pair and concat go on in pair_tail / concat_tail.  What differs between the commands is their row of kBucketCmds.
+struct BucketRun {
+    const BucketCmd& cmd;
+    bsk_ctx* ctx = nullptr;
+    uint64_t budget = 0;
+    Output res;
+    struct Piece { const uint8_t* p; size_t n; uint64_t first; size_t file; uint64_t count; };
+    std::vector<MappedFile> files;
+    std::vector<Piece> pieces;
+    std::vector<uint64_t> file_records;  // (behind the histogram pass)
+    uint64_t total_bytes = 0;
+    static constexpr uint32_t kBins = 4096;  // the fine bins of all of them (include/bsk.h)
+    std::vector<uint64_t> hist = std::vector<uint64_t>(kBins), bounds = std::vector<uint64_t>(kBins + 1);
+    int n_buckets = 0, n_second = 0;    // (n_second: the order buckets of pair, the windows of concat)
+    uint64_t counted = 0, flagged = 0;  // (rmdup: removed; rename: renamed; common: kept; pair: pairs; concat: records with a head)
+
+    void ok(int rc) const { if (rc != BSK_OK) die(bsk_last_error(ctx)); }
+    // the files mapped, of one format, and cut into record-aligned pieces; a piece never spans two files
+    void map_pieces(const std::vector<std::string>& paths, size_t n_files) {
+        const char* pinned = getenv("BSK_STREAM_PIECE_BYTES");
+        const size_t piece = pinned ? std::max<size_t>(1, (size_t)strtoull(pinned, nullptr, 10)) : ((size_t)1 << 30);
+        files.resize(n_files);
+        int fmt = -1;
+        for (size_t fi = 0; fi < n_files; ++fi) {
+            MappedFile& f = files[fi];
+            map_file(paths[fi], &f);
+            const int ffmt = sniff_format(paths[fi], f.size ? std::string((const char*)f.text, 1) : std::string());
+            if (fmt >= 0 && ffmt != fmt) die(std::string(cmd.use) + ": inputs of different formats");
+            fmt = ffmt;
+            total_bytes += f.size;
+            for (size_t lo = 0; lo < f.size;) {
+                const size_t hi = piece_end(f, lo, piece, fmt);
+                pieces.push_back({f.text + lo, hi - lo, 0, fi, 0});
+                lo = hi;
+            }
+        }
+        res.fmt = fmt < 0 ? BSK_FORMAT_FASTA : fmt;
+    }
+    // the pass over all pieces that counts the records: it leaves every piece's first record index and its count
+    template <class Call>
+    void count_pass(Call call) {
+        uint64_t g = 0;
+        int64_t k = 0;
+        for (auto& pc : pieces) {
+            uint64_t cnt = 0;
+            pc.first = g;
+            ok(call(pc, k++, g, &cnt));
+            g += cnt;
+            pc.count = cnt;
+        }
+    }
+    // sort: the sample of keys and the splitters; all: the histogram over all pieces and the plan of the buckets
+    void plan_buckets() {
+        if (std::string(cmd.use) == "sort") {
+            double rate = 1.0;
+            if (!pieces.empty()) {
+                uint64_t cnt = 0;
+                ok(bsk_index_build(ctx, pieces[0].p, pieces[0].n, 0, res.fmt, nullptr, &cnt));
+                const double records = (double)total_bytes * (double)cnt / (double)std::max<size_t>(pieces[0].n, 1);
+                rate = std::min(1.0, 32.0 * (double)kBins / std::max(records, 1.0));
+            }
+            count_pass([&](const Piece& pc, int64_t k, uint64_t g, uint64_t* cnt) {
+                return bsk_sort_sample_run(ctx, pc.p, pc.n, 0, res.fmt, k, g, rate, nullptr, cnt);
+            });
+            uint32_t n_bins = 0;
+            ok(bsk_sort_splitters_build(ctx, kBins, &n_bins));
+            mark("sort: sample of the keys, splitters");
+        }
+        count_pass([&](const Piece& pc, int64_t k, uint64_t g, uint64_t* cnt) { return cmd.hist_run(ctx, pc.p, pc.n, 0, res.fmt, k, g, nullptr, cnt); });
+        mark(cmd.mark_hist);
+        file_records.assign(files.size(), 0);
+        for (auto& pc : pieces) file_records[pc.file] += pc.count;
+        ok(cmd.hist_get(ctx, hist.data(), nullptr));
+        if (bsk_shuffle_plan(hist.data(), budget, bounds.data(), &n_buckets) != BSK_OK) die(std::string(bsk_global_error()) + cmd.plan_hint);
+    }
+    // bucket b of the plan opened and every piece added to it, in input order
+    void fill_bucket(int b) {
+        ok(cmd.bucket_begin(ctx, (uint32_t)bounds[b], (uint32_t)bounds[b + 1]));
+        int64_t k = 0;
+        for (auto& pc : pieces) ok(cmd.bucket_add(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr));
+    }
+    void append_out(const bsk_out& out) {
+        const size_t at = res.text.size();
+        res.text.resize(at + out.len);
+        if (out.len) ok(bsk_out_to_host(ctx, &out, &res.text[at], out.len));
+    }
+    // shuffle, sort: every finished bucket is appended to the output; backwards (sort -r): from the last to the first
+    void print_buckets(bool backwards) {
+        for (int i = 0; i < n_buckets; ++i) {
+            fill_bucket(backwards ? n_buckets - 1 - i : i);
+            bsk_out out;
+            ok(cmd.finish_out(ctx, nullptr, &out));
+            append_out(out);
+        }
+        mark(cmd.mark_buckets);
+    }
+    // the others: the verdict begins; every bucket over all pieces, in order, ends in its share of it
+    void decide_buckets() {
+        uint64_t total_records = 0;
+        for (uint64_t n : file_records) total_records += n;
+        ok(cmd.verdict_total ? cmd.verdict_total(ctx, total_records) : cmd.verdict_files(ctx, file_records.data(), (uint32_t)file_records.size()));
+        for (int b = 0; b < n_buckets; ++b) {
+            fill_bucket(b);
+            uint64_t r = 0, f = 0;
+            ok(cmd.finish_counted(ctx, nullptr, &r, &f));
+            counted += r;
+            flagged += f;
+        }
+        mark(cmd.mark_buckets);
+    }
+    // rmdup, rename, common: one emit pass prints the records in file order
+    void emit_pieces() {
+        int64_t k = 0;
+        for (auto& pc : pieces) {
+            if (cmd.emit_first_file_only && pc.file != 0) break;
+            bsk_out out;
+            ok(cmd.emit_run(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr, &out));
+            append_out(out);
+        }
+        mark(cmd.mark_emit);
+    }
+    void pair_tail(const Invocation& inv, const std::string& outdir);
+    void concat_tail(const Invocation& inv);
+};
+
+// pair behind its match buckets: the rank step, the emit over both files and -- file 2 out of mate order -- the order buckets
+void BucketRun::pair_tail(const Invocation& inv, const std::string& outdir) {
+    const bool unp = inv.pget("save-unpaired") == "true";
+    if (!is_dir(outdir) && mkdir(outdir.c_str(), 0755) != 0) die("cannot create directory " + outdir);
+    const char* names[4] = {"paired.1", "paired.2", "unpaired.1", "unpaired.2"};
+    std::ofstream outf[4];
+    for (int k = 0; k < (unp ? 4 : 2); ++k) {
+        outf[k].open(outdir + "/" + names[k], std::ios::binary);
+        if (!outf[k]) die("cannot create " + outdir + "/" + names[k]);
+    }
+    std::string share;
+    auto write_share = [&](int k, const bsk_out& out) {
+        if (!out.len || !outf[k].is_open()) return;
+        share.resize(out.len);
+        ok(bsk_out_to_host(ctx, &out, &share[0], out.len));
+        outf[k].write(share.data(), (std::streamsize)share.size());
+        if (!outf[k]) die("write " + outdir + "/" + names[k] + " failed");
+    };
+    decide_buckets();
+    uint64_t n_pairs = 0;
+    int in_mate_order = 0;
+    ok(bsk_pair_order_begin(ctx, nullptr, &n_pairs, &in_mate_order));
+    const char* forced = getenv("BSK_PAIR_ORDER");  // (the switch pair_order of the context: the emit leaves paired.2 to the order phase)
+    const bool by_emit = in_mate_order && !(forced && std::string(forced) == "buckets");
+    // the emit: paired.1 and unpaired.1 from the pieces of file 1; unpaired.2 -- and paired.2 when it is a filter of file 2 --
+    // from those of file 2, which are not read when neither is wanted
+    int64_t k = 0;
+    for (auto& pc : pieces) {
+        if (pc.file == 1 && !unp && !by_emit) break;
+        bsk_out outs[3];
+        ok(bsk_pair_emit_run(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr, outs));
+        if (pc.file == 0) write_share(0, outs[0]);
+        else write_share(1, outs[2]);
+        write_share(pc.file == 0 ? 2 : 3, outs[1]);
+    }
+    mark("pair: emit");
+    if (n_pairs && !by_emit) {
+        // paired.2 in buckets of the position: the histogram over the pieces of file 2, the plan, one pass per bucket
+        for (auto& pc : pieces) {
+            uint64_t cnt = 0;
+            if (pc.file == 1) ok(bsk_pair_order_hist_run(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr, &cnt));
+        }
+        ok(bsk_pair_order_hist_get(ctx, hist.data(), nullptr));
+        if (bsk_shuffle_plan(hist.data(), budget, bounds.data(), &n_second) != BSK_OK)
+            die(std::string(bsk_global_error()) + " -- pair: an order bin holds the text of the records of paired.2 whose positions share their upper bits, "
+                                                   "at most a 4096th of the pairs rounded up to a power of two");
+        for (int b = 0; b < n_second; ++b) {
+            ok(bsk_pair_order_bucket_begin(ctx, (uint32_t)bounds[b], (uint32_t)bounds[b + 1]));
+            for (auto& pc : pieces)
+                if (pc.file == 1) ok(bsk_pair_order_bucket_add(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr));
+            bsk_out out;
+            ok(bsk_pair_order_bucket_finish(ctx, nullptr, &out));
+            write_share(1, out);
+        }
+        mark("pair: order buckets");
+    }
+    for (int j = 0; j < 4; ++j)
+        if (outf[j].is_open()) {
+            outf[j].close();
+            if (!outf[j]) die("write " + outdir + "/" + names[j] + " failed");
+        }
+}
+
+// concat behind its match buckets: the weights, the window histogram and its plan, the windows and -- -f -- the tail
+void BucketRun::concat_tail(const Invocation& inv) {
+    // one file (-o <file> --merge) or the standard output (-o -) receives the shares as they finish; a directory of part files
+    // is cut from the whole result, which is collected on the host then (store)
+    const std::string outp = inv.pget("out-file");
+    const bool to_stdout = outp == "-", to_file = !outp.empty() && !to_stdout && inv.pget("merge") == "true";
+    std::ofstream outf;
+    if (to_file) {
+        outf.open(outp, std::ios::binary);
+        if (!outf) die("cannot create " + outp);
+    }
+    res.stored = to_file || to_stdout;
+    std::string share;
+    auto write_share = [&](const bsk_out& out) {
+        if (!res.stored) return append_out(out);
+        if (!out.len) return;
+        share.resize(out.len);
+        ok(bsk_out_to_host(ctx, &out, &share[0], out.len));
+        if (to_stdout) fwrite(share.data(), 1, share.size(), stdout);
+        else outf.write(share.data(), (std::streamsize)share.size());
+        if (to_file && !outf) die("write " + outp + " failed");
+    };
+    decide_buckets();
+    // the weights over the pieces of file 2, the window histogram over those of file 1, the plan of the windows
+    ok(bsk_concat_join_begin(ctx, nullptr));
+    int64_t k = 0;
+    for (int file = 1; file >= 0; --file)
+        for (auto& pc : pieces) {
+            uint64_t cnt = 0;
+            if ((int)pc.file == file) ok((file ? bsk_concat_weigh_run : bsk_concat_window_hist_run)(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr, &cnt));
+        }
+    ok(bsk_concat_window_hist_get(ctx, hist.data(), nullptr));
+    if (bsk_shuffle_plan(hist.data(), budget, bounds.data(), &n_second) != BSK_OK)
+        die(std::string(bsk_global_error()) + " -- concat: a window bin holds the cost of at most a 4096th of the records of file 1, rounded up to a "
+                                               "power of two: their text, the text of the records of file 2 with their IDs, and a bound of the joined "
+                                               "records; an ID with many records in both files fills one");
+    mark("concat: weights, histogram of the windows");
+    uint32_t shift = 0;
+    while (file_records[0] && ((file_records[0] - 1) >> shift) >= kBins) ++shift;
+    for (int b = 0; b < n_second; ++b) {
+        const uint64_t lo = bounds[b], hi = bounds[b + 1];
+        ok(bsk_concat_window_begin(ctx, (uint32_t)lo, (uint32_t)hi));
+        for (auto& pc : pieces) {
+            // (a piece of file 1 wholly outside the window adds nothing)
+            if (pc.file == 0 && (pc.count == 0 || ((pc.first + pc.count - 1) >> shift) < lo || (pc.first >> shift) >= hi)) continue;
+            ok(bsk_concat_window_add(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr));
+        }
+        bsk_out out;
+        ok(bsk_concat_window_finish(ctx, nullptr, &out));
+        write_share(out);
+    }
+    mark("concat: windows");
+    if (inv.pget("full") == "true") {
+        for (auto& pc : pieces) {
+            if (pc.file != 1) continue;
+            bsk_out out;
+            ok(bsk_concat_tail_run(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr, &out));
+            write_share(out);
+        }
+        mark("concat: tail");
+    }
+    if (to_file) {
+        outf.close();
+        if (!outf) die("write " + outp + " failed");
+    }
+}
+
 Output run_buckets(const Invocation& inv) {
     const std::string use = inv.cmd->use;
-    const bool sort = use == "sort", rmdup = use == "rmdup", rename = use == "rename", common = use == "common", pair = use == "pair",
-               concat = use == "concat";
+    const bool pair = use == "pair", concat = use == "concat";
     if (concat && inv.files.size() != 2) die("2 files needed");  // cli/concat.go
-    if (common && inv.files.size() < 2) die("at least 2 files needed");  // cli/common.go
+    if (use == "common" && inv.files.size() < 2) die("at least 2 files needed");  // cli/common.go
     const std::string outdir = pair ? inv.pget("out-dir") : std::string();
     if (pair) {  // cli/pair.go:13-66, the checks of the whole-file path
         if (inv.files.size() < 2) die("2 files needed");
@@ -1145,354 +1486,38 @@ Output run_buckets(const Invocation& inv) {
     }
     refuse_compressed(inv.files, "the buckets of '" + use + "' read", "decompress it first (bgzip -d), or unset the budget if the file and its text fit one GPU");
     const int device = (int)strtol(inv.pget("device").c_str(), nullptr, 10);
-    const uint64_t budget = bucket_budget(use);
-    constexpr uint32_t kBins = 4096;  // the fine bins of all five (include/bsk.h)
-    Output res;
-    bsk_ctx* ctx = nullptr;
-    if (bsk_create(inv.cmd->op, inv.js.c_str(), device, &ctx) != BSK_OK) die(bsk_global_error());
+    BucketRun R{*bucket_cmd(use)};
+    R.budget = bucket_budget(use);
+    if (bsk_create(inv.cmd->op, inv.js.c_str(), device, &R.ctx) != BSK_OK) die(bsk_global_error());
     const bool timing = getenv("BSK_CLI_TIMING") != nullptr;
-    if (timing) bsk_profile_enable(ctx, 1);
-    struct File { std::string whole; const uint8_t* text = nullptr; size_t size = 0; bool mapped = false; };
-    struct Piece { const uint8_t* p; size_t n; uint64_t first; size_t file; uint64_t count; };
-    std::vector<File> files(pair || concat ? 2 : inv.files.size());
-    std::vector<Piece> pieces;
-    const char* pinned = getenv("BSK_STREAM_PIECE_BYTES");
-    const size_t piece = pinned ? std::max<size_t>(1, (size_t)strtoull(pinned, nullptr, 10)) : ((size_t)1 << 30);
-    int fmt = -1;
-    uint64_t total_bytes = 0;
-    for (size_t fi = 0; fi < files.size(); ++fi) {
-        const std::string& path = inv.files[fi];
-        File& f = files[fi];
-        const int fd = open(path.c_str(), O_RDONLY);
-        if (fd < 0) die("open " + path + ": no such file or directory");
-        struct stat sb;
-        f.mapped = fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode);
-        if (f.mapped) {
-            f.size = (size_t)sb.st_size;
-            if (f.size) {
-                f.text = (const uint8_t*)mmap(nullptr, f.size, PROT_READ, MAP_SHARED, fd, 0);
-                if (f.text == MAP_FAILED) die("mmap " + path + " failed");
-            }
-        } else {  // (a pipe: read to its end first)
-            f.whole = read_file(path);
-            f.text = (const uint8_t*)f.whole.data();
-            f.size = f.whole.size();
-        }
-        close(fd);
-        const int ffmt = sniff_format(path, f.size ? std::string((const char*)f.text, 1) : std::string());
-        if (fmt >= 0 && ffmt != fmt) die(use + ": inputs of different formats");
-        fmt = ffmt;
-        total_bytes += f.size;
-        for (size_t lo = 0; lo < f.size;) {
-            size_t hi = f.size;
-            if (f.size - lo > piece) {
-                size_t at = 0;
-                if (bsk_find_record_start(f.text, f.size, lo + piece, fmt, &at) == BSK_OK && at > lo && at < f.size) hi = at;
-            }
-            pieces.push_back({f.text + lo, hi - lo, 0, fi, 0});
-            lo = hi;
-        }
-    }
-    res.fmt = fmt < 0 ? BSK_FORMAT_FASTA : fmt;
-    // the entry points of the passes that the five commands share, and what their timing marks say
-    struct Entry {
-        decltype(&bsk_shuffle_hist_run) hist_run;
-        decltype(&bsk_shuffle_hist_get) hist_get;
-        decltype(&bsk_shuffle_bucket_begin) bucket_begin;
-        decltype(&bsk_shuffle_bucket_add) bucket_add;
-        const char *mark_hist, *mark_buckets;
-    };
-    const Entry E = sort    ? Entry{bsk_sort_hist_run, bsk_sort_hist_get, bsk_sort_bucket_begin, bsk_sort_bucket_add, "sort: histogram of the bins", "sort: buckets"}
-                    : rmdup ? Entry{bsk_rmdup_hist_run, bsk_rmdup_hist_get, bsk_rmdup_bucket_begin, bsk_rmdup_bucket_add, "rmdup: histogram of the bins", "rmdup: buckets"}
-                    : rename ? Entry{bsk_rename_hist_run, bsk_rename_hist_get, bsk_rename_bucket_begin, bsk_rename_bucket_add, "rename: histogram of the bins", "rename: buckets"}
-                    : common ? Entry{bsk_common_hist_run, bsk_common_hist_get, bsk_common_bucket_begin, bsk_common_bucket_add, "common: histogram of the bins", "common: buckets"}
-                    : concat ? Entry{bsk_concat_hist_run, bsk_concat_hist_get, bsk_concat_bucket_begin, bsk_concat_bucket_add, "concat: histogram of the bins", "concat: match buckets"}
-                    : pair ? Entry{bsk_pair_hist_run, bsk_pair_hist_get, bsk_pair_bucket_begin, bsk_pair_bucket_add, "pair: histogram of the bins", "pair: match buckets"}
-                            : Entry{bsk_shuffle_hist_run, bsk_shuffle_hist_get, bsk_shuffle_bucket_begin, bsk_shuffle_bucket_add, "shuffle: histogram of the draws", "shuffle: buckets"};
-    // the pass over all pieces that counts the records: it leaves every piece's first record index
-    uint64_t last_count = 0;  // the records of the last piece
-    auto count_pass = [&](auto&& call) {
-        uint64_t g = 0;
-        int64_t k = 0;
-        for (auto& pc : pieces) {
-            uint64_t cnt = 0;
-            pc.first = g;
-            if (call(pc, k++, g, &cnt) != BSK_OK) die(bsk_last_error(ctx));
-            g += cnt;
-            pc.count = cnt;
-            last_count = cnt;
-        }
-    };
-    // bucket [lo, hi) of the plan opened and every piece added to it, in input order
-    auto fill_bucket = [&](uint32_t lo, uint32_t hi) {
-        if (E.bucket_begin(ctx, lo, hi) != BSK_OK) die(bsk_last_error(ctx));
-        int64_t k = 0;
-        for (auto& pc : pieces)
-            if (E.bucket_add(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr) != BSK_OK) die(bsk_last_error(ctx));
-    };
-    auto append_out = [&](const bsk_out& out) {
-        const size_t at = res.text.size();
-        res.text.resize(at + out.len);
-        if (out.len && bsk_out_to_host(ctx, &out, &res.text[at], out.len) != BSK_OK) die(bsk_last_error(ctx));
-    };
-    if (sort) {
-        double rate = 1.0;
-        if (!pieces.empty()) {
-            uint64_t cnt = 0;
-            if (bsk_index_build(ctx, pieces[0].p, pieces[0].n, 0, res.fmt, nullptr, &cnt) != BSK_OK) die(bsk_last_error(ctx));
-            const double records = (double)total_bytes * (double)cnt / (double)std::max<size_t>(pieces[0].n, 1);
-            rate = std::min(1.0, 32.0 * (double)kBins / std::max(records, 1.0));
-        }
-        count_pass([&](const Piece& pc, int64_t k, uint64_t g, uint64_t* cnt) {
-            return bsk_sort_sample_run(ctx, pc.p, pc.n, 0, res.fmt, k, g, rate, nullptr, cnt);
-        });
-        uint32_t n_bins = 0;
-        if (bsk_sort_splitters_build(ctx, kBins, &n_bins) != BSK_OK) die(bsk_last_error(ctx));
-        mark("sort: sample of the keys, splitters");
-    }
-    count_pass([&](const Piece& pc, int64_t k, uint64_t g, uint64_t* cnt) { return E.hist_run(ctx, pc.p, pc.n, 0, res.fmt, k, g, nullptr, cnt); });
-    mark(E.mark_hist);
-    std::vector<uint64_t> hist(kBins), bounds(kBins + 1);
-    int n_buckets = 0;
-    if (E.hist_get(ctx, hist.data(), nullptr) != BSK_OK) die(bsk_last_error(ctx));
-    if (bsk_shuffle_plan(hist.data(), budget, bounds.data(), &n_buckets) != BSK_OK) {
-        std::string msg = bsk_global_error();
-        if (sort) msg += " -- sort: a fine bin holds the records between two splitter keys; many equal keys, or a run that the sample missed, fill one";
-        if (rmdup) msg += " -- rmdup: a fine bin holds the subjects whose key shares its upper 12 bits; the copies of one subject fill one";
-        if (rename) msg += " -- rename: a fine bin holds the IDs (-n: the names) whose key shares its upper 12 bits, once per record; the records of one ID fill one";
-        if (common) msg += " -- common: a fine bin holds the subjects of all files whose key shares its upper 12 bits, once per record; the copies of one subject fill one";
-        if (pair) msg += " -- pair: a fine bin holds the IDs of both files whose key shares its upper 12 bits, once per record; the records of one ID fill one";
-        if (concat) msg += " -- concat: a fine bin holds the IDs of both files whose key shares its upper 12 bits, once per record; the records of one ID fill one";
-        die(msg);
-    }
-    uint64_t removed = 0, flagged = 0;  // (rename: renamed; common: kept; pair: pairs; concat: records with a head)
-    int n_order_buckets = 0;            // (pair; concat: windows)
+    if (timing) bsk_profile_enable(R.ctx, 1);
+    R.map_pieces(inv.files, pair || concat ? 2 : inv.files.size());
+    R.plan_buckets();
     if (concat) {
-        // one file (-o <file> --merge) or the standard output (-o -) receives the shares as they finish; a directory of part files
-        // is cut from the whole result, which is collected on the host then (store)
-        const std::string outp = inv.pget("out-file");
-        const bool to_stdout = outp == "-", to_file = !outp.empty() && !to_stdout && inv.pget("merge") == "true";
-        std::ofstream outf;
-        if (to_file) {
-            outf.open(outp, std::ios::binary);
-            if (!outf) die("cannot create " + outp);
-        }
-        res.stored = to_file || to_stdout;
-        std::string share;
-        auto write_share = [&](const bsk_out& out) {
-            if (!res.stored) return append_out(out);
-            if (!out.len) return;
-            share.resize(out.len);
-            if (bsk_out_to_host(ctx, &out, &share[0], out.len) != BSK_OK) die(bsk_last_error(ctx));
-            if (to_stdout) fwrite(share.data(), 1, share.size(), stdout);
-            else outf.write(share.data(), (std::streamsize)share.size());
-            if (to_file && !outf) die("write " + outp + " failed");
-        };
-        // every match bucket over the pieces of both files, in order, ends in its share of the heads
-        uint64_t file_records[2] = {0, 0};
-        for (auto& pc : pieces) file_records[pc.file] += pc.count;
-        if (bsk_concat_verdict_begin(ctx, file_records) != BSK_OK) die(bsk_last_error(ctx));
-        for (int b = 0; b < n_buckets; ++b) {
-            fill_bucket((uint32_t)bounds[b], (uint32_t)bounds[b + 1]);
-            uint64_t r = 0, f = 0;
-            if (bsk_concat_bucket_finish(ctx, nullptr, &r, &f) != BSK_OK) die(bsk_last_error(ctx));
-            removed += r;
-            flagged += f;
-        }
-        mark(E.mark_buckets);
-        // the weights over the pieces of file 2, the window histogram over those of file 1, the plan of the windows
-        if (bsk_concat_join_begin(ctx, nullptr) != BSK_OK) die(bsk_last_error(ctx));
-        int64_t k = 0;
-        for (int file = 1; file >= 0; --file)
-            for (auto& pc : pieces) {
-                uint64_t cnt = 0;
-                if ((int)pc.file == file && (file ? bsk_concat_weigh_run : bsk_concat_window_hist_run)(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr, &cnt) != BSK_OK)
-                    die(bsk_last_error(ctx));
-            }
-        if (bsk_concat_window_hist_get(ctx, hist.data(), nullptr) != BSK_OK) die(bsk_last_error(ctx));
-        if (bsk_shuffle_plan(hist.data(), budget, bounds.data(), &n_order_buckets) != BSK_OK)
-            die(std::string(bsk_global_error()) + " -- concat: a window bin holds the cost of at most a 4096th of the records of file 1, rounded up to a "
-                                                   "power of two: their text, the text of the records of file 2 with their IDs, and a bound of the joined "
-                                                   "records; an ID with many records in both files fills one");
-        mark("concat: weights, histogram of the windows");
-        uint32_t shift = 0;
-        while (file_records[0] && ((file_records[0] - 1) >> shift) >= kBins) ++shift;
-        for (int b = 0; b < n_order_buckets; ++b) {
-            const uint64_t lo = bounds[b], hi = bounds[b + 1];
-            if (bsk_concat_window_begin(ctx, (uint32_t)lo, (uint32_t)hi) != BSK_OK) die(bsk_last_error(ctx));
-            for (auto& pc : pieces) {
-                // (a piece of file 1 wholly outside the window adds nothing)
-                if (pc.file == 0 && (pc.count == 0 || ((pc.first + pc.count - 1) >> shift) < lo || (pc.first >> shift) >= hi)) continue;
-                if (bsk_concat_window_add(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr) != BSK_OK) die(bsk_last_error(ctx));
-            }
-            bsk_out out;
-            if (bsk_concat_window_finish(ctx, nullptr, &out) != BSK_OK) die(bsk_last_error(ctx));
-            write_share(out);
-        }
-        mark("concat: windows");
-        if (inv.pget("full") == "true") {
-            for (auto& pc : pieces) {
-                if (pc.file != 1) continue;
-                bsk_out out;
-                if (bsk_concat_tail_run(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr, &out) != BSK_OK) die(bsk_last_error(ctx));
-                write_share(out);
-            }
-            mark("concat: tail");
-        }
-        if (to_file) {
-            outf.close();
-            if (!outf) die("write " + outp + " failed");
-        }
+        R.concat_tail(inv);
     } else if (pair) {
-        const bool unp = inv.pget("save-unpaired") == "true";
-        if (!is_dir(outdir) && mkdir(outdir.c_str(), 0755) != 0) die("cannot create directory " + outdir);
-        const char* names[4] = {"paired.1", "paired.2", "unpaired.1", "unpaired.2"};
-        std::ofstream outf[4];
-        for (int k = 0; k < (unp ? 4 : 2); ++k) {
-            outf[k].open(outdir + "/" + names[k], std::ios::binary);
-            if (!outf[k]) die("cannot create " + outdir + "/" + names[k]);
-        }
-        std::string share;
-        auto write_share = [&](int k, const bsk_out& out) {
-            if (!out.len || !outf[k].is_open()) return;
-            share.resize(out.len);
-            if (bsk_out_to_host(ctx, &out, &share[0], out.len) != BSK_OK) die(bsk_last_error(ctx));
-            outf[k].write(share.data(), (std::streamsize)share.size());
-            if (!outf[k]) die("write " + outdir + "/" + names[k] + " failed");
-        };
-        // every match bucket over the pieces of both files, in order, ends in its share of the paired bits and the mates
-        uint64_t file_records[2] = {0, 0};
-        for (auto& pc : pieces) file_records[pc.file] += pc.count;
-        if (bsk_pair_verdict_begin(ctx, file_records) != BSK_OK) die(bsk_last_error(ctx));
-        for (int b = 0; b < n_buckets; ++b) {
-            fill_bucket((uint32_t)bounds[b], (uint32_t)bounds[b + 1]);
-            uint64_t r = 0, f = 0;
-            if (bsk_pair_bucket_finish(ctx, nullptr, &r, &f) != BSK_OK) die(bsk_last_error(ctx));
-            removed += r;
-            flagged += f;
-        }
-        mark(E.mark_buckets);
-        uint64_t n_pairs = 0;
-        int in_mate_order = 0;
-        if (bsk_pair_order_begin(ctx, nullptr, &n_pairs, &in_mate_order) != BSK_OK) die(bsk_last_error(ctx));
-        const char* forced = getenv("BSK_PAIR_ORDER");  // (the switch pair_order of the context: the emit leaves paired.2 to the order phase)
-        const bool by_emit = in_mate_order && !(forced && std::string(forced) == "buckets");
-        // the emit: paired.1 and unpaired.1 from the pieces of file 1; unpaired.2 -- and paired.2 when it is a filter of file 2 --
-        // from those of file 2, which are not read when neither is wanted
-        int64_t k = 0;
-        for (auto& pc : pieces) {
-            if (pc.file == 1 && !unp && !by_emit) break;
-            bsk_out outs[3];
-            if (bsk_pair_emit_run(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr, outs) != BSK_OK) die(bsk_last_error(ctx));
-            if (pc.file == 0) write_share(0, outs[0]);
-            else write_share(1, outs[2]);
-            write_share(pc.file == 0 ? 2 : 3, outs[1]);
-        }
-        mark("pair: emit");
-        if (n_pairs && !by_emit) {
-            // paired.2 in buckets of the position: the histogram over the pieces of file 2, the plan, one pass per bucket
-            for (auto& pc : pieces) {
-                uint64_t cnt = 0;
-                if (pc.file == 1 && bsk_pair_order_hist_run(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr, &cnt) != BSK_OK) die(bsk_last_error(ctx));
-            }
-            if (bsk_pair_order_hist_get(ctx, hist.data(), nullptr) != BSK_OK) die(bsk_last_error(ctx));
-            if (bsk_shuffle_plan(hist.data(), budget, bounds.data(), &n_order_buckets) != BSK_OK)
-                die(std::string(bsk_global_error()) + " -- pair: an order bin holds the text of the records of paired.2 whose positions share their upper bits, "
-                                                       "at most a 4096th of the pairs rounded up to a power of two");
-            for (int b = 0; b < n_order_buckets; ++b) {
-                if (bsk_pair_order_bucket_begin(ctx, (uint32_t)bounds[b], (uint32_t)bounds[b + 1]) != BSK_OK) die(bsk_last_error(ctx));
-                for (auto& pc : pieces)
-                    if (pc.file == 1 && bsk_pair_order_bucket_add(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr) != BSK_OK) die(bsk_last_error(ctx));
-                bsk_out out;
-                if (bsk_pair_order_bucket_finish(ctx, nullptr, &out) != BSK_OK) die(bsk_last_error(ctx));
-                write_share(1, out);
-            }
-            mark("pair: order buckets");
-        }
-        for (int j = 0; j < 4; ++j)
-            if (outf[j].is_open()) {
-                outf[j].close();
-                if (!outf[j]) die("write " + outdir + "/" + names[j] + " failed");
-            }
-    } else if (common) {
-        // every bucket over the pieces of all files, in order, ends in its share of the keep bits of the first file; one emit pass
-        // over the pieces of the first file prints its kept records in file order
-        std::vector<uint64_t> file_records(files.size(), 0);
-        for (auto& pc : pieces) file_records[pc.file] += pc.count;
-        if (bsk_common_verdict_begin(ctx, file_records.data(), (uint32_t)file_records.size()) != BSK_OK) die(bsk_last_error(ctx));
-        for (int b = 0; b < n_buckets; ++b) {
-            fill_bucket((uint32_t)bounds[b], (uint32_t)bounds[b + 1]);
-            uint64_t r = 0, f = 0;
-            if (bsk_common_bucket_finish(ctx, nullptr, &r, &f) != BSK_OK) die(bsk_last_error(ctx));
-            removed += r;
-            flagged += f;
-        }
-        mark(E.mark_buckets);
-        int64_t k = 0;
-        for (auto& pc : pieces) {
-            if (pc.file != 0) break;
-            bsk_out out;
-            if (bsk_common_emit_run(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr, &out) != BSK_OK) die(bsk_last_error(ctx));
-            append_out(out);
-        }
-        mark("common: emit");
-    } else if (rmdup || rename) {
-        // every bucket over all pieces, in order, ends in its share of the verdict; one emit pass prints the survivors (rename:
-        // every record under its new name) in file order
-        const uint64_t total_records = pieces.empty() ? 0 : pieces.back().first + last_count;
-        if ((rename ? bsk_rename_verdict_begin : bsk_rmdup_verdict_begin)(ctx, total_records) != BSK_OK) die(bsk_last_error(ctx));
-        for (int b = 0; b < n_buckets; ++b) {
-            fill_bucket((uint32_t)bounds[b], (uint32_t)bounds[b + 1]);
-            uint64_t r = 0, f = 0;
-            if ((rename ? bsk_rename_bucket_finish : bsk_rmdup_bucket_finish)(ctx, nullptr, &r, &f) != BSK_OK) die(bsk_last_error(ctx));
-            removed += r;
-            flagged += f;
-        }
-        mark(E.mark_buckets);
-        int64_t k = 0;
-        for (auto& pc : pieces) {
-            bsk_out out;
-            if ((rename ? bsk_rename_emit_run : bsk_rmdup_emit_run)(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr, &out) != BSK_OK) die(bsk_last_error(ctx));
-            append_out(out);
-        }
-        mark(rename ? "rename: emit" : "rmdup: emit");
+        R.pair_tail(inv, outdir);
+    } else if (R.cmd.finish_out) {
+        R.print_buckets(use == "sort" && inv.pget("reverse") == "true");
     } else {
-        // every finished bucket is appended to the output; sort -r: from the last to the first
-        const bool backwards = sort && inv.pget("reverse") == "true";
-        for (int i = 0; i < n_buckets; ++i) {
-            const int b = backwards ? n_buckets - 1 - i : i;
-            fill_bucket((uint32_t)bounds[b], (uint32_t)bounds[b + 1]);
-            bsk_out out;
-            if ((sort ? bsk_sort_bucket_finish(ctx, nullptr, &out) : bsk_shuffle_bucket_finish(ctx, nullptr, &out)) != BSK_OK) die(bsk_last_error(ctx));
-            append_out(out);
-        }
-        mark(E.mark_buckets);
+        R.decide_buckets();
+        R.emit_pieces();
     }
     if (timing) {
         std::vector<char> buf(1 << 16);
-        if (bsk_profile_dump(ctx, buf.data(), buf.size()) == BSK_OK)
-            fprintf(stderr, "[timing] %s in %d bucket(s) of at most %llu bytes, %zu piece(s); stages: %s\n", use.c_str(), n_buckets,
-                    (unsigned long long)budget, pieces.size(), buf.data());
-        if (rmdup)
-            fprintf(stderr, "[timing] rmdup: %llu record(s) removed, %llu flagged (subject differed from the survivor of its key group)\n",
-                    (unsigned long long)removed, (unsigned long long)flagged);
-        if (rename)
-            fprintf(stderr, "[timing] rename: %llu record(s) renamed, %llu flagged (subject differed from the first of its key group)\n",
-                    (unsigned long long)removed, (unsigned long long)flagged);
-        if (common)
-            fprintf(stderr, "[timing] common: %llu record(s) kept, %llu flagged (subject differed from the first of its key group)\n",
-                    (unsigned long long)removed, (unsigned long long)flagged);
-        if (pair)
-            fprintf(stderr, "[timing] pair: %llu pair(s), %llu flagged (subject differed from the first of its key group), %d order bucket(s)\n",
-                    (unsigned long long)removed, (unsigned long long)flagged, n_order_buckets);
-        if (concat)
-            fprintf(stderr, "[timing] concat: %llu record(s) with a head, %llu flagged (subject differed from the first of its key group), %d window(s)\n",
-                    (unsigned long long)removed, (unsigned long long)flagged, n_order_buckets);
+        if (bsk_profile_dump(R.ctx, buf.data(), buf.size()) == BSK_OK)
+            fprintf(stderr, "[timing] %s in %d bucket(s) of at most %llu bytes, %zu piece(s); stages: %s\n", use.c_str(), R.n_buckets,
+                    (unsigned long long)R.budget, R.pieces.size(), buf.data());
+        if (R.cmd.counted) {
+            fprintf(stderr, "[timing] %s: %llu %s, %llu flagged (subject differed from the %s of its key group)", use.c_str(),
+                    (unsigned long long)R.counted, R.cmd.counted, (unsigned long long)R.flagged, R.cmd.group_first);
+            if (R.cmd.second_phase) fprintf(stderr, ", %d %s", R.n_second, R.cmd.second_phase);
+            fprintf(stderr, "\n");
+        }
     }
-    for (auto& f : files)
-        if (f.mapped && f.size) munmap((void*)f.text, f.size);
-    bsk_destroy(ctx);
-    return res;
+    for (auto& f : R.files) f.unmap();
+    bsk_destroy(R.ctx);
+    return R.res;
 }
 
 int run_devices(const Invocation& inv) {

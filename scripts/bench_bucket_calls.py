@@ -7,12 +7,10 @@ of the whole sequence and of every call kind (summed over the buckets), and the 
   python scripts/bench_bucket_calls.py [GB per shard, default 2] [reps, default 9] [--buckets N, default 4]"""
 import ctypes as C
 import json
-import os
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from bucket_bench import synth
 import torch
 import bigseqkit_amd as bsk
 from bigseqkit_amd import _lib
@@ -28,15 +26,6 @@ gb = float(argv[0]) if len(argv) > 0 else 2.0
 reps = int(argv[1]) if len(argv) > 1 else 9
 
 
-def synth(kind, nbytes):
-    rb = lib.bsk_synth_record_bytes(kind)
-    n = int(nbytes) // rb * rb
-    t = torch.empty(n, dtype=torch.uint8, device="cuda")
-    check(lib.bsk_synth_device(kind, 42, 0, 0, C.c_void_p(t.data_ptr()), n, 0, None))
-    torch.cuda.synchronize()
-    return t
-
-
 def med(v):
     v = sorted(v)
     return round(v[len(v) // 2], 4)
@@ -44,7 +33,7 @@ def med(v):
 
 res = {}
 for label, kind, fmt in (("fastq150", 0, 1), ("fasta1k", 1, 0)):
-    t = synth(kind, gb * 1e9)
+    t, _ = synth(kind, gb * 1e9)
     ptr, n = C.c_void_p(t.data_ptr()), t.numel()
     out = _lib.Out()
     with bsk.Operator("Shuffle", "{}", 0) as op:

@@ -13,12 +13,9 @@ tuned.  Prints one JSON object.  Not the driver's bench (that is bench.py).
   python scripts/bench_common_buckets.py [GB of file 1, default 1] [reps, default 3]"""
 import ctypes as C
 import json
-import os
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from bucket_bench import synth_at, device_copy, measure, profiled
 import torch
 import bigseqkit_amd as bsk
 from bigseqkit_amd import _lib
@@ -34,48 +31,10 @@ def synth(kind, nbytes):
     rb = lib.bsk_synth_record_bytes(kind)
     half = int(nbytes) // (2 * rb) * rb
     t = torch.empty(3 * half, dtype=torch.uint8, device="cuda")
-    check(lib.bsk_synth_device(kind, 42, 0, 0, C.c_void_p(t.data_ptr()), 2 * half, 0, None))
-    check(lib.bsk_synth_device(kind, 42, 0, 0, C.c_void_p(t.data_ptr() + 2 * half), half, 0, None))
+    synth_at(kind, t, 0, 2 * half)
+    synth_at(kind, t, 2 * half, half)
     torch.cuda.synchronize()
     return t, 2 * half
-
-
-def stages_of(op):
-    pb = C.create_string_buffer(1 << 16)
-    check(lib.bsk_profile_dump(op.ctx, pb, len(pb)), op.ctx)
-    stages = {}
-    for item in pb.value.decode().split(";"):
-        if "=" in item:
-            k, v = item.rsplit("=", 1)
-            stages[k] = round(float(v.split("/")[0]), 3)
-    return stages
-
-
-def device_copy(out):
-    got = torch.empty(out.len, dtype=torch.uint8, device="cuda")
-    if out.len:
-        check(lib.bsk_device_copy(C.c_void_p(got.data_ptr()), out.d_data, out.len, 3))
-    return got
-
-
-def measure(run):
-    run(False)  # (sizes the buffers)
-    ms = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        run(False)
-        ms.append((time.perf_counter() - t0) * 1e3)
-    ms.sort()
-    med = ms[len(ms) // 2]
-    return {"ms": round(med, 3), "spread": round((ms[-1] - ms[0]) / med, 3)}
-
-
-def profiled(op, run, leg):
-    lib.bsk_profile_reset(op.ctx)
-    lib.bsk_profile_enable(op.ctx, 1)
-    got = run(True)
-    leg["stages_ms"] = stages_of(op)
-    return got
 
 
 def one_call(t, n_first, fmt, opts):
@@ -86,7 +45,7 @@ def one_call(t, n_first, fmt, opts):
             check(lib.bsk_common_run(op.ctx, C.c_void_p(t.data_ptr()), t.numel(), ends, 2, 1, fmt, None, C.byref(out)), op.ctx)
             torch.cuda.synchronize()
             return device_copy(out) if keep else None
-        leg = measure(run)
+        leg = measure(run, reps)
         got = profiled(op, run, leg)
     return leg, got
 
@@ -118,7 +77,7 @@ def in_buckets(t, n_first, fmt, opts, nb):
             info.update(buckets=len(bounds) - 1, records=counts, kept=kept, flagged=flagged, subject_share=round(sum(hb) / max(1, t.numel()), 4),
                         largest_bin_share=round(max(hb) / max(1, sum(hb)), 4))
             return device_copy(out) if keep else None
-        leg = measure(run)
+        leg = measure(run, reps)
         got = profiled(op, run, leg)
     leg.update(info)
     return leg, got

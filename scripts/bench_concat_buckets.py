@@ -14,12 +14,9 @@ driver's bench (that is bench.py).
   python scripts/bench_concat_buckets.py [GB of either file, default 1] [reps, default 3]"""
 import ctypes as C
 import json
-import os
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from bucket_bench import synth_two_files, device_copy, measure, profiled
 import torch
 import bigseqkit_amd as bsk
 from bigseqkit_amd import _lib
@@ -32,62 +29,6 @@ FMT = 1  # FASTQ
 OPTS = json.dumps({"Full": False})
 
 
-def device_copy(out):
-    got = torch.empty(out.len, dtype=torch.uint8, device="cuda")
-    if out.len:
-        check(lib.bsk_device_copy(C.c_void_p(got.data_ptr()), out.d_data, out.len, 3))
-    return got
-
-
-def synth(nbytes, shuffled):
-    """file 1 and, behind it in one tensor, file 2: (tensor, bytes of file 1)"""
-    rb = lib.bsk_synth_record_bytes(0)
-    n1 = int(nbytes) // (4 * rb) * 4 * rb
-    t = torch.empty(2 * n1, dtype=torch.uint8, device="cuda")
-    check(lib.bsk_synth_device(0, 42, 0, 0, C.c_void_p(t.data_ptr()), n1, 0, None))
-    if shuffled:
-        out = _lib.Out()
-        with bsk.Operator("Shuffle", json.dumps({"Seed": 11}), 0) as op:
-            check(lib.bsk_shuffle_run(op.ctx, C.c_void_p(t.data_ptr()), n1, 1, FMT, 0, None, C.byref(out)), op.ctx)
-            assert out.len == n1
-            check(lib.bsk_device_copy(C.c_void_p(t.data_ptr() + n1), out.d_data, n1, 3))
-    else:
-        check(lib.bsk_synth_device(0, 42, 0, 0, C.c_void_p(t.data_ptr() + n1), n1, 0, None))
-    torch.cuda.synchronize()
-    return t, n1
-
-
-def stages_of(op):
-    pb = C.create_string_buffer(1 << 16)
-    check(lib.bsk_profile_dump(op.ctx, pb, len(pb)), op.ctx)
-    stages = {}
-    for item in pb.value.decode().split(";"):
-        if "=" in item:
-            k, v = item.rsplit("=", 1)
-            stages[k] = round(float(v.split("/")[0]), 3)
-    return stages
-
-
-def measure(run):
-    run(False)  # (sizes the buffers)
-    ms = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        run(False)
-        ms.append((time.perf_counter() - t0) * 1e3)
-    ms.sort()
-    med = ms[len(ms) // 2]
-    return {"ms": round(med, 3), "spread": round((ms[-1] - ms[0]) / med, 3)}
-
-
-def profiled(op, run, leg):
-    lib.bsk_profile_reset(op.ctx)
-    lib.bsk_profile_enable(op.ctx, 1)
-    got = run(True)
-    leg["stages_ms"] = stages_of(op)
-    return got
-
-
 def one_call(t, n1):
     out = _lib.Out()
     with bsk.Operator("Concat", OPTS, 0) as op:
@@ -95,7 +36,7 @@ def one_call(t, n1):
             check(lib.bsk_concat_run(op.ctx, C.c_void_p(t.data_ptr()), t.numel(), n1, 1, FMT, None, C.byref(out)), op.ctx)
             torch.cuda.synchronize()
             return device_copy(out) if keep else None
-        leg = measure(run)
+        leg = measure(run, reps)
         got = profiled(op, run, leg)
     return leg, got
 
@@ -146,7 +87,7 @@ def in_buckets(t, n1, nb):
             info.update(buckets=len(bounds) - 1, windows=len(wbounds) - 1, records=counts, with_head=matched, flagged=flagged,
                         reads={"file 1": reads[0], "file 2": reads[1]})
             return torch.cat(shares) if keep else None
-        leg = measure(run)
+        leg = measure(run, reps)
         got = profiled(op, run, leg)
     leg.update(info)
     return leg, got
@@ -154,7 +95,7 @@ def in_buckets(t, n1, nb):
 
 res = {}
 for label, shuffled in (("in order", False), ("shuffled", True)):
-    t, n1 = synth(gb * 1e9, shuffled)
+    t, n1 = synth_two_files(gb * 1e9, 4, shuffled)  # (file 2: as long as file 1)
     one, want = one_call(t, n1)
     for nb in (1, 4, 16):
         leg, got = in_buckets(t, n1, nb)

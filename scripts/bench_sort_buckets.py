@@ -10,12 +10,9 @@ and the 32 samples per bin are starting values.  Prints one JSON object.  Not th
   python scripts/bench_sort_buckets.py [GB per shard, default 2] [reps, default 3] [--buckets N, default 4]"""
 import ctypes as C
 import json
-import os
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from bucket_bench import synth, device_copy, measure, profiled
 import torch
 import bigseqkit_amd as bsk
 from bigseqkit_amd import _lib
@@ -31,45 +28,6 @@ gb = float(argv[0]) if len(argv) > 0 else 2.0
 reps = int(argv[1]) if len(argv) > 1 else 3
 
 
-def synth(kind, nbytes):
-    rb = lib.bsk_synth_record_bytes(kind)
-    n = int(nbytes) // rb * rb
-    t = torch.empty(n, dtype=torch.uint8, device="cuda")
-    check(lib.bsk_synth_device(kind, 42, 0, 0, C.c_void_p(t.data_ptr()), n, 0, None))
-    torch.cuda.synchronize()
-    return t, n // rb
-
-
-def stages_of(op):
-    pb = C.create_string_buffer(1 << 16)
-    check(lib.bsk_profile_dump(op.ctx, pb, len(pb)), op.ctx)
-    stages = {}
-    for item in pb.value.decode().split(";"):
-        if "=" in item:
-            k, v = item.rsplit("=", 1)
-            stages[k] = round(float(v.split("/")[0]), 3)
-    return stages
-
-
-def device_copy(out):
-    got = torch.empty(out.len, dtype=torch.uint8, device="cuda")
-    if out.len:
-        check(lib.bsk_device_copy(C.c_void_p(got.data_ptr()), out.d_data, out.len, 3))
-    return got
-
-
-def measure(run):
-    run(False)  # (sizes the buffers)
-    ms = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        run(False)
-        ms.append((time.perf_counter() - t0) * 1e3)
-    ms.sort()
-    med = ms[len(ms) // 2]
-    return {"ms": round(med, 3), "spread": round((ms[-1] - ms[0]) / med, 3)}
-
-
 def one_pass(t, fmt, opts):
     out = _lib.Out()
     with bsk.Operator("Sort", json.dumps(opts), 0) as op:
@@ -77,11 +35,8 @@ def one_pass(t, fmt, opts):
             check(lib.bsk_sort_run(op.ctx, C.c_void_p(t.data_ptr()), t.numel(), 1, fmt, 0, None, C.byref(out)), op.ctx)
             torch.cuda.synchronize()
             return device_copy(out) if keep else None
-        leg = measure(run)
-        lib.bsk_profile_reset(op.ctx)
-        lib.bsk_profile_enable(op.ctx, 1)
-        got = run(True)
-        leg["stages_ms"] = stages_of(op)
+        leg = measure(run, reps)
+        got = profiled(op, run, leg)
     return leg, got
 
 
@@ -114,11 +69,8 @@ def in_buckets(t, fmt, opts, n_records, nb):
             info["buckets"] = len(buckets)
             info["largest_bin_share"] = round(max(hb) / max(1, sum(hb)), 4)
             return torch.cat(parts) if parts else None
-        leg = measure(run)
-        lib.bsk_profile_reset(op.ctx)
-        lib.bsk_profile_enable(op.ctx, 1)
-        got = run(True)
-        leg["stages_ms"] = stages_of(op)
+        leg = measure(run, reps)
+        got = profiled(op, run, leg)
     leg.update(info)
     return leg, got
 
