@@ -111,6 +111,7 @@ SIGNATURES = {
     "bsk_stats_finalize": (_i, [_vp, _p(_i64), _p(_i64), _sz, _p(StatInfo)]),
     "bsk_stats_string": (_i, [_vp, C.c_char_p, C.c_char_p, _p(StatInfo), C.c_char_p, _sz]),
     "bsk_out_to_host": (_i, [_vp, _p(Out), _vp, _sz]),
+    "bsk_out_to_host_bgzf": (_i, [_vp, _p(Out), _i, _vp, _sz, _p(_sz)]),
     "bsk_out_materialize": (_i, [_vp, _p(Out), _vp]),
     "bsk_index_build": (_i, [_vp, _vp, _sz, _i, _i, _vp, _p(_u64)]),
     "bsk_index_copy": (_i, [_vp, _p(_u64), _p(C.c_uint32), _p(C.c_uint32), _p(C.c_uint32), _sz]),
@@ -219,6 +220,9 @@ SIGNATURES = {
     "bsk_bgzf_blocks_device": (_i, [_vp, _sz, _i, _p(C.c_uint64), _p(C.c_uint32), _p(C.c_uint32), _sz, _p(_sz)]),
     "bsk_bgzf_inflate_host": (_i, [C.c_char_p, _sz, _vp, _sz, _p(_sz), _i]),
     "bsk_selftest_bgzf_crc": (C.c_uint32, [C.c_char_p, _sz]),
+    "bsk_bgzf_deflate_bound": (_sz, [_sz, C.c_uint32]),
+    "bsk_bgzf_deflate_device": (_i, [_vp, _sz, _i, C.c_uint32, _i, _p(_vp), _p(_sz)]),
+    "bsk_bgzf_deflate_host": (_i, [C.c_char_p, _sz, C.c_uint32, _i, _vp, _sz, _p(_sz), _i]),
     "bsk_synth_record_bytes": (_sz, [_i]),
     "bsk_synth_offset": (_u64, [_i, _u64]),
     "bsk_synth_host": (_i, [_i, _u64, C.c_uint, _u64, _vp, _sz]),
@@ -230,6 +234,7 @@ SIGNATURES = {
     "bsk_selftest_regex_find": (_i, [C.c_char_p, C.c_char_p, _sz, _sz, _p(C.c_uint32), _p(C.c_uint32)]),
     "bsk_store_open": (_i, [C.c_char_p, _i, _p(_vp)]),
     "bsk_store_error": (C.c_char_p, [_vp]),
+    "bsk_store_set_bgzf": (_i, [_vp, _i]),
     "bsk_store_put": (_i, [_vp, _vp, _u64, _vp]),
     "bsk_store_put_host": (_i, [_vp, _u64, _vp, _sz]),
     "bsk_store_close": (_i, [_vp, _p(_u64)]),

@@ -144,6 +144,62 @@ def BgzfBlocks(data, device=0):
     return [(int(coff[i]), int(csize[i]), int(usize[i])) for i in range(k)]
 
 
+# ---- BGZF output (include/bsk.h "BGZF output"; PARITY.md BGZFW)
+def BgzfDeflateHost(data, block_bytes=0, eof=True, threads=0):
+    """the BGZF file that holds `data` (bytes), encoded on host threads: the bytes BgzfDeflate gives"""
+    data = bytes(data)
+    cap = int(lib.bsk_bgzf_deflate_bound(len(data), block_bytes))
+    buf = C.create_string_buffer(max(1, cap))
+    n_out = C.c_size_t()
+    check(lib.bsk_bgzf_deflate_host(data, len(data), block_bytes, 1 if eof else 0, buf, cap, C.byref(n_out), threads))
+    return buf.raw[:n_out.value]
+
+
+def BgzfDeflate(data, device=0, block_bytes=0, eof=True):
+    """the BGZF file that holds `data`: bytes or a CUDA uint8 tensor in, bytes out, one block per wavefront on the device (only
+    the compressed bytes come back).  block_bytes: the text of a block, 0 = 65 280.  device=-1: BgzfDeflateHost"""
+    if device < 0:
+        return BgzfDeflateHost(data, block_bytes, eof)
+    keep, ptr, n = _device_input(data, device)
+    d_comp, n_comp = C.c_void_p(), C.c_size_t()
+    check(lib.bsk_bgzf_deflate_device(ptr, n, device, block_bytes, 1 if eof else 0, C.byref(d_comp), C.byref(n_comp)))
+    del keep
+    buf = C.create_string_buffer(max(1, n_comp.value))
+    try:
+        if n_comp.value:
+            check(lib.bsk_device_copy(buf, d_comp, n_comp.value, 2))  # BSK_COPY_D2H
+    finally:
+        lib.bsk_device_free(d_comp)
+    return buf.raw[:n_comp.value]
+
+
+def WriteSeqFile(path, text_or_result, device=0):
+    """the counterpart of ReadSeqFile: the text -- bytes, a uint8 tensor, or a SeqFrame, whose shards follow each other -- goes
+    to `path`.  A path that ends in .gz / .bgz gets BGZF (text on the device is compressed there, bytes on host threads; the
+    pieces end with ONE EOF block), anything else the plain text.  Returns the bytes written"""
+    parts = text_or_result.shards if isinstance(text_or_result, SeqFrame) else [text_or_result]
+    packed = os.fspath(path).lower().endswith((".gz", ".bgz"))
+    total = 0
+    with open(os.fspath(path), "wb") as f:
+        for part in parts:
+            on_device = hasattr(part, "data_ptr") and part.is_cuda
+            if hasattr(part, "data_ptr") and not on_device:   # (a tensor in host memory: its bytes, not its elements one by one)
+                part = part.numpy().tobytes()
+            if packed:
+                piece = BgzfDeflate(part, part.device.index if on_device else -1, 0, False)
+            elif on_device:
+                piece = bytes(part.cpu().numpy().tobytes())
+            else:
+                piece = bytes(part)
+            f.write(piece)
+            total += len(piece)
+        if packed:
+            tail = BgzfDeflateHost(b"", 0, True)   # the EOF block
+            f.write(tail)
+            total += len(tail)
+    return total
+
+
 def _format_of(path, first):
     """the format of a file: its first TEXT byte, else the suffix under a trailing .gz / .bgz"""
     if first == b">":

@@ -18,6 +18,7 @@
 #include "anchor.hpp"
 #include "ctx.hpp"
 #include "ops_bgzf.hpp"
+#include "ops_bgzf_write.hpp"
 #include "ops_host.hpp"
 #include "ops_host_internal.hpp"
 #include "ops_sample.hpp"
@@ -742,6 +743,23 @@ int bsk_bgzf_inflate_host(const void* comp, size_t n_comp, void* out, size_t cap
     if (!n_out || (!comp && n_comp)) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bgzf: null argument");
     std::string err;
     const int rc = bgzf_inflate_host(comp, n_comp, out, cap, n_out, threads, err);
+    return rc == BSK_OK ? rc : fail_global(rc, err);
+}
+
+// ---- BGZF output (ops_bgzf_write.hip): thin shells as for the input
+size_t bsk_bgzf_deflate_bound(size_t n_text, uint32_t block_text_bytes) { return bgzf_deflate_bound(n_text, block_text_bytes); }
+
+int bsk_bgzf_deflate_device(const void* d_text, size_t n_text, int device, uint32_t block_text_bytes, int eof, void** d_comp, size_t* n_comp) {
+    if (!d_comp || !n_comp || (!d_text && n_text)) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bgzf: null argument");
+    std::string err;
+    const int rc = bgzf_deflate_device(d_text, n_text, device, block_text_bytes, eof != 0, d_comp, n_comp, err);
+    return rc == BSK_OK ? rc : fail_global(rc, err);
+}
+
+int bsk_bgzf_deflate_host(const void* text, size_t n, uint32_t block_text_bytes, int eof, void* out, size_t cap, size_t* n_out, int threads) {
+    if (!n_out || (!text && n)) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bgzf: null argument");
+    std::string err;
+    const int rc = bgzf_deflate_host(text, n, block_text_bytes, eof != 0, out, cap, n_out, threads, err);
     return rc == BSK_OK ? rc : fail_global(rc, err);
 }
 
@@ -2051,6 +2069,7 @@ int bsk_profile_enable(bsk_ctx* c, int on) {
     if (!c) return BSK_ERR_INVALID_ARG;
     c->profile = on != 0;
     bgzf_profile_enable(on != 0);  // (the BGZF calls have no context: their stages are the process's)
+    bgzf_write_profile_enable(on != 0);
     return BSK_OK;
 }
 
@@ -2091,6 +2110,7 @@ int bsk_profile_dump(bsk_ctx* c, char* buf, size_t cap) {
         out += num;
     }
     out += bgzf_profile_text();  // bgzf_find, bgzf_sizes, bgzf_inflate
+    out += bgzf_write_profile_text();  // bgzf_deflate, bgzf_pack
     if (c->translate_stream_fallbacks) {  // (not a stage: how often the one-pass translate did not fit and the tables ran instead)
         char num[96];
         snprintf(num, sizeof num, "translate_stream_fallback=0.000000/%llu;", (unsigned long long)c->translate_stream_fallbacks);
@@ -2113,6 +2133,7 @@ int bsk_profile_reset(bsk_ctx* c) {
     bsk_profile_read(c, "", &d, &l);
     c->prof.clear();
     bgzf_profile_reset();
+    bgzf_write_profile_reset();
     c->hg_indexed_bytes = 0;
     return BSK_OK;
 }

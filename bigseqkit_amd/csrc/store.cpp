@@ -31,6 +31,7 @@
 
 #include <cerrno>
 #include <cstring>
+#include <functional>
 #include <future>
 #include <map>
 #include <mutex>
@@ -42,6 +43,7 @@
 #include "ctx.hpp"
 #include "ops_host.hpp"
 #include "ops_host_internal.hpp"
+#include "ops_bgzf_write.hpp"
 #include "ops_segcopy.hpp"
 
 using namespace bsk;
@@ -57,6 +59,9 @@ struct bsk_store {
     std::map<uint64_t, Pending> parts;  // parts that are not `next` yet (single file) / open part files (directory)
     uint64_t total = 0;
     std::string err;
+    bool bgzf = false;         // bsk_store_set_bgzf: what is put is text, what is written is BGZF (every put piece whole blocks)
+    bool bgzf_eof = true;      // ... and a file ends with the EOF block (off: the file is a piece of one, bsk_store_set_bgzf(s, 2))
+    bool touched = false;      // something was put: the mode stays
 };
 
 namespace {
@@ -64,6 +69,13 @@ namespace {
 int store_fail(bsk_store* s, const std::string& m) {
     if (s) s->err = m;
     return BSK_ERR_INVALID_ARG;
+}
+
+// the file of a part in directory mode
+std::string part_name(const bsk_store* s, uint64_t part) {
+    char nm[64];
+    snprintf(nm, sizeof nm, s->bgzf ? "/part%05llu.gz" : "/part%05llu", (unsigned long long)part);
+    return s->path + nm;
 }
 
 bool write_all(int fd, const uint8_t* p, size_t n, uint64_t at) {
@@ -75,23 +87,35 @@ bool write_all(int fd, const uint8_t* p, size_t n, uint64_t at) {
     return true;
 }
 
+// a part file is complete: in BGZF mode the EOF block ends it
+bool end_part_file(bsk_store* s, int fd, uint64_t off) {
+    if (!s->bgzf || !s->bgzf_eof) return true;
+    uint8_t e[28];
+    bgzf_eof_block(e);
+    s->total += sizeof e;
+    return write_all(fd, e, sizeof e, off);
+}
+
 // bytes of part `part`; last: the part is complete
 int store_append(bsk_store* s, uint64_t part, const uint8_t* data, size_t n, bool last) {
     std::lock_guard<std::mutex> g(s->mu);
     if (!s->merge) {  // a file per partition (SaveAsTextFile)
         auto& P = s->parts[part];
         if (P.fd < 0) {
-            char nm[64];
-            snprintf(nm, sizeof nm, "/part%05llu", (unsigned long long)part);
-            P.fd = open((s->path + nm).c_str(), O_RDWR | O_CREAT | O_TRUNC, 0644);
-            if (P.fd < 0) return store_fail(s, "libbsk: cannot create " + s->path + nm + ": " + strerror(errno));
+            const std::string nm = part_name(s, part);
+            P.fd = open(nm.c_str(), O_RDWR | O_CREAT | O_TRUNC, 0644);
+            if (P.fd < 0) return store_fail(s, "libbsk: cannot create " + nm + ": " + strerror(errno));
             P.bytes.clear();
             P.off = 0;
         }
         if (!write_all(P.fd, data, n, P.off)) return store_fail(s, "libbsk: write failed: " + std::string(strerror(errno)));
         P.off += n;
         s->total += n;
-        if (last) { close(P.fd); s->parts.erase(part); }
+        if (last) {
+            if (!end_part_file(s, P.fd, P.off)) return store_fail(s, "libbsk: write failed: " + std::string(strerror(errno)));
+            close(P.fd);
+            s->parts.erase(part);
+        }
         return BSK_OK;
     }
     if (part < s->next) return store_fail(s, "libbsk: part " + std::to_string(part) + " was already completed");
@@ -156,10 +180,9 @@ int reserve_target(bsk_store* s, uint64_t part, size_t n, Target* t) {
     if (!s->merge) {
         auto& P = s->parts[part];
         if (P.fd < 0) {
-            char nm[64];
-            snprintf(nm, sizeof nm, "/part%05llu", (unsigned long long)part);
-            P.fd = open((s->path + nm).c_str(), O_RDWR | O_CREAT | O_TRUNC, 0644);
-            if (P.fd < 0) return store_fail(s, "libbsk: cannot create " + s->path + nm + ": " + strerror(errno));
+            const std::string nm = part_name(s, part);
+            P.fd = open(nm.c_str(), O_RDWR | O_CREAT | O_TRUNC, 0644);
+            if (P.fd < 0) return store_fail(s, "libbsk: cannot create " + nm + ": " + strerror(errno));
             P.off = 0;
         }
         t->direct = true; t->fd = P.fd; t->base = P.off;
@@ -180,7 +203,13 @@ int finish_part(bsk_store* s, uint64_t part) {
     std::lock_guard<std::mutex> g(s->mu);
     if (!s->merge) {
         auto it = s->parts.find(part);
-        if (it != s->parts.end()) { if (it->second.fd >= 0) close(it->second.fd); s->parts.erase(it); }
+        if (it != s->parts.end()) {
+            if (it->second.fd >= 0) {
+                if (!end_part_file(s, it->second.fd, it->second.off)) return store_fail(s, "libbsk: write failed: " + std::string(strerror(errno)));
+                close(it->second.fd);
+            }
+            s->parts.erase(it);
+        }
         return BSK_OK;
     }
     if (part != s->next) return BSK_OK;  // (kept in memory: store_append marked it done)
@@ -201,6 +230,48 @@ int finish_part(bsk_store* s, uint64_t part) {
     return BSK_OK;
 }
 
+}  // namespace
+
+namespace bsk {
+// The text of a result -- n bytes at d, or the list of slices `seg` (d null) -- as BGZF, in bounded pieces: a piece is
+// BGZF_PIECE bytes of text (whole blocks, so a piece boundary is a block boundary), gathered if need be, compressed on the
+// context's device without an EOF block and handed to sink(d_comp, n_comp) before the next one is made.
+int bgzf_pieces(bsk_ctx* c, const uint8_t* d, const bsk_ctx::PendingOut* seg, size_t n, std::string* err,
+                const std::function<int(const void*, size_t)>& sink) {
+    // whole blocks of text AND whole tiles of the gather (launch_seg_copy_range starts a piece on a tile): 65 280 = 2^8 * 255
+    // and 4 096 meet every 1 044 480 bytes; 64 of those are 64 MiB less 256 KiB
+    constexpr uint64_t BGZF_UNIT = 1044480, BGZF_PIECE_DEFAULT = 64 * BGZF_UNIT;
+    static_assert(BGZF_UNIT % SEG_TILE == 0 && BGZF_UNIT % 65280 == 0, "a piece boundary is a block boundary and a tile boundary");
+    // BSK_BGZF_PIECE_BYTES moves the line (tests: a result of a few MB in several pieces); rounded up to the unit
+    uint64_t BGZF_PIECE = BGZF_PIECE_DEFAULT;
+    if (const char* e = getenv("BSK_BGZF_PIECE_BYTES")) BGZF_PIECE = std::max<uint64_t>(1, (strtoull(e, nullptr, 10) + BGZF_UNIT - 1) / BGZF_UNIT) * BGZF_UNIT;
+    uint8_t* d_piece = nullptr;
+    if (seg && hipMalloc((void**)&d_piece, (size_t)std::min<uint64_t>(BGZF_PIECE, ((uint64_t)n + 4095) & ~4095ull)) != hipSuccess) {
+        *err = "libbsk: bgzf: no device memory for a piece of the result";
+        return BSK_ERR_HIP;
+    }
+    int rc = BSK_OK;
+    for (uint64_t at = 0; at < n && rc == BSK_OK; at += BGZF_PIECE) {
+        const uint64_t to = std::min<uint64_t>(n, at + BGZF_PIECE);
+        const uint8_t* from = d ? d + at : d_piece;
+        if (seg) {
+            hipError_t e = launch_seg_copy_range(seg->seg_src, seg->seg_off, seg->nseg, seg->first4k, d_piece, at, to, seg->total, seg->lo, seg->hi, nullptr);
+            if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+            if (e != hipSuccess) { *err = std::string("libbsk: gathering the slices of the result failed: ") + hipGetErrorString(e); rc = BSK_ERR_HIP; break; }
+        }
+        void* d_comp = nullptr;
+        size_t n_comp = 0;
+        rc = bgzf_deflate_device(from, (size_t)(to - at), c->device, 0, false, &d_comp, &n_comp, *err);
+        if (rc == BSK_OK) rc = sink(d_comp, n_comp);
+        if (d_comp) hipFree(d_comp);
+    }
+    if (d_piece) hipFree(d_piece);
+    return rc;
+}
+}  // namespace bsk
+
+namespace {
+
 // device bytes -> store.  Returns a status and, on failure, the message in *err (the caller owns the context's error
 // text: this function also runs on the writer thread of bsk_run_to_store, next to the thread that computes).
 int drain_to_store(bsk_ctx* c, bsk_store* s, uint64_t part, const uint8_t* d, size_t n, bool last, hipStream_t d2h, std::string* err,
@@ -211,7 +282,18 @@ int drain_to_store(bsk_ctx* c, bsk_store* s, uint64_t part, const uint8_t* d, si
     Drainer* D = (Drainer*)c->drainer;
     if (!D) { *err = "libbsk: drain without staging buffers"; return BSK_ERR_INVALID_ARG; }
     int rc = BSK_OK;
-    if (n) {
+    if (n && s->bgzf) {
+        // the text is compressed on the device in front of the D2H copy, piece by piece, and appended as the bytes of a part are
+        std::vector<uint8_t> host;
+        rc = bgzf_pieces(c, d, seg, n, err, [&](const void* d_comp, size_t n_comp) {
+            host.resize(n_comp);
+            if (n_comp && hipMemcpy(host.data(), d_comp, n_comp, hipMemcpyDeviceToHost) != hipSuccess) { *err = "libbsk: bgzf: the D2H copy of a compressed piece failed"; return BSK_ERR_HIP; }
+            const int r = store_append(s, part, host.data(), n_comp, false);
+            if (r != BSK_OK) *err = s->err;
+            return r;
+        });
+        if (rc != BSK_OK) return rc;
+    } else if (n) {
         Target t;
         rc = reserve_target(s, part, n, &t);
         if (rc != BSK_OK) { *err = s->err; return rc; }
@@ -294,15 +376,33 @@ int bsk_store_open(const char* path, int merge, bsk_store** out) {
     return BSK_OK;
 }
 
+int bsk_store_set_bgzf(bsk_store* s, int on) {
+    if (!s) return BSK_ERR_INVALID_ARG;
+    if (s->touched) return store_fail(s, "libbsk: bsk_store_set_bgzf comes before the first put");
+    s->bgzf = on != 0;
+    s->bgzf_eof = on != 2;
+    return BSK_OK;
+}
+
 const char* bsk_store_error(const bsk_store* s) { return s ? s->err.c_str() : ""; }
 
 int bsk_store_put_host(bsk_store* s, uint64_t part, const void* data, size_t n) {
     if (!s || (n && !data)) return BSK_ERR_INVALID_ARG;
+    s->touched = true;
+    if (s->bgzf && n) {
+        std::vector<uint8_t> comp(bgzf_deflate_bound(n, 0));
+        size_t got = 0;
+        std::string err;
+        const int rc = bgzf_deflate_host(data, n, 0, false, comp.data(), comp.size(), &got, 0, err);
+        if (rc != BSK_OK) { s->err = err; return rc; }
+        return store_append(s, part, comp.data(), got, true);
+    }
     return store_append(s, part, (const uint8_t*)data, n, true);
 }
 
 int bsk_store_put(bsk_store* s, bsk_ctx* c, uint64_t part, const bsk_out* o) {
     if (!s || !c || !o) return BSK_ERR_INVALID_ARG;
+    s->touched = true;
     if (c->device < 0) { c->set_error("libbsk: context was created without a device"); return BSK_ERR_NO_DEVICE; }
     bsk_call_scope scope(c);
     if (!scope.owns) { c->set_error(BSK_BUSY_TEXT); return BSK_ERR_INVALID_ARG; }
@@ -331,6 +431,46 @@ int bsk_store_put(bsk_store* s, bsk_ctx* c, uint64_t part, const bsk_out* o) {
     return rc;
 }
 
+int bsk_out_to_host_bgzf(bsk_ctx* c, const bsk_out* o, int eof, void* dst, size_t cap, size_t* n_comp) {
+    if (!c || !o || !n_comp || (cap && !dst)) { if (c) c->set_error("libbsk: null argument"); return BSK_ERR_INVALID_ARG; }
+    *n_comp = 0;
+    if (c->device < 0) { c->set_error("libbsk: context was created without a device"); return BSK_ERR_NO_DEVICE; }
+    bsk_call_scope scope(c);
+    if (!scope.owns) { c->set_error(BSK_BUSY_TEXT); return BSK_ERR_INVALID_ARG; }
+    HIP_TRYX(c, hipSetDevice(c->device));
+    HIP_TRYX(c, hipDeviceSynchronize());
+    const bsk_ctx::PendingOut* seg = nullptr;
+    if (o->n_segments && o->len) {
+        const bsk_ctx::PendingOut& P = c->pend_out;
+        if (P.kind == 0 || o->d_seg_src != P.seg_src || o->d_seg_off != P.seg_off || o->n_segments != P.nseg || o->len != P.total) {
+            c->set_error("libbsk: this result is not the one the context holds as slices (a later run replaced it)");
+            return BSK_ERR_INVALID_ARG;
+        }
+        const int rc = pending_first4k(c, nullptr);
+        if (rc != BSK_OK) return rc;
+        HIP_TRYX(c, hipDeviceSynchronize());
+        seg = &P;
+    }
+    std::string err;
+    size_t at = 0;
+    auto put = [&](const void* src, size_t n, bool on_device) {
+        if (n > cap - at) { err = "libbsk: bgzf: the output buffer holds " + std::to_string(cap) + " bytes, the file needs more (bsk_bgzf_deflate_bound)"; return BSK_ERR_CAPACITY; }
+        if (on_device) { if (n && hipMemcpy((uint8_t*)dst + at, src, n, hipMemcpyDeviceToHost) != hipSuccess) { err = "libbsk: bgzf: the D2H copy of a compressed piece failed"; return BSK_ERR_HIP; } }
+        else memcpy((uint8_t*)dst + at, src, n);
+        at += n;
+        return BSK_OK;
+    };
+    int rc = bgzf_pieces(c, seg ? nullptr : (const uint8_t*)o->d_data, seg, o->len, &err, [&](const void* d_comp, size_t n) { return put(d_comp, n, true); });
+    if (rc == BSK_OK && eof) {
+        uint8_t e[28];
+        bgzf_eof_block(e);
+        rc = put(e, sizeof e, false);
+    }
+    if (rc != BSK_OK) { c->set_error(err); return rc; }
+    *n_comp = at;
+    return BSK_OK;
+}
+
 int bsk_store_close(bsk_store* s, uint64_t* total_bytes) {
     if (!s) return BSK_ERR_INVALID_ARG;
     int rc = BSK_OK;
@@ -345,9 +485,14 @@ int bsk_store_close(bsk_store* s, uint64_t* total_bytes) {
                     s->total += kv.second.bytes.size();
                 }
             }
+            if (s->bgzf && s->fd >= 0 && !end_part_file(s, s->fd, s->offset)) rc = BSK_ERR_INVALID_ARG;
             if (s->fd >= 0) close(s->fd);
         } else {
-            for (auto& kv : s->parts) if (kv.second.fd >= 0) close(kv.second.fd);
+            for (auto& kv : s->parts)
+                if (kv.second.fd >= 0) {
+                    if (!end_part_file(s, kv.second.fd, kv.second.off)) rc = BSK_ERR_INVALID_ARG;
+                    close(kv.second.fd);
+                }
         }
         if (total_bytes) *total_bytes = s->total;
     }
@@ -358,6 +503,7 @@ int bsk_store_close(bsk_store* s, uint64_t* total_bytes) {
 int bsk_run_to_store(bsk_ctx* c, const void* host_shard, size_t n, int format, int64_t pid, bsk_store* s, uint64_t part,
                      uint64_t* out_bytes, uint64_t* out_records) {
     if (!c || !s) return BSK_ERR_INVALID_ARG;
+    s->touched = true;
     if (c->device < 0) { c->set_error("libbsk: context was created without a device"); return BSK_ERR_NO_DEVICE; }
     if (format != BSK_FORMAT_FASTA && format != BSK_FORMAT_FASTQ) { c->set_error("libbsk: bad format"); return BSK_ERR_INVALID_ARG; }
     if (n && !host_shard) { c->set_error("libbsk: null shard"); return BSK_ERR_INVALID_ARG; }

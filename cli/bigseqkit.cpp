@@ -351,11 +351,62 @@ void inflate_host_text(const std::string& path, std::string& text) {
     text.swap(out);
 }
 
+// ---- compressed output (PARITY.md BGZFW).  THE rule: an -o name that ends in .gz / .bgz makes every file written under it BGZF
+// ("-" and the default <input>-out do not end so: plain).  It is decided here and nowhere else; the writers below share it.
+bool name_is_bgzf(const std::string& out_name) { return has_suffix(out_name, {".gz", ".bgz"}); }
+const char* part_suffix(bool bgzf) { return bgzf ? ".gz" : ""; }
+std::string eof_block() {
+    std::string e(28, '\0');
+    size_t n = 0;
+    if (bsk_bgzf_deflate_host(nullptr, 0, 0, 1, &e[0], e.size(), &n, 1) != BSK_OK || n != e.size()) die(bsk_global_error());
+    return e;
+}
+// the result of a run joins `text`: as it is, or -- pack -- as BGZF without an EOF block, compressed on the context's device so
+// that only the compressed bytes cross to the host (a share or a piece ends on a block: the pieces and one EOF block are a file)
+void append_result(bsk_ctx* c, const bsk_out& out, std::string& text, bool pack) {
+    if (!out.len) return;
+    const size_t at = text.size();
+    if (!pack) {
+        text.resize(at + out.len);
+        if (bsk_out_to_host(c, &out, &text[at], out.len) != BSK_OK) die(bsk_last_error(c));
+        return;
+    }
+    const size_t cap = bsk_bgzf_deflate_bound(out.len, 0);
+    size_t got = 0;
+    text.resize(at + cap);
+    if (bsk_out_to_host_bgzf(c, &out, 0, &text[at], cap, &got) != BSK_OK) die(bsk_last_error(c));
+    text.resize(at + got);
+}
+// host text as BGZF without an EOF block, on host threads (the bytes the device writes): the rare paths that hold the text on
+// the host -- part files cut at record starts, the commands that join their inputs there
+std::string deflate_host_text(const char* p, size_t n) {
+    std::string comp(bsk_bgzf_deflate_bound(n, 0), '\0');
+    size_t got = 0;
+    if (bsk_bgzf_deflate_host(p, n, 0, 0, &comp[0], comp.size(), &got, 0) != BSK_OK) die(bsk_global_error());
+    comp.resize(got);
+    return comp;
+}
+// one file of the output: [p, p + n) is text, or -- packed -- BGZF already; a BGZF file ends with the EOF block
+void write_out_file(const std::string& path, bool bgzf, bool packed, const char* p, size_t n) {
+    std::ofstream f(path, std::ios::binary);
+    if (!f) die("cannot create " + path);
+    if (bgzf && !packed) {
+        const std::string comp = deflate_host_text(p, n);
+        f.write(comp.data(), (std::streamsize)comp.size());
+    } else {
+        f.write(p, (std::streamsize)n);
+    }
+    if (bgzf) f.write(eof_block().data(), 28);
+    f.close();  // (die() ends the process without destructors: nothing may still sit in a stream buffer by then)
+    if (!f) die("write " + path + " failed");
+}
+
 void usage() {
     std::cout << "bigseqkit -- MI355X-native seqkit-compatible commands (libbsk)\n\nUsage:\n  bigseqkit <command> [flags] files...\n\nCommands:\n";
     for (auto& c : kCommands) std::cout << "  " << c.use << "\n";
     std::cout << "\nGlobal flags: -t/--seq-type -w/--line-width --id-regexp --id-ncbi -o/--out-file --quiet\n"
-                 "  --alphabet-guess-seq-length --infile-list --merge --partitions --order --device --dry-run\n";
+                 "  --alphabet-guess-seq-length --infile-list --merge --partitions --order --device --dry-run\n"
+                 "An -o name that ends in .gz or .bgz is written as BGZF (what bgzip writes), compressed on the GPU; any other name is plain text.\n";
 }
 
 // one parsed command line: `args[0]` is the command, the rest flags and input files
@@ -558,7 +609,16 @@ struct Output {
     bool is_text = false;     // `text` is the result (not record text)
     int fmt = -1;             // format of the record text in `text` (-1: line oriented)
     bool stored = false;      // the result has been written already, share by share (run_buckets, concat): store() is not called
+    bool packed = false;      // `text` is BGZF without its EOF block (append_result with pack): store() writes it as it comes
 };
+
+bool g_pipe_job = false;  // the jobs of a `pipe` run: their results stay text, `pipe` itself stores (and compresses) the last one
+bool out_is_bgzf(const Invocation& inv) { return name_is_bgzf(inv.pget("out-file")); }
+// the result goes to ONE compressed file: it can leave the device compressed.  (Several part files are cut from the host text at
+// record starts, as ever, and each is compressed on host threads: rare.)
+bool packs_on_device(const Invocation& inv) {
+    return !g_pipe_job && out_is_bgzf(inv) && (inv.pget("merge") == "true" || strtol(inv.pget("partitions").c_str(), nullptr, 10) <= 1);
+}
 
 bool g_faidx_query = false;  // `faidx` with regions: records out, not index rows
 
@@ -732,9 +792,9 @@ Output execute(const Invocation& inv, std::vector<Part>& inputs, bool keep_on_de
             continue;
         }
         res.fmt = rows_out ? -1 : ofmt;
-        const size_t at = res.text.size();
-        res.text.resize(at + out.len);
-        if (bsk_out_to_host(c, &out, res.text.data() + at, out.len) != BSK_OK) die(bsk_last_error(c));
+        // (in a `pipe` job only what is stored is compressed: what one job hands to the next stays text on the device)
+        res.packed = !keep_on_device && packs_on_device(inv);
+        append_result(c, out, res.text, res.packed);
     }
     if (ctx) bsk_destroy(ctx);
     if (grep_count) { res.is_text = true; res.text = std::to_string(grep_total); }  // fmt.Print: no newline (cli/grep.go:14)
@@ -950,18 +1010,19 @@ void store(const Invocation& inv, const Output& out, const std::vector<std::stri
     if (outp.empty()) outp = files.size() == 1 ? files[0] + "-out" : (getenv("IGNIS_JOB_NAME") ? std::string(getenv("IGNIS_JOB_NAME")) + "-out" : std::string());
     if (outp.empty()) die("out file -o required");
     if (outp == "-") { fwrite(out_text.data(), 1, out_text.size(), stdout); return; }
+    const bool bgzf = name_is_bgzf(outp);
     if (inv.pget("merge") == "true") {  // StoreFASTX: one file
-        std::ofstream f(outp, std::ios::binary);
-        if (!f) die("cannot create " + outp);
-        f.write(out_text.data(), (std::streamsize)out_text.size());
-        f.close();  // (die() ends the process without destructors: nothing may still sit in a stream buffer by then)
-        if (!f) die("write " + outp + " failed");
+        write_out_file(outp, bgzf, out.packed, out_text.data(), out_text.size());
         return;
     }
     // StoreFASTXN == SaveAsTextFile: a directory of part files; a record is never split between two parts
     long parts = strtol(inv.pget("partitions").c_str(), nullptr, 10);
     if (parts < 1) parts = 1;
     if (!is_dir(outp) && mkdir(outp.c_str(), 0755) != 0) die("cannot create directory " + outp);
+    if (out.packed) {  // (packs_on_device: one part, compressed already)
+        write_out_file(outp + "/part00000.gz", true, true, out_text.data(), out_text.size());
+        return;
+    }
     size_t pos = 0;
     for (long p = 0; p < parts; ++p) {
         size_t end = p + 1 == parts ? out_text.size() : out_text.size() * (size_t)(p + 1) / (size_t)parts;
@@ -976,11 +1037,8 @@ void store(const Invocation& inv, const Output& out, const std::vector<std::stri
             }
         }
         char nm[64];
-        snprintf(nm, sizeof nm, "/part%05ld", p);
-        std::ofstream f(outp + nm, std::ios::binary);
-        f.write(out_text.data() + pos, (std::streamsize)(end - pos));
-        f.close();
-        if (!f) die("write " + outp + nm + " failed");
+        snprintf(nm, sizeof nm, "/part%05ld%s", p, part_suffix(bgzf));
+        write_out_file(outp + nm, bgzf, false, out_text.data() + pos, end - pos);
         pos = end;
     }
 }
@@ -1148,6 +1206,7 @@ Output run_head_genome(const Invocation& inv) {
     bsk_ctx* ctx = nullptr;
     if (bsk_create(inv.cmd->op, inv.js.c_str(), device, &ctx) != BSK_OK) die(bsk_global_error());
     bsk_ctx_set(ctx, "out", "slices");
+    res.packed = packs_on_device(inv);
     const char* pinned = getenv("BSK_STREAM_PIECE_BYTES");
     for (auto& path : inv.files) {
         if (bsk_head_genome_reset(ctx) != BSK_OK) die(bsk_last_error(ctx));
@@ -1170,9 +1229,7 @@ Output run_head_genome(const Invocation& inv) {
             const size_t hi = piece_end(f, lo, piece, fmt);
             bsk_out out;
             if (bsk_head_genome_run(ctx, f.text + lo, hi - lo, 0, fmt, k++, nullptr, &out) != BSK_OK) die(bsk_last_error(ctx));
-            const size_t at = res.text.size();
-            res.text.resize(at + out.len);
-            if (out.len && bsk_out_to_host(ctx, &out, &res.text[at], out.len) != BSK_OK) die(bsk_last_error(ctx));
+            append_result(ctx, out, res.text, res.packed);
             int cut = 0;
             bsk_head_genome_state(ctx, &cut, nullptr);
             if (cut) break;  // the rest of the file is never read
@@ -1300,11 +1357,7 @@ struct BucketRun {
         int64_t k = 0;
         for (auto& pc : pieces) ok(cmd.bucket_add(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr));
     }
-    void append_out(const bsk_out& out) {
-        const size_t at = res.text.size();
-        res.text.resize(at + out.len);
-        if (out.len) ok(bsk_out_to_host(ctx, &out, &res.text[at], out.len));
-    }
+    void append_out(const bsk_out& out) { append_result(ctx, out, res.text, res.packed); }
     // shuffle, sort: every finished bucket is appended to the output; backwards (sort -r): from the last to the first
     void print_buckets(bool backwards) {
         for (int i = 0; i < n_buckets; ++i) {
@@ -1419,12 +1472,13 @@ void BucketRun::concat_tail(const Invocation& inv) {
         if (!outf) die("cannot create " + outp);
     }
     res.stored = to_file || to_stdout;
+    const bool pack = to_file && name_is_bgzf(outp);
     std::string share;
     auto write_share = [&](const bsk_out& out) {
         if (!res.stored) return append_out(out);
         if (!out.len) return;
-        share.resize(out.len);
-        ok(bsk_out_to_host(ctx, &out, &share[0], out.len));
+        share.clear();
+        append_result(ctx, out, share, pack);
         if (to_stdout) fwrite(share.data(), 1, share.size(), stdout);
         else outf.write(share.data(), (std::streamsize)share.size());
         if (to_file && !outf) die("write " + outp + " failed");
@@ -1469,6 +1523,7 @@ void BucketRun::concat_tail(const Invocation& inv) {
         mark("concat: tail");
     }
     if (to_file) {
+        if (pack) outf.write(eof_block().data(), 28);
         outf.close();
         if (!outf) die("write " + outp + " failed");
     }
@@ -1487,6 +1542,7 @@ Output run_buckets(const Invocation& inv) {
     refuse_compressed(inv.files, "the buckets of '" + use + "' read", "decompress it first (bgzip -d), or unset the budget if the file and its text fit one GPU");
     const int device = (int)strtol(inv.pget("device").c_str(), nullptr, 10);
     BucketRun R{*bucket_cmd(use)};
+    R.res.packed = !pair && packs_on_device(inv);  // (pair -O writes its four files under fixed names: plain)
     R.budget = bucket_budget(use);
     if (bsk_create(inv.cmd->op, inv.js.c_str(), device, &R.ctx) != BSK_OK) die(bsk_global_error());
     const bool timing = getenv("BSK_CLI_TIMING") != nullptr;
@@ -1561,6 +1617,7 @@ int run_devices(const Invocation& inv) {
     std::string out_file = inv.pget("out-file");
     if (out_file.empty()) out_file = path + "-out";
     const bool merge = inv.pget("merge") == "true", to_stdout = out_file == "-";
+    const bool bgzf = name_is_bgzf(out_file);  // (every store below writes BGZF then: bsk_store_set_bgzf)
     const bool grep_count = use == "grep" && inv.pget("count") == "true";
     const bool records = !(use == "stats" || grep_count);
     bsk_store* dir_store = nullptr;
@@ -1571,10 +1628,11 @@ int run_devices(const Invocation& inv) {
         // (part files of an earlier run with MORE workers would be read as part of this result: ADVICE r04)
         for (int k = world; k < world + 4096; ++k) {
             char nm[64];
-            snprintf(nm, sizeof nm, "/part%05d", k);
+            snprintf(nm, sizeof nm, "/part%05d%s", k, part_suffix(bgzf));
             if (unlink((out_file + nm).c_str()) != 0) break;
         }
         if (bsk_store_open(out_file.c_str(), 0, &dir_store) != BSK_OK) die("cannot open the directory " + out_file);
+        bsk_store_set_bgzf(dir_store, bgzf);
     }
     std::vector<Worker> W((size_t)world);
     std::atomic<int> failed{0};
@@ -1726,6 +1784,7 @@ int run_devices(const Invocation& inv) {
                 else {
                     close(tfd);
                     if (bsk_store_open(me.spool.c_str(), 1, &own) != BSK_OK) give_up("cannot create " + me.spool);
+                    else bsk_store_set_bgzf(own, bgzf ? 2 : 0);  // (a spool is a piece: no EOF block, the parent appends the one)
                     st = own;
                     part = 0;
                 }
@@ -1749,8 +1808,9 @@ int run_devices(const Invocation& inv) {
                 uint64_t p0 = 0;
                 if (!mine) {
                     char nm[64];
-                    snprintf(nm, sizeof nm, "/part%05d", rank);
+                    snprintf(nm, sizeof nm, "/part%05d%s", rank, part_suffix(bgzf));
                     if (bsk_store_open((out_file + nm).c_str(), 1, &mine) != BSK_OK) give_up("cannot create " + out_file + nm);
+                    else bsk_store_set_bgzf(mine, bgzf);
                 }
                 const size_t piece = std::max<size_t>(1 << 16, getenv("BSK_STREAM_PIECE_BYTES") ? (size_t)strtoull(getenv("BSK_STREAM_PIECE_BYTES"), nullptr, 10) : ((size_t)2 << 30));
                 const uint8_t* fmap = (const uint8_t*)mmap(nullptr, size, PROT_READ, MAP_SHARED, fd, 0);
@@ -1834,9 +1894,10 @@ int run_devices(const Invocation& inv) {
         for (int r = 0; r < world; ++r)  // (an empty part file still marks the partition, as SaveAsTextFile does)
             if (W[(size_t)r].out_bytes == 0) {
                 char nm[64];
-                snprintf(nm, sizeof nm, "/part%05d", r);
+                snprintf(nm, sizeof nm, "/part%05d%s", r, part_suffix(bgzf));
                 // (O_TRUNC: a non-empty part of an earlier run into the same directory must not pass for this run's -- ADVICE r05)
                 const int e = open((out_file + nm).c_str(), O_CREAT | O_TRUNC | O_WRONLY, 0644);
+                if (e >= 0 && bgzf && write(e, eof_block().data(), 28) != 28) die("write " + out_file + nm + " failed");
                 if (e >= 0) close(e);
             }
         return 0;
@@ -1859,6 +1920,7 @@ int run_devices(const Invocation& inv) {
         }
         close(src);
     }
+    if (okw && bgzf && write(dst, eof_block().data(), 28) != 28) okw = false;  // (the spools are BGZF without it: the ONE EOF block)
     if (!to_stdout && close(dst) != 0) okw = false;
     drop_spools();
     if (!okw) die("write " + out_file + " failed");
@@ -1886,7 +1948,9 @@ static int run_main(int argc, char** argv) {
             const std::string text = read_file(job);
             j = bsk::json::Parser(text).parse();
         } catch (const std::exception&) { die("incorrect job format"); }
+        g_pipe_job = true;
         Output o = run_job(*j, true);
+        g_pipe_job = false;
         // the files given to `pipe` itself are appended unchanged (pipe.go:61-66)
         for (auto& p : read_parts(inv.files)) o.text += p.host;
         store(inv, o, inv.files);
@@ -1971,8 +2035,8 @@ static int run_main(int argc, char** argv) {
         if (crc != BSK_OK) die(bsk_last_error(c));
         Output o;
         o.fmt = inputs[0].fmt;
-        o.text.resize(out.len);
-        if (out.len && bsk_out_to_host(c, &out, &o.text[0], out.len) != BSK_OK) die(bsk_last_error(c));
+        o.packed = packs_on_device(inv);
+        append_result(c, out, o.text, o.packed);
         bsk_destroy(c);
         store(inv, o, inv.files);
         return 0;
@@ -1996,8 +2060,8 @@ static int run_main(int argc, char** argv) {
             die(bsk_last_error(c));
         Output o;
         o.fmt = inputs[0].fmt;
-        o.text.resize(out.len);
-        if (out.len && bsk_out_to_host(c, &out, &o.text[0], out.len) != BSK_OK) die(bsk_last_error(c));
+        o.packed = packs_on_device(inv);
+        append_result(c, out, o.text, o.packed);
         bsk_destroy(c);
         store(inv, o, inv.files);
         return 0;

@@ -189,6 +189,24 @@ int bsk_bgzf_inflate_host(const void* comp, size_t n_comp, void* out, size_t cap
 /* CRC32 of data[0, n), n <= 65536, taken as the kernel takes it: chunks of 1 KiB measured from the end, folded with the
  * "advance by 1 KiB" operator.  For the tests, which compare it with zlib's. */
 uint32_t bsk_selftest_bgzf_crc(const void* data, size_t n);
+/* ---- BGZF output (PARITY.md BGZFW; ops_bgzf_write.hip, bgzf_deflate_dev.hpp) ----
+ * A text becomes the BGZF file that holds it: blocks of `block_text_bytes` of text (0: 65 280, bgzip's size; at most
+ * 65 280), each encoded by one wavefront -- LZ77 matches inside the block, dynamic Huffman codes per block, and per block the
+ * cheapest of dynamic, fixed and stored, so that no member is longer than its text + 31 bytes.  zlib judges the bytes:
+ * gzip.decompress of the file is the text.  The host encoder and the device encoder write THE SAME bytes.  Errors:
+ * bsk_global_error().
+ *   bsk_bgzf_deflate_bound   the most bytes n_text bytes can become, the EOF block included
+ *   bsk_bgzf_deflate_device  d_text[0, n_text) in the memory of `device` -> a NEW buffer *d_comp of *n_comp bytes
+ *                            (bsk_device_free; a text beyond one round -- four blocks per resident wave, 256 MiB on an MI355X --
+ *                            gets a buffer of the bound, of which *n_comp bytes are the file).  The workspace is sized by the
+ *                            resident waves, not by the text.  eof != 0: the 28-byte EOF block follows.  An empty text gives the EOF block
+ *                            alone, or nothing.  The outputs of several calls with eof = 0 and one EOF block, concatenated,
+ *                            are one valid file: this is how a text is written in pieces
+ *   bsk_bgzf_deflate_host    the same encoder on `threads` host threads (<= 0: 8), the same bytes.  *n_out is what the file
+ *                            needs, also when `cap` is too small (BSK_ERR_CAPACITY) */
+size_t bsk_bgzf_deflate_bound(size_t n_text, uint32_t block_text_bytes);
+int bsk_bgzf_deflate_device(const void* d_text, size_t n_text, int device, uint32_t block_text_bytes, int eof, void** d_comp, size_t* n_comp);
+int bsk_bgzf_deflate_host(const void* text, size_t n, uint32_t block_text_bytes, int eof, void* out, size_t cap, size_t* n_out, int threads);
 int bsk_stats_reset(bsk_ctx* ctx, void* stream); /* zero the ctx-owned vector, error flags and overflow list */
 /* The context's list of sequence lengths >= hist_cap (the part of the reference's map[int64]int64,
  * bigseqkit-lib/stats.go:86, that does not fit the dense vector).  _get copies it to the host (cap 0 + NULL: size
@@ -255,6 +273,11 @@ typedef struct {
 } bsk_out;
 /* copy an operator result to host memory (synchronises) */
 int bsk_out_to_host(bsk_ctx* ctx, const bsk_out* out, void* dst, size_t cap);
+/* The same result as BGZF: compressed on the context's device, so only the compressed bytes cross to the host.  The text is
+ * taken in pieces of 64 MiB (whole blocks: a piece boundary is a block boundary), gathered piece by piece where the result
+ * is a list of slices.  eof != 0: the EOF block ends the file.  cap: bsk_bgzf_deflate_bound(out->len, 0) always suffices
+ * (BSK_ERR_CAPACITY otherwise).  *n_comp: the bytes written to dst. */
+int bsk_out_to_host_bgzf(bsk_ctx* ctx, const bsk_out* out, int eof, void* dst, size_t cap, size_t* n_comp);
 /* a result that is still a list of slices becomes ONE block in the context's output buffer (today's second move of the
  * text: k_seg_copy / k_names_compact); out->d_data is set, the slice fields are cleared.  No-op on a contiguous result. */
 int bsk_out_materialize(bsk_ctx* ctx, bsk_out* out, void* stream);
@@ -889,6 +912,13 @@ const char* bsk_store_error(const bsk_store* s);
 /* the output of an operator call (device memory of `ctx`), copied to the host in 64 MiB pieces through two pinned
  * buffers -- the copy of a piece runs while the piece before it is written */
 int bsk_store_put(bsk_store* s, bsk_ctx* ctx, uint64_t part, const bsk_out* out);
+/* on != 0, before the first put: what is put stays text, what is written is BGZF.  bsk_store_put compresses every piece
+ * of the drain on the device in front of its D2H copy, bsk_store_put_host on host threads; parts are appended in order as
+ * before (one that arrives early waits compressed).  bsk_store_close ends the single file with ONE EOF block; in directory
+ * mode the files are named part%05d.gz and each ends with its own.  on == 0: nothing changes, names included.
+ * on == 2: BGZF as with 1, but no file gets an EOF block -- the file is a piece of a larger one, whose writer appends the one
+ * EOF block behind the last piece (the spools of the command line's --devices --merge). */
+int bsk_store_set_bgzf(bsk_store* s, int on);
 int bsk_store_put_host(bsk_store* s, uint64_t part, const void* data, size_t n);
 int bsk_store_close(bsk_store* s, uint64_t* total_bytes); /* also frees s */
 /* Call(partition) + FileStore for a partition in HOST memory (best: pinned, bsk_host_alloc): record-aligned chunks of
