@@ -144,6 +144,82 @@ def BgzfBlocks(data, device=0):
     return [(int(coff[i]), int(csize[i]), int(usize[i])) for i in range(k)]
 
 
+class BgzfReader:
+    """the text of a BGZF file in record-aligned pieces (bsk_bgzf_reader_*): the file is never held whole, compressed or
+    inflated.  Iterating gives (piece, voff_lo, voff_hi): the piece a CUDA uint8 tensor that VIEWS the reader's buffer --
+    valid until the second piece after it, clone it to keep it -- or, with device=-1, bytes from the same reader on the
+    host.  The offsets are BGZF virtual offsets; .piece(lo, hi) gives the bytes of a piece again on a later pass.
+    0 for a size: 1 GiB of text, 1 MiB of lookahead, 256 MiB of compressed bytes.
+
+        with BgzfReader("reads.fq.gz", FORMAT_FASTQ) as r:
+            where = [(lo, hi) for _, lo, hi in r]
+            again = r.piece(*where[0])
+    """
+
+    def __init__(self, path, fmt, device=0, piece_text_bytes=0, lookahead_bytes=0, comp_chunk_bytes=0):
+        self.device = device
+        self._f = open(os.fspath(path), "rb")
+        self._r = C.c_void_p()
+        self._done = False
+        try:
+            check(lib.bsk_bgzf_reader_open(self._f.fileno(), device, fmt, piece_text_bytes, lookahead_bytes, comp_chunk_bytes, C.byref(self._r)))
+        except Exception:
+            self._f.close()
+            raise
+
+    def close(self):
+        if self._r:
+            lib.bsk_bgzf_reader_close(self._r)
+            self._r = C.c_void_p()
+        self._f.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def _wrap(self, ptr, n):
+        if self.device < 0:
+            return C.string_at(ptr, n) if n else b""
+        return _view(ptr.value, n, self.device)
+
+    def seek(self, voff):
+        check(lib.bsk_bgzf_reader_seek(self._r, voff))
+        self._done = False
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        if self._done:
+            raise StopIteration
+        ptr, n, lo, hi, last = C.c_void_p(), C.c_size_t(), C.c_uint64(), C.c_uint64(), C.c_int()
+        check(lib.bsk_bgzf_reader_next(self._r, C.byref(ptr), C.byref(n), C.byref(lo), C.byref(hi), C.byref(last)))
+        self._done = bool(last.value)
+        return self._wrap(ptr, n.value), lo.value, hi.value
+
+    def piece(self, voff_lo, voff_hi):
+        ptr, n = C.c_void_p(), C.c_size_t()
+        check(lib.bsk_bgzf_reader_piece(self._r, voff_lo, voff_hi, C.byref(ptr), C.byref(n)))
+        return self._wrap(ptr, n.value)
+
+
+class _Foreign:
+    """n bytes of device memory that the library owns, for torch to look at (__cuda_array_interface__)"""
+
+    def __init__(self, ptr, n):
+        self.__cuda_array_interface__ = {"shape": (n,), "typestr": "|u1", "data": (ptr, False), "version": 2, "strides": None}
+
+
+def _view(ptr, n, device):
+    import torch
+    if n == 0:
+        return torch.empty(0, dtype=torch.uint8, device="cuda:%d" % device)
+    return torch.as_tensor(_Foreign(ptr, n), device="cuda:%d" % device)
+
+
 # ---- BGZF output (include/bsk.h "BGZF output"; PARITY.md BGZFW)
 def BgzfDeflateHost(data, block_bytes=0, eof=True, threads=0):
     """the BGZF file that holds `data` (bytes), encoded on host threads: the bytes BgzfDeflate gives"""

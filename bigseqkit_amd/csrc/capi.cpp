@@ -17,6 +17,7 @@
 #include "../../include/bsk.h"
 #include "anchor.hpp"
 #include "ctx.hpp"
+#include "bgzf_stream.hpp"
 #include "ops_bgzf.hpp"
 #include "ops_bgzf_write.hpp"
 #include "ops_host.hpp"
@@ -743,6 +744,52 @@ int bsk_bgzf_inflate_host(const void* comp, size_t n_comp, void* out, size_t cap
     if (!n_out || (!comp && n_comp)) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bgzf: null argument");
     std::string err;
     const int rc = bgzf_inflate_host(comp, n_comp, out, cap, n_out, threads, err);
+    return rc == BSK_OK ? rc : fail_global(rc, err);
+}
+
+// ---- the piece reader of a BGZF file (bgzf_stream.hpp, ops_bgzf_stream.hip): thin shells again
+struct bsk_bgzf_reader { BgzfPieceReader* r; };
+
+int bsk_bgzf_reader_open(int fd, int device, int format, size_t piece_text_bytes, size_t lookahead_bytes, size_t comp_chunk_bytes,
+                         bsk_bgzf_reader** out) {
+    if (!out || (format != BSK_FORMAT_FASTA && format != BSK_FORMAT_FASTQ)) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bgzf: bad arguments");
+    *out = nullptr;
+    int rc = BSK_OK;
+    std::string err;
+    BgzfPieceReader* r = bgzf_reader_open(fd, device, format, piece_text_bytes, lookahead_bytes, comp_chunk_bytes, &rc, err);
+    if (!r) return fail_global(rc, err);
+    *out = new bsk_bgzf_reader{r};
+    return BSK_OK;
+}
+
+int bsk_bgzf_reader_next(bsk_bgzf_reader* r, const void** ptr, size_t* n, uint64_t* voff_lo, uint64_t* voff_hi, int* last) {
+    if (!r || !ptr || !n || !voff_lo || !voff_hi || !last) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bgzf: null argument");
+    const int rc = r->r->next(ptr, n, voff_lo, voff_hi, last);
+    return rc == BSK_OK ? rc : fail_global(rc, r->r->error());
+}
+
+int bsk_bgzf_reader_seek(bsk_bgzf_reader* r, uint64_t voff) {
+    if (!r) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bgzf: null argument");
+    const int rc = r->r->seek(voff);
+    return rc == BSK_OK ? rc : fail_global(rc, r->r->error());
+}
+
+int bsk_bgzf_reader_piece(bsk_bgzf_reader* r, uint64_t voff_lo, uint64_t voff_hi, const void** ptr, size_t* n) {
+    if (!r || !ptr || !n) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bgzf: null argument");
+    const int rc = r->r->piece(voff_lo, voff_hi, ptr, n);
+    return rc == BSK_OK ? rc : fail_global(rc, r->r->error());
+}
+
+void bsk_bgzf_reader_close(bsk_bgzf_reader* r) {
+    if (!r) return;
+    delete r->r;
+    delete r;
+}
+
+int bsk_selftest_bgzf_stream_cut(const void* text, size_t n, size_t from, int format, int device, uint64_t* cut) {
+    if (!cut || (!text && n)) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bgzf: null argument");
+    std::string err;
+    const int rc = bgzf_stream_cut_run((const uint8_t*)text, n, from, format, device, cut, err);
     return rc == BSK_OK ? rc : fail_global(rc, err);
 }
 
@@ -2109,7 +2156,7 @@ int bsk_profile_dump(bsk_ctx* c, char* buf, size_t cap) {
         out += kv.first;
         out += num;
     }
-    out += bgzf_profile_text();  // bgzf_find, bgzf_sizes, bgzf_inflate
+    out += bgzf_profile_text();  // bgzf_find, bgzf_sizes, bgzf_inflate, bgzf_stream_cut
     out += bgzf_write_profile_text();  // bgzf_deflate, bgzf_pack
     if (c->translate_stream_fallbacks) {  // (not a stage: how often the one-pass translate did not fit and the tables ran instead)
         char num[96];

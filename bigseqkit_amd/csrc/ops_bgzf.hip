@@ -137,10 +137,7 @@ __device__ __forceinline__ uint64_t uni64(uint64_t v) {
 }
 
 // what k_bgzf_inflate needs of a block, in one place (k_bgzf_sizes and the scan fill usize, crc and ooff)
-struct BlockDesc {
-    uint64_t coff, ooff;
-    uint32_t csize, xlen, usize, crc;
-};
+using BlockDesc = BgzfBlockDesc;
 
 // one block of 64 lanes per BGZF block: nothing of the launch stays live while the block is decoded but its own description
 __global__ __launch_bounds__(64) void k_bgzf_inflate(const uint8_t* __restrict__ comp, uint64_t n, const BlockDesc* __restrict__ desc,
@@ -274,6 +271,23 @@ std::string bgzf_profile_text() {
         out += kv.first + num;
     }
     return out;
+}
+
+bool bgzf_profile_on() { std::lock_guard<std::mutex> g(g_prof_mu); return g_prof_on; }
+void bgzf_profile_add(const char* stage, double ms) {
+    std::lock_guard<std::mutex> g(g_prof_mu);
+    g_prof[stage].ms += ms;
+    g_prof[stage].launches += 1;
+}
+
+void bgzf_crc_matrix(uint32_t mat[32]) { bgzf::crc_advance_matrix(mat, WaveLane::CRC_CHUNK); }
+
+int bgzf_launch_inflate(const void* d_comp, uint64_t n, const BgzfBlockDesc* d_desc, uint64_t nb, void* d_text, const uint32_t* d_mat,
+                        unsigned long long* d_status, void* stream) {
+    if (nb == 0) return (int)hipSuccess;
+    hipLaunchKernelGGL(k_bgzf_inflate, dim3((unsigned)nb), dim3(64), 0, (hipStream_t)stream, (const uint8_t*)d_comp, n, d_desc, (uint8_t*)d_text,
+                       d_mat, d_status);
+    return (int)hipGetLastError();
 }
 
 int bgzf_probe(const void* head, size_t n) {

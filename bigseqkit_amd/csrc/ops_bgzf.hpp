@@ -25,9 +25,26 @@ int bgzf_probe(const void* head, size_t n);
 // advance operator (the tests compare it with zlib's)
 uint32_t bgzf_crc_chunked(const uint8_t* data, uint32_t n, uint32_t chunk);
 
-// stages for bsk_profile_dump: "bgzf_find", "bgzf_sizes", "bgzf_inflate" (process-wide: these calls have no context)
+// what k_bgzf_inflate needs of a block: where it lies in the compressed buffer, where its text goes, and what the trailer says
+struct BgzfBlockDesc {
+    uint64_t coff, ooff;
+    uint32_t csize, xlen, usize, crc;
+};
+// The streaming reader (bgzf_stream.hpp, ops_bgzf_stream.hip) launches the same kernel on a chunk of a file: the blocks
+// d_desc[0, nb) of d_comp[0, n) (a multiple of 8) are written into place at d_text + ooff, d_text a multiple of 16 -- the
+// kernel's aligned 16-byte stores follow the address, whatever ooff is.  d_mat: bgzf_crc_matrix in device memory; *d_status:
+// ~0 before the launch, afterwards the least index << 8 | code of a block that was refused.  `stream` is a hipStream_t;
+// returns a hipError_t.
+int bgzf_launch_inflate(const void* d_comp, uint64_t n, const BgzfBlockDesc* d_desc, uint64_t nb, void* d_text, const uint32_t* d_mat,
+                        unsigned long long* d_status, void* stream);
+void bgzf_crc_matrix(uint32_t mat[32]);
+
+// stages for bsk_profile_dump: "bgzf_find", "bgzf_sizes", "bgzf_inflate", and of the reader "bgzf_stream_cut" (process-wide:
+// these calls have no context)
 void bgzf_profile_enable(bool on);
 void bgzf_profile_reset();
 std::string bgzf_profile_text();  // "name=ms/launches;" per stage that ran
+bool bgzf_profile_on();
+void bgzf_profile_add(const char* stage, double ms);  // (the reader times its launches on its own stream)
 
 }  // namespace bsk

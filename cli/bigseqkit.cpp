@@ -340,6 +340,54 @@ void refuse_compressed(const std::vector<std::string>& files, const std::string&
 }
 
 // `text` as read from a file or a pipe: inflated in place when it is BGZF (host threads, the decoder of the device)
+// The first byte of a BGZF file's text (0: it has none): the blocks are walked by their BSIZE, and the first one that holds text is
+// inflated on the host -- what sniff_format asks of a file that is not read whole
+char bgzf_first_text_byte(const std::string& path) {
+    const int fd = open(path.c_str(), O_RDONLY);
+    if (fd < 0) die("open " + path + ": no such file or directory");
+    std::string blk((size_t)12 + 65535 + 65536, '\0');
+    char first = 0;
+    for (off_t off = 0;;) {
+        const ssize_t got = pread(fd, &blk[0], blk.size(), off);
+        if (got < 18) break;
+        const uint8_t* b = (const uint8_t*)blk.data();
+        const size_t xlen = b[10] | (size_t)b[11] << 8;
+        size_t bsize = 0;
+        for (size_t at = 12; at + 4 <= 12 + xlen && at + 6 <= (size_t)got;) {
+            const size_t slen = b[at + 2] | (size_t)b[at + 3] << 8;
+            if (b[at] == 'B' && b[at + 1] == 'C' && slen == 2) { bsize = (b[at + 4] | (size_t)b[at + 5] << 8) + 1; break; }
+            at += 4 + slen;
+        }
+        if (bsize == 0 || bsize > (size_t)got) break;  // (not a whole block: the reader will say what is wrong with the file)
+        size_t n = 0;
+        if (bsk_bgzf_inflate_host(b, bsize, nullptr, 0, &n, 1) != BSK_OK) break;
+        if (n) {
+            std::string text(n, '\0');
+            if (bsk_bgzf_inflate_host(b, bsize, &text[0], n, &n, 1) == BSK_OK) first = text[0];
+            break;
+        }
+        off += (off_t)bsize;
+    }
+    close(fd);
+    return first;
+}
+
+// The paths for inputs that are not loaded whole read a BGZF file in pieces (bsk_bgzf_reader_*) only when asked to:
+// BSK_BGZF_STREAM=1.  Every pass over the input inflates the file again -- a bucket command reads it 2 + B times and more --, which
+// a user should choose knowingly; without the switch these paths refuse a compressed file as before, and the message names it
+bool bgzf_stream_on() {
+    const char* e = getenv("BSK_BGZF_STREAM");
+    return e && *e && strcmp(e, "0") != 0;
+}
+const char* const kStreamHint = ", or set BSK_BGZF_STREAM=1 to read it in record-aligned pieces, inflated once per pass";
+
+// the sizes of the BGZF piece reader (bsk_bgzf_reader_open; 0: its defaults).  The tests pin them
+struct BgzfSizes { size_t piece, look, chunk; };
+BgzfSizes bgzf_sizes() {
+    auto env = [](const char* name) { const char* e = getenv(name); return e ? (size_t)strtoull(e, nullptr, 10) : (size_t)0; };
+    return {env("BSK_STREAM_PIECE_BYTES"), env("BSK_BGZF_LOOKAHEAD_BYTES"), env("BSK_BGZF_CHUNK_BYTES")};
+}
+
 void inflate_host_text(const std::string& path, std::string& text) {
     const int kind = bsk_bgzf_probe(text.data(), text.size());
     if (kind == 2) die(path + kPlainGzip);
@@ -588,6 +636,9 @@ struct Part {
     // host-shard path (bsk_stats_run with on_device = 0: record-aligned 256 MiB chunks, H2D of chunk i + 1 under the kernels of i)
     const void* map = nullptr;
     size_t map_n = 0;
+    // ... and a BGZF file of that size: the open file, which `stats` reads through the piece reader (bsk_bgzf_reader_*: the text
+    // arrives in record-aligned pieces on the device, the file is never held whole)
+    int bgzf_fd = -1;
     const void* ptr() const { return dptr ? dptr : (map ? map : (const void*)host.data()); }
     size_t size() const { return dptr ? n : (map ? map_n : host.size()); }
     int on_device() const { return dptr ? 1 : 0; }
@@ -598,7 +649,8 @@ void release(std::vector<Part>& parts) {
         if (p.owner) bsk_destroy(p.owner);
         else if (p.owned_alloc && p.dptr) bsk_device_free(p.dptr);
         if (p.map) munmap(const_cast<void*>(p.map), p.map_n);
-        p.owner = nullptr; p.dptr = nullptr; p.map = nullptr;
+        if (p.bgzf_fd >= 0) close(p.bgzf_fd);
+        p.owner = nullptr; p.dptr = nullptr; p.map = nullptr; p.bgzf_fd = -1;
     }
     parts.clear();
 }
@@ -693,7 +745,20 @@ Output execute(const Invocation& inv, std::vector<Part>& inputs, bool keep_on_de
             const Part& in = inputs[fi];
             bsk_ctx* sc = nullptr;  // one Stats per input (cli/stats.go:16-21)
             if (bsk_create("Stats", js.c_str(), device, &sc) != BSK_OK) die(bsk_global_error());
-            if (bsk_stats_run(sc, in.ptr(), in.size(), in.on_device(), in.fmt, 0, nullptr, nullptr) != BSK_OK) die(bsk_last_error(sc));
+            if (in.bgzf_fd >= 0) {  // every piece of the reader is a device shard of its own, the pids ascending
+                const BgzfSizes z = bgzf_sizes();
+                bsk_bgzf_reader* rd = nullptr;
+                if (bsk_bgzf_reader_open(in.bgzf_fd, device, in.fmt, z.piece, z.look, z.chunk, &rd) != BSK_OK) die(bsk_global_error());
+                int last = 0;
+                for (int64_t pid = 0; !last; ++pid) {
+                    const void* p = nullptr;
+                    size_t n = 0;
+                    uint64_t lo = 0, hi = 0;
+                    if (bsk_bgzf_reader_next(rd, &p, &n, &lo, &hi, &last) != BSK_OK) die(bsk_global_error());
+                    if (n && bsk_stats_run(sc, p, n, 1, in.fmt, pid, nullptr, nullptr) != BSK_OK) die(bsk_last_error(sc));
+                }
+                bsk_bgzf_reader_close(rd);  // (waits for the kernels that still read the last pieces)
+            } else if (bsk_stats_run(sc, in.ptr(), in.size(), in.on_device(), in.fmt, 0, nullptr, nullptr) != BSK_OK) die(bsk_last_error(sc));
             std::vector<int64_t> keys(1 << 20), vals(1 << 20);
             size_t n = 0;
             if (bsk_stats_collect(sc, nullptr, keys.data(), vals.data(), keys.size(), &n) != BSK_OK) die(bsk_last_error(sc));
@@ -930,10 +995,26 @@ std::vector<Part> read_parts(const std::vector<std::string>& files, int device =
             const int kind = probe_file(f);
             if (kind == 2) die(f + kPlainGzip);
             if (kind == 1) {  // compressed across PCIe, inflated in HBM: from here on an ordinary device part
-                if (use == "stats" && sb.st_size > 0 && (size_t)sb.st_size >= whole_file_limit())
-                    refuse_compressed({f}, "'stats' streams a file that does not fit one GPU", "decompress it first (bgzip -d), or cut it into files that fit");
-                if (bsk_bgzf_load(fd, device, 0, &p.dptr, &p.n) != BSK_OK)
-                    die(f + ": " + bsk_global_error() + " -- a BGZF file is inflated whole on one device: it and its text must fit there; decompress it first (bgzip -d) to use the paths for larger inputs");
+                if (use == "stats" && sb.st_size > 0 && (size_t)sb.st_size >= whole_file_limit()) {
+                    if (!bgzf_stream_on())
+                        refuse_compressed({f}, "'stats' streams a file that does not fit one GPU",
+                                          std::string("decompress it first (bgzip -d), or cut it into files that fit") + kStreamHint);
+                    // stats: the file stays where it is, the piece reader streams its text in record-aligned pieces (execute)
+                    p.fmt = sniff_format(f, std::string(1, bgzf_first_text_byte(f)));
+                    p.bgzf_fd = fd;
+                    parts.push_back(std::move(p));
+                    continue;
+                }
+                if (bsk_bgzf_load(fd, device, 0, &p.dptr, &p.n) != BSK_OK) {
+                    if (bucket_budget(use) > 0 && bgzf_stream_on()) {  // (as for a plain file that does not fit: through the buckets, piece by piece)
+                        close(fd);
+                        g_buckets_unfit = true;
+                        release(parts);
+                        return parts;
+                    }
+                    die(f + ": " + bsk_global_error() + " -- a BGZF file is inflated whole on one device: it and its text must fit there; decompress it first (bgzip -d) to use the paths for larger inputs -- "
+                        "with BSK_BGZF_STREAM=1, 'stats' and the bucket paths (BSK_<COMMAND>_BUDGET_BYTES) read a larger one in pieces");
+                }
                 close(fd);
                 char first = 0;
                 if (p.n && bsk_device_copy(&first, p.dptr, 1, BSK_COPY_D2H) != BSK_OK) die(bsk_global_error());
@@ -1165,9 +1246,16 @@ struct MappedFile {
     const uint8_t* text = nullptr;
     size_t size = 0;
     bool mapped = false;
+    // a BGZF file of the bucket paths is not mapped: its pieces are virtual-offset ranges, inflated on the device when asked for
+    bsk_bgzf_reader* reader = nullptr;
+    int fd = -1;
     void unmap() {
         if (mapped && size) munmap((void*)text, size);
         mapped = false;
+        if (reader) bsk_bgzf_reader_close(reader);
+        if (fd >= 0) close(fd);
+        reader = nullptr;
+        fd = -1;
     }
 };
 static void map_file(const std::string& path, MappedFile* f) {
@@ -1272,6 +1360,9 @@ Output run_head_genome(const Invocation& inv) {
 //             every piece of file 2; every window's share is written as it finishes, and with -f the tail over file 2.  File 1 is
 //             read 1 + B1 times, once for the window histogram and once across all windows; file 2 1 + B1 times, once for the
 //             weights, once per window and once more with -f
+// A BGZF input is refused as before unless BSK_BGZF_STREAM=1 asks for it.  Then it is not mapped: the piece reader (bsk_bgzf_reader_*) runs over it once and lists its pieces as ranges of virtual
+// offsets, and every later pass asks the reader for the piece again -- inflated on the device, handed over as a device shard.  The
+// file is inflated once per pass.  Plain and BGZF inputs may be mixed.
 // Every finished bucket is appended to the output.  A piece never spans two files, so a file that ends without a newline
 // behaves like the union of the whole-file path: its last record gets the newline.
 // The steps are written once: map_pieces (the files, their format and the pieces), plan_buckets (the passes in front of the buckets
@@ -1282,7 +1373,9 @@ struct BucketRun {
     bsk_ctx* ctx = nullptr;
     uint64_t budget = 0;
     Output res;
-    struct Piece { const uint8_t* p; size_t n; uint64_t first; size_t file; uint64_t count; };
+    // host bytes, or (p == nullptr) the range [vlo, vhi) of virtual offsets of a BGZF file, n bytes of text
+    struct Piece { const uint8_t* p; size_t n; uint64_t first; size_t file; uint64_t count; uint64_t vlo = 0, vhi = 0; bool bgzf = false; };
+    struct View { const void* p; size_t n; int on_device; };
     std::vector<MappedFile> files;
     std::vector<Piece> pieces;
     std::vector<uint64_t> file_records;  // (behind the histogram pass)
@@ -1293,14 +1386,43 @@ struct BucketRun {
     uint64_t counted = 0, flagged = 0;  // (rmdup: removed; rename: renamed; common: kept; pair: pairs; concat: records with a head)
 
     void ok(int rc) const { if (rc != BSK_OK) die(bsk_last_error(ctx)); }
+    // what an operator is handed for a piece: the mapped bytes, or the piece inflated on the device (valid until the second
+    // view of a piece of the same file after it)
+    View view(const Piece& pc) {
+        if (!pc.bgzf) return {pc.p, pc.n, 0};
+        const void* p = nullptr;
+        size_t n = 0;
+        if (bsk_bgzf_reader_piece(files[pc.file].reader, pc.vlo, pc.vhi, &p, &n) != BSK_OK) die(bsk_global_error());
+        return {p, n, 1};
+    }
     // the files mapped, of one format, and cut into record-aligned pieces; a piece never spans two files
-    void map_pieces(const std::vector<std::string>& paths, size_t n_files) {
+    void map_pieces(const std::vector<std::string>& paths, size_t n_files, int device) {
         const char* pinned = getenv("BSK_STREAM_PIECE_BYTES");
         const size_t piece = pinned ? std::max<size_t>(1, (size_t)strtoull(pinned, nullptr, 10)) : ((size_t)1 << 30);
         files.resize(n_files);
         int fmt = -1;
         for (size_t fi = 0; fi < n_files; ++fi) {
             MappedFile& f = files[fi];
+            const int kind = probe_file(paths[fi]);
+            if (kind == 2) die(paths[fi] + kPlainGzip);
+            if (kind == 1) {  // BGZF: the reader runs over the file once and lists its pieces; plain and BGZF inputs may be mixed
+                f.fd = open(paths[fi].c_str(), O_RDONLY);
+                if (f.fd < 0) die("open " + paths[fi] + ": no such file or directory");
+                const int ffmt = sniff_format(paths[fi], std::string(1, bgzf_first_text_byte(paths[fi])));
+                if (fmt >= 0 && ffmt != fmt) die(std::string(cmd.use) + ": inputs of different formats");
+                fmt = ffmt;
+                const BgzfSizes z = bgzf_sizes();
+                if (bsk_bgzf_reader_open(f.fd, device, fmt, z.piece, z.look, z.chunk, &f.reader) != BSK_OK) die(paths[fi] + ": " + bsk_global_error());
+                for (int last = 0; !last;) {
+                    Piece pc{nullptr, 0, 0, fi, 0};
+                    const void* p = nullptr;
+                    if (bsk_bgzf_reader_next(f.reader, &p, &pc.n, &pc.vlo, &pc.vhi, &last) != BSK_OK) die(paths[fi] + ": " + bsk_global_error());
+                    pc.bgzf = true;
+                    total_bytes += pc.n;
+                    if (pc.n) pieces.push_back(pc);
+                }
+                continue;
+            }
             map_file(paths[fi], &f);
             const int ffmt = sniff_format(paths[fi], f.size ? std::string((const char*)f.text, 1) : std::string());
             if (fmt >= 0 && ffmt != fmt) die(std::string(cmd.use) + ": inputs of different formats");
@@ -1333,18 +1455,23 @@ struct BucketRun {
             double rate = 1.0;
             if (!pieces.empty()) {
                 uint64_t cnt = 0;
-                ok(bsk_index_build(ctx, pieces[0].p, pieces[0].n, 0, res.fmt, nullptr, &cnt));
+                const View v = view(pieces[0]);
+                ok(bsk_index_build(ctx, v.p, v.n, v.on_device, res.fmt, nullptr, &cnt));
                 const double records = (double)total_bytes * (double)cnt / (double)std::max<size_t>(pieces[0].n, 1);
                 rate = std::min(1.0, 32.0 * (double)kBins / std::max(records, 1.0));
             }
             count_pass([&](const Piece& pc, int64_t k, uint64_t g, uint64_t* cnt) {
-                return bsk_sort_sample_run(ctx, pc.p, pc.n, 0, res.fmt, k, g, rate, nullptr, cnt);
+                const View v = view(pc);
+                return bsk_sort_sample_run(ctx, v.p, v.n, v.on_device, res.fmt, k, g, rate, nullptr, cnt);
             });
             uint32_t n_bins = 0;
             ok(bsk_sort_splitters_build(ctx, kBins, &n_bins));
             mark("sort: sample of the keys, splitters");
         }
-        count_pass([&](const Piece& pc, int64_t k, uint64_t g, uint64_t* cnt) { return cmd.hist_run(ctx, pc.p, pc.n, 0, res.fmt, k, g, nullptr, cnt); });
+        count_pass([&](const Piece& pc, int64_t k, uint64_t g, uint64_t* cnt) {
+            const View v = view(pc);
+            return cmd.hist_run(ctx, v.p, v.n, v.on_device, res.fmt, k, g, nullptr, cnt);
+        });
         mark(cmd.mark_hist);
         file_records.assign(files.size(), 0);
         for (auto& pc : pieces) file_records[pc.file] += pc.count;
@@ -1355,7 +1482,10 @@ struct BucketRun {
     void fill_bucket(int b) {
         ok(cmd.bucket_begin(ctx, (uint32_t)bounds[b], (uint32_t)bounds[b + 1]));
         int64_t k = 0;
-        for (auto& pc : pieces) ok(cmd.bucket_add(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr));
+        for (auto& pc : pieces) {
+            const View v = view(pc);
+            ok(cmd.bucket_add(ctx, v.p, v.n, v.on_device, res.fmt, k++, pc.first, nullptr));
+        }
     }
     void append_out(const bsk_out& out) { append_result(ctx, out, res.text, res.packed); }
     // shuffle, sort: every finished bucket is appended to the output; backwards (sort -r): from the last to the first
@@ -1388,7 +1518,8 @@ struct BucketRun {
         for (auto& pc : pieces) {
             if (cmd.emit_first_file_only && pc.file != 0) break;
             bsk_out out;
-            ok(cmd.emit_run(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr, &out));
+            const View v = view(pc);
+            ok(cmd.emit_run(ctx, v.p, v.n, v.on_device, res.fmt, k++, pc.first, nullptr, &out));
             append_out(out);
         }
         mark(cmd.mark_emit);
@@ -1427,7 +1558,8 @@ void BucketRun::pair_tail(const Invocation& inv, const std::string& outdir) {
     for (auto& pc : pieces) {
         if (pc.file == 1 && !unp && !by_emit) break;
         bsk_out outs[3];
-        ok(bsk_pair_emit_run(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr, outs));
+        const View v = view(pc);
+        ok(bsk_pair_emit_run(ctx, v.p, v.n, v.on_device, res.fmt, k++, pc.first, nullptr, outs));
         if (pc.file == 0) write_share(0, outs[0]);
         else write_share(1, outs[2]);
         write_share(pc.file == 0 ? 2 : 3, outs[1]);
@@ -1437,7 +1569,9 @@ void BucketRun::pair_tail(const Invocation& inv, const std::string& outdir) {
         // paired.2 in buckets of the position: the histogram over the pieces of file 2, the plan, one pass per bucket
         for (auto& pc : pieces) {
             uint64_t cnt = 0;
-            if (pc.file == 1) ok(bsk_pair_order_hist_run(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr, &cnt));
+            if (pc.file != 1) continue;
+            const View v = view(pc);
+            ok(bsk_pair_order_hist_run(ctx, v.p, v.n, v.on_device, res.fmt, k++, pc.first, nullptr, &cnt));
         }
         ok(bsk_pair_order_hist_get(ctx, hist.data(), nullptr));
         if (bsk_shuffle_plan(hist.data(), budget, bounds.data(), &n_second) != BSK_OK)
@@ -1445,8 +1579,11 @@ void BucketRun::pair_tail(const Invocation& inv, const std::string& outdir) {
                                                    "at most a 4096th of the pairs rounded up to a power of two");
         for (int b = 0; b < n_second; ++b) {
             ok(bsk_pair_order_bucket_begin(ctx, (uint32_t)bounds[b], (uint32_t)bounds[b + 1]));
-            for (auto& pc : pieces)
-                if (pc.file == 1) ok(bsk_pair_order_bucket_add(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr));
+            for (auto& pc : pieces) {
+                if (pc.file != 1) continue;
+                const View v = view(pc);
+                ok(bsk_pair_order_bucket_add(ctx, v.p, v.n, v.on_device, res.fmt, k++, pc.first, nullptr));
+            }
             bsk_out out;
             ok(bsk_pair_order_bucket_finish(ctx, nullptr, &out));
             write_share(1, out);
@@ -1490,7 +1627,9 @@ void BucketRun::concat_tail(const Invocation& inv) {
     for (int file = 1; file >= 0; --file)
         for (auto& pc : pieces) {
             uint64_t cnt = 0;
-            if ((int)pc.file == file) ok((file ? bsk_concat_weigh_run : bsk_concat_window_hist_run)(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr, &cnt));
+            if ((int)pc.file != file) continue;
+            const View v = view(pc);
+            ok((file ? bsk_concat_weigh_run : bsk_concat_window_hist_run)(ctx, v.p, v.n, v.on_device, res.fmt, k++, pc.first, nullptr, &cnt));
         }
     ok(bsk_concat_window_hist_get(ctx, hist.data(), nullptr));
     if (bsk_shuffle_plan(hist.data(), budget, bounds.data(), &n_second) != BSK_OK)
@@ -1506,7 +1645,8 @@ void BucketRun::concat_tail(const Invocation& inv) {
         for (auto& pc : pieces) {
             // (a piece of file 1 wholly outside the window adds nothing)
             if (pc.file == 0 && (pc.count == 0 || ((pc.first + pc.count - 1) >> shift) < lo || (pc.first >> shift) >= hi)) continue;
-            ok(bsk_concat_window_add(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr));
+            const View v = view(pc);
+            ok(bsk_concat_window_add(ctx, v.p, v.n, v.on_device, res.fmt, k++, pc.first, nullptr));
         }
         bsk_out out;
         ok(bsk_concat_window_finish(ctx, nullptr, &out));
@@ -1517,7 +1657,8 @@ void BucketRun::concat_tail(const Invocation& inv) {
         for (auto& pc : pieces) {
             if (pc.file != 1) continue;
             bsk_out out;
-            ok(bsk_concat_tail_run(ctx, pc.p, pc.n, 0, res.fmt, k++, pc.first, nullptr, &out));
+            const View v = view(pc);
+            ok(bsk_concat_tail_run(ctx, v.p, v.n, v.on_device, res.fmt, k++, pc.first, nullptr, &out));
             write_share(out);
         }
         mark("concat: tail");
@@ -1539,7 +1680,9 @@ Output run_buckets(const Invocation& inv) {
         if (inv.files.size() < 2) die("2 files needed");
         if (outdir.empty()) die("out-dir required");
     }
-    refuse_compressed(inv.files, "the buckets of '" + use + "' read", "decompress it first (bgzip -d), or unset the budget if the file and its text fit one GPU");
+    if (!bgzf_stream_on())
+        refuse_compressed(inv.files, "the buckets of '" + use + "' read",
+                          std::string("decompress it first (bgzip -d), or unset the budget if the file and its text fit one GPU") + kStreamHint);
     const int device = (int)strtol(inv.pget("device").c_str(), nullptr, 10);
     BucketRun R{*bucket_cmd(use)};
     R.res.packed = !pair && packs_on_device(inv);  // (pair -O writes its four files under fixed names: plain)
@@ -1547,7 +1690,7 @@ Output run_buckets(const Invocation& inv) {
     if (bsk_create(inv.cmd->op, inv.js.c_str(), device, &R.ctx) != BSK_OK) die(bsk_global_error());
     const bool timing = getenv("BSK_CLI_TIMING") != nullptr;
     if (timing) bsk_profile_enable(R.ctx, 1);
-    R.map_pieces(inv.files, pair || concat ? 2 : inv.files.size());
+    R.map_pieces(inv.files, pair || concat ? 2 : inv.files.size(), device);
     R.plan_buckets();
     if (concat) {
         R.concat_tail(inv);

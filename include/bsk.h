@@ -189,6 +189,48 @@ int bsk_bgzf_inflate_host(const void* comp, size_t n_comp, void* out, size_t cap
 /* CRC32 of data[0, n), n <= 65536, taken as the kernel takes it: chunks of 1 KiB measured from the end, folded with the
  * "advance by 1 KiB" operator.  For the tests, which compare it with zlib's. */
 uint32_t bsk_selftest_bgzf_crc(const void* data, size_t n);
+/* ---- a BGZF file as record-aligned pieces (PARITY.md BGZF "pieces"; bgzf_stream.hpp, ops_bgzf_stream.hip) ----
+ * bsk_bgzf_load holds the file and its text whole.  The reader hands the text out piece by piece instead -- every piece begins
+ * on a record and holds about piece_text_bytes -- and holds neither: two buffers of compressed bytes (comp_chunk_bytes each,
+ * pinned and on the device) and two buffers of text are allocated at open.  device >= 0: the pieces lie in the memory of that
+ * device, chunk k + 1 is read (pread) and copied under the inflate of chunk k; device = -1: the same reader with host buffers
+ * and the decoder on host threads, the same pieces.  `fd` stays the caller's.  0 for a size means 1 GiB of text, 1 MiB of
+ * lookahead, 256 MiB of compressed bytes.
+ *
+ * Positions are BGZF VIRTUAL OFFSETS: coffset << 16 | uoffset, coffset the file offset of a block, uoffset < ISIZE a byte of its
+ * text.  The reader's are normalised -- never in an empty block, never at a block's end -- and the end of the text is
+ * file_size << 16.  A piece is [voff_lo, voff_hi): a caller that reads the file several times keeps two numbers per piece and
+ * gets the same bytes back from bsk_bgzf_reader_piece on every pass.
+ *
+ * Which pieces: a function of the text and the block ends alone, not of comp_chunk_bytes and not of the device.  From the
+ * piece's start s, whole blocks are inflated up to E, the first block end with E - s >= piece_text_bytes + lookahead_bytes, or
+ * the end of the text, where the piece is the rest.  Else the piece ends at the answer of bsk_find_record_start on text[s, E)
+ * from piece_text_bytes; if there is none before E, E moves on with the lookahead doubled: a record longer than a piece makes a
+ * longer piece.  The text behind the cut is the head of the next piece.
+ *
+ *   bsk_bgzf_reader_next    the next piece: *ptr (device or host memory, as opened; a multiple of 256), *n bytes, its offsets,
+ *                           *last != 0 with the piece that ends the text.  An empty file and a lone EOF block give one empty
+ *                           last piece.  A PIECE STAYS VALID UNTIL THE SECOND CALL OF next / piece AFTER THE ONE THAT GAVE IT:
+ *                           operators that take a device shard are asynchronous, so the piece in front of the current one may
+ *                           still be read.  Before a buffer is written again the reader's stream waits for an event recorded
+ *                           on the default stream at that call
+ *   bsk_bgzf_reader_seek    the next piece begins at voff (uoffset != 0: inside a block)
+ *   bsk_bgzf_reader_piece   the bytes [voff_lo, voff_hi), offsets as next gave them; consecutive pieces are read on without a
+ *                           seek.  Validity as for next
+ *   bsk_bgzf_reader_close   waits for the device, then frees the buffers: no piece is valid afterwards
+ * Refusals: those of BGZF input above, the block numbered over the whole file and named with its file offset (behind a seek
+ * to a place the reader has not handed out, the message says that the number counts from the seek).  Errors:
+ * bsk_global_error(); after one the reader answers with it until the next seek. */
+typedef struct bsk_bgzf_reader bsk_bgzf_reader;
+int bsk_bgzf_reader_open(int fd, int device, int format, size_t piece_text_bytes, size_t lookahead_bytes, size_t comp_chunk_bytes,
+                         bsk_bgzf_reader** out);
+int bsk_bgzf_reader_next(bsk_bgzf_reader* r, const void** ptr, size_t* n, uint64_t* voff_lo, uint64_t* voff_hi, int* last);
+int bsk_bgzf_reader_seek(bsk_bgzf_reader* r, uint64_t voff);
+int bsk_bgzf_reader_piece(bsk_bgzf_reader* r, uint64_t voff_lo, uint64_t voff_hi, const void** ptr, size_t* n);
+void bsk_bgzf_reader_close(bsk_bgzf_reader* r);
+/* Where the reader's kernel cuts text[0, n) (host memory) from `from`: bsk_find_record_start's answer, n where neither finds a
+ * start, or ~0: declined, the host rule decides.  device = -1: the same function on the host.  For the tests. */
+int bsk_selftest_bgzf_stream_cut(const void* text, size_t n, size_t from, int format, int device, uint64_t* cut);
 /* ---- BGZF output (PARITY.md BGZFW; ops_bgzf_write.hip, bgzf_deflate_dev.hpp) ----
  * A text becomes the BGZF file that holds it: blocks of `block_text_bytes` of text (0: 65 280, bgzip's size; at most
  * 65 280), each encoded by one wavefront -- LZ77 matches inside the block, dynamic Huffman codes per block, and per block the
