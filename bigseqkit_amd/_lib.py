@@ -220,6 +220,12 @@ SIGNATURES = {
     "bsk_bgzf_blocks_device": (_i, [_vp, _sz, _i, _p(C.c_uint64), _p(C.c_uint32), _p(C.c_uint32), _sz, _p(_sz)]),
     "bsk_bgzf_inflate_host": (_i, [C.c_char_p, _sz, _vp, _sz, _p(_sz), _i]),
     "bsk_selftest_bgzf_crc": (C.c_uint32, [C.c_char_p, _sz]),
+    "bsk_gzip_inflate_device": (_i, [_vp, _sz, _i, _sz, _p(_vp), _p(_sz)]),
+    "bsk_gzip_load": (_i, [_i, _i, _i, _sz, _p(_vp), _p(_sz)]),
+    "bsk_gzip_inflate_host": (_i, [C.c_char_p, _sz, _vp, _sz, _p(_sz), _sz]),
+    "bsk_gzip_last_plan": (None, [_p(_u64)]),
+    "bsk_selftest_gzip_find": (_i, [C.c_char_p, _sz, _sz, _p(_u64), _sz]),
+    "bsk_selftest_gzip_header_ok": (_i, [C.c_char_p, _sz, _u64]),
     "bsk_bgzf_reader_open": (_i, [_i, _i, _i, _sz, _sz, _sz, _p(_vp)]),
     "bsk_bgzf_reader_next": (_i, [_vp, _p(_vp), _p(_sz), _p(_u64), _p(_u64), _p(_i)]),
     "bsk_bgzf_reader_seek": (_i, [_vp, _u64]),

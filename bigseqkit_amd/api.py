@@ -132,6 +132,37 @@ def BgzfInflate(data, device=0):
     return _adopt(d_text, n_text.value, device)
 
 
+# ---- plain gzip input (include/bsk.h "plain gzip input"; PARITY.md GZIP)
+def GzipInflate(data, device=0, chunk_bytes=0):
+    """the text of a gzip file of any number of members: bytes or a CUDA uint8 tensor in, a CUDA uint8 tensor out, inflated on
+    the device in speculative chunks of chunk_bytes (0: the library's choice).  device=-1: bytes in, bytes out, the same method
+    with one host lane (chunk_bytes 0: one piece)"""
+    n_text = C.c_size_t()
+    if device < 0:
+        data = bytes(data)
+        check(lib.bsk_gzip_inflate_host(data, len(data), None, 0, C.byref(n_text), chunk_bytes))
+        buf = C.create_string_buffer(max(1, n_text.value))
+        check(lib.bsk_gzip_inflate_host(data, len(data), buf, n_text.value, C.byref(n_text), chunk_bytes))
+        return buf.raw[:n_text.value]
+    keep, ptr, n = _device_input(data, device)
+    d_text = C.c_void_p()
+    check(lib.bsk_gzip_inflate_device(ptr, n, device, chunk_bytes, C.byref(d_text), C.byref(n_text)))
+    del keep
+    return _adopt(d_text, n_text.value, device)
+
+
+_PLAN_FIELDS = ("chunks", "with_candidate", "on_chain", "off_chain", "members", "text_bytes", "dropped_bytes", "chunk_bytes")
+
+
+def GzipPlan():
+    """the numbers of the last GzipInflate / gzip ReadSeqFile on this thread, as a dict: chunks, with_candidate (chunks in which
+    a block start was found), on_chain (chunks that the true chain of blocks visits, the first included), off_chain (candidates
+    that were dropped), members, text_bytes, dropped_bytes (decoded by chunks that were dropped), chunk_bytes"""
+    out = (C.c_uint64 * 8)()
+    lib.bsk_gzip_last_plan(out)
+    return dict(zip(_PLAN_FIELDS, (int(v) for v in out)))
+
+
 def BgzfBlocks(data, device=0):
     """the block index: [(offset in the file, size of the block, bytes it holds), ...]"""
     keep, ptr, n = _device_input(data, device)
@@ -293,18 +324,22 @@ def _format_of(path, first):
     raise BskError(_lib.BSK_ERR_FORMAT, "%s must be fasta or fastq" % os.fspath(path))
 
 
-def ReadSeqFile(path, device=0):
+def ReadSeqFile(path, device=0, gzip=False):
     """a FASTA / FASTQ file, plain or BGZF, as a SeqFrame over one shard.  A BGZF file crosses to the device compressed and is
-    inflated there (bsk_bgzf_load); a plain one is read as ReadFASTA / ReadFASTQ read it.  gzip that is not BGZF is refused"""
+    inflated there (bsk_bgzf_load); a plain one is read as ReadFASTA / ReadFASTQ read it.  gzip that is not BGZF is refused,
+    unless gzip=True: then it crosses compressed too and is inflated in speculative chunks (bsk_gzip_load)"""
     with open(os.fspath(path), "rb") as f:
         head = f.read(12 + 65535)
         kind = BgzfProbe(head)
-        if kind == 2:
+        if kind == 2 and not gzip:
             raise BskError(_lib.BSK_ERR_UNSUPPORTED, "%s is gzip but not BGZF: one gzip stream cannot be cut into independent blocks; recompress it with bgzip" % os.fspath(path))
         if kind == 0:
             return SeqFrame(_format_of(path, head[:1]), [head + f.read()])
         d_text, n_text = C.c_void_p(), C.c_size_t()
-        check(lib.bsk_bgzf_load(f.fileno(), device, 0, C.byref(d_text), C.byref(n_text)))
+        if kind == 2:
+            check(lib.bsk_gzip_load(f.fileno(), device, 0, 0, C.byref(d_text), C.byref(n_text)))
+        else:
+            check(lib.bsk_bgzf_load(f.fileno(), device, 0, C.byref(d_text), C.byref(n_text)))
     t = _adopt(d_text, n_text.value, device)
     return SeqFrame(_format_of(path, bytes(t[:1].cpu().numpy().tobytes())), [t])
 

@@ -129,25 +129,24 @@ BGZF_HD int huff_walk(const uint16_t* count, const uint16_t* symtab, uint32_t bi
     return -1;
 }
 
-template <class P>
-struct Inflater {
+// What every decoder of this family shares: the bit reader, the tables of a block and the decode of one symbol.  L is what the
+// lanes share (BgzfLds, or another struct with the same table members), Pos the type that counts compressed words and bits: 32
+// bits for a BGZF block, 64 for a gzip stream of any length (gzip_spec_dev.hpp).
+template <class P, class L, class Pos>
+struct HuffCore {
     P& io;
-    BgzfLds& S;
-    // the bit reader: `buf` holds `cnt` bits, `wnext` is the next word of the compressed buffer, `left` the bits of the block's
+    L& S;
+    // the bit reader: `buf` holds `cnt` bits, `wnext` is the next word of the compressed buffer, `left` the bits of the
     // data that are not consumed yet (those in `buf` included; what `buf` holds beyond them is never consumed)
     uint64_t buf = 0;
-    uint32_t wnext = 0, left = 0, cnt = 0, in_end = 0;
-    // the output: p bytes produced, f of them stored; ring_at(q) = (shift + q) & RING_MASK
-    uint32_t p = 0, f = 0, isize = 0, shift = 0;
-    uint32_t nlit = 0, mylit = 0;   // literals that wait in the lanes' registers, lane k holds literal k
-    uint32_t crc = 0xFFFFFFFFu;     // of this lane's chunk
+    Pos wnext = 0, left = 0;
+    uint32_t cnt = 0;
+    Pos in_end = 0;
     bool fixed_ready = false;
 
-    BGZF_HD Inflater(P& io_, BgzfLds& S_) : io(io_), S(S_) {}
+    BGZF_HD HuffCore(P& io_, L& S_) : io(io_), S(S_) {}
 
-    BGZF_HD uint32_t ring_at(uint32_t q) const { return (shift + q) & RING_MASK; }
-
-    BGZF_HD void seek(uint32_t byte) {
+    BGZF_HD void seek(Pos byte) {
         wnext = byte >> 2;
         const uint32_t skip = (uint32_t)(byte & 3u) * 8u;
         buf = (uint64_t)(io.word(wnext++) >> skip);
@@ -168,34 +167,6 @@ struct Inflater {
         return true;
     }
     BGZF_HD uint32_t peek(uint32_t n) const { return (uint32_t)buf & ((1u << n) - 1u); }
-
-    // bytes [a, b) leave the ring: every lane takes the CRC of what is its chunk's, then they are stored
-    BGZF_HD void drain(uint32_t a, uint32_t b) {
-        const uint32_t l = io.lane();
-        const uint64_t back = (uint64_t)l * P::CRC_CHUNK;
-        if (back < isize) {
-            const uint32_t ce = isize - (uint32_t)back, cs = ce > P::CRC_CHUNK ? ce - P::CRC_CHUNK : 0u;
-            const uint32_t q0 = a > cs ? a : cs, q1 = b < ce ? b : ce;
-            uint32_t c = crc;
-            for (uint32_t q = q0; q < q1; ++q) c = S.crc_tab[(c ^ S.ring[ring_at(q)]) & 255u] ^ (c >> 8);
-            crc = c;
-        }
-        io.store(S.ring, shift, a, b);
-        f = b;
-    }
-    // after every step that produced bytes: at most DRAIN_AT + 4096 + 15 < RING bytes ever wait
-    BGZF_HD void maybe_drain() {
-        if (p - f >= DRAIN_AT) drain(f, p - ((shift + p) & 15u));  // (up to a 16-byte boundary of the output)
-    }
-    BGZF_HD void flush_lits() {
-        if (nlit) {
-            if (io.lane() < nlit) S.ring[ring_at(p + io.lane())] = (uint8_t)mylit;
-            p += nlit;
-            nlit = 0;
-            io.sync();
-            maybe_drain();
-        }
-    }
 
     // The tables of one code from lens[0, n).  kind 0: the code-length code, 1: literal/length, 2: distance.  What zlib's
     // inflate_table takes and refuses: an over-subscribed set is refused; an incomplete one is refused for the code-length code
@@ -329,6 +300,49 @@ struct Inflater {
         }
         fixed_ready = type == 1u;
         return OK;
+    }
+};
+
+template <class P>
+struct Inflater : HuffCore<P, BgzfLds, uint32_t> {
+    using Core = HuffCore<P, BgzfLds, uint32_t>;
+    using Core::io; using Core::S; using Core::buf; using Core::wnext; using Core::left; using Core::cnt; using Core::in_end;
+    using Core::seek; using Core::need32; using Core::drop; using Core::peek; using Core::symbol; using Core::tables;
+    // the output: p bytes produced, f of them stored; ring_at(q) = (shift + q) & RING_MASK
+    uint32_t p = 0, f = 0, isize = 0, shift = 0;
+    uint32_t nlit = 0, mylit = 0;   // literals that wait in the lanes' registers, lane k holds literal k
+    uint32_t crc = 0xFFFFFFFFu;     // of this lane's chunk
+
+    BGZF_HD Inflater(P& io_, BgzfLds& S_) : Core(io_, S_) {}
+
+    BGZF_HD uint32_t ring_at(uint32_t q) const { return (shift + q) & RING_MASK; }
+
+    // bytes [a, b) leave the ring: every lane takes the CRC of what is its chunk's, then they are stored
+    BGZF_HD void drain(uint32_t a, uint32_t b) {
+        const uint32_t l = io.lane();
+        const uint64_t back = (uint64_t)l * P::CRC_CHUNK;
+        if (back < isize) {
+            const uint32_t ce = isize - (uint32_t)back, cs = ce > P::CRC_CHUNK ? ce - P::CRC_CHUNK : 0u;
+            const uint32_t q0 = a > cs ? a : cs, q1 = b < ce ? b : ce;
+            uint32_t c = crc;
+            for (uint32_t q = q0; q < q1; ++q) c = S.crc_tab[(c ^ S.ring[ring_at(q)]) & 255u] ^ (c >> 8);
+            crc = c;
+        }
+        io.store(S.ring, shift, a, b);
+        f = b;
+    }
+    // after every step that produced bytes: at most DRAIN_AT + 4096 + 15 < RING bytes ever wait
+    BGZF_HD void maybe_drain() {
+        if (p - f >= DRAIN_AT) drain(f, p - ((shift + p) & 15u));  // (up to a 16-byte boundary of the output)
+    }
+    BGZF_HD void flush_lits() {
+        if (nlit) {
+            if (io.lane() < nlit) S.ring[ring_at(p + io.lane())] = (uint8_t)mylit;
+            p += nlit;
+            nlit = 0;
+            io.sync();
+            maybe_drain();
+        }
     }
 
     BGZF_HD int read_stored() {

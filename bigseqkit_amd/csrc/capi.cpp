@@ -20,6 +20,7 @@
 #include "bgzf_stream.hpp"
 #include "ops_bgzf.hpp"
 #include "ops_bgzf_write.hpp"
+#include "ops_gzip.hpp"
 #include "ops_host.hpp"
 #include "ops_host_internal.hpp"
 #include "ops_sample.hpp"
@@ -746,6 +747,49 @@ int bsk_bgzf_inflate_host(const void* comp, size_t n_comp, void* out, size_t cap
     const int rc = bgzf_inflate_host(comp, n_comp, out, cap, n_out, threads, err);
     return rc == BSK_OK ? rc : fail_global(rc, err);
 }
+
+// ---- plain gzip input (ops_gzip.hip, gzip_spec_dev.hpp): thin shells as for BGZF
+int bsk_gzip_inflate_device(const void* d_comp, size_t n_comp, int device, size_t chunk_bytes, void** d_text, size_t* n_text) {
+    if (!d_text || !n_text || (!d_comp && n_comp)) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: gzip: null argument");
+    std::string err;
+    const int rc = gzip_inflate_device(d_comp, n_comp, device, chunk_bytes, d_text, n_text, err);
+    return rc == BSK_OK ? rc : fail_global(rc, err);
+}
+
+int bsk_gzip_load(int fd, int device, int threads, size_t chunk_bytes, void** d_text, size_t* n_text) {
+    if (!d_text || !n_text || fd < 0) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: gzip: bad arguments");
+    *d_text = nullptr;
+    *n_text = 0;
+    const off_t size = lseek(fd, 0, SEEK_END);
+    if (size < 0) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: gzip: the file cannot be measured (a pipe goes through bsk_gzip_inflate_host)");
+    void* d_comp = nullptr;
+    int rc = bsk_shard_load(fd, 0, (size_t)size, device, threads, &d_comp);
+    if (rc != BSK_OK) return rc;
+    std::string err;
+    rc = gzip_inflate_device(d_comp, (size_t)size, device, chunk_bytes, d_text, n_text, err);
+    hipFree(d_comp);
+    return rc == BSK_OK ? rc : fail_global(rc, err);
+}
+
+int bsk_gzip_inflate_host(const void* comp, size_t n_comp, void* out, size_t cap, size_t* n_out, size_t chunk_bytes) {
+    if (!n_out || (!comp && n_comp)) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: gzip: null argument");
+    std::string err;
+    const int rc = gzip_inflate_host(comp, n_comp, out, cap, n_out, chunk_bytes, err);
+    return rc == BSK_OK ? rc : fail_global(rc, err);
+}
+
+void bsk_gzip_last_plan(uint64_t out[8]) {
+    if (out) gzip_last_plan(out);
+}
+
+int bsk_selftest_gzip_find(const void* comp, size_t n_comp, size_t chunk_bytes, uint64_t* cand, size_t nchunks) {
+    if ((!comp && n_comp) || !cand || chunk_bytes == 0 || nchunks != (n_comp + chunk_bytes - 1) / chunk_bytes)
+        return fail_global(BSK_ERR_INVALID_ARG, "libbsk: gzip: bad arguments");
+    gzip_find_host(comp, n_comp, chunk_bytes, cand, nchunks);
+    return BSK_OK;
+}
+
+int bsk_selftest_gzip_header_ok(const void* comp, size_t n_comp, uint64_t bit) { return comp ? gzip_header_ok_host(comp, n_comp, bit) : 0; }
 
 // ---- the piece reader of a BGZF file (bgzf_stream.hpp, ops_bgzf_stream.hip): thin shells again
 struct bsk_bgzf_reader { BgzfPieceReader* r; };

@@ -310,9 +310,23 @@ int sniff_format(const std::string& file_, const std::string& data) {
     die(" <file> must be fasta or fastq");
 }
 
-// ---- compressed input (PARITY.md BGZF): BGZF is inflated, on the device where the part lives there; any other gzip is refused
+// ---- compressed input (PARITY.md BGZF, GZIP): BGZF is inflated, on the device where the part lives there; any other gzip is
+// refused unless BSK_GZIP=1 asks for it: then it is read wherever a BGZF file is read whole (bsk_gzip_load on the device, the same
+// method on the host for the commands that keep host strings).  The paths that read a file in pieces still refuse it: a gzip
+// stream has no virtual offsets to re-enter at
 const char* const kPlainGzip = " is gzip but not BGZF: one gzip stream cannot be cut into independent blocks, so it is not read; "
-                               "recompress it with bgzip (gzip -dc FILE | bgzip > FILE.gz) or decompress it first";
+                               "recompress it with bgzip (gzip -dc FILE | bgzip > FILE.gz) or decompress it first, or set BSK_GZIP=1 "
+                               "to have it inflated whole, in speculative chunks, where the file and its text fit one GPU";
+bool gzip_on() {
+    const char* e = getenv("BSK_GZIP");
+    return e && *e && strcmp(e, "0") != 0;
+}
+// plain gzip on a path that BSK_GZIP=1 does not reach (without the switch: the refusal of every path)
+[[noreturn]] void refuse_plain_gzip(const std::string& f, const std::string& where) {
+    if (!gzip_on()) die(f + kPlainGzip);
+    die(f + " is gzip but not BGZF, and " + where + " a file in pieces: a gzip stream has no virtual offsets to re-enter at, so BSK_GZIP=1 "
+        "reads it only where a file is read whole; decompress it first (gzip -d), or recompress it with bgzip (gzip -dc FILE | bgzip > FILE.gz)");
+}
 
 // what the first bytes of a regular file are (bsk_bgzf_probe): 0 plain, 1 BGZF, 2 other gzip.  A pipe is 0: it is looked at
 // once it has been read
@@ -334,7 +348,7 @@ int probe_file(const std::string& path) {
 void refuse_compressed(const std::vector<std::string>& files, const std::string& where, const std::string& instead) {
     for (auto& f : files) {
         const int kind = probe_file(f);
-        if (kind == 2) die(f + kPlainGzip);
+        if (kind == 2) refuse_plain_gzip(f, where);
         if (kind == 1) die(f + " is BGZF-compressed, and " + where + " a file by its bytes, which a compressed file does not allow yet; " + instead);
     }
 }
@@ -390,7 +404,15 @@ BgzfSizes bgzf_sizes() {
 
 void inflate_host_text(const std::string& path, std::string& text) {
     const int kind = bsk_bgzf_probe(text.data(), text.size());
-    if (kind == 2) die(path + kPlainGzip);
+    if (kind == 2) {  // (plain gzip: the speculative method with one host lane, in one piece)
+        if (!gzip_on()) die(path + kPlainGzip);
+        size_t n = 0;
+        if (bsk_gzip_inflate_host(text.data(), text.size(), nullptr, 0, &n, 0) != BSK_OK) die(path + ": " + bsk_global_error());
+        std::string out(n, '\0');
+        if (n && bsk_gzip_inflate_host(text.data(), text.size(), &out[0], n, &n, 0) != BSK_OK) die(path + ": " + bsk_global_error());
+        text.swap(out);
+        return;
+    }
     if (kind != 1) return;
     size_t n = 0;
     if (bsk_bgzf_inflate_host(text.data(), text.size(), nullptr, 0, &n, 0) != BSK_OK) die(path + ": " + bsk_global_error());
@@ -993,7 +1015,20 @@ std::vector<Part> read_parts(const std::vector<std::string>& files, int device =
                 continue;
             }
             const int kind = probe_file(f);
-            if (kind == 2) die(f + kPlainGzip);
+            if (kind == 2) {  // plain gzip: compressed across PCIe, inflated whole in HBM -- there are no pieces of it
+                if (!gzip_on()) die(f + kPlainGzip);
+                if (use == "stats" && sb.st_size > 0 && (size_t)sb.st_size >= whole_file_limit()) refuse_plain_gzip(f, "'stats' streams");
+                if (bsk_gzip_load(fd, device, 0, 0, &p.dptr, &p.n) != BSK_OK)
+                    die(f + ": " + bsk_global_error() + " -- a gzip file is inflated whole on one device: it, its text and twice its text in symbols must fit there; "
+                        "decompress it first (gzip -d), or recompress it with bgzip to use the paths for larger inputs");
+                close(fd);
+                char first = 0;
+                if (p.n && bsk_device_copy(&first, p.dptr, 1, BSK_COPY_D2H) != BSK_OK) die(bsk_global_error());
+                p.fmt = sniff_format(f, p.n ? std::string(1, first) : std::string());
+                p.owned_alloc = true;
+                parts.push_back(std::move(p));
+                continue;
+            }
             if (kind == 1) {  // compressed across PCIe, inflated in HBM: from here on an ordinary device part
                 if (use == "stats" && sb.st_size > 0 && (size_t)sb.st_size >= whole_file_limit()) {
                     if (!bgzf_stream_on())
@@ -1404,7 +1439,7 @@ struct BucketRun {
         for (size_t fi = 0; fi < n_files; ++fi) {
             MappedFile& f = files[fi];
             const int kind = probe_file(paths[fi]);
-            if (kind == 2) die(paths[fi] + kPlainGzip);
+            if (kind == 2) refuse_plain_gzip(paths[fi], std::string("the buckets of '") + cmd.use + "' read");
             if (kind == 1) {  // BGZF: the reader runs over the file once and lists its pieces; plain and BGZF inputs may be mixed
                 f.fd = open(paths[fi].c_str(), O_RDONLY);
                 if (f.fd < 0) die("open " + paths[fi] + ": no such file or directory");
@@ -1680,6 +1715,8 @@ Output run_buckets(const Invocation& inv) {
         if (inv.files.size() < 2) die("2 files needed");
         if (outdir.empty()) die("out-dir required");
     }
+    for (auto& f : inv.files)  // (plain gzip has no pieces, with or without the switches: said before a device is touched)
+        if (probe_file(f) == 2) refuse_plain_gzip(f, "the buckets of '" + use + "' read");
     if (!bgzf_stream_on())
         refuse_compressed(inv.files, "the buckets of '" + use + "' read",
                           std::string("decompress it first (bgzip -d), or unset the budget if the file and its text fit one GPU") + kStreamHint);
@@ -2130,8 +2167,9 @@ static int run_main(int argc, char** argv) {
             "a worker could not judge its shard before the shards in front of it are done, so --devices is refused");
     if (!inv.pget("devices").empty()) return run_devices(inv);  // several GPUs: worker threads + librccl, in this process
     if (inv.files.empty()) die("no input files (stdin is not supported by the IgnisHPC CLI either)");
-    for (auto& f : inv.files)  // (gzip that is not BGZF is read by no path: said before a device is touched)
-        if (probe_file(f) == 2) die(f + kPlainGzip);
+    if (!gzip_on())
+        for (auto& f : inv.files)  // (gzip that is not BGZF is read by no path without the switch: said before a device is touched)
+            if (probe_file(f) == 2) die(f + kPlainGzip);
     g_faidx_query = faidx_query;
     const std::string use_cmd = inv.cmd->use;
     const bool joins_on_host = use_cmd == "concat" || use_cmd == "common" || use_cmd == "pair";

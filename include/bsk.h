@@ -189,6 +189,44 @@ int bsk_bgzf_inflate_host(const void* comp, size_t n_comp, void* out, size_t cap
 /* CRC32 of data[0, n), n <= 65536, taken as the kernel takes it: chunks of 1 KiB measured from the end, folded with the
  * "advance by 1 KiB" operator.  For the tests, which compare it with zlib's. */
 uint32_t bsk_selftest_bgzf_crc(const void* data, size_t n);
+/* ---- plain gzip input (PARITY.md GZIP; ops_gzip.hip, gzip_spec_dev.hpp) ----
+ * What gzip / pigz write: RFC 1952 members (FEXTRA / FNAME / FCOMMENT / FHCRC allowed) of stored, fixed and dynamic blocks, up
+ * to 65 536 members, empty ones included.  zlib defines the bytes: the text is every member's, concatenated.  One DEFLATE
+ * stream has no independent blocks, so the compressed bytes are cut into chunks of chunk_bytes, a start of a dynamic block is
+ * searched in every chunk, every chunk is decoded from its candidate at once with the unknown 32 KiB in front of it as
+ * markers, the chunks that the true chain of blocks lands on are kept and their markers resolved in order.  The text does not
+ * depend on chunk_bytes or on what the search finds; every member is checked against its CRC32 and ISIZE (modulo 2^32).
+ * Refused with BSK_ERR_FORMAT, the text naming the member, the file offset and the reason: a bad DEFLATE stream, a CRC32 or
+ * ISIZE that does not fit, a stream that ends inside a member, bytes behind the last member that are no member header (zero
+ * padding too).  More than 65 536 members: BSK_ERR_UNSUPPORTED with the count.  Text, symbols (twice the text) and input that
+ * do not fit on the device together: BSK_ERR_CAPACITY with the sizes.  A BGZF file given to these calls is a gzip file of many
+ * members and gives the same text.  The bsk_bgzf_* calls refuse plain gzip as before.
+ *   bsk_gzip_inflate_device  d_comp[0, n_comp) in the memory of `device` -> a NEW buffer *d_text of *n_text bytes
+ *                            (bsk_device_free).  chunk_bytes 0: BSK_GZIP_CHUNK_BYTES if set, else the compressed size over four
+ *                            times the waves of the decode kernel that the device holds, at least 256 KiB; never below 1 KiB.
+ *                            THE SIZE USED IS A POWER OF TWO: a chunk_bytes, a BSK_GZIP_CHUNK_BYTES or a default between two
+ *                            powers is rounded DOWN (3000 -> 2048; the default may be as little as half the quotient above),
+ *                            and a size that holds the whole input makes one chunk.  bsk_gzip_last_plan says which size
+ *                            was used; the text does not depend on it
+ *   bsk_gzip_load            bsk_shard_load of the whole file `fd`, inflated; the compressed copy is freed
+ *   bsk_gzip_inflate_host    the same source with one host lane.  chunk_bytes 0 decodes in one piece, any other value runs the
+ *                            whole method (find, size, chain, decode, windows, translate) on the host, chunk_bytes rounded as
+ *                            above.  cap = 0 asks for the size: *n_out -- the text is inflated then, and kept for this
+ *                            thread's next call with the same comp, n_comp and chunk_bytes, which only copies it
+ *   bsk_gzip_last_plan       the numbers of the last of these calls on this thread: chunks, chunks with a candidate, chunks on
+ *                            the chain, candidates that were not on the chain, members, text bytes, bytes decoded by chunks that
+ *                            were dropped, chunk size used
+ * Stages of bsk_profile_dump (process-wide, as for BGZF): gzip_find, gzip_size, gzip_decode, gzip_windows, gzip_translate,
+ * gzip_crc.  Errors: bsk_global_error(). */
+int bsk_gzip_inflate_device(const void* d_comp, size_t n_comp, int device, size_t chunk_bytes, void** d_text, size_t* n_text);
+int bsk_gzip_load(int fd, int device, int threads, size_t chunk_bytes, void** d_text, size_t* n_text);
+int bsk_gzip_inflate_host(const void* comp, size_t n_comp, void* out, size_t cap, size_t* n_out, size_t chunk_bytes);
+void bsk_gzip_last_plan(uint64_t out[8]);
+/* For the tests: the finder's answer per chunk from the library's predicate on the host (cand[k] = S_k in bits, ~0: none, and for
+ * chunk 0; nchunks = ceil(n_comp / chunk_bytes)), and the predicate itself at one bit position (1: a non-final dynamic block
+ * can start there). */
+int bsk_selftest_gzip_find(const void* comp, size_t n_comp, size_t chunk_bytes, uint64_t* cand, size_t nchunks);
+int bsk_selftest_gzip_header_ok(const void* comp, size_t n_comp, uint64_t bit);
 /* ---- a BGZF file as record-aligned pieces (PARITY.md BGZF "pieces"; bgzf_stream.hpp, ops_bgzf_stream.hip) ----
  * bsk_bgzf_load holds the file and its text whole.  The reader hands the text out piece by piece instead -- every piece begins
  * on a record and holds about piece_text_bytes -- and holds neither: two buffers of compressed bytes (comp_chunk_bytes each,
