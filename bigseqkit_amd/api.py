@@ -115,21 +115,27 @@ def _adopt(d_text, n, device):
     return out
 
 
-def BgzfInflate(data, device=0):
-    """the text of a BGZF file: bytes or a CUDA uint8 tensor in, a CUDA uint8 tensor out, inflated on the device.
-    device=-1: bytes in, bytes out, the same decoder on host threads"""
+def _inflate(host, on_device, data, device, host_extra, device_extra):
+    """the double call of a host inflate (size, then fill), or the device call and its buffer adopted.  host_extra: what the
+    host entry point takes behind its output (threads, or chunk_bytes); device_extra: what the device's takes in front of it"""
     n_text = C.c_size_t()
     if device < 0:
         data = bytes(data)
-        check(lib.bsk_bgzf_inflate_host(data, len(data), None, 0, C.byref(n_text), 0))
+        check(host(data, len(data), None, 0, C.byref(n_text), *host_extra))
         buf = C.create_string_buffer(max(1, n_text.value))
-        check(lib.bsk_bgzf_inflate_host(data, len(data), buf, n_text.value, C.byref(n_text), 0))
+        check(host(data, len(data), buf, n_text.value, C.byref(n_text), *host_extra))
         return buf.raw[:n_text.value]
     keep, ptr, n = _device_input(data, device)
     d_text = C.c_void_p()
-    check(lib.bsk_bgzf_inflate_device(ptr, n, device, C.byref(d_text), C.byref(n_text)))
+    check(on_device(ptr, n, device, *device_extra, C.byref(d_text), C.byref(n_text)))
     del keep
     return _adopt(d_text, n_text.value, device)
+
+
+def BgzfInflate(data, device=0):
+    """the text of a BGZF file: bytes or a CUDA uint8 tensor in, a CUDA uint8 tensor out, inflated on the device.
+    device=-1: bytes in, bytes out, the same decoder on host threads"""
+    return _inflate(lib.bsk_bgzf_inflate_host, lib.bsk_bgzf_inflate_device, data, device, (0,), ())   # (0: the default number of threads)
 
 
 # ---- plain gzip input (include/bsk.h "plain gzip input"; PARITY.md GZIP)
@@ -137,18 +143,7 @@ def GzipInflate(data, device=0, chunk_bytes=0):
     """the text of a gzip file of any number of members: bytes or a CUDA uint8 tensor in, a CUDA uint8 tensor out, inflated on
     the device in speculative chunks of chunk_bytes (0: the library's choice).  device=-1: bytes in, bytes out, the same method
     with one host lane (chunk_bytes 0: one piece)"""
-    n_text = C.c_size_t()
-    if device < 0:
-        data = bytes(data)
-        check(lib.bsk_gzip_inflate_host(data, len(data), None, 0, C.byref(n_text), chunk_bytes))
-        buf = C.create_string_buffer(max(1, n_text.value))
-        check(lib.bsk_gzip_inflate_host(data, len(data), buf, n_text.value, C.byref(n_text), chunk_bytes))
-        return buf.raw[:n_text.value]
-    keep, ptr, n = _device_input(data, device)
-    d_text = C.c_void_p()
-    check(lib.bsk_gzip_inflate_device(ptr, n, device, chunk_bytes, C.byref(d_text), C.byref(n_text)))
-    del keep
-    return _adopt(d_text, n_text.value, device)
+    return _inflate(lib.bsk_gzip_inflate_host, lib.bsk_gzip_inflate_device, data, device, (chunk_bytes,), (chunk_bytes,))
 
 
 _PLAN_FIELDS = ("chunks", "with_candidate", "on_chain", "off_chain", "members", "text_bytes", "dropped_bytes", "chunk_bytes")
@@ -336,10 +331,8 @@ def ReadSeqFile(path, device=0, gzip=False):
         if kind == 0:
             return SeqFrame(_format_of(path, head[:1]), [head + f.read()])
         d_text, n_text = C.c_void_p(), C.c_size_t()
-        if kind == 2:
-            check(lib.bsk_gzip_load(f.fileno(), device, 0, 0, C.byref(d_text), C.byref(n_text)))
-        else:
-            check(lib.bsk_bgzf_load(f.fileno(), device, 0, C.byref(d_text), C.byref(n_text)))
+        load, extra = (lib.bsk_gzip_load, (0,)) if kind == 2 else (lib.bsk_bgzf_load, ())   # (gzip: chunk_bytes 0, the library's choice)
+        check(load(f.fileno(), device, 0, *extra, C.byref(d_text), C.byref(n_text)))
     t = _adopt(d_text, n_text.value, device)
     return SeqFrame(_format_of(path, bytes(t[:1].cpu().numpy().tobytes())), [t])
 

@@ -18,6 +18,7 @@
 #include "anchor.hpp"
 #include "ctx.hpp"
 #include "bgzf_stream.hpp"
+#include "codec_host.hpp"
 #include "ops_bgzf.hpp"
 #include "ops_bgzf_write.hpp"
 #include "ops_gzip.hpp"
@@ -122,6 +123,32 @@ int init_device(bsk_ctx* c) {
         HIP_TRY(c, hipMemset(c->d_vec, 0, len * sizeof(uint64_t)));
     }
     return BSK_OK;
+}
+
+// ---- the codec calls (BGZF, gzip) have no context: the text of a failure goes to bsk_global_error()
+// a shell without a context: call(err) returns a BSK_* code and leaves the text of a failure in err
+template <class Call>
+int shell(Call call) {
+    std::string err;
+    const int rc = call(err);
+    return rc == BSK_OK ? rc : fail_global(rc, err);
+}
+
+// the whole file of fd into the memory of the device, inflate(d_comp, size, err) there; codec: "bgzf" or "gzip"
+template <class Inflate>
+int load_compressed(int fd, int device, int threads, const std::string& codec, void** d_text, size_t* n_text, Inflate inflate) {
+    *d_text = nullptr;
+    *n_text = 0;
+    const off_t size = lseek(fd, 0, SEEK_END);
+    if (size < 0) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: " + codec + ": the file cannot be measured (a pipe goes through bsk_" + codec + "_inflate_host)");
+    void* d_comp = nullptr;
+    const int rc = bsk_shard_load(fd, 0, (size_t)size, device, threads, &d_comp);
+    if (rc != BSK_OK) return rc;
+    return shell([&](std::string& err) {
+        const int r = inflate(d_comp, (size_t)size, err);
+        hipFree(d_comp);
+        return r;
+    });
 }
 
 }  // namespace
@@ -705,33 +732,22 @@ int bsk_bgzf_probe(const void* head, size_t n) { return bgzf_probe(head, n); }
 
 int bsk_bgzf_inflate_device(const void* d_comp, size_t n_comp, int device, void** d_text, size_t* n_text) {
     if (!d_text || !n_text || (!d_comp && n_comp)) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bgzf: null argument");
-    std::string err;
-    const int rc = bgzf_inflate_device(d_comp, n_comp, device, d_text, n_text, nullptr, false, err);
-    return rc == BSK_OK ? rc : fail_global(rc, err);
+    return shell([&](std::string& err) { return bgzf_inflate_device(d_comp, n_comp, device, d_text, n_text, nullptr, false, err); });
 }
 
 int bsk_bgzf_load(int fd, int device, int threads, void** d_text, size_t* n_text) {
     if (!d_text || !n_text || fd < 0) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bgzf: bad arguments");
-    *d_text = nullptr;
-    *n_text = 0;
-    const off_t size = lseek(fd, 0, SEEK_END);
-    if (size < 0) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bgzf: the file cannot be measured (a pipe goes through bsk_bgzf_inflate_host)");
-    void* d_comp = nullptr;
-    int rc = bsk_shard_load(fd, 0, (size_t)size, device, threads, &d_comp);
-    if (rc != BSK_OK) return rc;
-    std::string err;
-    rc = bgzf_inflate_device(d_comp, (size_t)size, device, d_text, n_text, nullptr, false, err);
-    hipFree(d_comp);
-    return rc == BSK_OK ? rc : fail_global(rc, err);
+    return load_compressed(fd, device, threads, "bgzf", d_text, n_text, [&](const void* d_comp, size_t n, std::string& err) {
+        return bgzf_inflate_device(d_comp, n, device, d_text, n_text, nullptr, false, err);
+    });
 }
 
 int bsk_bgzf_blocks_device(const void* d_comp, size_t n_comp, int device, uint64_t* coff, uint32_t* csize, uint32_t* usize, size_t cap,
                            size_t* count) {
     if (!count || (!d_comp && n_comp) || (cap && (!coff || !csize || !usize))) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bgzf: null argument");
-    std::string err;
     BgzfIndex ix;
-    const int rc = bgzf_inflate_device(d_comp, n_comp, device, nullptr, nullptr, &ix, true, err);
-    if (rc != BSK_OK) return fail_global(rc, err);
+    const int rc = shell([&](std::string& err) { return bgzf_inflate_device(d_comp, n_comp, device, nullptr, nullptr, &ix, true, err); });
+    if (rc != BSK_OK) return rc;
     *count = ix.coff.size();
     for (size_t i = 0; i < ix.coff.size() && i < cap; ++i) {
         coff[i] = ix.coff[i];
@@ -743,39 +759,25 @@ int bsk_bgzf_blocks_device(const void* d_comp, size_t n_comp, int device, uint64
 
 int bsk_bgzf_inflate_host(const void* comp, size_t n_comp, void* out, size_t cap, size_t* n_out, int threads) {
     if (!n_out || (!comp && n_comp)) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bgzf: null argument");
-    std::string err;
-    const int rc = bgzf_inflate_host(comp, n_comp, out, cap, n_out, threads, err);
-    return rc == BSK_OK ? rc : fail_global(rc, err);
+    return shell([&](std::string& err) { return bgzf_inflate_host(comp, n_comp, out, cap, n_out, threads, err); });
 }
 
 // ---- plain gzip input (ops_gzip.hip, gzip_spec_dev.hpp): thin shells as for BGZF
 int bsk_gzip_inflate_device(const void* d_comp, size_t n_comp, int device, size_t chunk_bytes, void** d_text, size_t* n_text) {
     if (!d_text || !n_text || (!d_comp && n_comp)) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: gzip: null argument");
-    std::string err;
-    const int rc = gzip_inflate_device(d_comp, n_comp, device, chunk_bytes, d_text, n_text, err);
-    return rc == BSK_OK ? rc : fail_global(rc, err);
+    return shell([&](std::string& err) { return gzip_inflate_device(d_comp, n_comp, device, chunk_bytes, d_text, n_text, err); });
 }
 
 int bsk_gzip_load(int fd, int device, int threads, size_t chunk_bytes, void** d_text, size_t* n_text) {
     if (!d_text || !n_text || fd < 0) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: gzip: bad arguments");
-    *d_text = nullptr;
-    *n_text = 0;
-    const off_t size = lseek(fd, 0, SEEK_END);
-    if (size < 0) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: gzip: the file cannot be measured (a pipe goes through bsk_gzip_inflate_host)");
-    void* d_comp = nullptr;
-    int rc = bsk_shard_load(fd, 0, (size_t)size, device, threads, &d_comp);
-    if (rc != BSK_OK) return rc;
-    std::string err;
-    rc = gzip_inflate_device(d_comp, (size_t)size, device, chunk_bytes, d_text, n_text, err);
-    hipFree(d_comp);
-    return rc == BSK_OK ? rc : fail_global(rc, err);
+    return load_compressed(fd, device, threads, "gzip", d_text, n_text, [&](const void* d_comp, size_t n, std::string& err) {
+        return gzip_inflate_device(d_comp, n, device, chunk_bytes, d_text, n_text, err);
+    });
 }
 
 int bsk_gzip_inflate_host(const void* comp, size_t n_comp, void* out, size_t cap, size_t* n_out, size_t chunk_bytes) {
     if (!n_out || (!comp && n_comp)) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: gzip: null argument");
-    std::string err;
-    const int rc = gzip_inflate_host(comp, n_comp, out, cap, n_out, chunk_bytes, err);
-    return rc == BSK_OK ? rc : fail_global(rc, err);
+    return shell([&](std::string& err) { return gzip_inflate_host(comp, n_comp, out, cap, n_out, chunk_bytes, err); });
 }
 
 void bsk_gzip_last_plan(uint64_t out[8]) {
@@ -793,35 +795,33 @@ int bsk_selftest_gzip_header_ok(const void* comp, size_t n_comp, uint64_t bit) {
 
 // ---- the piece reader of a BGZF file (bgzf_stream.hpp, ops_bgzf_stream.hip): thin shells again
 struct bsk_bgzf_reader { BgzfPieceReader* r; };
+static int reader_result(bsk_bgzf_reader* r, int rc) { return rc == BSK_OK ? rc : fail_global(rc, r->r->error()); }
 
 int bsk_bgzf_reader_open(int fd, int device, int format, size_t piece_text_bytes, size_t lookahead_bytes, size_t comp_chunk_bytes,
                          bsk_bgzf_reader** out) {
     if (!out || (format != BSK_FORMAT_FASTA && format != BSK_FORMAT_FASTQ)) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bgzf: bad arguments");
     *out = nullptr;
-    int rc = BSK_OK;
-    std::string err;
-    BgzfPieceReader* r = bgzf_reader_open(fd, device, format, piece_text_bytes, lookahead_bytes, comp_chunk_bytes, &rc, err);
-    if (!r) return fail_global(rc, err);
-    *out = new bsk_bgzf_reader{r};
-    return BSK_OK;
+    return shell([&](std::string& err) {
+        int rc = BSK_OK;
+        BgzfPieceReader* r = bgzf_reader_open(fd, device, format, piece_text_bytes, lookahead_bytes, comp_chunk_bytes, &rc, err);
+        if (r) *out = new bsk_bgzf_reader{r};
+        return r ? BSK_OK : rc;
+    });
 }
 
 int bsk_bgzf_reader_next(bsk_bgzf_reader* r, const void** ptr, size_t* n, uint64_t* voff_lo, uint64_t* voff_hi, int* last) {
     if (!r || !ptr || !n || !voff_lo || !voff_hi || !last) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bgzf: null argument");
-    const int rc = r->r->next(ptr, n, voff_lo, voff_hi, last);
-    return rc == BSK_OK ? rc : fail_global(rc, r->r->error());
+    return reader_result(r, r->r->next(ptr, n, voff_lo, voff_hi, last));
 }
 
 int bsk_bgzf_reader_seek(bsk_bgzf_reader* r, uint64_t voff) {
     if (!r) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bgzf: null argument");
-    const int rc = r->r->seek(voff);
-    return rc == BSK_OK ? rc : fail_global(rc, r->r->error());
+    return reader_result(r, r->r->seek(voff));
 }
 
 int bsk_bgzf_reader_piece(bsk_bgzf_reader* r, uint64_t voff_lo, uint64_t voff_hi, const void** ptr, size_t* n) {
     if (!r || !ptr || !n) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bgzf: null argument");
-    const int rc = r->r->piece(voff_lo, voff_hi, ptr, n);
-    return rc == BSK_OK ? rc : fail_global(rc, r->r->error());
+    return reader_result(r, r->r->piece(voff_lo, voff_hi, ptr, n));
 }
 
 void bsk_bgzf_reader_close(bsk_bgzf_reader* r) {
@@ -832,9 +832,7 @@ void bsk_bgzf_reader_close(bsk_bgzf_reader* r) {
 
 int bsk_selftest_bgzf_stream_cut(const void* text, size_t n, size_t from, int format, int device, uint64_t* cut) {
     if (!cut || (!text && n)) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bgzf: null argument");
-    std::string err;
-    const int rc = bgzf_stream_cut_run((const uint8_t*)text, n, from, format, device, cut, err);
-    return rc == BSK_OK ? rc : fail_global(rc, err);
+    return shell([&](std::string& err) { return bgzf_stream_cut_run((const uint8_t*)text, n, from, format, device, cut, err); });
 }
 
 // ---- BGZF output (ops_bgzf_write.hip): thin shells as for the input
@@ -842,16 +840,12 @@ size_t bsk_bgzf_deflate_bound(size_t n_text, uint32_t block_text_bytes) { return
 
 int bsk_bgzf_deflate_device(const void* d_text, size_t n_text, int device, uint32_t block_text_bytes, int eof, void** d_comp, size_t* n_comp) {
     if (!d_comp || !n_comp || (!d_text && n_text)) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bgzf: null argument");
-    std::string err;
-    const int rc = bgzf_deflate_device(d_text, n_text, device, block_text_bytes, eof != 0, d_comp, n_comp, err);
-    return rc == BSK_OK ? rc : fail_global(rc, err);
+    return shell([&](std::string& err) { return bgzf_deflate_device(d_text, n_text, device, block_text_bytes, eof != 0, d_comp, n_comp, err); });
 }
 
 int bsk_bgzf_deflate_host(const void* text, size_t n, uint32_t block_text_bytes, int eof, void* out, size_t cap, size_t* n_out, int threads) {
     if (!n_out || (!text && n)) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bgzf: null argument");
-    std::string err;
-    const int rc = bgzf_deflate_host(text, n, block_text_bytes, eof != 0, out, cap, n_out, threads, err);
-    return rc == BSK_OK ? rc : fail_global(rc, err);
+    return shell([&](std::string& err) { return bgzf_deflate_host(text, n, block_text_bytes, eof != 0, out, cap, n_out, threads, err); });
 }
 
 uint32_t bsk_selftest_bgzf_crc(const void* data, size_t n) { return n <= 65536 ? bgzf_crc_chunked((const uint8_t*)data, (uint32_t)n, 1024) : 0; }
@@ -2159,8 +2153,7 @@ int bsk_event_destroy(void* ev) {
 int bsk_profile_enable(bsk_ctx* c, int on) {
     if (!c) return BSK_ERR_INVALID_ARG;
     c->profile = on != 0;
-    bgzf_profile_enable(on != 0);  // (the BGZF calls have no context: their stages are the process's)
-    bgzf_write_profile_enable(on != 0);
+    codec_profile_enable(on != 0);  // (the codec calls have no context: their stages are the process's)
     return BSK_OK;
 }
 
@@ -2200,8 +2193,7 @@ int bsk_profile_dump(bsk_ctx* c, char* buf, size_t cap) {
         out += kv.first;
         out += num;
     }
-    out += bgzf_profile_text();  // bgzf_find, bgzf_sizes, bgzf_inflate, bgzf_stream_cut
-    out += bgzf_write_profile_text();  // bgzf_deflate, bgzf_pack
+    out += codec_profile_text();  // bgzf_find, bgzf_sizes, bgzf_inflate, bgzf_stream_cut, bgzf_deflate, bgzf_pack, gzip_*
     if (c->translate_stream_fallbacks) {  // (not a stage: how often the one-pass translate did not fit and the tables ran instead)
         char num[96];
         snprintf(num, sizeof num, "translate_stream_fallback=0.000000/%llu;", (unsigned long long)c->translate_stream_fallbacks);
@@ -2223,8 +2215,7 @@ int bsk_profile_reset(bsk_ctx* c) {
     uint64_t l;
     bsk_profile_read(c, "", &d, &l);
     c->prof.clear();
-    bgzf_profile_reset();
-    bgzf_write_profile_reset();
+    codec_profile_reset();
     c->hg_indexed_bytes = 0;
     return BSK_OK;
 }

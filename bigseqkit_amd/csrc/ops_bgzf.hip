@@ -11,13 +11,11 @@
 #include <algorithm>
 #include <atomic>
 #include <cstring>
-#include <map>
 #include <memory>
-#include <mutex>
-#include <thread>
 
 #include "../../include/bsk.h"
 #include "bgzf_inflate_dev.hpp"
+#include "codec_host.hpp"
 #include "index.hpp"  // launch_scan_u32
 #include "ops_bgzf.hpp"
 
@@ -172,40 +170,6 @@ __global__ __launch_bounds__(256) void k_bgzf_desc(uint64_t nb, const uint64_t* 
 
 // ---- host side
 
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 1); }
-    template <class T> T* as() const { return (T*)p; }
-};
-
-std::mutex g_prof_mu;
-bool g_prof_on = false;
-struct Stage { double ms = 0; uint64_t launches = 0; };
-std::map<std::string, Stage> g_prof;
-
-struct StageTimer {
-    const char* name;
-    hipEvent_t a = nullptr, b = nullptr;
-    bool on;
-    explicit StageTimer(const char* nm) : name(nm) {
-        { std::lock_guard<std::mutex> g(g_prof_mu); on = g_prof_on; }
-        if (on) on = hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess && hipEventRecord(a, nullptr) == hipSuccess;
-    }
-    void stop() {
-        if (!on || !a) return;
-        float ms = 0;
-        if (hipEventRecord(b, nullptr) != hipSuccess || hipEventSynchronize(b) != hipSuccess || hipEventElapsedTime(&ms, a, b) != hipSuccess) ms = 0;
-        (void)hipEventDestroy(a);
-        (void)hipEventDestroy(b);
-        a = nullptr;
-        std::lock_guard<std::mutex> g(g_prof_mu);
-        g_prof[name].ms += ms;
-        g_prof[name].launches += 1;
-    }
-    ~StageTimer() { stop(); }
-};
-
 std::string where(uint64_t block, uint64_t off) { return "libbsk: bgzf: block " + std::to_string(block) + " at offset " + std::to_string(off) + ": "; }
 
 // The chain of blocks from offset 0.  fetch(off, len, dst) brings bytes of the file; known(off, &h) answers from the list of
@@ -252,33 +216,7 @@ int decode_error(const BgzfIndex& ix, uint64_t packed, std::string& err) {
     return BSK_ERR_FORMAT;
 }
 
-#define BGZF_HIP(x)                                                                                                      \
-    do {                                                                                                                 \
-        const hipError_t e_ = (x);                                                                                       \
-        if (e_ != hipSuccess) { err = std::string("libbsk: bgzf: ") + hipGetErrorString(e_) + " (" #x ")"; return BSK_ERR_HIP; } \
-    } while (0)
-
 }  // namespace
-
-void bgzf_profile_enable(bool on) { std::lock_guard<std::mutex> g(g_prof_mu); g_prof_on = on; }
-void bgzf_profile_reset() { std::lock_guard<std::mutex> g(g_prof_mu); g_prof.clear(); }
-std::string bgzf_profile_text() {
-    std::lock_guard<std::mutex> g(g_prof_mu);
-    std::string out;
-    for (auto& kv : g_prof) {
-        char num[96];
-        snprintf(num, sizeof num, "=%.6f/%llu;", kv.second.ms, (unsigned long long)kv.second.launches);
-        out += kv.first + num;
-    }
-    return out;
-}
-
-bool bgzf_profile_on() { std::lock_guard<std::mutex> g(g_prof_mu); return g_prof_on; }
-void bgzf_profile_add(const char* stage, double ms) {
-    std::lock_guard<std::mutex> g(g_prof_mu);
-    g_prof[stage].ms += ms;
-    g_prof[stage].launches += 1;
-}
 
 void bgzf_crc_matrix(uint32_t mat[32]) { bgzf::crc_advance_matrix(mat, WaveLane::CRC_CHUNK); }
 
@@ -315,48 +253,41 @@ int bgzf_inflate_device(const void* d_comp_, size_t n, int device, void** d_text
                         std::string& err) {
     if (d_text) *d_text = nullptr;
     if (n_text) *n_text = 0;
-    int have = 0;
-    if (hipGetDeviceCount(&have) != hipSuccess || have <= 0) { err = "libbsk: no HIP device visible"; return BSK_ERR_NO_DEVICE; }
-    if (device < 0 || device >= have) { err = "libbsk: device " + std::to_string(device) + " is not visible"; return BSK_ERR_NO_DEVICE; }
-    BGZF_HIP(hipSetDevice(device));
+    if (const int rc = select_device(device, kBgzf, err)) return rc;
     BgzfIndex local;
     BgzfIndex& ix = index ? *index : local;
     ix = BgzfIndex();
     if (n == 0) {
-        if (!index_only) BGZF_HIP(hipMalloc(d_text, 1));
+        if (!index_only) CODEC_HIP(kBgzf, hipMalloc(d_text, 1));
         return BSK_OK;
     }
     const uint8_t* d_comp = (const uint8_t*)d_comp_;
     DevBuf aligned;  // (the kernels load 16 and 8 bytes at a time from multiples of 16 and 8 of the buffer)
-    if ((uintptr_t)d_comp & 15u) {
-        BGZF_HIP(aligned.alloc(n));
-        BGZF_HIP(hipMemcpy(aligned.p, d_comp, n, hipMemcpyDeviceToDevice));
-        d_comp = aligned.as<uint8_t>();
-    }
+    if (const int rc = align_input(d_comp, n, aligned, kBgzf, err)) return rc;
     // ---- the candidates
     std::vector<uint64_t> cpos;
     std::vector<uint32_t> cinfo;
     {
-        StageTimer T("bgzf_find");
+        CodecStage T("bgzf_find");
         uint64_t cap = n / 256 + 4096;
         for (int turn = 0; turn < 2; ++turn) {  // (a file of tiny blocks has more headers than the first list holds: once more, to size)
             DevBuf list;
-            BGZF_HIP(list.alloc(cap * 12 + 16));
+            CODEC_HIP(kBgzf, list.alloc(cap * 12 + 16));
             unsigned long long* d_count = list.as<unsigned long long>();
             uint64_t* d_pos = list.as<uint64_t>() + 2;
             uint32_t* d_info = (uint32_t*)(d_pos + cap);
-            BGZF_HIP(hipMemsetAsync(d_count, 0, 8, nullptr));
+            CODEC_HIP(kBgzf, hipMemsetAsync(d_count, 0, 8, nullptr));
             const uint64_t threads = (n + 15) / 16;
             hipLaunchKernelGGL(k_bgzf_find, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, nullptr, d_comp, (uint64_t)n, d_pos, d_info, cap, d_count);
-            BGZF_HIP(hipGetLastError());
+            CODEC_HIP(kBgzf, hipGetLastError());
             unsigned long long count = 0;
-            BGZF_HIP(hipMemcpy(&count, d_count, 8, hipMemcpyDeviceToHost));
+            CODEC_HIP(kBgzf, hipMemcpy(&count, d_count, 8, hipMemcpyDeviceToHost));
             if (count > cap) { cap = count; continue; }
             cpos.resize(count);
             cinfo.resize(count);
             if (count) {
-                BGZF_HIP(hipMemcpy(cpos.data(), d_pos, count * 8, hipMemcpyDeviceToHost));
-                BGZF_HIP(hipMemcpy(cinfo.data(), d_info, count * 4, hipMemcpyDeviceToHost));
+                CODEC_HIP(kBgzf, hipMemcpy(cpos.data(), d_pos, count * 8, hipMemcpyDeviceToHost));
+                CODEC_HIP(kBgzf, hipMemcpy(cinfo.data(), d_info, count * 4, hipMemcpyDeviceToHost));
             }
             break;
         }
@@ -385,46 +316,46 @@ int bgzf_inflate_device(const void* d_comp_, size_t n, int device, void** d_text
     const size_t a_coff = 0, a_ooff = a_coff + 8 * nb, a_tmp = a_ooff + 8 * (nb + 1), a_ctl = a_tmp + 8 * scan_words, a_csize = a_ctl + 16,
                  a_xlen = a_csize + 4 * nb, a_usize = a_xlen + 4 * nb, a_crc = a_usize + 4 * nb, a_mat = a_crc + 4 * nb, a_desc = (a_mat + 128 + 15) & ~(size_t)15,
                  a_end = a_desc + sizeof(BlockDesc) * nb;
-    BGZF_HIP(arena.alloc(a_end));
+    CODEC_HIP(kBgzf, arena.alloc(a_end));
     uint8_t* A = arena.as<uint8_t>();
     unsigned long long* d_status = (unsigned long long*)(A + a_ctl);
     const unsigned long long clean = ~0ull;
     uint32_t mat[32];
     bgzf::crc_advance_matrix(mat, WaveLane::CRC_CHUNK);
-    BGZF_HIP(hipMemcpy(A + a_coff, ix.coff.data(), 8 * nb, hipMemcpyHostToDevice));
-    BGZF_HIP(hipMemcpy(A + a_csize, ix.csize.data(), 4 * nb, hipMemcpyHostToDevice));
-    BGZF_HIP(hipMemcpy(A + a_xlen, ix.xlen.data(), 4 * nb, hipMemcpyHostToDevice));
-    BGZF_HIP(hipMemcpy(d_status, &clean, 8, hipMemcpyHostToDevice));
-    BGZF_HIP(hipMemcpy(A + a_mat, mat, 128, hipMemcpyHostToDevice));
+    CODEC_HIP(kBgzf, hipMemcpy(A + a_coff, ix.coff.data(), 8 * nb, hipMemcpyHostToDevice));
+    CODEC_HIP(kBgzf, hipMemcpy(A + a_csize, ix.csize.data(), 4 * nb, hipMemcpyHostToDevice));
+    CODEC_HIP(kBgzf, hipMemcpy(A + a_xlen, ix.xlen.data(), 4 * nb, hipMemcpyHostToDevice));
+    CODEC_HIP(kBgzf, hipMemcpy(d_status, &clean, 8, hipMemcpyHostToDevice));
+    CODEC_HIP(kBgzf, hipMemcpy(A + a_mat, mat, 128, hipMemcpyHostToDevice));
     uint64_t total = 0;
     unsigned long long status = clean;
     {
-        StageTimer T("bgzf_sizes");
+        CodecStage T("bgzf_sizes");
         hipLaunchKernelGGL(k_bgzf_sizes, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, nullptr, d_comp, (const uint64_t*)(A + a_coff),
                            (const uint32_t*)(A + a_csize), nb, (uint32_t*)(A + a_usize), (uint32_t*)(A + a_crc), d_status);
-        BGZF_HIP(hipGetLastError());
-        BGZF_HIP(launch_scan_u32((const uint32_t*)(A + a_usize), (uint64_t*)(A + a_ooff), nb, (uint64_t*)(A + a_tmp), nullptr));
-        BGZF_HIP(hipMemcpy(&total, A + a_ooff + 8 * nb, 8, hipMemcpyDeviceToHost));
-        BGZF_HIP(hipMemcpy(&status, d_status, 8, hipMemcpyDeviceToHost));
+        CODEC_HIP(kBgzf, hipGetLastError());
+        CODEC_HIP(kBgzf, launch_scan_u32((const uint32_t*)(A + a_usize), (uint64_t*)(A + a_ooff), nb, (uint64_t*)(A + a_tmp), nullptr));
+        CODEC_HIP(kBgzf, hipMemcpy(&total, A + a_ooff + 8 * nb, 8, hipMemcpyDeviceToHost));
+        CODEC_HIP(kBgzf, hipMemcpy(&status, d_status, 8, hipMemcpyDeviceToHost));
     }
     if (status != clean) return decode_error(ix, status, err);
     if (index) {
         ix.usize.resize(nb);
-        BGZF_HIP(hipMemcpy(ix.usize.data(), A + a_usize, 4 * nb, hipMemcpyDeviceToHost));
+        CODEC_HIP(kBgzf, hipMemcpy(ix.usize.data(), A + a_usize, 4 * nb, hipMemcpyDeviceToHost));
     }
     if (index_only) return BSK_OK;
     // ---- the text
     DevBuf text;
-    BGZF_HIP(text.alloc(total));
+    CODEC_HIP(kBgzf, text.alloc(total));
     {
-        StageTimer T("bgzf_inflate");
+        CodecStage T("bgzf_inflate");
         hipLaunchKernelGGL(k_bgzf_desc, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, nullptr, nb, (const uint64_t*)(A + a_coff),
                            (const uint32_t*)(A + a_csize), (const uint32_t*)(A + a_xlen), (const uint32_t*)(A + a_usize),
                            (const uint32_t*)(A + a_crc), (const uint64_t*)(A + a_ooff), (BlockDesc*)(A + a_desc));
         hipLaunchKernelGGL(k_bgzf_inflate, dim3((unsigned)nb), dim3(64), 0, nullptr, d_comp, (uint64_t)n, (const BlockDesc*)(A + a_desc),
                            text.as<uint8_t>(), (const uint32_t*)(A + a_mat), d_status);
-        BGZF_HIP(hipGetLastError());
-        BGZF_HIP(hipMemcpy(&status, d_status, 8, hipMemcpyDeviceToHost));
+        CODEC_HIP(kBgzf, hipGetLastError());
+        CODEC_HIP(kBgzf, hipMemcpy(&status, d_status, 8, hipMemcpyDeviceToHost));
     }
     if (status != clean) return decode_error(ix, status, err);
     *d_text = text.p;
@@ -455,12 +386,12 @@ int bgzf_inflate_host(const void* comp_, size_t n, void* out_, size_t cap, size_
     if (n_out) *n_out = (size_t)ooff[nb];
     if (cap == 0) return BSK_OK;
     if (cap < ooff[nb] || !out) { err = "libbsk: bgzf: the output buffer holds " + std::to_string(cap) + " bytes, the text has " + std::to_string(ooff[nb]); return BSK_ERR_CAPACITY; }
-    std::atomic<uint64_t> next{0}, bad{~0ull};
-    auto work = [&]() {
+    std::atomic<uint64_t> bad{~0ull};
+    run_workers(threads, nb, [&](auto next) {
         std::unique_ptr<BgzfLds> S(new BgzfLds);
         memset(S->crc_mat, 0, sizeof S->crc_mat);  // (one chunk per block on the host: never applied)
         for (;;) {
-            const uint64_t i = next.fetch_add(1);
+            const uint64_t i = next();
             if (i >= nb) break;
             const uint8_t* t = comp + ix.coff[i] + ix.csize[i] - 8;
             const uint32_t want = t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
@@ -473,12 +404,7 @@ int bgzf_inflate_host(const void* comp_, size_t n, void* out_, size_t cap, size_
                 while (mine < seen && !bad.compare_exchange_weak(seen, mine)) {}
             }
         }
-    };
-    const int T = (int)std::min<uint64_t>((uint64_t)std::max(1, std::min(threads > 0 ? threads : 8, 64)), std::max<uint64_t>(nb, 1));
-    std::vector<std::thread> pool;
-    for (int t = 1; t < T; ++t) pool.emplace_back(work);
-    work();
-    for (auto& t : pool) t.join();
+    });
     if (bad.load() != ~0ull) return decode_error(ix, bad.load(), err);
     return BSK_OK;
 }

@@ -38,13 +38,6 @@ struct BgzfBlockDesc {
 int bgzf_launch_inflate(const void* d_comp, uint64_t n, const BgzfBlockDesc* d_desc, uint64_t nb, void* d_text, const uint32_t* d_mat,
                         unsigned long long* d_status, void* stream);
 void bgzf_crc_matrix(uint32_t mat[32]);
-
-// stages for bsk_profile_dump: "bgzf_find", "bgzf_sizes", "bgzf_inflate", and of the reader "bgzf_stream_cut" (process-wide:
-// these calls have no context)
-void bgzf_profile_enable(bool on);
-void bgzf_profile_reset();
-std::string bgzf_profile_text();  // "name=ms/launches;" per stage that ran
-bool bgzf_profile_on();
-void bgzf_profile_add(const char* stage, double ms);  // (the reader times its launches on its own stream)
+// (stages for bsk_profile_dump, through codec_host.hpp: "bgzf_find", "bgzf_sizes", "bgzf_inflate", and of the reader "bgzf_stream_cut")
 
 }  // namespace bsk

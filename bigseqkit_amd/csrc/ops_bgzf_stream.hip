@@ -15,6 +15,7 @@
 #include <sys/stat.h>
 
 #include "bgzf_stream.hpp"
+#include "codec_host.hpp"
 
 namespace bsk {
 namespace {
@@ -25,37 +26,9 @@ __global__ __launch_bounds__(64) void k_bgzf_stream_cut(const uint8_t* __restric
     *res = stream_cut(buf, n, from, format);
 }
 
-#define STREAM_HIP(x)                                                                                              \
-    do {                                                                                                           \
-        const hipError_t e_ = (x);                                                                                 \
-        if (e_ != hipSuccess) { err = std::string("libbsk: bgzf: ") + hipGetErrorString(e_) + " (" #x ")"; return BSK_ERR_HIP; } \
-    } while (0)
-
 // the look-behind of find_fastq_cut (fastq_multiline_prev_agrees: 8 MiB) and a margin, so that a copy that begins there is read
 // as the whole window is
 constexpr uint64_t CUT_BACK = (8ull << 20) + 64;
-
-struct Timed {  // one stage of bsk_profile_dump, timed on the reader's stream
-    const char* name;
-    hipStream_t st;
-    hipEvent_t a = nullptr, b = nullptr;
-    Timed(const char* nm, hipStream_t s) : name(nm), st(s) {
-        if (!bgzf_profile_on()) return;
-        if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess || hipEventRecord(a, st) != hipSuccess) drop();
-    }
-    void drop() {
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-        a = b = nullptr;
-    }
-    void stop() {  // (the caller has synchronised the stream or does so here)
-        if (!a) return;
-        float ms = 0;
-        if (hipEventRecord(b, st) == hipSuccess && hipEventSynchronize(b) == hipSuccess && hipEventElapsedTime(&ms, a, b) == hipSuccess) bgzf_profile_add(name, ms);
-        drop();
-    }
-    ~Timed() { drop(); }
-};
 
 struct BgzfDeviceBackend : BgzfStreamBackend {
     int device;
@@ -94,25 +67,22 @@ struct BgzfDeviceBackend : BgzfStreamBackend {
     uint64_t* d_cut() const { return (uint64_t*)(d_small + 136); }
 
     int open(size_t chunk_bytes, size_t text_cap_) override {
-        int have = 0;
-        if (hipGetDeviceCount(&have) != hipSuccess || have <= 0) { err = "libbsk: no HIP device visible"; return BSK_ERR_NO_DEVICE; }
-        if (device >= have) { err = "libbsk: device " + std::to_string(device) + " is not visible"; return BSK_ERR_NO_DEVICE; }
-        STREAM_HIP(hipSetDevice(device));
-        STREAM_HIP(hipStreamCreateWithFlags(&sx, hipStreamNonBlocking));
-        STREAM_HIP(hipStreamCreateWithFlags(&sc, hipStreamNonBlocking));
-        STREAM_HIP(hipEventCreateWithFlags(&ev_reuse, hipEventDisableTiming));
+        if (const int rc = select_device(device, kBgzf, err)) return rc;  // (device -1, the host backend, never comes here)
+        CODEC_HIP(kBgzf, hipStreamCreateWithFlags(&sx, hipStreamNonBlocking));
+        CODEC_HIP(kBgzf, hipStreamCreateWithFlags(&sc, hipStreamNonBlocking));
+        CODEC_HIP(kBgzf, hipEventCreateWithFlags(&ev_reuse, hipEventDisableTiming));
         for (int k = 0; k < 2; ++k) {
-            STREAM_HIP(hipHostMalloc((void**)&h_comp[k], FRONT + chunk_bytes, hipHostMallocDefault));
-            STREAM_HIP(hipMalloc((void**)&d_comp[k], FRONT + chunk_bytes));
-            STREAM_HIP(hipMalloc((void**)&d_text[k], text_cap_));
+            CODEC_HIP(kBgzf, hipHostMalloc((void**)&h_comp[k], FRONT + chunk_bytes, hipHostMallocDefault));
+            CODEC_HIP(kBgzf, hipMalloc((void**)&d_comp[k], FRONT + chunk_bytes));
+            CODEC_HIP(kBgzf, hipMalloc((void**)&d_text[k], text_cap_));
             cap_text[k] = text_cap_;
         }
-        STREAM_HIP(hipMalloc((void**)&d_small, 256));
-        STREAM_HIP(hipHostMalloc((void**)&h_small, 64, hipHostMallocDefault));
+        CODEC_HIP(kBgzf, hipMalloc((void**)&d_small, 256));
+        CODEC_HIP(kBgzf, hipHostMalloc((void**)&h_small, 64, hipHostMallocDefault));
         h_small[2] = ~0ull;
         uint32_t mat[32];
         bgzf_crc_matrix(mat);
-        STREAM_HIP(hipMemcpy(d_small, mat, 128, hipMemcpyHostToDevice));
+        CODEC_HIP(kBgzf, hipMemcpy(d_small, mat, 128, hipMemcpyHostToDevice));
         return BSK_OK;
     }
     uint8_t* comp_host(int slot) override { return h_comp[slot]; }
@@ -143,27 +113,27 @@ struct BgzfDeviceBackend : BgzfStreamBackend {
         return BSK_OK;
     }
     int push_front(int slot, size_t left) override {
-        STREAM_HIP(hipMemcpyAsync(d_comp[slot] + FRONT - left, h_comp[slot] + FRONT - left, left, hipMemcpyHostToDevice, sx));
+        CODEC_HIP(kBgzf, hipMemcpyAsync(d_comp[slot] + FRONT - left, h_comp[slot] + FRONT - left, left, hipMemcpyHostToDevice, sx));
         return BSK_OK;
     }
     int inflate(int slot, size_t slot_bytes, const BgzfBlockDesc* d, size_t nb, int tbuf, uint64_t* bad) override {
         *bad = ~0ull;
         if (nb == 0) return BSK_OK;
         if (nb > cap_desc) {
-            STREAM_HIP(hipStreamSynchronize(sx));
-            if (d_desc) STREAM_HIP(hipFree(d_desc));
+            CODEC_HIP(kBgzf, hipStreamSynchronize(sx));
+            if (d_desc) CODEC_HIP(kBgzf, hipFree(d_desc));
             d_desc = nullptr;
             cap_desc = std::max<size_t>(nb, 2 * cap_desc);
-            STREAM_HIP(hipMalloc((void**)&d_desc, cap_desc * sizeof(BgzfBlockDesc)));
+            CODEC_HIP(kBgzf, hipMalloc((void**)&d_desc, cap_desc * sizeof(BgzfBlockDesc)));
         }
         for (size_t i = 0; i < nb; ++i)  // (the list is the host's own; still: nothing is launched that writes outside the buffer)
             if (d[i].coff + d[i].csize > slot_bytes || d[i].ooff + d[i].usize > cap_text[tbuf]) { err = "libbsk: bgzf: a block does not fit the reader's buffers"; return BSK_ERR_INVALID_ARG; }
-        Timed T("bgzf_inflate", sx);
-        STREAM_HIP(hipMemcpyAsync(d_desc, d, nb * sizeof(BgzfBlockDesc), hipMemcpyHostToDevice, sx));
-        STREAM_HIP(hipMemcpyAsync(d_status(), &h_small[2], 8, hipMemcpyHostToDevice, sx));
-        STREAM_HIP((hipError_t)bgzf_launch_inflate(d_comp[slot], slot_bytes, d_desc, nb, d_text[tbuf], d_mat(), d_status(), sx));
-        STREAM_HIP(hipMemcpyAsync(&h_small[0], d_status(), 8, hipMemcpyDeviceToHost, sx));
-        STREAM_HIP(hipStreamSynchronize(sx));
+        CodecStage T("bgzf_inflate", sx);
+        CODEC_HIP(kBgzf, hipMemcpyAsync(d_desc, d, nb * sizeof(BgzfBlockDesc), hipMemcpyHostToDevice, sx));
+        CODEC_HIP(kBgzf, hipMemcpyAsync(d_status(), &h_small[2], 8, hipMemcpyHostToDevice, sx));
+        CODEC_HIP(kBgzf, (hipError_t)bgzf_launch_inflate(d_comp[slot], slot_bytes, d_desc, nb, d_text[tbuf], d_mat(), d_status(), sx));
+        CODEC_HIP(kBgzf, hipMemcpyAsync(&h_small[0], d_status(), 8, hipMemcpyDeviceToHost, sx));
+        CODEC_HIP(kBgzf, hipStreamSynchronize(sx));
         T.stop();
         *bad = h_small[0];
         return BSK_OK;
@@ -171,13 +141,13 @@ struct BgzfDeviceBackend : BgzfStreamBackend {
     size_t text_cap(int tbuf) const override { return cap_text[tbuf]; }
     int text_grow(int tbuf, size_t cap, size_t keep) override {
         uint8_t* p = nullptr;
-        STREAM_HIP(hipMalloc((void**)&p, cap));
+        CODEC_HIP(kBgzf, hipMalloc((void**)&p, cap));
         if (keep) {
             const hipError_t e = hipMemcpyAsync(p, d_text[tbuf], std::min(keep, cap_text[tbuf]), hipMemcpyDeviceToDevice, sx);
-            if (e != hipSuccess) { (void)hipFree(p); STREAM_HIP(e); }
+            if (e != hipSuccess) { (void)hipFree(p); CODEC_HIP(kBgzf, e); }
         }
-        STREAM_HIP(hipStreamSynchronize(sx));
-        STREAM_HIP(hipFree(d_text[tbuf]));
+        CODEC_HIP(kBgzf, hipStreamSynchronize(sx));
+        CODEC_HIP(kBgzf, hipFree(d_text[tbuf]));
         d_text[tbuf] = p;
         cap_text[tbuf] = cap;
         return BSK_OK;
@@ -185,22 +155,22 @@ struct BgzfDeviceBackend : BgzfStreamBackend {
     const uint8_t* text(int tbuf) const override { return d_text[tbuf]; }
     int reuse(int) override {
         // (the operators that were handed the buffer's last piece run on the default stream, or on streams that it waits for)
-        STREAM_HIP(hipSetDevice(device));
-        STREAM_HIP(hipEventRecord(ev_reuse, nullptr));
-        STREAM_HIP(hipStreamWaitEvent(sx, ev_reuse, 0));
+        CODEC_HIP(kBgzf, hipSetDevice(device));
+        CODEC_HIP(kBgzf, hipEventRecord(ev_reuse, nullptr));
+        CODEC_HIP(kBgzf, hipStreamWaitEvent(sx, ev_reuse, 0));
         return BSK_OK;
     }
     int move(int from, size_t from_off, int to, size_t to_off, size_t n) override {
         if (from_off + n > cap_text[from] || to_off + n > cap_text[to]) { err = "libbsk: bgzf: the carried head does not fit the reader's buffers"; return BSK_ERR_INVALID_ARG; }
-        STREAM_HIP(hipMemcpyAsync(d_text[to] + to_off, d_text[from] + from_off, n, hipMemcpyDeviceToDevice, sx));
+        CODEC_HIP(kBgzf, hipMemcpyAsync(d_text[to] + to_off, d_text[from] + from_off, n, hipMemcpyDeviceToDevice, sx));
         return BSK_OK;
     }
     int cut_on_device(const uint8_t* d_buf, uint64_t n, uint64_t from, int format, uint64_t* cut) {
-        Timed T("bgzf_stream_cut", sx);
+        CodecStage T("bgzf_stream_cut", sx);
         hipLaunchKernelGGL(k_bgzf_stream_cut, dim3(1), dim3(64), 0, sx, d_buf, n, from, format, d_cut());
-        STREAM_HIP(hipGetLastError());
-        STREAM_HIP(hipMemcpyAsync(&h_small[1], d_cut(), 8, hipMemcpyDeviceToHost, sx));
-        STREAM_HIP(hipStreamSynchronize(sx));
+        CODEC_HIP(kBgzf, hipGetLastError());
+        CODEC_HIP(kBgzf, hipMemcpyAsync(&h_small[1], d_cut(), 8, hipMemcpyDeviceToHost, sx));
+        CODEC_HIP(kBgzf, hipStreamSynchronize(sx));
         T.stop();
         *cut = h_small[1];
         return BSK_OK;
@@ -217,14 +187,14 @@ struct BgzfDeviceBackend : BgzfStreamBackend {
         // declined, or no start: the host rule on a copy of the window
         const uint64_t lo = from > CUT_BACK ? from - CUT_BACK : 0;
         std::vector<uint8_t> h((size_t)(n - lo));
-        STREAM_HIP(hipMemcpyAsync(h.data(), d_text[tbuf] + FRONT + lo, h.size(), hipMemcpyDeviceToHost, sx));
-        STREAM_HIP(hipStreamSynchronize(sx));
+        CODEC_HIP(kBgzf, hipMemcpyAsync(h.data(), d_text[tbuf] + FRONT + lo, h.size(), hipMemcpyDeviceToHost, sx));
+        CODEC_HIP(kBgzf, hipStreamSynchronize(sx));
         const uint64_t r = find_fastq_cut(h.data(), h.size(), from - lo);
         *cut = r >= h.size() ? n : r + lo;
         return BSK_OK;
     }
     int sync() override {
-        STREAM_HIP(hipStreamSynchronize(sx));
+        CODEC_HIP(kBgzf, hipStreamSynchronize(sx));
         return BSK_OK;
     }
 };
@@ -258,7 +228,7 @@ int bgzf_stream_cut_run(const uint8_t* text, uint64_t n, uint64_t from, int form
     BgzfDeviceBackend B(device);
     const int rc = B.open(1, BgzfStreamBackend::FRONT + (size_t)n + 16);
     if (rc != BSK_OK) { err = B.err; return rc; }
-    STREAM_HIP(hipMemcpy(B.d_text[0] + BgzfStreamBackend::FRONT, text, (size_t)n, hipMemcpyHostToDevice));
+    CODEC_HIP(kBgzf, hipMemcpy(B.d_text[0] + BgzfStreamBackend::FRONT, text, (size_t)n, hipMemcpyHostToDevice));
     const int rc2 = B.cut_on_device(B.d_text[0] + BgzfStreamBackend::FRONT, n, from, format, cut);
     if (rc2 != BSK_OK) err = B.err;
     return rc2;

@@ -9,16 +9,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cstring>
-#include <map>
 #include <memory>
-#include <mutex>
-#include <thread>
 #include <vector>
 
 #include "../../include/bsk.h"
 #include "bgzf_deflate_dev.hpp"
+#include "codec_host.hpp"
 #include "index.hpp"  // launch_scan_u32
 #include "ops_bgzf_write.hpp"
 
@@ -143,44 +140,6 @@ __global__ __launch_bounds__(256) void k_bgzf_pack(const uint8_t* __restrict__ s
     if (t0 + t < sz) dst[t0 + t] = src[t0 + t];
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 1); }
-    template <class T> T* as() const { return (T*)p; }
-};
-
-std::mutex g_prof_mu;
-bool g_prof_on = false;
-struct Stage { double ms = 0; uint64_t launches = 0; };
-std::map<std::string, Stage> g_prof;
-
-struct StageTimer {
-    const char* name;
-    hipEvent_t a = nullptr, b = nullptr;
-    bool on;
-    explicit StageTimer(const char* nm) : name(nm) {
-        { std::lock_guard<std::mutex> g(g_prof_mu); on = g_prof_on; }
-        if (on) on = hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess && hipEventRecord(a, nullptr) == hipSuccess;
-    }
-    ~StageTimer() {
-        if (!on || !a) return;
-        float ms = 0;
-        if (hipEventRecord(b, nullptr) != hipSuccess || hipEventSynchronize(b) != hipSuccess || hipEventElapsedTime(&ms, a, b) != hipSuccess) ms = 0;
-        (void)hipEventDestroy(a);
-        (void)hipEventDestroy(b);
-        std::lock_guard<std::mutex> g(g_prof_mu);
-        g_prof[name].ms += ms;
-        g_prof[name].launches += 1;
-    }
-};
-
-#define BGZFW_HIP(x)                                                                                                     \
-    do {                                                                                                                 \
-        const hipError_t e_ = (x);                                                                                       \
-        if (e_ != hipSuccess) { err = std::string("libbsk: bgzf: ") + hipGetErrorString(e_) + " (" #x ")"; return BSK_ERR_HIP; } \
-    } while (0)
-
 bool block_bytes_ok(uint32_t& bt, std::string& err) {
     if (bt == 0) bt = bgzf::BLOCK_TEXT;
     if (bt <= bgzf::BLOCK_TEXT) return true;
@@ -189,19 +148,6 @@ bool block_bytes_ok(uint32_t& bt, std::string& err) {
 }
 
 }  // namespace
-
-void bgzf_write_profile_enable(bool on) { std::lock_guard<std::mutex> g(g_prof_mu); g_prof_on = on; }
-void bgzf_write_profile_reset() { std::lock_guard<std::mutex> g(g_prof_mu); g_prof.clear(); }
-std::string bgzf_write_profile_text() {
-    std::lock_guard<std::mutex> g(g_prof_mu);
-    std::string out;
-    for (auto& kv : g_prof) {
-        char num[96];
-        snprintf(num, sizeof num, "=%.6f/%llu;", kv.second.ms, (unsigned long long)kv.second.launches);
-        out += kv.first + num;
-    }
-    return out;
-}
 
 void bgzf_eof_block(uint8_t out[28]) {
     for (uint32_t i = 0; i < bgzf::EOF_BYTES; ++i) out[i] = bgzf::eof_byte(i);
@@ -217,19 +163,16 @@ int bgzf_deflate_device(const void* d_text, size_t n, int device, uint32_t bt, b
     *d_comp = nullptr;
     *n_comp = 0;
     if (!block_bytes_ok(bt, err)) return BSK_ERR_INVALID_ARG;
-    int have = 0;
-    if (hipGetDeviceCount(&have) != hipSuccess || have <= 0) { err = "libbsk: no HIP device visible"; return BSK_ERR_NO_DEVICE; }
-    if (device < 0 || device >= have) { err = "libbsk: device " + std::to_string(device) + " is not visible"; return BSK_ERR_NO_DEVICE; }
-    BGZFW_HIP(hipSetDevice(device));
+    if (const int rc = select_device(device, kBgzf, err)) return rc;
     const uint64_t nb = ((uint64_t)n + bt - 1) / bt;
     if (nb >> 31) { err = "libbsk: bgzf: more than 2^31 blocks in one call"; return BSK_ERR_UNSUPPORTED; }
     DevBuf comp;
     if (nb == 0) {
-        BGZFW_HIP(comp.alloc(bgzf::EOF_BYTES));
+        CODEC_HIP(kBgzf, comp.alloc(bgzf::EOF_BYTES));
         if (eof) {
             uint8_t e[28];
             bgzf_eof_block(e);
-            BGZFW_HIP(hipMemcpy(comp.p, e, sizeof e, hipMemcpyHostToDevice));
+            CODEC_HIP(kBgzf, hipMemcpy(comp.p, e, sizeof e, hipMemcpyHostToDevice));
             *n_comp = sizeof e;
         }
         *d_comp = comp.p;
@@ -237,7 +180,7 @@ int bgzf_deflate_device(const void* d_text, size_t n, int device, uint32_t bt, b
         return BSK_OK;
     }
     int cus = 0;
-    BGZFW_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    CODEC_HIP(kBgzf, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
     // The call goes in rounds of SLOTS_PER_WAVE blocks per resident wave, so the workspace -- the tokens of a wave, the slots the
     // members wait in until the scan says where they go -- is sized by the device, not by the text.  A text of one round (every
     // 64 MiB piece of a result is one) gets a buffer of exactly its size; a longer one a buffer of the bound, filled round by round.
@@ -248,11 +191,11 @@ int bgzf_deflate_device(const void* d_text, size_t n, int device, uint32_t bt, b
     const size_t a_stage = 0, a_toks = a_stage + (size_t)rb * slot, a_off = a_toks + (size_t)std::min<uint64_t>(rb, resident) * tok_stride * 4, a_tmp = a_off + 8 * (rb + 1),
                  a_sizes = a_tmp + 8 * scan_words, a_prm = (a_sizes + 4 * rb + 15) & ~(size_t)15, a_end = a_prm + sizeof(DeflateParams);
     DevBuf arena;
-    BGZFW_HIP(arena.alloc(a_end));
+    CODEC_HIP(kBgzf, arena.alloc(a_end));
     uint8_t* A = arena.as<uint8_t>();
     DeflateParams prm{nullptr, 0, (uint32_t*)(A + a_toks), A + a_stage, (uint32_t*)(A + a_sizes), bt, 0, tok_stride, slot, 0, {}};
     bgzf::crc_advance_matrix(prm.mat, WaveDeflateLane::CRC_CHUNK);
-    if (nb > rb) BGZFW_HIP(comp.alloc(bgzf_deflate_bound(n, bt)));
+    if (nb > rb) CODEC_HIP(kBgzf, comp.alloc(bgzf_deflate_bound(n, bt)));
     size_t bytes = 0;
     for (uint64_t b0 = 0; b0 < nb; b0 += rb) {
         const uint64_t nbr = std::min<uint64_t>(rb, nb - b0), t0 = b0 * bt;
@@ -262,24 +205,24 @@ int bgzf_deflate_device(const void* d_text, size_t n, int device, uint32_t bt, b
         prm.nb = (uint32_t)nbr;
         prm.waves = (uint32_t)std::min<uint64_t>(nbr, resident);
         // (a blocking copy on the null stream: the pack of the round before has read the slots by now)
-        BGZFW_HIP(hipMemcpy(A + a_prm, &prm, sizeof prm, hipMemcpyHostToDevice));
+        CODEC_HIP(kBgzf, hipMemcpy(A + a_prm, &prm, sizeof prm, hipMemcpyHostToDevice));
         uint64_t total = 0;
         {
-            StageTimer T("bgzf_deflate");
+            CodecStage T("bgzf_deflate");
             hipLaunchKernelGGL(k_bgzf_deflate, dim3(prm.waves), dim3(64), 0, nullptr, (const DeflateParams*)(A + a_prm));
-            BGZFW_HIP(hipGetLastError());
-            BGZFW_HIP(launch_scan_u32((const uint32_t*)(A + a_sizes), (uint64_t*)(A + a_off), nbr, (uint64_t*)(A + a_tmp), nullptr));
-            BGZFW_HIP(hipMemcpy(&total, A + a_off + 8 * nbr, 8, hipMemcpyDeviceToHost));
+            CODEC_HIP(kBgzf, hipGetLastError());
+            CODEC_HIP(kBgzf, launch_scan_u32((const uint32_t*)(A + a_sizes), (uint64_t*)(A + a_off), nbr, (uint64_t*)(A + a_tmp), nullptr));
+            CODEC_HIP(kBgzf, hipMemcpy(&total, A + a_off + 8 * nbr, 8, hipMemcpyDeviceToHost));
         }
         if (total > prm.n + nbr * bgzf::MEMBER_EXTRA) { err = "libbsk: bgzf: the encoder wrote more than its bound"; return BSK_ERR_HIP; }
         const bool tail = last && eof;
-        if (!comp.p) BGZFW_HIP(comp.alloc((size_t)total + (tail ? bgzf::EOF_BYTES : 0u)));
+        if (!comp.p) CODEC_HIP(kBgzf, comp.alloc((size_t)total + (tail ? bgzf::EOF_BYTES : 0u)));
         {
-            StageTimer T("bgzf_pack");
+            CodecStage T("bgzf_pack");
             hipLaunchKernelGGL(k_bgzf_pack, dim3((unsigned)(nbr + (tail ? 1u : 0u))), dim3(256), 0, nullptr, A + a_stage, slot, (const uint32_t*)(A + a_sizes),
                                (const uint64_t*)(A + a_off), nbr, comp.as<uint8_t>() + bytes);
-            BGZFW_HIP(hipGetLastError());
-            if (last) BGZFW_HIP(hipDeviceSynchronize());
+            CODEC_HIP(kBgzf, hipGetLastError());
+            if (last) CODEC_HIP(kBgzf, hipDeviceSynchronize());
         }
         bytes += (size_t)total + (tail ? bgzf::EOF_BYTES : 0u);
     }
@@ -298,8 +241,7 @@ int bgzf_deflate_host(const void* text_, size_t n, uint32_t bt, bool eof, void* 
     const uint32_t slot = bgzf::slot_bytes(bt);
     std::vector<uint8_t> stage((size_t)nb * slot);
     std::vector<uint32_t> sizes(nb);
-    std::atomic<uint64_t> next{0};
-    auto work = [&]() {
+    run_workers(threads, nb, [&](auto next) {
         std::unique_ptr<DeflateLds> S(new DeflateLds);
         memset(S->crc_mat, 0, sizeof S->crc_mat);  // (one chunk per block on the host: never applied)
         std::vector<uint32_t> toks(bt + 1u);
@@ -307,19 +249,14 @@ int bgzf_deflate_host(const void* text_, size_t n, uint32_t bt, bool eof, void* 
         bgzf::Deflater<bgzf::HostDeflateLane> D(io, *S);
         D.init();
         for (;;) {
-            const uint64_t b = next.fetch_add(1);
+            const uint64_t b = next();
             if (b >= nb) break;
             const uint64_t off = b * bt;
             io.text = text + off;
             io.out = stage.data() + b * slot;
             sizes[b] = D.run((uint32_t)(n - off < bt ? n - off : bt));
         }
-    };
-    const int T = (int)std::min<uint64_t>((uint64_t)std::max(1, std::min(threads > 0 ? threads : 8, 64)), std::max<uint64_t>(nb, 1));
-    std::vector<std::thread> pool;
-    for (int t = 1; t < T; ++t) pool.emplace_back(work);
-    work();
-    for (auto& t : pool) t.join();
+    });
     uint64_t total = eof ? bgzf::EOF_BYTES : 0u;
     for (uint64_t b = 0; b < nb; ++b) total += sizes[b];
     if (n_out) *n_out = (size_t)total;

@@ -20,10 +20,6 @@ int bgzf_deflate_host(const void* text, size_t n, uint32_t block_text_bytes, boo
                       std::string& err);
 // the EOF block
 void bgzf_eof_block(uint8_t out[28]);
-
-// stages for bsk_profile_dump: "bgzf_deflate", "bgzf_pack" (process-wide: these calls have no context)
-void bgzf_write_profile_enable(bool on);
-void bgzf_write_profile_reset();
-std::string bgzf_write_profile_text();  // "name=ms/launches;" per stage that ran
+// (stages for bsk_profile_dump, through codec_host.hpp: "bgzf_deflate", "bgzf_pack")
 
 }  // namespace bsk

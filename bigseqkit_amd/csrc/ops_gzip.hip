@@ -16,8 +16,8 @@
 #include <vector>
 
 #include "../../include/bsk.h"
+#include "codec_host.hpp"
 #include "gzip_spec_dev.hpp"
-#include "ops_bgzf.hpp"  // the process-wide stages of bsk_profile_dump
 #include "ops_gzip.hpp"
 
 namespace bsk {
@@ -243,40 +243,9 @@ __global__ __launch_bounds__(64) void k_gz_crc(const uint8_t* __restrict__ text,
 
 // ---- host side
 
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { release(); }
-    void release() { if (p) (void)hipFree(p); p = nullptr; }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 1); }
-    template <class T> T* as() const { return (T*)p; }
-};
-
-struct StageTimer {
-    const char* name;
-    hipEvent_t a = nullptr, b = nullptr;
-    bool on;
-    explicit StageTimer(const char* nm) : name(nm), on(bgzf_profile_on()) {
-        if (on) on = hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess && hipEventRecord(a, nullptr) == hipSuccess;
-    }
-    ~StageTimer() {
-        if (!on || !a) return;
-        float ms = 0;
-        if (hipEventRecord(b, nullptr) != hipSuccess || hipEventSynchronize(b) != hipSuccess || hipEventElapsedTime(&ms, a, b) != hipSuccess) ms = 0;
-        (void)hipEventDestroy(a);
-        (void)hipEventDestroy(b);
-        bgzf_profile_add(name, ms);
-    }
-};
-
 thread_local gz::Plan g_plan;
 
 int fail_code(int f) { return f == gz::FAIL_UNSUPPORTED ? BSK_ERR_UNSUPPORTED : BSK_ERR_FORMAT; }
-
-#define GZ_HIP(x)                                                                                                        \
-    do {                                                                                                                 \
-        const hipError_t e_ = (x);                                                                                       \
-        if (e_ != hipSuccess) { err = std::string("libbsk: gzip: ") + hipGetErrorString(e_) + " (" #x ")"; return BSK_ERR_HIP; } \
-    } while (0)
 
 }  // namespace
 
@@ -326,28 +295,21 @@ int gzip_inflate_device(const void* d_comp_, size_t n, int device, size_t chunk_
     *d_text = nullptr;
     *n_text = 0;
     g_plan = gz::Plan();
-    int have = 0;
-    if (hipGetDeviceCount(&have) != hipSuccess || have <= 0) { err = "libbsk: no HIP device visible"; return BSK_ERR_NO_DEVICE; }
-    if (device < 0 || device >= have) { err = "libbsk: device " + std::to_string(device) + " is not visible"; return BSK_ERR_NO_DEVICE; }
-    GZ_HIP(hipSetDevice(device));
+    if (const int rc = select_device(device, kGzip, err)) return rc;
     if (n == 0) {
-        GZ_HIP(hipMalloc(d_text, 1));
+        CODEC_HIP(kGzip, hipMalloc(d_text, 1));
         return BSK_OK;
     }
     const uint8_t* d_comp = (const uint8_t*)d_comp_;
     DevBuf aligned;  // (the kernels load 8 and 4 bytes at a time from multiples of 8 and 4 of the buffer)
-    if ((uintptr_t)d_comp & 15u) {
-        GZ_HIP(aligned.alloc(n));
-        GZ_HIP(hipMemcpy(aligned.p, d_comp, n, hipMemcpyDeviceToDevice));
-        d_comp = aligned.as<uint8_t>();
-    }
+    if (const int rc = align_input(d_comp, n, aligned, kGzip, err)) return rc;
     if (chunk_bytes == 0) {
         const char* e = getenv("BSK_GZIP_CHUNK_BYTES");
         if (e && *e) chunk_bytes = (size_t)strtoull(e, nullptr, 10);
     }
     if (chunk_bytes == 0) {
         hipDeviceProp_t prop;
-        GZ_HIP(hipGetDeviceProperties(&prop, device));
+        CODEC_HIP(kGzip, hipGetDeviceProperties(&prop, device));
         const uint64_t waves = 2ull * (uint64_t)std::max(1, prop.multiProcessorCount);  // (69 120 bytes of LDS a wave: two per CU)
         chunk_bytes = std::max<uint64_t>(n / (4 * waves), 256u << 10);
     }
@@ -358,27 +320,27 @@ int gzip_inflate_device(const void* d_comp_, size_t n, int device, size_t chunk_
     if (nchunks > 0x7FFFFFFFull) { err = "libbsk: gzip: " + std::to_string(nchunks) + " chunks of " + std::to_string(chunk_bytes) + " bytes are more than one launch takes; use larger chunks"; return BSK_ERR_UNSUPPORTED; }
     // ---- find and size
     DevBuf d_cand, d_res, d_geo;
-    GZ_HIP(d_cand.alloc(8 * nchunks));
-    GZ_HIP(d_geo.alloc(sizeof(gz::Geometry)));
+    CODEC_HIP(kGzip, d_cand.alloc(8 * nchunks));
+    CODEC_HIP(kGzip, d_geo.alloc(sizeof(gz::Geometry)));
     geo.cand = (const uint64_t*)d_cand.p;
-    GZ_HIP(hipMemcpy(d_geo.p, &geo, sizeof geo, hipMemcpyHostToDevice));
-    GZ_HIP(d_res.alloc(sizeof(ChunkResult) * nchunks));
-    GZ_HIP(hipMemset(d_cand.p, 0xFF, 8 * nchunks));
+    CODEC_HIP(kGzip, hipMemcpy(d_geo.p, &geo, sizeof geo, hipMemcpyHostToDevice));
+    CODEC_HIP(kGzip, d_res.alloc(sizeof(ChunkResult) * nchunks));
+    CODEC_HIP(kGzip, hipMemset(d_cand.p, 0xFF, 8 * nchunks));
     std::vector<uint64_t> cand(nchunks);
     std::vector<ChunkResult> res(nchunks);
     {
-        StageTimer T("gzip_find");
+        CodecStage T("gzip_find");
         if (nchunks > 1) {
             hipLaunchKernelGGL(k_gz_find, dim3((unsigned)(nchunks - 1)), dim3(256), 0, nullptr, d_comp, (uint64_t)n, (uint64_t)chunk_bytes, d_cand.as<uint64_t>());
-            GZ_HIP(hipGetLastError());
+            CODEC_HIP(kGzip, hipGetLastError());
         }
-        GZ_HIP(hipMemcpy(cand.data(), d_cand.p, 8 * nchunks, hipMemcpyDeviceToHost));
+        CODEC_HIP(kGzip, hipMemcpy(cand.data(), d_cand.p, 8 * nchunks, hipMemcpyDeviceToHost));
     }
     {
-        StageTimer T("gzip_size");
+        CodecStage T("gzip_size");
         hipLaunchKernelGGL(k_gz_size, dim3((unsigned)nchunks), dim3(64), 0, nullptr, d_comp, d_geo.as<gz::Geometry>(), d_res.as<ChunkResult>());
-        GZ_HIP(hipGetLastError());
-        GZ_HIP(hipMemcpy(res.data(), d_res.p, sizeof(ChunkResult) * nchunks, hipMemcpyDeviceToHost));
+        CODEC_HIP(kGzip, hipGetLastError());
+        CODEC_HIP(kGzip, hipMemcpy(res.data(), d_res.p, sizeof(ChunkResult) * nchunks, hipMemcpyDeviceToHost));
     }
     d_res.release();
     // ---- the chain
@@ -388,7 +350,7 @@ int gzip_inflate_device(const void* d_comp_, size_t n, int device, size_t chunk_
     const uint64_t total = g_plan.text, nchain = chain.size(), nmem = g_plan.members;
     {
         size_t free_b = 0, all_b = 0;
-        GZ_HIP(hipMemGetInfo(&free_b, &all_b));
+        CODEC_HIP(kGzip, hipMemGetInfo(&free_b, &all_b));
         const uint64_t need = 3 * total + nchain * gz::WIN + (64u << 20);
         if (need > free_b) {
             err = "libbsk: gzip: the text (" + std::to_string(total) + " bytes), its symbols (" + std::to_string(2 * total) + " bytes) and the input (" +
@@ -399,23 +361,23 @@ int gzip_inflate_device(const void* d_comp_, size_t n, int device, size_t chunk_
     std::vector<ChainDesc> desc(nchain);
     for (uint64_t i = 0; i < nchain; ++i) desc[i] = ChainDesc{chain[i].k, chain[i].text_off, chain[i].text, chain[i].member0, chain[i].marker_lo, chain[i].members};
     DevBuf d_chain, d_sym, d_mem, d_dres, d_W, d_text_buf, d_ctl;
-    GZ_HIP(d_chain.alloc(sizeof(ChainDesc) * nchain));
-    GZ_HIP(d_sym.alloc(2 * total + 32));
-    GZ_HIP(d_mem.alloc(sizeof(MemberRec) * nmem));
-    GZ_HIP(d_dres.alloc(sizeof(ChunkResult) * nchain));
-    GZ_HIP(d_W.alloc(nchain * gz::WIN));
-    GZ_HIP(d_text_buf.alloc(total));
-    GZ_HIP(d_ctl.alloc(8 + 128));
-    GZ_HIP(hipMemcpy(d_chain.p, desc.data(), sizeof(ChainDesc) * nchain, hipMemcpyHostToDevice));
+    CODEC_HIP(kGzip, d_chain.alloc(sizeof(ChainDesc) * nchain));
+    CODEC_HIP(kGzip, d_sym.alloc(2 * total + 32));
+    CODEC_HIP(kGzip, d_mem.alloc(sizeof(MemberRec) * nmem));
+    CODEC_HIP(kGzip, d_dres.alloc(sizeof(ChunkResult) * nchain));
+    CODEC_HIP(kGzip, d_W.alloc(nchain * gz::WIN));
+    CODEC_HIP(kGzip, d_text_buf.alloc(total));
+    CODEC_HIP(kGzip, d_ctl.alloc(8 + 128));
+    CODEC_HIP(kGzip, hipMemcpy(d_chain.p, desc.data(), sizeof(ChainDesc) * nchain, hipMemcpyHostToDevice));
     std::vector<ChunkResult> dres(nchain);
     std::vector<MemberRec> mem(nmem);
     {
-        StageTimer T("gzip_decode");
+        CodecStage T("gzip_decode");
         hipLaunchKernelGGL(k_gz_decode, dim3((unsigned)nchain), dim3(64), 0, nullptr, d_comp, d_geo.as<gz::Geometry>(), d_chain.as<ChainDesc>(),
                            d_sym.as<uint16_t>(), d_mem.as<MemberRec>(), d_dres.as<ChunkResult>());
-        GZ_HIP(hipGetLastError());
-        GZ_HIP(hipMemcpy(dres.data(), d_dres.p, sizeof(ChunkResult) * nchain, hipMemcpyDeviceToHost));
-        if (nmem) GZ_HIP(hipMemcpy(mem.data(), d_mem.p, sizeof(MemberRec) * nmem, hipMemcpyDeviceToHost));
+        CODEC_HIP(kGzip, hipGetLastError());
+        CODEC_HIP(kGzip, hipMemcpy(dres.data(), d_dres.p, sizeof(ChunkResult) * nchain, hipMemcpyDeviceToHost));
+        if (nmem) CODEC_HIP(kGzip, hipMemcpy(mem.data(), d_mem.p, sizeof(MemberRec) * nmem, hipMemcpyDeviceToHost));
     }
     for (uint64_t i = 0; i < nchain; ++i) {
         if (dres[i].err) return fail_code(gz::chunk_failure(dres[i], chain[i].member0, err));
@@ -428,42 +390,42 @@ int gzip_inflate_device(const void* d_comp_, size_t n, int device, size_t chunk_
     const unsigned long long clean = ~0ull;
     uint32_t mat[32];
     bgzf::crc_advance_matrix(mat, gz::CRC_CHUNK);
-    GZ_HIP(hipMemcpy(d_status, &clean, 8, hipMemcpyHostToDevice));
-    GZ_HIP(hipMemcpy(d_mat, mat, 128, hipMemcpyHostToDevice));
-    GZ_HIP(hipMemset(d_W.p, 0, gz::WIN));
+    CODEC_HIP(kGzip, hipMemcpy(d_status, &clean, 8, hipMemcpyHostToDevice));
+    CODEC_HIP(kGzip, hipMemcpy(d_mat, mat, 128, hipMemcpyHostToDevice));
+    CODEC_HIP(kGzip, hipMemset(d_W.p, 0, gz::WIN));
     {
-        StageTimer T("gzip_windows");
+        CodecStage T("gzip_windows");
         if (nchain > 1) {
             hipLaunchKernelGGL(k_gz_windows, dim3(1), dim3(1024), 0, nullptr, d_chain.as<ChainDesc>(), nchain, d_sym.as<uint16_t>(), d_W.as<uint8_t>());
-            GZ_HIP(hipGetLastError());
+            CODEC_HIP(kGzip, hipGetLastError());
         }
     }
     {
-        StageTimer T("gzip_translate");
+        CodecStage T("gzip_translate");
         if (total) {
             const uint64_t threads = (total + 15) / 16;
             hipLaunchKernelGGL(k_gz_translate, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, nullptr, d_chain.as<ChainDesc>(), nchain,
                                d_sym.as<uint16_t>(), d_W.as<uint8_t>(), d_text_buf.as<uint8_t>(), total, d_status);
-            GZ_HIP(hipGetLastError());
+            CODEC_HIP(kGzip, hipGetLastError());
         }
     }
     std::vector<gz::Piece> pieces;
     gz::crc_pieces(mem, pieces);
     std::vector<uint32_t> pcrc(pieces.size());
     {
-        StageTimer T("gzip_crc");
+        CodecStage T("gzip_crc");
         DevBuf d_pieces, d_pcrc;
-        GZ_HIP(d_pieces.alloc(sizeof(gz::Piece) * pieces.size()));
-        GZ_HIP(d_pcrc.alloc(4 * pieces.size()));
+        CODEC_HIP(kGzip, d_pieces.alloc(sizeof(gz::Piece) * pieces.size()));
+        CODEC_HIP(kGzip, d_pcrc.alloc(4 * pieces.size()));
         if (!pieces.empty()) {
-            GZ_HIP(hipMemcpy(d_pieces.p, pieces.data(), sizeof(gz::Piece) * pieces.size(), hipMemcpyHostToDevice));
+            CODEC_HIP(kGzip, hipMemcpy(d_pieces.p, pieces.data(), sizeof(gz::Piece) * pieces.size(), hipMemcpyHostToDevice));
             hipLaunchKernelGGL(k_gz_crc, dim3((unsigned)pieces.size()), dim3(64), 0, nullptr, d_text_buf.as<uint8_t>(), d_pieces.as<gz::Piece>(), d_mat,
                                d_pcrc.as<uint32_t>());
-            GZ_HIP(hipGetLastError());
-            GZ_HIP(hipMemcpy(pcrc.data(), d_pcrc.p, 4 * pieces.size(), hipMemcpyDeviceToHost));
+            CODEC_HIP(kGzip, hipGetLastError());
+            CODEC_HIP(kGzip, hipMemcpy(pcrc.data(), d_pcrc.p, 4 * pieces.size(), hipMemcpyDeviceToHost));
         }
         unsigned long long status = clean;
-        GZ_HIP(hipMemcpy(&status, d_status, 8, hipMemcpyDeviceToHost));
+        CODEC_HIP(kGzip, hipMemcpy(&status, d_status, 8, hipMemcpyDeviceToHost));
         if (status != clean) {
             const gz::ChainChunk& c = chain[(size_t)status];
             err = gz::where(c.member0, cand[c.k] / 8u) + gz::error_text(bgzf::ERR_DISTANCE) + " (in chunk " + std::to_string(c.k) + ")";

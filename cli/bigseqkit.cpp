@@ -313,47 +313,102 @@ int sniff_format(const std::string& file_, const std::string& data) {
 // ---- compressed input (PARITY.md BGZF, GZIP): BGZF is inflated, on the device where the part lives there; any other gzip is
 // refused unless BSK_GZIP=1 asks for it: then it is read wherever a BGZF file is read whole (bsk_gzip_load on the device, the same
 // method on the host for the commands that keep host strings).  The paths that read a file in pieces still refuse it: a gzip
-// stream has no virtual offsets to re-enter at
-const char* const kPlainGzip = " is gzip but not BGZF: one gzip stream cannot be cut into independent blocks, so it is not read; "
-                               "recompress it with bgzip (gzip -dc FILE | bgzip > FILE.gz) or decompress it first, or set BSK_GZIP=1 "
-                               "to have it inflated whole, in speculative chunks, where the file and its text fit one GPU";
-bool gzip_on() {
-    const char* e = getenv("BSK_GZIP");
-    return e && *e && strcmp(e, "0") != 0;
-}
-// plain gzip on a path that BSK_GZIP=1 does not reach (without the switch: the refusal of every path)
-[[noreturn]] void refuse_plain_gzip(const std::string& f, const std::string& where) {
-    if (!gzip_on()) die(f + kPlainGzip);
-    die(f + " is gzip but not BGZF, and " + where + " a file in pieces: a gzip stream has no virtual offsets to re-enter at, so BSK_GZIP=1 "
-        "reads it only where a file is read whole; decompress it first (gzip -d), or recompress it with bgzip (gzip -dc FILE | bgzip > FILE.gz)");
-}
+// stream has no virtual offsets to re-enter at.
+// The paths for inputs that are not loaded whole read a BGZF file in pieces (bsk_bgzf_reader_*) only when asked to:
+// BSK_BGZF_STREAM=1.  Every pass over the input inflates the file again -- a bucket command reads it 2 + B times and more --, which
+// a user should choose knowingly; without the switch these paths refuse a compressed file as before, and the message names it
 
-// what the first bytes of a regular file are (bsk_bgzf_probe): 0 plain, 1 BGZF, 2 other gzip.  A pipe is 0: it is looked at
-// once it has been read
-int probe_file(const std::string& path) {
-    const int fd = open(path.c_str(), O_RDONLY);
-    if (fd < 0) die("open " + path + ": no such file or directory");
-    struct stat sb;
-    int kind = 0;
-    if (fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode)) {
-        std::string head((size_t)12 + 65535, '\0');
-        const ssize_t got = pread(fd, &head[0], head.size(), 0);
-        kind = got > 0 ? bsk_bgzf_probe(head.data(), (size_t)got) : 0;
+// One input file of an invocation, looked at once (classify_inputs): the record goes to whoever opens the file.  kind is what
+// bsk_bgzf_probe says of its first bytes; a pipe is plain here: it is looked at once it has been read
+enum InputKind { kPlain = 0, kBgzf = 1, kGzip = 2 };
+struct Input {
+    std::string path;
+    int kind = kPlain;
+    bool regular = false, missing = false;
+    size_t size = 0;
+};
+std::vector<Input> classify_inputs(const std::vector<std::string>& files) {
+    std::vector<Input> ins;
+    for (auto& path : files) {
+        Input in;
+        in.path = path;
+        const int fd = open(path.c_str(), O_RDONLY);
+        in.missing = fd < 0;  // (said by admit, or by whoever opens the file)
+        struct stat sb;
+        if (fd >= 0 && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode)) {
+            in.regular = true;
+            in.size = (size_t)sb.st_size;
+            std::string head((size_t)12 + 65535, '\0');
+            const ssize_t got = pread(fd, &head[0], head.size(), 0);
+            if (got > 0) in.kind = bsk_bgzf_probe(head.data(), (size_t)got);
+        }
+        if (fd >= 0) close(fd);
+        ins.push_back(std::move(in));
     }
-    close(fd);
-    return kind;
+    return ins;
 }
 
-// the paths that cut or stream a FILE by its bytes cannot take a compressed one: said before a device is touched
-void refuse_compressed(const std::vector<std::string>& files, const std::string& where, const std::string& instead) {
-    for (auto& f : files) {
-        const int kind = probe_file(f);
-        if (kind == 2) refuse_plain_gzip(f, where);
-        if (kind == 1) die(f + " is BGZF-compressed, and " + where + " a file by its bytes, which a compressed file does not allow yet; " + instead);
+// files of at least this many bytes do not go to the GPU as one shard: `stats` streams them from the host, the other
+// commands say what to do.  BSK_HOST_PIPELINE_FROM moves the line (tests: 0)
+static size_t whole_file_limit() {
+    size_t lim = (size_t)200 << 30;  // (288 GB of HBM: the shard, the stats vector and nothing else)
+    if (const char* e = getenv("BSK_HOST_PIPELINE_FROM")) lim = (size_t)strtoull(e, nullptr, 10);
+    return lim;
+}
+static bool stats_streams(const std::string& use, size_t size) { return use == "stats" && size > 0 && size >= whole_file_limit(); }
+
+// THE admission rule: which kind of input a route takes under which switch, and what a refusal says.
+//   Any       every invocation on one device, before a device is touched
+//   HostText  the text of a file or a pipe on the host, inflated there (inflate_host_text)
+//   Device    a file that goes to the GPU whole (read_parts), or -- `stats` on a file that does not fit -- is streamed
+//   Buckets   the bucket paths (run_buckets), which read a file in pieces
+//   Devices   --devices, which cuts a file by its bytes
+// Returns whether a BGZF file may be read in pieces (BSK_BGZF_STREAM=1); the refusals of plain gzip come first, over all files
+enum class Route { Any, HostText, Device, Buckets, Devices };
+bool admit(const std::vector<Input>& ins, Route route, const std::string& use = "") {
+    static const char* const kPlainGzip = " is gzip but not BGZF: one gzip stream cannot be cut into independent blocks, so it is not read; "
+                                          "recompress it with bgzip (gzip -dc FILE | bgzip > FILE.gz) or decompress it first, or set BSK_GZIP=1 "
+                                          "to have it inflated whole, in speculative chunks, where the file and its text fit one GPU";
+    static const char* const kStreamHint = ", or set BSK_BGZF_STREAM=1 to read it in record-aligned pieces, inflated once per pass";
+    auto switch_on = [](const char* name) { const char* e = getenv(name); return e && *e && strcmp(e, "0") != 0; };
+    const bool gzip = switch_on("BSK_GZIP"), pieces = switch_on("BSK_BGZF_STREAM");
+    // the routes that read a file by its bytes or in pieces: what they do, and what to do about a BGZF file instead
+    std::string gzip_where, bgzf_where, instead;
+    if (route == Route::Device) {
+        gzip_where = "'stats' streams";
+        bgzf_where = "'stats' streams a file that does not fit one GPU";
+        instead = std::string("decompress it first (bgzip -d), or cut it into files that fit") + kStreamHint;
+    } else if (route == Route::Buckets) {
+        gzip_where = bgzf_where = "the buckets of '" + use + "' read";
+        instead = std::string("decompress it first (bgzip -d), or unset the budget if the file and its text fit one GPU") + kStreamHint;
+    } else if (route == Route::Devices) {
+        gzip_where = bgzf_where = "--devices cuts";
+        instead = "run it on one device (--device N), or decompress it first (bgzip -d)";
     }
+    auto by_bytes = [&](const Input& in) { return route == Route::Buckets || route == Route::Devices || (route == Route::Device && stats_streams(use, in.size)); };
+    for (auto& in : ins) {
+        if (in.missing && (route != Route::Any || !gzip)) die("open " + in.path + ": no such file or directory");
+        if (in.kind != kGzip) continue;
+        if (!gzip) die(in.path + kPlainGzip);  // (read by no path without the switch)
+        if (by_bytes(in))
+            die(in.path + " is gzip but not BGZF, and " + gzip_where + " a file in pieces: a gzip stream has no virtual offsets to re-enter at, so BSK_GZIP=1 "
+                "reads it only where a file is read whole; decompress it first (gzip -d), or recompress it with bgzip (gzip -dc FILE | bgzip > FILE.gz)");
+    }
+    for (auto& in : ins)
+        if (in.kind == kBgzf && by_bytes(in) && !(pieces && route != Route::Devices))
+            die(in.path + " is BGZF-compressed, and " + bgzf_where + " a file by its bytes, which a compressed file does not allow yet; " + instead);
+    return pieces;
 }
 
-// `text` as read from a file or a pipe: inflated in place when it is BGZF (host threads, the decoder of the device)
+// the double call of an inflate entry point: call(nullptr, 0, &n) says how many bytes the text has, call(buf, n, &n) brings them
+template <class Call>
+bool size_then_fill(std::string& out, Call call) {
+    size_t n = 0;
+    if (call(nullptr, 0, &n) != BSK_OK) return false;
+    out.assign(n, '\0');
+    return n == 0 || call(&out[0], n, &n) == BSK_OK;
+}
+
 // The first byte of a BGZF file's text (0: it has none): the blocks are walked by their BSIZE, and the first one that holds text is
 // inflated on the host -- what sniff_format asks of a file that is not read whole
 char bgzf_first_text_byte(const std::string& path) {
@@ -373,11 +428,10 @@ char bgzf_first_text_byte(const std::string& path) {
             at += 4 + slen;
         }
         if (bsize == 0 || bsize > (size_t)got) break;  // (not a whole block: the reader will say what is wrong with the file)
-        size_t n = 0;
-        if (bsk_bgzf_inflate_host(b, bsize, nullptr, 0, &n, 1) != BSK_OK) break;
-        if (n) {
-            std::string text(n, '\0');
-            if (bsk_bgzf_inflate_host(b, bsize, &text[0], n, &n, 1) == BSK_OK) first = text[0];
+        std::string text;
+        if (!size_then_fill(text, [&](char* buf, size_t cap, size_t* n) { return bsk_bgzf_inflate_host(b, bsize, buf, cap, n, 1); })) break;
+        if (!text.empty()) {
+            first = text[0];
             break;
         }
         off += (off_t)bsize;
@@ -386,15 +440,6 @@ char bgzf_first_text_byte(const std::string& path) {
     return first;
 }
 
-// The paths for inputs that are not loaded whole read a BGZF file in pieces (bsk_bgzf_reader_*) only when asked to:
-// BSK_BGZF_STREAM=1.  Every pass over the input inflates the file again -- a bucket command reads it 2 + B times and more --, which
-// a user should choose knowingly; without the switch these paths refuse a compressed file as before, and the message names it
-bool bgzf_stream_on() {
-    const char* e = getenv("BSK_BGZF_STREAM");
-    return e && *e && strcmp(e, "0") != 0;
-}
-const char* const kStreamHint = ", or set BSK_BGZF_STREAM=1 to read it in record-aligned pieces, inflated once per pass";
-
 // the sizes of the BGZF piece reader (bsk_bgzf_reader_open; 0: its defaults).  The tests pin them
 struct BgzfSizes { size_t piece, look, chunk; };
 BgzfSizes bgzf_sizes() {
@@ -402,22 +447,19 @@ BgzfSizes bgzf_sizes() {
     return {env("BSK_STREAM_PIECE_BYTES"), env("BSK_BGZF_LOOKAHEAD_BYTES"), env("BSK_BGZF_CHUNK_BYTES")};
 }
 
+// `text` as read from a file or a pipe: inflated in place when it is compressed -- BGZF on host threads with the decoder of the
+// device, plain gzip by the speculative method with one host lane, in one piece
 void inflate_host_text(const std::string& path, std::string& text) {
-    const int kind = bsk_bgzf_probe(text.data(), text.size());
-    if (kind == 2) {  // (plain gzip: the speculative method with one host lane, in one piece)
-        if (!gzip_on()) die(path + kPlainGzip);
-        size_t n = 0;
-        if (bsk_gzip_inflate_host(text.data(), text.size(), nullptr, 0, &n, 0) != BSK_OK) die(path + ": " + bsk_global_error());
-        std::string out(n, '\0');
-        if (n && bsk_gzip_inflate_host(text.data(), text.size(), &out[0], n, &n, 0) != BSK_OK) die(path + ": " + bsk_global_error());
-        text.swap(out);
-        return;
-    }
-    if (kind != 1) return;
-    size_t n = 0;
-    if (bsk_bgzf_inflate_host(text.data(), text.size(), nullptr, 0, &n, 0) != BSK_OK) die(path + ": " + bsk_global_error());
-    std::string out(n, '\0');
-    if (n && bsk_bgzf_inflate_host(text.data(), text.size(), &out[0], n, &n, 0) != BSK_OK) die(path + ": " + bsk_global_error());
+    Input in;
+    in.path = path;
+    in.kind = bsk_bgzf_probe(text.data(), text.size());
+    if (in.kind == kPlain) return;
+    admit({in}, Route::HostText);
+    std::string out;
+    const bool ok = size_then_fill(out, [&](char* buf, size_t cap, size_t* n) {
+        return in.kind == kGzip ? bsk_gzip_inflate_host(text.data(), text.size(), buf, cap, n, 0) : bsk_bgzf_inflate_host(text.data(), text.size(), buf, cap, n, 0);
+    });
+    if (!ok) die(path + ": " + bsk_global_error());
     text.swap(out);
 }
 
@@ -889,16 +931,6 @@ Output execute(const Invocation& inv, std::vector<Part>& inputs, bool keep_on_de
     return res;
 }
 
-// device >= 0: the files go straight to that GPU (bsk_shard_load: several readers, pread || H2D) -- what every command but
-// the ones that join their inputs on the host (concat, common, pair) takes; device < 0: host strings
-// files of at least this many bytes do not go to the GPU as one shard: `stats` streams them from the host, the other
-// commands say what to do.  BSK_HOST_PIPELINE_FROM moves the line (tests: 0)
-static size_t whole_file_limit() {
-    size_t lim = (size_t)200 << 30;  // (288 GB of HBM: the shard, the stats vector and nothing else)
-    if (const char* e = getenv("BSK_HOST_PIPELINE_FROM")) lim = (size_t)strtoull(e, nullptr, 10);
-    return lim;
-}
-
 // The key-bucket family of the command line (run_buckets): one row per command.
 //   budget_env   the bytes a bucket may hold (rmdup, rename, common and the match buckets of pair and concat: bytes of subjects and
 //                their per-record words, not of record text; the order buckets of pair: bytes of record text, the windows of concat:
@@ -994,54 +1026,34 @@ static uint64_t bucket_budget(const std::string& use) {
 }
 bool g_buckets_unfit = false;  // read_parts: the whole-file load of a `shuffle` / `sort` / `rmdup` / `rename` input failed and a budget is set
 
-std::vector<Part> read_parts(const std::vector<std::string>& files, int device = -1, const std::string& use = "") {
+// device >= 0: the files go straight to that GPU (bsk_shard_load: several readers, pread || H2D) -- what every command but
+// the ones that join their inputs on the host (concat, common, pair) takes; device < 0: host strings
+std::vector<Part> read_parts(const std::vector<Input>& inputs, int device = -1, const std::string& use = "") {
     std::vector<Part> parts;
-    for (auto& f : files) {
+    for (auto& in : inputs) {
+        const std::string& f = in.path;
         Part p;
-        if (device < 0) {
+        if (device < 0 || (!in.missing && !in.regular)) {  // (a pipe: read to its end first)
             p.host = read_file(f);
             inflate_host_text(f, p.host);
             p.fmt = sniff_format(f, p.host);
         } else {
+            const bool pieces = admit({in}, Route::Device, use);
             const int fd = open(f.c_str(), O_RDONLY);
             if (fd < 0) die("open " + f + ": no such file or directory");
-            struct stat sb;
-            if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) {  // (a pipe: read to its end first)
-                close(fd);
-                p.host = read_file(f);
-                inflate_host_text(f, p.host);
-                p.fmt = sniff_format(f, p.host);
+            if (in.kind == kBgzf && stats_streams(use, in.size)) {
+                // stats: the file stays where it is, the piece reader streams its text in record-aligned pieces (execute)
+                p.fmt = sniff_format(f, std::string(1, bgzf_first_text_byte(f)));
+                p.bgzf_fd = fd;
                 parts.push_back(std::move(p));
                 continue;
             }
-            const int kind = probe_file(f);
-            if (kind == 2) {  // plain gzip: compressed across PCIe, inflated whole in HBM -- there are no pieces of it
-                if (!gzip_on()) die(f + kPlainGzip);
-                if (use == "stats" && sb.st_size > 0 && (size_t)sb.st_size >= whole_file_limit()) refuse_plain_gzip(f, "'stats' streams");
-                if (bsk_gzip_load(fd, device, 0, 0, &p.dptr, &p.n) != BSK_OK)
+            if (in.kind != kPlain) {  // compressed across PCIe, inflated in HBM: from here on an ordinary device part
+                if (in.kind == kGzip && bsk_gzip_load(fd, device, 0, 0, &p.dptr, &p.n) != BSK_OK)  // (whole: there are no pieces of it)
                     die(f + ": " + bsk_global_error() + " -- a gzip file is inflated whole on one device: it, its text and twice its text in symbols must fit there; "
                         "decompress it first (gzip -d), or recompress it with bgzip to use the paths for larger inputs");
-                close(fd);
-                char first = 0;
-                if (p.n && bsk_device_copy(&first, p.dptr, 1, BSK_COPY_D2H) != BSK_OK) die(bsk_global_error());
-                p.fmt = sniff_format(f, p.n ? std::string(1, first) : std::string());
-                p.owned_alloc = true;
-                parts.push_back(std::move(p));
-                continue;
-            }
-            if (kind == 1) {  // compressed across PCIe, inflated in HBM: from here on an ordinary device part
-                if (use == "stats" && sb.st_size > 0 && (size_t)sb.st_size >= whole_file_limit()) {
-                    if (!bgzf_stream_on())
-                        refuse_compressed({f}, "'stats' streams a file that does not fit one GPU",
-                                          std::string("decompress it first (bgzip -d), or cut it into files that fit") + kStreamHint);
-                    // stats: the file stays where it is, the piece reader streams its text in record-aligned pieces (execute)
-                    p.fmt = sniff_format(f, std::string(1, bgzf_first_text_byte(f)));
-                    p.bgzf_fd = fd;
-                    parts.push_back(std::move(p));
-                    continue;
-                }
-                if (bsk_bgzf_load(fd, device, 0, &p.dptr, &p.n) != BSK_OK) {
-                    if (bucket_budget(use) > 0 && bgzf_stream_on()) {  // (as for a plain file that does not fit: through the buckets, piece by piece)
+                if (in.kind == kBgzf && bsk_bgzf_load(fd, device, 0, &p.dptr, &p.n) != BSK_OK) {
+                    if (bucket_budget(use) > 0 && pieces) {  // (as for a plain file that does not fit: through the buckets, piece by piece)
                         close(fd);
                         g_buckets_unfit = true;
                         release(parts);
@@ -1061,9 +1073,8 @@ std::vector<Part> read_parts(const std::vector<std::string>& files, int device =
             char first = 0;
             const ssize_t got = pread(fd, &first, 1, 0);
             p.fmt = sniff_format(f, got == 1 ? std::string(1, first) : std::string());
-            p.n = (size_t)sb.st_size;
-            const bool too_big = use == "stats" && p.n > 0 && p.n >= whole_file_limit();
-            if (too_big || bsk_shard_load(fd, 0, p.n, device, 0, &p.dptr) != BSK_OK) {
+            p.n = in.size;
+            if (stats_streams(use, p.n) || bsk_shard_load(fd, 0, p.n, device, 0, &p.dptr) != BSK_OK) {
                 p.dptr = nullptr;
                 if (use != "stats") {
                     close(fd);
@@ -1111,7 +1122,7 @@ Output run_job(const bsk::json::Value& j, bool root) {
     std::vector<std::string> args;
     for (auto& a : cmd->arr) args.push_back(a->str);
     Invocation inv = parse_invocation(args);
-    for (auto& p : read_parts(inv.files, (int)strtol(inv.pget("device").c_str(), nullptr, 10), inv.cmd->use)) inputs.push_back(std::move(p));
+    for (auto& p : read_parts(classify_inputs(inv.files), (int)strtol(inv.pget("device").c_str(), nullptr, 10), inv.cmd->use)) inputs.push_back(std::move(p));
     if (inputs.empty()) die("no input for job command " + args[0]);
     Output o = execute(inv, inputs, !root);
     release(inputs);
@@ -1431,35 +1442,34 @@ struct BucketRun {
         return {p, n, 1};
     }
     // the files mapped, of one format, and cut into record-aligned pieces; a piece never spans two files
-    void map_pieces(const std::vector<std::string>& paths, size_t n_files, int device) {
+    void map_pieces(const std::vector<Input>& ins, size_t n_files, int device) {
         const char* pinned = getenv("BSK_STREAM_PIECE_BYTES");
         const size_t piece = pinned ? std::max<size_t>(1, (size_t)strtoull(pinned, nullptr, 10)) : ((size_t)1 << 30);
         files.resize(n_files);
         int fmt = -1;
         for (size_t fi = 0; fi < n_files; ++fi) {
             MappedFile& f = files[fi];
-            const int kind = probe_file(paths[fi]);
-            if (kind == 2) refuse_plain_gzip(paths[fi], std::string("the buckets of '") + cmd.use + "' read");
-            if (kind == 1) {  // BGZF: the reader runs over the file once and lists its pieces; plain and BGZF inputs may be mixed
-                f.fd = open(paths[fi].c_str(), O_RDONLY);
-                if (f.fd < 0) die("open " + paths[fi] + ": no such file or directory");
-                const int ffmt = sniff_format(paths[fi], std::string(1, bgzf_first_text_byte(paths[fi])));
+            const std::string& path = ins[fi].path;
+            if (ins[fi].kind == kBgzf) {  // BGZF: the reader runs over the file once and lists its pieces; plain and BGZF inputs may be mixed
+                f.fd = open(path.c_str(), O_RDONLY);
+                if (f.fd < 0) die("open " + path + ": no such file or directory");
+                const int ffmt = sniff_format(path, std::string(1, bgzf_first_text_byte(path)));
                 if (fmt >= 0 && ffmt != fmt) die(std::string(cmd.use) + ": inputs of different formats");
                 fmt = ffmt;
                 const BgzfSizes z = bgzf_sizes();
-                if (bsk_bgzf_reader_open(f.fd, device, fmt, z.piece, z.look, z.chunk, &f.reader) != BSK_OK) die(paths[fi] + ": " + bsk_global_error());
+                if (bsk_bgzf_reader_open(f.fd, device, fmt, z.piece, z.look, z.chunk, &f.reader) != BSK_OK) die(path + ": " + bsk_global_error());
                 for (int last = 0; !last;) {
                     Piece pc{nullptr, 0, 0, fi, 0};
                     const void* p = nullptr;
-                    if (bsk_bgzf_reader_next(f.reader, &p, &pc.n, &pc.vlo, &pc.vhi, &last) != BSK_OK) die(paths[fi] + ": " + bsk_global_error());
+                    if (bsk_bgzf_reader_next(f.reader, &p, &pc.n, &pc.vlo, &pc.vhi, &last) != BSK_OK) die(path + ": " + bsk_global_error());
                     pc.bgzf = true;
                     total_bytes += pc.n;
                     if (pc.n) pieces.push_back(pc);
                 }
                 continue;
             }
-            map_file(paths[fi], &f);
-            const int ffmt = sniff_format(paths[fi], f.size ? std::string((const char*)f.text, 1) : std::string());
+            map_file(path, &f);
+            const int ffmt = sniff_format(path, f.size ? std::string((const char*)f.text, 1) : std::string());
             if (fmt >= 0 && ffmt != fmt) die(std::string(cmd.use) + ": inputs of different formats");
             fmt = ffmt;
             total_bytes += f.size;
@@ -1705,7 +1715,7 @@ void BucketRun::concat_tail(const Invocation& inv) {
     }
 }
 
-Output run_buckets(const Invocation& inv) {
+Output run_buckets(const Invocation& inv, const std::vector<Input>& ins) {
     const std::string use = inv.cmd->use;
     const bool pair = use == "pair", concat = use == "concat";
     if (concat && inv.files.size() != 2) die("2 files needed");  // cli/concat.go
@@ -1715,11 +1725,7 @@ Output run_buckets(const Invocation& inv) {
         if (inv.files.size() < 2) die("2 files needed");
         if (outdir.empty()) die("out-dir required");
     }
-    for (auto& f : inv.files)  // (plain gzip has no pieces, with or without the switches: said before a device is touched)
-        if (probe_file(f) == 2) refuse_plain_gzip(f, "the buckets of '" + use + "' read");
-    if (!bgzf_stream_on())
-        refuse_compressed(inv.files, "the buckets of '" + use + "' read",
-                          std::string("decompress it first (bgzip -d), or unset the budget if the file and its text fit one GPU") + kStreamHint);
+    admit(ins, Route::Buckets, use);  // (plain gzip has no pieces, with or without the switches: said before a device is touched)
     const int device = (int)strtol(inv.pget("device").c_str(), nullptr, 10);
     BucketRun R{*bucket_cmd(use)};
     R.res.packed = !pair && packs_on_device(inv);  // (pair -O writes its four files under fixed names: plain)
@@ -1727,7 +1733,7 @@ Output run_buckets(const Invocation& inv) {
     if (bsk_create(inv.cmd->op, inv.js.c_str(), device, &R.ctx) != BSK_OK) die(bsk_global_error());
     const bool timing = getenv("BSK_CLI_TIMING") != nullptr;
     if (timing) bsk_profile_enable(R.ctx, 1);
-    R.map_pieces(inv.files, pair || concat ? 2 : inv.files.size(), device);
+    R.map_pieces(ins, pair || concat ? 2 : ins.size(), device);
     R.plan_buckets();
     if (concat) {
         R.concat_tail(inv);
@@ -1766,7 +1772,7 @@ int run_devices(const Invocation& inv) {
     if (inv.files.size() != 1) die("--devices: exactly one input file (it is cut into one shard per GPU)");
     const std::vector<int> devices = parse_devices(inv.pget("devices"));
     const int world = (int)devices.size();
-    refuse_compressed(inv.files, "--devices cuts", "run it on one device (--device N), or decompress it first (bgzip -d)");
+    admit(classify_inputs(inv.files), Route::Devices);
     mark("start");
     if (bsk_device_count() <= 0) die("no HIP device visible (the hot path has no CPU fallback)");
     const std::string& path = inv.files[0];
@@ -2132,7 +2138,7 @@ static int run_main(int argc, char** argv) {
         Output o = run_job(*j, true);
         g_pipe_job = false;
         // the files given to `pipe` itself are appended unchanged (pipe.go:61-66)
-        for (auto& p : read_parts(inv.files)) o.text += p.host;
+        for (auto& p : read_parts(classify_inputs(inv.files))) o.text += p.host;
         store(inv, o, inv.files);
         return 0;
     }
@@ -2167,9 +2173,8 @@ static int run_main(int argc, char** argv) {
             "a worker could not judge its shard before the shards in front of it are done, so --devices is refused");
     if (!inv.pget("devices").empty()) return run_devices(inv);  // several GPUs: worker threads + librccl, in this process
     if (inv.files.empty()) die("no input files (stdin is not supported by the IgnisHPC CLI either)");
-    if (!gzip_on())
-        for (auto& f : inv.files)  // (gzip that is not BGZF is read by no path without the switch: said before a device is touched)
-            if (probe_file(f) == 2) die(f + kPlainGzip);
+    const std::vector<Input> ins = classify_inputs(inv.files);
+    admit(ins, Route::Any);  // (gzip that is not BGZF is read by no path without the switch: said before a device is touched)
     g_faidx_query = faidx_query;
     const std::string use_cmd = inv.cmd->use;
     const bool joins_on_host = use_cmd == "concat" || use_cmd == "common" || use_cmd == "pair";
@@ -2182,18 +2187,17 @@ static int run_main(int argc, char** argv) {
     if (bucket_budget(use_cmd) > 0) {  // (shuffle, sort, rmdup, rename, common, pair, concat)
         // more bytes than a bucket may hold: not loaded whole (a pipe has no size: it takes the whole-file path)
         uint64_t total = 0;
-        struct stat sb;
-        for (auto& f : inv.files)
-            if (stat(f.c_str(), &sb) == 0 && S_ISREG(sb.st_mode)) total += (uint64_t)sb.st_size;
+        for (auto& in : ins)
+            if (in.regular) total += in.size;
         if (total > bucket_budget(use_cmd)) {
-            Output o = run_buckets(inv);
+            Output o = run_buckets(inv, ins);
             if (use_cmd != "pair" && !o.stored) store(inv, o, inv.files);  // (pair has written its four files, concat its shares)
             return 0;
         }
     }
-    std::vector<Part> inputs = read_parts(inv.files, joins_on_host ? -1 : (int)strtol(inv.pget("device").c_str(), nullptr, 10), use_cmd);
+    std::vector<Part> inputs = read_parts(ins, joins_on_host ? -1 : (int)strtol(inv.pget("device").c_str(), nullptr, 10), use_cmd);
     if (g_buckets_unfit) {
-        Output o = run_buckets(inv);
+        Output o = run_buckets(inv, ins);
         store(inv, o, inv.files);
         return 0;
     }

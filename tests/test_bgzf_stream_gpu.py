@@ -121,8 +121,44 @@ def test_stages_of_the_reader(tmp_path, cases):
     assert int(stages["bgzf_stream_cut"].split("/")[1]) >= n - 1 and int(stages["bgzf_inflate"].split("/")[1]) >= n, stages
 
 
+CODEC_STAGES = ("bgzf_find", "bgzf_sizes", "bgzf_inflate", "bgzf_deflate", "bgzf_pack",
+                "gzip_find", "gzip_size", "gzip_decode", "gzip_windows", "gzip_translate", "gzip_crc")
+
+
+def test_one_registry_holds_the_stages_of_every_codec(monkeypatch):
+    """BGZF input, BGZF output and plain gzip feed one process-wide registry: with profiling on, one call of each leaves every
+    one of their stages in bsk_profile_dump with at least one launch; a reset empties it; with profiling off nothing is added"""
+    text, fq = R.fastq_text(2048)[:2048], R.fastq_text(20000)
+    z_bgzf = R.write(text, block=1024)                     # two blocks of 1 KB of text, and the EOF block
+    z_gzip = gzip.compress(fq, mtime=0)
+    monkeypatch.setenv("BSK_GZIP_CHUNK_BYTES", "4096")     # (more than one chunk)
+    assert len(R.index(z_bgzf)) == 3 and len(z_gzip) > 4096
+
+    def one_of_each():
+        assert bytes(bsk.BgzfInflate(z_bgzf).cpu().numpy().tobytes()) == text
+        assert gzip.decompress(bsk.BgzfDeflate(text, block_bytes=1024)) == text
+        assert bytes(bsk.GzipInflate(z_gzip).cpu().numpy().tobytes()) == fq
+
+    def dump(op):
+        buf = C.create_string_buffer(1 << 16)
+        check(lib.bsk_profile_dump(op.ctx, buf, len(buf)), op.ctx)
+        return {k: int(v.split("/")[1]) for k, v in (x.split("=") for x in buf.value.decode().split(";") if x)}
+
+    with bsk.Operator("Stats", "{}") as op:
+        check(lib.bsk_profile_enable(op.ctx, 1), op.ctx)
+        check(lib.bsk_profile_reset(op.ctx), op.ctx)
+        one_of_each()
+        stages = dump(op)
+        assert all(stages.get(s, 0) >= 1 for s in CODEC_STAGES), stages
+        check(lib.bsk_profile_reset(op.ctx), op.ctx)
+        assert not set(dump(op)) & set(CODEC_STAGES)
+        check(lib.bsk_profile_enable(op.ctx, 0), op.ctx)
+        one_of_each()
+        assert not set(dump(op)) & set(CODEC_STAGES)
+
+
 # ------------------------------------------------------------------ the command line
-STREAM = {"BSK_BGZF_STREAM": "1", "BSK_STREAM_PIECE_BYTES": "20000", "BSK_BGZF_LOOKAHEAD_BYTES": "2000", "BSK_BGZF_CHUNK_BYTES": "30000"}
+STREAM ={"BSK_BGZF_STREAM": "1", "BSK_STREAM_PIECE_BYTES": "20000", "BSK_BGZF_LOOKAHEAD_BYTES": "2000", "BSK_BGZF_CHUNK_BYTES": "30000"}
 
 
 def cli(args, env=None):
@@ -239,17 +275,23 @@ def test_cli_buckets_write_bgzf(inputs):
 def test_cli_without_the_switch_refuses_as_before(inputs):
     """the paths that read a BGZF file in pieces are asked for by BSK_BGZF_STREAM=1: without it both refuse as they did, and the
     message names the switch"""
+    from test_gzip_cpu import BY_BYTES, UNSET_BUDGET
     z = inputs["a.fq"][1]
+    said = lambda r, where, instead: r.returncode == 1 and r.stderr.decode() == "Error: " + z + BY_BYTES % (where, instead) + "\n"
+    cut_it = "decompress it first (bgzip -d), or cut it into files that fit, or set BSK_BGZF_STREAM=1 to read it in record-aligned pieces, inflated once per pass"
     r = cli(["stats", z], {"BSK_HOST_PIPELINE_FROM": "0"})
-    assert r.returncode == 1 and b"BGZF-compressed" in r.stderr and b"streams" in r.stderr and b"BSK_BGZF_STREAM=1" in r.stderr
+    assert said(r, "'stats' streams a file that does not fit one GPU", cut_it), r.stderr
     r = cli(["sort", z, "-o", "-"], {"BSK_SORT_BUDGET_BYTES": "40000"})
-    assert r.returncode == 1 and b"BGZF-compressed" in r.stderr and b"buckets of 'sort'" in r.stderr and b"BSK_BGZF_STREAM=1" in r.stderr
+    assert said(r, "the buckets of 'sort' read", UNSET_BUDGET) and b"BSK_BGZF_STREAM=1" in r.stderr, r.stderr
     r = cli(["stats", z], {"BSK_HOST_PIPELINE_FROM": "0", "BSK_BGZF_STREAM": "0"})
-    assert r.returncode == 1 and b"BGZF-compressed" in r.stderr
+    assert said(r, "'stats' streams a file that does not fit one GPU", cut_it), r.stderr
 
 
 def test_cli_devices_still_refused(inputs):
     """--devices with a BGZF file: refused as before, before a device is touched"""
-    r = cli(["stats", "--devices", "0", inputs["a.fq"][1]], {"HIP_VISIBLE_DEVICES": "-1", "ROCR_VISIBLE_DEVICES": "-1", "BSK_BGZF_STREAM": "1"})
-    assert r.returncode == 1 and b"BGZF-compressed" in r.stderr and b"--devices cuts a file by its bytes, which a compressed file does not allow yet" in r.stderr
+    from test_gzip_cpu import BY_BYTES, ONE_DEVICE
+    z = inputs["a.fq"][1]
+    r = cli(["stats", "--devices", "0", z], {"HIP_VISIBLE_DEVICES": "-1", "ROCR_VISIBLE_DEVICES": "-1", "BSK_BGZF_STREAM": "1"})
+    assert r.returncode == 1 and r.stderr.decode() == "Error: " + z + BY_BYTES % ("--devices cuts", ONE_DEVICE) + "\n", r.stderr
+    assert b"--devices cuts a file by its bytes, which a compressed file does not allow yet" in r.stderr
     assert b"--device N" in r.stderr and b"no HIP device" not in r.stderr

@@ -136,7 +136,7 @@ CLI = os.path.join(ROOT, "bigseqkit_amd", "bin", "bigseqkit")
 
 
 def cli(args, env=None):
-    e = {k: v for k, v in os.environ.items() if not k.startswith("BSK_GZIP")}
+    e = {k: v for k, v in os.environ.items() if not k.startswith(("BSK_GZIP", "BSK_BGZF_STREAM"))}
     e.update(env or {})
     return subprocess.run([CLI, *args], capture_output=True, timeout=120, env=e)
 
@@ -155,6 +155,62 @@ def test_command_line_dry_run_and_refusals(tmp_path, corpus):
     assert r.returncode == 1 and b"not BGZF" in r.stderr and b"--devices cuts" in r.stderr and b"virtual offsets" in r.stderr and b"bgzip" in r.stderr, r.stderr
     r = cli(["common", z, z], dict(on, BSK_COMMON_BUDGET_BYTES="1000"))
     assert r.returncode == 1 and b"not BGZF" in r.stderr and b"buckets of 'common'" in r.stderr and b"virtual offsets" in r.stderr, r.stderr
+    refusals_in_full(tmp_path)
+
+
+# The refusals that end without a device, whole: exit status 1 and these lines on stderr, the file's name in front.  The texts are
+# those of the command line before its admission rule had one owner (recorded from that binary).
+NO_SWITCH = (" is gzip but not BGZF: one gzip stream cannot be cut into independent blocks, so it is not read; recompress it with bgzip "
+             "(gzip -dc FILE | bgzip > FILE.gz) or decompress it first, or set BSK_GZIP=1 to have it inflated whole, in speculative chunks, "
+             "where the file and its text fit one GPU")
+IN_PIECES = (" is gzip but not BGZF, and %s a file in pieces: a gzip stream has no virtual offsets to re-enter at, so BSK_GZIP=1 reads it "
+             "only where a file is read whole; decompress it first (gzip -d), or recompress it with bgzip (gzip -dc FILE | bgzip > FILE.gz)")
+BY_BYTES = " is BGZF-compressed, and %s a file by its bytes, which a compressed file does not allow yet; %s"
+UNSET_BUDGET = ("decompress it first (bgzip -d), or unset the budget if the file and its text fit one GPU, or set BSK_BGZF_STREAM=1 to read "
+                "it in record-aligned pieces, inflated once per pass")
+ONE_DEVICE = "run it on one device (--device N), or decompress it first (bgzip -d)"
+NO_DEVICE = {"HIP_VISIBLE_DEVICES": "-1", "ROCR_VISIBLE_DEVICES": "-1"}
+
+
+def refusals_in_full(tmp_path):
+    """a 1-record FASTQ as plain text, as BGZF and as gzip: every refusal that is issued before a device is touched, with no
+    device visible -- the whole of stderr, not words of it"""
+    import bgzf_ref
+    import gzip
+    text = b"@r0 d=0\nACGTACGTAC\n+\nIIIIIIIIII\n"
+    p, b, z = (str(tmp_path / n) for n in ("one.fq", "one.bgzf.fq.gz", "one.fq.gz"))
+    open(p, "wb").write(text)
+    open(b, "wb").write(bgzf_ref.write(text))
+    open(z, "wb").write(gzip.compress(text, mtime=0))
+    assert bsk.BgzfProbe(open(p, "rb").read()) == 0 and bsk.BgzfProbe(open(b, "rb").read()) == 1 and bsk.BgzfProbe(open(z, "rb").read()) == 2
+
+    def refused(args, env, want):
+        r = cli(args, dict(NO_DEVICE, **env))
+        assert r.returncode == 1 and r.stderr.decode() == "Error: " + want + "\n", (args, env, r.stderr)
+
+    on, stream = {"BSK_GZIP": "1"}, {"BSK_BGZF_STREAM": "1"}
+    bucketed = {"concat": ["concat"], "common": ["common"], "pair": ["pair", "-O", str(tmp_path / "o")]}
+    # any command on the gzip file without BSK_GZIP, whatever else is set
+    for args in (["stats", z], ["seq", z], ["head-genome", z], ["stats", "--devices", "0", z], ["concat", z, z], ["common", p, z], ["pair", "-O", str(tmp_path / "o"), z, z]):
+        for env in ({}, stream, {"BSK_GZIP": "0"}):
+            refused(args, env, z + NO_SWITCH)
+    for use, args in bucketed.items():
+        budget = {"BSK_%s_BUDGET_BYTES" % use.upper(): "1"}
+        buckets = "the buckets of '%s' read" % use
+        refused([*args, z, z], budget, z + NO_SWITCH)
+        # the buckets on a BGZF input without BSK_BGZF_STREAM (a plain file in front of it changes nothing)
+        for files in ([b, b], [p, b]):
+            for env in ({}, {"BSK_BGZF_STREAM": "0"}, on):
+                refused([*args, *files], dict(budget, **env), b + BY_BYTES % (buckets, UNSET_BUDGET))
+        # the buckets on a gzip input with BSK_GZIP=1, with and without BSK_BGZF_STREAM; gzip is refused before BGZF
+        for files in ([z, z], [p, z], [b, z]):
+            for env in (on, dict(on, **stream)):
+                refused([*args, *files], dict(budget, **env), z + IN_PIECES % buckets)
+    # --devices
+    for env in ({}, stream, on, dict(on, **stream)):
+        refused(["stats", "--devices", "0", b], env, b + BY_BYTES % ("--devices cuts", ONE_DEVICE))
+    for env in (on, dict(on, **stream)):
+        refused(["stats", "--devices", "0", z], env, z + IN_PIECES % "--devices cuts")
 
 
 LDS = {"k_gz_find": 8, "k_gz_size": 3672, "k_gz_decode": 69216, "k_gz_windows": 0, "k_gz_translate": 0, "k_gz_crc": 1152}

@@ -196,17 +196,20 @@ def test_command_line_gzip_in_gz_out(seqfiles):
 
 
 def test_command_line_refusals(seqfiles):
+    """the whole of stderr, as test_gzip_cpu.py holds it for the refusals that need no device"""
+    from test_gzip_cpu import NO_SWITCH, IN_PIECES
     _, fqz, _ = seqfiles["x.fq"]
+    said = lambda r, want: r.returncode == 1 and r.stderr.decode() == "Error: " + fqz + want + "\n"
     r = cli(["stats", fqz])   # without the switch: as before, and the message names the switch
-    assert r.returncode == 1 and b"bgzip" in r.stderr and b"not BGZF" in r.stderr and b"BSK_GZIP=1" in r.stderr
+    assert said(r, NO_SWITCH) and b"bgzip" in r.stderr and b"BSK_GZIP=1" in r.stderr, r.stderr
     # with it, the paths that read a file in pieces still refuse, and say what to do instead
     r = cli(["stats", "--devices", "0", fqz], GZ)
-    assert r.returncode == 1 and b"not BGZF" in r.stderr and b"--devices cuts" in r.stderr and b"virtual offsets" in r.stderr and b"bgzip" in r.stderr, r.stderr
+    assert said(r, IN_PIECES % "--devices cuts") and b"virtual offsets" in r.stderr and b"bgzip" in r.stderr, r.stderr
     for stream in ({}, {"BSK_BGZF_STREAM": "1"}):
         r = cli(["sort", fqz], dict(GZ, BSK_SORT_BUDGET_BYTES="1000", BSK_HOST_PIPELINE_FROM="0", **stream))
-        assert r.returncode == 1 and b"not BGZF" in r.stderr and b"buckets of 'sort'" in r.stderr and b"virtual offsets" in r.stderr, r.stderr
+        assert said(r, IN_PIECES % "the buckets of 'sort' read"), r.stderr
     r = cli(["stats", fqz], dict(GZ, BSK_HOST_PIPELINE_FROM="0"))
-    assert r.returncode == 1 and b"not BGZF" in r.stderr and b"'stats' streams" in r.stderr and b"virtual offsets" in r.stderr, r.stderr
+    assert said(r, IN_PIECES % "'stats' streams"), r.stderr
     with pytest.raises(bsk.BskError) as e:   # the piece reader itself, at its first piece
         with bsk.BgzfReader(fqz, bsk.FORMAT_FASTQ) as r:
             list(r)
