@@ -231,6 +231,11 @@ SIGNATURES = {
     "bsk_bgzf_reader_seek": (_i, [_vp, _u64]),
     "bsk_bgzf_reader_piece": (_i, [_vp, _u64, _u64, _p(_vp), _p(_sz)]),
     "bsk_bgzf_reader_close": (None, [_vp]),
+    "bsk_gzip_reader_open": (_i, [_i, _i, _i, _sz, _sz, _sz, _sz, _p(_vp)]),
+    "bsk_gzip_reader_next": (_i, [_vp, _p(_vp), _p(_sz), _p(_u64), _p(_u64), _p(_i)]),
+    "bsk_gzip_reader_piece": (_i, [_vp, _u64, _u64, _p(_vp), _p(_sz)]),
+    "bsk_gzip_reader_info": (_i, [_vp, _p(_u64)]),
+    "bsk_gzip_reader_close": (None, [_vp]),
     "bsk_selftest_bgzf_stream_cut": (_i, [C.c_char_p, _sz, _sz, _i, _i, _p(_u64)]),
     "bsk_bgzf_deflate_bound": (_sz, [_sz, C.c_uint32]),
     "bsk_bgzf_deflate_device": (_i, [_vp, _sz, _i, C.c_uint32, _i, _p(_vp), _p(_sz)]),

@@ -232,6 +232,73 @@ class BgzfReader:
         return self._wrap(ptr, n.value)
 
 
+_READER_INFO_FIELDS = ("segments", "access_points", "doublings", "dropped_chunks", "members", "text_bytes", "peak_bytes", "chunk_bytes")
+
+
+class GzipReader:
+    """the text of a plain gzip file of any size in record-aligned pieces (bsk_gzip_reader_*): a segment of the file is held at
+    a time, never the file or its text.  Iterating gives (piece, text_lo, text_hi) and checks every member's CRC32 and ISIZE;
+    the piece a CUDA uint8 tensor that VIEWS the reader's buffer -- valid until the second piece after it, clone it to keep
+    it -- or, with device=-1, bytes from the same reader on the host.  The offsets are offsets of the text;
+    .piece(lo, hi) gives the bytes of a piece again on a later pass (the reader re-enters at the segment start in front of lo).
+    0 for a size: 1 GiB of text, 1 MiB of lookahead, 64 MiB of compressed bytes, the library's chunk rule.
+
+        with GzipReader("reads.fq.gz", FORMAT_FASTQ) as r:
+            where = [(lo, hi) for _, lo, hi in r]
+            again = r.piece(*where[0])
+    """
+
+    def __init__(self, path, fmt, device=0, piece_text_bytes=0, lookahead_bytes=0, segment_bytes=0, chunk_bytes=0):
+        self.device = device
+        self._f = open(os.fspath(path), "rb")
+        self._r = C.c_void_p()
+        self._done = False
+        try:
+            check(lib.bsk_gzip_reader_open(self._f.fileno(), device, fmt, piece_text_bytes, lookahead_bytes, segment_bytes, chunk_bytes, C.byref(self._r)))
+        except Exception:
+            self._f.close()
+            raise
+
+    def close(self):
+        if self._r:
+            lib.bsk_gzip_reader_close(self._r)
+            self._r = C.c_void_p()
+        self._f.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def _wrap(self, ptr, n):
+        if self.device < 0:
+            return C.string_at(ptr, n) if n else b""
+        return _view(ptr.value, n, self.device)
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        if self._done:
+            raise StopIteration
+        ptr, n, lo, hi, last = C.c_void_p(), C.c_size_t(), C.c_uint64(), C.c_uint64(), C.c_int()
+        check(lib.bsk_gzip_reader_next(self._r, C.byref(ptr), C.byref(n), C.byref(lo), C.byref(hi), C.byref(last)))
+        self._done = bool(last.value)
+        return self._wrap(ptr, n.value), lo.value, hi.value
+
+    def piece(self, text_lo, text_hi):
+        ptr, n = C.c_void_p(), C.c_size_t()
+        check(lib.bsk_gzip_reader_piece(self._r, text_lo, text_hi, C.byref(ptr), C.byref(n)))
+        return self._wrap(ptr, n.value)
+
+    def info(self):
+        out = (C.c_uint64 * 8)()
+        check(lib.bsk_gzip_reader_info(self._r, out))
+        return dict(zip(_READER_INFO_FIELDS, (int(v) for v in out)))
+
+
 class _Foreign:
     """n bytes of device memory that the library owns, for torch to look at (__cuda_array_interface__)"""
 

@@ -477,5 +477,8 @@ struct BgzfHostBackend : BgzfStreamBackend {
 BgzfPieceReader* bgzf_reader_open(int fd, int device, int format, size_t piece, size_t look, size_t chunk, int* rc, std::string& err);
 // stream_cut on text[0, n): by k_bgzf_stream_cut on `device`, or (device < 0) on the host
 int bgzf_stream_cut_run(const uint8_t* text, uint64_t n, uint64_t from, int format, int device, uint64_t* cut, std::string& err);
+// k_bgzf_stream_cut on d_text[0, n) in device memory, the answer to *d_cut; `stream` is a hipStream_t, returns a hipError_t (the
+// gzip reader of gzip_stream.hpp cuts its pieces with the same kernel)
+int bgzf_launch_stream_cut(const uint8_t* d_text, uint64_t n, uint64_t from, int format, uint64_t* d_cut, void* stream);
 
 }  // namespace bsk

@@ -18,6 +18,7 @@
 #include "anchor.hpp"
 #include "ctx.hpp"
 #include "bgzf_stream.hpp"
+#include "gzip_stream.hpp"
 #include "codec_host.hpp"
 #include "ops_bgzf.hpp"
 #include "ops_bgzf_write.hpp"
@@ -825,6 +826,44 @@ int bsk_bgzf_reader_piece(bsk_bgzf_reader* r, uint64_t voff_lo, uint64_t voff_hi
 }
 
 void bsk_bgzf_reader_close(bsk_bgzf_reader* r) {
+    if (!r) return;
+    delete r->r;
+    delete r;
+}
+
+// ---- the piece reader of a plain gzip file (gzip_stream.hpp, ops_gzip_stream.hip): the same shells
+struct bsk_gzip_reader { GzipPieceReader* r; };
+static int gzip_reader_result(bsk_gzip_reader* r, int rc) { return rc == BSK_OK ? rc : fail_global(rc, r->r->error()); }
+
+int bsk_gzip_reader_open(int fd, int device, int format, size_t piece_text_bytes, size_t lookahead_bytes, size_t segment_bytes, size_t chunk_bytes,
+                         bsk_gzip_reader** out) {
+    if (!out || (format != BSK_FORMAT_FASTA && format != BSK_FORMAT_FASTQ)) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: gzip: bad arguments");
+    *out = nullptr;
+    return shell([&](std::string& err) {
+        int rc = BSK_OK;
+        GzipPieceReader* r = gzip_reader_open(fd, device, format, piece_text_bytes, lookahead_bytes, segment_bytes, chunk_bytes, &rc, err);
+        if (r) *out = new bsk_gzip_reader{r};
+        return r ? BSK_OK : rc;
+    });
+}
+
+int bsk_gzip_reader_next(bsk_gzip_reader* r, const void** ptr, size_t* n, uint64_t* text_lo, uint64_t* text_hi, int* last) {
+    if (!r || !ptr || !n || !text_lo || !text_hi || !last) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: gzip: null argument");
+    return gzip_reader_result(r, r->r->next(ptr, n, text_lo, text_hi, last));
+}
+
+int bsk_gzip_reader_piece(bsk_gzip_reader* r, uint64_t text_lo, uint64_t text_hi, const void** ptr, size_t* n) {
+    if (!r || !ptr || !n) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: gzip: null argument");
+    return gzip_reader_result(r, r->r->piece(text_lo, text_hi, ptr, n));
+}
+
+int bsk_gzip_reader_info(bsk_gzip_reader* r, uint64_t out[8]) {
+    if (!r || !out) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: gzip: null argument");
+    r->r->info(out);
+    return BSK_OK;
+}
+
+void bsk_gzip_reader_close(bsk_gzip_reader* r) {
     if (!r) return;
     delete r->r;
     delete r;

@@ -212,8 +212,10 @@ BGZF_HD bool header_ok(Word word, uint64_t total, uint64_t pos) {
     return true;
 }
 
-// ---- the walk over blocks and members from one start.  EMIT false: sizes only (no ring); true: symbols
-template <class P, bool EMIT>
+// ---- the walk over blocks and members from one start.  EMIT false: sizes only (no ring); true: symbols.  RESUME: the buffer is
+// a segment of a file that is re-entered (gzip_stream.hpp): chunk 0 starts at the bit cand[0] like every later chunk, inside a
+// member whose start it does not know
+template <class P, bool EMIT, bool RESUME = false>
 struct Walker : bgzf::HuffCore<P, GzTables, uint64_t> {
     using Core = bgzf::HuffCore<P, GzTables, uint64_t>;
     using Core::io; using Core::S; using Core::buf; using Core::left; using Core::cnt; using Core::in_end;
@@ -377,7 +379,7 @@ struct Walker : bgzf::HuffCore<P, GzTables, uint64_t> {
         room = io.uni64(S.park.limit);
         shift = shift_ & 7u;
         int rc = bgzf::OK;
-        if (io.uni64(S.park.k) == 0) {
+        if (!RESUME && io.uni64(S.park.k) == 0) {
             uint64_t byte = 0;
             rc = member_header(byte);
             if (rc) {
@@ -481,16 +483,29 @@ struct Plan {
     }
 };
 
-inline int chunk_failure(const ChunkResult& r, uint64_t member0, std::string& err) {
+inline int chunk_failure(const ChunkResult& r, uint64_t member0, std::string& err, uint64_t file_off = 0) {
     if (r.err == (uint32_t)-1) { err = "libbsk: gzip: the input is not gzip"; return FAIL_NOT_GZIP; }
     const int code = r.err == (uint32_t)ERR_MARKER ? (int)bgzf::ERR_DISTANCE : (int)r.err;
-    err = where(member0 + r.members, r.err_bit / 8u) + error_text(code);
+    err = where(member0 + r.members, file_off + r.err_bit / 8u) + error_text(code);
     return FAIL_FORMAT;
 }
 
+// A buffer that is a segment of a file (gzip_stream.hpp): what the chain is told of the file in front of the buffer, how the
+// segment may end, and how it did end
+struct SegmentEnds {
+    int64_t open_at = 0;        // the text offset at which the open member began, from the segment's first text byte (<= 0)
+    uint64_t members = 0;       // the members in front
+    uint64_t file_off = 0;      // the file offset of the buffer: messages name offsets of the whole file
+    bool more = false;          // the file goes on behind the buffer: a chain chunk that runs into the buffer's end ends the segment
+    uint64_t text_cap = ~0ull;  // the chain is cut in front of the chunk that would bring the segment's text above this (not chunk 0)
+    // out
+    uint64_t next = NONE;       // the chunk whose start is the next resume point; NONE: the segment ends the file
+    bool grow = false;          // chunk 0 itself did not land inside the buffer: nothing was decoded
+};
+
 // the chain from chunk 0 by "landed on"; res[k].land == NONE and no error: the chunk had no candidate and was not run
 inline int walk_chain(const std::vector<uint64_t>& cand, const std::vector<ChunkResult>& res, uint64_t chunk_bytes, std::vector<ChainChunk>& chain,
-                      Plan& plan, std::string& err) {
+                      Plan& plan, std::string& err, SegmentEnds* seg = nullptr) {
     plan = Plan();
     plan.chunks = res.size();
     plan.chunk_bytes = chunk_bytes;
@@ -500,14 +515,21 @@ inline int walk_chain(const std::vector<uint64_t>& cand, const std::vector<Chunk
             ++plan.with_candidate;
             all_text += res[k].text;
         }
-    uint64_t text = 0, members = 0;
-    int64_t open_at = 0;  // text offset at which the member began that is open now
+    uint64_t text = 0, members = seg ? seg->members : 0;
+    int64_t open_at = seg ? seg->open_at : 0;  // text offset at which the member began that is open now
     for (uint64_t c = 0;;) {
         const ChunkResult& r = res[c];
+        // a segment of a file ends in front of the chunk that meets the end of the buffer -- inside a block (truncated) or behind a
+        // trailer, where the next member cannot be resumed at -- and in front of the one that brings too much text
+        if (seg && ((seg->more && (r.err == (uint32_t)bgzf::ERR_TRUNCATED || (!r.err && r.land == LAND_END))) || (c != 0 && !r.err && text + r.text > seg->text_cap))) {
+            if (c == 0) { seg->grow = true; return FAIL_NONE; }
+            seg->next = c;
+            break;
+        }
         int64_t lo = open_at - ((int64_t)text - (int64_t)WIN);
         lo = lo < 0 ? 0 : lo > (int64_t)WIN ? (int64_t)WIN : lo;
         chain.push_back(ChainChunk{c, text, r.text, members, r.members, (uint32_t)lo});
-        if (r.err) return chunk_failure(r, members, err);
+        if (r.err) return chunk_failure(r, members, err, seg ? seg->file_off : 0);
         if (r.mstart != NONE) open_at = (int64_t)(text + r.mstart);
         text += r.text;
         members += r.members;
@@ -519,6 +541,7 @@ inline int walk_chain(const std::vector<uint64_t>& cand, const std::vector<Chunk
         if (r.land == LAND_END) break;
         c = r.land;  // (always a later chunk: the walk ends)
     }
+    if (seg) seg->open_at = open_at;  // (as the segment leaves it: from ITS first text byte)
     plan.on_chain = chain.size();
     plan.off_chain = plan.with_candidate - (plan.on_chain - 1);
     plan.members = members;
@@ -542,22 +565,37 @@ inline void crc_pieces(const std::vector<MemberRec>& mem, std::vector<Piece>& pi
 }
 
 // every member's CRC32 from its pieces' and its length against the trailer.  ISIZE is the length modulo 2^32
-inline int check_members(const std::vector<MemberRec>& mem, const std::vector<Piece>& pieces, const std::vector<uint32_t>& piece_crc, std::string& err) {
+// A segment of a file (gzip_stream.hpp): what the member that is open at its start has behind it, and -- afterwards -- what the
+// member that is open at its end has; mem then holds one record more than members end in the segment, whose text_end is the
+// segment's and which is not compared
+struct OpenMember {
+    uint64_t member0 = 0, file_off = 0;  // members and bytes of the file in front of the segment
+    uint32_t crc = 0;
+    uint64_t len = 0;
+};
+inline int check_members(const std::vector<MemberRec>& mem, const std::vector<Piece>& pieces, const std::vector<uint32_t>& piece_crc, std::string& err,
+                         OpenMember* open = nullptr) {
     static const CrcAdvance A;
     size_t pi = 0;
     uint64_t begin = 0;
+    const uint64_t member0 = open ? open->member0 : 0, file_off = open ? open->file_off : 0;
     for (size_t m = 0; m < mem.size(); ++m) {
-        uint32_t crc = 0;
+        uint32_t crc = open && m == 0 ? open->crc : 0;
         for (; pi < pieces.size() && pieces[pi].member == m; ++pi) crc = A.advance(crc, pieces[pi].len) ^ piece_crc[pi];
-        const uint64_t len = mem[m].text_end - begin;
+        const uint64_t len = mem[m].text_end - begin + (open && m == 0 ? open->len : 0);
         begin = mem[m].text_end;
+        if (open && m + 1 == mem.size()) {
+            open->crc = crc;
+            open->len = len;
+            break;
+        }
         if ((uint32_t)len != mem[m].isize) {
-            err = where(m, mem[m].trailer) + bgzf::error_text((uint32_t)len < mem[m].isize ? bgzf::ERR_SHORT : bgzf::ERR_OVERRUN) + " (the member has " +
+            err = where(member0 + m, file_off + mem[m].trailer) + bgzf::error_text((uint32_t)len < mem[m].isize ? bgzf::ERR_SHORT : bgzf::ERR_OVERRUN) + " (the member has " +
                   std::to_string(len) + " bytes, ISIZE says " + std::to_string(mem[m].isize) + ")";
             return FAIL_FORMAT;
         }
         if (crc != mem[m].crc) {
-            err = where(m, mem[m].trailer) + bgzf::error_text(bgzf::ERR_CRC);
+            err = where(member0 + m, file_off + mem[m].trailer) + bgzf::error_text(bgzf::ERR_CRC);
             return FAIL_FORMAT;
         }
     }
@@ -597,10 +635,11 @@ inline uint64_t find_host(const uint8_t* comp, uint64_t n, uint64_t chunk_bytes,
 }
 
 // the W of the chain chunks: W[i * WIN + m] is the text byte at chain[i].text_off - WIN + m (0 in front of the text)
-inline void windows_host(const std::vector<ChainChunk>& chain, const uint16_t* sym, uint8_t* W) {
+// (carried: the window of a segment that is re-entered, in place of the zeros in front of a file)
+inline void windows_host(const std::vector<ChainChunk>& chain, const uint16_t* sym, uint8_t* W, const uint8_t* carried = nullptr) {
     for (size_t j = 0; j < chain.size(); ++j) {
         uint8_t* Wj = W + j * (size_t)WIN;
-        if (j == 0) { for (uint32_t m = 0; m < WIN; ++m) Wj[m] = 0; continue; }
+        if (j == 0) { for (uint32_t m = 0; m < WIN; ++m) Wj[m] = carried ? carried[m] : 0; continue; }
         const uint8_t* Wi = Wj - WIN;
         const int64_t start_i = (int64_t)chain[j - 1].text_off, start_j = (int64_t)chain[j].text_off;
         for (uint32_t m = 0; m < WIN; ++m) {

@@ -220,6 +220,11 @@ BgzfPieceReader* bgzf_reader_open(int fd, int device, int format, size_t piece, 
     return R.release();
 }
 
+int bgzf_launch_stream_cut(const uint8_t* d_text, uint64_t n, uint64_t from, int format, uint64_t* d_cut, void* stream) {
+    hipLaunchKernelGGL(k_bgzf_stream_cut, dim3(1), dim3(64), 0, (hipStream_t)stream, d_text, n, from, format, d_cut);
+    return (int)hipGetLastError();
+}
+
 int bgzf_stream_cut_run(const uint8_t* text, uint64_t n, uint64_t from, int format, int device, uint64_t* cut, std::string& err) {
     if (device < 0) {
         *cut = stream_cut(text, n, from, format);

@@ -8,6 +8,8 @@
 //   k_gz_translate  a thread per 16 bytes of text: symbols become bytes, markers through the chunk's window
 //   k_gz_crc        one wave per piece of at most 64 KiB of text, lanes take 1 KiB chunks from the piece's end (bgzf::crc_fold)
 // The host walks the chain between size and decode, and joins the CRC pieces of each member at the end: four read-backs a call.
+// The lane policy of the walks is gzip_wave_dev.hpp; the launchers at the end of the host side hand the same kernels to the
+// segment reader (ops_gzip_stream.hip), which runs them on a segment of a file.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,12 +20,14 @@
 #include "../../include/bsk.h"
 #include "codec_host.hpp"
 #include "gzip_spec_dev.hpp"
+#include "gzip_wave_dev.hpp"
 #include "ops_gzip.hpp"
 
 namespace bsk {
 namespace {
 
 using gz::ChunkResult;
+using gz::GzWaveLane;
 using gz::MemberRec;
 
 __device__ __forceinline__ uint32_t load_word(const uint8_t* __restrict__ comp, uint64_t n, uint64_t w) {
@@ -58,64 +62,6 @@ __global__ __launch_bounds__(256) void k_gz_find(const uint8_t* __restrict__ com
     if (threadIdx.x == 0) cand[k] = best;
 }
 
-// the 64 lanes of a wave that walks a chunk
-struct GzWaveLane {
-    static constexpr uint32_t LANES = 64;
-    const uint8_t* __restrict__ comp;  // a multiple of 8
-    uint64_t n;
-    uint2 held;                        // bytes [4 * held_base + 8 * lane, + 8)
-    uint32_t held_base;                // in units of 512 bytes
-    // (the lane is taken anew wherever it is asked for: what depends on it alone -- `lane < 16`, `lane < nlit` as 64-bit lane masks
-    // in scalar registers -- is otherwise computed once in front of the walk's one big loop and stays live, or spilled, through it)
-    __device__ __forceinline__ uint32_t lane() const {
-        uint32_t l = threadIdx.x;
-        asm volatile("" : "+v"(l));
-        return l;
-    }
-    __device__ __forceinline__ void sync() const { __syncthreads(); }
-    __device__ __forceinline__ uint32_t uni(uint32_t v) const { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-    __device__ __forceinline__ uint64_t uni64(uint64_t v) const { return (uint64_t)uni((uint32_t)v) | (uint64_t)uni((uint32_t)(v >> 32)) << 32; }
-    __device__ __forceinline__ uint64_t vec64(uint64_t v) const {
-        uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
-        asm volatile("" : "+v"(lo), "+v"(hi));
-        return (uint64_t)lo | (uint64_t)hi << 32;
-    }
-    __device__ __forceinline__ uint32_t word(uint64_t w) {
-        const uint32_t cb = (uint32_t)(w >> 7);
-        if (cb != held_base) {
-            held_base = cb;
-            const uint64_t at = (uint64_t)cb * 512u + threadIdx.x * 8u;
-            uint2 v = make_uint2(0u, 0u);
-            if (at + 8u <= n) v = *reinterpret_cast<const uint2*>(comp + at);
-            else {
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    const uint32_t x = at + k < n ? (uint32_t)comp[at + k] << (8 * (k & 3)) : 0u;
-                    if (k < 4) v.x |= x; else v.y |= x;
-                }
-            }
-            held = v;
-        }
-        const int j = (int)(w & 127u);
-        const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)held.x, j >> 1), hi = (uint32_t)__builtin_amdgcn_readlane((int)held.y, j >> 1);
-        return (j & 1) ? hi : lo;
-    }
-    __device__ __forceinline__ uint8_t in_byte(uint64_t a) const { return comp[a]; }
-    // symbols [a, b) of the chunk: single ones up to the first 16-byte boundary of the buffer and behind the last, 8 a lane between
-    // ((out + q) is a multiple of 16 bytes where (shift + q) is one of 8)
-    __device__ __forceinline__ void store(const uint16_t* ring, uint16_t* __restrict__ out, uint32_t shift, uint64_t a, uint64_t b) const {
-        const uint32_t l = threadIdx.x;
-        uint64_t h = a + ((8u - ((shift + (uint32_t)a) & 7u)) & 7u);
-        if (h > b) h = b;
-        if (a + l < h) out[a + l] = ring[(shift + (uint32_t)(a + l)) & gz::RING_MASK];
-        uint64_t t = b - ((shift + (uint32_t)b) & 7u);
-        if (t < h || t > b) t = h;
-        for (uint64_t q = h + 8u * l; q < t; q += 8u * LANES)
-            *reinterpret_cast<uint4*>(out + q) = *reinterpret_cast<const uint4*>(ring + ((shift + (uint32_t)q) & gz::RING_MASK));
-        if (t + l < b) out[t + l] = ring[(shift + (uint32_t)(t + l)) & gz::RING_MASK];
-    }
-};
-
 __global__ __launch_bounds__(64) void k_gz_size(const uint8_t* __restrict__ comp, const gz::Geometry* __restrict__ G, ChunkResult* __restrict__ res) {
     __shared__ gz::GzTables T;
     const uint64_t k = blockIdx.x;
@@ -130,12 +76,6 @@ __global__ __launch_bounds__(64) void k_gz_size(const uint8_t* __restrict__ comp
     const ChunkResult R = W.run(0);
     if (threadIdx.x == 0) res[blockIdx.x] = R;
 }
-
-// a chain chunk for the kernels behind the chain
-struct ChainDesc {
-    uint64_t k, text_off, text, member0;
-    uint32_t marker_lo, members;
-};
 
 __global__ __launch_bounds__(64) void k_gz_decode(const uint8_t* __restrict__ comp, const gz::Geometry* __restrict__ G,
                                                   const ChainDesc* __restrict__ chain, uint16_t* __restrict__ sym, MemberRec* __restrict__ mem,
@@ -250,6 +190,35 @@ int fail_code(int f) { return f == gz::FAIL_UNSUPPORTED ? BSK_ERR_UNSUPPORTED : 
 }  // namespace
 
 void gzip_last_plan(uint64_t out[8]) { g_plan.to(out); }
+
+// ---- the kernels for the segment reader (ops_gzip.hpp): nothing is launched over an empty grid
+int gzip_launch_find(const void* d_comp, uint64_t n, uint64_t chunk_bytes, uint64_t nchunks, uint64_t* d_cand, void* stream) {
+    if (nchunks > 1) hipLaunchKernelGGL(k_gz_find, dim3((unsigned)(nchunks - 1)), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)d_comp, n, chunk_bytes, d_cand);
+    return (int)hipGetLastError();
+}
+int gzip_launch_size(const void* d_comp, const gz::Geometry* d_geo, uint64_t nchunks, ChunkResult* d_res, void* stream) {
+    if (nchunks) hipLaunchKernelGGL(k_gz_size, dim3((unsigned)nchunks), dim3(64), 0, (hipStream_t)stream, (const uint8_t*)d_comp, d_geo, d_res);
+    return (int)hipGetLastError();
+}
+int gzip_launch_decode(const void* d_comp, const gz::Geometry* d_geo, const ChainDesc* d_chain, uint64_t nchain, uint16_t* d_sym, MemberRec* d_mem,
+                       ChunkResult* d_res, void* stream) {
+    if (nchain) hipLaunchKernelGGL(k_gz_decode, dim3((unsigned)nchain), dim3(64), 0, (hipStream_t)stream, (const uint8_t*)d_comp, d_geo, d_chain, d_sym, d_mem, d_res);
+    return (int)hipGetLastError();
+}
+int gzip_launch_windows(const ChainDesc* d_chain, uint64_t nchain, const uint16_t* d_sym, uint8_t* d_W, void* stream) {
+    if (nchain > 1) hipLaunchKernelGGL(k_gz_windows, dim3(1), dim3(1024), 0, (hipStream_t)stream, d_chain, nchain, d_sym, d_W);
+    return (int)hipGetLastError();
+}
+int gzip_launch_translate(const ChainDesc* d_chain, uint64_t nchain, const uint16_t* d_sym, const uint8_t* d_W, uint8_t* d_text, uint64_t total,
+                          unsigned long long* d_status, void* stream) {
+    const uint64_t threads = (total + 15) / 16;
+    if (total && nchain) hipLaunchKernelGGL(k_gz_translate, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_chain, nchain, d_sym, d_W, d_text, total, d_status);
+    return (int)hipGetLastError();
+}
+int gzip_launch_crc(const uint8_t* d_text, const gz::Piece* d_pieces, uint64_t npieces, const uint32_t* d_mat, uint32_t* d_out, void* stream) {
+    if (npieces) hipLaunchKernelGGL(k_gz_crc, dim3((unsigned)npieces), dim3(64), 0, (hipStream_t)stream, d_text, d_pieces, d_mat, d_out);
+    return (int)hipGetLastError();
+}
 
 void gzip_find_host(const void* comp, size_t n, size_t chunk_bytes, uint64_t* cand, size_t nchunks) {
     for (size_t k = 0; k < nchunks; ++k) cand[k] = k ? gz::find_host((const uint8_t*)comp, n, chunk_bytes, k) : gz::NONE;

@@ -312,8 +312,10 @@ int sniff_format(const std::string& file_, const std::string& data) {
 
 // ---- compressed input (PARITY.md BGZF, GZIP): BGZF is inflated, on the device where the part lives there; any other gzip is
 // refused unless BSK_GZIP=1 asks for it: then it is read wherever a BGZF file is read whole (bsk_gzip_load on the device, the same
-// method on the host for the commands that keep host strings).  The paths that read a file in pieces still refuse it: a gzip
-// stream has no virtual offsets to re-enter at.
+// method on the host for the commands that keep host strings).  The paths that read a file in pieces refuse it -- unless
+// BSK_GZIP_STREAM=1 is set as well: then `stats` on a file that is not read whole and the bucket paths read it through the
+// segment reader (bsk_gzip_reader_*), which re-enters the stream at the block starts it has recorded; its positions are text
+// offsets.  Without that switch every exit status and every byte of stderr is as before.
 // The paths for inputs that are not loaded whole read a BGZF file in pieces (bsk_bgzf_reader_*) only when asked to:
 // BSK_BGZF_STREAM=1.  Every pass over the input inflates the file again -- a bucket command reads it 2 + B times and more --, which
 // a user should choose knowingly; without the switch these paths refuse a compressed file as before, and the message names it
@@ -363,15 +365,17 @@ static bool stats_streams(const std::string& use, size_t size) { return use == "
 //   Device    a file that goes to the GPU whole (read_parts), or -- `stats` on a file that does not fit -- is streamed
 //   Buckets   the bucket paths (run_buckets), which read a file in pieces
 //   Devices   --devices, which cuts a file by its bytes
-// Returns whether a BGZF file may be read in pieces (BSK_BGZF_STREAM=1); the refusals of plain gzip come first, over all files
+// Returns whether a BGZF file may be read in pieces (BSK_BGZF_STREAM=1), and in *gzip_pieces whether a plain gzip file may
+// (BSK_GZIP=1 BSK_GZIP_STREAM=1: read here and nowhere else); the refusals of plain gzip come first, over all files
 enum class Route { Any, HostText, Device, Buckets, Devices };
-bool admit(const std::vector<Input>& ins, Route route, const std::string& use = "") {
+bool admit(const std::vector<Input>& ins, Route route, const std::string& use = "", bool* gzip_pieces = nullptr) {
     static const char* const kPlainGzip = " is gzip but not BGZF: one gzip stream cannot be cut into independent blocks, so it is not read; "
                                           "recompress it with bgzip (gzip -dc FILE | bgzip > FILE.gz) or decompress it first, or set BSK_GZIP=1 "
                                           "to have it inflated whole, in speculative chunks, where the file and its text fit one GPU";
     static const char* const kStreamHint = ", or set BSK_BGZF_STREAM=1 to read it in record-aligned pieces, inflated once per pass";
     auto switch_on = [](const char* name) { const char* e = getenv(name); return e && *e && strcmp(e, "0") != 0; };
-    const bool gzip = switch_on("BSK_GZIP"), pieces = switch_on("BSK_BGZF_STREAM");
+    const bool gzip = switch_on("BSK_GZIP"), pieces = switch_on("BSK_BGZF_STREAM"), segments = gzip && switch_on("BSK_GZIP_STREAM");
+    if (gzip_pieces) *gzip_pieces = segments;
     // the routes that read a file by its bytes or in pieces: what they do, and what to do about a BGZF file instead
     std::string gzip_where, bgzf_where, instead;
     if (route == Route::Device) {
@@ -390,7 +394,10 @@ bool admit(const std::vector<Input>& ins, Route route, const std::string& use = 
         if (in.missing && (route != Route::Any || !gzip)) die("open " + in.path + ": no such file or directory");
         if (in.kind != kGzip) continue;
         if (!gzip) die(in.path + kPlainGzip);  // (read by no path without the switch)
-        if (by_bytes(in))
+        if (by_bytes(in) && segments && route == Route::Devices)
+            die(in.path + " is gzip but not BGZF, and --devices cuts a file by its bytes: where a worker starts in a gzip stream is known only after a pass over "
+                "the stream in front of it, so BSK_GZIP_STREAM=1 reads it in pieces on one device only; run it on one device (--device N), or decompress it first (gzip -d)");
+        if (by_bytes(in) && !segments)
             die(in.path + " is gzip but not BGZF, and " + gzip_where + " a file in pieces: a gzip stream has no virtual offsets to re-enter at, so BSK_GZIP=1 "
                 "reads it only where a file is read whole; decompress it first (gzip -d), or recompress it with bgzip (gzip -dc FILE | bgzip > FILE.gz)");
     }
@@ -445,6 +452,29 @@ struct BgzfSizes { size_t piece, look, chunk; };
 BgzfSizes bgzf_sizes() {
     auto env = [](const char* name) { const char* e = getenv(name); return e ? (size_t)strtoull(e, nullptr, 10) : (size_t)0; };
     return {env("BSK_STREAM_PIECE_BYTES"), env("BSK_BGZF_LOOKAHEAD_BYTES"), env("BSK_BGZF_CHUNK_BYTES")};
+}
+
+// the sizes of the gzip segment reader (bsk_gzip_reader_open; 0: its defaults)
+struct GzipSizes { size_t piece, look, segment, chunk; };
+GzipSizes gzip_sizes() {
+    auto env = [](const char* name) { const char* e = getenv(name); return e ? (size_t)strtoull(e, nullptr, 10) : (size_t)0; };
+    return {env("BSK_STREAM_PIECE_BYTES"), env("BSK_GZIP_LOOKAHEAD_BYTES"), env("BSK_GZIP_SEGMENT_BYTES"), env("BSK_GZIP_CHUNK_BYTES")};
+}
+
+// The first byte of a gzip file's text (0: it has none): the reader on the host, in small segments, asked for one byte -- what
+// sniff_format asks of a file that is not read whole
+char gzip_first_text_byte(const std::string& path) {
+    const int fd = open(path.c_str(), O_RDONLY);
+    if (fd < 0) die("open " + path + ": no such file or directory");
+    bsk_gzip_reader* rd = nullptr;
+    if (bsk_gzip_reader_open(fd, -1, BSK_FORMAT_FASTA, 1, 1, (size_t)64 << 10, (size_t)16 << 10, &rd) != BSK_OK) die(path + ": " + bsk_global_error());
+    const void* p = nullptr;
+    size_t n = 0;
+    char first = 0;
+    if (bsk_gzip_reader_piece(rd, 0, 1, &p, &n) == BSK_OK && n == 1) first = *(const char*)p;  // (an empty text, or a bad file: the pass over it says so)
+    bsk_gzip_reader_close(rd);
+    close(fd);
+    return first;
 }
 
 // `text` as read from a file or a pipe: inflated in place when it is compressed -- BGZF on host threads with the decoder of the
@@ -703,6 +733,8 @@ struct Part {
     // ... and a BGZF file of that size: the open file, which `stats` reads through the piece reader (bsk_bgzf_reader_*: the text
     // arrives in record-aligned pieces on the device, the file is never held whole)
     int bgzf_fd = -1;
+    // ... and a plain gzip file of that size (BSK_GZIP_STREAM=1): the segment reader (bsk_gzip_reader_*), in the same way
+    int gzip_fd = -1;
     const void* ptr() const { return dptr ? dptr : (map ? map : (const void*)host.data()); }
     size_t size() const { return dptr ? n : (map ? map_n : host.size()); }
     int on_device() const { return dptr ? 1 : 0; }
@@ -714,7 +746,8 @@ void release(std::vector<Part>& parts) {
         else if (p.owned_alloc && p.dptr) bsk_device_free(p.dptr);
         if (p.map) munmap(const_cast<void*>(p.map), p.map_n);
         if (p.bgzf_fd >= 0) close(p.bgzf_fd);
-        p.owner = nullptr; p.dptr = nullptr; p.map = nullptr; p.bgzf_fd = -1;
+        if (p.gzip_fd >= 0) close(p.gzip_fd);
+        p.owner = nullptr; p.dptr = nullptr; p.map = nullptr; p.bgzf_fd = p.gzip_fd = -1;
     }
     parts.clear();
 }
@@ -822,6 +855,19 @@ Output execute(const Invocation& inv, std::vector<Part>& inputs, bool keep_on_de
                     if (n && bsk_stats_run(sc, p, n, 1, in.fmt, pid, nullptr, nullptr) != BSK_OK) die(bsk_last_error(sc));
                 }
                 bsk_bgzf_reader_close(rd);  // (waits for the kernels that still read the last pieces)
+            } else if (in.gzip_fd >= 0) {  // the same over the segment reader: the pass checks every member's CRC32 and ISIZE
+                const GzipSizes z = gzip_sizes();
+                bsk_gzip_reader* rd = nullptr;
+                if (bsk_gzip_reader_open(in.gzip_fd, device, in.fmt, z.piece, z.look, z.segment, z.chunk, &rd) != BSK_OK) die(bsk_global_error());
+                int last = 0;
+                for (int64_t pid = 0; !last; ++pid) {
+                    const void* p = nullptr;
+                    size_t n = 0;
+                    uint64_t lo = 0, hi = 0;
+                    if (bsk_gzip_reader_next(rd, &p, &n, &lo, &hi, &last) != BSK_OK) die(bsk_global_error());
+                    if (n && bsk_stats_run(sc, p, n, 1, in.fmt, pid, nullptr, nullptr) != BSK_OK) die(bsk_last_error(sc));
+                }
+                bsk_gzip_reader_close(rd);
             } else if (bsk_stats_run(sc, in.ptr(), in.size(), in.on_device(), in.fmt, 0, nullptr, nullptr) != BSK_OK) die(bsk_last_error(sc));
             std::vector<int64_t> keys(1 << 20), vals(1 << 20);
             size_t n = 0;
@@ -1038,9 +1084,16 @@ std::vector<Part> read_parts(const std::vector<Input>& inputs, int device = -1, 
             inflate_host_text(f, p.host);
             p.fmt = sniff_format(f, p.host);
         } else {
-            const bool pieces = admit({in}, Route::Device, use);
+            bool segments = false;
+            const bool pieces = admit({in}, Route::Device, use, &segments);
             const int fd = open(f.c_str(), O_RDONLY);
             if (fd < 0) die("open " + f + ": no such file or directory");
+            if (in.kind == kGzip && stats_streams(use, in.size)) {  // (admitted: BSK_GZIP_STREAM=1) stats: the segment reader streams its text (execute)
+                p.fmt = sniff_format(f, std::string(1, gzip_first_text_byte(f)));
+                p.gzip_fd = fd;
+                parts.push_back(std::move(p));
+                continue;
+            }
             if (in.kind == kBgzf && stats_streams(use, in.size)) {
                 // stats: the file stays where it is, the piece reader streams its text in record-aligned pieces (execute)
                 p.fmt = sniff_format(f, std::string(1, bgzf_first_text_byte(f)));
@@ -1049,9 +1102,16 @@ std::vector<Part> read_parts(const std::vector<Input>& inputs, int device = -1, 
                 continue;
             }
             if (in.kind != kPlain) {  // compressed across PCIe, inflated in HBM: from here on an ordinary device part
-                if (in.kind == kGzip && bsk_gzip_load(fd, device, 0, 0, &p.dptr, &p.n) != BSK_OK)  // (whole: there are no pieces of it)
+                if (in.kind == kGzip && bsk_gzip_load(fd, device, 0, 0, &p.dptr, &p.n) != BSK_OK) {  // (whole, unless its pieces were asked for)
+                    if (bucket_budget(use) > 0 && segments) {
+                        close(fd);
+                        g_buckets_unfit = true;
+                        release(parts);
+                        return parts;
+                    }
                     die(f + ": " + bsk_global_error() + " -- a gzip file is inflated whole on one device: it, its text and twice its text in symbols must fit there; "
                         "decompress it first (gzip -d), or recompress it with bgzip to use the paths for larger inputs");
+                }
                 if (in.kind == kBgzf && bsk_bgzf_load(fd, device, 0, &p.dptr, &p.n) != BSK_OK) {
                     if (bucket_budget(use) > 0 && pieces) {  // (as for a plain file that does not fit: through the buckets, piece by piece)
                         close(fd);
@@ -1294,11 +1354,15 @@ struct MappedFile {
     bool mapped = false;
     // a BGZF file of the bucket paths is not mapped: its pieces are virtual-offset ranges, inflated on the device when asked for
     bsk_bgzf_reader* reader = nullptr;
+    // ... nor is a plain gzip file (BSK_GZIP_STREAM=1): its pieces are ranges of text offsets, asked of the segment reader
+    bsk_gzip_reader* gzip_reader = nullptr;
     int fd = -1;
     void unmap() {
         if (mapped && size) munmap((void*)text, size);
         mapped = false;
         if (reader) bsk_bgzf_reader_close(reader);
+        if (gzip_reader) bsk_gzip_reader_close(gzip_reader);
+        gzip_reader = nullptr;
         if (fd >= 0) close(fd);
         reader = nullptr;
         fd = -1;
@@ -1408,7 +1472,9 @@ Output run_head_genome(const Invocation& inv) {
 //             weights, once per window and once more with -f
 // A BGZF input is refused as before unless BSK_BGZF_STREAM=1 asks for it.  Then it is not mapped: the piece reader (bsk_bgzf_reader_*) runs over it once and lists its pieces as ranges of virtual
 // offsets, and every later pass asks the reader for the piece again -- inflated on the device, handed over as a device shard.  The
-// file is inflated once per pass.  Plain and BGZF inputs may be mixed.
+// file is inflated once per pass.  A plain gzip input (BSK_GZIP=1 BSK_GZIP_STREAM=1) goes the same way through the segment reader
+// (bsk_gzip_reader_*), its pieces ranges of text offsets; the listing pass checks every member's CRC32 and ISIZE, so a corrupt file
+// is refused before a byte of output is written.  Plain, BGZF and gzip inputs may be mixed.
 // Every finished bucket is appended to the output.  A piece never spans two files, so a file that ends without a newline
 // behaves like the union of the whole-file path: its last record gets the newline.
 // The steps are written once: map_pieces (the files, their format and the pieces), plan_buckets (the passes in front of the buckets
@@ -1419,8 +1485,10 @@ struct BucketRun {
     bsk_ctx* ctx = nullptr;
     uint64_t budget = 0;
     Output res;
-    // host bytes, or (p == nullptr) the range [vlo, vhi) of virtual offsets of a BGZF file, n bytes of text
-    struct Piece { const uint8_t* p; size_t n; uint64_t first; size_t file; uint64_t count; uint64_t vlo = 0, vhi = 0; bool bgzf = false; };
+    // host bytes, or (p == nullptr) n bytes of text that a reader is asked for: the range [vlo, vhi) of virtual offsets of a BGZF
+    // file, or of text offsets of a plain gzip file
+    enum PieceKind { kHostBytes, kBgzfRange, kGzipRange };
+    struct Piece { const uint8_t* p; size_t n; uint64_t first; size_t file; uint64_t count; uint64_t vlo = 0, vhi = 0; PieceKind kind = kHostBytes; };
     struct View { const void* p; size_t n; int on_device; };
     std::vector<MappedFile> files;
     std::vector<Piece> pieces;
@@ -1435,10 +1503,12 @@ struct BucketRun {
     // what an operator is handed for a piece: the mapped bytes, or the piece inflated on the device (valid until the second
     // view of a piece of the same file after it)
     View view(const Piece& pc) {
-        if (!pc.bgzf) return {pc.p, pc.n, 0};
+        if (pc.kind == kHostBytes) return {pc.p, pc.n, 0};
         const void* p = nullptr;
         size_t n = 0;
-        if (bsk_bgzf_reader_piece(files[pc.file].reader, pc.vlo, pc.vhi, &p, &n) != BSK_OK) die(bsk_global_error());
+        if ((pc.kind == kGzipRange ? bsk_gzip_reader_piece(files[pc.file].gzip_reader, pc.vlo, pc.vhi, &p, &n)
+                                   : bsk_bgzf_reader_piece(files[pc.file].reader, pc.vlo, pc.vhi, &p, &n)) != BSK_OK)
+            die(bsk_global_error());
         return {p, n, 1};
     }
     // the files mapped, of one format, and cut into record-aligned pieces; a piece never spans two files
@@ -1462,7 +1532,25 @@ struct BucketRun {
                     Piece pc{nullptr, 0, 0, fi, 0};
                     const void* p = nullptr;
                     if (bsk_bgzf_reader_next(f.reader, &p, &pc.n, &pc.vlo, &pc.vhi, &last) != BSK_OK) die(path + ": " + bsk_global_error());
-                    pc.bgzf = true;
+                    pc.kind = kBgzfRange;
+                    total_bytes += pc.n;
+                    if (pc.n) pieces.push_back(pc);
+                }
+                continue;
+            }
+            if (ins[fi].kind == kGzip) {  // (admitted: BSK_GZIP_STREAM=1) the listing pass reads the whole file and checks every member
+                f.fd = open(path.c_str(), O_RDONLY);
+                if (f.fd < 0) die("open " + path + ": no such file or directory");
+                const int ffmt = sniff_format(path, std::string(1, gzip_first_text_byte(path)));
+                if (fmt >= 0 && ffmt != fmt) die(std::string(cmd.use) + ": inputs of different formats");
+                fmt = ffmt;
+                const GzipSizes z = gzip_sizes();
+                if (bsk_gzip_reader_open(f.fd, device, fmt, z.piece, z.look, z.segment, z.chunk, &f.gzip_reader) != BSK_OK) die(path + ": " + bsk_global_error());
+                for (int last = 0; !last;) {
+                    Piece pc{nullptr, 0, 0, fi, 0};
+                    const void* p = nullptr;
+                    if (bsk_gzip_reader_next(f.gzip_reader, &p, &pc.n, &pc.vlo, &pc.vhi, &last) != BSK_OK) die(path + ": " + bsk_global_error());
+                    pc.kind = kGzipRange;
                     total_bytes += pc.n;
                     if (pc.n) pieces.push_back(pc);
                 }
@@ -1725,7 +1813,7 @@ Output run_buckets(const Invocation& inv, const std::vector<Input>& ins) {
         if (inv.files.size() < 2) die("2 files needed");
         if (outdir.empty()) die("out-dir required");
     }
-    admit(ins, Route::Buckets, use);  // (plain gzip has no pieces, with or without the switches: said before a device is touched)
+    admit(ins, Route::Buckets, use);  // (plain gzip has pieces only with BSK_GZIP_STREAM=1: said before a device is touched)
     const int device = (int)strtol(inv.pget("device").c_str(), nullptr, 10);
     BucketRun R{*bucket_cmd(use)};
     R.res.packed = !pair && packs_on_device(inv);  // (pair -O writes its four files under fixed names: plain)

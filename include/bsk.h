@@ -269,6 +269,48 @@ void bsk_bgzf_reader_close(bsk_bgzf_reader* r);
 /* Where the reader's kernel cuts text[0, n) (host memory) from `from`: bsk_find_record_start's answer, n where neither finds a
  * start, or ~0: declined, the host rule decides.  device = -1: the same function on the host.  For the tests. */
 int bsk_selftest_bgzf_stream_cut(const void* text, size_t n, size_t from, int format, int device, uint64_t* cut);
+/* ---- a plain gzip file of any size as record-aligned pieces (PARITY.md GZIP "segments"; gzip_stream.hpp, ops_gzip_stream.hip) ----
+ * bsk_gzip_load holds the file, its text and twice its text in symbols on one device.  The reader holds a SEGMENT of the file
+ * at a time instead: segment_bytes of compressed data from a RESUME POINT -- a bit position at which a non-final dynamic block
+ * starts, where the chain of the speculative method has landed, with the 32 KiB of text in front of it, the open member's
+ * number, start, CRC and length so far -- decoded by the same steps (find, size, chain, decode, windows, translate, crc), chunk 0
+ * starting at the resume bit.  A segment ends in front of the chain chunk that runs into the end of its buffer, or that would
+ * bring its text above 8 times segment_bytes; that chunk's start is the next resume point.  Memory follows the sizes given
+ * here, not the file.  device >= 0: the pieces lie in the memory of that device, segment k + 1 is read (pread) and copied under
+ * the decode of segment k; device = -1: the same reader with host buffers and one host lane, the same pieces.  `fd` stays the
+ * caller's.  0 for a size means 1 GiB of text, 1 MiB of lookahead, 64 MiB of compressed bytes, and for chunk_bytes the rule of
+ * bsk_gzip_inflate_device applied to a segment (host: a sixteenth of it); sizes are rounded as there; a segment holds at least 2 KiB.
+ *
+ * A stream in which no non-final dynamic block starts inside a segment -- stored or fixed blocks only, one very long block --
+ * makes the segment double, up to 32 times segment_bytes: then BSK_ERR_CAPACITY with the sizes (never another answer).
+ *
+ * Positions are TEXT OFFSETS; a piece is [text_lo, text_hi).  Which pieces: a function of the text alone, not of the segment
+ * size, the chunk size or the device.  From the piece's start s the window is text[s, min(s + piece_text_bytes +
+ * lookahead_bytes, end)); if it reaches the end of the text the piece is the rest, else the piece ends at the answer of
+ * bsk_find_record_start on the window from piece_text_bytes; no start in the window: the lookahead doubles.
+ *
+ *   bsk_gzip_reader_next    the next piece: *ptr (device or host memory, as opened; a multiple of 256), *n bytes, its offsets,
+ *                           *last != 0 with the piece that ends the text.  THE SEQUENTIAL PASS CHECKS CRC32 AND ISIZE of every
+ *                           member, at the call that decodes its trailer.  Validity of a piece as for bsk_bgzf_reader_next: until
+ *                           the second call of next / piece after the one that gave it
+ *   bsk_gzip_reader_piece   the bytes [text_lo, text_hi) again.  The reader re-enters at the last resume point it has recorded
+ *                           (one per segment start, 32 KiB and a few words each, in host memory) at or in front of text_lo and
+ *                           decodes forward; consecutive pieces are read on without re-entry.  It checks the DEFLATE stream only
+ *   bsk_gzip_reader_info    segments decoded, access points, buffer doublings, chain chunks dropped, members, text bytes so far,
+ *                           peak bytes of the reader's buffers, chunk size used
+ *   bsk_gzip_reader_close   waits for the device, then frees the buffers: no piece is valid afterwards
+ * Refusals: those of plain gzip input above, members and offsets counted over the whole file.  Stages of bsk_profile_dump: the
+ * gzip_* stages above and gzip_stream_cut.  On the command line BSK_GZIP=1 BSK_GZIP_STREAM=1 sends `stats` on a file that is not
+ * read whole and the bucket paths (BSK_<COMMAND>_BUDGET_BYTES) through this reader; BSK_STREAM_PIECE_BYTES, BSK_GZIP_LOOKAHEAD_BYTES,
+ * BSK_GZIP_SEGMENT_BYTES and BSK_GZIP_CHUNK_BYTES set the sizes.  Errors: bsk_global_error(); after one the reader answers with
+ * it until a piece is asked for by its offsets. */
+typedef struct bsk_gzip_reader bsk_gzip_reader;
+int bsk_gzip_reader_open(int fd, int device, int format, size_t piece_text_bytes, size_t lookahead_bytes, size_t segment_bytes, size_t chunk_bytes,
+                         bsk_gzip_reader** out);
+int bsk_gzip_reader_next(bsk_gzip_reader* r, const void** ptr, size_t* n, uint64_t* text_lo, uint64_t* text_hi, int* last);
+int bsk_gzip_reader_piece(bsk_gzip_reader* r, uint64_t text_lo, uint64_t text_hi, const void** ptr, size_t* n);
+int bsk_gzip_reader_info(bsk_gzip_reader* r, uint64_t out[8]);
+void bsk_gzip_reader_close(bsk_gzip_reader* r);
 /* ---- BGZF output (PARITY.md BGZFW; ops_bgzf_write.hip, bgzf_deflate_dev.hpp) ----
  * A text becomes the BGZF file that holds it: blocks of `block_text_bytes` of text (0: 65 280, bgzip's size; at most
  * 65 280), each encoded by one wavefront -- LZ77 matches inside the block, dynamic Huffman codes per block, and per block the
