@@ -9,7 +9,7 @@ from .options import (SeqKitConfig, SeqKitStatsOptions, SeqKitSeqOptions, SeqKit
                       SeqKitLocateOptions, SeqKitSubseqOptions, SeqKitTranslateOptions, SeqKitRmDupOptions,
                       SeqKitFq2FaOptions, SeqKitRangeOptions, SeqKitHeadOptions, SeqKitDuplicateOptions, SeqKitRenameOptions, SeqKitSortOptions, SeqKitFaidxOptions, SeqKitPairOptions, SeqKitCommonOptions, SeqKitConcatOptions, SeqKitReplaceOptions, SeqKitFa2FqOptions, SeqKitSampleOptions,
                       SeqKitShuffleOptions, SeqKitHeadGenomeOptions)
-from .api import (SeqFrame, BgzfProbe, BgzfInflate, GzipInflate, GzipPlan, BgzfBlocks, BgzfReader, GzipReader, BgzfDeflate, BgzfDeflateHost, ReadSeqFile, WriteSeqFile, ReadFASTA, ReadFASTAN, ReadFASTQ, ReadFASTQN, Operator, Stats, StatsString,  # noqa: F401
+from .api import (SeqFrame, BgzfProbe, BgzfInflate, GzipInflate, GzipPlan, BgzfBlocks, BgzfReader, BgzfCutPoints, BgzfShardLoad,GzipReader, BgzfDeflate, BgzfDeflateHost, ReadSeqFile, WriteSeqFile, ReadFASTA, ReadFASTAN, ReadFASTQ, ReadFASTQN, Operator, Stats, StatsString,  # noqa: F401
                   stats_map, Seq, build_index, Grep, GrepCount, Subseq, Translate, RmDup, Locate, Fq2Fa, Range, Head,
                   Duplicate, Count, Rename, Sort, Faidx, Pair, Common, Concat, FaidxQuery, Replace, Fa2Fq, Sample, Shuffle, ShuffleBuckets, ShuffleHistRun, ShuffleHistGet, ShuffleHistReset, ShufflePlan, ShuffleBucket, HeadGenome,
                   SortBuckets, SortBucketsPlan, SortBucket, SortSampleRun, SortSampleReset, SortSampleCount, SortPickSplitters, SortSplittersBuild,

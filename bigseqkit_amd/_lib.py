@@ -219,7 +219,9 @@ SIGNATURES = {
     "bsk_bgzf_load": (_i, [_i, _i, _i, _p(_vp), _p(_sz)]),
     "bsk_bgzf_blocks_device": (_i, [_vp, _sz, _i, _p(C.c_uint64), _p(C.c_uint32), _p(C.c_uint32), _sz, _p(_sz)]),
     "bsk_bgzf_inflate_host": (_i, [C.c_char_p, _sz, _vp, _sz, _p(_sz), _i]),
-    "bsk_selftest_bgzf_crc": (C.c_uint32, [C.c_char_p, _sz]),
+    "bsk_bgzf_cut_points": (_i, [_i, _i, _i, _p(_u64)]),
+    "bsk_bgzf_shard_load": (_i, [_i, _u64, _u64, _i, _i, _p(_vp), _p(_sz)]),
+    "bsk_selftest_bgzf_crc":(C.c_uint32, [C.c_char_p, _sz]),
     "bsk_gzip_inflate_device": (_i, [_vp, _sz, _i, _sz, _p(_vp), _p(_sz)]),
     "bsk_gzip_load": (_i, [_i, _i, _i, _sz, _p(_vp), _p(_sz)]),
     "bsk_gzip_inflate_host": (_i, [C.c_char_p, _sz, _vp, _sz, _p(_sz), _sz]),

@@ -404,6 +404,27 @@ def ReadSeqFile(path, device=0, gzip=False):
     return SeqFrame(_format_of(path, bytes(t[:1].cpu().numpy().tobytes())), [t])
 
 
+# ---- a BGZF file under several workers (include/bsk.h "BGZF under several workers"; PARITY.md BGZF "workers")
+def BgzfCutPoints(path, format, world):
+    """where `world` workers cut the BGZF file `path`: world + 1 virtual offsets, worker k owns the text [v[k], v[k + 1]).
+    Found on the host from the file around size * k / world (bsk_bgzf_cut_points); no device is touched"""
+    voffs = (C.c_uint64 * (world + 1))()
+    with open(os.fspath(path), "rb") as f:
+        check(lib.bsk_bgzf_cut_points(f.fileno(), format, world, voffs))
+    return [int(v) for v in voffs]
+
+
+def BgzfShardLoad(path, voff_lo, voff_hi, device=0):
+    """the text [voff_lo, voff_hi) of the BGZF file `path` as a SeqFrame over one shard on `device`: only the blocks of the range
+    cross to the device, where they are inflated (bsk_bgzf_shard_load).  The offsets are BgzfCutPoints'.  An empty shard takes
+    its format from the file's name"""
+    d_text, n_text = C.c_void_p(), C.c_size_t()
+    with open(os.fspath(path), "rb") as f:
+        check(lib.bsk_bgzf_shard_load(f.fileno(), voff_lo, voff_hi, device, 0, C.byref(d_text), C.byref(n_text)))
+    t = _adopt(d_text, n_text.value, device)
+    return SeqFrame(_format_of(path, bytes(t[:1].cpu().numpy().tobytes())), [t])
+
+
 class Operator:
     """One plugin operator between Before() and After() (bsk_create .. bsk_destroy)."""
 

@@ -5,18 +5,22 @@
 // into the helpers behind "the key-bucket family" below, which look the operator up in one row per Op.
 #include <hip/hip_runtime_api.h>
 
+#include <sys/stat.h>
 #include <unistd.h>
 
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <new>
 #include <optional>
+#include <unordered_map>
 
 #include "../../include/bsk.h"
 #include "anchor.hpp"
 #include "ctx.hpp"
+#include "bgzf_cuts.hpp"
 #include "bgzf_stream.hpp"
 #include "gzip_stream.hpp"
 #include "codec_host.hpp"
@@ -715,8 +719,22 @@ void* bsk_device_alloc(size_t n) {
     return p;
 }
 
+// a buffer that was handed out at an offset into its allocation (bsk_bgzf_shard_load: the shard's first byte behind its room) is
+// remembered with the allocation's base, so that the caller frees what it was given
+static std::mutex g_offset_mu;
+static std::unordered_map<void*, void*> g_offset_base;
+
 void bsk_device_free(void* p) {
-    if (p) hipFree(p);
+    if (!p) return;
+    {
+        std::lock_guard<std::mutex> g(g_offset_mu);
+        const auto it = g_offset_base.find(p);
+        if (it != g_offset_base.end()) {
+            p = it->second;
+            g_offset_base.erase(it);
+        }
+    }
+    hipFree(p);
 }
 
 int bsk_device_copy(void* dst, const void* src, size_t n, int kind) {
@@ -761,6 +779,34 @@ int bsk_bgzf_blocks_device(const void* d_comp, size_t n_comp, int device, uint64
 int bsk_bgzf_inflate_host(const void* comp, size_t n_comp, void* out, size_t cap, size_t* n_out, int threads) {
     if (!n_out || (!comp && n_comp)) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bgzf: null argument");
     return shell([&](std::string& err) { return bgzf_inflate_host(comp, n_comp, out, cap, n_out, threads, err); });
+}
+
+// ---- a BGZF file under several workers (bgzf_cuts.hpp: the host rule; ops_bgzf.hip: a worker's shard)
+int bsk_bgzf_cut_points(int fd, int format, int world, uint64_t* voffs) {
+    struct stat sb;
+    if (fd < 0 || !voffs || world < 1 || (format != BSK_FORMAT_FASTA && format != BSK_FORMAT_FASTQ)) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bgzf: bad arguments");
+    if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bgzf: the cut points need a regular file");
+    BgzfCutter cutter([fd](uint64_t off, size_t len, uint8_t* dst) {
+        size_t at = 0;
+        while (at < len) {
+            const ssize_t k = pread(fd, dst + at, len - at, (off_t)(off + at));
+            if (k <= 0) return false;
+            at += (size_t)k;
+        }
+        return true;
+    }, (uint64_t)sb.st_size, format);
+    const int rc = cutter.cut_points(world, voffs);
+    return rc == BSK_OK ? rc : fail_global(rc, cutter.error());
+}
+
+int bsk_bgzf_shard_load(int fd, uint64_t voff_lo, uint64_t voff_hi, int device, int threads, void** d_text, size_t* n_text) {
+    if (!d_text || !n_text || fd < 0) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bgzf: bad arguments");
+    void* base = nullptr;
+    const int rc = shell([&](std::string& err) { return bgzf_shard_load(fd, voff_lo, voff_hi, device, threads, &base, d_text, n_text, err); });
+    if (rc != BSK_OK) return rc;
+    std::lock_guard<std::mutex> g(g_offset_mu);
+    g_offset_base[*d_text] = base;
+    return BSK_OK;
 }
 
 // ---- plain gzip input (ops_gzip.hip, gzip_spec_dev.hpp): thin shells as for BGZF

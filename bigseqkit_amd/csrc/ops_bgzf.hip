@@ -6,7 +6,13 @@
 //                   entries in scalar registers), the lanes share the copies, the table fills and the CRC.  The compressed
 //                   bytes come 512 at a time, 8 per lane, and are handed out with v_readlane; the window is a 32 KiB ring in
 //                   LDS, from which finished bytes leave in aligned 16-byte stores.  No match ever reads global memory.
+// A worker's shard of a file under --devices (bgzf_shard_load; row f20) is the same three kernels on the blocks of its range:
+// the walk starts at the shard's first block and must pass through the next worker's (the join check), and k_bgzf_desc moves
+// the text offsets so that the shard's first byte lands behind 64 KiB of room, a multiple of 256.
 #include <hip/hip_runtime.h>
+
+#include <sys/stat.h>
+#include <unistd.h>
 
 #include <algorithm>
 #include <atomic>
@@ -158,24 +164,39 @@ __global__ __launch_bounds__(64) void k_bgzf_inflate(const uint8_t* __restrict__
     if (rc != bgzf::OK && threadIdx.x == 0) atomicMin(status, (unsigned long long)(b << 8 | (uint64_t)rc));
 }
 
-// usize, crc and the scanned offsets join the description
+// usize, crc and the scanned offsets join the description.  obase: where the first block's text begins in the text buffer (a
+// shard that begins inside its first block has that block's first bytes in the room in front of it: bgzf_shard_load)
 __global__ __launch_bounds__(256) void k_bgzf_desc(uint64_t nb, const uint64_t* __restrict__ coff, const uint32_t* __restrict__ csize,
                                                    const uint32_t* __restrict__ xlen, const uint32_t* __restrict__ usize,
-                                                   const uint32_t* __restrict__ crc, const uint64_t* __restrict__ ooff,
+                                                   const uint32_t* __restrict__ crc, const uint64_t* __restrict__ ooff, uint64_t obase,
                                                    BlockDesc* __restrict__ desc) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nb) return;
-    desc[i] = BlockDesc{coff[i], ooff[i], csize[i], xlen[i], usize[i], crc[i]};
+    desc[i] = BlockDesc{coff[i], obase + ooff[i], csize[i], xlen[i], usize[i], crc[i]};
 }
 
 // ---- host side
 
-std::string where(uint64_t block, uint64_t off) { return "libbsk: bgzf: block " + std::to_string(block) + " at offset " + std::to_string(off) + ": "; }
+// How a block is named in a refusal.  A whole file: its number and its offset.  A shard (bgzf_shard_load) that begins at the file
+// offset `base` > 0: its offset in the file, and its number counted from the shard's first block, said so
+struct Naming {
+    uint64_t base = 0;
+    bool whole() const { return base == 0; }
+};
+std::string where(const Naming& nm, uint64_t block, uint64_t off) {
+    if (nm.whole()) return "libbsk: bgzf: block " + std::to_string(block) + " at offset " + std::to_string(off) + ": ";
+    return "libbsk: bgzf: block at offset " + std::to_string(nm.base + off) + " (number " + std::to_string(block) + " from the shard's first block at offset " +
+           std::to_string(nm.base) + "): ";
+}
+constexpr uint64_t NO_JOIN = ~0ull;
 
 // The chain of blocks from offset 0.  fetch(off, len, dst) brings bytes of the file; known(off, &h) answers from the list of
 // k_bgzf_find where it can (a header whose only subfield is BC).  A header of any other shape is read through fetch.
+// join (a shard's walk): an offset the chain must pass through -- the block start the next worker begins at.  A chain that steps
+// over it began at, or ran through, something that is no block of the file: BSK_ERR_UNSUPPORTED, nothing is decoded
 template <class Fetch, class Known>
-int bgzf_walk(uint64_t n, Fetch fetch, Known known, BgzfIndex& ix, std::string& err) {
+int bgzf_walk(uint64_t n, Fetch fetch, Known known, BgzfIndex& ix, std::string& err, const Naming& nm = Naming(), uint64_t join = NO_JOIN) {
+    auto where = [&nm](uint64_t block, uint64_t off) { return bsk::where(nm, block, off); };
     std::vector<uint8_t> hdr;
     for (uint64_t off = 0; off < n;) {
         const uint64_t k = ix.coff.size();
@@ -195,12 +216,20 @@ int bgzf_walk(uint64_t n, Fetch fetch, Known known, BgzfIndex& ix, std::string& 
             }
             if (r == -1) { err = where(k, off) + "truncated: the file ends inside the block header"; return BSK_ERR_FORMAT; }
             if (r != 1) {
+                if (off == 0 && !nm.whole()) { err = where(k, off) + "the bytes there are not a block header"; return BSK_ERR_FORMAT; }
                 if (off == 0 && r == 2) { err = "libbsk: bgzf: the input is gzip but not BGZF: one gzip stream cannot be cut into independent blocks; recompress it with bgzip"; return BSK_ERR_UNSUPPORTED; }
                 if (off == 0) { err = "libbsk: bgzf: the input is not gzip"; return BSK_ERR_FORMAT; }
                 err = where(k, off) + "the bytes after the last block are not a block header"; return BSK_ERR_FORMAT;
             }
         }
         if (h.bsize < 12u + h.xlen + 8u) { err = where(k, off) + "BSIZE is smaller than the header and the trailer"; return BSK_ERR_FORMAT; }
+        if (join != NO_JOIN && off < join && off + h.bsize > join) {
+            err = "libbsk: bgzf: offset " + std::to_string(nm.base + join) + " of the file is not a block start: the blocks from offset " + std::to_string(nm.base) +
+                  " step over it (the block at " + std::to_string(nm.base + off) + " ends at " + std::to_string(nm.base + off + h.bsize) +
+                  "), so a cut of --devices was placed on bytes that only look like a block -- the data of a block holds a whole BGZF block; "
+                  "nothing was written: run the file on one device (--device N)";
+            return BSK_ERR_UNSUPPORTED;
+        }
         if (off + h.bsize > n) { err = where(k, off) + "truncated: BSIZE reaches past the end of the file"; return BSK_ERR_FORMAT; }
         ix.coff.push_back(off);
         ix.csize.push_back(h.bsize);
@@ -210,9 +239,9 @@ int bgzf_walk(uint64_t n, Fetch fetch, Known known, BgzfIndex& ix, std::string& 
     return BSK_OK;
 }
 
-int decode_error(const BgzfIndex& ix, uint64_t packed, std::string& err) {
+int decode_error(const BgzfIndex& ix, uint64_t packed, std::string& err, const Naming& nm = Naming()) {
     const uint64_t k = packed >> 8;
-    err = where(k, k < ix.coff.size() ? ix.coff[k] : 0) + bgzf::error_text((int)(packed & 255u));
+    err = where(nm, k, k < ix.coff.size() ? ix.coff[k] : 0) + bgzf::error_text((int)(packed & 255u));
     return BSK_ERR_FORMAT;
 }
 
@@ -249,16 +278,29 @@ uint32_t bgzf_crc_chunked(const uint8_t* data, uint32_t n, uint32_t chunk) {
     });
 }
 
-int bgzf_inflate_device(const void* d_comp_, size_t n, int device, void** d_text, size_t* n_text, BgzfIndex* index, bool index_only,
-                        std::string& err) {
+namespace {
+// What makes the buffer a shard of a file (bgzf_shard_load): d_comp[0] is the file's byte `base`, the text wanted begins `skip`
+// bytes into the first block and ends `uhi` bytes into the block at `join` (uhi == 0: in front of it), and the chain must pass
+// through `join`.  The text buffer then has BGZF_SHARD_FRONT bytes of room in front: *d_text is its base, the shard's first byte
+// lies at base + BGZF_SHARD_FRONT, and *n_text counts the shard's bytes
+struct Shard {
+    uint64_t base = 0, join = NO_JOIN;
+    uint32_t skip = 0, uhi = 0;
+};
+
+int inflate_device(const void* d_comp_, size_t n, int device, void** d_text, size_t* n_text, BgzfIndex* index, bool index_only, const Shard* sh,
+                   std::string& err) {
     if (d_text) *d_text = nullptr;
     if (n_text) *n_text = 0;
     if (const int rc = select_device(device, kBgzf, err)) return rc;
     BgzfIndex local;
     BgzfIndex& ix = index ? *index : local;
     ix = BgzfIndex();
+    Naming nm;
+    if (sh) nm.base = sh->base;
     if (n == 0) {
-        if (!index_only) CODEC_HIP(kBgzf, hipMalloc(d_text, 1));
+        if (sh && (sh->skip || sh->uhi)) { err = "libbsk: bgzf: the virtual offsets of the shard do not lie in its blocks"; return BSK_ERR_INVALID_ARG; }
+        if (!index_only) CODEC_HIP(kBgzf, hipMalloc(d_text, sh ? BGZF_SHARD_FRONT + 16 : 1));
         return BSK_OK;
     }
     const uint8_t* d_comp = (const uint8_t*)d_comp_;
@@ -307,7 +349,7 @@ int bgzf_inflate_device(const void* d_comp_, size_t n, int device, void** d_text
         return true;
     };
     auto fetch = [&](uint64_t off, uint32_t len, uint8_t* dst) { return hipMemcpy(dst, d_comp + off, len, hipMemcpyDeviceToHost) == hipSuccess; };
-    int rc = bgzf_walk(n, fetch, known, ix, err);
+    int rc = bgzf_walk(n, fetch, known, ix, err, nm, sh ? sh->join : NO_JOIN);
     if (rc != BSK_OK) return rc;
     const uint64_t nb = ix.coff.size();
     // ---- sizes and offsets
@@ -338,29 +380,99 @@ int bgzf_inflate_device(const void* d_comp_, size_t n, int device, void** d_text
         CODEC_HIP(kBgzf, hipMemcpy(&total, A + a_ooff + 8 * nb, 8, hipMemcpyDeviceToHost));
         CODEC_HIP(kBgzf, hipMemcpy(&status, d_status, 8, hipMemcpyDeviceToHost));
     }
-    if (status != clean) return decode_error(ix, status, err);
+    if (status != clean) return decode_error(ix, status, err, nm);
     if (index) {
         ix.usize.resize(nb);
         CODEC_HIP(kBgzf, hipMemcpy(ix.usize.data(), A + a_usize, 4 * nb, hipMemcpyDeviceToHost));
     }
     if (index_only) return BSK_OK;
-    // ---- the text
+    // ---- the text (of a shard: behind the room, trimmed to its virtual offsets)
+    uint64_t obase = 0, cut_front = 0, cut_back = 0;
+    if (sh) {
+        uint32_t first = 0, last = 0;
+        CODEC_HIP(kBgzf, hipMemcpy(&first, A + a_usize, 4, hipMemcpyDeviceToHost));
+        CODEC_HIP(kBgzf, hipMemcpy(&last, A + a_usize + 4 * (nb - 1), 4, hipMemcpyDeviceToHost));
+        const bool in_last = sh->uhi != 0;  // (the walk has seen to it that the last block is then the one at `join`)
+        if (sh->skip > first || (in_last && (ix.coff[nb - 1] != sh->join || sh->uhi > last)) || (uint64_t)sh->skip + (in_last ? last - sh->uhi : 0) > total) {
+            err = "libbsk: bgzf: the virtual offsets of the shard do not lie in the text of their blocks";
+            return BSK_ERR_INVALID_ARG;
+        }
+        cut_front = sh->skip;
+        cut_back = in_last ? last - sh->uhi : 0;
+        obase = BGZF_SHARD_FRONT - cut_front;
+    }
     DevBuf text;
-    CODEC_HIP(kBgzf, text.alloc(total));
+    if (!sh) {
+        CODEC_HIP(kBgzf, text.alloc(total));
+    } else if (text.alloc(BGZF_SHARD_FRONT + total + 16) != hipSuccess) {
+        (void)hipGetLastError();
+        err ="libbsk: bgzf: the shard's " + std::to_string(n) + " compressed bytes and its " + std::to_string(total) + " bytes of text do not fit the device side by side";
+        return BSK_ERR_CAPACITY;
+    }
     {
         CodecStage T("bgzf_inflate");
         hipLaunchKernelGGL(k_bgzf_desc, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, nullptr, nb, (const uint64_t*)(A + a_coff),
                            (const uint32_t*)(A + a_csize), (const uint32_t*)(A + a_xlen), (const uint32_t*)(A + a_usize),
-                           (const uint32_t*)(A + a_crc), (const uint64_t*)(A + a_ooff), (BlockDesc*)(A + a_desc));
+                           (const uint32_t*)(A + a_crc), (const uint64_t*)(A + a_ooff), obase, (BlockDesc*)(A + a_desc));
         hipLaunchKernelGGL(k_bgzf_inflate, dim3((unsigned)nb), dim3(64), 0, nullptr, d_comp, (uint64_t)n, (const BlockDesc*)(A + a_desc),
                            text.as<uint8_t>(), (const uint32_t*)(A + a_mat), d_status);
         CODEC_HIP(kBgzf, hipGetLastError());
         CODEC_HIP(kBgzf, hipMemcpy(&status, d_status, 8, hipMemcpyDeviceToHost));
     }
-    if (status != clean) return decode_error(ix, status, err);
+    if (status != clean) return decode_error(ix, status, err, nm);
     *d_text = text.p;
     text.p = nullptr;
-    *n_text = (size_t)total;
+    *n_text = (size_t)(total - cut_front - cut_back);
+    return BSK_OK;
+}
+}  // namespace
+
+int bgzf_inflate_device(const void* d_comp, size_t n, int device, void** d_text, size_t* n_text, BgzfIndex* index, bool index_only,
+                        std::string& err) {
+    return inflate_device(d_comp, n, device, d_text, n_text, index, index_only, nullptr, err);
+}
+
+int bgzf_shard_load(int fd, uint64_t voff_lo, uint64_t voff_hi, int device, int threads, void** d_base, void** d_text, size_t* n_text,
+                    std::string& err) {
+    *d_base = *d_text = nullptr;
+    *n_text = 0;
+    struct stat sb;
+    if (fd < 0 || fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) { err = "libbsk: bgzf: a shard is loaded from a regular file"; return BSK_ERR_INVALID_ARG; }
+    const uint64_t size = (uint64_t)sb.st_size, clo = voff_lo >> 16, chi = voff_hi >> 16;
+    Shard sh;
+    sh.base = clo;
+    sh.skip = (uint32_t)(voff_lo & 0xFFFFu);
+    sh.uhi = (uint32_t)(voff_hi & 0xFFFFu);
+    if (voff_hi < voff_lo || chi > size || (chi == size && sh.uhi)) { err = "libbsk: bgzf: bad virtual offsets of a shard"; return BSK_ERR_INVALID_ARG; }
+    // the compressed bytes: from the block of the first byte to the end of the block that holds the last one
+    uint64_t end = chi;
+    if (sh.uhi) {
+        std::vector<uint8_t> head((size_t)std::min<uint64_t>(size - chi, 65536));
+        size_t at = 0;
+        while (at < head.size()) {
+            const ssize_t k = pread(fd, head.data() + at, head.size() - at, (off_t)(chi + at));
+            if (k <= 0) { err = "libbsk: bgzf: reading the file failed"; return BSK_ERR_INVALID_ARG; }
+            at += (size_t)k;
+        }
+        bgzf::BlockHeader h{0, 0};
+        if (bgzf::parse_header(head.data(), head.size(), &h) != 1 || chi + h.bsize > size) {
+            err = "libbsk: bgzf: offset " + std::to_string(chi) + " of the file, where the shard's last block should begin, holds no whole block: "
+                  "the virtual offsets are not positions of this file";
+            return BSK_ERR_INVALID_ARG;
+        }
+        end = chi + h.bsize;
+    }
+    if (chi < size) sh.join = chi - clo;  // (the last worker's chain ends with the file, under the rules of any BGZF file)
+    const size_t n = (size_t)(end - clo);
+    void* d_comp = nullptr;
+    if (n) {
+        const int rc = bsk_shard_load(fd, clo, n, device, threads, &d_comp);
+        if (rc != BSK_OK) { err = bsk_global_error(); return rc; }
+    }
+    const int rc = inflate_device(d_comp, n, device, d_base, n_text, nullptr, false, &sh, err);
+    if (d_comp) (void)hipFree(d_comp);
+    if (rc != BSK_OK) return rc;
+    *d_text = (uint8_t*)*d_base + BGZF_SHARD_FRONT;
     return BSK_OK;
 }
 

@@ -17,6 +17,15 @@ struct BgzfIndex {
 // Every function returns a BSK_* code and leaves the text of a failure in `err`.
 // d_comp[0, n) in the memory of `device` -> a new buffer *d_text of *n_text bytes (hipFree).  index (may be null) receives the blocks.
 int bgzf_inflate_device(const void* d_comp, size_t n, int device, void** d_text, size_t* n_text, BgzfIndex* index, bool index_only, std::string& err);
+// A worker's shard of a BGZF file (PARITY.md BGZF "workers"): the text [voff_lo, voff_hi) of the open file `fd`, both virtual
+// offsets as bgzf_cuts.hpp names them.  The compressed bytes from coffset(voff_lo) to the end of the block that holds the last
+// byte come in by bsk_shard_load, the chain is walked from there and every block is written into place behind
+// BGZF_SHARD_FRONT bytes of room, so *d_text = *d_base + BGZF_SHARD_FRONT (a multiple of 256) is the shard's first byte and
+// there is no second copy; *d_base is what hipFree takes.  The chain must pass through coffset(voff_hi) -- the join check:
+// BSK_ERR_UNSUPPORTED where it steps over it.  The text does not fit next to the compressed bytes: BSK_ERR_CAPACITY
+constexpr size_t BGZF_SHARD_FRONT = 65536;
+int bgzf_shard_load(int fd, uint64_t voff_lo, uint64_t voff_hi, int device, int threads, void** d_base, void** d_text, size_t* n_text,
+                    std::string& err);
 // the same decoder on `threads` host threads.  cap == 0: only *n_out is set
 int bgzf_inflate_host(const void* comp, size_t n, void* out, size_t cap, size_t* n_out, int threads, std::string& err);
 // 0: not gzip, 1: BGZF, 2: gzip that is not BGZF

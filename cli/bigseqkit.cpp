@@ -318,7 +318,10 @@ int sniff_format(const std::string& file_, const std::string& data) {
 // offsets.  Without that switch every exit status and every byte of stderr is as before.
 // The paths for inputs that are not loaded whole read a BGZF file in pieces (bsk_bgzf_reader_*) only when asked to:
 // BSK_BGZF_STREAM=1.  Every pass over the input inflates the file again -- a bucket command reads it 2 + B times and more --, which
-// a user should choose knowingly; without the switch these paths refuse a compressed file as before, and the message names it
+// a user should choose knowingly; without the switch these paths refuse a compressed file as before, and the message names it.
+// --devices reads a BGZF file only under BSK_BGZF_DEVICES=1: the file is cut at block starts found near size * k / world and at
+// the record starts behind them (bsk_bgzf_cut_points), every worker inflates its own blocks (bsk_bgzf_shard_load), and a cut
+// that fell on bytes that only look like a block is refused by the worker whose chain steps over it, before anything is written
 
 // One input file of an invocation, looked at once (classify_inputs): the record goes to whoever opens the file.  kind is what
 // bsk_bgzf_probe says of its first bytes; a pipe is plain here: it is looked at once it has been read
@@ -364,7 +367,7 @@ static bool stats_streams(const std::string& use, size_t size) { return use == "
 //   HostText  the text of a file or a pipe on the host, inflated there (inflate_host_text)
 //   Device    a file that goes to the GPU whole (read_parts), or -- `stats` on a file that does not fit -- is streamed
 //   Buckets   the bucket paths (run_buckets), which read a file in pieces
-//   Devices   --devices, which cuts a file by its bytes
+//   Devices   --devices, which cuts a file by its bytes -- and a BGZF file by its blocks, when BSK_BGZF_DEVICES=1 asks for it
 // Returns whether a BGZF file may be read in pieces (BSK_BGZF_STREAM=1), and in *gzip_pieces whether a plain gzip file may
 // (BSK_GZIP=1 BSK_GZIP_STREAM=1: read here and nowhere else); the refusals of plain gzip come first, over all files
 enum class Route { Any, HostText, Device, Buckets, Devices };
@@ -375,6 +378,7 @@ bool admit(const std::vector<Input>& ins, Route route, const std::string& use = 
     static const char* const kStreamHint = ", or set BSK_BGZF_STREAM=1 to read it in record-aligned pieces, inflated once per pass";
     auto switch_on = [](const char* name) { const char* e = getenv(name); return e && *e && strcmp(e, "0") != 0; };
     const bool gzip = switch_on("BSK_GZIP"), pieces = switch_on("BSK_BGZF_STREAM"), segments = gzip && switch_on("BSK_GZIP_STREAM");
+    const bool shards = switch_on("BSK_BGZF_DEVICES");  // (a BGZF file under --devices: block-aligned cuts, a shard per worker)
     if (gzip_pieces) *gzip_pieces = segments;
     // the routes that read a file by its bytes or in pieces: what they do, and what to do about a BGZF file instead
     std::string gzip_where, bgzf_where, instead;
@@ -402,7 +406,7 @@ bool admit(const std::vector<Input>& ins, Route route, const std::string& use = 
                 "reads it only where a file is read whole; decompress it first (gzip -d), or recompress it with bgzip (gzip -dc FILE | bgzip > FILE.gz)");
     }
     for (auto& in : ins)
-        if (in.kind == kBgzf && by_bytes(in) && !(pieces && route != Route::Devices))
+        if (in.kind == kBgzf && by_bytes(in) && !(route == Route::Devices ? shards : pieces))
             die(in.path + " is BGZF-compressed, and " + bgzf_where + " a file by its bytes, which a compressed file does not allow yet; " + instead);
     return pieces;
 }
@@ -1860,7 +1864,12 @@ int run_devices(const Invocation& inv) {
     if (inv.files.size() != 1) die("--devices: exactly one input file (it is cut into one shard per GPU)");
     const std::vector<int> devices = parse_devices(inv.pget("devices"));
     const int world = (int)devices.size();
-    admit(classify_inputs(inv.files), Route::Devices);
+    const std::vector<Input> ins = classify_inputs(inv.files);
+    const bool admit_pieces = admit(ins, Route::Devices);  // (BSK_BGZF_STREAM=1: `stats` may read a worker's range in pieces)
+    // (admitted: BSK_BGZF_DEVICES=1) a BGZF file is cut at block starts near size * k / world, found from the file's bytes there,
+    // and at the first record start of the text behind them (bsk_bgzf_cut_points: PARITY.md BGZF "workers"); a worker's range is
+    // a pair of virtual offsets, its shard what bsk_bgzf_shard_load inflates of it -- from there on a device shard as any other
+    const bool bgzf_in = ins[0].kind == kBgzf;
     mark("start");
     if (bsk_device_count() <= 0) die("no HIP device visible (the hot path has no CPU fallback)");
     const std::string& path = inv.files[0];
@@ -1870,14 +1879,19 @@ int run_devices(const Invocation& inv) {
     if (fstat(fd, &sb) != 0) die("stat " + path + " failed");
     const size_t size = (size_t)sb.st_size;
     const uint8_t* map = nullptr;
-    if (size) {
+    if (size && !bgzf_in) {
         map = (const uint8_t*)mmap(nullptr, size, PROT_READ, MAP_SHARED, fd, 0);
         if (map == MAP_FAILED) die("mmap " + path + " failed");
     }
-    const int fmt = sniff_format(path, size ? std::string((const char*)map, 1) : std::string());
-    const std::vector<size_t> cuts = size ? cut_points(map, size, world, fmt) : std::vector<size_t>((size_t)world + 1, 0);
+    const int fmt = bgzf_in ? sniff_format(path, std::string(1, bgzf_first_text_byte(path))) : sniff_format(path, size ? std::string((const char*)map, 1) : std::string());
+    const std::vector<size_t> cuts = size && !bgzf_in ? cut_points(map, size, world, fmt) : std::vector<size_t>((size_t)world + 1, 0);
     if (map) munmap((void*)map, size);
     mark("device count + cut points");
+    std::vector<uint64_t> voffs((size_t)world + 1, 0);
+    if (bgzf_in) {
+        if (bsk_bgzf_cut_points(fd, fmt, world, voffs.data()) != BSK_OK) die(path + ": " + bsk_global_error());
+        mark("bgzf cut points");
+    }
     // RCCL greets on file descriptor 1 (its version banner, when a communicator is first used) -- and stdout is where
     // `stats`, `grep -C` and `-o -` put their RESULT.  For the rest of this call descriptor 1 IS stderr; results go to the
     // real stdout through a duplicate of it.
@@ -1919,13 +1933,17 @@ int run_devices(const Invocation& inv) {
         Worker& me = W[(size_t)rank];
         bsk_comm* comm = comms[(size_t)rank];
         const int device = devices[(size_t)rank];
-        const size_t lo = cuts[(size_t)rank], n = cuts[(size_t)rank + 1] - lo;
+        const size_t lo = cuts[(size_t)rank];
+        size_t n = cuts[(size_t)rank + 1] - lo;  // (a BGZF shard: its text, known once it is inflated)
+        const uint64_t v_lo = voffs[(size_t)rank], v_hi = voffs[(size_t)rank + 1];
+        // the compressed bytes of a BGZF shard, to the start of the next worker's first block (its own last block may add 64 KiB)
+        const size_t comp_n = bgzf_in ? (size_t)((v_hi >> 16) - (v_lo >> 16)) + ((v_hi & 0xFFFFu) ? 1 : 0) : 0;
         bsk_ctx* ctx = nullptr;
         void* d_shard = nullptr;
         void* h = nullptr;
         // stats: a shard that does not fit (or whose allocation fails) is streamed from the file in pinned pieces (below)
-        const bool stats_stream = use == "stats" && n > 0 && n >= std::min(host_pipeline_from * 4, whole_file_limit());
-        const bool via_host = streamed && n > host_pipeline_from;
+        const bool stats_stream = bgzf_in ? v_hi > v_lo && stats_streams(use, comp_n) : use == "stats" && n > 0 && n >= std::min(host_pipeline_from * 4, whole_file_limit());
+        const bool via_host = !bgzf_in && streamed && n > host_pipeline_from;
         bsk_store* own = nullptr;
         bool stream_stats = stats_stream;
         auto give_up = [&](const std::string& m) { if (me.error.empty()) me.error = m.empty() ? "failed" : m; failed.fetch_add(1); };
@@ -1937,6 +1955,28 @@ int run_devices(const Invocation& inv) {
             // A record operator whose shard AND output may not fit the GPU side by side keeps the chunked host pipeline
             // (bsk_run_to_store: pinned shard, 256 MiB chunks through two device buffers).
             if (stats_stream) break;
+            if (bgzf_in) {
+                // (v_hi == v_lo, an empty shard -- more workers than blocks, or one record over the whole range -- is loaded as well)
+                if (bsk_bgzf_shard_load(fd, v_lo, v_hi, device, 0, &d_shard, &n) != BSK_OK) {
+                    d_shard = nullptr;
+                    n = 0;
+                    const std::string why = bsk_global_error();
+                    // (the join check, a damaged block: said as it is.  No room: stats reads the range in pieces instead)
+                    const bool no_room = why.find("do not fit") != std::string::npos || why.find("allocation") != std::string::npos;
+                    if (use == "stats" && no_room) { stream_stats = true; break; }
+                    give_up(path + ": " + why + (no_room ? " -- '" + use + "' needs every worker's shard (" + std::to_string(comp_n) + " compressed bytes here) and its text in HBM: more devices make smaller shards" : std::string()));
+                    break;
+                }
+                mark("bgzf shard on the device", rank);
+                // the pipelined host path is not built for compressed shards: the line that sends a plain shard there refuses this one
+                if (use != "stats" && n > host_pipeline_from) {
+                    give_up(path + ": this worker's shard (" + std::to_string(comp_n) + " compressed bytes, " + std::to_string(n) + " bytes of text) is above the " +
+                            std::to_string(host_pipeline_from) + " bytes that '" + use + "' keeps on the device next to its result, and a compressed shard is not streamed through the host: "
+                            "more devices make smaller shards, or decompress the file first (bgzip -d)");
+                    break;
+                }
+                break;
+            }
             if (!via_host) {
                 if (bsk_shard_load(fd, (uint64_t)lo, n, device, 0, &d_shard) != BSK_OK) {
                     if (use == "stats") { d_shard = nullptr; stream_stats = true; break; }  // (no room: streamed below)
@@ -1955,13 +1995,49 @@ int run_devices(const Invocation& inv) {
         } while (false);
         // every worker enters every collective, also the one that has given up (its contribution is empty): the others must
         // not wait for it for ever
+        if (bgzf_in) {
+            // the barrier of the join check: every worker has loaded its shard and walked its chain before any operator runs, so
+            // a run that is refused there has written no part file, no spool and no table
+            if (me.error.empty() && stream_stats && !admit_pieces)
+                give_up(path + ": this worker's range (" + std::to_string(comp_n) + " compressed bytes) is not loaded whole; set BSK_BGZF_STREAM=1 to have 'stats' read it in "
+                        "record-aligned pieces, or use more devices: they make smaller shards");
+            uint64_t bad = (uint64_t)failed.load();
+            if (bsk_count_allreduce(comm, &bad, nullptr) != BSK_OK) { give_up(bsk_comm_error(comm)); bad = 1; }
+            if (bad) {
+                if (d_shard) bsk_device_free(d_shard);
+                if (ctx) bsk_destroy(ctx);
+                return;
+            }
+        }
         const bool ok0 = me.error.empty();
         if (use == "stats") {
             std::vector<int64_t> keys(1 << 20), vals(1 << 20);
             size_t cnt = 0;
             int rc = ok0 ? bsk_stats_reset(ctx, nullptr) : BSK_ERR_INVALID_ARG;
             if (rc == BSK_OK && n && !stream_stats) rc = bsk_stats_run(ctx, d_shard, n, 1, fmt, rank, nullptr, nullptr);
-            if (rc == BSK_OK && n && stream_stats) {
+            if (rc == BSK_OK && bgzf_in && stream_stats && v_hi > v_lo) {
+                // the worker's range through the piece reader on its device: seek, then piece after piece; the piece that would run
+                // past the next worker's start is asked for again by its offsets -- which also is this path's join check: an
+                // offset that is not on the reader's chain is no position of the text, and the reader says so
+                const BgzfSizes z = bgzf_sizes();
+                bsk_bgzf_reader* rd = nullptr;
+                rc = bsk_bgzf_reader_open(fd, device, fmt, z.piece, z.look, z.chunk, &rd);
+                if (rc == BSK_OK) rc = bsk_bgzf_reader_seek(rd, v_lo);
+                for (int64_t k = 0; rc == BSK_OK; ++k) {
+                    const void* p = nullptr;
+                    size_t pn = 0;
+                    uint64_t plo = 0, phi = 0;
+                    int last = 0;
+                    rc = bsk_bgzf_reader_next(rd, &p, &pn, &plo, &phi, &last);
+                    if (rc == BSK_OK && phi > v_hi) rc = bsk_bgzf_reader_piece(rd, plo, v_hi, &p, &pn);
+                    if (rc != BSK_OK) break;
+                    if (pn && bsk_stats_run(ctx, p, pn, 1, fmt, (int64_t)rank * 1000000 + k, nullptr, nullptr) != BSK_OK) { rc = BSK_ERR_INVALID_ARG; give_up(bsk_last_error(ctx)); break; }
+                    if (last || phi >= v_hi) break;
+                }
+                if (rc != BSK_OK && me.error.empty()) give_up(path + ": " + bsk_global_error());
+                if (rd) bsk_bgzf_reader_close(rd);
+                mark("bgzf range streamed in pieces", rank);
+            } else if (rc == BSK_OK && n && stream_stats) {
                 // Round 6: a shard larger than the GPU's memory (the reference takes any file size through its partitions,
                 // bigseqkit/helper.go:148-178).  Pieces of ~1 GiB that end on record starts are read into two pinned buffers
                 // -- the pread of piece i + 1 runs while piece i crosses PCIe under the kernels (bsk_stats_run with a host

@@ -266,6 +266,30 @@ int bsk_bgzf_reader_next(bsk_bgzf_reader* r, const void** ptr, size_t* n, uint64
 int bsk_bgzf_reader_seek(bsk_bgzf_reader* r, uint64_t voff);
 int bsk_bgzf_reader_piece(bsk_bgzf_reader* r, uint64_t voff_lo, uint64_t voff_hi, const void** ptr, size_t* n);
 void bsk_bgzf_reader_close(bsk_bgzf_reader* r);
+/* ---- BGZF under several workers (PARITY.md BGZF "workers"; bgzf_cuts.hpp, ops_bgzf.hip) ----
+ * BGZF blocks are independent, so a compressed file can be cut for `world` workers without decompressing it: worker k owns the
+ * text [voffs[k], voffs[k + 1]), virtual offsets as the reader's above (normalised; voffs[world] = size << 16).  The cut k lies
+ * at the first record start at or behind the text of B_k, the first block start at or behind size * k / world (not in front
+ * of B_{k-1}).  The chain from offset 0 is not walked: B_k is found from the block headers of the ~1 MiB in front of the
+ * nominal cut, tested by their BSIZE chain and a full decode (CRC32, ISIZE) of its blocks -- so the cuts are a function of the
+ * file and `world` alone.  A block whose DATA holds a whole valid block can mislead that test; the worker's own walk finds it
+ * out (the join check), so a wrong candidate costs time or an explicit refusal, never bytes.
+ *   bsk_bgzf_cut_points   voffs[0 .. world] of the open file `fd`.  Host only: no device is touched.  A file that is damaged at
+ *                         a cut: BSK_ERR_FORMAT, the offsets named
+ *   bsk_bgzf_shard_load   the text [voff_lo, voff_hi) in a NEW buffer on `device` (*d_text, *n_text; bsk_device_free).  The
+ *                         compressed bytes from coffset(voff_lo) to the end of the block that holds the last byte come in by
+ *                         bsk_shard_load (`threads` as there), are inflated as bsk_bgzf_load inflates a file, and freed.  Every
+ *                         block is written into place behind 64 KiB of room, so *d_text is a multiple of 256 and the text is
+ *                         not copied again; bsk_device_free knows the allocation behind *d_text.
+ *                         The join check: the chain from coffset(voff_lo) must pass through coffset(voff_hi) -- for
+ *                         voff_hi = size << 16 it ends with the file, under the rules of any BGZF file.  A chain that steps
+ *                         over it: BSK_ERR_UNSUPPORTED, the offset that is no block start named, nothing decoded.
+ *                         Refusals: those of BGZF input above; a shard that does not begin at offset 0 names a block by its
+ *                         offset in the file and numbers it from the shard's first block, and says so.  The compressed bytes
+ *                         and the text do not fit side by side: BSK_ERR_CAPACITY with both sizes.
+ * Errors: bsk_global_error(). */
+int bsk_bgzf_cut_points(int fd, int format, int world, uint64_t* voffs /* world + 1 */);
+int bsk_bgzf_shard_load(int fd, uint64_t voff_lo, uint64_t voff_hi, int device, int threads, void** d_text, size_t* n_text);
 /* Where the reader's kernel cuts text[0, n) (host memory) from `from`: bsk_find_record_start's answer, n where neither finds a
  * start, or ~0: declined, the host rule decides.  device = -1: the same function on the host.  For the tests. */
 int bsk_selftest_bgzf_stream_cut(const void* text, size_t n, size_t from, int format, int device, uint64_t* cut);
