@@ -11,7 +11,7 @@ from .options import (SeqKitConfig, SeqKitStatsOptions, SeqKitSeqOptions, SeqKit
                       SeqKitShuffleOptions, SeqKitHeadGenomeOptions)
 from .api import (SeqFrame, BgzfProbe, BgzfInflate, GzipInflate, GzipPlan, BgzfBlocks, BgzfReader, BgzfCutPoints, BgzfShardLoad,GzipReader, BgzfDeflate, BgzfDeflateHost, ReadSeqFile, WriteSeqFile, ReadFASTA, ReadFASTAN, ReadFASTQ, ReadFASTQN, Operator, Stats, StatsString,  # noqa: F401
                   stats_map, Seq, build_index, Grep, GrepCount, Subseq, Translate, RmDup, Locate, Fq2Fa, Range, Head,
-                  Duplicate, Count, Rename, Sort, Faidx, Pair, Common, Concat, FaidxQuery, Replace, Fa2Fq, Sample, Shuffle, ShuffleBuckets, ShuffleHistRun, ShuffleHistGet, ShuffleHistReset, ShufflePlan, ShuffleBucket, HeadGenome,
+                  Duplicate, Count, Rename, Sort, Faidx, Pair, Common, Concat, FaidxQuery, FaidxFetch, FaidxFetchPlan, BgzfGzi, Replace, Fa2Fq, Sample, Shuffle, ShuffleBuckets, ShuffleHistRun, ShuffleHistGet, ShuffleHistReset, ShufflePlan, ShuffleBucket, HeadGenome,
                   SortBuckets, SortBucketsPlan, SortBucket, SortSampleRun, SortSampleReset, SortSampleCount, SortPickSplitters, SortSplittersBuild,
                   SortSplittersSet, SortSplittersGet, SortHistRun, SortHistGet, SortHistReset,
                   RmDupBuckets, RmDupHistRun, RmDupHistGet, RmDupHistReset, RmDupVerdictBegin, RmDupVerdictGet, RmDupBucket, RmDupEmit,

@@ -132,6 +132,17 @@ SIGNATURES = {
     "bsk_common_run": (_i, [_vp, _vp, _sz, _p(C.c_uint64), C.c_uint32, _i, _i, _vp, _p(Out)]),
     "bsk_faidx_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp, _p(Out)]),
     "bsk_faidx_query_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, _vp, _p(Out)]),
+    "bsk_faidx_fetch_plan": (_i, [_vp, C.c_char_p, _sz, _u64, _i, _u64, _p(_vp)]),
+    "bsk_faidx_fetch_plan_free": (None, [_vp]),
+    "bsk_faidx_fetch_plan_counts": (_i, [_vp, _p(_u64)]),
+    "bsk_faidx_fetch_plan_hits": (_i, [_vp, _p(_u64), _sz]),
+    "bsk_faidx_fetch_plan_header": (_i, [_vp, _sz, _vp, _sz, _p(_sz)]),
+    "bsk_faidx_fetch_plan_batch": (_i, [_vp, _sz, _p(_u64), _p(_u64), _sz, _p(_sz)]),
+    "bsk_faidx_fetch_run": (_i, [_vp, _i, C.c_char_p, _sz, _vp, _sz, _i, _vp, _p(Out)]),
+    "bsk_faidx_fetch_host": (_i, [_vp, _i, C.c_char_p, _sz, _vp, _sz, _vp, _sz, _p(_sz)]),
+    "bsk_bgzf_gzi_build": (_i, [_i, _vp, _sz, _p(_sz), _p(_u64)]),
+    "bsk_bgzf_gzi_text_size": (_i, [_i, C.c_char_p, _sz, _p(_u64)]),
+    "bsk_faidx_fetch_info": (_i, [_vp, _p(_u64)]),
     "bsk_duplicate_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, _vp, _p(Out)]),
     "bsk_range_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp, _p(Out)]),
     "bsk_sample_run": (_i, [_vp, _vp, _sz, _i, _i, _i64, C.c_uint64, _vp, _p(Out)]),

@@ -776,6 +776,112 @@ def FaidxQuery(input, o, device=0):
     return _run_records("Faidx", lib.bsk_faidx_query_run, input, o, device)[0]
 
 
+class FaidxFetchPlan:
+    """The plan of `faidx -d` (bsk_faidx_fetch_plan; PARITY.md FAIX): the rows of an index `fai` (bytes), the regions of the
+    options `o` and the size of the sequence file -> hits in row order, and batches with the spans of the file they read.
+    Host only: device=-1 needs no GPU and nothing is read.  `op` is the Faidx operator the plan belongs to."""
+
+    def __init__(self, fai, o, file_size, device=-1, format=-1, budget=0):
+        self.op = Operator("Faidx", o.to_json(), device)
+        self.ptr = C.c_void_p()
+        try:
+            check(lib.bsk_faidx_fetch_plan(self.op.ctx, fai, len(fai), file_size, format, budget, C.byref(self.ptr)), self.op.ctx)
+            v = (C.c_uint64 * 8)()
+            check(lib.bsk_faidx_fetch_plan_counts(self.ptr, v))
+            self.rows, nh, nb, fq, self.T, self.read_bytes, self.out_bytes, self.alphabet_bytes = [int(x) for x in v]
+            self.fastq = bool(fq)
+            w = (C.c_uint64 * (8 * max(1, nh)))()
+            check(lib.bsk_faidx_fetch_plan_hits(self.ptr, w, nh))
+            self.hits = []
+            for k in range(nh):
+                row, p0, p1, minus, lo, hi, probe, out_len = [int(x) for x in w[8 * k:8 * k + 8]]
+                n = C.c_size_t()
+                buf = C.create_string_buffer(65536)
+                check(lib.bsk_faidx_fetch_plan_header(self.ptr, k, buf, len(buf), C.byref(n)))
+                self.hits.append(dict(row=row, p0=p0, p1=p1, minus=bool(minus), lines=(lo, hi), probe=probe, out_len=out_len,
+                                      header=buf.raw[:n.value]))
+            self.batches = []
+            for b in range(nb):
+                head, n = (C.c_uint64 * 4)(), C.c_size_t()
+                lib.bsk_faidx_fetch_plan_batch(self.ptr, b, head, None, 0, C.byref(n))
+                sp = (C.c_uint64 * (2 * max(1, n.value)))()
+                check(lib.bsk_faidx_fetch_plan_batch(self.ptr, b, head, sp, n.value, C.byref(n)))
+                self.batches.append(dict(hits=(int(head[0]), int(head[1])), read_bytes=int(head[2]), out_bytes=int(head[3]),
+                                         spans=[(int(sp[2 * k]), int(sp[2 * k + 1])) for k in range(n.value)]))
+        except Exception:
+            self.close()
+            raise
+
+    def close(self):
+        if self.ptr:
+            lib.bsk_faidx_fetch_plan_free(self.ptr)
+            self.ptr = C.c_void_p()
+        self.op.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def info(self):
+        """bsk_faidx_fetch_info: what the last fetch of the calling thread did"""
+        v = (C.c_uint64 * 8)()
+        check(lib.bsk_faidx_fetch_info(self.op.ctx, v), self.op.ctx)
+        return dict(hits=int(v[0]), spans=int(v[1]), bytes_read=int(v[2]), blocks_inflated=int(v[3]), T=int(v[4]), tiles=int(v[5]),
+                    bytes_written=int(v[6]))
+
+
+def BgzfGzi(path):
+    """The block table of a BGZF file by a header walk (bsk_bgzf_gzi_build: BSIZE and ISIZE of every block, no inflate) ->
+    (the image of FILE.gzi as htslib writes it, bytes of text)"""
+    import os
+    fd = os.open(path, os.O_RDONLY)
+    try:
+        n, text = C.c_size_t(), C.c_uint64()
+        lib.bsk_bgzf_gzi_build(fd, None, 0, C.byref(n), C.byref(text))
+        buf = C.create_string_buffer(max(1, n.value))
+        check(lib.bsk_bgzf_gzi_build(fd, buf, n.value, C.byref(n), C.byref(text)))
+        return buf.raw[:n.value], text.value
+    finally:
+        os.close(fd)
+
+
+def FaidxFetch(path, fai, o, device=0, gzi=None, host=False, budget=0, info=None):
+    """`faidx -d`: the regions of the options `o` fetched from the sequence file `path` through the index rows `fai` (bytes,
+    as Faidx wrote them for that file): the bytes of FaidxQuery on the whole file, the file never loaded whole.  gzi: `path`
+    is a BGZF file and gzi the image of its block table (BgzfGzi(path)[0], or the bytes of FILE.gzi); the rows' offsets are
+    text offsets.  host=True: the same source on one host lane (bsk_faidx_fetch_host; device=-1 then needs no GPU).  info: a
+    dict that takes the sums of bsk_faidx_fetch_info over the batches."""
+    import os
+    fd = os.open(path, os.O_RDONLY)
+    try:
+        size = os.fstat(fd).st_size
+        if gzi is not None:
+            t = C.c_uint64()
+            check(lib.bsk_bgzf_gzi_text_size(fd, gzi, len(gzi), C.byref(t)))
+            size = t.value
+        glen = len(gzi) if gzi is not None else 0
+        chunks = []
+        with FaidxFetchPlan(fai, o, size, device, -1, budget) as plan:
+            for b in range(len(plan.batches)):
+                if host:
+                    n = C.c_size_t()
+                    buf = C.create_string_buffer(max(1, plan.batches[b]["out_bytes"]))
+                    check(lib.bsk_faidx_fetch_host(plan.op.ctx, fd, gzi, glen, plan.ptr, b, buf, len(buf), C.byref(n)), plan.op.ctx)
+                    chunks.append(buf.raw[:n.value])
+                else:
+                    out = _lib.Out()
+                    check(lib.bsk_faidx_fetch_run(plan.op.ctx, fd, gzi, glen, plan.ptr, b, 0, None, C.byref(out)), plan.op.ctx)
+                    chunks.append(_out_bytes(plan.op, out))
+                if info is not None:
+                    for k, v in plan.info().items():
+                        info[k] = v if k == "T" else info.get(k, 0) + v
+        return b"".join(chunks)
+    finally:
+        os.close(fd)
+
+
 def Count(input, device=0):
     """input.Count(): records per shard (the record table of every shard is built once)"""
     counts = []

@@ -24,6 +24,7 @@
 #include "bgzf_stream.hpp"
 #include "gzip_stream.hpp"
 #include "codec_host.hpp"
+#include "fai_fetch.hpp"
 #include "ops_bgzf.hpp"
 #include "ops_bgzf_write.hpp"
 #include "ops_gzip.hpp"
@@ -2364,6 +2365,132 @@ int bsk_selftest_regex_find(const char* expr, const uint8_t* text, size_t n, siz
         fail_global(BSK_ERR_OPTS, e.what());
         return -1;
     }
+}
+
+// ---- faidx -d: regions through the index (include/bsk.h; fai_fetch.hpp plans, fai_fetch.cpp runs a batch)
+struct bsk_fai_plan { bsk::fai::Plan plan; };
+
+static int fai_ctx_check(const bsk_ctx* c, bool args_ok) {
+    if (!c || !args_ok) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: null argument");
+    if (c->op != Op::Faidx) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: not a Faidx context");
+    return BSK_OK;
+}
+
+int bsk_faidx_fetch_plan(bsk_ctx* c, const char* fai, size_t fai_len, uint64_t file_size, int format, uint64_t budget_bytes,
+                         bsk_fai_plan** plan) {
+    int rc = fai_ctx_check(c, (fai || !fai_len) && plan);
+    if (rc != BSK_OK) return rc;
+    *plan = nullptr;
+    bsk_call_scope scope(c);
+    if (!scope.owns) return fail_busy();
+    bsk_fai_plan* p = new (std::nothrow) bsk_fai_plan();
+    if (!p) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: out of memory");
+    rc = fai_plan_build(c, std::string(fai ? fai : "", fai_len), file_size, format, budget_bytes, &p->plan);
+    if (rc != BSK_OK) { delete p; g_error = c->last_error; return rc; }
+    *plan = p;
+    return BSK_OK;
+}
+
+void bsk_faidx_fetch_plan_free(bsk_fai_plan* plan) { delete plan; }
+
+int bsk_faidx_fetch_plan_counts(const bsk_fai_plan* plan, uint64_t out[8]) {
+    if (!plan || !out) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: null argument");
+    const fai::Plan& P = plan->plan;
+    uint64_t rd = 0, wr = 0;
+    for (const fai::Batch& b : P.batches) { rd += b.read_bytes; wr += b.out_bytes; }
+    bool minus = false;
+    for (const fai::Hit& h : P.hits) minus = minus || h.minus;
+    const uint64_t v[8] = {P.rows.size(), P.hits.size(), P.batches.size(), P.fastq ? 1u : 0u, fai::FETCH_T, rd, wr, minus ? P.alphabet_bytes : 0};
+    memcpy(out, v, sizeof v);
+    return BSK_OK;
+}
+
+int bsk_faidx_fetch_plan_hits(const bsk_fai_plan* plan, uint64_t* words, size_t cap_hits) {
+    if (!plan || (!words && cap_hits)) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: null argument");
+    const fai::Plan& P = plan->plan;
+    if (cap_hits < P.hits.size()) return fail_global(BSK_ERR_CAPACITY, "libbsk: bsk_faidx_fetch_plan_hits: room for fewer hits than the plan has");
+    for (size_t k = 0; k < P.hits.size(); ++k) {
+        const fai::Hit& h = P.hits[k];
+        const uint64_t v[8] = {h.row, h.p0, h.p1, h.minus ? 1u : 0u, h.lines.lo, h.lines.hi, h.probe, h.out_len};
+        memcpy(words + 8 * k, v, sizeof v);
+    }
+    return BSK_OK;
+}
+
+int bsk_faidx_fetch_plan_header(const bsk_fai_plan* plan, size_t hit, char* dst, size_t cap, size_t* len) {
+    if (!plan || !len || (!dst && cap)) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: null argument");
+    if (hit >= plan->plan.hits.size()) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bsk_faidx_fetch_plan_header: no such hit");
+    const std::string& h = plan->plan.hits[hit].header;
+    *len = h.size();
+    if (h.size() > cap) return fail_global(BSK_ERR_CAPACITY, "libbsk: output buffer too small");
+    memcpy(dst, h.data(), h.size());
+    return BSK_OK;
+}
+
+int bsk_faidx_fetch_plan_batch(const bsk_fai_plan* plan, size_t batch, uint64_t head[4], uint64_t* spans, size_t cap_spans, size_t* n_spans) {
+    if (!plan || !head || !n_spans || (!spans && cap_spans)) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: null argument");
+    if (batch >= plan->plan.batches.size()) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bsk_faidx_fetch_plan_batch: no such batch");
+    const fai::Batch& b = plan->plan.batches[batch];
+    head[0] = b.hit0; head[1] = b.hit1; head[2] = b.read_bytes; head[3] = b.out_bytes;
+    *n_spans = b.spans.size();
+    if (b.spans.size() > cap_spans) return fail_global(BSK_ERR_CAPACITY, "libbsk: bsk_faidx_fetch_plan_batch: room for fewer spans than the batch has");
+    for (size_t k = 0; k < b.spans.size(); ++k) { spans[2 * k] = b.spans[k].lo; spans[2 * k + 1] = b.spans[k].hi; }
+    return BSK_OK;
+}
+
+int bsk_faidx_fetch_run(bsk_ctx* c, int fd, const void* gzi, size_t gzi_len, const bsk_fai_plan* plan, size_t batch, int threads, void* stream,
+                        bsk_out* out) {
+    int rc = fai_ctx_check(c, plan && out && fd >= 0);
+    if (rc != BSK_OK) return rc;
+    if (c->device < 0) return fail(c, BSK_ERR_NO_DEVICE, "libbsk: context was created without a device");
+    out->d_data = nullptr; out->len = 0; out->records = 0;
+    out->d_seg_src = nullptr; out->d_seg_off = nullptr; out->n_segments = 0;
+    BSK_ENTER(c);
+    c->pend_out.kind = 0;
+    rc = clear_status(c, stream);
+    if (rc != BSK_OK) return rc;
+    rc = fai_fetch_device(c, fd, plan->plan, batch, threads, (hipStream_t)stream, out, gzi, gzi_len);
+    if (rc != BSK_OK) g_error = c->last_error;
+    return rc;
+}
+
+int bsk_faidx_fetch_host(bsk_ctx* c, int fd, const void* gzi, size_t gzi_len, const bsk_fai_plan* plan, size_t batch, void* dst, size_t cap,
+                         size_t* n_out) {
+    int rc = fai_ctx_check(c, plan && n_out && fd >= 0 && (dst || !cap));
+    if (rc != BSK_OK) return rc;
+    bsk_call_scope scope(c);
+    if (!scope.owns) return fail_busy();
+    std::string text;
+    rc = fai_fetch_host(c, fd, plan->plan, batch, &text, gzi, gzi_len);
+    if (rc != BSK_OK) { g_error = c->last_error; return rc; }
+    *n_out = text.size();
+    if (text.size() > cap) return fail(c, BSK_ERR_CAPACITY, "libbsk: output buffer too small");
+    if (!text.empty()) memcpy(dst, text.data(), text.size());
+    return BSK_OK;
+}
+
+int bsk_bgzf_gzi_build(int fd, void* dst, size_t cap, size_t* n_bytes, uint64_t* text_size) {
+    if (fd < 0 || !n_bytes || (!dst && cap)) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bgzf: bad arguments");
+    std::string image, err;
+    const int rc = fai_gzi_build(fd, &image, text_size, &err);
+    if (rc != BSK_OK) return fail_global(rc, err);
+    *n_bytes = image.size();
+    if (image.size() > cap) return fail_global(BSK_ERR_CAPACITY, "libbsk: output buffer too small");
+    memcpy(dst, image.data(), image.size());
+    return BSK_OK;
+}
+
+int bsk_bgzf_gzi_text_size(int fd, const void* gzi, size_t gzi_len, uint64_t* text_size) {
+    if (fd < 0 || !gzi || !text_size) return fail_global(BSK_ERR_INVALID_ARG, "libbsk: bgzf: bad arguments");
+    std::string err;
+    const int rc = fai_gzi_text_size(fd, gzi, gzi_len, text_size, &err);
+    return rc == BSK_OK ? rc : fail_global(rc, err);
+}
+
+int bsk_faidx_fetch_info(const bsk_ctx* c, uint64_t out[8]) {
+    if (!c || !out) return fail(c, BSK_ERR_INVALID_ARG, "libbsk: null argument");
+    fai_last_info(out);
+    return BSK_OK;
 }
 
 }  // extern "C"

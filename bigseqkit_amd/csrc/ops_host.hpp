@@ -151,6 +151,19 @@ int common_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, const uint64_t
                       hipStream_t st, bsk_out* out);
 int concat_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, size_t n_first, int format, hipStream_t st, bsk_out* out);
 int faidx_query_run_device(bsk_ctx* c, const uint8_t* d_buf, size_t n, int format, hipStream_t st, bsk_out* out);
+// faidx -d (fai_fetch.hpp / fai_fetch.cpp / ops_faidx_fetch.hip): the options of a Faidx context and the rows of an index -> a
+// plan; one batch of the plan read from fd and written on the device (`out` as faidx_query_run_device leaves it) / on one
+// host lane.  Every fetch leaves what it did with the calling thread (fai_last_info).
+namespace fai { struct Plan; }
+int fai_plan_build(bsk_ctx* c, const std::string& fai_text, uint64_t file_size, int format, uint64_t budget, fai::Plan* plan);
+// gzi != null: fd is a BGZF file, gzi its block table (.gzi image), the plan's offsets are text offsets
+int fai_fetch_device(bsk_ctx* c, int fd, const fai::Plan& plan, size_t batch, int threads, hipStream_t st, bsk_out* out, const void* gzi,
+                     size_t gzi_len);
+int fai_fetch_host(bsk_ctx* c, int fd, const fai::Plan& plan, size_t batch, std::string* text, const void* gzi, size_t gzi_len);
+// the block table of a BGZF file by a header walk (BSIZE and ISIZE of every block, no inflate), and the bytes of text a table describes
+int fai_gzi_build(int fd, std::string* image, uint64_t* text_size, std::string* err);
+int fai_gzi_text_size(int fd, const void* gzi, size_t gzi_len, uint64_t* text_size, std::string* err);
+void fai_last_info(uint64_t out[8]);
 void store_drainer_free(bsk_ctx* c);  // store.cpp
 int ensure_out(bsk_ctx* c, uint64_t bytes);
 int ensure_record_scratch(bsk_ctx* c);

@@ -552,6 +552,8 @@ void usage() {
     for (auto& c : kCommands) std::cout << "  " << c.use << "\n";
     std::cout << "\nGlobal flags: -t/--seq-type -w/--line-width --id-regexp --id-ncbi -o/--out-file --quiet\n"
                  "  --alphabet-guess-seq-length --infile-list --merge --partitions --order --device --dry-run\n"
+                 "faidx FILE REGION... -d IDX: with IDX present the regions are fetched through it and FILE is not loaded (plain, or BGZF\n"
+                 "  with its block table FILE.gzi, built where absent; the bytes are checked against the index); with IDX absent the run is the whole-file run and writes the index rows to IDX.\n"
                  "An -o name that ends in .gz or .bgz is written as BGZF (what bgzip writes), compressed on the GPU; any other name is plain text.\n";
 }
 
@@ -1169,6 +1171,77 @@ std::vector<Part> read_parts(const std::vector<Input>& inputs, int device = -1, 
     return parts;
 }
 
+// ---- faidx -d IDX (PARITY.md FAIX): regions fetched through the index, the sequence file never loaded whole
+const char* const kFaidxIndexInPipe =
+    "faidx: -d (--index-file) inside a 'pipe' job is refused: a job hands its input over as a dataframe on the device, the fetch "
+    "through an index reads a file; run 'faidx -d' as a command of its own";
+const char* const kFaidxIndexDevices =
+    "faidx: -d (--index-file) with --devices is refused: the fetch reads the few spans of the file that the regions name, on one "
+    "device (--device N)";
+
+// the regions of `inv` through the present index `idx`: the batches of the plan, in order, are the result
+Output run_faidx_fetch(const Invocation& inv, const Input& in, const std::string& idx) {
+    const std::string rows = read_file(idx);
+    const int fd = open(in.path.c_str(), O_RDONLY);
+    if (fd < 0) die("open " + in.path + ": no such file or directory");
+    // a BGZF file: the rows' offsets are text offsets, the block table FILE.gzi (htslib's format) turns them into blocks; where
+    // that file is absent the table is built by a header walk and written there
+    std::string gzi;
+    uint64_t size = in.size;
+    if (in.kind == kBgzf) {
+        const std::string gzi_path = in.path + ".gzi";
+        struct stat sb;
+        if (stat(gzi_path.c_str(), &sb) == 0) {
+            gzi = read_file(gzi_path);
+        } else {
+            size_t n = 0;
+            bsk_bgzf_gzi_build(fd, nullptr, 0, &n, nullptr);
+            gzi.assign(n, '\0');
+            if (bsk_bgzf_gzi_build(fd, &gzi[0], gzi.size(), &n, nullptr) != BSK_OK) die(bsk_global_error());
+            std::ofstream f(gzi_path, std::ios::binary);
+            if (f) { f.write(gzi.data(), (std::streamsize)gzi.size()); f.close(); }
+            if (!f && inv.pget("quiet") != "true")
+                std::cerr << "[INFO] the block table could not be written to " << gzi_path << ": it is built again by the next run\n";
+        }
+        if (bsk_bgzf_gzi_text_size(fd, gzi.data(), gzi.size(), &size) != BSK_OK) die(bsk_global_error());
+    }
+    bsk_ctx* c = nullptr;
+    const int device = (int)strtol(inv.pget("device").c_str(), nullptr, 10);
+    if (bsk_create("Faidx", inv.js.c_str(), device, &c) != BSK_OK) die(bsk_global_error());
+    bsk_fai_plan* plan = nullptr;
+    if (bsk_faidx_fetch_plan(c, rows.data(), rows.size(), size, -1, 0, &plan) != BSK_OK) die(bsk_last_error(c));
+    uint64_t counts[8];
+    bsk_faidx_fetch_plan_counts(plan, counts);
+    Output o;
+    o.fmt = BSK_FORMAT_FASTA;
+    o.packed = packs_on_device(inv);
+    for (uint64_t b = 0; b < counts[2]; ++b) {
+        bsk_out out;
+        if (bsk_faidx_fetch_run(c, fd, in.kind == kBgzf ? gzi.data() : nullptr, gzi.size(), plan, (size_t)b, 0, nullptr, &out) != BSK_OK) die(bsk_last_error(c));
+        append_result(c, out, o.text, o.packed);
+    }
+    bsk_faidx_fetch_plan_free(plan);
+    bsk_destroy(c);
+    close(fd);
+    return o;
+}
+
+// IDX was absent: the run was today's whole-file run, and the index rows of the file (-f honoured) go to IDX -- the intent of
+// StoreFASTX(idx, idxFile), bigseqkit-cli/faidx.go:29-32
+void write_faidx_index(const Invocation& inv, const Part& in, const std::string& idx) {
+    bsk_ctx* c = nullptr;
+    const int device = (int)strtol(inv.pget("device").c_str(), nullptr, 10);
+    if (bsk_create("Faidx", inv.js.c_str(), device, &c) != BSK_OK) die(bsk_global_error());
+    bsk_out out;
+    if (bsk_faidx_run(c, in.ptr(), in.size(), in.on_device(), in.fmt, 0, 0, nullptr, &out) != BSK_OK) die(bsk_last_error(c));
+    std::string rows;
+    append_result(c, out, rows, false);
+    bsk_destroy(c);
+    std::ofstream f(idx, std::ios::binary);
+    if (f) { f.write(rows.data(), (std::streamsize)rows.size()); f.close(); }
+    if (!f) die("write " + idx + " failed");
+}
+
 // `pipe` job (bigseqkit-cli/pipe.go:12-40): {"pipe": [job, ...], "cmd": ["grep", "-s", ...]} -- the outputs of the
 // jobs under "pipe" become inputs of "cmd", ahead of the files named in it.  ("sh" hooks are not run.)
 Output run_job(const bsk::json::Value& j, bool root) {
@@ -1186,6 +1259,9 @@ Output run_job(const bsk::json::Value& j, bool root) {
     std::vector<std::string> args;
     for (auto& a : cmd->arr) args.push_back(a->str);
     Invocation inv = parse_invocation(args);
+    // (-d applies to a run with regions only: in a job they come with -l, or as arguments behind the file)
+    if (std::string(inv.cmd->use) == "faidx" && !inv.pget("index-file").empty() && (!inv.pget("region-file").empty() || inv.files.size() > 1))
+        die(kFaidxIndexInPipe);
     for (auto& p : read_parts(classify_inputs(inv.files), (int)strtol(inv.pget("device").c_str(), nullptr, 10), inv.cmd->use)) inputs.push_back(std::move(p));
     if (inputs.empty()) die("no input for job command " + args[0]);
     Output o = execute(inv, inputs, !root);
@@ -2335,16 +2411,36 @@ static int run_main(int argc, char** argv) {
     if (std::string(inv.cmd->use) == "head-genome" && !inv.pget("devices").empty())
         die("'head-genome' runs on one device (bigseqkit head-genome ... --device N): the cut is sequential over the whole input, "
             "a worker could not judge its shard before the shards in front of it are done, so --devices is refused");
+    // faidx -d IDX applies to a run with regions only (PARITY.md FAIX); what it refuses is decided here, on the flags
+    const std::string faidx_idx = faidx_query ? inv.pget("index-file") : std::string();
+    if (!faidx_idx.empty() && !inv.pget("devices").empty()) die(kFaidxIndexDevices);
     if (!inv.pget("devices").empty()) return run_devices(inv);  // several GPUs: worker threads + librccl, in this process
     if (inv.files.empty()) die("no input files (stdin is not supported by the IgnisHPC CLI either)");
     const std::vector<Input> ins = classify_inputs(inv.files);
     admit(ins, Route::Any);  // (gzip that is not BGZF is read by no path without the switch: said before a device is touched)
     g_faidx_query = faidx_query;
+    bool faidx_idx_present = false;
+    if (!faidx_idx.empty()) {
+        if (ins[0].kind == kGzip)
+            die(ins[0].path + " is gzip but not BGZF: faidx -d addresses bases by their offsets, and a gzip stream has none to enter at; "
+                "recompress it with bgzip (gzip -dc FILE | bgzip > FILE.gz), or run without -d");
+        struct stat sb;
+        faidx_idx_present = stat(faidx_idx.c_str(), &sb) == 0;
+        if (faidx_idx_present && (inv.val.scalar.count("id-regexp") || inv.pget("id-ncbi") == "true"))
+            die("faidx: -d with the present index " + faidx_idx + " and --id-regexp / --id-ncbi is refused: the names of an index are those of the "
+                "default ID rule and cannot restate another one; run without -d");
+        if (faidx_idx_present && !ins[0].regular) die("faidx: -d needs a file it can read at offsets: " + ins[0].path);
+    }
     const std::string use_cmd = inv.cmd->use;
     const bool joins_on_host = use_cmd == "concat" || use_cmd == "common" || use_cmd == "pair";
     if (!joins_on_host && bsk_device_count() <= 0) die("no HIP device visible (the hot path has no CPU fallback)");
     if (use_cmd == "head-genome") {
         Output o = run_head_genome(inv);
+        store(inv, o, inv.files);
+        return 0;
+    }
+    if (faidx_idx_present) {
+        Output o = run_faidx_fetch(inv, ins[0], faidx_idx);
         store(inv, o, inv.files);
         return 0;
     }
@@ -2451,6 +2547,7 @@ static int run_main(int argc, char** argv) {
         return 0;
     }
     Output o = execute(inv, inputs, false);
+    if (!faidx_idx.empty() && !inputs.empty()) write_faidx_index(inv, inputs[0], faidx_idx);
     store(inv, o, inv.files);
     return 0;
 }

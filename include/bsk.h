@@ -506,6 +506,55 @@ int bsk_faidx_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int 
 int bsk_faidx_query_run(bsk_ctx* ctx, const void* shard, size_t n, int on_device, int format, int64_t pid, void* stream,
                         bsk_out* out);
 
+/* ---- faidx -d: the same regions fetched THROUGH an index, the sequence file never loaded whole (PARITY.md FAIX).  With
+ * the rows bsk_faidx_run wrote for the file, the batches of a plan, in order, are the bytes of bsk_faidx_query_run on the
+ * whole file as one shard.  The context is a Faidx context with regions (Regions / RegionFile / UseRegexp); --id-regexp and
+ * --id-ncbi cannot be restated from an index and are BSK_ERR_OPTS here.
+ *   bsk_faidx_fetch_plan   host only, no file behind it: `fai` = the text of the index (5 columns, or 6 for FASTQ: format 0 / 1,
+ *                          -1 = told from the first row), file_size = bytes of the sequence file, budget_bytes = what one batch may
+ *                          read and write together (0: BSK_FAIDX_FETCH_BYTES, else 1 GiB).  A row that cannot be used is
+ *                          BSK_ERR_FORMAT naming the row; one region above the budget is BSK_ERR_CAPACITY with the sizes.
+ *   ..._plan_counts        out[0..7] = rows, hits, batches, 1 for a FASTQ index, bases of a tile (T), bytes the batches read,
+ *                          bytes they write, bytes at the head of the file read for the alphabet of '-' regions (0: none)
+ *   ..._plan_hits          8 words per hit, row order: row (0-based), p0, p1 (the region, 0-based half-open), 1 for '-',
+ *                          the first and one past the last file byte of its lines, the offset of its end probe, output bytes
+ *   ..._plan_header        the hit's ">name[:b-e]\n"
+ *   ..._plan_batch         head[0..3] = first hit, one past the last, bytes read, bytes written; spans[2k], spans[2k + 1] = the
+ *                          merged 4 KiB-rounded ranges of the file it reads (cap_spans pairs; *n_spans is the number it has)
+ *   bsk_faidx_fetch_run    one batch: pread of its spans (threads <= 0: 4) into pinned memory, one copy, the fetch kernel.
+ *                          `out` as bsk_faidx_query_run leaves it, valid until the context's next call.  Bytes that are not
+ *                          what the index predicts (every byte of every line read is judged, and two bytes behind every hit
+ *                          record's predicted end): BSK_ERR_FORMAT naming row and file offset.
+ *   bsk_faidx_fetch_host   the same bytes from the same source on one host lane; needs no device.  *n_out is what the batch
+ *                          needs, also when `cap` is too small (BSK_ERR_CAPACITY).
+ *   BGZF                   gzi != NULL: fd is a BGZF file and gzi the image of its block table (htslib's .gzi: little-endian uint64
+ *                          count, then compressed offset and text offset of every block behind the first); the plan was made with
+ *                          file_size = the bytes of TEXT (bsk_bgzf_gzi_text_size) and the rows' offsets are text offsets.  Every
+ *                          merged span becomes a run of whole blocks: on the device through the range load of bsk_bgzf_shard_load
+ *                          (every refusal of PARITY BGZF, CRC included), on the host through the host lane.  An entry that does not
+ *                          land on a block header, or whose block contradicts the next entry, on a block that is touched:
+ *                          BSK_ERR_FORMAT naming the entry; entries of blocks that are not touched are not looked at.
+ *   bsk_bgzf_gzi_build     the image of the table by a header walk (BSIZE and ISIZE of every block, no inflate); *n_bytes is what it
+ *                          needs, also when cap is too small (BSK_ERR_CAPACITY); *text_size (may be NULL) the bytes of text
+ *   bsk_faidx_fetch_info   of the calling thread's last fetch (as bsk_gzip_last_plan): out[0..7] = hits, merged spans, bytes read from the file, BGZF blocks
+ *                          inflated (0: a plain file; whole blocks, a block counts once per span it serves), T, tiles, bytes written, 0 */
+typedef struct bsk_fai_plan bsk_fai_plan;
+int bsk_faidx_fetch_plan(bsk_ctx* ctx, const char* fai, size_t fai_len, uint64_t file_size, int format, uint64_t budget_bytes,
+                         bsk_fai_plan** plan);
+void bsk_faidx_fetch_plan_free(bsk_fai_plan* plan);
+int bsk_faidx_fetch_plan_counts(const bsk_fai_plan* plan, uint64_t out[8]);
+int bsk_faidx_fetch_plan_hits(const bsk_fai_plan* plan, uint64_t* words, size_t cap_hits);
+int bsk_faidx_fetch_plan_header(const bsk_fai_plan* plan, size_t hit, char* dst, size_t cap, size_t* len);
+int bsk_faidx_fetch_plan_batch(const bsk_fai_plan* plan, size_t batch, uint64_t head[4], uint64_t* spans, size_t cap_spans,
+                               size_t* n_spans);
+int bsk_faidx_fetch_run(bsk_ctx* ctx, int fd, const void* gzi, size_t gzi_len, const bsk_fai_plan* plan, size_t batch, int threads,
+                        void* stream, bsk_out* out);
+int bsk_faidx_fetch_host(bsk_ctx* ctx, int fd, const void* gzi, size_t gzi_len, const bsk_fai_plan* plan, size_t batch, void* dst,
+                         size_t cap, size_t* n_out);
+int bsk_bgzf_gzi_build(int fd, void* dst, size_t cap, size_t* n_bytes, uint64_t* text_size);
+int bsk_bgzf_gzi_text_size(int fd, const void* gzi, size_t gzi_len, uint64_t* text_size);
+int bsk_faidx_fetch_info(const bsk_ctx* ctx, uint64_t out[8]);
+
 /* ---- Sort (bigseqkit/sort.go:91-147; SortParseInputString / SortParseInputInt + SortByKey, bigseqkit-lib/sort.go):
  * by ID (default), full name (ByName), sequence prefix (BySeq, SeqPrefixLength), length (ByLength) or non-gap bases
  * (ByBases); IgnoreCase, Reverse.  Records with equal keys keep file order.  Global: ONE call sees the whole input of
